@@ -109,7 +109,13 @@ def parse_args():
     ap.add_argument("--tp-steps", type=int, default=0, help="timed steps of each tp_70b figure (0 = min(--steps, 30))")
     ap.add_argument("--tp-timeout", type=float, default=float(os.environ.get("QPAL_TP_TIMEOUT", "300")),
                     help="seconds after which the tp_70b leg is abandoned (the headline line is printed without it)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step as DIR/out_<i>.npy (float32, in the "
+                         "order the token returns them; rank 0; a fixed seeded sample of each when all of them exceed 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(n):
@@ -248,6 +254,28 @@ KINDS = ["q|k|v", "o", "gate|up", "down"]  # the four dependent multi-job launch
 def _kind_on(only_kind, gi):
     """only_kind: None (every launch kind), one kind index, or a collection of them"""
     return only_kind is None or (gi in only_kind if hasattr(only_kind, "__contains__") else only_kind == gi)
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: all files together, headers included
+
+
+def dump_outputs(torch, outs, dirname):
+    """--dump-outputs: the tensors one timed token returned, as DIR/out_<i>.npy in float32 (index = position in the token's output
+    list).  Up to DUMP_BYTES the arrays keep their shapes; above, every output is cut to the same share of its elements, drawn
+    from a fixed seed (sorted flat indices, the same in every run with the same arguments) and stored flat."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    header = 256  # bound of one .npy header
+    total = sum(t.numel() for t in outs)
+    frac = min(1.0, (DUMP_BYTES - header * len(outs)) / 4 / max(total, 1))
+    rng = np.random.default_rng(20240615)
+    for i, t in enumerate(outs):
+        a = t.detach().float()
+        if frac < 1.0:
+            idx = np.sort(rng.choice(a.numel(), int(a.numel() * frac), replace=False))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(dirname, f"out_{i:03d}.npy"), a.cpu().numpy())
 
 
 def make_token(qp, torch, layers, xs, n, device, launch="multi", no_prezero=False, gather=None, side=(), main_stream=None,
@@ -813,14 +841,19 @@ def main():
         return token_incoherent() if args.incoherent else plain_token()
 
     graph = None
+    last = [None]  # the outputs of the latest token: the graph's own buffers when replayed, refreshed by every eager call
     with torch.cuda.stream(main_stream):
         token()  # registers ops, sizes the allocator
         torch.cuda.synchronize()
         if not args.no_graph and (not tp or isinstance(gather, qp.shard.PeerGatherer)):
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=main_stream):
-                token()
-        run = graph.replay if graph is not None else token
+                last[0] = token()
+        if graph is not None:
+            run = graph.replay
+        else:
+            def run():
+                last[0] = token()
 
         def sync_all():
             torch.cuda.synchronize()
@@ -840,6 +873,8 @@ def main():
         sync_all()
         wall = time.perf_counter() - t0
         dev_s = e0.elapsed_time(e1) / 1e3
+        if args.dump_outputs and rank == 0:  # before any later leg runs on the device
+            dump_outputs(torch, last[0], args.dump_outputs)
 
     # Per launch kind (N = 1, multi-job launches, after the timed region): the four dependent launches of a block timed one
     # kind at a time — 32 launches of that kind, each with its in-token arguments, as one graph — so that the launch

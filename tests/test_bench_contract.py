@@ -156,3 +156,60 @@ def test_headline_line_survives_an_abandoned_tp_leg():
     r = subprocess.run(cmd + ["--lenient-exit"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     assert len([l for l in r.stdout.splitlines() if l.startswith("{")]) == 1
+
+
+def test_dump_outputs_keeps_shapes_or_samples_under_the_cap(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): float32 files in the token's output order; above the cap a fixed seeded sample of
+    every output, the same elements in every run, all files together within the cap."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(5)
+    outs = [torch.randn(2, 96, generator=g), torch.randn(2, 32, generator=g).half()]
+    bench.dump_outputs(torch, outs, str(tmp_path / "all"))
+    got = [np.load(tmp_path / "all" / f"out_{i:03d}.npy") for i in range(2)]
+    assert [a.dtype for a in got] == [np.float32, np.float32] and [a.shape for a in got] == [(2, 96), (2, 32)]
+    assert np.array_equal(got[0], outs[0].numpy()) and np.array_equal(got[1], outs[1].float().numpy())
+    cap = 2 * 256 + 4 * 64  # two header bounds + 64 of the 256 float32 elements
+    monkeypatch.setattr(bench, "DUMP_BYTES", cap)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(torch, outs, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == ["out_000.npy", "out_001.npy"]
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= cap
+    s1 = [np.load(tmp_path / "s1" / f) for f in files]
+    s2 = [np.load(tmp_path / "s2" / f) for f in files]
+    assert [a.size for a in s1] == [48, 16] and all(np.array_equal(a, b) for a, b in zip(s1, s2))
+    for a, t in zip(s1, outs):  # every sampled value is one of the output's own elements
+        assert np.isin(a, t.float().numpy().ravel()).all()
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_timed_token(tmp_path):
+    """`bench.py --dump-outputs DIR`: after the timed steps, the outputs of the last timed token (one per quantized linear of the
+    2-layer model, model order) as float32 .npy; the same arguments give the same inputs, so two runs agree up to the
+    summation order of split-K atomics.  --steps sets the number of timed steps the line reports."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import subprocess
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    dumps = []
+    for run in ("a", "b"):
+        d_ = tmp_path / run
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--layers", "2",
+               "--no-cpu-baseline", "--no-other-configs", "--no-whole-model", "--no-incoherent-extra", "--no-kind-breakdown",
+               "--no-calibration", "--dump-outputs", str(d_)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        dumps.append([np.load(d_ / f) for f in sorted(os.listdir(d_))])
+    a, b = dumps
+    # q, k, v, o, gate, up, down of each of the 2 layers (Llama-3.1-8B widths), batch 1
+    assert [x.shape for x in a] == [(1, m) for m in (4096, 1024, 1024, 4096, 14336, 14336, 4096)] * 2
+    for x, y in zip(a, b):
+        assert x.dtype == np.float32 and np.isfinite(x).all() and np.abs(x).max() > 0
+        assert np.allclose(x, y, rtol=1e-4, atol=1e-5 * np.abs(x).max())
