@@ -208,6 +208,22 @@ int qpal_pack_tcq_states(void *dst, const uint16_t *states, int m, int k, int KV
 int qpal_pack_lut_tc(void *dst, const int32_t *idx, int m, int k, int bits, int vec);
 int qpal_pack_lut_simt(void *dst, const int32_t *idx, int m, int k, int bits, int vec);
 
+/* TCQ encoder (the quantiser's inner loop): tail-biting Viterbi search of the bitshift trellis, L = 16, V = 2, on B independent
+ * sequences of 256 values; bit for bit bitshift_codebook(L=16, KV, V=2, tlut_bits=S, decode_mode="quantlut_sym",
+ * tlut=tlut16.float()).quantize(X), lib/codebook/bitshift.py:202-294.  DEVICE pointers:
+ *   x_f16    fp16 [B][256]: the input ROUNDED TO FP16 (the reference's quantize() does X.to(float16) first), widened to fp32
+ *   tlut_f16 fp16 [2^S][2]: the codebook QTIPLinearTCQ.tlut stores
+ *   states   int32 [B][128]: the trellis states of the chosen tail-biting walk (the reference's state.T)
+ *   hat      fp16 [B][256] or NULL: the reconstruction of states, element 2t + v = pair v of state t (exact in fp16)
+ *   ws       qpal_tcq_viterbi_ws_bytes(KV) bytes of device memory, 8-byte aligned, no initialisation; independent of B
+ * S in 9..11, KV in 2..10.  Per-state error (r0 - x0)^2 + (r1 - x1)^2 in fp32, each square rounded, no fused multiply-add; cost
+ * = error + best predecessor cost in fp32.  Ties: the predecessor with the lowest d (p = g + (d << (16 - KV))) and, at the end, the
+ * lowest state — what CPU torch.min / torch.argmin return.  Argument errors return before any stream work; one launch on `stream`,
+ * no synchronisation (graph-capturable).                                                                                   */
+long qpal_tcq_viterbi_ws_bytes(int KV);
+int qpal_tcq_viterbi(int32_t *states, void *hat_or_null, const void *x_f16, const void *tlut_f16, int B, int S, int KV, void *ws,
+                     void *stream);
+
 /* One-shot all-gather of a small activation slice across the GPUs of a node by direct peer writes over xGMI (SURVEY.md §8e;
  * no counterpart in the reference, which has no multi-GPU code): rank `rank` stores `bytes` bytes from src into
  * peer_bufs[p] + rank * bytes for every p and raises a flag in peer_ws[p]; the call returns (in stream order) when all

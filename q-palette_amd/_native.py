@@ -69,6 +69,8 @@ _SIGNATURES = {
     "qpal_ipc_close": [_P],
     "qpal_calib_stream_read": [ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_long), _I, _P, _I, _P],
     "qpal_calib_decode_rate": [_P, _P, _I, _I, _I, _I, _P],
+    "qpal_tcq_viterbi": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
+    "qpal_tcq_viterbi_ws_bytes": [_I],
 }
 
 
@@ -102,6 +104,7 @@ def lib():
         l.qpal_version.restype = _I
         l.qpal_attn_ws_bytes.restype = ctypes.c_long
         l.qpal_lm_head_ws_bytes.restype = ctypes.c_long
+        l.qpal_tcq_viterbi_ws_bytes.restype = ctypes.c_long
         _lib = l
     return _lib
 
