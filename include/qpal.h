@@ -224,6 +224,25 @@ long qpal_tcq_viterbi_ws_bytes(int KV);
 int qpal_tcq_viterbi(int32_t *states, void *hat_or_null, const void *x_f16, const void *tlut_f16, int B, int S, int KV, void *ws,
                      void *stream);
 
+/* VQ / SQ encoder (the fixed-codebook LDLQ quantiser's inner loop): the nearest codeword of every vec-group of m rows of `cols`
+ * values, vq_codebook(vec, bits).quantize (lib/codebook/vq_codebook.py), optionally with the in-block error feedback of LDLQ_VQ
+ * (lib/algo/ldlq.py).  DEVICE pointers; every fp64 matrix has row stride `ld` (elements):
+ *   idx      int32 [m][ld / vec]: the chosen codeword of group g of row r at idx[r * (ld / vec) + g], g < cols / vec
+ *   hat      fp64 [m][ld] or NULL: the chosen codewords (fp32 widened)
+ *   w        fp64 [m][ld]: the weights of the column block
+ *   prod     fp64 [m][ld] or NULL: LDLQ's feedback from the blocks to the right (needs lt)
+ *   lt       fp64 or NULL: the cols x cols diagonal block of the unit block-lower LDL factor (diagonal zeroed), COLUMN-major:
+ *            L[e][c] at lt[c * ld_l + e]
+ *   lut      fp32 [2^bits][vec]: the codebook
+ * Without lt every group takes its nearest codeword on its own (target = w).  With lt the groups of a row run from the last to
+ * the first and group i's target is (w_i + sum_{e in later groups} L[e][i] (w_e - hat_e)) + prod_i — LDLQ_VQ's WXWX; the
+ * feedback uses w - hat, not the target, so prod is a separate input.  Distance sum_v fl((t_v - c_v)^2) in fp64 without fused
+ * multiply-add; ties go to the lowest index (CPU torch.argmin).  vec in {1, 2, 4}, bits 1..12, cols % vec == 0, ld >= cols,
+ * ld % vec == 0, with lt cols <= 128 and ld_l >= cols.  Argument errors return before any stream work; one launch on `stream`,
+ * no synchronisation, no workspace.                                                                                         */
+int qpal_vq_encode(int32_t *idx, double *hat_or_null, const double *w, const double *prod_or_null, const double *lt_or_null, int ld,
+                   int ld_l, const float *lut, int m, int cols, int bits, int vec, void *stream);
+
 /* One-shot all-gather of a small activation slice across the GPUs of a node by direct peer writes over xGMI (SURVEY.md §8e;
  * no counterpart in the reference, which has no multi-GPU code): rank `rank` stores `bytes` bytes from src into
  * peer_bufs[p] + rank * bytes for every p and raises a flag in peer_ws[p]; the call returns (in stream order) when all

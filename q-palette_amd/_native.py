@@ -71,6 +71,7 @@ _SIGNATURES = {
     "qpal_calib_decode_rate": [_P, _P, _I, _I, _I, _I, _P],
     "qpal_tcq_viterbi": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
     "qpal_tcq_viterbi_ws_bytes": [_I],
+    "qpal_vq_encode": [_P, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P],
 }
 
 
