@@ -17,6 +17,13 @@ row-shards every linear over the ranks and all-gathers the activations over RCCL
 Prints ONE JSON line (rank 0).  roofline: HBM-bound; achieved = algorithmic bytes per token (packed
 weights + codebooks + x + out of every linear) / measured time per token, per GPU,
 timed with HIP events on the launch stream; per-launch figures = per-token / 224.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line.
+`--full` adds, after the timed steps, every other figure the line can carry: per-launch-kind times and the calibration
+block of the roofline, the token behind the incoherence wrapper, the whole-model decode step, the other BASELINE configs,
+the CPU baseline and, N > 1, the row-sharded 70B leg (`tp_70b`).
+
+    python bench.py --full
 """
 import argparse
 import json
@@ -78,14 +85,19 @@ def parse_args():
     ap.add_argument("--packing", default="qdict", choices=["qdict", "mi355x"],
                     help="qdict workloads: tensor-core-order vs SIMT packing of the VQ/SQ layers as published (chosen from the "
                          "reference's RTX 4090 latency table) or re-chosen from this GPU's table (perf/latency/)")
-    ap.add_argument("--no-kind-breakdown", action="store_true", help="skip the per-launch-kind timing of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also measure every other figure of the line: per-launch-kind times, the "
+                         "roofline's calibration block, the token behind the incoherence wrapper, the whole-model decode step, "
+                         "`other_configs`, the CPU baseline and (N > 1) the tp_70b leg; the --no-* switches below skip one of them.  "
+                         "Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the headline line")
+    ap.add_argument("--no-kind-breakdown", action="store_true", help="--full: skip the per-launch-kind timing")
     ap.add_argument("--no-calibration", action="store_true",
-                    help="skip the calibration block of the roofline (measured stream ceiling, stream token, decode floor)")
+                    help="--full: skip the calibration block of the roofline (measured stream ceiling, stream token, decode floor)")
     ap.add_argument("--no-swiglu-epilogue", action="store_true",
                     help="--incoherent: up|gate as fp32 outputs and SwiGLU inside the rotation launch (default: interleaved up|gate layer, "
                          "SwiGLU in the GEMV epilogue)")
     ap.add_argument("--no-incoherent-extra", action="store_true",
-                    help="skip the second figure (token with the incoherence wrapper) of the default run")
+                    help="--full: skip the second figure (token with the incoherence wrapper)")
     ap.add_argument("--no-fuse-rotation", action="store_true",
                     help="--incoherent: always rotate in a launch of its own (default: inside the GEMV where k allows)")
     ap.add_argument("--layers", type=int, default=0, help="override the number of layers (0 = model's)")
@@ -96,15 +108,15 @@ def parse_args():
                          "the leg, is printed either way and carries \"tp_70b_abandoned\": true)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) for real runs; gloo to rehearse ranks on one GPU")
     ap.add_argument("--force-device", type=int, default=-1, help="rehearsal only: put every rank on this GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the `other_configs` key of the default N = 1 run (BASELINE configs[2..4]: mem3p25, figure1d, figure1c, the 70B "
+                    help="--full: skip the `other_configs` key of an N = 1 run (BASELINE configs[2..4]: mem3p25, figure1d, figure1c, the 70B "
                          "shapes at batch 1 and 16 — <= 10 steps each, after the headline's timed region)")
     ap.add_argument("--no-whole-model", action="store_true",
-                    help="skip the `whole_model_decode` figure of the default N = 1 run (the fused decode step of perf/decode_llama.py)")
+                    help="--full: skip the `whole_model_decode` figure of an N = 1 run (the fused decode step of perf/decode_llama.py)")
     ap.add_argument("--no-tp-leg", action="store_true",
-                    help="N > 1: skip the `tp_70b` figures (Llama-3.1-70B shapes row-sharded over the N GPUs, batch 1 and 16)")
+                    help="--full, N > 1: skip the `tp_70b` figures (Llama-3.1-70B shapes row-sharded over the N GPUs, batch 1 and 16)")
     ap.add_argument("--tp-layers", type=int, default=0, help="layers of the tp_70b leg (0 = the model's 80)")
     ap.add_argument("--tp-steps", type=int, default=0, help="timed steps of each tp_70b figure (0 = min(--steps, 30))")
     ap.add_argument("--tp-timeout", type=float, default=float(os.environ.get("QPAL_TP_TIMEOUT", "300")),
@@ -876,11 +888,12 @@ def main():
         if args.dump_outputs and rank == 0:  # before any later leg runs on the device
             dump_outputs(torch, last[0], args.dump_outputs)
 
+    # Every leg from here until the line is printed runs with --full only; a plain run derives its figures from the timed steps above.
     # Per launch kind (N = 1, multi-job launches, after the timed region): the four dependent launches of a block timed one
     # kind at a time — 32 launches of that kind, each with its in-token arguments, as one graph — so that the launch
-    # furthest from the roofline can be read from the driver's record.
+    # furthest from the roofline can be read from the record.
     by_kind = None
-    if world == 1 and not args.incoherent and args.launch == "multi" and graph is not None and not args.no_kind_breakdown:
+    if args.full and world == 1 and not args.incoherent and args.launch == "multi" and graph is not None and not args.no_kind_breakdown:
         try:
             by_kind = {}
             with torch.cuda.stream(main_stream):
@@ -920,7 +933,7 @@ def main():
             by_kind = {"error": repr(exc)}
 
     calib = None
-    if world == 1 and not args.incoherent and not args.no_calibration and graph is not None:
+    if args.full and world == 1 and not args.incoherent and not args.no_calibration and graph is not None:
         try:
             calib = calibrate(qp, torch, layers, n, device, main_stream, args.steps)
         except Exception as exc:  # the headline line must not depend on this leg
@@ -929,7 +942,7 @@ def main():
     # Second figure (N = 1 only, after the timed region of the headline): the same token with every projection group
     # inside the reference's incoherence wrapper (rotation + scales), i.e. what an IncoherentMLP / attention forward costs.
     extra = None
-    if world == 1 and not args.incoherent and not args.no_incoherent_extra and args.launch == "multi" and graph is not None:
+    if args.full and world == 1 and not args.incoherent and not args.no_incoherent_extra and args.launch == "multi" and graph is not None:
         try:
             build_incoherent_state()
             with torch.cuda.stream(main_stream):
@@ -1024,7 +1037,7 @@ def main():
     printed = [False]
     tp_failed = [False]
     watchdog = None
-    if world > 1 and not args.no_tp_leg and not tp:
+    if args.full and world > 1 and not args.no_tp_leg and not tp:
         # BASELINE configs[4]: Llama-3.1-70B shapes @3.0 b row-sharded over the N GPUs, batch 1 and batch 16 (strong scaling),
         # after the headline's timed region; every rank takes part (collectives), rank 0 reports.
         # The headline line must not depend on this leg: a rank that raises leaves the others inside a collective, and a
@@ -1070,20 +1083,20 @@ def main():
             tp_failed[0] = True
             print(f"[bench rank {rank}] tp_70b leg raised at stage '{_TP_STATE.get('stage', '?')}': {exc!r}", file=sys.stderr, flush=True)
     if rank == 0:
-        if world == 1 and not args.no_whole_model and not args.incoherent and n == 1:
+        if args.full and world == 1 and not args.no_whole_model and not args.incoherent and n == 1:
             # the reference's own metric (eval/measure_latency.py:236-272 times whole-model generate()): the fused decode step of
             # perf/decode_llama.py — embedding, 32 decoder blocks (6 launches each), final norm + lm_head + argmax — short context
             try:
                 out["whole_model_decode"] = whole_model_leg(args)
             except Exception as exc:
                 out["whole_model_decode"] = {"error": repr(exc)}
-        if (world == 1 and not args.no_other_configs and not args.incoherent and n == 1 and args.launch == "multi"
+        if (args.full and world == 1 and not args.no_other_configs and not args.incoherent and n == 1 and args.launch == "multi"
                 and args.workload == "llama3.1-8b_tcomb_6_7" and not args.no_graph):
             try:
                 out["other_configs"] = other_configs_leg(qp, torch, device, args, main_stream)
             except Exception as exc:
                 out["other_configs"] = {"error": repr(exc)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             layers = build_model(qp, torch, model_key, qstr, 1, device, distinct_codebooks=args.distinct_codebooks,
                                  packing=args.packing, keep_infos=True)
             out["cpu_baseline"] = cpu_baseline(qp, layers, n, args.cpu_seconds, nlayers)

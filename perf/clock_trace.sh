@@ -7,7 +7,7 @@ rocm-smi --showclocks --showpower --showtemp --showmaxpower 2>&1 | head -40 >> $
 echo "== sampling (idle 2 s, then bench --steps 3000)" >> $out
 sample & SP=$!
 sleep 2
-python bench.py --steps 3000 --warmup 20 --no-cpu-baseline --no-other-configs --no-incoherent-extra --no-whole-model --no-kind-breakdown 2>/dev/null | python -c "
+python bench.py --full --steps 3000 --warmup 20 --no-cpu-baseline --no-other-configs --no-incoherent-extra --no-whole-model --no-kind-breakdown 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

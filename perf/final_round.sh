@@ -36,6 +36,6 @@ timeout -k 10 300 python perf/decode_llama.py --tokens 64 --qdict figure1d 2>/de
 echo "decode done"
 fi
 if has bench; then
-timeout -k 10 600 python bench.py > $out/bench_default.json 2>$out/bench_default.err
+timeout -k 10 600 python bench.py --full > $out/bench_default.json 2>$out/bench_default.err
 tail -c 600 $out/bench_default.json
 fi

@@ -1,4 +1,5 @@
-"""bench.py keeps the driver's contract: one JSON line with the agreed keys (checked in-process on a 2-layer model)."""
+"""bench.py keeps its contract: one JSON line with the agreed keys (checked in-process on a 2-layer model); a plain run measures
+the headline alone, --full every other figure of the line."""
 import io
 import json
 import os
@@ -18,7 +19,7 @@ def test_bench_prints_one_contract_line(monkeypatch):
     sys.path.insert(0, ROOT)
     import bench
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "1", "--layers", "2",
-                                      "--cpu-seconds", "1"])
+                                      "--cpu-seconds", "1", "--full"])
     for var in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         monkeypatch.delenv(var, raising=False)
     buf = io.StringIO()
@@ -50,6 +51,32 @@ def test_bench_prints_one_contract_line(monkeypatch):
     assert rs["world_size"] == 1 and rs["distinct_devices"] == 1 and rs["ranks"][0]["rank"] == 0 and rs["ranks"][0]["pci_bus_id"]
     wm = d["whole_model_decode"]  # the reference's own metric (whole-model decode step), measured after the headline
     assert "error" not in wm and wm["unit"] == "tokens/s" and 0 < wm["value"] < d["value"] and wm["launches_per_token"] == 2 * 5 + 1  # q|k|v, attention, o, gate|up, down (its rotation inside) per layer + the lm_head launch
+
+
+@pytest.mark.gpu
+def test_plain_run_measures_the_headline_alone(monkeypatch):
+    """Without --full the line carries the headline and the figures derived from its timed steps, and none of the figures that
+    take runs of their own."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "1", "--layers", "2"])
+    for var in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(var, raising=False)
+    buf = io.StringIO()
+    with redirect_stdout(buf):
+        bench.main()
+    lines = [l for l in buf.getvalue().splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config", "roofline"):
+        assert key in d, key
+    assert d["steps"] == 5 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and 0 < d["roofline"]["frac"] < 1
+    for key in ("cpu_baseline", "with_incoherence_wrapper", "whole_model_decode", "other_configs", "tp_70b"):
+        assert key not in d, key
+    for key in ("by_launch_kind", "measured_stream_GBps", "stream_token_ms", "decode_floor_ms"):
+        assert key not in d["roofline"], key
 
 
 def test_gpus_n_without_a_launcher_spawns_the_ranks(tmp_path, monkeypatch):
@@ -107,7 +134,7 @@ def test_gpus_n_without_a_launcher_spawns_the_ranks(tmp_path, monkeypatch):
 
 @pytest.mark.gpu
 def test_gpus_2_rehearsed_on_one_gpu_through_the_spawn_path():
-    """`python bench.py --gpus 2 --force-device 0 --dist-backend gloo` — no launcher — on the one-GPU box: the parent spawns two
+    """`python bench.py --gpus 2 --force-device 0 --dist-backend gloo --full` — no launcher — on the one-GPU box: the parent spawns two
     ranks that share the card, rank 0 prints ONE line: dp replicas as the headline and the tp_70b leg (row-sharded 70B shapes,
     batch 1 and 16, peer gather validated against the collective, then timed inside a HIP graph)."""
     if not torch.cuda.is_available():
@@ -115,7 +142,7 @@ def test_gpus_2_rehearsed_on_one_gpu_through_the_spawn_path():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--force-device", "0", "--dist-backend", "gloo",
-           "--steps", "4", "--warmup", "1", "--layers", "2", "--tp-layers", "2", "--no-kind-breakdown"]
+           "--steps", "4", "--warmup", "1", "--layers", "2", "--tp-layers", "2", "--no-kind-breakdown", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -136,7 +163,7 @@ def test_gpus_2_rehearsed_on_one_gpu_through_the_spawn_path():
 
 @pytest.mark.gpu
 def test_headline_line_survives_an_abandoned_tp_leg():
-    """The tp_70b leg runs after the headline's timed region and contains collectives: if it cannot complete (a rank fails, a
+    """The tp_70b leg (--full) runs after the headline's timed region and contains collectives: if it cannot complete (a rank fails, a
     collective hangs) the watchdog must still get rank 0's ONE line out, with the leg marked as an error — and the run must FAIL
     with exit code 75 (round 5: a hang on a multi-GPU node has to be visible in the driver's rc), every rank saying on stderr where
     it stood (stage of the leg, peer-gather slot / epoch view); --lenient-exit restores exit code 0."""
@@ -145,7 +172,7 @@ def test_headline_line_survives_an_abandoned_tp_leg():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--force-device", "0", "--dist-backend", "gloo",
-           "--steps", "4", "--warmup", "1", "--layers", "2", "--tp-layers", "2", "--no-kind-breakdown", "--tp-timeout", "0.05"]
+           "--steps", "4", "--warmup", "1", "--layers", "2", "--tp-layers", "2", "--no-kind-breakdown", "--tp-timeout", "0.05", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 75, (r.returncode, r.stderr[-2000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
