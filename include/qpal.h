@@ -194,6 +194,21 @@ int qpal_hadamard(void *out_f16, const void *in, const void *su, const void *sv,
 int qpal_hadamard_rms(void *out_f16, const float *in_f32, const void *rms_w, float rms_eps, const void *su, const void *hadk,
                       int rows, int n, int K, float post_scale, void *stream);
 
+/* fp32 Hadamard rotation for the quantiser's incoherence preprocessing (no fp16 rounding anywhere):
+ *   out[r][blk] = (hadK (x) H_P) (in[r][blk] * su[blk]) / sqrt(hd) * post_scale
+ * for every block of hd = K * P consecutive elements of every row, P = 2^p >= 16, the block viewed as [K][P] (as
+ * qpal_hadamard).  Replaces matmul_hadUt_head / matmul_hadU_head (lib/utils/matmul_had.py:95-120) on W * SU and on the
+ * proxy Hessian (lib/quantizer/tcq_quant.py:105-131, vq_quant.py:97-125), which need fp32 precision.  DEVICE pointers:
+ *   in, out   fp32 [rows][n], 16-byte aligned; out == in is allowed (every block is read completely before any of it is written)
+ *   su        fp32 [n] element-wise pre-multiplier, 16-byte aligned, or NULL
+ *   hadk      fp16 [K][K] row-major, entries +-1 (only the sign is read), applied as given (pass the transpose for the Ut
+ *             direction); NULL if K == 1
+ * K = 1 or a multiple of 4 up to 256 (every factor of get_hadK); the block (hd * 4 bytes, rounded up to 256) and the sign
+ * masks of hadK (K * ceil(K / 32) * 4 bytes) must fit the 160 KiB LDS: hd <= 40 960.  Butterflies and the K x K product in
+ * fp32.  Argument errors return before any stream work; one launch on `stream`, no synchronisation, no workspace.      */
+int qpal_hadamard_f32(float *out, const float *in, const float *su, const void *hadk, int rows, int n, int hd, int K,
+                      float post_scale, void *stream);
+
 /* Host-side encoders of the packed formats (plain CPU code; HOST pointers; no GPU involved): what a quantiser or a
  * checkpoint converter calls once per layer.  Bit for bit the reference's packers:
  *   qpal_pack_tcq         Qidxs int32 [m][k/2] (state t of tile (tr, tc) at [16 tr + t/8][8 tc + t%8]) -> int16

@@ -12,6 +12,8 @@ Layout:
   packers.py       pack_trellis / pack_qweight / pack_qweight_{sq,vq}_simt on the C-ABI's host-side encoders
   quantize.py      TCQ quantiser: tail-biting Viterbi encoder (csrc/tcq_viterbi.hip) + LDLQ -> QTIPLinearTCQ
                    VQ / SQ quantiser: nearest-codeword LDLQ encoder (csrc/vq_encode.hip) -> VQLinearPack{TensorCore,SIMT}
+  quantize_layer.py  whole layers: incoherence preprocessing (fp32 rotation, csrc/hadamard_f32.hip), comb / combt LDLQ,
+                   quantize_linear (tcq_* / tcomb_* / comb_* / ldlq_* strings) -> IncoherentLinear + layer file
   shard.py         row-sharding of packed layers across GPUs (torch.distributed / RCCL)
 
 There is deliberately no CPU implementation here: the CPU restatement lives in /oracle and is test
@@ -38,5 +40,7 @@ from .linear import (  # noqa: F401
     share_codebooks,
 )
 from . import quantize  # noqa: F401
+from . import quantize_layer  # noqa: F401
+from .quantize_layer import incoherent_preprocess, layer_file_path, load_hessian, quantize_linear  # noqa: F401
 
 __version__ = "0.1.0"

@@ -55,6 +55,7 @@ _SIGNATURES = {
     "qpal_pack_lut_simt": [_P, _P, _I, _I, _I, _I],
     "qpal_hadamard": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
     "qpal_hadamard_rms": [_P, _P, _P, _F, _P, _P, _I, _I, _I, _F, _P],
+    "qpal_hadamard_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "qpal_rope_kv": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_long, _P],
     "qpal_attn_decode": [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_long, _F, _P],
     "qpal_attn_rope_decode": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_long, _F, _P, ctypes.c_long, _P],

@@ -212,3 +212,47 @@ def ensure_hadamard_op():
         if x.dtype != torch.float16:
             raise _native.QpalError("hadamard::hadamard is implemented for fp16 tensors (the inference path's dtype)")
         return rotate(x, post_scale=scale * math.sqrt(x.shape[-1]))
+
+
+def rotate_f32(x, hd=None, hadK=None, K=1, su=None, post_scale=1.0, out=None):
+    """One launch of ``qpal_hadamard_f32`` (see include/qpal.h): fp32 in, fp32 out, no fp16 rounding anywhere.
+    x: fp32 [..., n]; every block of hd consecutive elements becomes (hadK (x) H_P)(x * su) / sqrt(hd) * post_scale.
+    hadK: the K x K +-1 factor as applied (fp16 or fp32, any device); su: fp32 [n] or None; out may be x (in place)."""
+    if not x.is_cuda:
+        raise _native.QpalError("qpalette_amd has no CPU implementation: rotate_f32() needs device tensors")
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise _native.QpalError("rotate_f32: x must be a contiguous fp32 tensor")
+    n = x.shape[-1]
+    hd = n if hd is None else hd
+    rows = x.numel() // n if n else 0
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != torch.float32 or out.shape != x.shape or not out.is_contiguous() or out.device != x.device:
+        raise _native.QpalError("rotate_f32: out must be a contiguous fp32 tensor shaped like x on x's device")
+    if su is not None and (su.dtype != torch.float32 or su.numel() != n or su.device != x.device or not su.is_contiguous()):
+        raise _native.QpalError(f"rotate_f32: su must be a contiguous fp32 vector of {n} elements on {x.device}")
+    hk = None
+    if K > 1:
+        if hadK is None or tuple(hadK.shape) != (K, K):
+            raise _native.QpalError(f"rotate_f32: hadK must be a [{K}, {K}] matrix")
+        hk = hadK.to(device=x.device, dtype=torch.float16).contiguous()
+    if rows == 0:
+        return out
+    with torch.cuda.device_of(x):
+        _native.check(_native.lib().qpal_hadamard_f32(out.data_ptr(), x.data_ptr(), su.data_ptr() if su is not None else None,
+                                                      hk.data_ptr() if hk is not None else None, rows, n, hd, K, float(post_scale),
+                                                      torch.cuda.current_stream(x.device).cuda_stream), "qpal_hadamard_f32")
+    return out
+
+
+def matmul_hadUt_head_f32(X, head_dim):
+    """reference matmul_hadUt_head (matmul_had.py:116-120) in fp32 on qpal_hadamard_f32: blocks of head_dim, hadK^T applied.
+    X: fp32 CUDA [..., n] -> fp32 [..., n]."""
+    hadK, K = get_hadK(head_dim, transpose=True)
+    return rotate_f32(X.contiguous(), hd=head_dim, hadK=hadK, K=K)
+
+
+def matmul_hadU_head_f32(X, head_dim):
+    """reference matmul_hadU_head (matmul_had.py:110-114) in fp32: the inverse of matmul_hadUt_head_f32."""
+    hadK, K = get_hadK(head_dim)
+    return rotate_f32(X.contiguous(), hd=head_dim, hadK=hadK, K=K)

@@ -38,8 +38,9 @@ def _bits(tlut):
     return S
 
 
-def tcq_viterbi(X, tlut, KV):
+def tcq_viterbi(X, tlut, KV, ws=None):
     """X: [B, 256] float CUDA tensor; tlut: fp16 [2^S, 2] codebook -> (hat fp32 [B, 256], states int32 [B, 128]).
+    ws: optional workspace of qpal_tcq_viterbi_ws_bytes(KV) bytes on X's device (allocated per call when None).
 
     X is rounded to fp16 first (through fp32, as torch's CPU conversion does from fp64) like the reference's quantize().
     Ties: lowest predecessor, then lowest final state (CPU torch.min / argmin)."""
@@ -55,7 +56,8 @@ def tcq_viterbi(X, tlut, KV):
     if B == 0:
         return hat.float(), states
     lib = _native.lib()
-    ws = torch.empty(lib.qpal_tcq_viterbi_ws_bytes(KV), dtype=torch.uint8, device=dev)
+    if ws is None:
+        ws = torch.empty(lib.qpal_tcq_viterbi_ws_bytes(KV), dtype=torch.uint8, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     for b0 in range(0, B, MAX_LAUNCH):
         n = min(MAX_LAUNCH, B - b0)
@@ -64,11 +66,11 @@ def tcq_viterbi(X, tlut, KV):
     return hat.float(), states
 
 
-def _quantize_rows(Wb, tlut, KV):
+def _quantize_rows(Wb, tlut, KV, ws=None):
     """Wb: [m, 16] column block -> (hat [m, 16] fp64, Qidxs block [m, 8]): ldlq.py:96-110 (for_kernel=True)."""
     m = Wb.shape[0]
     X = Wb.reshape(m // 16, 256)[:, PERMUTE.to(Wb.device)]
-    hat, st = tcq_viterbi(X, tlut, KV)
+    hat, st = tcq_viterbi(X, tlut, KV, ws)
     hat = hat[:, INV_PERMUTE.to(Wb.device)].reshape(m, 16).to(Wb.dtype)
     return hat, st.reshape(m, 8)
 
@@ -83,10 +85,13 @@ def block_ldl(H, b=16):
     return torch.einsum("rjb,jbc->rjc", C.reshape(n, nb, b), torch.linalg.inv(Dc)).reshape(n, n)
 
 
-def _ldlq(W, L, tlut, KV, buf_cols):
-    """Column-block LDLQ with error feedback (ldlq.py:63-121) in fp64; W: [m, n] fp64, L: unit block-lower, zero diagonal."""
+def _ldlq(W, L, tlut, KV, buf_cols, kv_at=None):
+    """Column-block LDLQ with error feedback (ldlq.py:63-121) in fp64; W: [m, n] fp64, L: unit block-lower, zero diagonal.
+    kv_at(r0): the KV of the column block starting at r0 (LDLQ_combt, ldlq.py:124-193), KV for every block when None.
+    One Viterbi workspace per KV for the whole loop."""
     m, n = W.shape
     nb = buf_cols // 16
+    ws = {}
     WT = W.T.contiguous()
     hatT = torch.zeros(n, m, dtype=W.dtype, device=W.device)
     QT = torch.zeros(n // 2, m, dtype=torch.int32, device=W.device)
@@ -94,10 +99,13 @@ def _ldlq(W, L, tlut, KV, buf_cols):
     for cur in range(n // 16, 0, -nb):
         r0, r1 = 16 * (cur - nb), 16 * cur
         bW, bhat, bL, bprod = WT[r0:r1], hatT[r0:r1], L[r0:r1], prod[r0:r1]
+        kv = KV if kv_at is None else kv_at(r0)
+        if kv not in ws:
+            ws[kv] = torch.empty(_native.lib().qpal_tcq_viterbi_ws_bytes(kv), dtype=torch.uint8, device=W.device)
         for i in reversed(range(nb)):
             fb = bL[16 * (i + 1):, r0 + 16 * i:r0 + 16 * (i + 1)].T @ (bW[16 * (i + 1):] - bhat[16 * (i + 1):])
             target = bW[16 * i:16 * (i + 1)] + fb + bprod[16 * i:16 * (i + 1)]
-            hat, q = _quantize_rows(target.T, tlut, KV)
+            hat, q = _quantize_rows(target.T, tlut, kv, ws[kv])
             bhat[16 * i:16 * (i + 1)] = hat.T
             QT[(r0 + 16 * i) // 2:(r0 + 16 * (i + 1)) // 2] = q.T
         prod += bL.T @ (bW - bhat)
