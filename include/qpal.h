@@ -320,6 +320,24 @@ int qpal_attn_rope_decode(const float *q, const float *k, const float *v, void *
                           const long *pos, const float *inv_freq, int nq, int nkv, int hd, long max_len, float scale,
                           void *ws, long ws_bytes, void *stream);
 
+/* Decode attention of B concurrent sequences, one launch (csrc/attn_batch.hip): for every sequence b < B with 0 <= pos[b] < max_len,
+ * rotary embedding of its new q and k (qpal_rope_kv's convention), k and v appended as fp16 to ITS cache at row pos[b], and
+ * softmax(q k^T * scale) v over its positions 0 .. pos[b] (fp32 accumulation, fp16 out).  q / k / v: fp32 rows [B][ld_qkv] (ld_qkv
+ * in elements, >= nq * hd: column slices of the q|k|v GEMV output [B][nq*hd + 2*nkv*hd]), inside a row q [nq * hd], k / v
+ * [nkv * hd]; caches fp16 [B][nkv][max_len][hd], 16-byte aligned; out fp16 [B][ld_out], out[b][h * hd + d]; pos int64 [B] on
+ * the device (never read by the host: graph-capturable with positions that change between replays); inv_freq fp32 [hd / 2].
+ * hd in {64, 128, 256}; nq / nkv in {1, 2, 4, 8} with (nq / nkv) * hd <= 1024; 1 <= B <= 128; max_len % 4 == 0, up to 64 k.
+ * A sequence whose pos[b] lies outside [0, max_len) is inactive: its cache and its out row are left as they were.
+ * Workgroup = (sequence, kv head, chunk of that sequence's existing context): only rows <= pos[b] are read.
+ * ws: qpal_attn_batch_ws_bytes(B, ...) bytes of device memory, 4-byte aligned, zero-filled ONCE, kept across launches; 0: no
+ * workspace needed, pass ws = NULL (max_len < 512).  The size is monotone in B and max_len: a workspace sized for (B, max_len)
+ * serves every launch of the same nq, nkv, hd with fewer sequences or a shorter cache (launches on one stream may share it). */
+long qpal_attn_batch_ws_bytes(int B, int nq, int nkv, int hd, long max_len);
+int qpal_attn_rope_decode_batch(const float *q, const float *k, const float *v, long ld_qkv,
+                                void *kcache_f16, void *vcache_f16, void *out_f16, long ld_out,
+                                const long *pos, const float *inv_freq, int B, int nq, int nkv, int hd,
+                                long max_len, float scale, void *ws, long ws_bytes, void *stream);
+
 /* The launch planner of the fused GEMV entry points, on its own (host code, no GPU call; what tests and tools inspect).
  * A launch of njobs jobs — rows[j] supertile rows (m / 32) of steps1[j] + steps2[j] steps (a step = 128 columns; steps2 = 0: one
  * stream) — is cut into workgroup-sized pieces: a GROUP of G = 1 << lg_g workgroups (`waves` = 16 or 8 waves each) owns rg

@@ -1,0 +1,68 @@
+#!/usr/bin/env python3
+"""Batched decode attention alone (qpalette_amd.decode_attention, csrc/attn_batch.hip): time per launch and achieved KV bytes/s.
+
+Llama-3 8B heads (32 query / 8 kv heads, hd 128) unless told otherwise.  Positions are ragged and seeded (uniform over the cache)
+or, with --full, every sequence at max_len - 1.  The bytes are the K and V rows the launch has to read, sum_b (pos[b] + 1) rows of
+nkv * hd fp16 each, not B * max_len.  Back-to-back launches timed with events; under `rocprofv3 --kernel-trace --stats` the
+kernel's own time comes from the trace.
+
+    python perf/attn_batch_bench.py [--batch 8 64] [--context 1024 4096] [--iters 200] [--full]
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+import qpalette_amd as qp
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, nargs="+", default=[8, 64])
+    ap.add_argument("--context", type=int, nargs="+", default=[1024, 4096])
+    ap.add_argument("--nq", type=int, default=32)
+    ap.add_argument("--nkv", type=int, default=8)
+    ap.add_argument("--hd", type=int, default=128)
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--full", action="store_true", help="every sequence at the last position of its cache")
+    args = ap.parse_args(argv)
+    dev = torch.device("cuda", 0)
+    nq, nkv, hd = args.nq, args.nkv, args.hd
+    inv_freq = 1.0 / (500000.0 ** (torch.arange(0, hd, 2, device=dev).float() / hd))
+    rows = []
+    for L in args.context:
+        for B in args.batch:
+            g = torch.Generator().manual_seed(B * 7 + L)
+            pos_h = torch.full((B,), L - 1, dtype=torch.long) if args.full else torch.randint(0, L, (B,), generator=g)
+            pos = pos_h.to(dev)
+            qkv = torch.randn(B, (nq + 2 * nkv) * hd, device=dev)
+            q, k, v = qkv.split([nq * hd, nkv * hd, nkv * hd], dim=1)
+            kc = torch.randn(B, nkv, L, hd, device=dev).half()
+            vc = torch.randn(B, nkv, L, hd, device=dev).half()
+            out = torch.empty(B, nq * hd, dtype=torch.float16, device=dev)
+            ws = qp.attention_workspace(B, nq, nkv, hd, L, dev)
+            for _ in range(10):
+                qp.decode_attention(q, k, v, kc, vc, pos, inv_freq, out=out, ws=ws)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.iters):
+                qp.decode_attention(q, k, v, kc, vc, pos, inv_freq, out=out, ws=ws)
+            e1.record()
+            torch.cuda.synchronize()
+            us = e0.elapsed_time(e1) * 1e3 / args.iters
+            kv_rows = int((pos_h + 1).sum())
+            nbytes = kv_rows * nkv * hd * 2 * 2
+            rows.append({"batch": B, "context": L, "full": args.full, "kv_rows": kv_rows, "kv_MB": nbytes / 1e6,
+                         "us_per_launch_events": us, "TBps_events": nbytes / (us * 1e-6) / 1e12,
+                         "workspace_bytes": 0 if ws is None else ws.numel() * 4})
+            del kc, vc
+            torch.cuda.empty_cache()
+    print(json.dumps({"what": "batched decode attention, one launch", "nq": nq, "nkv": nkv, "hd": hd, "rows": rows}))
+
+
+if __name__ == "__main__":
+    main()

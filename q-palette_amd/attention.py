@@ -1,0 +1,83 @@
+"""Decode attention of B concurrent sequences (C-ABI ``qpal_attn_rope_decode_batch``, csrc/attn_batch.hip).
+
+One launch per layer and step: rotary embedding of every sequence's new q and k, k and v appended to that sequence's static
+KV cache at ``pos[b]``, and attention over its positions ``0 .. pos[b]``.  A sequence whose position lies outside the cache
+(``pos[b] = -1`` for a free slot, for example) is inactive: its cache and its output row are left as they were.
+
+    ws = attention_workspace(B, nq, nkv, hd, max_len, device)      # once, shared by every layer
+    out = decode_attention(q, k, v, kcache, vcache, pos, inv_freq, ws=ws)
+"""
+import math
+
+import torch
+
+from . import _native
+from ._native import QpalError
+
+
+def attention_workspace(B, nq, nkv, hd, max_len, device):
+    """The zero-filled workspace ``decode_attention`` needs for up to B sequences and caches of up to max_len positions (same nq,
+    nkv, hd), or None where no launch of that shape needs one.  Keep it across launches: the kernel leaves it as it found it."""
+    n = _native.lib().qpal_attn_batch_ws_bytes(int(B), int(nq), int(nkv), int(hd), int(max_len))
+    if n <= 0:
+        return None
+    return torch.zeros((n + 3) // 4, dtype=torch.float32, device=device)
+
+
+def _rows(t, name, B, width):
+    if t.dtype != torch.float32 or not t.is_cuda:
+        raise QpalError(f"decode_attention: {name} must be an fp32 device tensor, got {t.dtype} on {t.device}")
+    if t.dim() != 2 or t.shape[0] != B or t.shape[1] != width:
+        raise QpalError(f"decode_attention: {name} must have shape [{B}, {width}], got {list(t.shape)}")
+    if t.stride(1) != 1:
+        raise QpalError(f"decode_attention: {name} rows must be contiguous")
+    return t.stride(0) if B > 1 else width
+
+
+def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=None, ws=None):
+    """q fp32 [B, nq*hd], k / v fp32 [B, nkv*hd] (rows may be strided: column slices of one q|k|v output with a common row
+    stride); kcache / vcache fp16 [B, nkv, max_len, hd] contiguous, 16-byte aligned, updated in place at row pos[b]; pos int64
+    [B] on the device; inv_freq fp32 [hd/2].  Returns out fp16 [B, nq*hd] (``out`` if given: rows of an inactive sequence keep
+    what they held).  scale defaults to 1/sqrt(hd).  Launches on the current stream."""
+    if kcache.dim() != 4 or kcache.shape != vcache.shape:
+        raise QpalError("decode_attention: kcache / vcache must both have shape [B, nkv, max_len, hd]")
+    B, nkv, max_len, hd = kcache.shape
+    for name, t in (("kcache", kcache), ("vcache", vcache)):
+        if t.dtype != torch.float16 or not t.is_cuda or not t.is_contiguous():
+            raise QpalError(f"decode_attention: {name} must be a contiguous fp16 device tensor")
+        if t.data_ptr() % 16:
+            raise QpalError(f"decode_attention: {name} must be 16-byte aligned")
+    if q.dim() != 2 or q.shape[0] != B or q.shape[1] % hd:
+        raise QpalError(f"decode_attention: q must have shape [{B}, nq*{hd}], got {list(q.shape)}")
+    nq = q.shape[1] // hd
+    ld = _rows(q, "q", B, nq * hd)
+    for name, t in (("k", k), ("v", v)):
+        if _rows(t, name, B, nkv * hd) != ld and B > 1:
+            raise QpalError("decode_attention: q, k and v must share one row stride")
+    if pos.dtype != torch.int64 or pos.shape != (B,) or pos.device != kcache.device or not pos.is_contiguous():
+        raise QpalError(f"decode_attention: pos must be a contiguous int64 [{B}] tensor on {kcache.device}")
+    if inv_freq.dtype != torch.float32 or inv_freq.numel() != hd // 2 or inv_freq.device != kcache.device or not inv_freq.is_contiguous():
+        raise QpalError(f"decode_attention: inv_freq must be a contiguous fp32 [{hd // 2}] tensor on {kcache.device}")
+    if any(t.device != kcache.device for t in (q, k, v)):
+        raise QpalError("decode_attention: every tensor must be on the caches' device")
+    if out is None:
+        out = torch.empty(B, nq * hd, dtype=torch.float16, device=kcache.device)
+    elif out.dtype != torch.float16 or out.dim() != 2 or out.shape != (B, nq * hd) or out.stride(1) != 1 or out.device != kcache.device:
+        raise QpalError(f"decode_attention: out must be fp16 [{B}, {nq * hd}] with contiguous rows on {kcache.device}")
+    ld_out = out.stride(0) if B > 1 else nq * hd
+    lib = _native.lib()
+    need = lib.qpal_attn_batch_ws_bytes(B, nq, nkv, hd, max_len)
+    if need > 0:
+        if ws is None:
+            raise QpalError("decode_attention: this shape needs a workspace (attention_workspace(...))")
+        if ws.device != kcache.device or ws.numel() * ws.element_size() < need or not ws.is_contiguous():
+            raise QpalError(f"decode_attention: ws must be a contiguous device buffer of >= {need} bytes on {kcache.device}")
+    scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
+    with torch.cuda.device(kcache.device):
+        rc = lib.qpal_attn_rope_decode_batch(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
+            pos.data_ptr(), inv_freq.data_ptr(), B, nq, nkv, hd, max_len, scale,
+            ws.data_ptr() if need > 0 else None, ws.numel() * ws.element_size() if need > 0 else 0,
+            torch.cuda.current_stream(kcache.device).cuda_stream)
+    _native.check(rc, "qpal_attn_rope_decode_batch")
+    return out

@@ -1,0 +1,424 @@
+// Decode attention of B concurrent sequences in one launch (qpal_attn_rope_decode_batch): for every sequence b with 0 <= pos[b] <
+// max_len, rotary embedding of its new q and k (qpal_rope_kv's convention: rotate_half, cos / sin of pos * inv_freq rounded to
+// fp16, fp16 arithmetic), k and v appended to ITS cache at row pos[b], and softmax(q k^T * scale) v over its positions 0 .. pos[b].
+// A sequence whose position lies outside the cache is inactive: nothing of it is read or written.
+//
+// Shape: the group form of decoder_glue.hip's split-context kernel with a batch dimension.  Workgroup = (sequence, kv head,
+// chunk of that sequence's context) and serves all REP = nq / nkv query heads of its group, so a K / V row is read once per group
+// and only rows <= pos[b] are read at all (bytes ~ sum_b (pos[b] + 1), not B * max_len).  The host fixes the grid from (B, nkv,
+// max_len) alone — *pos is never read on the host, the launch stays graph-capturable with positions that change between
+// replays — and every workgroup cuts the context that EXISTS for its sequence into at most `nsplit` chunks itself, leaving at
+// once when its chunk is empty.  Small B with long contexts still spreads over the compute units; at large B (nsplit = 1) a
+// sequence is one workgroup per kv head and nothing is merged.  Chunks of one (sequence, kv head) leave a partial (max, sum,
+// unnormalised out) per head in the workspace and take a ticket; the last to arrive merges them in a fixed order (bitwise
+// reproducible: no float atomics) and resets the ticket.
+#include <hip/hip_runtime.h>
+
+#include "qpal_common.h"
+
+namespace qpal {
+
+namespace {
+
+constexpr int kBatchMax = 128;        // the linears' fused batch
+constexpr long kBatchSplitFrom = 512; // caches shorter than this: one chunk per (sequence, kv head), no workspace
+constexpr long kBatchMinChunk = 128;  // a chunk holds at least this many positions (fewer: the merge costs more than it saves)
+constexpr int kBatchNW = 16;          // waves per workgroup
+constexpr int kBatchMaxSplit = 64;
+constexpr size_t kBatchLdsMax = 160 * 1024;
+
+struct AttnBatchParams {
+    const float *q, *k, *v;  // fp32 rows [B][ld_qkv]: q [nq * HD], k / v [nkv * HD] inside a row
+    long ld_qkv;
+    uint16_t *kcache, *vcache;  // fp16 [B][nkv][max_len][HD]
+    uint16_t *out;              // fp16 [B][ld_out]
+    long ld_out;
+    const long *pos;            // int64 [B], device
+    const float *inv_freq;      // fp32 [HD / 2]
+    int nkv;
+    long max_len;
+    float scale;
+    unsigned *tickets;          // [kBatchMax * nkv] (zero-filled once)
+    float *part;                // [B * nkv * nsplit][REP][HD + 2] partials
+    int nsplit, chunk;          // chunk: LDS score capacity per head (multiple of 64, nsplit * chunk >= max_len)
+};
+
+__device__ __forceinline__ void st_agent(float *p, float v) {
+    __hip_atomic_store(as_global(reinterpret_cast<unsigned *>(p)), __builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ float ld_agent(const float *p) {
+    return __builtin_bit_cast(float, __hip_atomic_load(as_global(reinterpret_cast<const unsigned *>(p)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+
+template <int HD, int REP>
+__global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const AttnBatchParams p) {
+    constexpr int NW = kBatchNW, NT = 64 * NW, HALF = HD / 2;
+    constexpr int LPR = HD / 8, DPL = HD / 64;
+    static_assert(REP * HD <= 1024, "partial-out buffer: NW x REP x HD floats of LDS");
+    static_assert(NW % REP == 0, "waves split evenly over the heads of a group");
+    extern __shared__ float sh[];  // scores [REP][chunk] | q [REP][HD/2 dwords] | new k [HD/2 dwords] | new v [HD] | partial out [NW][REP][HD] | reduce [2 NW REP] | new-position scores, maxima, sums [3 REP] | flag
+    const int CL = p.chunk;
+    float *sc = sh;
+    uint32_t *qh = reinterpret_cast<uint32_t *>(sh + REP * CL), *knh = qh + REP * HALF;
+    float *vn = reinterpret_cast<float *>(knh + HALF), *po = vn + HD, *red = po + NW * REP * HD;
+    float *park = red + 2 * NW * REP, *mxf = park + REP, *sumf = mxf + REP;
+    unsigned *flag = reinterpret_cast<unsigned *>(sumf + REP);
+    const int per_seq = p.nkv * p.nsplit;
+    const int b = blockIdx.x / per_seq, rem = blockIdx.x - b * per_seq;
+    const int kh = rem / p.nsplit, split = rem - kh * p.nsplit;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long pos = p.pos[b];
+    if (pos < 0 || pos >= p.max_len) return;  // inactive sequence: nothing is read or written, no ticket taken
+    // the context that exists, cut evenly over the splits (chunks of a multiple of 64 positions, at least kBatchMinChunk, at most
+    // the LDS capacity); chunks 0 .. neff-1 hold positions <= pos, the last of them the new one
+    // (32-bit unsigned divisions: positions are below max_len < 2^30)
+    long cld = CL;
+    if (p.nsplit > 1) {
+        cld = (long)((((unsigned)pos + (unsigned)p.nsplit) / (unsigned)p.nsplit + 63u) & ~63u);
+        if (cld < kBatchMinChunk) cld = kBatchMinChunk;
+        if (cld > CL) cld = CL;
+    }
+    const long c0 = (long)split * cld;
+    const int neff = (int)((unsigned)pos / (unsigned)cld) + 1;
+    if (split >= neff) return;
+    const bool owner = split == neff - 1;                    // this chunk holds the new position
+    const long cend = pos < c0 + cld ? pos : c0 + cld;       // cached positions of the chunk: [c0, cend)
+    const int nc = cend > c0 ? (int)(cend - c0) : 0;
+    const long kvoff = ((long)b * p.nkv + kh) * p.max_len * HD;
+    const gptr<const uint16_t> K = as_global(p.kcache) + kvoff, V = as_global(p.vcache) + kvoff;
+    const float *qrow = p.q + (long)b * p.ld_qkv, *krow = p.k + (long)b * p.ld_qkv, *vrow = p.v + (long)b * p.ld_qkv;
+    uint16_t *orow = p.out + (long)b * p.ld_out + (long)kh * REP * HD;
+    const long slot = ((long)b * p.nkv + kh) * p.nsplit;
+    float *wsp = p.part + (slot + split) * REP * (HD + 2);
+    unsigned *ticket = p.tickets + (long)b * p.nkv + kh;
+
+    // ---- new token: rope of the group's REP query heads (+ k, v in the chunk that owns the new position)
+    for (int idx = tid; idx < (REP + 1) * HALF; idx += NT) {
+        const int hh = idx / HALF, i = idx - hh * HALF;
+        const bool is_k = hh == REP;
+        if (is_k && !owner) continue;
+        const float *src = is_k ? krow + (long)kh * HD : qrow + (long)(kh * REP + hh) * HD;
+        const float ang = (float)pos * p.inv_freq[i];
+        const _Float16 c = (_Float16)cosf(ang), s = (_Float16)sinf(ang);
+        const _Float16 x1 = (_Float16)src[i], x2 = (_Float16)src[i + HALF];
+        const _Float16 o1 = x1 * c + (-x2) * s, o2 = x2 * c + x1 * s;
+        uint16_t *dst16 = reinterpret_cast<uint16_t *>(is_k ? knh : qh + hh * HALF);
+        dst16[i] = __builtin_bit_cast(uint16_t, o1);
+        dst16[i + HALF] = __builtin_bit_cast(uint16_t, o2);
+        if (is_k) {
+            uint16_t *dst = p.kcache + kvoff + pos * HD;
+            dst[i] = __builtin_bit_cast(uint16_t, o1);
+            dst[i + HALF] = __builtin_bit_cast(uint16_t, o2);
+        }
+    }
+    if (owner) {
+        for (int d = tid; d < HD; d += NT) {
+            const _Float16 hv = (_Float16)vrow[(long)kh * HD + d];
+            vn[d] = (float)hv;
+            p.vcache[kvoff + pos * HD + d] = __builtin_bit_cast(uint16_t, hv);
+        }
+    }
+    __syncthreads();
+
+    // ---- scores on the matrix pipe: D[head][position] = Q[head][:] . K[position][:], v_mfma_f32_16x16x32_f16 with the group's
+    // query heads as the (zero-padded) 16 rows of A and 16 cache rows as B (a B fragment: lane (column mi = position, mq = lane
+    // >> 4) loads 8 consecutive dims 32 kc + 8 mq .. of its row, 16 bytes)
+    const int grp = lane / LPR, sl = lane % LPR;
+    constexpr int U = 2;    // 16-row tiles in flight per wave
+    constexpr int KC = HD / 32;
+    typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+    typedef float float4_t __attribute__((ext_vector_type(4)));
+    const int mi = lane & 15, mq = lane >> 4;
+    float mx4[4] = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};  // heads 4 mq + r
+    {
+        half8_t afr[KC];
+#pragma unroll
+        for (int kc = 0; kc < KC; kc++) {
+            u32x4 a{0u, 0u, 0u, 0u};
+            if (mi < REP) a = *reinterpret_cast<const u32x4 *>(qh + mi * HALF + 16 * kc + 4 * mq);
+            afr[kc] = __builtin_bit_cast(half8_t, a);
+        }
+        for (int t0 = wave * 16; t0 < nc; t0 += NW * 16 * U) {
+            u32x4 kb[U][KC];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int t = t0 + u * NW * 16 + mi;
+                const gptr<const uint16_t> row = K + (c0 + (t < nc ? t : 0)) * HD + 8 * mq;
+#pragma unroll
+                for (int kc = 0; kc < KC; kc++) kb[u][kc] = *(gptr<const u32x4>)(row + 32 * kc);
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int t = t0 + u * NW * 16 + mi;
+                float4_t d{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kc = 0; kc < KC; kc++)
+                    d = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[kc], __builtin_bit_cast(half8_t, kb[u][kc]), d, 0, 0, 0);
+                if (4 * mq < REP && t < nc) {
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        if (4 * mq + r < REP) {
+                            const float a = d[r] * p.scale;
+                            sc[(4 * mq + r) * CL + t] = a;
+                            mx4[r] = a > mx4[r] ? a : mx4[r];
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (owner && wave == NW - 1) {  // the new position, from LDS (parked apart: the chunk's nc may equal CL)
+        u32x4 kn = u32x4{0u, 0u, 0u, 0u};
+        if (grp == 0) kn = *reinterpret_cast<const u32x4 *>(knh + 4 * sl);
+#pragma unroll
+        for (int h = 0; h < REP; h++) {
+            const u32x4 qv = *reinterpret_cast<const u32x4 *>(qh + h * HALF + 4 * sl);
+            float a = fdot2(kn.x, qv.x, 0.f);
+            a = fdot2(kn.y, qv.y, a);
+            a = fdot2(kn.z, qv.z, a);
+            a = fdot2(kn.w, qv.w, a);
+            a = group_sum<LPR>(a);
+            if (lane == 0) park[h] = a * p.scale;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; r++) {  // maximum over the 16 positions (lanes) of this lane's head group, per wave
+        float m = mx4[r];
+        m = group_max<16>(m);
+        if (mi == 0 && 4 * mq + r < REP) red[(4 * mq + r) * NW + wave] = m;
+    }
+    __syncthreads();
+    if (tid < REP) {
+        float m = red[tid * NW];
+#pragma unroll
+        for (int w = 1; w < NW; w++) m = red[tid * NW + w] > m ? red[tid * NW + w] : m;
+        if (owner) m = park[tid] > m ? park[tid] : m;
+        mxf[tid] = m;
+    }
+    __syncthreads();
+    {   // exponentials and their sums: wave -> (head wave % REP, part wave / REP of the chunk)
+        constexpr int NP = NW / REP;
+        const int hh = wave % REP, pw = wave / REP;
+        const float m = mxf[hh];
+        float sm = 0.f;
+        for (int t = pw * 64 + lane; t < nc; t += 64 * NP) {
+            const float e = __expf(sc[hh * CL + t] - m);
+            sc[hh * CL + t] = e;
+            sm += e;
+        }
+        sm = wave_sum(sm);
+        if (lane == 0) red[NW * REP + wave] = sm;
+    }
+    __syncthreads();
+    if (tid < REP) {
+        constexpr int NP = NW / REP;
+        float sm = 0.f;
+#pragma unroll
+        for (int pw = 0; pw < NP; pw++) sm += red[NW * REP + pw * REP + tid];
+        const float wn = owner ? __expf(park[tid] - mxf[tid]) : 0.f;
+        park[tid] = wn;  // from here on: the new position's softmax weight
+        sumf[tid] = sm + wn;
+    }
+
+    // ---- values: wave w takes positions w, w + NW, ...; a lane owns DPL adjacent dims
+    float acc[REP][DPL];
+#pragma unroll
+    for (int h = 0; h < REP; h++)
+#pragma unroll
+        for (int e = 0; e < DPL; e++) acc[h][e] = 0.f;
+    constexpr int UV = REP * DPL > 16 ? 2 : 4;  // rows in flight per wave
+    for (int t0 = wave; t0 < nc; t0 += NW * UV) {
+        uint16_t raw[UV][DPL];
+#pragma unroll
+        for (int u = 0; u < UV; u++) {
+            const int t = t0 + u * NW;
+            const gptr<const uint16_t> row = V + (c0 + (t < nc ? t : 0)) * HD + DPL * lane;
+            if constexpr (DPL == 1) raw[u][0] = row[0];
+            else if constexpr (DPL == 2) { const uint32_t r = *(gptr<const uint32_t>)row; raw[u][0] = (uint16_t)r; raw[u][1] = (uint16_t)(r >> 16); }
+            else { const u32x2 r = *(gptr<const u32x2>)row; raw[u][0] = (uint16_t)r.x; raw[u][1] = (uint16_t)(r.x >> 16); raw[u][2] = (uint16_t)r.y; raw[u][3] = (uint16_t)(r.y >> 16); }
+        }
+#pragma unroll
+        for (int u = 0; u < UV; u++) {
+            const int t = t0 + u * NW;
+#pragma unroll
+            for (int h = 0; h < REP; h++) {
+                const float w = t < nc ? sc[h * CL + t] : 0.f;
+#pragma unroll
+                for (int e = 0; e < DPL; e++) acc[h][e] += w * (float)__builtin_bit_cast(_Float16, raw[u][e]);
+            }
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < REP; h++)
+#pragma unroll
+        for (int e = 0; e < DPL; e++) po[(wave * REP + h) * HD + DPL * lane + e] = acc[h][e];
+    __syncthreads();  // (also orders park / sumf, written by the first REP threads above, before the reads below)
+    for (int idx = tid; idx < REP * HD; idx += NT) {
+        float v = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; w++) v += po[w * REP * HD + idx];
+        const int h = idx / HD, d = idx - h * HD;
+        if (owner) v += park[h] * vn[d];
+        if (neff == 1) orow[idx] = __builtin_bit_cast(uint16_t, (_Float16)(v / sumf[h]));  // the only chunk
+        else st_agent(wsp + h * (HD + 2) + 2 + d, v);
+    }
+    if (neff == 1) return;  // no partials, no ticket
+    if (tid < REP) {
+        st_agent(wsp + tid * (HD + 2), mxf[tid]);
+        st_agent(wsp + tid * (HD + 2) + 1, sumf[tid]);
+    }
+    // ---- ticket: the partial stores are agent-scope (write-through); wait for them, then arrive with an agent-scope release /
+    // acquire so that the last arriver sees every other chunk's partials
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned t = __hip_atomic_fetch_add(as_global(ticket), 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        *flag = t == (unsigned)neff - 1 ? 1u : 0u;
+    }
+    __syncthreads();
+    if (*flag == 0u) return;
+    // ---- last arriver of this (sequence, kv head): merge in chunk order (max / sum of every partial through LDS first, then the
+    // out partials sixteen at a time: agent-scope loads are issued together, never one per iteration)
+    const float *base = p.part + slot * REP * (HD + 2);
+    float *ml = sh;  // [neff * REP][2]: the score buffer and what follows it are free now
+    for (int i = tid; i < neff * REP; i += NT) {
+        const float *pp = base + (long)i * (HD + 2);
+        ml[2 * i] = ld_agent(pp);
+        ml[2 * i + 1] = ld_agent(pp + 1);
+    }
+    __syncthreads();
+    for (int idx = tid; idx < REP * HD; idx += NT) {
+        const int h = idx / HD, d = idx - h * HD;
+        float M = -3.0e38f;
+        for (int s = 0; s < neff; s++) {
+            const float m = ml[2 * (s * REP + h)];
+            M = m > M ? m : M;
+        }
+        float L = 0.f, o = 0.f;
+        for (int s0 = 0; s0 < neff; s0 += 16) {
+            float v[16];
+#pragma unroll
+            for (int u = 0; u < 16; u++) {
+                const int sx = s0 + u < neff ? s0 + u : neff - 1;
+                v[u] = ld_agent(base + ((long)sx * REP + h) * (HD + 2) + 2 + d);
+            }
+#pragma unroll
+            for (int u = 0; u < 16; u++) {
+                const int sx = s0 + u;
+                if (sx < neff) {
+                    const float f = __expf(ml[2 * (sx * REP + h)] - M);
+                    L += ml[2 * (sx * REP + h) + 1] * f;
+                    o += v[u] * f;
+                }
+            }
+        }
+        orow[idx] = __builtin_bit_cast(uint16_t, (_Float16)(o / L));
+    }
+    if (tid == 0) __hip_atomic_store(as_global(ticket), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// LDS floats of the kernel's layout at score capacity `chunk`
+size_t batch_lds_floats(int rep, int hd, long chunk) {
+    const int nw = kBatchNW;
+    return (size_t)rep * chunk + (size_t)rep * hd / 2 + hd / 2 + hd + (size_t)nw * rep * hd + 2 * (size_t)nw * rep + 3 * rep + 4;
+}
+
+struct BatchGeometry {
+    int nsplit, chunk;
+    size_t lds, ws_bytes;
+};
+
+// Launch geometry from (B, heads, max_len) only.  ws_bytes is an upper bound of what ANY launch with at most B sequences and at
+// most max_len positions needs (monotone in both): one workspace serves every smaller launch of the same heads.
+int batch_geometry(int B, int nq, int nkv, int hd, long max_len, BatchGeometry &g) {
+    g = BatchGeometry{0, 0, 0, 0};
+    if (B < 1 || B > kBatchMax || nq < 1 || nkv < 1 || nq % nkv || (hd != 64 && hd != 128 && hd != 256)) return QPAL_E_SHAPE;
+    const int rep = nq / nkv;
+    if ((rep != 1 && rep != 2 && rep != 4 && rep != 8) || rep * hd > 1024) return QPAL_E_SHAPE;
+    if (max_len < 4 || max_len % 4 || max_len >= (1L << 30)) return QPAL_E_SHAPE;
+    const size_t budget = kBatchLdsMax / sizeof(float), fixed = batch_lds_floats(rep, hd, 0);
+    const long cl_max = (long)((budget - fixed) / rep) / 64 * 64;  // the most positions one chunk's scores can hold
+    if (cl_max < 64) return QPAL_E_SHAPE;
+    const long ns_lds = (max_len + cl_max - 1) / cl_max;           // chunks the LDS forces
+    if (ns_lds > kBatchMaxSplit) return QPAL_E_SHAPE;
+    int ns = 1;
+    if (max_len >= kBatchSplitFrom) {
+        // ~one workgroup of 16 waves per compute unit over the whole launch
+        long want = (256 + (long)B * nkv - 1) / ((long)B * nkv);
+        if (want > kBatchMaxSplit) want = kBatchMaxSplit;
+        ns = (int)(want > ns_lds ? want : ns_lds);
+    } else {
+        ns = (int)ns_lds;  // (1: a 512-position cache always fits)
+    }
+    long c = ((max_len + ns - 1) / ns + 63) / 64 * 64;
+    if (c > cl_max) c = cl_max;
+    ns = (int)((max_len + c - 1) / c);
+    g.nsplit = ns, g.chunk = (int)c;
+    g.lds = batch_lds_floats(rep, hd, c) * sizeof(float);
+    if (max_len >= kBatchSplitFrom) {
+        // slots: B nkv ns_lds where the LDS forces the split, else B nkv ceil(256 / (B nkv)) <= 256 + B nkv
+        const long by_lds = (long)B * nkv * ns_lds, by_want = 256 + (long)B * nkv;
+        const long slots = by_lds > by_want ? by_lds : by_want;
+        g.ws_bytes = ((size_t)kBatchMax * nkv + (size_t)slots * rep * (hd + 2)) * sizeof(float);
+    }
+    return QPAL_OK;
+}
+
+template <class Kern>
+int launch_batch(Kern kern, const AttnBatchParams &p, int grid, size_t lds, void *stream) {
+    static bool attr_set[64] = {};  // one latch per instantiation and device
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (lds > 64 * 1024 && (dev < 0 || !attr_set[dev])) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBatchLdsMax);
+        if (e != hipSuccess) return (int)e;
+        if (dev >= 0) attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kBatchNW), lds, static_cast<hipStream_t>(stream), p);
+    return (int)hipGetLastError();
+}
+
+}  // namespace
+
+}  // namespace qpal
+
+using namespace qpal;
+
+extern "C" long qpal_attn_batch_ws_bytes(int B, int nq, int nkv, int hd, long max_len) {
+    BatchGeometry g;
+    if (batch_geometry(B, nq, nkv, hd, max_len, g) != QPAL_OK) return 0;
+    return (long)g.ws_bytes;
+}
+
+extern "C" int qpal_attn_rope_decode_batch(const float *q, const float *k, const float *v, long ld_qkv, void *kcache_f16, void *vcache_f16,
+                                           void *out_f16, long ld_out, const long *pos, const float *inv_freq, int B, int nq, int nkv,
+                                           int hd, long max_len, float scale, void *ws, long ws_bytes, void *stream) {
+    if (!q || !k || !v || !kcache_f16 || !vcache_f16 || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
+    BatchGeometry g;
+    const int rc = batch_geometry(B, nq, nkv, hd, max_len, g);
+    if (rc != QPAL_OK) return rc;
+    if (ld_qkv < (long)nq * hd || ld_out < (long)nq * hd) return QPAL_E_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(kcache_f16) | reinterpret_cast<uintptr_t>(vcache_f16)) & 15) return QPAL_E_ALIGN;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
+         reinterpret_cast<uintptr_t>(inv_freq) | reinterpret_cast<uintptr_t>(pos)) & 3)
+        return QPAL_E_ALIGN;
+    if (reinterpret_cast<uintptr_t>(out_f16) & 1) return QPAL_E_ALIGN;
+    if (g.ws_bytes) {
+        if (!ws) return QPAL_E_NULL;
+        if (ws_bytes < (long)g.ws_bytes) return QPAL_E_SHAPE;
+        if (reinterpret_cast<uintptr_t>(ws) & 3) return QPAL_E_ALIGN;
+    }
+    float *wsf = static_cast<float *>(ws);
+    AttnBatchParams p{q, k, v, ld_qkv, static_cast<uint16_t *>(kcache_f16), static_cast<uint16_t *>(vcache_f16),
+                      static_cast<uint16_t *>(out_f16), ld_out, pos, inv_freq, nkv, max_len, scale,
+                      g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr, g.ws_bytes ? wsf + (long)kBatchMax * nkv : nullptr,
+                      g.nsplit, g.chunk};
+    const int grid = B * nkv * g.nsplit, rep = nq / nkv;
+#define QPAL_BATCH(HD_, REP_) \
+    if (hd == HD_ && rep == REP_) return launch_batch(attn_rope_batch_kernel<HD_, REP_>, p, grid, g.lds, stream);
+    QPAL_BATCH(64, 1) QPAL_BATCH(64, 2) QPAL_BATCH(64, 4) QPAL_BATCH(64, 8)
+    QPAL_BATCH(128, 1) QPAL_BATCH(128, 2) QPAL_BATCH(128, 4) QPAL_BATCH(128, 8)
+    QPAL_BATCH(256, 1) QPAL_BATCH(256, 2) QPAL_BATCH(256, 4)
+#undef QPAL_BATCH
+    return QPAL_E_SHAPE;
+}
