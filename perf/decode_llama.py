@@ -11,6 +11,9 @@ Triton and therefore not used here): RMSNorm, rotary embedding, KV-cache update,
 hundred small launches per token.  The script reports the whole-step rate and, next to it, the rate of the quantized
 projections alone (same graph without the glue), so the two are not confused.
 
+Third figure: the same step on this library's own glue, `qpalette_amd.DecodeStep` (q-palette_amd/decoder.py), on the same caches,
+token and position; the modular step above is the reference its final normalised hidden state is checked against.
+
     python perf/decode_llama.py [--quantizer tcomb_6_7_0.5_none_0.9 | --qdict figure1d] [--context 1024] [--tokens 64]
 """
 import argparse
@@ -94,6 +97,69 @@ class DecoderLayer(nn.Module):
         return h + self.mlp(self.post_attention_layernorm(h))
 
 
+def build_model(model, quantizer, qdict_name, nlayers, vocab, dev):
+    """The random Llama-shaped model both decode scripts run: cfg, layers (every one or the first `nlayers`; --quantizer on every
+    linear or the published perf/qdicts/<qdict_name>.json with its merge_info), embed, lm_head, the final norm, inv_freq."""
+    li = qp.mem_op.get_layer_info(model)
+    H, I = li["mlp.gate_proj"]["in_features"], li["mlp.gate_proj"]["out_features"]
+    head_dim = 128
+    cfg = types.SimpleNamespace(hidden_size=H, intermediate_size=I, hidden_act="silu", num_attention_heads=H // head_dim,
+                                num_key_value_heads=li["self_attn.k_proj"]["out_features"] // head_dim, head_dim=head_dim,
+                                attention_dropout=0.0)
+    qdict, merge_info = None, None
+    if qdict_name:
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "qdicts", qdict_name + ".json")) as f:
+            data = json.load(f)
+        qdict, merge_info = data["qdict"], data["merge_info"]
+
+    def qof(layer, key):
+        if qdict is None:
+            return quantizer, False
+        q, simt = qdict[f"{layer}_{key}"]
+        return q, simt == "1"
+
+    gen = torch.Generator(device=dev).manual_seed(1234)
+    layers = nn.ModuleList([DecoderLayer(cfg, model, i, qof, set(merge_info[i]) if merge_info else set(), dev, gen)
+                            for i in range(nlayers or li["nlayers"])])
+    qp.share_codebooks([m for m in layers.modules() if hasattr(m, "tlut") or hasattr(m, "lut")])
+    embed = (torch.randn(vocab, H, device=dev, generator=gen) * 0.5).half()
+    lm_head = (torch.randn(vocab, H, device=dev, generator=gen) * 0.02).half()
+    inv_freq = 1.0 / (500000.0 ** (torch.arange(0, head_dim, 2, device=dev).float() / head_dim))
+    return types.SimpleNamespace(cfg=cfg, layers=layers, embed=embed, lm_head=lm_head, norm=RMSNorm(H).to(dev), inv_freq=inv_freq)
+
+
+WARMUP = 8
+
+
+def time_graph(fn, replays, dev, before=None):
+    """ms per replay of `replays` replays of fn() captured in a graph, after one eager run and WARMUP untimed replays.  The loop that
+    is timed is the loop that is warmed up: `before(i)` (i counts the replays from the first untimed one) runs in front of every
+    replay — a decode loop copies the sampled token in and sets the position there, two tiny launches whose FIRST use loads their
+    code objects (~28 ms that round 3 had inside the timed region: 284 tok/s at 20 tokens against 472 at 64).
+    Timed with events on the replay stream around the whole loop, the host loop runs ahead of the GPU."""
+    s = torch.cuda.Stream(dev)
+    with torch.cuda.stream(s):
+        fn()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            fn()
+
+        def run(lo, hi):
+            for i in range(lo, hi):
+                if before is not None:
+                    before(i)
+                g.replay()
+        run(0, WARMUP)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run(WARMUP, WARMUP + replays)
+        e1.record()
+        torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / replays
+
+
 def main(argv=None, quiet=False):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="3_8b", choices=sorted(qp.mem_op.LAYER_INFO))
@@ -114,34 +180,10 @@ def main(argv=None, quiet=False):
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
     dev = torch.device("cuda", 0)
-    li = qp.mem_op.get_layer_info(args.model)
-    H, I = li["mlp.gate_proj"]["in_features"], li["mlp.gate_proj"]["out_features"]
-    kv_out = li["self_attn.k_proj"]["out_features"]
-    head_dim = 128
-    cfg = types.SimpleNamespace(hidden_size=H, intermediate_size=I, hidden_act="silu", num_attention_heads=H // head_dim,
-                                num_key_value_heads=kv_out // head_dim, head_dim=head_dim, attention_dropout=0.0)
-    nlayers = args.layers or li["nlayers"]
-    qdict, merge_info = None, None
-    if args.qdict:
-        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "qdicts", args.qdict + ".json")) as f:
-            data = json.load(f)
-        qdict, merge_info = data["qdict"], data["merge_info"]
-
-    def qof(layer, key):
-        if qdict is None:
-            return args.quantizer, False
-        q, simt = qdict[f"{layer}_{key}"]
-        return q, simt == "1"
-
-    gen = torch.Generator(device=dev).manual_seed(1234)
-    layers = nn.ModuleList([DecoderLayer(cfg, args.model, i, qof, set(merge_info[i]) if merge_info else set(), dev, gen)
-                            for i in range(nlayers)])
-    qp.share_codebooks([m for m in layers.modules() if hasattr(m, "tlut") or hasattr(m, "lut")])
-    embed = (torch.randn(args.vocab, H, device=dev, generator=gen) * 0.5).half()
-    lm_head = (torch.randn(args.vocab, H, device=dev, generator=gen) * 0.02).half()
-    norm = RMSNorm(H).to(dev)
-    cache = StaticKV(nlayers, cfg.num_key_value_heads, head_dim, args.context, dev)
-    inv_freq = 1.0 / (500000.0 ** (torch.arange(0, head_dim, 2, device=dev).float() / head_dim))
+    m = build_model(args.model, args.quantizer, args.qdict, args.layers, args.vocab, dev)
+    cfg, layers, embed, lm_head, norm, inv_freq = m.cfg, m.layers, m.embed, m.lm_head, m.norm, m.inv_freq
+    H, nlayers = cfg.hidden_size, len(layers)
+    cache = StaticKV(nlayers, cfg.num_key_value_heads, cfg.head_dim, args.context, dev)
     tok = torch.zeros(1, dtype=torch.long, device=dev)
     pos = torch.zeros(1, dtype=torch.long, device=dev)
     out_tok = torch.zeros(1, dtype=torch.long, device=dev)
@@ -162,206 +204,43 @@ def main(argv=None, quiet=False):
             out_tok.copy_(logits.argmax(-1))
         return h
 
-    def _time_tokens(g, feed):
-        """ms-free seconds per token of `args.tokens` replays of the captured step.  The loop that is timed is the loop that is warmed
-        up: with `feed` every token first copies the sampled token in and sets the position (two tiny launches whose FIRST use
-        loads their code objects — ~28 ms that round 3 had inside the timed region: 284 tok/s at 20 tokens against 472 at 64).
-        Timed with events on the replay stream around the whole loop, the host loop runs ahead of the GPU."""
-        def one(i):
-            if feed:                           # the next step consumes the sampled token at the next position
-                tok.copy_(out_tok)
-                pos.fill_(min(args.context - 1, args.start_pos + i))
-            g.replay()
-        for i in range(8):
-            one(i)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for i in range(args.tokens):
-            one(i)
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e-3 / args.tokens
+    def feed(i):
+        """the next step consumes the sampled token at the next position; the timed tokens start at --start-pos like the untimed ones"""
+        tok.copy_(out_tok)
+        pos.fill_(min(args.context - 1, args.start_pos + (i if i < WARMUP else i - WARMUP)))
 
-    def timed(glue):
-        s = torch.cuda.Stream(dev)
-        with torch.cuda.stream(s):
-            step(glue)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=s):
-                step(glue)
-            return _time_tokens(g, glue)
+    def timed(fn, before=feed):
+        return time_graph(fn, args.tokens, dev, before) * 1e-3  # seconds per token
 
-    # ---- fused glue (MI355X decoder block): the residual stream stays fp32; RMSNorm + sign flip + Hadamard run inside the
-    # q|k|v and up|gate launches (x_rms / x_rot on the fp32 stream), o_proj and down_proj ADD into the stream (accumulate),
-    # rotary embedding + KV-cache append + attention over the cache are one launch (qpal_attn_rope_decode), the SwiGLU rotation
-    # one: 6 launches per layer instead of ~41.
-    nat = qp._native
-    h32 = torch.zeros(1, H, dtype=torch.float32, device=dev)
-    nq, nkv = cfg.num_attention_heads, cfg.num_key_value_heads
-    q16 = torch.zeros(1, nq, 1, head_dim, dtype=torch.float16, device=dev)
-    a16 = torch.zeros(1, H, dtype=torch.float16, device=dev)
-    qkv32 = torch.zeros(1, H + 2 * kv_out, dtype=torch.float32, device=dev)
-    ug32 = torch.zeros(1, 2 * I, dtype=torch.float32, device=dev)
-    act16 = torch.zeros(1, I, dtype=torch.float16, device=dev)
-    eps = layers[0].input_layernorm.eps
-    # long caches: split-context attention (one workspace serves every layer: launches are stream-ordered)
-    attn_ws_bytes = 0 if args.no_split_attention else nat.lib().qpal_attn_ws_bytes(nq, nkv, head_dim, args.context)
-    attn_ws = torch.zeros(max(attn_ws_bytes, 4) // 4, dtype=torch.float32, device=dev)
-    lm_ws_bytes = nat.lib().qpal_lm_head_ws_bytes(args.vocab)
-    lm_ws = torch.zeros(lm_ws_bytes // 4, dtype=torch.float32, device=dev)
-    want_hidden = [False]  # the parity check below wants the normalised hidden state back (an extra torch norm, not timed)
-
-    rot_in_gemv = bool(qp.ops.can_fuse_rotation(1, H))  # k in {2048, 4096}: the GEMV staging rotates x itself
-
-    def _hid(mod, name):
-        """(hadK^T fp16 on the device or None, K) of a module's rotation of the hidden width (cached on the module)"""
-        if not hasattr(mod, name):
-            hk, K = qp.hadamard.get_hadK(H)
-            setattr(mod, name, (None if hk is None else hk.T.contiguous().half().to(dev), K))
-        return getattr(mod, name)
-
-    def k28_in_gemv(mlp):
-        """down_proj's rotation inside its own launch: k = 14336 = 28 x 512, a tensor-core-order layer whose codebook image can lend
-        the rotation its scratch (every TCQ codec; --no-k28-fusion: the qpal_hadamard launch of round 2)."""
-        if args.no_k28_fusion or mlp.inter_K <= 1 or not qp.ops.can_fuse_rotation(1, mlp.intermediate_size, mlp.inter_K):
-            return False
-        d = mlp.down_proj
-        if isinstance(d, qp.VQLinearPackTensorCore):
-            idx = d.lut_bits if d.vec_sz == 2 else (2 * d.lut_bits if d.lut_bits <= 6 else d.lut_bits)
-            return (4 << (idx + min(15 - idx, 5))) >= 40 * 1024
-        return isinstance(d, (qp.QTIPLinearTCQ, qp.CombtLinearTCQ)) and qp.linear._codec_key(d)[0] != "single"
-
-    def fused_layer(idx, layer, mask):
-        att, mlp = layer.self_attn, layer.mlp
-        proj, wsc, blocks = att._qkv_layout()
-        widths = [l.out_features for l in proj]
-        if rot_in_gemv:
-            qp.multi_gemv(proj, h32, outs=list(qkv32.split(widths, dim=1)), wscales=wsc, oscale=att.scale,
-                          x_rot=(att.SU_qkv, 1.0 / att.scale), x_rms=(eps, layer.input_layernorm.weight))
-        else:  # wider hidden sizes (70B: 8192): RMSNorm + rotation as ONE launch of their own, then the plain GEMV launch
-            hk, K = _hid(att, "_hadk_hidden")
-            xr = qp.hadamard.rotate(h32, hadK=hk, K=K, su=att.SU_qkv, post_scale=1.0 / att.scale, in_mode=qp.hadamard.IN_F32,
-                                    rms=(eps, layer.input_layernorm.weight))
-            qp.multi_gemv(proj, xr, outs=list(qkv32.split(widths, dim=1)), wscales=wsc, oscale=att.scale)
-        parts = dict(zip([b[0] for b in blocks], qkv32.split([b[1] for b in blocks], dim=1)))
-        with torch.cuda.device(dev):
-            rc = nat.lib().qpal_attn_rope_decode(parts["q"].data_ptr(), parts["k"].data_ptr(), parts["v"].data_ptr(),
-                                                 cache.k[idx].data_ptr(), cache.v[idx].data_ptr(), a16.data_ptr(), pos.data_ptr(),
-                                                 inv_freq.data_ptr(), nq, nkv, head_dim, args.context, 1.0 / math.sqrt(head_dim),
-                                                 attn_ws.data_ptr() if attn_ws_bytes else None, attn_ws_bytes,
-                                                 torch.cuda.current_stream(dev).cuda_stream)
-        nat.check(rc, "qpal_attn_rope_decode")
-        if rot_in_gemv:
-            qp.multi_gemv([att.o_proj], a16, outs=[h32], wscales=[att.Wscale_o], oscale=att.scale,
-                          x_rot=(att.SU_o, 1.0 / att.scale), accumulate=True)
-        else:
-            hk, K = _hid(att, "_hadk_hidden")
-            xr = qp.hadamard.rotate(a16, hadK=hk, K=K, su=att.SU_o, post_scale=1.0 / att.scale)
-            qp.multi_gemv([att.o_proj], xr, outs=[h32], wscales=[att.Wscale_o], oscale=att.scale, accumulate=True)
-        inter = mlp.intermediate_size
-        if mlp.merge_ug:
-            ugl, ugw = [mlp.ug_proj], [mlp.Wscale_ug]
-        else:
-            ugl, ugw = [mlp.up_proj, mlp.gate_proj], [mlp.Wscale_ug[:inter], mlp.Wscale_ug[inter:]]
-        ug_outs = list(ug32.split([l.out_features for l in ugl], dim=1))
-        if rot_in_gemv and not args.no_swiglu_epilogue:
-            # up | gate as ONE layer with interleaved supertile rows: the launch's epilogue writes fp16 silu(gate) * up itself
-            if not hasattr(mlp, "_ug_il"):
-                il = qp.linear.interleave_up_gate(mlp.ug_proj, None) if mlp.merge_ug else qp.linear.interleave_up_gate(mlp.up_proj, mlp.gate_proj)
-                qp.share_codebooks([il, mlp.down_proj] + ugl)
-                mlp._ug_il = il
-                mlp._ug_il_w = qp.linear.interleave_rows(mlp.Wscale_ug[:inter], mlp.Wscale_ug[inter:])
-            fuse28 = k28_in_gemv(mlp)
-            # with the fused rotation the gate|up epilogue also applies down_proj's sign vector (a sign flip: exact), so the rotation
-            # inside every down_proj workgroup reads one 28 KiB vector instead of two
-            qp.multi_gemv([mlp._ug_il], h32, wscales=[mlp._ug_il_w], oscale=mlp.scale, x_rot=(mlp.SU_ug, 1.0 / mlp.scale),
-                          x_rms=(eps, layer.post_attention_layernorm.weight), act_out=act16, act_su=mlp.SU_dp if fuse28 else None)
-            if fuse28:  # the 28 x 512 rotation inside down_proj's x staging (csrc/rot_k28.h): no launch of its own
-                qp.multi_gemv([mlp.down_proj], act16, outs=[h32], wscales=[mlp.Wscale_dp], oscale=mlp.scale,
-                              x_rot=(None, 1.0 / mlp.scale, mlp.had_left_dp_T, mlp.inter_K), accumulate=True)
-                return
-            xr = qp.hadamard.rotate(act16, hadK=mlp.had_left_dp_T, K=mlp.inter_K, su=mlp.SU_dp, post_scale=1.0 / mlp.scale)
-            qp.multi_gemv([mlp.down_proj], xr, outs=[h32], wscales=[mlp.Wscale_dp], oscale=mlp.scale,
-                          accumulate=True)
-            return
-        if rot_in_gemv:
-            qp.multi_gemv(ugl, h32, outs=ug_outs, wscales=ugw, oscale=mlp.scale, x_rot=(mlp.SU_ug, 1.0 / mlp.scale),
-                          x_rms=(eps, layer.post_attention_layernorm.weight))
-        else:
-            hk, K = _hid(mlp, "_hadk_hidden")
-            xr = qp.hadamard.rotate(h32, hadK=hk, K=K, su=mlp.SU_ug, post_scale=1.0 / mlp.scale, in_mode=qp.hadamard.IN_F32,
-                                    rms=(eps, layer.post_attention_layernorm.weight))
-            qp.multi_gemv(ugl, xr, outs=ug_outs, wscales=ugw, oscale=mlp.scale)
-        xr = qp.hadamard.rotate(ug32, hadK=mlp.had_left_dp_T, K=mlp.inter_K, su=mlp.SU_dp, post_scale=1.0 / mlp.scale,
-                                in_mode=qp.hadamard.IN_SWIGLU_F32)
-        qp.multi_gemv([mlp.down_proj], xr, outs=[h32], wscales=[mlp.Wscale_dp], oscale=mlp.scale,
-                      accumulate=True)
-
-    def fused_step():
-        h32.copy_(embed[tok].view(1, H))
-        mask = torch.where(ar <= pos, 0.0, float("-inf")).half().view(1, 1, 1, -1)
-        for idx, layer in enumerate(layers):
-            fused_layer(idx, layer, mask)
-        if args.torch_lm_head:
-            hn = norm(h32.half().view(1, 1, H))
-            logits = hn.view(1, H) @ lm_head.T
-            out_tok.copy_(logits.argmax(-1))
-            return hn
-        with torch.cuda.device(dev):  # final RMSNorm + lm_head GEMV + argmax: one launch
-            rc = nat.lib().qpal_lm_head_argmax(h32.data_ptr(), norm.weight.data_ptr(), norm.eps, lm_head.data_ptr(), None,
-                                               out_tok.data_ptr(), lm_ws.data_ptr(), lm_ws_bytes, args.vocab, H,
-                                               torch.cuda.current_stream(dev).cuda_stream)
-        nat.check(rc, "qpal_lm_head_argmax")
-        return norm(h32.half().view(1, 1, H)) if want_hidden[0] else None
-
-    def _tc(l):
-        return isinstance(l, qp.linear._base.PackedLinearBase) and not isinstance(l, qp.VQLinearPackSIMT)
-
-    fusable = (not args.no_fused and
-               all(all(_tc(p_) for p_ in l.self_attn._qkv_layout()[0]) and _tc(l.self_attn.o_proj) and _tc(l.mlp.down_proj)
-                   and all(_tc(p_) for p_ in ([l.mlp.ug_proj] if l.mlp.merge_ug else [l.mlp.up_proj, l.mlp.gate_proj]))
-                   and (not rot_in_gemv or (qp.linear.rotation_fusable(l.self_attn._qkv_layout()[0], 1)
-                                            and qp.linear.rotation_fusable([l.self_attn.o_proj], 1)))
-                   for l in layers))
-
-    def timed_fused():
-        s = torch.cuda.Stream(dev)
-        with torch.cuda.stream(s):
-            fused_step()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=s):
-                fused_step()
-            return _time_tokens(g, True)
+    # ---- fused glue (MI355X decoder block, qpalette_amd.decoder): 5 / 6 / 9 launches per layer instead of ~41
+    fused = None
+    if not args.no_fused and qp.decoder.fusable(layers):
+        fused = qp.DecodeStep(layers, embed, norm, lm_head, cache.k, cache.v, inv_freq, tok, pos, out_tok,
+                              swiglu_epilogue=not args.no_swiglu_epilogue, k28_fusion=not args.no_k28_fusion,
+                              native_lm_head=not args.torch_lm_head, split_attention=not args.no_split_attention)
 
     # the fused step computes what the modular step computes (fp32 residual stream instead of fp16: small differences)
     check = None
-    if fusable and not args.no_modular:
+    if fused and not args.no_modular:
         tok.zero_()
         pos.fill_(3)
         ref_h = norm(step(True).view(1, 1, H)).float()
         tok.zero_()
         pos.fill_(3)
-        want_hidden[0] = True
-        got_h = fused_step().float()
-        want_hidden[0] = False
+        fused()
+        got_h = fused.hidden().float()  # an extra torch norm, not timed
         check = {"max_abs_diff_final_norm": float((ref_h - got_h).abs().max()), "max_abs_ref": float(ref_h.abs().max())}
     if args.no_modular:
-        if not fusable:
+        if not fused:
             raise SystemExit("--no-modular: this configuration has no fused-glue step")
-        t_fused = timed_fused()
-        # kernel launches of one fused step: per layer q|k|v (+ its rotation where the GEMV cannot rotate), attention, o (+ rotation),
-        # up|gate (+ rotation), SwiGLU rotation, down; + the norm / lm_head / argmax launch (the embedding row copy is a memcpy node)
-        per_layer = (5 if k28_in_gemv(layers[0].mlp) else 6) if rot_in_gemv else 9
+        t_fused = timed(fused)
         if not quiet:
             print(json.dumps({"model": args.model, "layers": nlayers, "quantizer": args.qdict or args.quantizer, "context": args.context,
                               "tokens_per_s_fused_glue": 1.0 / t_fused, "ms_fused_glue": t_fused * 1e3}))
-        return {"ms_whole_step": None, "ms_fused_glue": t_fused * 1e3, "check": None, "launches_per_token": per_layer * nlayers + 1}
-    t_full = timed(True)
-    t_proj = timed(False)
-    t_fused = timed_fused() if fusable else None
+        return {"ms_whole_step": None, "ms_fused_glue": t_fused * 1e3, "check": None, "launches_per_token": fused.launches_per_token}
+    t_full = timed(step)
+    t_proj = timed(lambda: step(False), None)
+    t_fused = timed(fused) if fused else None
     finite = bool(torch.isfinite(step(True)).all())
     packed = sum(t.numel() * t.element_size() for m in layers.modules() for name in ("trellis", "trellis1", "trellis2", "qweight")
                  if (t := getattr(m, name, None)) is not None)

@@ -4,7 +4,7 @@
 The model is perf/decode_llama.py's (same random layers from this package's modules, same --model / --layers / --quantizer /
 --qdict / --vocab), with per-layer KV caches [B][nkv][context][hd].  The B sequences sit at ragged, seeded positions; with
 --inactive N the last N slots carry pos = -1 (free slots of a continuous-batching server: they cost nothing and change nothing).
-One step at batch B:
+One step at batch B (qpalette_amd.decoder.DecodeStep; a batch of one runs the same way here, generic=True):
 
   1. RMSNorm + sign flip + Hadamard rotation of the fp32 residual stream [B, H] (hadamard.rotate(..., rms=...): one launch)
   2. q|k|v through multi_gemv (fp32 out [B, nq*hd + 2*nkv*hd])
@@ -21,18 +21,15 @@ rotary embedding, a per-sequence cache write, SDPA with a per-sequence mask), wh
 """
 import argparse
 import json
-import math
 import os
 import sys
-import types
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
-import torch.nn as nn
 
 import qpalette_amd as qp
-from decode_llama import LINEARS, DecoderLayer, RMSNorm  # noqa: F401  (LINEARS: the projection names the layers are built from)
+from decode_llama import build_model, time_graph
 
 
 class BatchKV:
@@ -73,38 +70,9 @@ def main(argv=None, quiet=False):
     if args.context % 4 or args.context < args.tokens + 16:
         raise SystemExit("--context: a multiple of 4, at least --tokens + 16")
     dev = torch.device("cuda", 0)
-    li = qp.mem_op.get_layer_info(args.model)
-    H, I = li["mlp.gate_proj"]["in_features"], li["mlp.gate_proj"]["out_features"]
-    kv_out = li["self_attn.k_proj"]["out_features"]
-    head_dim = 128
-    cfg = types.SimpleNamespace(hidden_size=H, intermediate_size=I, hidden_act="silu", num_attention_heads=H // head_dim,
-                                num_key_value_heads=kv_out // head_dim, head_dim=head_dim, attention_dropout=0.0)
-    nq, nkv = cfg.num_attention_heads, cfg.num_key_value_heads
-    nlayers = args.layers or li["nlayers"]
-    qdict, merge_info = None, None
-    if args.qdict:
-        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "qdicts", args.qdict + ".json")) as f:
-            data = json.load(f)
-        qdict, merge_info = data["qdict"], data["merge_info"]
-
-    def qof(layer, key):
-        if qdict is None:
-            return args.quantizer, False
-        q, simt = qdict[f"{layer}_{key}"]
-        return q, simt == "1"
-
-    gen = torch.Generator(device=dev).manual_seed(1234)
-    layers = nn.ModuleList([DecoderLayer(cfg, args.model, i, qof, set(merge_info[i]) if merge_info else set(), dev, gen)
-                            for i in range(nlayers)])
-    qp.share_codebooks([m for m in layers.modules() if hasattr(m, "tlut") or hasattr(m, "lut")])
-    embed = (torch.randn(args.vocab, H, device=dev, generator=gen) * 0.5).half()
-    lm_head = (torch.randn(args.vocab, H, device=dev, generator=gen) * 0.02).half()
-    norm = RMSNorm(H).to(dev)
-    inv_freq = 1.0 / (500000.0 ** (torch.arange(0, head_dim, 2, device=dev).float() / head_dim))
-    eps = layers[0].input_layernorm.eps
-    had = qp.hadamard
-    hk_hidden, K_hidden = had.get_hadK(H)
-    hk_hidden = None if hk_hidden is None else hk_hidden.T.contiguous().half().to(dev)
+    m = build_model(args.model, args.quantizer, args.qdict, args.layers, args.vocab, dev)
+    cfg, layers, embed, lm_head, norm, inv_freq = m.cfg, m.layers, m.embed, m.lm_head, m.norm, m.inv_freq
+    H, I, nkv, head_dim, nlayers = cfg.hidden_size, cfg.intermediate_size, cfg.num_key_value_heads, cfg.head_dim, len(layers)
 
     def run_batch(B):
         nact = B - args.inactive
@@ -126,57 +94,23 @@ def main(argv=None, quiet=False):
         cg = torch.Generator(device=dev).manual_seed(args.seed)
         kc = [(torch.randn(B, nkv, args.context, head_dim, device=dev, generator=cg) * 0.5).half() for _ in range(nlayers)]
         vc = [(torch.randn(B, nkv, args.context, head_dim, device=dev, generator=cg) * 0.5).half() for _ in range(nlayers)]
-        ws = qp.attention_workspace(B, nq, nkv, head_dim, args.context, dev)
-        h32 = torch.zeros(B, H, dtype=torch.float32, device=dev)
-        qkv32 = torch.zeros(B, H + 2 * kv_out, dtype=torch.float32, device=dev)
-        a16 = torch.zeros(B, H, dtype=torch.float16, device=dev)
-        ug32 = torch.zeros(B, 2 * I, dtype=torch.float32, device=dev)
+        # generic: the B = 1 row runs the way every other row runs (rotation launches, decode_attention, torch tail)
+        kernel_step = qp.DecodeStep(layers, embed, norm, lm_head, kc, vc, inv_freq, tok, pos, out_tok, generic=True)
         xh16 = torch.zeros(B, H, dtype=torch.float16, device=dev)      # linears-only: fixed rotated inputs
         xi16 = torch.zeros(B, I, dtype=torch.float16, device=dev)
-        want_hidden = [False]
 
-        def ug_layout(mlp):
-            inter = mlp.intermediate_size
-            if mlp.merge_ug:
-                return [mlp.ug_proj], [mlp.Wscale_ug]
-            return [mlp.up_proj, mlp.gate_proj], [mlp.Wscale_ug[:inter], mlp.Wscale_ug[inter:]]
-
-        def layer_step(idx, layer, glue):
-            att, mlp = layer.self_attn, layer.mlp
-            proj, wsc, blocks = att._qkv_layout()
-            outs = list(qkv32.split([l.out_features for l in proj], dim=1))
-            ugl, ugw = ug_layout(mlp)
-            ug_outs = list(ug32.split([l.out_features for l in ugl], dim=1))
-            if not glue:
-                qp.multi_gemv(proj, xh16, outs=outs, wscales=wsc, oscale=att.scale)
-                qp.multi_gemv([att.o_proj], xh16, outs=[h32], wscales=[att.Wscale_o], oscale=att.scale, accumulate=True)
-                qp.multi_gemv(ugl, xh16, outs=ug_outs, wscales=ugw, oscale=mlp.scale)
-                qp.multi_gemv([mlp.down_proj], xi16, outs=[h32], wscales=[mlp.Wscale_dp], oscale=mlp.scale, accumulate=True)
-                return
-            xr = had.rotate(h32, hadK=hk_hidden, K=K_hidden, su=att.SU_qkv, post_scale=1.0 / att.scale, in_mode=had.IN_F32,
-                            rms=(eps, layer.input_layernorm.weight))
-            qp.multi_gemv(proj, xr, outs=outs, wscales=wsc, oscale=att.scale)
-            parts = dict(zip([b[0] for b in blocks], qkv32.split([b[1] for b in blocks], dim=1)))
-            qp.decode_attention(parts["q"], parts["k"], parts["v"], kc[idx], vc[idx], pos, inv_freq,
-                                scale=1.0 / math.sqrt(head_dim), out=a16, ws=ws)
-            xr = had.rotate(a16, hadK=hk_hidden, K=K_hidden, su=att.SU_o, post_scale=1.0 / att.scale)
-            qp.multi_gemv([att.o_proj], xr, outs=[h32], wscales=[att.Wscale_o], oscale=att.scale, accumulate=True)
-            xr = had.rotate(h32, hadK=hk_hidden, K=K_hidden, su=mlp.SU_ug, post_scale=1.0 / mlp.scale, in_mode=had.IN_F32,
-                            rms=(eps, layer.post_attention_layernorm.weight))
-            qp.multi_gemv(ugl, xr, outs=ug_outs, wscales=ugw, oscale=mlp.scale)
-            xr = had.rotate(ug32, hadK=mlp.had_left_dp_T, K=mlp.inter_K, su=mlp.SU_dp, post_scale=1.0 / mlp.scale,
-                            in_mode=had.IN_SWIGLU_F32)
-            qp.multi_gemv([mlp.down_proj], xr, outs=[h32], wscales=[mlp.Wscale_dp], oscale=mlp.scale, accumulate=True)
-
-        def kernel_step(glue=True):
+        def linears_only():
+            """the four projection groups of every layer alone, into the step's buffers"""
+            h32, qkv32, ug32 = kernel_step.h32, kernel_step.qkv32, kernel_step.ug32
             h32.copy_(embed[tok])
-            for idx, layer in enumerate(layers):
-                layer_step(idx, layer, glue)
-            if not glue:
-                return None
-            hn = norm(h32.half())
-            out_tok.copy_((hn @ lm_head.T).argmax(-1))
-            return hn if want_hidden[0] else None
+            for layer in layers:
+                att, mlp = layer.self_attn, layer.mlp
+                proj, wsc, _ = att._qkv_layout()
+                ugl, ugw = qp.decoder.ug_layout(mlp)
+                qp.multi_gemv(proj, xh16, outs=list(qkv32.split([l.out_features for l in proj], dim=1)), wscales=wsc, oscale=att.scale)
+                qp.multi_gemv([att.o_proj], xh16, outs=[h32], wscales=[att.Wscale_o], oscale=att.scale, accumulate=True)
+                qp.multi_gemv(ugl, xh16, outs=list(ug32.split([l.out_features for l in ugl], dim=1)), wscales=ugw, oscale=mlp.scale)
+                qp.multi_gemv([mlp.down_proj], xi16, outs=[h32], wscales=[mlp.Wscale_dp], oscale=mlp.scale, accumulate=True)
 
         # torch-glue reference at the same B: the Incoherent* modules, torch rope, per-sequence cache rows, SDPA with a mask per sequence
         ref_cache = BatchKV(kc, vc)
@@ -195,31 +129,15 @@ def main(argv=None, quiet=False):
             out_tok.copy_((hn @ lm_head.T).argmax(-1))
             return hn
 
-        def timed(fn, feed):
-            s = torch.cuda.Stream(dev)
-            with torch.cuda.stream(s):
-                fn()
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, stream=s):
-                    fn()
+        def feed(i):
+            """next token at the next position of every active sequence"""
+            tok.copy_(out_tok)
+            torch.add(pos0, inc, alpha=i, out=pos)
 
-                def one(i):
-                    if feed:                                   # next token at the next position of every active sequence
-                        tok.copy_(out_tok)
-                        torch.add(pos0, inc, alpha=i, out=pos)
-                    graph.replay()
-                for i in range(8):
-                    one(i)
-                torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for i in range(args.tokens):
-                    one(8 + i)
-                e1.record()
-                torch.cuda.synchronize()
+        def timed(fn, before=feed):
+            ms = time_graph(fn, args.tokens, dev, before)
             pos.copy_(pos0)
-            return e0.elapsed_time(e1) / args.tokens  # ms per step
+            return ms  # per step
 
         check = None
         if not args.no_torch_glue:
@@ -231,21 +149,20 @@ def main(argv=None, quiet=False):
             for t, t0 in zip(kc + vc, kc0 + vc0):
                 t.copy_(t0)
             del kc0, vc0
-            want_hidden[0] = True
-            got_h = kernel_step().float()
-            want_hidden[0] = False
+            kernel_step()
+            got_h = kernel_step.hidden().float()
             act = pos0 >= 0
             d = (ref_h[act] - got_h[act]).abs()
             check = {"max_abs_diff_final_norm": float(d.max()), "max_abs_ref": float(ref_h[act].abs().max()),
                      "finite": bool(torch.isfinite(got_h[act]).all())}
-        ms_step = timed(kernel_step, True)
-        ms_lin = timed(lambda: kernel_step(False), False)
-        ms_torch = None if args.no_torch_glue else timed(torch_step, True)
+        ms_step = timed(kernel_step)
+        ms_lin = timed(linears_only, None)
+        ms_torch = None if args.no_torch_glue else timed(torch_step)
         res = {"batch": B, "active": nact, "ms_step": ms_step, "tokens_per_s": nact / ms_step * 1e3,
                "ms_linears_only": ms_lin, "ms_torch_glue": ms_torch,
                "tokens_per_s_torch_glue": None if ms_torch is None else nact / ms_torch * 1e3,
                "kv_rows_attended_first_step": int((pos0[pos0 >= 0] + 1).sum()), "check": check}
-        del kc, vc, ref_cache
+        del kc, vc, ref_cache, kernel_step
         torch.cuda.empty_cache()
         return res
 

@@ -1,0 +1,184 @@
+"""Whole-model decode step of a Llama-shaped model on this library's kernels: B >= 1 sequences, one token each per step.
+
+The residual stream stays fp32 ([B, H]).  Per layer: q|k|v -> rotary embedding + KV append + attention (one launch) -> o_proj
+(ADDS into the stream) -> up|gate -> SwiGLU -> down_proj (adds into the stream); then final norm, lm_head and argmax.  Every
+projection group reads rotate(RMSNorm(x) * su) / scale: inside the GEMV launch where its staging can rotate the hidden width
+(batch 1, k in {2048, 4096}), as one `hadamard.rotate` launch in front of the plain GEMV launch otherwise.
+
+At batch 1 the step also takes what only exists there: up|gate as one interleaved layer whose epilogue writes
+fp16 silu(gate) * up, down_proj's 28 x 512 rotation inside its own staging, `qpal_attn_rope_decode` with its split-context
+workspace, and `qpal_lm_head_argmax`: 5 or 6 launches per layer, 9 where the hidden width has to be rotated by a launch of its
+own (70B: 8192).  `generic=True` runs a batch of one the way every larger batch runs.
+
+    step = DecodeStep(layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok)
+    step()                      # capturable: reads tok / pos, updates the caches at pos, writes out_tok
+"""
+import math
+
+import torch
+
+from . import _native as nat
+from . import hadamard as had
+from . import linear, ops
+from .attention import attention_workspace, decode_attention
+from .linear import multi_gemv
+
+
+def ug_layout(mlp):
+    """(layers, their Wscale slices) of an IncoherentMLP's up|gate group"""
+    inter = mlp.intermediate_size
+    if mlp.merge_ug:
+        return [mlp.ug_proj], [mlp.Wscale_ug]
+    return [mlp.up_proj, mlp.gate_proj], [mlp.Wscale_ug[:inter], mlp.Wscale_ug[inter:]]
+
+
+def _tc(l):
+    return isinstance(l, linear._base.PackedLinearBase) and not isinstance(l, linear.VQLinearPackSIMT)
+
+
+def fusable(layers):
+    """True if the batch-1 step can run on `layers`: tensor-core-order projections, and codecs with a multi-job launch where the
+    GEMV staging is to rotate the hidden width."""
+    rot_in_gemv = ops.can_fuse_rotation(1, layers[0].self_attn.hidden_size)
+    return all(all(_tc(p) for p in l.self_attn._qkv_layout()[0] + ug_layout(l.mlp)[0] + [l.self_attn.o_proj, l.mlp.down_proj])
+               and (not rot_in_gemv or (linear.rotation_fusable(l.self_attn._qkv_layout()[0], 1)
+                                        and linear.rotation_fusable([l.self_attn.o_proj], 1)))
+               for l in layers)
+
+
+def k28_in_gemv(mlp):
+    """down_proj's rotation inside its own launch: k = 14336 = 28 x 512, a tensor-core-order layer whose codebook image can lend
+    the rotation its scratch (every TCQ codec)."""
+    if mlp.inter_K <= 1 or not ops.can_fuse_rotation(1, mlp.intermediate_size, mlp.inter_K):
+        return False
+    d = mlp.down_proj
+    if isinstance(d, linear.VQLinearPackTensorCore):
+        idx = d.lut_bits if d.vec_sz == 2 else (2 * d.lut_bits if d.lut_bits <= 6 else d.lut_bits)
+        return (4 << (idx + min(15 - idx, 5))) >= 40 * 1024
+    return isinstance(d, (linear.QTIPLinearTCQ, linear.CombtLinearTCQ)) and linear._codec_key(d)[0] != "single"
+
+
+class DecodeStep:
+    """layers: modules with self_attn (IncoherentSdpaAttention), mlp (IncoherentMLP), input_layernorm, post_attention_layernorm;
+    embed / lm_head fp16 [vocab, H]; norm: the final RMSNorm; kcache / vcache: per-layer fp16 [B, nkv, context, hd]; inv_freq fp32
+    [hd / 2]; tok, pos, out_tok int64 [B] (pos[b] outside the cache: sequence b is inactive).  The caller owns the caches and
+    tok / pos / out_tok and may write them between replays of a captured step.  swiglu_epilogue, k28_fusion, native_lm_head,
+    split_attention switch single fusions of the batch-1 step off (profiling)."""
+
+    def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok, generic=False,
+                 swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True):
+        att, mlp = layers[0].self_attn, layers[0].mlp
+        B, H, dev = tok.shape[0], att.hidden_size, embed.device
+        self.layers, self.embed, self.norm, self.lm_head, self.inv_freq = layers, embed, norm, lm_head, inv_freq
+        self.kcache, self.vcache, self.tok, self.pos, self.out_tok = kcache, vcache, tok, pos, out_tok
+        self.nq, self.nkv, self.head_dim, self.context = att.num_heads, att.num_key_value_heads, att.head_dim, kcache[0].shape[2]
+        self.eps = layers[0].input_layernorm.eps
+        self.batch1 = B == 1 and not generic
+        if self.batch1 and not fusable(layers):
+            raise nat.QpalError("DecodeStep: these layers have no batch-1 step (fusable(layers))")
+        self.rot_in_gemv = self.batch1 and ops.can_fuse_rotation(1, H)  # k in {2048, 4096}: the GEMV staging rotates x itself
+        hk, self.hidden_K = had.get_hadK(H)
+        self.hidden_hadT = None if hk is None else hk.T.contiguous().half().to(dev)
+        self.h32 = torch.zeros(B, H, dtype=torch.float32, device=dev)
+        self.a16 = torch.zeros(B, H, dtype=torch.float16, device=dev)
+        self.qkv32 = torch.zeros(B, H + 2 * att.kv_out, dtype=torch.float32, device=dev)
+        self.ug32 = torch.zeros(B, 2 * mlp.intermediate_size, dtype=torch.float32, device=dev)
+        self.ug_il = self.lm_ws = None
+        if self.rot_in_gemv and swiglu_epilogue:
+            # up | gate as ONE layer with interleaved supertile rows: the launch's epilogue writes fp16 silu(gate) * up itself
+            self.act16 = torch.zeros(1, mlp.intermediate_size, dtype=torch.float16, device=dev)
+            self.ug_il = []
+            for m in (l.mlp for l in layers):
+                il = linear.interleave_up_gate(m.ug_proj, None) if m.merge_ug else linear.interleave_up_gate(m.up_proj, m.gate_proj)
+                linear.share_codebooks([il, m.down_proj] + ug_layout(m)[0])
+                inter = m.intermediate_size
+                self.ug_il.append((il, linear.interleave_rows(m.Wscale_ug[:inter], m.Wscale_ug[inter:]),
+                                   k28_fusion and k28_in_gemv(m)))
+        if self.batch1:
+            # long caches: split-context attention (one workspace serves every layer: launches are stream-ordered)
+            self.attn_ws_bytes = nat.lib().qpal_attn_ws_bytes(self.nq, self.nkv, self.head_dim, self.context) if split_attention else 0
+            self.attn_ws = torch.zeros(max(self.attn_ws_bytes, 4) // 4, dtype=torch.float32, device=dev)
+            if native_lm_head:
+                self.lm_ws_bytes = nat.lib().qpal_lm_head_ws_bytes(lm_head.shape[0])
+                self.lm_ws = torch.zeros(self.lm_ws_bytes // 4, dtype=torch.float32, device=dev)
+        else:
+            self.attn_ws = attention_workspace(B, self.nq, self.nkv, self.head_dim, self.context, dev)
+
+    @property
+    def launches_per_token(self):
+        """kernel launches of one step: per layer q|k|v, attention, o, up|gate, SwiGLU rotation, down (+ a rotation in front of
+        q|k|v, o and up|gate where the GEMV cannot rotate; - the SwiGLU rotation where down_proj's staging runs it); + the norm /
+        lm_head / argmax launch (the embedding row copy is a memcpy node)"""
+        per_layer = (5 if self.ug_il and self.ug_il[0][2] else 6) if self.rot_in_gemv else 9
+        return per_layer * len(self.layers) + 1
+
+    def _gemv(self, proj, x, su, scale, rms=None, **kw):
+        """multi_gemv of one projection group on rotate(RMSNorm(x) * su) / scale: RMSNorm + rotation inside the GEMV launch, or
+        (wider hidden sizes, 70B: 8192, and every batch > 1) as ONE launch of their own, then the plain GEMV launch"""
+        if self.rot_in_gemv:
+            return multi_gemv(proj, x, oscale=scale, x_rot=(su, 1.0 / scale), x_rms=rms, **kw)
+        xr = had.rotate(x, hadK=self.hidden_hadT, K=self.hidden_K, su=su, post_scale=1.0 / scale, rms=rms,
+                        in_mode=had.IN_F32 if x.dtype == torch.float32 else had.IN_F16)
+        return multi_gemv(proj, xr, oscale=scale, **kw)
+
+    def _attention(self, i, q, k, v):
+        scale = 1.0 / math.sqrt(self.head_dim)
+        if not self.batch1:
+            decode_attention(q, k, v, self.kcache[i], self.vcache[i], self.pos, self.inv_freq, scale=scale, out=self.a16, ws=self.attn_ws)
+            return
+        dev = self.h32.device
+        with torch.cuda.device(dev):
+            rc = nat.lib().qpal_attn_rope_decode(q.data_ptr(), k.data_ptr(), v.data_ptr(), self.kcache[i].data_ptr(),
+                                                 self.vcache[i].data_ptr(), self.a16.data_ptr(), self.pos.data_ptr(),
+                                                 self.inv_freq.data_ptr(), self.nq, self.nkv, self.head_dim, self.context, scale,
+                                                 self.attn_ws.data_ptr() if self.attn_ws_bytes else None, self.attn_ws_bytes,
+                                                 torch.cuda.current_stream(dev).cuda_stream)
+        nat.check(rc, "qpal_attn_rope_decode")
+
+    def _layer(self, i):
+        layer, h32 = self.layers[i], self.h32
+        att, mlp = layer.self_attn, layer.mlp
+        proj, wsc, blocks = att._qkv_layout()
+        self._gemv(proj, h32, att.SU_qkv, att.scale, rms=(self.eps, layer.input_layernorm.weight), wscales=wsc,
+                   outs=list(self.qkv32.split([l.out_features for l in proj], dim=1)))
+        parts = dict(zip([b[0] for b in blocks], self.qkv32.split([b[1] for b in blocks], dim=1)))
+        self._attention(i, parts["q"], parts["k"], parts["v"])
+        self._gemv([att.o_proj], self.a16, att.SU_o, att.scale, wscales=[att.Wscale_o], outs=[h32], accumulate=True)
+        rms = (self.eps, layer.post_attention_layernorm.weight)
+        dp_rot = dict(hadK=mlp.had_left_dp_T, K=mlp.inter_K, su=mlp.SU_dp, post_scale=1.0 / mlp.scale)
+        x_rot = None
+        if self.ug_il:
+            il, il_w, fuse28 = self.ug_il[i]
+            # with the fused rotation the gate|up epilogue also applies down_proj's sign vector (a sign flip: exact), so the rotation
+            # inside every down_proj workgroup reads one 28 KiB vector instead of two
+            self._gemv([il], h32, mlp.SU_ug, mlp.scale, rms=rms, wscales=[il_w], act_out=self.act16,
+                       act_su=mlp.SU_dp if fuse28 else None)
+            if fuse28:  # the 28 x 512 rotation inside down_proj's x staging (csrc/rot_k28.h): no launch of its own
+                x, x_rot = self.act16, (None, 1.0 / mlp.scale, mlp.had_left_dp_T, mlp.inter_K)
+            else:
+                x = had.rotate(self.act16, **dp_rot)
+        else:
+            ugl, ugw = ug_layout(mlp)
+            self._gemv(ugl, h32, mlp.SU_ug, mlp.scale, rms=rms, wscales=ugw,
+                       outs=list(self.ug32.split([l.out_features for l in ugl], dim=1)))
+            x = had.rotate(self.ug32, in_mode=had.IN_SWIGLU_F32, **dp_rot)
+        multi_gemv([mlp.down_proj], x, outs=[h32], wscales=[mlp.Wscale_dp], oscale=mlp.scale, x_rot=x_rot, accumulate=True)
+
+    def hidden(self):
+        """fp16 [B, H]: the final norm of the residual stream the last step left (a torch op: for checks, not part of the step)"""
+        return self.norm(self.h32.half())
+
+    def __call__(self):
+        self.h32.copy_(self.embed[self.tok])
+        for i in range(len(self.layers)):
+            self._layer(i)
+        if self.lm_ws is None:
+            self.out_tok.copy_((self.hidden() @ self.lm_head.T).argmax(-1))
+            return
+        dev = self.h32.device
+        with torch.cuda.device(dev):  # final RMSNorm + lm_head GEMV + argmax: one launch
+            rc = nat.lib().qpal_lm_head_argmax(self.h32.data_ptr(), self.norm.weight.data_ptr(), self.norm.eps, self.lm_head.data_ptr(),
+                                               None, self.out_tok.data_ptr(), self.lm_ws.data_ptr(), self.lm_ws_bytes,
+                                               self.lm_head.shape[0], self.h32.shape[1],
+                                               torch.cuda.current_stream(dev).cuda_stream)
+        nat.check(rc, "qpal_lm_head_argmax")
