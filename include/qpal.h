@@ -338,6 +338,25 @@ int qpal_attn_rope_decode_batch(const float *q, const float *k, const float *v, 
                                 const long *pos, const float *inv_freq, int B, int nq, int nkv, int hd,
                                 long max_len, float scale, void *ws, long ws_bytes, void *stream);
 
+/* Prompt prefill attention of ONE sequence, one launch (csrc/attn_prefill.hip): T new tokens at positions *pos0 .. *pos0 + T - 1.
+ * Rotary embedding of their q and k (qpal_rope_kv's convention), k and v appended as fp16 to the cache at rows *pos0 + t (bit for
+ * bit what qpal_rope_kv writes there; no other cache byte changes), and causal attention: row t over positions 0 .. *pos0 + t
+ * (the existing context plus new rows 0 .. t), both products on the matrix pipe, online softmax, fp32 accumulation, fp16 out.
+ * q / k / v: fp32 rows [T][ld_qkv] as for qpal_attn_rope_decode_batch (row t = the token at *pos0 + t); caches fp16
+ * [nkv][max_len][hd] of one sequence, 16-byte aligned (kcache[b] of the batched layout is one); out fp16 [T][ld_out],
+ * out[t][h * hd + d]; pos0 int64 on the device (never read by the host: graph-capturable with a position that changes between
+ * replays); inv_freq fp32 [hd / 2].  hd in {64, 128, 256}; nq / nkv in {1, 2, 4, 8} with (nq / nkv) * hd <= 1024; 1 <= T <= 128;
+ * max_len % 4 == 0, up to 64 k.  *pos0 < 0 or *pos0 + T > max_len: the launch does nothing (no cache byte, no out byte).
+ * New rows reach the products from the fp32 inputs, never from the cache: nothing the launch reads from the cache was written by
+ * it.  ws: qpal_attn_prefill_ws_bytes(T, ...) bytes of device memory, 4-byte aligned, zero-filled ONCE, kept across launches
+ * (split-context partials and tickets, merged in a fixed order: two launches are bitwise equal); 0: no workspace needed, pass
+ * ws = NULL (max_len < 512).  The size is monotone in T and max_len: one workspace serves every layer and every shorter chunk. */
+long qpal_attn_prefill_ws_bytes(int T, int nq, int nkv, int hd, long max_len);
+int qpal_attn_rope_prefill(const float *q, const float *k, const float *v, long ld_qkv,
+                           void *kcache_f16, void *vcache_f16, void *out_f16, long ld_out,
+                           const long *pos0, const float *inv_freq, int T, int nq, int nkv, int hd,
+                           long max_len, float scale, void *ws, long ws_bytes, void *stream);
+
 /* The launch planner of the fused GEMV entry points, on its own (host code, no GPU call; what tests and tools inspect).
  * A launch of njobs jobs — rows[j] supertile rows (m / 32) of steps1[j] + steps2[j] steps (a step = 128 columns; steps2 = 0: one
  * stream) — is cut into workgroup-sized pieces: a GROUP of G = 1 << lg_g workgroups (`waves` = 16 or 8 waves each) owns rg

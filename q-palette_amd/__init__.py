@@ -9,7 +9,8 @@ Layout:
                    (lib/utils/mem_op.py:2-307)
   hadamard.py      get_hadK (generated Paley factors), matmul_hadU*_cuda, the one-launch `rotate` (lib/utils/matmul_had.py)
   linear/incoherent_linear.py  IncoherentLinear / IncoherentMLP / IncoherentSdpaAttention (lib/linear/incoherent_linear.py)
-  attention.py     decode_attention / attention_workspace: rope + KV append + GQA attention of B sequences, one launch
+  attention.py     decode_attention / attention_workspace: rope + KV append + GQA attention of B sequences, one launch;
+                   prefill_attention / prefill_workspace: the same for up to 128 new tokens of one sequence, causal
   decoder.py       DecodeStep: the whole-model decode step at batch B >= 1 on the kernels above (per-layer launch sequence,
                    scratch buffers, final norm + lm_head + argmax, launches per token)
   packers.py       pack_trellis / pack_qweight / pack_qweight_{sq,vq}_simt on the C-ABI's host-side encoders
@@ -45,9 +46,9 @@ from .linear import (  # noqa: F401
 from . import quantize  # noqa: F401
 from . import quantize_layer  # noqa: F401
 from . import attention  # noqa: F401
-from .attention import attention_workspace, decode_attention  # noqa: F401
+from .attention import attention_workspace, decode_attention, prefill_attention, prefill_workspace  # noqa: F401
 from . import decoder  # noqa: F401
-from .decoder import DecodeStep  # noqa: F401
+from .decoder import DecodeStep, Prefill  # noqa: F401
 from .quantize_layer import incoherent_preprocess, layer_file_path, load_hessian, quantize_linear  # noqa: F401
 
 __version__ = "0.1.0"

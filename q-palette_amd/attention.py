@@ -6,6 +6,12 @@ KV cache at ``pos[b]``, and attention over its positions ``0 .. pos[b]``.  A seq
 
     ws = attention_workspace(B, nq, nkv, hd, max_len, device)      # once, shared by every layer
     out = decode_attention(q, k, v, kcache, vcache, pos, inv_freq, ws=ws)
+
+Prompt prefill of ONE sequence (``qpal_attn_rope_prefill``, csrc/attn_prefill.hip): T <= 128 new tokens at positions ``pos0 ..
+pos0 + T - 1`` in one launch, appended to that sequence's cache, every row attending causally to everything before it.
+
+    ws = prefill_workspace(128, nq, nkv, hd, max_len, device)      # once, shared by every layer and every shorter chunk
+    out = prefill_attention(q, k, v, kcache[b], vcache[b], pos0, inv_freq, ws=ws)
 """
 import math
 
@@ -24,13 +30,13 @@ def attention_workspace(B, nq, nkv, hd, max_len, device):
     return torch.zeros((n + 3) // 4, dtype=torch.float32, device=device)
 
 
-def _rows(t, name, B, width):
+def _rows(t, name, B, width, who="decode_attention"):
     if t.dtype != torch.float32 or not t.is_cuda:
-        raise QpalError(f"decode_attention: {name} must be an fp32 device tensor, got {t.dtype} on {t.device}")
+        raise QpalError(f"{who}: {name} must be an fp32 device tensor, got {t.dtype} on {t.device}")
     if t.dim() != 2 or t.shape[0] != B or t.shape[1] != width:
-        raise QpalError(f"decode_attention: {name} must have shape [{B}, {width}], got {list(t.shape)}")
+        raise QpalError(f"{who}: {name} must have shape [{B}, {width}], got {list(t.shape)}")
     if t.stride(1) != 1:
-        raise QpalError(f"decode_attention: {name} rows must be contiguous")
+        raise QpalError(f"{who}: {name} rows must be contiguous")
     return t.stride(0) if B > 1 else width
 
 
@@ -80,4 +86,66 @@ def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=Non
             ws.data_ptr() if need > 0 else None, ws.numel() * ws.element_size() if need > 0 else 0,
             torch.cuda.current_stream(kcache.device).cuda_stream)
     _native.check(rc, "qpal_attn_rope_decode_batch")
+    return out
+
+
+def prefill_workspace(T, nq, nkv, hd, max_len, device):
+    """The zero-filled workspace ``prefill_attention`` needs for chunks of up to T rows and a cache of up to max_len positions
+    (same nq, nkv, hd), or None where no launch of that shape needs one.  Keep it across launches: the kernel leaves it as it
+    found it."""
+    n = _native.lib().qpal_attn_prefill_ws_bytes(int(T), int(nq), int(nkv), int(hd), int(max_len))
+    if n <= 0:
+        return None
+    return torch.zeros((n + 3) // 4, dtype=torch.float32, device=device)
+
+
+def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=None, ws=None):
+    """q fp32 [T, nq*hd], k / v fp32 [T, nkv*hd], 1 <= T <= 128: row t is the token at position pos0 + t (rows may be strided:
+    column slices of one q|k|v output with a common row stride); kcache / vcache fp16 [nkv, max_len, hd] of ONE sequence,
+    contiguous, 16-byte aligned (``kcache[b]`` of the batched layout), updated in place at rows pos0 .. pos0 + T - 1; pos0 int64
+    [1] on the device; inv_freq fp32 [hd/2].  Returns out fp16 [T, nq*hd] (``out`` if given): row t attends to positions 0 ..
+    pos0 + t.  pos0 < 0 or pos0 + T > max_len: nothing is written, neither cache nor out.  scale defaults to 1/sqrt(hd).
+    Launches on the current stream."""
+    who = "prefill_attention"
+    if kcache.dim() != 3 or kcache.shape != vcache.shape:
+        raise QpalError(f"{who}: kcache / vcache must both have shape [nkv, max_len, hd]")
+    nkv, max_len, hd = kcache.shape
+    for name, t in (("kcache", kcache), ("vcache", vcache)):
+        if t.dtype != torch.float16 or not t.is_cuda or not t.is_contiguous():
+            raise QpalError(f"{who}: {name} must be a contiguous fp16 device tensor")
+        if t.data_ptr() % 16:
+            raise QpalError(f"{who}: {name} must be 16-byte aligned")
+    if q.dim() != 2 or not 1 <= q.shape[0] <= 128 or q.shape[1] % hd:
+        raise QpalError(f"{who}: q must have shape [T, nq*{hd}] with 1 <= T <= 128, got {list(q.shape)}")
+    T, nq = q.shape[0], q.shape[1] // hd
+    ld = _rows(q, "q", T, nq * hd, who)
+    for name, t in (("k", k), ("v", v)):
+        if _rows(t, name, T, nkv * hd, who) != ld and T > 1:
+            raise QpalError(f"{who}: q, k and v must share one row stride")
+    if pos0.dtype != torch.int64 or pos0.numel() != 1 or pos0.device != kcache.device:
+        raise QpalError(f"{who}: pos0 must be an int64 tensor of one element on {kcache.device}")
+    if inv_freq.dtype != torch.float32 or inv_freq.numel() != hd // 2 or inv_freq.device != kcache.device or not inv_freq.is_contiguous():
+        raise QpalError(f"{who}: inv_freq must be a contiguous fp32 [{hd // 2}] tensor on {kcache.device}")
+    if any(t.device != kcache.device for t in (q, k, v)):
+        raise QpalError(f"{who}: every tensor must be on the caches' device")
+    if out is None:
+        out = torch.empty(T, nq * hd, dtype=torch.float16, device=kcache.device)
+    elif out.dtype != torch.float16 or out.dim() != 2 or out.shape != (T, nq * hd) or out.stride(1) != 1 or out.device != kcache.device:
+        raise QpalError(f"{who}: out must be fp16 [{T}, {nq * hd}] with contiguous rows on {kcache.device}")
+    ld_out = out.stride(0) if T > 1 else nq * hd
+    lib = _native.lib()
+    need = lib.qpal_attn_prefill_ws_bytes(T, nq, nkv, hd, max_len)
+    if need > 0:
+        if ws is None:
+            raise QpalError(f"{who}: this shape needs a workspace (prefill_workspace(...))")
+        if ws.device != kcache.device or ws.numel() * ws.element_size() < need or not ws.is_contiguous():
+            raise QpalError(f"{who}: ws must be a contiguous device buffer of >= {need} bytes on {kcache.device}")
+    scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
+    with torch.cuda.device(kcache.device):
+        rc = lib.qpal_attn_rope_prefill(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
+            pos0.data_ptr(), inv_freq.data_ptr(), T, nq, nkv, hd, max_len, scale,
+            ws.data_ptr() if need > 0 else None, ws.numel() * ws.element_size() if need > 0 else 0,
+            torch.cuda.current_stream(kcache.device).cuda_stream)
+    _native.check(rc, "qpal_attn_rope_prefill")
     return out

@@ -12,6 +12,12 @@ own (70B: 8192).  `generic=True` runs a batch of one the way every larger batch 
 
     step = DecodeStep(layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok)
     step()                      # capturable: reads tok / pos, updates the caches at pos, writes out_tok
+
+`Prefill` takes a prompt into ONE slot of the same caches: the batch-B layer with rows = consecutive positions of one sequence,
+in chunks of at most 128 rows, with `prefill_attention` (causal, rows appended to the slot's cache) in the attention's place.
+
+    pf = Prefill(layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128)
+    next_tok = pf(tokens, slot=0, pos0=0)   # then DecodeStep with tok[slot] = next_tok, pos[slot] = len(tokens)
 """
 import math
 
@@ -20,7 +26,7 @@ import torch
 from . import _native as nat
 from . import hadamard as had
 from . import linear, ops
-from .attention import attention_workspace, decode_attention
+from .attention import attention_workspace, decode_attention, prefill_attention, prefill_workspace
 from .linear import multi_gemv
 
 
@@ -67,23 +73,14 @@ class DecodeStep:
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok, generic=False,
                  swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True):
-        att, mlp = layers[0].self_attn, layers[0].mlp
-        B, H, dev = tok.shape[0], att.hidden_size, embed.device
-        self.layers, self.embed, self.norm, self.lm_head, self.inv_freq = layers, embed, norm, lm_head, inv_freq
-        self.kcache, self.vcache, self.tok, self.pos, self.out_tok = kcache, vcache, tok, pos, out_tok
-        self.nq, self.nkv, self.head_dim, self.context = att.num_heads, att.num_key_value_heads, att.head_dim, kcache[0].shape[2]
-        self.eps = layers[0].input_layernorm.eps
+        B = tok.shape[0]
+        self.tok, self.pos, self.out_tok = tok, pos, out_tok
         self.batch1 = B == 1 and not generic
         if self.batch1 and not fusable(layers):
             raise nat.QpalError("DecodeStep: these layers have no batch-1 step (fusable(layers))")
-        self.rot_in_gemv = self.batch1 and ops.can_fuse_rotation(1, H)  # k in {2048, 4096}: the GEMV staging rotates x itself
-        hk, self.hidden_K = had.get_hadK(H)
-        self.hidden_hadT = None if hk is None else hk.T.contiguous().half().to(dev)
-        self.h32 = torch.zeros(B, H, dtype=torch.float32, device=dev)
-        self.a16 = torch.zeros(B, H, dtype=torch.float16, device=dev)
-        self.qkv32 = torch.zeros(B, H + 2 * att.kv_out, dtype=torch.float32, device=dev)
-        self.ug32 = torch.zeros(B, 2 * mlp.intermediate_size, dtype=torch.float32, device=dev)
-        self.ug_il = self.lm_ws = None
+        self._setup_rows(layers, embed, norm, lm_head, kcache, vcache, inv_freq, B)
+        att, mlp = layers[0].self_attn, layers[0].mlp
+        H, dev = att.hidden_size, embed.device
         if self.rot_in_gemv and swiglu_epilogue:
             # up | gate as ONE layer with interleaved supertile rows: the launch's epilogue writes fp16 silu(gate) * up itself
             self.act16 = torch.zeros(1, mlp.intermediate_size, dtype=torch.float16, device=dev)
@@ -103,6 +100,24 @@ class DecodeStep:
                 self.lm_ws = torch.zeros(self.lm_ws_bytes // 4, dtype=torch.float32, device=dev)
         else:
             self.attn_ws = attention_workspace(B, self.nq, self.nkv, self.head_dim, self.context, dev)
+
+    def _setup_rows(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows):
+        """what every step on `rows` rows of the residual stream needs (self.batch1 is set): the model, the rotation of the hidden
+        width and the fp32 / fp16 row buffers of one layer"""
+        att, mlp = layers[0].self_attn, layers[0].mlp
+        H, dev = att.hidden_size, embed.device
+        self.layers, self.embed, self.norm, self.lm_head, self.inv_freq = layers, embed, norm, lm_head, inv_freq
+        self.kcache, self.vcache = kcache, vcache
+        self.nq, self.nkv, self.head_dim, self.context = att.num_heads, att.num_key_value_heads, att.head_dim, kcache[0].shape[2]
+        self.eps = layers[0].input_layernorm.eps
+        self.rot_in_gemv = self.batch1 and ops.can_fuse_rotation(1, H)  # k in {2048, 4096}: the GEMV staging rotates x itself
+        hk, self.hidden_K = had.get_hadK(H)
+        self.hidden_hadT = None if hk is None else hk.T.contiguous().half().to(dev)
+        self.h32 = torch.zeros(rows, H, dtype=torch.float32, device=dev)
+        self.a16 = torch.zeros(rows, H, dtype=torch.float16, device=dev)
+        self.qkv32 = torch.zeros(rows, H + 2 * att.kv_out, dtype=torch.float32, device=dev)
+        self.ug32 = torch.zeros(rows, 2 * mlp.intermediate_size, dtype=torch.float32, device=dev)
+        self.ug_il = self.lm_ws = None
 
     @property
     def launches_per_token(self):
@@ -182,3 +197,78 @@ class DecodeStep:
                                                self.lm_head.shape[0], self.h32.shape[1],
                                                torch.cuda.current_stream(dev).cuda_stream)
         nat.check(rc, "qpal_lm_head_argmax")
+
+
+class Prefill(DecodeStep):
+    """A prompt into ONE slot of the caches a DecodeStep is built on (per-layer fp16 [B, nkv, context, hd]): chunks of at most
+    `chunk` <= 128 rows, each through DecodeStep's batch-B layer with rows = consecutive positions and `prefill_attention` on
+    kcache[i][slot] / vcache[i][slot] (rotary embedding at pos0 + row, rows appended, causal); final norm, lm_head and argmax for
+    the LAST row only.  Other slots are not touched.  The position lives on the device and the chunk loop advances it there: no
+    host synchronisation inside the call.
+
+        next_tok = pf(tokens, slot=0, pos0=0)   # tokens int64 [N] on the device, N >= 1; returns int64 [1]
+
+    pos0 as a Python int is checked on the host (N + pos0 > context: QpalError); as a device tensor it is not read by the host,
+    and a prompt that does not fit leaves caches untouched from the first chunk that crosses the end (the kernel's rule)."""
+
+    def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, native_lm_head=True):
+        if not 1 <= int(chunk) <= 128:
+            raise nat.QpalError(f"Prefill: chunk must be in 1 .. 128, got {chunk}")
+        self.chunk, self.batch1 = int(chunk), False
+        self._setup_rows(layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.chunk)
+        dev, H = embed.device, self.h32.shape[1]
+        self._full = (self.h32, self.a16, self.qkv32, self.ug32)
+        self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.out_tok = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.last32 = torch.zeros(1, H, dtype=torch.float32, device=dev)  # the last prompt row of the residual stream
+        self.slot = 0
+        self.attn_ws = prefill_workspace(self.chunk, self.nq, self.nkv, self.head_dim, self.context, dev)
+        if native_lm_head and H in (2048, 4096, 8192) and lm_head.data_ptr() % 16 == 0:
+            self.lm_ws_bytes = nat.lib().qpal_lm_head_ws_bytes(lm_head.shape[0])
+            self.lm_ws = torch.zeros(self.lm_ws_bytes // 4, dtype=torch.float32, device=dev)
+
+    @property
+    def launches_per_token(self):
+        raise nat.QpalError("Prefill: launches are per chunk (9 per layer), not per token")
+
+    def _attention(self, i, q, k, v):
+        prefill_attention(q, k, v, self.kcache[i][self.slot], self.vcache[i][self.slot], self.pos, self.inv_freq,
+                          scale=1.0 / math.sqrt(self.head_dim), out=self.a16, ws=self.attn_ws)
+
+    def hidden(self):
+        """fp16 [1, H]: the final norm of the last prompt row"""
+        return self.norm(self.last32.half())
+
+    def __call__(self, tokens, slot=0, pos0=0):
+        if tokens.dim() != 1 or tokens.shape[0] < 1 or tokens.dtype != torch.int64 or tokens.device != self.embed.device:
+            raise nat.QpalError(f"Prefill: tokens must be int64 [N >= 1] on {self.embed.device}")
+        N = tokens.shape[0]
+        if not 0 <= int(slot) < self.kcache[0].shape[0]:
+            raise nat.QpalError(f"Prefill: slot {slot} outside the caches' {self.kcache[0].shape[0]} sequences")
+        self.slot = int(slot)
+        if isinstance(pos0, torch.Tensor):
+            self.pos.copy_(pos0.reshape(1))
+        else:
+            if pos0 < 0 or N + pos0 > self.context:
+                raise nat.QpalError(f"Prefill: {N} tokens from position {pos0} do not fit a cache of {self.context} positions")
+            self.pos.fill_(int(pos0))
+        for c in range(0, N, self.chunk):
+            n = min(self.chunk, N - c)
+            self.h32, self.a16, self.qkv32, self.ug32 = (t[:n] for t in self._full)
+            self.h32.copy_(self.embed[tokens[c:c + n]])
+            for i in range(len(self.layers)):
+                self._layer(i)
+            self.pos += n
+        self.last32.copy_(self.h32[n - 1:n])
+        self.h32, self.a16, self.qkv32, self.ug32 = self._full
+        if self.lm_ws is None:
+            self.out_tok.copy_((self.hidden() @ self.lm_head.T).argmax(-1))
+            return self.out_tok
+        dev = self.embed.device
+        with torch.cuda.device(dev):  # final RMSNorm + lm_head GEMV + argmax of the last row: one launch
+            rc = nat.lib().qpal_lm_head_argmax(self.last32.data_ptr(), self.norm.weight.data_ptr(), self.norm.eps,
+                                               self.lm_head.data_ptr(), None, self.out_tok.data_ptr(), self.lm_ws.data_ptr(),
+                                               self.lm_ws_bytes, self.lm_head.shape[0], self.last32.shape[1],
+                                               torch.cuda.current_stream(dev).cuda_stream)
+        nat.check(rc, "qpal_lm_head_argmax")
+        return self.out_tok
