@@ -357,6 +357,34 @@ int qpal_attn_rope_prefill(const float *q, const float *k, const float *v, long 
                            const long *pos0, const float *inv_freq, int T, int nq, int nkv, int hd,
                            long max_len, float scale, void *ws, long ws_bytes, void *stream);
 
+/* Final norm + fp16 lm_head for `rows` rows of the residual stream at once, on the matrix pipe (csrc/lm_head_batch.hip): the
+ * logits a sampler needs, and the batch-B tail of a decode step.  h_f32 fp32 [rows][ld_h] (ld_h >= k, in elements), 1 <= rows <=
+ * 128; k a multiple of 512, 512 <= k <= 8192; w_f16 the lm_head fp16 [vocab][k]; logits_f32 fp32 [rows][ld_logits], ld_logits >=
+ * vocab: logits[b][v] for v < vocab is written, columns vocab .. ld_logits are left as they were.  Per row the arithmetic of
+ * qpal_lm_head_argmax: x = fp16(h * rsqrt(mean(h^2) + rms_eps)), then * rms_w in fp16 (rms_eps <= 0 or rms_w_f16 == NULL: x =
+ * fp16(h)); fp32 accumulation.  Every lm_head row is read once for all rows; no workspace, no atomics, one writer per logit: two
+ * launches are bitwise equal.  Alignment: w_f16 and h_f32 16 bytes, ld_h % 4 == 0 when rows > 1, rms_w_f16 8 bytes, logits 4. */
+int qpal_lm_head_logits(const float *h_f32, long ld_h, const void *rms_w_f16, float rms_eps, const void *w_f16, float *logits_f32,
+                        long ld_logits, int rows, int vocab, int k, void *stream);
+
+/* The next token of `rows` sequences (1 .. 128) from their logits fp32 [rows][ld_logits] (ld_logits >= vocab), one launch
+ * (csrc/sample.hip).  temperature / top_p fp32 [rows], top_k int32 [rows], seed / ctr int64 [rows], token int64 [rows]: all on the
+ * device and never read by the host (a captured launch can be replayed while the caller rewrites them); nothing is allocated.
+ * For row b with logits l[0 .. vocab):
+ *  1. ctr[b] < 0: the row is inactive; token[b] is not written.
+ *  2. temperature[b] <= 0 or top_k[b] == 1: greedy.  token[b] = argmax, lowest index on ties; no row selected (NaN, all -inf): 0.
+ *  3. Top-k on the raw fp32 logits: top_k[b] <= 0 or >= vocab keeps all; else keep {i : l[i] >= (k-th largest value)}; ties at the
+ *     k-th value are all kept.
+ *  4. z[i] = l[i] / T.  Top-p: top_p[b] >= 1 or <= 0 keeps all of step 3's set K.  Else with p[i] = exp(z[i] - zmax) / sum over K
+ *     of exp(z[j] - zmax), keep {i in K : p[i] >= tau}, tau the largest value among the p's with sum{p[j] : p[j] >= tau} >= top_p.
+ *  5. The race.  Token i: Philox4x32-10 with key (seed_lo, seed_hi) and counter (i >> 2, 0, ctr_lo, ctr_hi) (the 32-bit halves of
+ *     seed[b] / ctr[b] as unsigned); x = output word i & 3; u = ((x >> 9) + 0.5) * 2^-23; e = -ln u; s[i] = z[i] - ln e.
+ *     token[b] = argmax of s over the kept set, lowest index on ties (nothing selectable: 0).
+ * A draw depends on (seed, ctr, token index, the row's logits and parameters) and on nothing else.  A NaN logit is never kept.
+ * Integer arithmetic wherever sums could depend on an order: two launches are bitwise equal.                                 */
+int qpal_sample(const float *logits_f32, long ld_logits, int rows, int vocab, const float *temperature, const int *top_k,
+                const float *top_p, const long *seed, const long *ctr, long *token, void *stream);
+
 /* The launch planner of the fused GEMV entry points, on its own (host code, no GPU call; what tests and tools inspect).
  * A launch of njobs jobs — rows[j] supertile rows (m / 32) of steps1[j] + steps2[j] steps (a step = 128 columns; steps2 = 0: one
  * stream) — is cut into workgroup-sized pieces: a GROUP of G = 1 << lg_g workgroups (`waves` = 16 or 8 waves each) owns rg

@@ -17,7 +17,10 @@ The step is captured in a graph and replayed (positions advance on the device be
 the four projection groups alone (linears-only), and a torch-glue step at the same B built from the Incoherent* modules (torch
 rotary embedding, a per-sequence cache write, SDPA with a per-sequence mask), whose final normalised hidden state is the check.
 
-    python perf/decode_llama_batch.py [--model 3_8b] [--batch 1 8 16 32 64] [--context 1024] [--tokens 64] [--inactive 0]
+--sample adds the sampled step (DecodeStep(sampler=...): qpal_lm_head_logits + qpal_sample in the torch tail's place) at temperature
+0.6 / top-k 5 (the setting of the decode loop this was modelled on) and 0.8 / top-p 0.95, timed in the same call as the greedy step.
+
+    python perf/decode_llama_batch.py [--model 3_8b] [--batch 1 8 16 32 64] [--context 1024] [--tokens 64] [--inactive 0] [--sample]
 """
 import argparse
 import json
@@ -64,6 +67,7 @@ def main(argv=None, quiet=False):
     ap.add_argument("--vocab", type=int, default=128256)
     ap.add_argument("--seed", type=int, default=7, help="seed of the ragged positions")
     ap.add_argument("--no-torch-glue", action="store_true", help="skip the torch-glue step (its timing and the check)")
+    ap.add_argument("--sample", action="store_true", help="also time the step with a sampler (0.6 / top-k 5 and 0.8 / top-p 0.95)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
@@ -158,10 +162,23 @@ def main(argv=None, quiet=False):
         ms_step = timed(kernel_step)
         ms_lin = timed(linears_only, None)
         ms_torch = None if args.no_torch_glue else timed(torch_step)
+        sampled = None
+        if args.sample:
+            # the same layers with the native tail: lm_head logits of all B rows + one draw per active row (two launches)
+            sampled = []
+            for temperature, top_k, top_p in ((0.6, 5, 1.0), (0.8, 0, 0.95)):
+                smp = qp.Sampler(B, args.vocab, dev, temperature=temperature, top_k=top_k, top_p=top_p, seed=list(range(B)))
+                sstep = qp.DecodeStep(layers, embed, norm, lm_head, kc, vc, inv_freq, tok, pos, out_tok, generic=True, sampler=smp)
+                ms = timed(sstep)
+                sampled.append({"temperature": temperature, "top_k": top_k, "top_p": top_p, "ms_step": ms, "ms_minus_greedy": ms - ms_step,
+                                "tokens_per_s": nact / ms * 1e3})
+                del sstep, smp
         res = {"batch": B, "active": nact, "ms_step": ms_step, "tokens_per_s": nact / ms_step * 1e3,
                "ms_linears_only": ms_lin, "ms_torch_glue": ms_torch,
                "tokens_per_s_torch_glue": None if ms_torch is None else nact / ms_torch * 1e3,
                "kv_rows_attended_first_step": int((pos0[pos0 >= 0] + 1).sum()), "check": check}
+        if sampled is not None:
+            res["sampled"] = sampled
         del kc, vc, ref_cache, kernel_step
         torch.cuda.empty_cache()
         return res

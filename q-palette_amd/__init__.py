@@ -13,6 +13,8 @@ Layout:
                    prefill_attention / prefill_workspace: the same for up to 128 new tokens of one sequence, causal
   decoder.py       DecodeStep: the whole-model decode step at batch B >= 1 on the kernels above (per-layer launch sequence,
                    scratch buffers, final norm + lm_head + argmax, launches per token)
+  sampling.py      lm_head_logits (final norm + lm_head for up to 128 rows), sample / Sampler (temperature, top-k, top-p, seeded
+                   draw; per-slot parameters on the device), reference_draw (the draw's contract in numpy fp64)
   packers.py       pack_trellis / pack_qweight / pack_qweight_{sq,vq}_simt on the C-ABI's host-side encoders
   quantize.py      TCQ quantiser: tail-biting Viterbi encoder (csrc/tcq_viterbi.hip) + LDLQ -> QTIPLinearTCQ
                    VQ / SQ quantiser: nearest-codeword LDLQ encoder (csrc/vq_encode.hip) -> VQLinearPack{TensorCore,SIMT}
@@ -47,6 +49,8 @@ from . import quantize  # noqa: F401
 from . import quantize_layer  # noqa: F401
 from . import attention  # noqa: F401
 from .attention import attention_workspace, decode_attention, prefill_attention, prefill_workspace  # noqa: F401
+from . import sampling  # noqa: F401
+from .sampling import Sampler, lm_head_logits, reference_draw, sample  # noqa: F401
 from . import decoder  # noqa: F401
 from .decoder import DecodeStep, Prefill  # noqa: F401
 from .quantize_layer import incoherent_preprocess, layer_file_path, load_hessian, quantize_linear  # noqa: F401

@@ -1,0 +1,261 @@
+// qpal_sample: the next token of up to 128 sequences from their fp32 logits — temperature, top-k, top-p and a seeded draw, one
+// launch, per-row parameters on the device (DESIGN.md §14 has the contract word for word).  The reference's decode loop draws
+// every token with sample(logits, temperature=0.6, top_k=5) (eval/measure_latency.py:102-135: logits / T, keep >= the k-th
+// largest, softmax, argmax(probs / Exp(1))); this is that race with a counter-based generator, plus top-p.
+//
+// Workgroup = one row, 16 waves.  A 128 k row (513 KB) does not fit LDS and is read from L2 once per pass:
+//   greedy rows, rows without a filter            1 pass  (argmax / the race)
+//   top-k   the k-th largest value                3 passes: radix select (11 + 11 + 10 bits, most significant first) over the
+//           order-preserving unsigned image of the fp32 bits, LDS histogram of COUNTS
+//   top-p   the mass threshold                    1 pass for the row maximum + 3 passes of the same select with a histogram of
+//           MASS exp((l - lmax) / T) over the top-k set, as 2^-40 fixed point in 64-bit integers
+//   the race over the kept set                    1 pass (Philox only for groups of four tokens with a kept one)
+// Integer LDS atomics only: sums do not depend on the order of arrival, so two launches are bitwise equal, and the mass of a set
+// is exact in the summands (each exp truncated to 2^-40: at most 2^17 * 2^-40 = 2^-23 of the total, which is >= 1).
+#include <hip/hip_runtime.h>
+
+#include "qpal_common.h"
+
+namespace qpal {
+
+struct SampleParams {
+    const float *logits;
+    long ld;
+    int rows, vocab;
+    const float *temperature;
+    const int *top_k;
+    const float *top_p;
+    const long *seed, *ctr;
+    long *token;
+};
+
+constexpr int kSampleBins = 2048;
+constexpr float kNegInf = -__builtin_inff();
+
+// order-preserving unsigned image of an fp32 value: a < b <=> key(a) < key(b); -0 and +0 share a key; NaN: 0 (below -inf)
+__device__ __forceinline__ uint32_t sample_key(float l) {
+    if (l != l) return 0u;
+    if (l == 0.f) return 0x80000000u;
+    const uint32_t u = __builtin_bit_cast(uint32_t, l);
+    return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// every thread: groups of four consecutive tokens j = tid, tid + 1024, ...; f(j, n, v): tokens 4 j .. 4 j + n - 1
+template <class F>
+__device__ __forceinline__ void sample_row_pass(const float *row, int vocab, bool vec, F &&f) {
+    const int ngrp = (vocab + 3) >> 2;
+    for (int j = threadIdx.x; j < ngrp; j += 1024) {
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        const int i0 = 4 * j;
+        int n = vocab - i0 < 4 ? vocab - i0 : 4;
+        if (vec && n == 4) {
+            const float4 t = *reinterpret_cast<const float4 *>(row + i0);
+            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                if (e < n) v[e] = row[i0 + e];
+        }
+        f(j, n, v);
+    }
+}
+
+__device__ __forceinline__ unsigned long long shfl_down_u64(unsigned long long v, int off) {
+    const uint32_t lo = __shfl_down((uint32_t)v, off, 64), hi = __shfl_down((uint32_t)(v >> 32), off, 64);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+struct SampleShared {
+    unsigned long long hist[kSampleBins];
+    unsigned long long rem;   // what is left of the target inside the selected bin
+    int bin;                  // the selected bin; -1: nothing to select (no mass)
+    float redv[16];
+    int redi[16];
+};
+
+// Radix select, most significant digit first.  MASS = false: the largest key K with #{key >= K} >= target (the target-th largest
+// key).  MASS = true: the largest key K with mass{key >= K, key >= floor} >= top_p * mass{key >= floor}.  Returns K, the same in
+// every thread; with no mass at all (MASS): floor.
+template <bool MASS>
+__device__ uint32_t sample_select(SampleShared &sh, const float *row, int vocab, bool vec, unsigned long long target, uint32_t floor_key,
+                                  float lmax, float T, float top_p) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    uint32_t prefix = 0u;
+    int done_bits = 0;
+#pragma unroll 1
+    for (int pass = 0; pass < 3; pass++) {
+        const int nbits = pass < 2 ? 11 : 10, shift = 32 - done_bits - nbits;
+        for (int i = tid; i < kSampleBins; i += 1024) sh.hist[i] = 0ull;
+        __syncthreads();
+        sample_row_pass(row, vocab, vec, [&](int, int n, const float (&v)[4]) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                if (e >= n) continue;
+                const uint32_t key = sample_key(v[e]);
+                if (key < floor_key) continue;
+                if (done_bits && (key >> (32 - done_bits)) != prefix) continue;
+                unsigned long long wgt = 1ull;
+                if constexpr (MASS) {
+                    const float d = v[e] - lmax;  // NaN only for inf - inf (or a NaN logit: below every floor >= 1)
+                    const float w = d == d ? expf(d / T) : (v[e] == lmax ? 1.0f : 0.f);
+                    wgt = (unsigned long long)(w * 1099511627776.0f);  // 2^40, truncated; w in [0, 1]
+                    if (wgt == 0ull) continue;
+                }
+                atomicAdd(&sh.hist[(key >> shift) & ((1u << nbits) - 1u)], wgt);
+            }
+        });
+        __syncthreads();
+        if (tid < 64) {  // wave 0: lane L owns bins 32 L .. 32 L + 31; suffix sums over the lanes, then a walk inside one lane
+            unsigned long long own = 0ull;
+            for (int b = 0; b < 32; b++) own += sh.hist[32 * lane + b];
+            unsigned long long incl = own;  // sum over lanes >= this one
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const unsigned long long t = shfl_down_u64(incl, off);
+                if (lane + off < 64) incl += t;
+            }
+            unsigned long long tgt = target;
+            if (MASS && pass == 0) {
+                const uint32_t tlo = __shfl((uint32_t)incl, 0, 64), thi = __shfl((uint32_t)(incl >> 32), 0, 64);
+                const unsigned long long total = ((unsigned long long)thi << 32) | tlo;
+                tgt = (unsigned long long)((double)top_p * (double)total);
+                if (tgt > total) tgt = total;
+                if (tgt < 1ull) tgt = 1ull;
+                if (total == 0ull) tgt = 0ull;
+            }
+            const unsigned long long above = incl - own;
+            const bool mine = tgt != 0ull && incl >= tgt && above < tgt;
+            if (mine) {
+                unsigned long long cum = above;
+                int b = 31;
+                for (; b > 0; b--) {
+                    const unsigned long long hb = sh.hist[32 * lane + b];
+                    if (cum + hb >= tgt) break;
+                    cum += hb;
+                }
+                sh.bin = 32 * lane + b;
+                sh.rem = tgt - cum;
+            }
+            if (__ballot(mine) == 0ull && lane == 0) {  // no mass (or fewer keys than the target): nothing to select
+                sh.bin = -1;
+                sh.rem = 0ull;
+            }
+        }
+        __syncthreads();
+        const int bin = sh.bin;
+        target = sh.rem;
+        __syncthreads();  // (sh.bin / sh.hist are rewritten by the next pass)
+        if (bin < 0) return floor_key;
+        prefix = (prefix << nbits) | (uint32_t)bin;
+        done_bits += nbits;
+    }
+    return prefix > floor_key ? prefix : floor_key;
+}
+
+__global__ __launch_bounds__(1024) void sample_kernel(const SampleParams p) {
+    __shared__ SampleShared sh;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long ctr = p.ctr[b];
+    if (ctr < 0) return;  // inactive row: token[b] keeps what it held
+    const float T = p.temperature[b], top_p = p.top_p[b];
+    const int top_k = p.top_k[b], vocab = p.vocab;
+    const unsigned long long seed = (unsigned long long)p.seed[b];
+    const float *row = p.logits + (long)b * p.ld;
+    const bool vec = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+    const bool greedy = !(T > 0.f) || top_k == 1;
+
+    uint32_t thr = 1u;  // kept set: key >= thr (1: everything but NaN)
+    if (!greedy) {
+        if (top_k > 1 && top_k < vocab) thr = sample_select<false>(sh, row, vocab, vec, (unsigned long long)top_k, 0u, 0.f, 1.f, 1.f);
+        if (thr < 1u) thr = 1u;
+        if (top_p > 0.f && top_p < 1.f) {
+            float mx = kNegInf;
+            sample_row_pass(row, vocab, vec, [&](int, int n, const float (&v)[4]) {
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+                    if (e < n && v[e] > mx) mx = v[e];
+            });
+            mx = wave_max(mx);
+            if (lane == 0) sh.redv[wave] = mx;
+            __syncthreads();
+            mx = sh.redv[0];
+#pragma unroll
+            for (int w = 1; w < 16; w++) mx = sh.redv[w] > mx ? sh.redv[w] : mx;
+            __syncthreads();
+            if (mx > kNegInf) thr = sample_select<true>(sh, row, vocab, vec, 0ull, thr, mx, T, top_p);
+        }
+    }
+
+    // ---- the race (greedy: the plain argmax) over the kept set; lowest index on ties; nothing selected: 0
+    float best = kNegInf;
+    int besti = 0x7fffffff;
+    const uint32_t ctr_lo = (uint32_t)(unsigned long long)ctr, ctr_hi = (uint32_t)((unsigned long long)ctr >> 32);
+    sample_row_pass(row, vocab, vec, [&](int j, int n, const float (&v)[4]) {
+        bool any = false;
+#pragma unroll
+        for (int e = 0; e < 4; e++) any |= e < n && sample_key(v[e]) >= thr;
+        if (!any) return;
+        uint32_t x[4] = {0u, 0u, 0u, 0u};
+        if (!greedy) philox4x32_10((uint32_t)j, 0u, ctr_lo, ctr_hi, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            if (e >= n || sample_key(v[e]) < thr) continue;
+            float s = v[e];
+            if (!greedy) {
+                const float u = ((float)(x[e] >> 9) + 0.5f) * 1.1920928955078125e-07f;  // 2^-23: exact, in (0, 1)
+                const float ex = -logf(u);
+                s = v[e] / T - logf(ex);
+            }
+            if (s > best) best = s, besti = 4 * j + e;  // tokens ascend within a thread: strict > keeps the lowest index
+        }
+    });
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float ob = __shfl_xor(best, m, 64);
+        const int oi = __shfl_xor(besti, m, 64);
+        if (ob > best || (ob == best && oi < besti)) best = ob, besti = oi;
+    }
+    if (lane == 0) {
+        sh.redv[wave] = best;
+        sh.redi[wave] = besti;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 16; w++) {
+            const float v = sh.redv[w];
+            const int vi = sh.redi[w];
+            if (v > best || (v == best && vi < besti)) best = v, besti = vi;
+        }
+        if ((unsigned)besti >= (unsigned)vocab) besti = 0;  // NaN / all -inf: still a valid row of the embedding
+        p.token[b] = besti;
+    }
+}
+
+}  // namespace qpal
+
+using namespace qpal;
+
+extern "C" int qpal_sample(const float *logits_f32, long ld_logits, int rows, int vocab, const float *temperature, const int *top_k,
+                           const float *top_p, const long *seed, const long *ctr, long *token, void *stream) {
+    if (!logits_f32 || !temperature || !top_k || !top_p || !seed || !ctr || !token) return QPAL_E_NULL;
+    if (rows < 1 || rows > 128 || vocab < 1 || vocab > (1 << 30) || ld_logits < vocab) return QPAL_E_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(logits_f32) & 3) || (reinterpret_cast<uintptr_t>(temperature) & 3) ||
+        (reinterpret_cast<uintptr_t>(top_k) & 3) || (reinterpret_cast<uintptr_t>(top_p) & 3) || (reinterpret_cast<uintptr_t>(seed) & 7) ||
+        (reinterpret_cast<uintptr_t>(ctr) & 7) || (reinterpret_cast<uintptr_t>(token) & 7))
+        return QPAL_E_ALIGN;
+    SampleParams p{logits_f32, ld_logits, rows, vocab, temperature, top_k, top_p, seed, ctr, token};
+    hipLaunchKernelGGL(sample_kernel, dim3(rows), dim3(1024), 0, static_cast<hipStream_t>(stream), p);
+    return (int)hipGetLastError();
+}

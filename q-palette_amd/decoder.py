@@ -13,6 +13,10 @@ own (70B: 8192).  `generic=True` runs a batch of one the way every larger batch 
     step = DecodeStep(layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok)
     step()                      # capturable: reads tok / pos, updates the caches at pos, writes out_tok
 
+With `sampler=sampling.Sampler(B, vocab, device, ...)` the step ends in `qpal_lm_head_logits` + `qpal_sample` at every B instead of
+an argmax: out_tok[b] is drawn with slot b's temperature / top-k / top-p / seed and the counter pos[b] (DESIGN.md §14);
+sampler.logits holds the step's logits.
+
 `Prefill` takes a prompt into ONE slot of the same caches: the batch-B layer with rows = consecutive positions of one sequence,
 in chunks of at most 128 rows, with `prefill_attention` (causal, rows appended to the slot's cache) in the attention's place.
 
@@ -25,7 +29,7 @@ import torch
 
 from . import _native as nat
 from . import hadamard as had
-from . import linear, ops
+from . import linear, ops, sampling
 from .attention import attention_workspace, decode_attention, prefill_attention, prefill_workspace
 from .linear import multi_gemv
 
@@ -69,12 +73,14 @@ class DecodeStep:
     embed / lm_head fp16 [vocab, H]; norm: the final RMSNorm; kcache / vcache: per-layer fp16 [B, nkv, context, hd]; inv_freq fp32
     [hd / 2]; tok, pos, out_tok int64 [B] (pos[b] outside the cache: sequence b is inactive).  The caller owns the caches and
     tok / pos / out_tok and may write them between replays of a captured step.  swiglu_epilogue, k28_fusion, native_lm_head,
-    split_attention switch single fusions of the batch-1 step off (profiling)."""
+    split_attention switch single fusions of the batch-1 step off (profiling).  sampler: a sampling.Sampler of B slots — the tail
+    becomes lm_head logits of all B rows + one draw per active row with the counter pos[b] (two launches); None: argmax."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok, generic=False,
-                 swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True):
+                 swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True, sampler=None):
         B = tok.shape[0]
         self.tok, self.pos, self.out_tok = tok, pos, out_tok
+        self.sampler = self._check_sampler(sampler, B, embed, lm_head)
         self.batch1 = B == 1 and not generic
         if self.batch1 and not fusable(layers):
             raise nat.QpalError("DecodeStep: these layers have no batch-1 step (fusable(layers))")
@@ -101,6 +107,24 @@ class DecodeStep:
         else:
             self.attn_ws = attention_workspace(B, self.nq, self.nkv, self.head_dim, self.context, dev)
 
+    @staticmethod
+    def _check_sampler(sampler, B, embed, lm_head):
+        if sampler is None:
+            return None
+        H = embed.shape[1]
+        if sampler.B != B or sampler.vocab != lm_head.shape[0] or sampler.device != embed.device:
+            raise nat.QpalError(f"sampler: built for {sampler.B} slots of {sampler.vocab} logits on {sampler.device}, "
+                                f"the step has {B} of {lm_head.shape[0]} on {embed.device}")
+        if H % 512 or H > 8192 or lm_head.data_ptr() % 16 or not lm_head.is_contiguous():
+            raise nat.QpalError("sampler: qpal_lm_head_logits needs a hidden width that is a multiple of 512 up to 8192 and a "
+                                "contiguous 16-byte aligned lm_head")
+        return sampler
+
+    def _sample_tail(self, h32, smp, ctr, out_tok):
+        """final norm + lm_head of every row of h32 into smp.logits, then one draw per row with the counters ctr: two launches"""
+        sampling.lm_head_logits(h32, self.norm.weight, self.norm.eps, self.lm_head, out=smp.logits)
+        sampling.sample(smp.logits, smp, ctr, out=out_tok)
+
     def _setup_rows(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows):
         """what every step on `rows` rows of the residual stream needs (self.batch1 is set): the model, the rotation of the hidden
         width and the fp32 / fp16 row buffers of one layer"""
@@ -123,9 +147,9 @@ class DecodeStep:
     def launches_per_token(self):
         """kernel launches of one step: per layer q|k|v, attention, o, up|gate, SwiGLU rotation, down (+ a rotation in front of
         q|k|v, o and up|gate where the GEMV cannot rotate; - the SwiGLU rotation where down_proj's staging runs it); + the norm /
-        lm_head / argmax launch (the embedding row copy is a memcpy node)"""
+        lm_head / argmax launch, or the lm_head logits and the draw with a sampler (the embedding row copy is a memcpy node)"""
         per_layer = (5 if self.ug_il and self.ug_il[0][2] else 6) if self.rot_in_gemv else 9
-        return per_layer * len(self.layers) + 1
+        return per_layer * len(self.layers) + (1 if self.sampler is None else 2)
 
     def _gemv(self, proj, x, su, scale, rms=None, **kw):
         """multi_gemv of one projection group on rotate(RMSNorm(x) * su) / scale: RMSNorm + rotation inside the GEMV launch, or
@@ -187,6 +211,9 @@ class DecodeStep:
         self.h32.copy_(self.embed[self.tok])
         for i in range(len(self.layers)):
             self._layer(i)
+        if self.sampler is not None:
+            self._sample_tail(self.h32, self.sampler, self.pos, self.out_tok)
+            return
         if self.lm_ws is None:
             self.out_tok.copy_((self.hidden() @ self.lm_head.T).argmax(-1))
             return
@@ -209,17 +236,23 @@ class Prefill(DecodeStep):
         next_tok = pf(tokens, slot=0, pos0=0)   # tokens int64 [N] on the device, N >= 1; returns int64 [1]
 
     pos0 as a Python int is checked on the host (N + pos0 > context: QpalError); as a device tensor it is not read by the host,
-    and a prompt that does not fit leaves caches untouched from the first chunk that crosses the end (the kernel's rule)."""
+    and a prompt that does not fit leaves caches untouched from the first chunk that crosses the end (the kernel's rule).
 
-    def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, native_lm_head=True):
+    sampler: the sampling.Sampler of the DecodeStep whose caches this fills (one slot per sequence of the caches).  The token is then
+    drawn with slot `slot`'s parameters and the counter of the last prompt row's position, pos0 + N - 1 (computed on the device):
+    the counter a DecodeStep would have used had it fed that token.  sampler.logits[slot] holds the logits."""
+
+    def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, native_lm_head=True, sampler=None):
         if not 1 <= int(chunk) <= 128:
             raise nat.QpalError(f"Prefill: chunk must be in 1 .. 128, got {chunk}")
         self.chunk, self.batch1 = int(chunk), False
+        self.sampler = self._check_sampler(sampler, kcache[0].shape[0], embed, lm_head)
         self._setup_rows(layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.chunk)
         dev, H = embed.device, self.h32.shape[1]
         self._full = (self.h32, self.a16, self.qkv32, self.ug32)
         self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
         self.out_tok = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.ctr = torch.zeros(1, dtype=torch.int64, device=dev)  # with a sampler: the last prompt row's position
         self.last32 = torch.zeros(1, H, dtype=torch.float32, device=dev)  # the last prompt row of the residual stream
         self.slot = 0
         self.attn_ws = prefill_workspace(self.chunk, self.nq, self.nkv, self.head_dim, self.context, dev)
@@ -261,6 +294,10 @@ class Prefill(DecodeStep):
             self.pos += n
         self.last32.copy_(self.h32[n - 1:n])
         self.h32, self.a16, self.qkv32, self.ug32 = self._full
+        if self.sampler is not None:
+            torch.sub(self.pos, 1, out=self.ctr)
+            self._sample_tail(self.last32, self.sampler.slot(self.slot), self.ctr, self.out_tok)
+            return self.out_tok
         if self.lm_ws is None:
             self.out_tok.copy_((self.hidden() @ self.lm_head.T).argmax(-1))
             return self.out_tok

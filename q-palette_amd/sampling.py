@@ -1,0 +1,226 @@
+"""Sampling the next token on the GPU: the batched lm_head (C-ABI ``qpal_lm_head_logits``, csrc/lm_head_batch.hip) and the
+temperature / top-k / top-p / seeded draw (``qpal_sample``, csrc/sample.hip), one launch each for up to 128 rows.
+
+    smp = Sampler(B, vocab, device, temperature=0.6, top_k=5, seed=1234)   # per-slot parameters on the device
+    smp.set(3, temperature=0.8, top_k=0, top_p=0.95, seed=7)               # one slot (a new request)
+    lm_head_logits(h32, norm.weight, norm.eps, lm_head, out=smp.logits)
+    tok = sample(smp.logits, smp, ctr)                                     # ctr int64 [B]: the position; < 0: row inactive
+
+``decoder.DecodeStep(..., sampler=smp)`` and ``decoder.Prefill(..., sampler=smp)`` end in these two launches.
+
+The draw is specified exactly (include/qpal.h); ``reference_draw`` restates it in numpy fp64 with its own Philox.
+It is the specification the tests hold the kernel to: CPU only, no torch.cuda, no library call.
+"""
+import numpy as np
+
+_M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_MASK = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10.  counter: uint32 [..., 4], key: uint32 [..., 2] (broadcast against each other) -> uint32 [..., 4]"""
+    c = [np.asarray(counter)[..., i].astype(np.uint64) for i in range(4)]
+    k = [np.asarray(key)[..., i].astype(np.uint64) for i in range(2)]
+    for _ in range(10):
+        p0, p1 = np.uint64(_M0) * c[0], np.uint64(_M1) * c[2]  # 32 x 32 -> 64 bits: no overflow
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & _MASK, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & _MASK]
+        k = [(k[0] + np.uint64(_W0)) & _MASK, (k[1] + np.uint64(_W1)) & _MASK]
+    return np.stack(np.broadcast_arrays(*c), axis=-1).astype(np.uint32)
+
+
+def race_scores(z, seed, ctr):
+    """s[i] = z[i] - ln(-ln u_i) in fp64, u_i from Philox word i & 3 of counter (i >> 2, 0, ctr_lo, ctr_hi), key (seed_lo, seed_hi).
+    ctr: an int or an int array [n] -> s [vocab] or [n, vocab]"""
+    z = np.asarray(z, dtype=np.float64)
+    vocab = z.shape[0]
+    ctr_a = np.atleast_1d(np.asarray(ctr, dtype=np.int64)).astype(np.uint64)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    groups = np.arange((vocab + 3) // 4, dtype=np.uint64)
+    counter = np.zeros((ctr_a.shape[0], groups.shape[0], 4), dtype=np.uint64)
+    counter[..., 0] = groups[None, :]
+    counter[..., 2] = (ctr_a & _MASK)[:, None]
+    counter[..., 3] = (ctr_a >> np.uint64(32))[:, None]
+    key = np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64)
+    x = philox4x32(counter, key).reshape(ctr_a.shape[0], -1)[:, :vocab]
+    u = ((x >> np.uint32(9)).astype(np.float64) + 0.5) * 2.0 ** -23
+    with np.errstate(invalid="ignore"):
+        s = z[None, :] - np.log(-np.log(u))
+    return s[0] if np.ndim(ctr) == 0 else s
+
+
+def topk_mask(l, top_k):
+    """step 3 on l (fp32 values, NaN already -inf): {i : l[i] >= the k-th largest value}; top_k <= 0 or >= vocab: all"""
+    top_k = int(top_k)
+    if top_k <= 0 or top_k >= l.shape[0]:
+        return np.ones(l.shape[0], dtype=bool)
+    return l >= np.partition(l, l.shape[0] - top_k)[l.shape[0] - top_k]
+
+
+def probabilities(l, temperature, kmask):
+    """p (fp64) of step 4 over the set kmask; 0 outside it.  All -inf: zeros."""
+    z = np.where(kmask, l.astype(np.float64) / float(temperature), -np.inf)
+    zmax = z.max()
+    if not np.isfinite(zmax):
+        return np.zeros_like(z) if zmax < 0 else (z == zmax) / float((z == zmax).sum())
+    w = np.exp(z - zmax)
+    return w / w.sum()
+
+
+def nucleus_mask(p, kmask, top_p):
+    """step 4: {i in K : p[i] >= tau}, tau the largest value among the p's with sum{p[j] : p[j] >= tau} >= top_p"""
+    top_p = float(top_p)
+    if top_p >= 1.0 or top_p <= 0.0 or not p.any():
+        return kmask.copy()
+    vals, inv = np.unique(p[kmask], return_inverse=True)       # ascending
+    mass = np.bincount(inv, weights=p[kmask], minlength=vals.shape[0])
+    cum = np.cumsum(mass[::-1])                                  # mass of {p >= vals[::-1][j]}
+    j = int(np.searchsorted(cum, top_p, side="left"))
+    tau = vals[::-1][min(j, vals.shape[0] - 1)]
+    return kmask & (p >= tau)
+
+
+def clean_logits(logits_row):
+    """fp32 logits as the kernel sees them, NaN -> -inf (a NaN logit is never kept)"""
+    l = np.asarray(logits_row, dtype=np.float32).copy()
+    l[np.isnan(l)] = -np.inf
+    return l
+
+
+def reference_draw(logits_row, temperature, top_k, top_p, seed, ctr):
+    """The contract of qpal_sample for one row, in fp64.  temperature / top_p are rounded to fp32 first (what the kernel is given).
+    ctr: an int -> the token (None for ctr < 0: the row is inactive), or an int array of non-negative counters -> tokens."""
+    if np.ndim(ctr) == 0 and int(ctr) < 0:
+        return None
+    l = clean_logits(logits_row)
+    T, P = float(np.float32(temperature)), float(np.float32(top_p))
+    scalar = np.ndim(ctr) == 0
+    if not T > 0.0 or int(top_k) == 1:
+        tok = int(np.argmax(l)) if np.isfinite(l.max()) or l.max() > 0 else 0
+        return tok if scalar else np.full(np.shape(ctr), tok, dtype=np.int64)
+    kmask = topk_mask(l, top_k)
+    kept = nucleus_mask(probabilities(l, T, kmask), kmask, P)
+    z = l.astype(np.float64) / T
+    s = np.atleast_2d(race_scores(z, seed, ctr))
+    s = np.where(kept[None, :] & (z[None, :] > -np.inf), s, -np.inf)
+    tok = np.where(s.max(axis=1) > -np.inf, s.argmax(axis=1), 0).astype(np.int64)
+    return int(tok[0]) if scalar else tok
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU side
+
+def _torch():
+    import torch
+    return torch
+
+
+def lm_head_logits(h32, norm_weight, eps, lm_head, out=None):
+    """logits fp32 [rows, vocab] = lm_head @ fp16(RMSNorm(h32) * norm_weight) per row (eps <= 0 or norm_weight None: fp16(h32)).
+    h32 fp32 [rows, k] (rows may be strided), 1 <= rows <= 128, k a multiple of 512 up to 8192; lm_head fp16 [vocab, k] contiguous,
+    16-byte aligned; out: fp32 [rows, >= vocab columns] with contiguous rows (columns past vocab are left alone).  Launches on the
+    current stream."""
+    torch = _torch()
+    from . import _native
+    who, QpalError = "lm_head_logits", _native.QpalError
+    if h32.dtype != torch.float32 or not h32.is_cuda or h32.dim() != 2 or h32.stride(1) != 1:
+        raise QpalError(f"{who}: h32 must be an fp32 device tensor [rows, k] with contiguous rows")
+    rows, k = h32.shape
+    if not 1 <= rows <= 128 or k % 512 or not 512 <= k <= 8192:
+        raise QpalError(f"{who}: rows must be in 1 .. 128 and k a multiple of 512 up to 8192, got {list(h32.shape)}")
+    if lm_head.dtype != torch.float16 or lm_head.dim() != 2 or lm_head.shape[1] != k or not lm_head.is_contiguous() or lm_head.device != h32.device:
+        raise QpalError(f"{who}: lm_head must be a contiguous fp16 [vocab, {k}] tensor on {h32.device}")
+    vocab = lm_head.shape[0]
+    ld_h = h32.stride(0) if rows > 1 else k
+    if lm_head.data_ptr() % 16 or h32.data_ptr() % 16 or ld_h % 4:
+        raise QpalError(f"{who}: lm_head and h32 must be 16-byte aligned, the row stride of h32 a multiple of 4")
+    w = None
+    if norm_weight is not None and eps > 0:
+        w = norm_weight
+        if w.dtype != torch.float16 or w.shape != (k,) or not w.is_contiguous() or w.device != h32.device or w.data_ptr() % 8:
+            raise QpalError(f"{who}: norm_weight must be a contiguous 8-byte aligned fp16 [{k}] tensor on {h32.device}")
+    if out is None:
+        out = torch.empty(rows, vocab, dtype=torch.float32, device=h32.device)
+    elif (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != rows or out.shape[1] < vocab or out.stride(1) != 1
+          or out.device != h32.device or (rows > 1 and out.stride(0) < vocab)):
+        raise QpalError(f"{who}: out must be fp32 [{rows}, >= {vocab}] with contiguous rows on {h32.device}")
+    ld_out = out.stride(0) if rows > 1 else out.shape[1]
+    with torch.cuda.device(h32.device):
+        rc = _native.lib().qpal_lm_head_logits(h32.data_ptr(), ld_h, w.data_ptr() if w is not None else None, float(eps) if w is not None else 0.0,
+                                               lm_head.data_ptr(), out.data_ptr(), ld_out, rows, vocab, k,
+                                               torch.cuda.current_stream(h32.device).cuda_stream)
+    _native.check(rc, "qpal_lm_head_logits")
+    return out
+
+
+def _param(t, name, dtype, rows, dev, who):
+    from ._native import QpalError
+    if t.dtype != dtype or t.shape != (rows,) or t.device != dev or not t.is_contiguous():
+        raise QpalError(f"{who}: {name} must be a contiguous {dtype} [{rows}] tensor on {dev}")
+    return t.data_ptr()
+
+
+def sample(logits, params, ctr, out=None, vocab=None):
+    """token int64 [rows]: one draw per row of logits fp32 [rows, >= vocab] (contiguous rows; vocab defaults to the width) with
+    params.temperature / top_k / top_p / seed ([rows] device tensors: a Sampler, or a view of one) and the counter ctr int64 [rows]
+    (the position; < 0: the row is inactive and out[row] keeps what it held).  Launches on the current stream; no host read."""
+    torch = _torch()
+    from . import _native
+    who, QpalError = "sample", _native.QpalError
+    if logits.dtype != torch.float32 or not logits.is_cuda or logits.dim() != 2 or logits.stride(1) != 1:
+        raise QpalError(f"{who}: logits must be an fp32 device tensor [rows, vocab] with contiguous rows")
+    rows, dev = logits.shape[0], logits.device
+    vocab = logits.shape[1] if vocab is None else int(vocab)
+    ld = logits.stride(0) if rows > 1 else logits.shape[1]
+    if not 1 <= rows <= 128 or not 1 <= vocab <= logits.shape[1] or ld < vocab:
+        raise QpalError(f"{who}: rows must be in 1 .. 128 and 1 <= vocab <= the row width, got {list(logits.shape)}, vocab {vocab}")
+    ptrs = [_param(params.temperature, "temperature", torch.float32, rows, dev, who), _param(params.top_k, "top_k", torch.int32, rows, dev, who),
+            _param(params.top_p, "top_p", torch.float32, rows, dev, who), _param(params.seed, "seed", torch.int64, rows, dev, who),
+            _param(ctr, "ctr", torch.int64, rows, dev, who)]
+    if out is None:
+        out = torch.zeros(rows, dtype=torch.int64, device=dev)
+    else:
+        _param(out, "out", torch.int64, rows, dev, who)
+    with torch.cuda.device(dev):
+        rc = _native.lib().qpal_sample(logits.data_ptr(), ld, rows, vocab, *ptrs, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _native.check(rc, "qpal_sample")
+    return out
+
+
+class Sampler:
+    """Per-slot sampling parameters of B sequences, on the device: temperature fp32, top_k int32, top_p fp32, seed int64, each [B],
+    and the logits buffer fp32 [B, vocab] the step's lm_head writes.  Scalars broadcast; sequences of B values are taken per slot.
+    temperature <= 0 or top_k == 1: greedy; top_k <= 0: no top-k; top_p >= 1 or <= 0: no top-p.  A captured step reads the tensors
+    when it runs: ``set`` between replays changes the next draw."""
+
+    def __init__(self, B, vocab, device, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+        torch = _torch()
+        from ._native import QpalError
+        if not 1 <= int(B) <= 128 or int(vocab) < 1:
+            raise QpalError(f"Sampler: B must be in 1 .. 128 and vocab >= 1, got {B}, {vocab}")
+        self.B, self.vocab, self.device = int(B), int(vocab), torch.device(device)
+
+        def full(v, dtype):
+            t = torch.as_tensor(v, dtype=dtype).reshape(-1)
+            if t.numel() not in (1, self.B):
+                raise QpalError(f"Sampler: a scalar or {self.B} values, got {t.numel()}")
+            return t.expand(self.B).contiguous().to(self.device)
+
+        self.temperature, self.top_k = full(temperature, torch.float32), full(top_k, torch.int32)
+        self.top_p, self.seed = full(top_p, torch.float32), full(seed, torch.int64)
+        self.logits = torch.zeros(self.B, self.vocab, dtype=torch.float32, device=self.device)
+
+    def set(self, slot, temperature=None, top_k=None, top_p=None, seed=None):
+        """write one slot's parameters (those given)"""
+        from ._native import QpalError
+        if not 0 <= int(slot) < self.B:
+            raise QpalError(f"Sampler.set: slot {slot} outside 0 .. {self.B - 1}")
+        for t, v in ((self.temperature, temperature), (self.top_k, top_k), (self.top_p, top_p), (self.seed, seed)):
+            if v is not None:
+                t[int(slot)] = v
+
+    def slot(self, slot):
+        """a one-row view of slot `slot` (what Prefill draws with): same storage"""
+        v = object.__new__(Sampler)
+        v.B, v.vocab, v.device = 1, self.vocab, self.device
+        s = slice(int(slot), int(slot) + 1)
+        v.temperature, v.top_k, v.top_p, v.seed, v.logits = self.temperature[s], self.top_k[s], self.top_p[s], self.seed[s], self.logits[s]
+        return v
