@@ -385,6 +385,23 @@ int qpal_lm_head_logits(const float *h_f32, long ld_h, const void *rms_w_f16, fl
 int qpal_sample(const float *logits_f32, long ld_logits, int rows, int vocab, const float *temperature, const int *top_k,
                 const float *top_p, const long *seed, const long *ctr, long *token, void *stream);
 
+/* Log-probability of ONE token per row under the plain softmax of the row's raw logits (temperature 1, no top-k / top-p: what
+ * "logprobs" means to a sampler's user and what a cross-entropy sums), one launch (csrc/logprob.hip).  logits fp32
+ * [rows][ld_logits], 1 <= rows <= 128, 1 <= vocab <= 2^30, ld_logits >= vocab — the shapes and return codes of qpal_sample.  token int64
+ * [rows], logprob fp32 [rows]; lse fp32 [rows], rank int32 [rows] and active int64 [rows] may each be NULL.  All on the device and
+ * never read by the host (capturable; the caller may rewrite token / active between replays); no workspace, no atomics.
+ * For row b with logits l[0 .. vocab) and t = token[b]:
+ *  1. t < 0, t >= vocab, or active != NULL and active[b] < 0 (qpal_sample's rule for ctr: a decode step passes its positions):
+ *     the row is inactive; nothing is written to any output of it.
+ *  2. A NaN logit is read as -inf.  lse[b] = log sum_i exp(l[i]);  logprob[b] = l[t] - lse[b];  rank[b] = #{i : l[i] > l[t]}
+ *     on the raw fp32 values (exact; 0: t is a most likely token).
+ *  3. l[t] = -inf: logprob = -inf.  No logit above -inf: lse = -inf, logprob = -inf, rank = 0.  +inf logits: lse = +inf and the
+ *     +inf entries share the mass, logprob = -log(their number) for each of them, -inf for every other token.
+ * Sums run in a fixed order: two launches on the same input are bitwise equal.  lse and logprob are within 2^-15 + 2^-22 max|l|
+ * of the fp64 value.                                                                                          */
+int qpal_token_logprob(const float *logits_f32, long ld_logits, int rows, int vocab, const long long *token, float *logprob,
+                       float *lse, int *rank, const long long *active, void *stream);
+
 /* The launch planner of the fused GEMV entry points, on its own (host code, no GPU call; what tests and tools inspect).
  * A launch of njobs jobs — rows[j] supertile rows (m / 32) of steps1[j] + steps2[j] steps (a step = 128 columns; steps2 = 0: one
  * stream) — is cut into workgroup-sized pieces: a GROUP of G = 1 << lg_g workgroups (`waves` = 16 or 8 waves each) owns rg

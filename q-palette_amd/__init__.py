@@ -12,9 +12,11 @@ Layout:
   attention.py     decode_attention / attention_workspace: rope + KV append + GQA attention of B sequences, one launch;
                    prefill_attention / prefill_workspace: the same for up to 128 new tokens of one sequence, causal
   decoder.py       DecodeStep: the whole-model decode step at batch B >= 1 on the kernels above (per-layer launch sequence,
-                   scratch buffers, final norm + lm_head + argmax, launches per token)
+                   scratch buffers, final norm + lm_head + argmax, launches per token); Prefill: a prompt into one cache slot;
+                   Score: the log-probability of every next token of a sequence, nll and perplexity
   sampling.py      lm_head_logits (final norm + lm_head for up to 128 rows), sample / Sampler (temperature, top-k, top-p, seeded
-                   draw; per-slot parameters on the device), reference_draw (the draw's contract in numpy fp64)
+                   draw; per-slot parameters on the device), reference_draw (the draw's contract in numpy fp64);
+                   token_logprobs (log softmax of a row at one token, csrc/logprob.hip) and its contract reference_logprob
   packers.py       pack_trellis / pack_qweight / pack_qweight_{sq,vq}_simt on the C-ABI's host-side encoders
   quantize.py      TCQ quantiser: tail-biting Viterbi encoder (csrc/tcq_viterbi.hip) + LDLQ -> QTIPLinearTCQ
                    VQ / SQ quantiser: nearest-codeword LDLQ encoder (csrc/vq_encode.hip) -> VQLinearPack{TensorCore,SIMT}
@@ -50,9 +52,9 @@ from . import quantize_layer  # noqa: F401
 from . import attention  # noqa: F401
 from .attention import attention_workspace, decode_attention, prefill_attention, prefill_workspace  # noqa: F401
 from . import sampling  # noqa: F401
-from .sampling import Sampler, lm_head_logits, reference_draw, sample  # noqa: F401
+from .sampling import Sampler, lm_head_logits, reference_draw, reference_logprob, sample, token_logprobs  # noqa: F401
 from . import decoder  # noqa: F401
-from .decoder import DecodeStep, Prefill  # noqa: F401
+from .decoder import DecodeStep, Prefill, Score, perplexity  # noqa: F401
 from .quantize_layer import incoherent_preprocess, layer_file_path, load_hessian, quantize_linear  # noqa: F401
 
 __version__ = "0.1.0"

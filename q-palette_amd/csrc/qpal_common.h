@@ -168,4 +168,27 @@ __device__ __forceinline__ float wave_sum(float v) {
     return (r0 + r1) + (r2 + r3);
 }
 
+constexpr float kNegInf = -__builtin_inff();
+
+// One pass of a 1024-thread workgroup over a row of fp32 logits (csrc/sample.hip, csrc/logprob.hip).  Every thread: groups of four
+// consecutive tokens j = tid, tid + 1024, ...; f(j, n, v): tokens 4 j .. 4 j + n - 1.  vec: the row is 16-byte aligned.
+template <class F>
+__device__ __forceinline__ void row_pass4(const float *row, int vocab, bool vec, F &&f) {
+    const int ngrp = (vocab + 3) >> 2;
+    for (int j = threadIdx.x; j < ngrp; j += 1024) {
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        const int i0 = 4 * j;
+        int n = vocab - i0 < 4 ? vocab - i0 : 4;
+        if (vec && n == 4) {
+            const float4 t = *reinterpret_cast<const float4 *>(row + i0);
+            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                if (e < n) v[e] = row[i0 + e];
+        }
+        f(j, n, v);
+    }
+}
+
 }  // namespace qpal

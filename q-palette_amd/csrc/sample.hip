@@ -30,7 +30,6 @@ struct SampleParams {
 };
 
 constexpr int kSampleBins = 2048;
-constexpr float kNegInf = -__builtin_inff();
 
 // order-preserving unsigned image of an fp32 value: a < b <=> key(a) < key(b); -0 and +0 share a key; NaN: 0 (below -inf)
 __device__ __forceinline__ uint32_t sample_key(float l) {
@@ -50,26 +49,6 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// every thread: groups of four consecutive tokens j = tid, tid + 1024, ...; f(j, n, v): tokens 4 j .. 4 j + n - 1
-template <class F>
-__device__ __forceinline__ void sample_row_pass(const float *row, int vocab, bool vec, F &&f) {
-    const int ngrp = (vocab + 3) >> 2;
-    for (int j = threadIdx.x; j < ngrp; j += 1024) {
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        const int i0 = 4 * j;
-        int n = vocab - i0 < 4 ? vocab - i0 : 4;
-        if (vec && n == 4) {
-            const float4 t = *reinterpret_cast<const float4 *>(row + i0);
-            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-                if (e < n) v[e] = row[i0 + e];
-        }
-        f(j, n, v);
-    }
 }
 
 __device__ __forceinline__ unsigned long long shfl_down_u64(unsigned long long v, int off) {
@@ -99,7 +78,7 @@ __device__ uint32_t sample_select(SampleShared &sh, const float *row, int vocab,
         const int nbits = pass < 2 ? 11 : 10, shift = 32 - done_bits - nbits;
         for (int i = tid; i < kSampleBins; i += 1024) sh.hist[i] = 0ull;
         __syncthreads();
-        sample_row_pass(row, vocab, vec, [&](int, int n, const float (&v)[4]) {
+        row_pass4(row, vocab, vec, [&](int, int n, const float (&v)[4]) {
 #pragma unroll
             for (int e = 0; e < 4; e++) {
                 if (e >= n) continue;
@@ -182,7 +161,7 @@ __global__ __launch_bounds__(1024) void sample_kernel(const SampleParams p) {
         if (thr < 1u) thr = 1u;
         if (top_p > 0.f && top_p < 1.f) {
             float mx = kNegInf;
-            sample_row_pass(row, vocab, vec, [&](int, int n, const float (&v)[4]) {
+            row_pass4(row, vocab, vec, [&](int, int n, const float (&v)[4]) {
 #pragma unroll
                 for (int e = 0; e < 4; e++)
                     if (e < n && v[e] > mx) mx = v[e];
@@ -202,7 +181,7 @@ __global__ __launch_bounds__(1024) void sample_kernel(const SampleParams p) {
     float best = kNegInf;
     int besti = 0x7fffffff;
     const uint32_t ctr_lo = (uint32_t)(unsigned long long)ctr, ctr_hi = (uint32_t)((unsigned long long)ctr >> 32);
-    sample_row_pass(row, vocab, vec, [&](int j, int n, const float (&v)[4]) {
+    row_pass4(row, vocab, vec, [&](int j, int n, const float (&v)[4]) {
         bool any = false;
 #pragma unroll
         for (int e = 0; e < 4; e++) any |= e < n && sample_key(v[e]) >= thr;

@@ -22,6 +22,13 @@ in chunks of at most 128 rows, with `prefill_attention` (causal, rows appended t
 
     pf = Prefill(layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128)
     next_tok = pf(tokens, slot=0, pos0=0)   # then DecodeStep with tok[slot] = next_tok, pos[slot] = len(tokens)
+
+`Score` is `Prefill` with a tail on EVERY row instead of the last one: the log-probability of each next token of a sequence
+(`qpal_lm_head_logits` on the chunk's rows + `qpal_token_logprob`), `Score.nll` and `perplexity` over windows.
+
+    sc = Score(layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128)
+    lp = sc(tokens, slot=0, pos0=0)         # fp32 [N - 1]: lp[t] = log p(tokens[t + 1] | tokens[0 .. t])
+    ppl, loss = perplexity(sc, windows)     # windows int64 [W, N]
 """
 import math
 
@@ -74,7 +81,9 @@ class DecodeStep:
     [hd / 2]; tok, pos, out_tok int64 [B] (pos[b] outside the cache: sequence b is inactive).  The caller owns the caches and
     tok / pos / out_tok and may write them between replays of a captured step.  swiglu_epilogue, k28_fusion, native_lm_head,
     split_attention switch single fusions of the batch-1 step off (profiling).  sampler: a sampling.Sampler of B slots — the tail
-    becomes lm_head logits of all B rows + one draw per active row with the counter pos[b] (two launches); None: argmax."""
+    becomes lm_head logits of all B rows + one draw per active row with the counter pos[b] (two launches); None: argmax.  A sampler
+    built with logprobs=True adds a third launch: sampler.logprob[b] = the log-probability of out_tok[b] under the plain softmax of
+    sampler.logits[b], for the rows that drew (pos[b] >= 0 — the positions are the launch's `active` vector; other slots keep theirs)."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok, generic=False,
                  swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True, sampler=None):
@@ -108,22 +117,29 @@ class DecodeStep:
             self.attn_ws = attention_workspace(B, self.nq, self.nkv, self.head_dim, self.context, dev)
 
     @staticmethod
+    def _check_lm_head(who, embed, lm_head):
+        H = embed.shape[1]
+        if H % 512 or H > 8192 or lm_head.data_ptr() % 16 or not lm_head.is_contiguous():
+            raise nat.QpalError(f"{who}: qpal_lm_head_logits needs a hidden width that is a multiple of 512 up to 8192 and a "
+                                "contiguous 16-byte aligned lm_head")
+
+    @staticmethod
     def _check_sampler(sampler, B, embed, lm_head):
         if sampler is None:
             return None
-        H = embed.shape[1]
         if sampler.B != B or sampler.vocab != lm_head.shape[0] or sampler.device != embed.device:
             raise nat.QpalError(f"sampler: built for {sampler.B} slots of {sampler.vocab} logits on {sampler.device}, "
                                 f"the step has {B} of {lm_head.shape[0]} on {embed.device}")
-        if H % 512 or H > 8192 or lm_head.data_ptr() % 16 or not lm_head.is_contiguous():
-            raise nat.QpalError("sampler: qpal_lm_head_logits needs a hidden width that is a multiple of 512 up to 8192 and a "
-                                "contiguous 16-byte aligned lm_head")
+        DecodeStep._check_lm_head("sampler", embed, lm_head)
         return sampler
 
     def _sample_tail(self, h32, smp, ctr, out_tok):
-        """final norm + lm_head of every row of h32 into smp.logits, then one draw per row with the counters ctr: two launches"""
+        """final norm + lm_head of every row of h32 into smp.logits, then one draw per row with the counters ctr: two launches; with
+        smp.logprob a third, the log-probability of the tokens just drawn (rows with ctr < 0 drew nothing and keep theirs)"""
         sampling.lm_head_logits(h32, self.norm.weight, self.norm.eps, self.lm_head, out=smp.logits)
         sampling.sample(smp.logits, smp, ctr, out=out_tok)
+        if smp.logprob is not None:
+            sampling.token_logprobs(smp.logits, out_tok, out=smp.logprob, active=ctr)
 
     def _setup_rows(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows):
         """what every step on `rows` rows of the residual stream needs (self.batch1 is set): the model, the rotation of the hidden
@@ -147,9 +163,11 @@ class DecodeStep:
     def launches_per_token(self):
         """kernel launches of one step: per layer q|k|v, attention, o, up|gate, SwiGLU rotation, down (+ a rotation in front of
         q|k|v, o and up|gate where the GEMV cannot rotate; - the SwiGLU rotation where down_proj's staging runs it); + the norm /
-        lm_head / argmax launch, or the lm_head logits and the draw with a sampler (the embedding row copy is a memcpy node)"""
+        lm_head / argmax launch, or the lm_head logits and the draw with a sampler, + the log-probability launch of a sampler with
+        logprobs (the embedding row copy is a memcpy node)"""
         per_layer = (5 if self.ug_il and self.ug_il[0][2] else 6) if self.rot_in_gemv else 9
-        return per_layer * len(self.layers) + (1 if self.sampler is None else 2)
+        tail = 1 if self.sampler is None else (2 if self.sampler.logprob is None else 3)
+        return per_layer * len(self.layers) + tail
 
     def _gemv(self, proj, x, su, scale, rms=None, **kw):
         """multi_gemv of one projection group on rotate(RMSNorm(x) * su) / scale: RMSNorm + rotation inside the GEMV launch, or
@@ -240,7 +258,8 @@ class Prefill(DecodeStep):
 
     sampler: the sampling.Sampler of the DecodeStep whose caches this fills (one slot per sequence of the caches).  The token is then
     drawn with slot `slot`'s parameters and the counter of the last prompt row's position, pos0 + N - 1 (computed on the device):
-    the counter a DecodeStep would have used had it fed that token.  sampler.logits[slot] holds the logits."""
+    the counter a DecodeStep would have used had it fed that token.  sampler.logits[slot] holds the logits, and with a sampler
+    built with logprobs=True sampler.logprob[slot] the token's log-probability."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, native_lm_head=True, sampler=None):
         if not 1 <= int(chunk) <= 128:
@@ -272,28 +291,43 @@ class Prefill(DecodeStep):
         """fp16 [1, H]: the final norm of the last prompt row"""
         return self.norm(self.last32.half())
 
-    def __call__(self, tokens, slot=0, pos0=0):
-        if tokens.dim() != 1 or tokens.shape[0] < 1 or tokens.dtype != torch.int64 or tokens.device != self.embed.device:
-            raise nat.QpalError(f"Prefill: tokens must be int64 [N >= 1] on {self.embed.device}")
+    def _begin(self, tokens, slot, pos0, least=1):
+        """the argument checks of a call; sets self.slot and the device position; returns N"""
+        who = type(self).__name__
+        if tokens.dim() != 1 or tokens.shape[0] < least or tokens.dtype != torch.int64 or tokens.device != self.embed.device:
+            raise nat.QpalError(f"{who}: tokens must be int64 [N >= {least}] on {self.embed.device}")
         N = tokens.shape[0]
         if not 0 <= int(slot) < self.kcache[0].shape[0]:
-            raise nat.QpalError(f"Prefill: slot {slot} outside the caches' {self.kcache[0].shape[0]} sequences")
+            raise nat.QpalError(f"{who}: slot {slot} outside the caches' {self.kcache[0].shape[0]} sequences")
         self.slot = int(slot)
         if isinstance(pos0, torch.Tensor):
             self.pos.copy_(pos0.reshape(1))
         else:
             if pos0 < 0 or N + pos0 > self.context:
-                raise nat.QpalError(f"Prefill: {N} tokens from position {pos0} do not fit a cache of {self.context} positions")
+                raise nat.QpalError(f"{who}: {N} tokens from position {pos0} do not fit a cache of {self.context} positions")
             self.pos.fill_(int(pos0))
-        for c in range(0, N, self.chunk):
-            n = min(self.chunk, N - c)
-            self.h32, self.a16, self.qkv32, self.ug32 = (t[:n] for t in self._full)
-            self.h32.copy_(self.embed[tokens[c:c + n]])
-            for i in range(len(self.layers)):
-                self._layer(i)
-            self.pos += n
-        self.last32.copy_(self.h32[n - 1:n])
-        self.h32, self.a16, self.qkv32, self.ug32 = self._full
+        return N
+
+    def _chunks(self, tokens, N):
+        """runs the layers chunk by chunk; yields (c, n) after chunk tokens[c : c + n], with self.h32 its n rows of the residual
+        stream.  The full-size row buffers are back in place when the generator ends, however it ends."""
+        try:
+            for c in range(0, N, self.chunk):
+                n = min(self.chunk, N - c)
+                self.h32, self.a16, self.qkv32, self.ug32 = (t[:n] for t in self._full)
+                self.h32.copy_(self.embed[tokens[c:c + n]])
+                for i in range(len(self.layers)):
+                    self._layer(i)
+                self.pos += n
+                yield c, n
+            self.last32.copy_(self.h32[n - 1:n])
+        finally:
+            self.h32, self.a16, self.qkv32, self.ug32 = self._full
+
+    def __call__(self, tokens, slot=0, pos0=0):
+        N = self._begin(tokens, slot, pos0)
+        for _ in self._chunks(tokens, N):
+            pass
         if self.sampler is not None:
             torch.sub(self.pos, 1, out=self.ctr)
             self._sample_tail(self.last32, self.sampler.slot(self.slot), self.ctr, self.out_tok)
@@ -309,3 +343,66 @@ class Prefill(DecodeStep):
                                                torch.cuda.current_stream(dev).cuda_stream)
         nat.check(rc, "qpal_lm_head_argmax")
         return self.out_tok
+
+
+class Score(Prefill):
+    """The log-probability of every next token of a sequence: Prefill's chunks (same caches, chunking, slot / pos0 rules and errors),
+    each followed by `qpal_lm_head_logits` on ALL rows of the chunk and `qpal_token_logprob` against the tokens that follow them.
+
+        sc = Score(layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128)
+        lp = sc(tokens, slot=0, pos0=0)     # tokens int64 [N >= 2] on the device -> fp32 [N - 1]
+        # lp[t] = log p(tokens[t + 1] | the cache below pos0, tokens[0 .. t]); sc.rank int32 [N - 1]: tokens more likely than it
+
+    The logits live in ONE fp32 [chunk, vocab] buffer (sc.logits: the last chunk's n rows); lp and sc.rank are views of buffers of
+    max_tokens entries (default: the caches' context) that the next call overwrites.  No host synchronisation inside the call.  The
+    last row has no next token: its logits are computed, its row of the log-prob launch is inactive.  The slot is left as Prefill
+    leaves it: a DecodeStep can continue at position pos0 + N.  The lm_head must suit qpal_lm_head_logits (a sampler's demands)."""
+
+    def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, max_tokens=None):
+        self._check_lm_head("Score", embed, lm_head)
+        super().__init__(layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=chunk, native_lm_head=False)
+        self.max_tokens = self.context if max_tokens is None else int(max_tokens)
+        if self.max_tokens < 2:
+            raise nat.QpalError(f"Score: max_tokens must be at least 2, got {max_tokens}")
+        dev = embed.device
+        self._logits = torch.zeros(self.chunk, lm_head.shape[0], dtype=torch.float32, device=dev)
+        self._targets = torch.zeros(self.max_tokens, dtype=torch.int64, device=dev)  # tokens[1:], then -1: the row without a target
+        self._lp = torch.zeros(self.max_tokens, dtype=torch.float32, device=dev)
+        self._rank = torch.zeros(self.max_tokens, dtype=torch.int32, device=dev)
+        self.logits, self.rank = self._logits[:0], self._rank[:0]
+
+    def __call__(self, tokens, slot=0, pos0=0):
+        N = self._begin(tokens, slot, pos0, least=2)
+        if N > self.max_tokens:
+            raise nat.QpalError(f"Score: {N} tokens, built for max_tokens = {self.max_tokens}")
+        self._targets[:N - 1].copy_(tokens[1:])
+        self._targets[N - 1:N].fill_(-1)
+        for c, n in self._chunks(tokens, N):
+            self.logits = self._logits[:n]
+            sampling.lm_head_logits(self.h32, self.norm.weight, self.norm.eps, self.lm_head, out=self.logits)
+            sampling.token_logprobs(self.logits, self._targets[c:c + n], out=self._lp[c:c + n], rank=self._rank[c:c + n])
+        self.rank = self._rank[:N - 1]
+        return self._lp[:N - 1]
+
+    def nll(self, tokens, slot=0, pos0=0):
+        """device scalar (fp64): the mean of -lp over the N - 1 predicted tokens — the cross-entropy loss of one window"""
+        return -self(tokens, slot=slot, pos0=pos0).double().mean()
+
+
+def perplexity(score, windows, slot=0, out=None):
+    """(ppl, avg_loss) of int64 windows [W, N] on the device: every window scored from an empty context (pos0 = 0) in `slot`;
+    avg_loss = the mean over windows of each window's mean loss, summed on the device in fp64 and read once; ppl = exp(avg_loss).
+    out: an optional fp32 [W, N - 1] device tensor that receives the log-probabilities the figure was computed from."""
+    if windows.dim() != 2 or windows.shape[0] < 1 or windows.shape[1] < 2 or windows.dtype != torch.int64:
+        raise nat.QpalError("perplexity: windows must be int64 [W >= 1, N >= 2]")
+    W, N = windows.shape
+    if out is not None and (out.shape != (W, N - 1) or out.dtype != torch.float32 or out.device != windows.device):
+        raise nat.QpalError(f"perplexity: out must be fp32 [{W}, {N - 1}] on {windows.device}")
+    total = torch.zeros((), dtype=torch.float64, device=windows.device)
+    for w in range(W):
+        lp = score(windows[w], slot=slot, pos0=0)
+        if out is not None:
+            out[w].copy_(lp)
+        total -= lp.double().mean()
+    avg = float(total) / W
+    return math.exp(avg), avg

@@ -8,6 +8,11 @@ temperature / top-k / top-p / seeded draw (``qpal_sample``, csrc/sample.hip), on
 
 ``decoder.DecodeStep(..., sampler=smp)`` and ``decoder.Prefill(..., sampler=smp)`` end in these two launches.
 
+    lp = token_logprobs(smp.logits, tok)      # fp32 [B]: log softmax(logits)[tok], one launch (``qpal_token_logprob``, csrc/logprob.hip)
+
+``Sampler(..., logprobs=True)`` makes that the third launch of the tail (``smp.logprob``); ``decoder.Score`` runs it on every row of
+a prompt.  ``reference_logprob`` is its contract in numpy fp64.
+
 The draw is specified exactly (include/qpal.h); ``reference_draw`` restates it in numpy fp64 with its own Philox.
 It is the specification the tests hold the kernel to: CPU only, no torch.cuda, no library call.
 """
@@ -106,6 +111,24 @@ def reference_draw(logits_row, temperature, top_k, top_p, seed, ctr):
     return int(tok[0]) if scalar else tok
 
 
+def reference_logprob(logits_row, token):
+    """The contract of qpal_token_logprob for one row, in fp64 on clean_logits(row): (logprob, lse, rank) as Python floats and an
+    int, or None for an inactive row (token < 0 or >= vocab).  Plain softmax of the raw logits (temperature 1, no filter); rank =
+    #{i : l[i] > l[token]} on the fp32 values.  No logit above -inf: (-inf, -inf, 0); +inf logits share the mass equally."""
+    l = clean_logits(logits_row)
+    token = int(token)
+    if not 0 <= token < l.shape[0]:
+        return None
+    lt, lmax = float(l[token]), float(l.max())
+    rank = int((l > l[token]).sum())
+    if lmax == -np.inf:
+        return -np.inf, -np.inf, 0
+    if lmax == np.inf:
+        return (-float(np.log((l == lmax).sum())) if lt == lmax else -np.inf), np.inf, rank
+    lse = lmax + float(np.log(np.exp(l.astype(np.float64) - lmax).sum()))
+    return (lt - lse if lt > -np.inf else -np.inf), lse, rank
+
+
 # ---------------------------------------------------------------------------------------------------------------- GPU side
 
 def _torch():
@@ -185,13 +208,44 @@ def sample(logits, params, ctr, out=None, vocab=None):
     return out
 
 
+def token_logprobs(logits, tokens, out=None, lse=None, rank=None, vocab=None, active=None):
+    """logprob fp32 [rows]: log softmax(logits[row, :vocab])[tokens[row]] per row of logits fp32 [rows, >= vocab] (contiguous rows;
+    vocab defaults to the width), tokens int64 [rows].  A row whose token is < 0 or >= vocab, or whose active[row] < 0 (active: an
+    optional int64 [rows], a decode step's positions), is inactive: its entries of out / lse / rank keep what they held.  lse fp32
+    [rows] and rank int32 [rows], where given, receive the row's log-sum-exp and #{i : l[i] > l[token]}.  Launches on the current
+    stream; no host read."""
+    torch = _torch()
+    from . import _native
+    who, QpalError = "token_logprobs", _native.QpalError
+    if logits.dtype != torch.float32 or not logits.is_cuda or logits.dim() != 2 or logits.stride(1) != 1:
+        raise QpalError(f"{who}: logits must be an fp32 device tensor [rows, vocab] with contiguous rows")
+    rows, dev = logits.shape[0], logits.device
+    vocab = logits.shape[1] if vocab is None else int(vocab)
+    ld = logits.stride(0) if rows > 1 else logits.shape[1]
+    if not 1 <= rows <= 128 or not 1 <= vocab <= logits.shape[1] or ld < vocab:
+        raise QpalError(f"{who}: rows must be in 1 .. 128 and 1 <= vocab <= the row width, got {list(logits.shape)}, vocab {vocab}")
+    tok_p = _param(tokens, "tokens", torch.int64, rows, dev, who)
+    if out is None:
+        out = torch.zeros(rows, dtype=torch.float32, device=dev)
+    ptrs = [_param(out, "out", torch.float32, rows, dev, who),
+            None if lse is None else _param(lse, "lse", torch.float32, rows, dev, who),
+            None if rank is None else _param(rank, "rank", torch.int32, rows, dev, who),
+            None if active is None else _param(active, "active", torch.int64, rows, dev, who)]
+    with torch.cuda.device(dev):
+        rc = _native.lib().qpal_token_logprob(logits.data_ptr(), ld, rows, vocab, tok_p, *ptrs, torch.cuda.current_stream(dev).cuda_stream)
+    _native.check(rc, "qpal_token_logprob")
+    return out
+
+
 class Sampler:
     """Per-slot sampling parameters of B sequences, on the device: temperature fp32, top_k int32, top_p fp32, seed int64, each [B],
     and the logits buffer fp32 [B, vocab] the step's lm_head writes.  Scalars broadcast; sequences of B values are taken per slot.
     temperature <= 0 or top_k == 1: greedy; top_k <= 0: no top-k; top_p >= 1 or <= 0: no top-p.  A captured step reads the tensors
-    when it runs: ``set`` between replays changes the next draw."""
+    when it runs: ``set`` between replays changes the next draw.  logprobs=True: the sampler also owns logprob fp32 [B], and a step
+    with this sampler writes the log-probability of each token it draws there (plain softmax of the logits, whatever the filter:
+    token_logprobs; one more launch); otherwise logprob is None."""
 
-    def __init__(self, B, vocab, device, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+    def __init__(self, B, vocab, device, temperature=1.0, top_k=0, top_p=1.0, seed=0, logprobs=False):
         torch = _torch()
         from ._native import QpalError
         if not 1 <= int(B) <= 128 or int(vocab) < 1:
@@ -207,6 +261,7 @@ class Sampler:
         self.temperature, self.top_k = full(temperature, torch.float32), full(top_k, torch.int32)
         self.top_p, self.seed = full(top_p, torch.float32), full(seed, torch.int64)
         self.logits = torch.zeros(self.B, self.vocab, dtype=torch.float32, device=self.device)
+        self.logprob = torch.zeros(self.B, dtype=torch.float32, device=self.device) if logprobs else None
 
     def set(self, slot, temperature=None, top_k=None, top_p=None, seed=None):
         """write one slot's parameters (those given)"""
@@ -223,4 +278,5 @@ class Sampler:
         v.B, v.vocab, v.device = 1, self.vocab, self.device
         s = slice(int(slot), int(slot) + 1)
         v.temperature, v.top_k, v.top_p, v.seed, v.logits = self.temperature[s], self.top_k[s], self.top_p[s], self.seed[s], self.logits[s]
+        v.logprob = None if self.logprob is None else self.logprob[s]
         return v
