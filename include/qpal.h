@@ -357,6 +357,25 @@ int qpal_attn_rope_prefill(const float *q, const float *k, const float *v, long 
                            const long *pos0, const float *inv_freq, int T, int nq, int nkv, int hd,
                            long max_len, float scale, void *ws, long ws_bytes, void *stream);
 
+/* The same two launches on an 8-bit KV cache: OCP e4m3fn (torch.float8_e4m3fn, not the MI300 fnuz encoding), one byte per element,
+ * no scales, the layouts above ([B][nkv][max_len][hd] / [nkv][max_len][hd], 16-byte aligned).  With h the fp16 value the fp16
+ * entry point writes for a new row (bit for bit qpal_rope_kv's), the stored byte is h -> fp32, clamped to [-448, 448], rounded to
+ * nearest even, subnormals kept (torch: h.float().clamp(-448, 448).to(torch.float8_e4m3fn); NaN inputs unspecified).  A byte is
+ * converted exactly to fp16 and then used as an fp16 cache row is used: same products, same accumulation order.  The new rows of a
+ * launch take part in that launch at their stored value, so a position has ONE value whichever launch reads it, and a cache filled
+ * by prefill equals, byte for byte, a cache filled token by token from the same q|k|v.  Arguments, checks, error codes, inactive
+ * sequences, the *pos0 fit rule, graph capture and bitwise reproducibility are those of the fp16 siblings.  LDS layout, grid and
+ * workspace do not depend on the element type: qpal_attn_batch_ws_bytes / qpal_attn_prefill_ws_bytes size the workspace of both
+ * formats, and one workspace may serve launches of both. */
+int qpal_attn_rope_decode_batch_kv8(const float *q, const float *k, const float *v, long ld_qkv,
+                                    void *kcache_e4m3, void *vcache_e4m3, void *out_f16, long ld_out,
+                                    const long *pos, const float *inv_freq, int B, int nq, int nkv, int hd,
+                                    long max_len, float scale, void *ws, long ws_bytes, void *stream);
+int qpal_attn_rope_prefill_kv8(const float *q, const float *k, const float *v, long ld_qkv,
+                               void *kcache_e4m3, void *vcache_e4m3, void *out_f16, long ld_out,
+                               const long *pos0, const float *inv_freq, int T, int nq, int nkv, int hd,
+                               long max_len, float scale, void *ws, long ws_bytes, void *stream);
+
 /* Final norm + fp16 lm_head for `rows` rows of the residual stream at once, on the matrix pipe (csrc/lm_head_batch.hip): the
  * logits a sampler needs, and the batch-B tail of a decode step.  h_f32 fp32 [rows][ld_h] (ld_h >= k, in elements), 1 <= rows <=
  * 128; k a multiple of 512, 512 <= k <= 8192; w_f16 the lm_head fp16 [vocab][k]; logits_f32 fp32 [rows][ld_logits], ld_logits >=

@@ -3,10 +3,11 @@
 
 Llama-3 8B heads (32 query / 8 kv heads, hd 128) unless told otherwise.  Positions are ragged and seeded (uniform over the cache)
 or, with --full, every sequence at max_len - 1.  The bytes are the K and V rows the launch has to read, sum_b (pos[b] + 1) rows of
-nkv * hd fp16 each, not B * max_len.  Back-to-back launches timed with events; under `rocprofv3 --kernel-trace --stats` the
-kernel's own time comes from the trace.
+nkv * hd elements each (2 bytes with --kv fp16, 1 with --kv fp8: float8_e4m3fn caches), not B * max_len.
+Back-to-back launches timed with events; under `rocprofv3 --kernel-trace --stats` the kernel's own time comes from the trace (the
+two formats run different kernel instantiations; with both named, every row runs fp16 first, then fp8, 10 + iters launches each).
 
-    python perf/attn_batch_bench.py [--batch 8 64] [--context 1024 4096] [--iters 200] [--full]
+    python perf/attn_batch_bench.py [--batch 8 64] [--context 1024 4096] [--iters 200] [--full] [--kv fp16 fp8]
 """
 import argparse
 import json
@@ -28,6 +29,7 @@ def main(argv=None):
     ap.add_argument("--hd", type=int, default=128)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--full", action="store_true", help="every sequence at the last position of its cache")
+    ap.add_argument("--kv", nargs="+", default=["fp16"], choices=["fp16", "fp8"], help="KV-cache element format(s), in this order per row")
     args = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     nq, nkv, hd = args.nq, args.nkv, args.hd
@@ -40,26 +42,30 @@ def main(argv=None):
             pos = pos_h.to(dev)
             qkv = torch.randn(B, (nq + 2 * nkv) * hd, device=dev)
             q, k, v = qkv.split([nq * hd, nkv * hd, nkv * hd], dim=1)
-            kc = torch.randn(B, nkv, L, hd, device=dev).half()
-            vc = torch.randn(B, nkv, L, hd, device=dev).half()
+            kc16 = torch.randn(B, nkv, L, hd, device=dev).half()
+            vc16 = torch.randn(B, nkv, L, hd, device=dev).half()
             out = torch.empty(B, nq * hd, dtype=torch.float16, device=dev)
             ws = qp.attention_workspace(B, nq, nkv, hd, L, dev)
-            for _ in range(10):
-                qp.decode_attention(q, k, v, kc, vc, pos, inv_freq, out=out, ws=ws)
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(args.iters):
-                qp.decode_attention(q, k, v, kc, vc, pos, inv_freq, out=out, ws=ws)
-            e1.record()
-            torch.cuda.synchronize()
-            us = e0.elapsed_time(e1) * 1e3 / args.iters
-            kv_rows = int((pos_h + 1).sum())
-            nbytes = kv_rows * nkv * hd * 2 * 2
-            rows.append({"batch": B, "context": L, "full": args.full, "kv_rows": kv_rows, "kv_MB": nbytes / 1e6,
-                         "us_per_launch_events": us, "TBps_events": nbytes / (us * 1e-6) / 1e12,
-                         "workspace_bytes": 0 if ws is None else ws.numel() * 4})
-            del kc, vc
+            for kv in args.kv:
+                kc, vc = (kc16, vc16) if kv == "fp16" else (kc16.to(torch.float8_e4m3fn), vc16.to(torch.float8_e4m3fn))
+                for _ in range(10):
+                    qp.decode_attention(q, k, v, kc, vc, pos, inv_freq, out=out, ws=ws)
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(args.iters):
+                    qp.decode_attention(q, k, v, kc, vc, pos, inv_freq, out=out, ws=ws)
+                e1.record()
+                torch.cuda.synchronize()
+                us = e0.elapsed_time(e1) * 1e3 / args.iters
+                kv_rows = int((pos_h + 1).sum())
+                nbytes = kv_rows * nkv * hd * 2 * kc.element_size()
+                rows.append({"batch": B, "context": L, "kv": kv, "full": args.full, "kv_rows": kv_rows, "kv_MB": nbytes / 1e6,
+                             "us_per_launch_events": us, "TBps_events": nbytes / (us * 1e-6) / 1e12,
+                             "workspace_bytes": 0 if ws is None else ws.numel() * 4,
+                             "cache_bytes": 2 * qp.attention.kv_cache_bytes(B, nkv, L, hd, kc.dtype)})
+                del kc, vc
+            del kc16, vc16
             torch.cuda.empty_cache()
     print(json.dumps({"what": "batched decode attention, one launch", "nq": nq, "nkv": nkv, "hd": hd, "rows": rows}))
 

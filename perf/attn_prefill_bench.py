@@ -3,7 +3,9 @@
 4 nq hd sum_t (pos0 + t + 1), and torch SDPA on the same (already rotated) q and cache under a causal mask in the same call.
 Event timing here; for the kernel time proper run it under `rocprofv3 --kernel-trace --stats -- python perf/attn_prefill_bench.py`.
 
-    python perf/attn_prefill_bench.py [--T 128] [--pos0 0 1920 3968] [--context 4096] [--heads 32 8 128] [--iters 50]
+--kv fp8: float8_e4m3fn caches; torch SDPA then runs on their fp16 image.
+
+    python perf/attn_prefill_bench.py [--T 128] [--pos0 0 1920 3968] [--context 4096] [--heads 32 8 128] [--iters 50] [--kv fp16|fp8]
 """
 import argparse
 import json
@@ -23,6 +25,7 @@ def main(argv=None):
     ap.add_argument("--context", type=int, default=4096)
     ap.add_argument("--heads", type=int, nargs=3, default=[32, 8, 128], metavar=("NQ", "NKV", "HD"))
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--kv", default="fp16", choices=["fp16", "fp8"], help="KV-cache element format")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
@@ -33,6 +36,8 @@ def main(argv=None):
     q, k, v = qkv.split([nq * hd, nkv * hd, nkv * hd], dim=1)
     kc = (torch.randn(nkv, L, hd, device=dev, generator=gen) * 0.5).half()
     vc = (torch.randn(nkv, L, hd, device=dev, generator=gen) * 0.5).half()
+    if args.kv == "fp8":
+        kc, vc = kc.to(torch.float8_e4m3fn), vc.to(torch.float8_e4m3fn)
     inv_freq = 1.0 / (500000.0 ** (torch.arange(0, hd, 2, device=dev).float() / hd))
     ws = qp.prefill_workspace(T, nq, nkv, hd, L, dev)
     out = torch.empty(T, nq * hd, dtype=torch.float16, device=dev)
@@ -55,12 +60,12 @@ def main(argv=None):
         us = timed(lambda: qp.prefill_attention(q, k, v, kc, vc, pos_t, inv_freq, out=out, ws=ws))
         n = pos0 + T
         q16 = torch.randn(1, nq, T, hd, device=dev, generator=gen).half()
-        kk = kc[None, :, :n].repeat_interleave(nq // nkv, dim=1)
-        vv = vc[None, :, :n].repeat_interleave(nq // nkv, dim=1)
+        kk = kc[None, :, :n].half().repeat_interleave(nq // nkv, dim=1)
+        vv = vc[None, :, :n].half().repeat_interleave(nq // nkv, dim=1)
         mask = torch.arange(n, device=dev)[None, :] <= (pos0 + torch.arange(T, device=dev))[:, None]
         us_sdpa = timed(lambda: torch.nn.functional.scaled_dot_product_attention(q16, kk, vv, attn_mask=mask))
         flop = 4 * nq * hd * sum(pos0 + t + 1 for t in range(T))
-        rows.append({"T": T, "pos0": pos0, "flop": flop, "us_prefill_attention": us, "tflops": flop / us * 1e-6,
+        rows.append({"T": T, "pos0": pos0, "kv": args.kv, "flop": flop, "us_prefill_attention": us, "tflops": flop / us * 1e-6,
                      "us_torch_sdpa_causal_mask": us_sdpa})
     print(json.dumps({"what": "prefill attention launch (event timing) vs torch SDPA on the same shapes", "heads": args.heads,
                       "context": L, "rows": rows}))

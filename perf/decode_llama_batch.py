@@ -20,7 +20,13 @@ rotary embedding, a per-sequence cache write, SDPA with a per-sequence mask), wh
 --sample adds the sampled step (DecodeStep(sampler=...): qpal_lm_head_logits + qpal_sample in the torch tail's place) at temperature
 0.6 / top-k 5 (the setting of the decode loop this was modelled on) and 0.8 / top-p 0.95, timed in the same call as the greedy step.
 
+--kv fp8 keeps the caches as torch.float8_e4m3fn.  The torch-glue reference then keeps fp16 caches of its own that
+hold e4m3 values only: `BatchKV.update` stores a new row through the round trip clamp(-448, 448) -> float8_e4m3fn -> half and the
+step attends to the round-tripped cache, as the kernels do.  The check also reports how far the fp16-cache step lies from that
+reference (what the format itself moves; not a gate).
+
     python perf/decode_llama_batch.py [--model 3_8b] [--batch 1 8 16 32 64] [--context 1024] [--tokens 64] [--inactive 0] [--sample]
+                                      [--kv fp16|fp8]
 """
 import argparse
 import json
@@ -37,10 +43,11 @@ from decode_llama import build_model, time_graph
 
 class BatchKV:
     """Per-sequence static caches [B][nkv][max_len][hd] with the `update` the attention module calls: row pos[b] of sequence b
-    (a sequence whose position lies outside the cache keeps its cache as it is)."""
+    (a sequence whose position lies outside the cache keeps its cache as it is).  kv8: new rows are stored as the fp16 image of
+    their e4m3fn bytes (the stored value of an 8-bit cache)."""
 
-    def __init__(self, k, v):
-        self.k, self.v = k, v
+    def __init__(self, k, v, kv8=False):
+        self.k, self.v, self.kv8 = k, v, kv8
 
     def update(self, k, v, layer_idx, kwargs):
         pos = kwargs["cache_position"]
@@ -49,9 +56,16 @@ class BatchKV:
         live = ((pos >= 0) & (pos < L)).view(B, 1, 1)
         idx = pos.clamp(0, L - 1)
         rows = torch.arange(B, device=kc.device)
+        if self.kv8:
+            k, v = e4m3_round_trip(k), e4m3_round_trip(v)
         kc[rows, :, idx] = torch.where(live, k[:, :, 0], kc[rows, :, idx])
         vc[rows, :, idx] = torch.where(live, v[:, :, 0], vc[rows, :, idx])
         return kc, vc
+
+
+def e4m3_round_trip(x):
+    """the fp16 image of x stored as OCP e4m3fn: clamp to the format's range, round to nearest even, back to fp16 (exact)"""
+    return x.float().clamp(-448.0, 448.0).to(torch.float8_e4m3fn).half()
 
 
 def main(argv=None, quiet=False):
@@ -68,7 +82,9 @@ def main(argv=None, quiet=False):
     ap.add_argument("--seed", type=int, default=7, help="seed of the ragged positions")
     ap.add_argument("--no-torch-glue", action="store_true", help="skip the torch-glue step (its timing and the check)")
     ap.add_argument("--sample", action="store_true", help="also time the step with a sampler (0.6 / top-k 5 and 0.8 / top-p 0.95)")
+    ap.add_argument("--kv", default="fp16", choices=["fp16", "fp8"], help="KV-cache element format (fp8: OCP e4m3fn, no scales)")
     args = ap.parse_args(argv)
+    kv8 = args.kv == "fp8"
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
     if args.context % 4 or args.context < args.tokens + 16:
@@ -98,6 +114,11 @@ def main(argv=None, quiet=False):
         cg = torch.Generator(device=dev).manual_seed(args.seed)
         kc = [(torch.randn(B, nkv, args.context, head_dim, device=dev, generator=cg) * 0.5).half() for _ in range(nlayers)]
         vc = [(torch.randn(B, nkv, args.context, head_dim, device=dev, generator=cg) * 0.5).half() for _ in range(nlayers)]
+        kc_ref, vc_ref = kc, vc  # the torch-glue step's caches: the kernel step's own, or (fp8) an fp16 image of them
+        if kv8:
+            kc = [t.float().clamp(-448.0, 448.0).to(torch.float8_e4m3fn) for t in kc]
+            vc = [t.float().clamp(-448.0, 448.0).to(torch.float8_e4m3fn) for t in vc]
+            kc_ref, vc_ref = [t.half() for t in kc], [t.half() for t in vc]
         # generic: the B = 1 row runs the way every other row runs (rotation launches, decode_attention, torch tail)
         kernel_step = qp.DecodeStep(layers, embed, norm, lm_head, kc, vc, inv_freq, tok, pos, out_tok, generic=True)
         xh16 = torch.zeros(B, H, dtype=torch.float16, device=dev)      # linears-only: fixed rotated inputs
@@ -117,7 +138,7 @@ def main(argv=None, quiet=False):
                 qp.multi_gemv([mlp.down_proj], xi16, outs=[h32], wscales=[mlp.Wscale_dp], oscale=mlp.scale, accumulate=True)
 
         # torch-glue reference at the same B: the Incoherent* modules, torch rope, per-sequence cache rows, SDPA with a mask per sequence
-        ref_cache = BatchKV(kc, vc)
+        ref_cache = BatchKV(kc_ref, vc_ref, kv8)
         ar = torch.arange(args.context, device=dev)
 
         def torch_step():
@@ -149,6 +170,8 @@ def main(argv=None, quiet=False):
             kc0 = [t.clone() for t in kc]
             vc0 = [t.clone() for t in vc]
             pos.copy_(pos0)
+            if kv8:  # the fp16-cache step from the same (dequantised) contents, before the reference step writes its rows
+                kc16, vc16 = [t.clone() for t in kc_ref], [t.clone() for t in vc_ref]
             ref_h = torch_step().float()
             for t, t0 in zip(kc + vc, kc0 + vc0):
                 t.copy_(t0)
@@ -159,6 +182,11 @@ def main(argv=None, quiet=False):
             d = (ref_h[act] - got_h[act]).abs()
             check = {"max_abs_diff_final_norm": float(d.max()), "max_abs_ref": float(ref_h[act].abs().max()),
                      "finite": bool(torch.isfinite(got_h[act]).all())}
+            if kv8:
+                step16 = qp.DecodeStep(layers, embed, norm, lm_head, kc16, vc16, inv_freq, tok, pos, torch.zeros_like(out_tok), generic=True)
+                step16()
+                check["fp16_cache_max_abs_diff_final_norm"] = float((ref_h[act] - step16.hidden().float()[act]).abs().max())
+                del step16, kc16, vc16
         ms_step = timed(kernel_step)
         ms_lin = timed(linears_only, None)
         ms_torch = None if args.no_torch_glue else timed(torch_step)
@@ -176,10 +204,11 @@ def main(argv=None, quiet=False):
         res = {"batch": B, "active": nact, "ms_step": ms_step, "tokens_per_s": nact / ms_step * 1e3,
                "ms_linears_only": ms_lin, "ms_torch_glue": ms_torch,
                "tokens_per_s_torch_glue": None if ms_torch is None else nact / ms_torch * 1e3,
-               "kv_rows_attended_first_step": int((pos0[pos0 >= 0] + 1).sum()), "check": check}
+               "kv_rows_attended_first_step": int((pos0[pos0 >= 0] + 1).sum()), "check": check, "kv": args.kv,
+               "kv_cache_bytes": 2 * nlayers * qp.attention.kv_cache_bytes(B, nkv, args.context, head_dim, kc[0].dtype)}
         if sampled is not None:
             res["sampled"] = sampled
-        del kc, vc, ref_cache, kernel_step
+        del kc, vc, kc_ref, vc_ref, ref_cache, kernel_step
         torch.cuda.empty_cache()
         return res
 

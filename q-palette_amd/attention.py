@@ -12,6 +12,11 @@ pos0 + T - 1`` in one launch, appended to that sequence's cache, every row atten
 
     ws = prefill_workspace(128, nq, nkv, hd, max_len, device)      # once, shared by every layer and every shorter chunk
     out = prefill_attention(q, k, v, kcache[b], vcache[b], pos0, inv_freq, ws=ws)
+
+Both take the caches in one of two element formats and dispatch on their dtype: ``torch.float16``, or ``torch.float8_e4m3fn`` (OCP
+e4m3, one byte per element, no scales: ``qpal_attn_rope_decode_batch_kv8`` / ``qpal_attn_rope_prefill_kv8``).  A
+new row is stored as ``h.float().clamp(-448, 448).to(torch.float8_e4m3fn)`` of the fp16 row ``h`` the fp16 path writes and takes
+part in its own launch at that stored value; stored bytes are converted exactly to fp16.  The workspaces serve both formats.
 """
 import math
 
@@ -30,6 +35,30 @@ def attention_workspace(B, nq, nkv, hd, max_len, device):
     return torch.zeros((n + 3) // 4, dtype=torch.float32, device=device)
 
 
+_CACHE_ENTRY = {torch.float16: "", torch.float8_e4m3fn: "_kv8"}  # cache dtype -> suffix of the C entry point
+
+
+def kv_cache_bytes(B, nkv, max_len, hd, dtype=torch.float16):
+    """Bytes of ONE cache tensor [B, nkv, max_len, hd] (k or v of one layer) in the element format `dtype`."""
+    if dtype not in _CACHE_ENTRY:
+        raise QpalError(f"kv_cache_bytes: a KV cache is torch.float16 or torch.float8_e4m3fn, got {dtype}")
+    return int(B) * int(nkv) * int(max_len) * int(hd) * torch.empty(0, dtype=dtype).element_size()
+
+
+def _cache_entry(kcache, vcache, who):
+    """the caches' common element format as the suffix of the entry point; everything the library would not check for itself"""
+    if kcache.dtype != vcache.dtype:
+        raise QpalError(f"{who}: kcache and vcache must share one dtype, got {kcache.dtype} and {vcache.dtype}")
+    if kcache.dtype not in _CACHE_ENTRY:
+        raise QpalError(f"{who}: the caches' dtype must be torch.float16 or torch.float8_e4m3fn, got {kcache.dtype}")
+    for name, t in (("kcache", kcache), ("vcache", vcache)):
+        if not t.is_cuda or not t.is_contiguous():
+            raise QpalError(f"{who}: {name} must be a contiguous device tensor, got one on {t.device}")
+        if t.data_ptr() % 16:
+            raise QpalError(f"{who}: {name} must be 16-byte aligned")
+    return _CACHE_ENTRY[kcache.dtype]
+
+
 def _rows(t, name, B, width, who="decode_attention"):
     if t.dtype != torch.float32 or not t.is_cuda:
         raise QpalError(f"{who}: {name} must be an fp32 device tensor, got {t.dtype} on {t.device}")
@@ -42,17 +71,18 @@ def _rows(t, name, B, width, who="decode_attention"):
 
 def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=None, ws=None):
     """q fp32 [B, nq*hd], k / v fp32 [B, nkv*hd] (rows may be strided: column slices of one q|k|v output with a common row
-    stride); kcache / vcache fp16 [B, nkv, max_len, hd] contiguous, 16-byte aligned, updated in place at row pos[b]; pos int64
+    stride); kcache / vcache [B, nkv, max_len, hd] contiguous, 16-byte aligned, updated in place at row pos[b]; pos int64
     [B] on the device; inv_freq fp32 [hd/2].  Returns out fp16 [B, nq*hd] (``out`` if given: rows of an inactive sequence keep
-    what they held).  scale defaults to 1/sqrt(hd).  Launches on the current stream."""
+    what they held).  scale defaults to 1/sqrt(hd).  Launches on the current stream.
+
+    The caches' dtype selects the kernel: torch.float16 -> qpal_attn_rope_decode_batch; torch.float8_e4m3fn ->
+    qpal_attn_rope_decode_batch_kv8 (the new row is stored as h.float().clamp(-448, 448).to(torch.float8_e4m3fn) of the fp16 row h
+    and attended to at that value).  Caches of two different dtypes, or of any other dtype, raise QpalError before the library is
+    reached.  One attention_workspace serves both formats."""
     if kcache.dim() != 4 or kcache.shape != vcache.shape:
         raise QpalError("decode_attention: kcache / vcache must both have shape [B, nkv, max_len, hd]")
     B, nkv, max_len, hd = kcache.shape
-    for name, t in (("kcache", kcache), ("vcache", vcache)):
-        if t.dtype != torch.float16 or not t.is_cuda or not t.is_contiguous():
-            raise QpalError(f"decode_attention: {name} must be a contiguous fp16 device tensor")
-        if t.data_ptr() % 16:
-            raise QpalError(f"decode_attention: {name} must be 16-byte aligned")
+    entry = "qpal_attn_rope_decode_batch" + _cache_entry(kcache, vcache, "decode_attention")
     if q.dim() != 2 or q.shape[0] != B or q.shape[1] % hd:
         raise QpalError(f"decode_attention: q must have shape [{B}, nq*{hd}], got {list(q.shape)}")
     nq = q.shape[1] // hd
@@ -80,12 +110,12 @@ def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=Non
             raise QpalError(f"decode_attention: ws must be a contiguous device buffer of >= {need} bytes on {kcache.device}")
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
     with torch.cuda.device(kcache.device):
-        rc = lib.qpal_attn_rope_decode_batch(
+        rc = getattr(lib, entry)(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
             pos.data_ptr(), inv_freq.data_ptr(), B, nq, nkv, hd, max_len, scale,
             ws.data_ptr() if need > 0 else None, ws.numel() * ws.element_size() if need > 0 else 0,
             torch.cuda.current_stream(kcache.device).cuda_stream)
-    _native.check(rc, "qpal_attn_rope_decode_batch")
+    _native.check(rc, entry)
     return out
 
 
@@ -101,20 +131,21 @@ def prefill_workspace(T, nq, nkv, hd, max_len, device):
 
 def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=None, ws=None):
     """q fp32 [T, nq*hd], k / v fp32 [T, nkv*hd], 1 <= T <= 128: row t is the token at position pos0 + t (rows may be strided:
-    column slices of one q|k|v output with a common row stride); kcache / vcache fp16 [nkv, max_len, hd] of ONE sequence,
+    column slices of one q|k|v output with a common row stride); kcache / vcache [nkv, max_len, hd] of ONE sequence,
     contiguous, 16-byte aligned (``kcache[b]`` of the batched layout), updated in place at rows pos0 .. pos0 + T - 1; pos0 int64
     [1] on the device; inv_freq fp32 [hd/2].  Returns out fp16 [T, nq*hd] (``out`` if given): row t attends to positions 0 ..
     pos0 + t.  pos0 < 0 or pos0 + T > max_len: nothing is written, neither cache nor out.  scale defaults to 1/sqrt(hd).
-    Launches on the current stream."""
+    Launches on the current stream.
+
+    The caches' dtype selects the kernel: torch.float16 -> qpal_attn_rope_prefill; torch.float8_e4m3fn -> qpal_attn_rope_prefill_kv8
+    (new rows are stored as h.float().clamp(-448, 448).to(torch.float8_e4m3fn) of the fp16 rows h and attended to at that value: the
+    cache ends up byte for byte as decode_attention would have filled it token by token).  Caches of two different dtypes, or of any
+    other dtype, raise QpalError before the library is reached.  One prefill_workspace serves both formats."""
     who = "prefill_attention"
     if kcache.dim() != 3 or kcache.shape != vcache.shape:
         raise QpalError(f"{who}: kcache / vcache must both have shape [nkv, max_len, hd]")
     nkv, max_len, hd = kcache.shape
-    for name, t in (("kcache", kcache), ("vcache", vcache)):
-        if t.dtype != torch.float16 or not t.is_cuda or not t.is_contiguous():
-            raise QpalError(f"{who}: {name} must be a contiguous fp16 device tensor")
-        if t.data_ptr() % 16:
-            raise QpalError(f"{who}: {name} must be 16-byte aligned")
+    entry = "qpal_attn_rope_prefill" + _cache_entry(kcache, vcache, who)
     if q.dim() != 2 or not 1 <= q.shape[0] <= 128 or q.shape[1] % hd:
         raise QpalError(f"{who}: q must have shape [T, nq*{hd}] with 1 <= T <= 128, got {list(q.shape)}")
     T, nq = q.shape[0], q.shape[1] // hd
@@ -142,10 +173,10 @@ def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=N
             raise QpalError(f"{who}: ws must be a contiguous device buffer of >= {need} bytes on {kcache.device}")
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
     with torch.cuda.device(kcache.device):
-        rc = lib.qpal_attn_rope_prefill(
+        rc = getattr(lib, entry)(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
             pos0.data_ptr(), inv_freq.data_ptr(), T, nq, nkv, hd, max_len, scale,
             ws.data_ptr() if need > 0 else None, ws.numel() * ws.element_size() if need > 0 else 0,
             torch.cuda.current_stream(kcache.device).cuda_stream)
-    _native.check(rc, "qpal_attn_rope_prefill")
+    _native.check(rc, entry)
     return out

@@ -12,8 +12,16 @@
 // sequence is one workgroup per kv head and nothing is merged.  Chunks of one (sequence, kv head) leave a partial (max, sum,
 // unnormalised out) per head in the workspace and take a ticket; the last to arrive merges them in a fixed order (bitwise
 // reproducible: no float atomics) and resets the ticket.
+//
+// The cache element type CT is a template parameter: uint16_t = fp16 (qpal_attn_rope_decode_batch), uint8_t = OCP e4m3fn
+// (qpal_attn_rope_decode_batch_kv8, kv8.h).  The e4m3 instantiation differs at the load, convert and store sites
+// only: a byte row is converted exactly to the fp16 values the matrix pipe and the value loop take today, the new row is quantised
+// once and takes part at its stored value.  LDS layout, workspace and grid do not depend on CT.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
+#include "kv8.h"
 #include "qpal_common.h"
 
 namespace qpal {
@@ -27,10 +35,11 @@ constexpr int kBatchNW = 16;          // waves per workgroup
 constexpr int kBatchMaxSplit = 64;
 constexpr size_t kBatchLdsMax = 160 * 1024;
 
+template <class CT>
 struct AttnBatchParams {
     const float *q, *k, *v;  // fp32 rows [B][ld_qkv]: q [nq * HD], k / v [nkv * HD] inside a row
     long ld_qkv;
-    uint16_t *kcache, *vcache;  // fp16 [B][nkv][max_len][HD]
+    CT *kcache, *vcache;        // fp16 (uint16_t) or e4m3fn (uint8_t) [B][nkv][max_len][HD]
     uint16_t *out;              // fp16 [B][ld_out]
     long ld_out;
     const long *pos;            // int64 [B], device
@@ -50,8 +59,9 @@ __device__ __forceinline__ float ld_agent(const float *p) {
     return __builtin_bit_cast(float, __hip_atomic_load(as_global(reinterpret_cast<const unsigned *>(p)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
-template <int HD, int REP>
-__global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const AttnBatchParams p) {
+template <class CT, int HD, int REP>
+__global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const AttnBatchParams<CT> p) {
+    constexpr bool KV8 = kIsKv8<CT>;
     constexpr int NW = kBatchNW, NT = 64 * NW, HALF = HD / 2;
     constexpr int LPR = HD / 8, DPL = HD / 64;
     static_assert(REP * HD <= 1024, "partial-out buffer: NW x REP x HD floats of LDS");
@@ -85,7 +95,7 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
     const long cend = pos < c0 + cld ? pos : c0 + cld;       // cached positions of the chunk: [c0, cend)
     const int nc = cend > c0 ? (int)(cend - c0) : 0;
     const long kvoff = ((long)b * p.nkv + kh) * p.max_len * HD;
-    const gptr<const uint16_t> K = as_global(p.kcache) + kvoff, V = as_global(p.vcache) + kvoff;
+    const gptr<const CT> K = as_global(p.kcache) + kvoff, V = as_global(p.vcache) + kvoff;
     const float *qrow = p.q + (long)b * p.ld_qkv, *krow = p.k + (long)b * p.ld_qkv, *vrow = p.v + (long)b * p.ld_qkv;
     uint16_t *orow = p.out + (long)b * p.ld_out + (long)kh * REP * HD;
     const long slot = ((long)b * p.nkv + kh) * p.nsplit;
@@ -103,28 +113,49 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
         const _Float16 x1 = (_Float16)src[i], x2 = (_Float16)src[i + HALF];
         const _Float16 o1 = x1 * c + (-x2) * s, o2 = x2 * c + x1 * s;
         uint16_t *dst16 = reinterpret_cast<uint16_t *>(is_k ? knh : qh + hh * HALF);
+        if constexpr (KV8) {
+            if (is_k) {  // quantised once: the bytes go to the cache, their fp16 image to this launch's scores
+                const uint32_t b8 = e4m3_pack2(o1, o2), h2 = e4m3_half2<false>(b8);
+                dst16[i] = (uint16_t)h2;
+                dst16[i + HALF] = (uint16_t)(h2 >> 16);
+                CT *dst = p.kcache + kvoff + pos * HD;
+                dst[i] = (CT)b8;
+                dst[i + HALF] = (CT)(b8 >> 8);
+                continue;
+            }
+        }
         dst16[i] = __builtin_bit_cast(uint16_t, o1);
         dst16[i + HALF] = __builtin_bit_cast(uint16_t, o2);
-        if (is_k) {
-            uint16_t *dst = p.kcache + kvoff + pos * HD;
-            dst[i] = __builtin_bit_cast(uint16_t, o1);
-            dst[i + HALF] = __builtin_bit_cast(uint16_t, o2);
+        if constexpr (!KV8) {
+            if (is_k) {
+                uint16_t *dst = p.kcache + kvoff + pos * HD;
+                dst[i] = __builtin_bit_cast(uint16_t, o1);
+                dst[i + HALF] = __builtin_bit_cast(uint16_t, o2);
+            }
         }
     }
     if (owner) {
         for (int d = tid; d < HD; d += NT) {
             const _Float16 hv = (_Float16)vrow[(long)kh * HD + d];
-            vn[d] = (float)hv;
-            p.vcache[kvoff + pos * HD + d] = __builtin_bit_cast(uint16_t, hv);
+            if constexpr (KV8) {
+                const uint32_t b8 = e4m3_pack2(hv, hv);
+                vn[d] = e4m3_float2<false>(b8).x;
+                p.vcache[kvoff + pos * HD + d] = (CT)b8;
+            } else {
+                vn[d] = (float)hv;
+                p.vcache[kvoff + pos * HD + d] = __builtin_bit_cast(uint16_t, hv);
+            }
         }
     }
     __syncthreads();
 
     // ---- scores on the matrix pipe: D[head][position] = Q[head][:] . K[position][:], v_mfma_f32_16x16x32_f16 with the group's
     // query heads as the (zero-padded) 16 rows of A and 16 cache rows as B (a B fragment: lane (column mi = position, mq = lane
-    // >> 4) loads 8 consecutive dims 32 kc + 8 mq .. of its row, 16 bytes)
+    // >> 4) loads 8 consecutive dims 32 kc + 8 mq .. of its row, 16 bytes; e4m3: 8 bytes, converted in registers, and twice the
+    // tiles in flight — the same bytes and registers in flight per wave)
     const int grp = lane / LPR, sl = lane % LPR;
-    constexpr int U = 2;    // 16-row tiles in flight per wave
+    constexpr int U = KV8 ? 4 : 2;  // 16-row tiles in flight per wave
+    using KB = std::conditional_t<KV8, u32x2, u32x4>;  // a lane's 8 dims of one row
     constexpr int KC = HD / 32;
     typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
     typedef float float4_t __attribute__((ext_vector_type(4)));
@@ -139,21 +170,23 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
             afr[kc] = __builtin_bit_cast(half8_t, a);
         }
         for (int t0 = wave * 16; t0 < nc; t0 += NW * 16 * U) {
-            u32x4 kb[U][KC];
+            KB kb[U][KC];
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const int t = t0 + u * NW * 16 + mi;
-                const gptr<const uint16_t> row = K + (c0 + (t < nc ? t : 0)) * HD + 8 * mq;
+                const gptr<const CT> row = K + (c0 + (t < nc ? t : 0)) * HD + 8 * mq;
 #pragma unroll
-                for (int kc = 0; kc < KC; kc++) kb[u][kc] = *(gptr<const u32x4>)(row + 32 * kc);
+                for (int kc = 0; kc < KC; kc++) kb[u][kc] = *(gptr<const KB>)(row + 32 * kc);
             }
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const int t = t0 + u * NW * 16 + mi;
                 float4_t d{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int kc = 0; kc < KC; kc++)
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[kc], __builtin_bit_cast(half8_t, kb[u][kc]), d, 0, 0, 0);
+                for (int kc = 0; kc < KC; kc++) {
+                    if constexpr (KV8) d = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[kc], __builtin_bit_cast(half8_t, e4m3_half8(kb[u][kc])), d, 0, 0, 0);
+                    else d = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[kc], __builtin_bit_cast(half8_t, kb[u][kc]), d, 0, 0, 0);
+                }
                 if (4 * mq < REP && t < nc) {
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
@@ -226,25 +259,43 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
     for (int h = 0; h < REP; h++)
 #pragma unroll
         for (int e = 0; e < DPL; e++) acc[h][e] = 0.f;
-    constexpr int UV = REP * DPL > 16 ? 2 : 4;  // rows in flight per wave
+    // rows in flight per wave (e4m3: a lane's DPL bytes, so twice the rows while their REP weights each stay within 32 registers)
+    constexpr int UV16 = REP * DPL > 16 ? 2 : 4, UV = !KV8 ? UV16 : (2 * UV16 * REP > 32 ? 32 / REP : 2 * UV16);
     for (int t0 = wave; t0 < nc; t0 += NW * UV) {
-        uint16_t raw[UV][DPL];
+        std::conditional_t<KV8, uint32_t, uint16_t> raw[UV][KV8 ? 1 : DPL];  // (e4m3: the DPL bytes in one register)
 #pragma unroll
         for (int u = 0; u < UV; u++) {
             const int t = t0 + u * NW;
-            const gptr<const uint16_t> row = V + (c0 + (t < nc ? t : 0)) * HD + DPL * lane;
-            if constexpr (DPL == 1) raw[u][0] = row[0];
+            const gptr<const CT> row = V + (c0 + (t < nc ? t : 0)) * HD + DPL * lane;
+            if constexpr (KV8) {
+                if constexpr (DPL == 1) raw[u][0] = row[0];
+                else if constexpr (DPL == 2) raw[u][0] = *(gptr<const uint16_t>)row;
+                else raw[u][0] = *(gptr<const uint32_t>)row;
+            } else if constexpr (DPL == 1) raw[u][0] = row[0];
             else if constexpr (DPL == 2) { const uint32_t r = *(gptr<const uint32_t>)row; raw[u][0] = (uint16_t)r; raw[u][1] = (uint16_t)(r >> 16); }
             else { const u32x2 r = *(gptr<const u32x2>)row; raw[u][0] = (uint16_t)r.x; raw[u][1] = (uint16_t)(r.x >> 16); raw[u][2] = (uint16_t)r.y; raw[u][3] = (uint16_t)(r.y >> 16); }
         }
 #pragma unroll
         for (int u = 0; u < UV; u++) {
             const int t = t0 + u * NW;
+            [[maybe_unused]] float vf[DPL];
+            if constexpr (KV8) {
+                const kv8_float2_t lo = e4m3_float2<false>(raw[u][0]);
+                vf[0] = lo.x;
+                if constexpr (DPL >= 2) vf[1] = lo.y;
+                if constexpr (DPL == 4) {
+                    const kv8_float2_t hi = e4m3_float2<true>(raw[u][0]);
+                    vf[2] = hi.x, vf[3] = hi.y;
+                }
+            }
 #pragma unroll
             for (int h = 0; h < REP; h++) {
                 const float w = t < nc ? sc[h * CL + t] : 0.f;
 #pragma unroll
-                for (int e = 0; e < DPL; e++) acc[h][e] += w * (float)__builtin_bit_cast(_Float16, raw[u][e]);
+                for (int e = 0; e < DPL; e++) {
+                    if constexpr (KV8) acc[h][e] += w * vf[e];
+                    else acc[h][e] += w * (float)__builtin_bit_cast(_Float16, raw[u][e]);
+                }
             }
         }
     }
@@ -364,8 +415,9 @@ int batch_geometry(int B, int nq, int nkv, int hd, long max_len, BatchGeometry &
     return QPAL_OK;
 }
 
-template <class Kern>
-int launch_batch(Kern kern, const AttnBatchParams &p, int grid, size_t lds, void *stream) {
+template <class CT, int HD, int REP>
+int launch_batch(const AttnBatchParams<CT> &p, int grid, size_t lds, void *stream) {
+    const auto kern = attn_rope_batch_kernel<CT, HD, REP>;
     static bool attr_set[64] = {};  // one latch per instantiation and device
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
@@ -376,6 +428,41 @@ int launch_batch(Kern kern, const AttnBatchParams &p, int grid, size_t lds, void
     }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kBatchNW), lds, static_cast<hipStream_t>(stream), p);
     return (int)hipGetLastError();
+}
+
+// the two entry points: the same checks, geometry and launch, the cache element type apart
+template <class CT>
+int attn_rope_decode_batch(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16,
+                           long ld_out, const long *pos, const float *inv_freq, int B, int nq, int nkv, int hd, long max_len,
+                           float scale, void *ws, long ws_bytes, void *stream) {
+    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
+    BatchGeometry g;
+    const int rc = batch_geometry(B, nq, nkv, hd, max_len, g);
+    if (rc != QPAL_OK) return rc;
+    if (ld_qkv < (long)nq * hd || ld_out < (long)nq * hd) return QPAL_E_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(kcache) | reinterpret_cast<uintptr_t>(vcache)) & 15) return QPAL_E_ALIGN;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
+         reinterpret_cast<uintptr_t>(inv_freq) | reinterpret_cast<uintptr_t>(pos)) & 3)
+        return QPAL_E_ALIGN;
+    if (reinterpret_cast<uintptr_t>(out_f16) & 1) return QPAL_E_ALIGN;
+    if (g.ws_bytes) {
+        if (!ws) return QPAL_E_NULL;
+        if (ws_bytes < (long)g.ws_bytes) return QPAL_E_SHAPE;
+        if (reinterpret_cast<uintptr_t>(ws) & 3) return QPAL_E_ALIGN;
+    }
+    float *wsf = static_cast<float *>(ws);
+    AttnBatchParams<CT> p{q, k, v, ld_qkv, static_cast<CT *>(kcache), static_cast<CT *>(vcache),
+                          static_cast<uint16_t *>(out_f16), ld_out, pos, inv_freq, nkv, max_len, scale,
+                          g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr, g.ws_bytes ? wsf + (long)kBatchMax * nkv : nullptr,
+                          g.nsplit, g.chunk};
+    const int grid = B * nkv * g.nsplit, rep = nq / nkv;
+#define QPAL_BATCH(HD_, REP_) \
+    if (hd == HD_ && rep == REP_) return launch_batch<CT, HD_, REP_>(p, grid, g.lds, stream);
+    QPAL_BATCH(64, 1) QPAL_BATCH(64, 2) QPAL_BATCH(64, 4) QPAL_BATCH(64, 8)
+    QPAL_BATCH(128, 1) QPAL_BATCH(128, 2) QPAL_BATCH(128, 4) QPAL_BATCH(128, 8)
+    QPAL_BATCH(256, 1) QPAL_BATCH(256, 2) QPAL_BATCH(256, 4)
+#undef QPAL_BATCH
+    return QPAL_E_SHAPE;
 }
 
 }  // namespace
@@ -393,32 +480,14 @@ extern "C" long qpal_attn_batch_ws_bytes(int B, int nq, int nkv, int hd, long ma
 extern "C" int qpal_attn_rope_decode_batch(const float *q, const float *k, const float *v, long ld_qkv, void *kcache_f16, void *vcache_f16,
                                            void *out_f16, long ld_out, const long *pos, const float *inv_freq, int B, int nq, int nkv,
                                            int hd, long max_len, float scale, void *ws, long ws_bytes, void *stream) {
-    if (!q || !k || !v || !kcache_f16 || !vcache_f16 || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
-    BatchGeometry g;
-    const int rc = batch_geometry(B, nq, nkv, hd, max_len, g);
-    if (rc != QPAL_OK) return rc;
-    if (ld_qkv < (long)nq * hd || ld_out < (long)nq * hd) return QPAL_E_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(kcache_f16) | reinterpret_cast<uintptr_t>(vcache_f16)) & 15) return QPAL_E_ALIGN;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
-         reinterpret_cast<uintptr_t>(inv_freq) | reinterpret_cast<uintptr_t>(pos)) & 3)
-        return QPAL_E_ALIGN;
-    if (reinterpret_cast<uintptr_t>(out_f16) & 1) return QPAL_E_ALIGN;
-    if (g.ws_bytes) {
-        if (!ws) return QPAL_E_NULL;
-        if (ws_bytes < (long)g.ws_bytes) return QPAL_E_SHAPE;
-        if (reinterpret_cast<uintptr_t>(ws) & 3) return QPAL_E_ALIGN;
-    }
-    float *wsf = static_cast<float *>(ws);
-    AttnBatchParams p{q, k, v, ld_qkv, static_cast<uint16_t *>(kcache_f16), static_cast<uint16_t *>(vcache_f16),
-                      static_cast<uint16_t *>(out_f16), ld_out, pos, inv_freq, nkv, max_len, scale,
-                      g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr, g.ws_bytes ? wsf + (long)kBatchMax * nkv : nullptr,
-                      g.nsplit, g.chunk};
-    const int grid = B * nkv * g.nsplit, rep = nq / nkv;
-#define QPAL_BATCH(HD_, REP_) \
-    if (hd == HD_ && rep == REP_) return launch_batch(attn_rope_batch_kernel<HD_, REP_>, p, grid, g.lds, stream);
-    QPAL_BATCH(64, 1) QPAL_BATCH(64, 2) QPAL_BATCH(64, 4) QPAL_BATCH(64, 8)
-    QPAL_BATCH(128, 1) QPAL_BATCH(128, 2) QPAL_BATCH(128, 4) QPAL_BATCH(128, 8)
-    QPAL_BATCH(256, 1) QPAL_BATCH(256, 2) QPAL_BATCH(256, 4)
-#undef QPAL_BATCH
-    return QPAL_E_SHAPE;
+    return attn_rope_decode_batch<uint16_t>(q, k, v, ld_qkv, kcache_f16, vcache_f16, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd,
+                                            max_len, scale, ws, ws_bytes, stream);
+}
+
+extern "C" int qpal_attn_rope_decode_batch_kv8(const float *q, const float *k, const float *v, long ld_qkv, void *kcache_e4m3,
+                                               void *vcache_e4m3, void *out_f16, long ld_out, const long *pos, const float *inv_freq,
+                                               int B, int nq, int nkv, int hd, long max_len, float scale, void *ws, long ws_bytes,
+                                               void *stream) {
+    return attn_rope_decode_batch<uint8_t>(q, k, v, ld_qkv, kcache_e4m3, vcache_e4m3, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd,
+                                           max_len, scale, ws, ws_bytes, stream);
 }

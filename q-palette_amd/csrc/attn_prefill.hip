@@ -16,8 +16,17 @@
 //                                row-major V image
 // Chunks of one (kv head, query tile) leave (max, sum, unnormalised out) per row in the workspace and take a ticket; the last to
 // arrive merges them in chunk order (bitwise reproducible, no float atomics) and resets the ticket: attn_batch.hip's pattern.
+//
+// The cache element type CT is a template parameter: uint16_t = fp16 (qpal_attn_rope_prefill), uint8_t = OCP e4m3fn
+// (qpal_attn_rope_prefill_kv8, kv8.h).  The e4m3 instantiation keeps the fp16 LDS image and everything that reads
+// it; the register prefetch holds bytes (cached rows as loaded, new rows quantised by the thread that rotates them, which also
+// stores them where its tile owns them) and the bytes are converted exactly on their way into LDS — a new row takes part at its
+// stored value.  Workspace and grid do not depend on CT.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
+#include "kv8.h"
 #include "qpal_common.h"
 
 namespace qpal {
@@ -31,10 +40,11 @@ constexpr long kPfMinChunk = 128;   // a chunk holds at least this many keys
 constexpr int kPfMaxSplit = 16;
 constexpr int kPfMaxTiles = 8;      // query tiles of a launch: 128 rows / 16
 
+template <class CT>
 struct AttnPrefillParams {
     const float *q, *k, *v;  // fp32 rows [T][ld_qkv]: q [nq * HD], k / v [nkv * HD] inside a row
     long ld_qkv;
-    uint16_t *kcache, *vcache;  // fp16 [nkv][max_len][HD]
+    CT *kcache, *vcache;        // fp16 (uint16_t) or e4m3fn (uint8_t) [nkv][max_len][HD]
     uint16_t *out;              // fp16 [T][ld_out]
     long ld_out;
     const long *pos0;           // int64, device
@@ -89,8 +99,10 @@ __device__ __forceinline__ u32x4 rope_chunk(const float *src, int ch, long pos, 
     return val;
 }
 
-template <int HD, int REP>
-__global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(const AttnPrefillParams p) {
+template <class CT, int HD, int REP>
+__global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(const AttnPrefillParams<CT> p) {
+    constexpr bool KV8 = kIsKv8<CT>;
+    using KR = std::conditional_t<KV8, u32x2, u32x4>;  // eight elements of a cache row as prefetched
     constexpr int QS = pf_qs(REP), NW = REP * QS, NT = 64 * NW, TQ = 16 * QS, R = 16 * NW;
     constexpr int HALF = HD / 2, KC = HD / 32, DT = HD / 16, CPR = HD / 8;
     constexpr int RS = 2 * HD + 16;                     // bytes of an LDS row (padded by one 16-byte access)
@@ -125,7 +137,7 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(con
     const int trow = t0 + qsub * 16 + mi;  // this lane's query row (a column of S^T)
     const long qpos = pos0 + trow;
     const long kvoff = (long)kh * p.max_len * HD;
-    const gptr<const uint16_t> Kc = as_global(p.kcache) + kvoff, Vc = as_global(p.vcache) + kvoff;
+    const gptr<const CT> Kc = as_global(p.kcache) + kvoff, Vc = as_global(p.vcache) + kvoff;
 
     // ---- the wave's 16 query rows after the rotary embedding, through LDS into B fragments (rows >= T: zeros)
     for (int idx = lane; idx < 16 * HALF; idx += 64) {
@@ -152,16 +164,31 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(con
 
     // ---- one 16-byte chunk of the K | V tile at keys kt0 ..: cached rows from the cache, new rows from the inputs (and into the
     // cache where this tile owns them), rows past the chunk as zeros
-    auto fetch = [&](long kt0, u32x4(&regs)[NCH]) {
+    auto fetch = [&](long kt0, KR(&regs)[NCH]) {
 #pragma unroll
         for (int u = 0; u < NCH; u++) {
             const int idx = tid + u * NT;
             const int isv = idx / (kPfKT * CPR), rr = (idx / CPR) % kPfKT, ch = idx % CPR;
             const long n = kt0 + rr;
-            u32x4 val{0u, 0u, 0u, 0u};
+            KR val{};
             if (n < c1) {
                 if (n < pos0) {
-                    val = *(gptr<const u32x4>)((isv ? Vc : Kc) + n * HD + 8 * ch);
+                    val = *(gptr<const KR>)((isv ? Vc : Kc) + n * HD + 8 * ch);
+                } else if constexpr (KV8) {
+                    const int tn = (int)(n - pos0);  // < tend <= T
+                    u32x4 h16;
+                    if (isv) {
+                        const float *src = p.v + (long)tn * p.ld_qkv + (long)kh * HD + 8 * ch;
+                        uint16_t h[8];
+#pragma unroll
+                        for (int e = 0; e < 8; e++) h[e] = __builtin_bit_cast(uint16_t, (_Float16)src[e]);
+                        h16 = u32x4{(uint32_t)h[0] | (uint32_t)h[1] << 16, (uint32_t)h[2] | (uint32_t)h[3] << 16,
+                                    (uint32_t)h[4] | (uint32_t)h[5] << 16, (uint32_t)h[6] | (uint32_t)h[7] << 16};
+                    } else {
+                        h16 = rope_chunk<HD>(p.k + (long)tn * p.ld_qkv + (long)kh * HD, ch, n, p.inv_freq);
+                    }
+                    val = e4m3_pack8(h16);  // quantised once: these bytes reach the cache and, converted back, the LDS image
+                    if (tn >= t0) *reinterpret_cast<u32x2 *>((isv ? p.vcache : p.kcache) + kvoff + n * HD + 8 * ch) = val;
                 } else {
                     const int tn = (int)(n - pos0);  // < tend <= T
                     if (isv) {
@@ -180,12 +207,13 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(con
             regs[u] = val;
         }
     };
-    auto commit = [&](const u32x4(&regs)[NCH]) {
+    auto commit = [&](const KR(&regs)[NCH]) {
 #pragma unroll
         for (int u = 0; u < NCH; u++) {
             const int idx = tid + u * NT;
             const int row = idx / CPR, ch = idx % CPR;  // rows 0..31: K, 32..63: V
-            *reinterpret_cast<u32x4 *>(sm + row * RS + 16 * ch) = regs[u];
+            if constexpr (KV8) *reinterpret_cast<u32x4 *>(sm + row * RS + 16 * ch) = e4m3_half8(regs[u]);
+            else *reinterpret_cast<u32x4 *>(sm + row * RS + 16 * ch) = regs[u];
         }
     };
 
@@ -193,7 +221,7 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(con
     float4_t oacc[DT];
 #pragma unroll
     for (int dt = 0; dt < DT; dt++) oacc[dt] = float4_t{0.f, 0.f, 0.f, 0.f};
-    u32x4 regs[NCH];
+    KR regs[NCH];
     // per step: fetch tile k into registers (loads in flight), products of tile k - 1 from LDS, then tile k into LDS
     for (long kt0 = c0;; kt0 += kPfKT) {
         const bool more = kt0 < c1;
@@ -352,6 +380,45 @@ int prefill_geometry(int T, int nq, int nkv, int hd, long max_len, PrefillGeomet
     return QPAL_OK;
 }
 
+// the two entry points: the same checks, geometry and launch, the cache element type apart
+template <class CT>
+int attn_rope_prefill(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16,
+                      long ld_out, const long *pos0, const float *inv_freq, int T, int nq, int nkv, int hd, long max_len, float scale,
+                      void *ws, long ws_bytes, void *stream) {
+    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos0 || !inv_freq) return QPAL_E_NULL;
+    PrefillGeometry g;
+    const int rc = prefill_geometry(T, nq, nkv, hd, max_len, g);
+    if (rc != QPAL_OK) return rc;
+    if (ld_qkv < (long)nq * hd || ld_out < (long)nq * hd) return QPAL_E_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(kcache) | reinterpret_cast<uintptr_t>(vcache)) & 15) return QPAL_E_ALIGN;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
+         reinterpret_cast<uintptr_t>(inv_freq) | reinterpret_cast<uintptr_t>(pos0)) & 3)
+        return QPAL_E_ALIGN;
+    if (reinterpret_cast<uintptr_t>(out_f16) & 1) return QPAL_E_ALIGN;
+    if (g.ws_bytes) {
+        if (!ws) return QPAL_E_NULL;
+        if (ws_bytes < (long)g.ws_bytes) return QPAL_E_SHAPE;
+        if (reinterpret_cast<uintptr_t>(ws) & 3) return QPAL_E_ALIGN;
+    }
+    float *wsf = static_cast<float *>(ws);
+    AttnPrefillParams<CT> p{q, k, v, ld_qkv, static_cast<CT *>(kcache), static_cast<CT *>(vcache),
+                            static_cast<uint16_t *>(out_f16), ld_out, pos0, inv_freq, T, nkv, max_len, scale,
+                            g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr, g.ws_bytes ? wsf + (long)nkv * kPfMaxTiles : nullptr,
+                            g.nsplit, g.ntile};
+    const int grid = nkv * g.ntile * g.nsplit, rep = nq / nkv;
+#define QPAL_PREFILL(HD_, REP_)                                                                                                    \
+    if (hd == HD_ && rep == REP_) {                                                                                                \
+        hipLaunchKernelGGL((attn_prefill_kernel<CT, HD_, REP_>), dim3(grid), dim3(64 * REP_ * pf_qs(REP_)), 0,                     \
+                           static_cast<hipStream_t>(stream), p);                                                                   \
+        return (int)hipGetLastError();                                                                                             \
+    }
+    QPAL_PREFILL(64, 1) QPAL_PREFILL(64, 2) QPAL_PREFILL(64, 4) QPAL_PREFILL(64, 8)
+    QPAL_PREFILL(128, 1) QPAL_PREFILL(128, 2) QPAL_PREFILL(128, 4) QPAL_PREFILL(128, 8)
+    QPAL_PREFILL(256, 1) QPAL_PREFILL(256, 2) QPAL_PREFILL(256, 4)
+#undef QPAL_PREFILL
+    return QPAL_E_SHAPE;
+}
+
 }  // namespace
 
 }  // namespace qpal
@@ -367,36 +434,13 @@ extern "C" long qpal_attn_prefill_ws_bytes(int T, int nq, int nkv, int hd, long 
 extern "C" int qpal_attn_rope_prefill(const float *q, const float *k, const float *v, long ld_qkv, void *kcache_f16, void *vcache_f16,
                                       void *out_f16, long ld_out, const long *pos0, const float *inv_freq, int T, int nq, int nkv,
                                       int hd, long max_len, float scale, void *ws, long ws_bytes, void *stream) {
-    if (!q || !k || !v || !kcache_f16 || !vcache_f16 || !out_f16 || !pos0 || !inv_freq) return QPAL_E_NULL;
-    PrefillGeometry g;
-    const int rc = prefill_geometry(T, nq, nkv, hd, max_len, g);
-    if (rc != QPAL_OK) return rc;
-    if (ld_qkv < (long)nq * hd || ld_out < (long)nq * hd) return QPAL_E_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(kcache_f16) | reinterpret_cast<uintptr_t>(vcache_f16)) & 15) return QPAL_E_ALIGN;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
-         reinterpret_cast<uintptr_t>(inv_freq) | reinterpret_cast<uintptr_t>(pos0)) & 3)
-        return QPAL_E_ALIGN;
-    if (reinterpret_cast<uintptr_t>(out_f16) & 1) return QPAL_E_ALIGN;
-    if (g.ws_bytes) {
-        if (!ws) return QPAL_E_NULL;
-        if (ws_bytes < (long)g.ws_bytes) return QPAL_E_SHAPE;
-        if (reinterpret_cast<uintptr_t>(ws) & 3) return QPAL_E_ALIGN;
-    }
-    float *wsf = static_cast<float *>(ws);
-    AttnPrefillParams p{q, k, v, ld_qkv, static_cast<uint16_t *>(kcache_f16), static_cast<uint16_t *>(vcache_f16),
-                        static_cast<uint16_t *>(out_f16), ld_out, pos0, inv_freq, T, nkv, max_len, scale,
-                        g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr, g.ws_bytes ? wsf + (long)nkv * kPfMaxTiles : nullptr,
-                        g.nsplit, g.ntile};
-    const int grid = nkv * g.ntile * g.nsplit, rep = nq / nkv;
-#define QPAL_PREFILL(HD_, REP_)                                                                                                    \
-    if (hd == HD_ && rep == REP_) {                                                                                                \
-        hipLaunchKernelGGL((attn_prefill_kernel<HD_, REP_>), dim3(grid), dim3(64 * REP_ * pf_qs(REP_)), 0,                         \
-                           static_cast<hipStream_t>(stream), p);                                                                   \
-        return (int)hipGetLastError();                                                                                             \
-    }
-    QPAL_PREFILL(64, 1) QPAL_PREFILL(64, 2) QPAL_PREFILL(64, 4) QPAL_PREFILL(64, 8)
-    QPAL_PREFILL(128, 1) QPAL_PREFILL(128, 2) QPAL_PREFILL(128, 4) QPAL_PREFILL(128, 8)
-    QPAL_PREFILL(256, 1) QPAL_PREFILL(256, 2) QPAL_PREFILL(256, 4)
-#undef QPAL_PREFILL
-    return QPAL_E_SHAPE;
+    return attn_rope_prefill<uint16_t>(q, k, v, ld_qkv, kcache_f16, vcache_f16, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, max_len,
+                                       scale, ws, ws_bytes, stream);
+}
+
+extern "C" int qpal_attn_rope_prefill_kv8(const float *q, const float *k, const float *v, long ld_qkv, void *kcache_e4m3,
+                                          void *vcache_e4m3, void *out_f16, long ld_out, const long *pos0, const float *inv_freq, int T,
+                                          int nq, int nkv, int hd, long max_len, float scale, void *ws, long ws_bytes, void *stream) {
+    return attn_rope_prefill<uint8_t>(q, k, v, ld_qkv, kcache_e4m3, vcache_e4m3, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, max_len,
+                                      scale, ws, ws_bytes, stream);
 }

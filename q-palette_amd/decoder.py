@@ -77,7 +77,7 @@ def k28_in_gemv(mlp):
 
 class DecodeStep:
     """layers: modules with self_attn (IncoherentSdpaAttention), mlp (IncoherentMLP), input_layernorm, post_attention_layernorm;
-    embed / lm_head fp16 [vocab, H]; norm: the final RMSNorm; kcache / vcache: per-layer fp16 [B, nkv, context, hd]; inv_freq fp32
+    embed / lm_head fp16 [vocab, H]; norm: the final RMSNorm; kcache / vcache: per-layer fp16 or float8_e4m3fn [B, nkv, context, hd]; inv_freq fp32
     [hd / 2]; tok, pos, out_tok int64 [B] (pos[b] outside the cache: sequence b is inactive).  The caller owns the caches and
     tok / pos / out_tok and may write them between replays of a captured step.  swiglu_epilogue, k28_fusion, native_lm_head,
     split_attention switch single fusions of the batch-1 step off (profiling).  sampler: a sampling.Sampler of B slots — the tail
@@ -106,6 +106,9 @@ class DecodeStep:
                 inter = m.intermediate_size
                 self.ug_il.append((il, linear.interleave_rows(m.Wscale_ug[:inter], m.Wscale_ug[inter:]),
                                    k28_fusion and k28_in_gemv(m)))
+        # the fused single-sequence attention kernel reads fp16 caches only: on float8_e4m3fn caches the batch-1 step keeps its GEMV
+        # fusions and launches decode_attention at B = 1 (same launch count)
+        self.attn_batch = not self.batch1 or kcache[0].dtype != torch.float16
         if self.batch1:
             # long caches: split-context attention (one workspace serves every layer: launches are stream-ordered)
             self.attn_ws_bytes = nat.lib().qpal_attn_ws_bytes(self.nq, self.nkv, self.head_dim, self.context) if split_attention else 0
@@ -113,7 +116,7 @@ class DecodeStep:
             if native_lm_head:
                 self.lm_ws_bytes = nat.lib().qpal_lm_head_ws_bytes(lm_head.shape[0])
                 self.lm_ws = torch.zeros(self.lm_ws_bytes // 4, dtype=torch.float32, device=dev)
-        else:
+        if self.attn_batch:
             self.attn_ws = attention_workspace(B, self.nq, self.nkv, self.head_dim, self.context, dev)
 
     @staticmethod
@@ -180,7 +183,7 @@ class DecodeStep:
 
     def _attention(self, i, q, k, v):
         scale = 1.0 / math.sqrt(self.head_dim)
-        if not self.batch1:
+        if self.attn_batch:
             decode_attention(q, k, v, self.kcache[i], self.vcache[i], self.pos, self.inv_freq, scale=scale, out=self.a16, ws=self.attn_ws)
             return
         dev = self.h32.device
@@ -245,7 +248,7 @@ class DecodeStep:
 
 
 class Prefill(DecodeStep):
-    """A prompt into ONE slot of the caches a DecodeStep is built on (per-layer fp16 [B, nkv, context, hd]): chunks of at most
+    """A prompt into ONE slot of the caches a DecodeStep is built on (per-layer fp16 or float8_e4m3fn [B, nkv, context, hd]): chunks of at most
     `chunk` <= 128 rows, each through DecodeStep's batch-B layer with rows = consecutive positions and `prefill_attention` on
     kcache[i][slot] / vcache[i][slot] (rotary embedding at pos0 + row, rows appended, causal); final norm, lm_head and argmax for
     the LAST row only.  Other slots are not touched.  The position lives on the device and the chunk loop advances it there: no
