@@ -376,6 +376,31 @@ int qpal_attn_rope_prefill_kv8(const float *q, const float *k, const float *v, l
                                const long *pos0, const float *inv_freq, int T, int nq, int nkv, int hd,
                                long max_len, float scale, void *ws, long ws_bytes, void *stream);
 
+/* The same two launches on a PAGED KV cache.  kpool / vpool: [num_pages][nkv][page_size][hd] of one layer, contiguous,
+ * 16-byte aligned, elements fp16 (kv_fmt 0) or e4m3fn (kv_fmt 1: the store rule of the _kv8 entry points); page_size in {16, 32,
+ * 64, 128, 256}.  block_table: int32 [B][ld_table] on the device, ld_table >= max_pages, 4-byte aligned: entry j of row b is the
+ * page that holds positions j * page_size .. (j + 1) * page_size - 1 of sequence b (block_row: the [max_pages] row of the ONE
+ * sequence a prefill launch serves).  The table is never read by the host (graph-capturable with entries that change between
+ * replays).  max_len = max_pages * page_size takes the place of the contiguous max_len in every rule: the shape rules, the inactive
+ * rule (pos[b] outside [0, max_len)), the *pos0 fit rule, the launch geometry and the workspace (qpal_attn_batch_ws_bytes /
+ * qpal_attn_prefill_ws_bytes of that max_len; one workspace may serve paged and contiguous launches).
+ * Contract: bit for bit the contiguous launch of the same max_len on the gathered cache - out rows and the bytes appended to the
+ * pools, in both formats; only where a row lives differs.  Only entries that cover positions 0 .. pos[b] (prefill: 0 .. *pos0 + T
+ * - 1) are read; every other entry may hold anything.  A used entry outside [0, num_pages): loads through it read page 0 instead,
+ * stores through it are dropped, that sequence's out is unspecified; no byte outside the pools, out and ws is touched.
+ * Checks and codes are the contiguous siblings'; in addition page_size outside the set, num_pages < 1, max_pages < 1, ld_table <
+ * max_pages, kv_fmt not 0 / 1: QPAL_E_SHAPE; a null table: QPAL_E_NULL; a table that is not 4-byte aligned: QPAL_E_ALIGN. */
+int qpal_attn_rope_decode_batch_paged(const float *q, const float *k, const float *v, long ld_qkv,
+                                      void *kpool, void *vpool, void *out_f16, long ld_out,
+                                      const long *pos, const float *inv_freq, const int *block_table, long ld_table,
+                                      int num_pages, int page_size, int max_pages, int kv_fmt /* 0 fp16, 1 e4m3fn */,
+                                      int B, int nq, int nkv, int hd, float scale, void *ws, long ws_bytes, void *stream);
+int qpal_attn_rope_prefill_paged(const float *q, const float *k, const float *v, long ld_qkv,
+                                 void *kpool, void *vpool, void *out_f16, long ld_out,
+                                 const long *pos0, const float *inv_freq, const int *block_row /* [max_pages] of ONE sequence */,
+                                 int num_pages, int page_size, int max_pages, int kv_fmt,
+                                 int T, int nq, int nkv, int hd, float scale, void *ws, long ws_bytes, void *stream);
+
 /* Final norm + fp16 lm_head for `rows` rows of the residual stream at once, on the matrix pipe (csrc/lm_head_batch.hip): the
  * logits a sampler needs, and the batch-B tail of a decode step.  h_f32 fp32 [rows][ld_h] (ld_h >= k, in elements), 1 <= rows <=
  * 128; k a multiple of 512, 512 <= k <= 8192; w_f16 the lm_head fp16 [vocab][k]; logits_f32 fp32 [rows][ld_logits], ld_logits >=

@@ -7,7 +7,12 @@ nkv * hd elements each (2 bytes with --kv fp16, 1 with --kv fp8: float8_e4m3fn c
 Back-to-back launches timed with events; under `rocprofv3 --kernel-trace --stats` the kernel's own time comes from the trace (the
 two formats run different kernel instantiations; with both named, every row runs fp16 first, then fp8, 10 + iters launches each).
 
-    python perf/attn_batch_bench.py [--batch 8 64] [--context 1024 4096] [--iters 200] [--full] [--kv fp16 fp8]
+--paged PAGE_SIZE ...: after the contiguous launch of a row, the same caches scattered into page pools (pages handed out in a seeded
+random order) through qpalette_amd.paged_decode_attention, once per page size, then the contiguous launch AGAIN (its two timings are
+the spread the paged ones are read against).  "pool_bytes": what the pools of a cache that backs only the positions in
+use would take (sum_b ceil((pos[b] + 1) / page_size) pages), against "cache_bytes".
+
+    python perf/attn_batch_bench.py [--batch 8 64] [--context 1024 4096] [--iters 200] [--full] [--kv fp16 fp8] [--paged 16 64]
 """
 import argparse
 import json
@@ -18,6 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 import qpalette_amd as qp
+from paged import random_table, scatter
 
 
 def main(argv=None):
@@ -30,6 +36,7 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--full", action="store_true", help="every sequence at the last position of its cache")
     ap.add_argument("--kv", nargs="+", default=["fp16"], choices=["fp16", "fp8"], help="KV-cache element format(s), in this order per row")
+    ap.add_argument("--paged", type=int, nargs="*", default=[], metavar="PAGE_SIZE", help="also time paged launches of these page sizes")
     args = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     nq, nkv, hd = args.nq, args.nkv, args.hd
@@ -48,22 +55,36 @@ def main(argv=None):
             ws = qp.attention_workspace(B, nq, nkv, hd, L, dev)
             for kv in args.kv:
                 kc, vc = (kc16, vc16) if kv == "fp16" else (kc16.to(torch.float8_e4m3fn), vc16.to(torch.float8_e4m3fn))
-                for _ in range(10):
-                    qp.decode_attention(q, k, v, kc, vc, pos, inv_freq, out=out, ws=ws)
-                torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(args.iters):
-                    qp.decode_attention(q, k, v, kc, vc, pos, inv_freq, out=out, ws=ws)
-                e1.record()
-                torch.cuda.synchronize()
-                us = e0.elapsed_time(e1) * 1e3 / args.iters
                 kv_rows = int((pos_h + 1).sum())
                 nbytes = kv_rows * nkv * hd * 2 * kc.element_size()
-                rows.append({"batch": B, "context": L, "kv": kv, "full": args.full, "kv_rows": kv_rows, "kv_MB": nbytes / 1e6,
-                             "us_per_launch_events": us, "TBps_events": nbytes / (us * 1e-6) / 1e12,
-                             "workspace_bytes": 0 if ws is None else ws.numel() * 4,
-                             "cache_bytes": 2 * qp.attention.kv_cache_bytes(B, nkv, L, hd, kc.dtype)})
+                for ps in [0] + args.paged + ([0] if args.paged else []):  # 0: contiguous (again at the end: the spread)
+                    if ps:
+                        table = random_table(B, L // ps, B * (L // ps), B + L + ps, dev)
+                        kp, vp = scatter(kc, table, ps, B * (L // ps)), scatter(vc, table, ps, B * (L // ps))
+                        launch = lambda: qp.paged_decode_attention(q, k, v, kp, vp, table, pos, inv_freq, out=out, ws=ws)  # noqa: E731
+                    else:
+                        launch = lambda: qp.decode_attention(q, k, v, kc, vc, pos, inv_freq, out=out, ws=ws)  # noqa: E731
+                    for _ in range(10):
+                        launch()
+                    torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(args.iters):
+                        launch()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us = e0.elapsed_time(e1) * 1e3 / args.iters
+                    row = {"batch": B, "context": L, "kv": kv, "full": args.full, "kv_rows": kv_rows, "kv_MB": nbytes / 1e6,
+                           "us_per_launch_events": us, "TBps_events": nbytes / (us * 1e-6) / 1e12,
+                           "workspace_bytes": 0 if ws is None else ws.numel() * 4,
+                           "cache_bytes": 2 * qp.attention.kv_cache_bytes(B, nkv, L, hd, kc.dtype)}
+                    if args.paged:
+                        row["paged"] = ps
+                    if ps:
+                        pages = int(((pos_h + ps) // ps).sum())
+                        row["pool_bytes"] = 2 * qp.attention.kv_cache_bytes(pages, nkv, ps, hd, kc.dtype)
+                        del kp, vp, table
+                    rows.append(row)
                 del kc, vc
             del kc16, vc16
             torch.cuda.empty_cache()

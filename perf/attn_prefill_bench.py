@@ -5,7 +5,12 @@ Event timing here; for the kernel time proper run it under `rocprofv3 --kernel-t
 
 --kv fp8: float8_e4m3fn caches; torch SDPA then runs on their fp16 image.
 
+--paged PAGE_SIZE ...: per row also the same cache scattered into page pools (pages in a seeded random order) through
+qpalette_amd.paged_prefill_attention, once per page size ("us_paged"), and the contiguous launch a second time
+("us_prefill_attention_again": the spread the paged times are read against).
+
     python perf/attn_prefill_bench.py [--T 128] [--pos0 0 1920 3968] [--context 4096] [--heads 32 8 128] [--iters 50] [--kv fp16|fp8]
+                                      [--paged 16 64]
 """
 import argparse
 import json
@@ -16,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 import qpalette_amd as qp
+from paged import random_table, scatter
 
 
 def main(argv=None):
@@ -26,6 +32,7 @@ def main(argv=None):
     ap.add_argument("--heads", type=int, nargs=3, default=[32, 8, 128], metavar=("NQ", "NKV", "HD"))
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--kv", default="fp16", choices=["fp16", "fp8"], help="KV-cache element format")
+    ap.add_argument("--paged", type=int, nargs="*", default=[], metavar="PAGE_SIZE", help="also time paged launches of these page sizes")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
@@ -67,6 +74,14 @@ def main(argv=None):
         flop = 4 * nq * hd * sum(pos0 + t + 1 for t in range(T))
         rows.append({"T": T, "pos0": pos0, "kv": args.kv, "flop": flop, "us_prefill_attention": us, "tflops": flop / us * 1e-6,
                      "us_torch_sdpa_causal_mask": us_sdpa})
+        if args.paged:
+            rows[-1]["us_paged"] = {}
+            for ps in args.paged:
+                table = random_table(1, L // ps, L // ps, L + ps, dev)
+                kp, vp = scatter(kc[None], table, ps, L // ps), scatter(vc[None], table, ps, L // ps)
+                rows[-1]["us_paged"][str(ps)] = timed(
+                    lambda: qp.paged_prefill_attention(q, k, v, kp, vp, table[0], pos_t, inv_freq, out=out, ws=ws))
+            rows[-1]["us_prefill_attention_again"] = timed(lambda: qp.prefill_attention(q, k, v, kc, vc, pos_t, inv_freq, out=out, ws=ws))
     print(json.dumps({"what": "prefill attention launch (event timing) vs torch SDPA on the same shapes", "heads": args.heads,
                       "context": L, "rows": rows}))
 

@@ -26,7 +26,7 @@ step attends to the round-tripped cache, as the kernels do.  The check also repo
 reference (what the format itself moves; not a gate).
 
     python perf/decode_llama_batch.py [--model 3_8b] [--batch 1 8 16 32 64] [--context 1024] [--tokens 64] [--inactive 0] [--sample]
-                                      [--kv fp16|fp8]
+                                      [--kv fp16|fp8] [--paged PAGE_SIZE]
 """
 import argparse
 import json
@@ -39,6 +39,7 @@ import torch
 
 import qpalette_amd as qp
 from decode_llama import build_model, time_graph
+from paged import random_table, scatter
 
 
 class BatchKV:
@@ -83,12 +84,16 @@ def main(argv=None, quiet=False):
     ap.add_argument("--no-torch-glue", action="store_true", help="skip the torch-glue step (its timing and the check)")
     ap.add_argument("--sample", action="store_true", help="also time the step with a sampler (0.6 / top-k 5 and 0.8 / top-p 0.95)")
     ap.add_argument("--kv", default="fp16", choices=["fp16", "fp8"], help="KV-cache element format (fp8: OCP e4m3fn, no scales)")
+    ap.add_argument("--paged", type=int, default=0, metavar="PAGE_SIZE",
+                    help="also time the step on a paged cache of this page size (pages in a seeded random order; DESIGN.md §17)")
     args = ap.parse_args(argv)
     kv8 = args.kv == "fp8"
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
     if args.context % 4 or args.context < args.tokens + 16:
         raise SystemExit("--context: a multiple of 4, at least --tokens + 16")
+    if args.paged and (args.paged not in qp.attention.PAGE_SIZES or args.context % args.paged):
+        raise SystemExit(f"--paged: one of {qp.attention.PAGE_SIZES} that divides --context")
     dev = torch.device("cuda", 0)
     m = build_model(args.model, args.quantizer, args.qdict, args.layers, args.vocab, dev)
     cfg, layers, embed, lm_head, norm, inv_freq = m.cfg, m.layers, m.embed, m.lm_head, m.norm, m.inv_freq
@@ -188,6 +193,17 @@ def main(argv=None, quiet=False):
                 check["fp16_cache_max_abs_diff_final_norm"] = float((ref_h[act] - step16.hidden().float()[act]).abs().max())
                 del step16, kc16, vc16
         ms_step = timed(kernel_step)
+        paged = None
+        if args.paged:
+            # the same cache contents behind a block table; "pool_bytes": pools that back only the positions the run reaches
+            ps, mp = args.paged, args.context // args.paged
+            table = random_table(B, mp, B * mp, args.seed + B, dev)
+            kp, vp = [scatter(t, table, ps, B * mp) for t in kc], [scatter(t, table, ps, B * mp) for t in vc]
+            pstep = qp.DecodeStep(layers, embed, norm, lm_head, kp, vp, inv_freq, tok, pos, out_tok, generic=True, block_table=table)
+            pages = int(((base[:nact] + args.tokens + ps) // ps).sum())
+            paged = {"page_size": ps, "ms_step": timed(pstep), "ms_step_contiguous_again": timed(kernel_step),
+                     "pool_bytes": 2 * nlayers * qp.attention.kv_cache_bytes(pages, nkv, ps, head_dim, kc[0].dtype)}
+            del pstep, kp, vp, table
         ms_lin = timed(linears_only, None)
         ms_torch = None if args.no_torch_glue else timed(torch_step)
         sampled = None
@@ -208,6 +224,8 @@ def main(argv=None, quiet=False):
                "kv_cache_bytes": 2 * nlayers * qp.attention.kv_cache_bytes(B, nkv, args.context, head_dim, kc[0].dtype)}
         if sampled is not None:
             res["sampled"] = sampled
+        if paged is not None:
+            res["paged"] = paged
         del kc, vc, kc_ref, vc_ref, ref_cache, kernel_step
         torch.cuda.empty_cache()
         return res

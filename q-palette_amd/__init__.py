@@ -10,7 +10,9 @@ Layout:
   hadamard.py      get_hadK (generated Paley factors), matmul_hadU*_cuda, the one-launch `rotate` (lib/utils/matmul_had.py)
   linear/incoherent_linear.py  IncoherentLinear / IncoherentMLP / IncoherentSdpaAttention (lib/linear/incoherent_linear.py)
   attention.py     decode_attention / attention_workspace: rope + KV append + GQA attention of B sequences, one launch;
-                   prefill_attention / prefill_workspace: the same for up to 128 new tokens of one sequence, causal
+                   prefill_attention / prefill_workspace: the same for up to 128 new tokens of one sequence, causal;
+                   paged_decode_attention / paged_prefill_attention: both on page pools behind a block table
+  paging.py        PagedKVCache: per-layer page pools, the block table and the host-side page allocator (reserve / release / fork)
   decoder.py       DecodeStep: the whole-model decode step at batch B >= 1 on the kernels above (per-layer launch sequence,
                    scratch buffers, final norm + lm_head + argmax, launches per token); Prefill: a prompt into one cache slot;
                    Score: the log-probability of every next token of a sequence, nll and perplexity
@@ -51,6 +53,9 @@ from . import quantize  # noqa: F401
 from . import quantize_layer  # noqa: F401
 from . import attention  # noqa: F401
 from .attention import attention_workspace, decode_attention, prefill_attention, prefill_workspace  # noqa: F401
+from .attention import paged_decode_attention, paged_prefill_attention  # noqa: F401
+from . import paging  # noqa: F401
+from .paging import PagedKVCache  # noqa: F401
 from . import sampling  # noqa: F401
 from .sampling import Sampler, lm_head_logits, reference_draw, reference_logprob, sample, token_logprobs  # noqa: F401
 from . import decoder  # noqa: F401

@@ -70,6 +70,10 @@ _SIGNATURES = {
                                         _F, _P, ctypes.c_long, _P],
     "qpal_attn_rope_prefill_kv8": [_P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _P, _I, _I, _I, _I, ctypes.c_long, _F,
                                    _P, ctypes.c_long, _P],
+    "qpal_attn_rope_decode_batch_paged": [_P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _I, _I, _I, _I,
+                                          _I, _I, _I, _I, _F, _P, ctypes.c_long, _P],
+    "qpal_attn_rope_prefill_paged": [_P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _P, _P, _I, _I, _I, _I,
+                                     _I, _I, _I, _I, _F, _P, ctypes.c_long, _P],
     "qpal_lm_head_argmax": [_P, _P, _F, _P, _P, _P, _P, ctypes.c_long, _I, _I, _P],
     "qpal_lm_head_ws_bytes": [_I],
     "qpal_lm_head_logits": [_P, ctypes.c_long, _P, _F, _P, _P, ctypes.c_long, _I, _I, _I, _P],

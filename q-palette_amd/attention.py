@@ -17,6 +17,14 @@ Both take the caches in one of two element formats and dispatch on their dtype: 
 e4m3, one byte per element, no scales: ``qpal_attn_rope_decode_batch_kv8`` / ``qpal_attn_rope_prefill_kv8``).  A
 new row is stored as ``h.float().clamp(-448, 448).to(torch.float8_e4m3fn)`` of the fp16 row ``h`` the fp16 path writes and takes
 part in its own launch at that stored value; stored bytes are converted exactly to fp16.  The workspaces serve both formats.
+
+Paged caches (``qpal_attn_rope_decode_batch_paged`` / ``qpal_attn_rope_prefill_paged``): per-layer pools
+``[num_pages, nkv, page_size, hd]`` and one int32 block table ``[B, max_pages]`` (``paging.PagedKVCache`` owns both); position n of
+sequence b lives in page ``block_table[b, n // page_size]``.  ``max_pages * page_size`` takes the place of max_len everywhere,
+the workspaces of that max_len serve the paged launches, and the result is bit for bit the contiguous launch's on the gathered cache.
+
+    out = paged_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, ws=ws)
+    out = paged_prefill_attention(q, k, v, kpool, vpool, block_table[b], pos0, inv_freq, ws=ws)
 """
 import math
 
@@ -45,12 +53,16 @@ def kv_cache_bytes(B, nkv, max_len, hd, dtype=torch.float16):
     return int(B) * int(nkv) * int(max_len) * int(hd) * torch.empty(0, dtype=dtype).element_size()
 
 
-def _cache_entry(kcache, vcache, who):
-    """the caches' common element format as the suffix of the entry point; everything the library would not check for itself"""
+def _cache_dtype(kcache, vcache, who):
     if kcache.dtype != vcache.dtype:
         raise QpalError(f"{who}: kcache and vcache must share one dtype, got {kcache.dtype} and {vcache.dtype}")
     if kcache.dtype not in _CACHE_ENTRY:
         raise QpalError(f"{who}: the caches' dtype must be torch.float16 or torch.float8_e4m3fn, got {kcache.dtype}")
+
+
+def _cache_entry(kcache, vcache, who):
+    """the caches' common element format as the suffix of the entry point; everything the library would not check for itself"""
+    _cache_dtype(kcache, vcache, who)
     for name, t in (("kcache", kcache), ("vcache", vcache)):
         if not t.is_cuda or not t.is_contiguous():
             raise QpalError(f"{who}: {name} must be a contiguous device tensor, got one on {t.device}")
@@ -83,6 +95,11 @@ def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=Non
         raise QpalError("decode_attention: kcache / vcache must both have shape [B, nkv, max_len, hd]")
     B, nkv, max_len, hd = kcache.shape
     entry = "qpal_attn_rope_decode_batch" + _cache_entry(kcache, vcache, "decode_attention")
+    return _decode(entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, None)
+
+
+def _decode(entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, paged):
+    """the checks and the launch both decode entry points share; paged: None, or the arguments that take max_len's place"""
     if q.dim() != 2 or q.shape[0] != B or q.shape[1] % hd:
         raise QpalError(f"decode_attention: q must have shape [{B}, nq*{hd}], got {list(q.shape)}")
     nq = q.shape[1] // hd
@@ -112,7 +129,7 @@ def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=Non
     with torch.cuda.device(kcache.device):
         rc = getattr(lib, entry)(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
-            pos.data_ptr(), inv_freq.data_ptr(), B, nq, nkv, hd, max_len, scale,
+            pos.data_ptr(), inv_freq.data_ptr(), *((B, nq, nkv, hd, max_len) if paged is None else paged + (B, nq, nkv, hd)), scale,
             ws.data_ptr() if need > 0 else None, ws.numel() * ws.element_size() if need > 0 else 0,
             torch.cuda.current_stream(kcache.device).cuda_stream)
     _native.check(rc, entry)
@@ -146,6 +163,11 @@ def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=N
         raise QpalError(f"{who}: kcache / vcache must both have shape [nkv, max_len, hd]")
     nkv, max_len, hd = kcache.shape
     entry = "qpal_attn_rope_prefill" + _cache_entry(kcache, vcache, who)
+    return _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, None)
+
+
+def _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, paged):
+    """the checks and the launch both prefill entry points share; paged: None, or the arguments that take max_len's place"""
     if q.dim() != 2 or not 1 <= q.shape[0] <= 128 or q.shape[1] % hd:
         raise QpalError(f"{who}: q must have shape [T, nq*{hd}] with 1 <= T <= 128, got {list(q.shape)}")
     T, nq = q.shape[0], q.shape[1] // hd
@@ -175,8 +197,66 @@ def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=N
     with torch.cuda.device(kcache.device):
         rc = getattr(lib, entry)(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
-            pos0.data_ptr(), inv_freq.data_ptr(), T, nq, nkv, hd, max_len, scale,
+            pos0.data_ptr(), inv_freq.data_ptr(), *((T, nq, nkv, hd, max_len) if paged is None else paged + (T, nq, nkv, hd)), scale,
             ws.data_ptr() if need > 0 else None, ws.numel() * ws.element_size() if need > 0 else 0,
             torch.cuda.current_stream(kcache.device).cuda_stream)
     _native.check(rc, entry)
     return out
+
+
+PAGE_SIZES = (16, 32, 64, 128, 256)
+_KV_FMT = {torch.float16: 0, torch.float8_e4m3fn: 1}  # pool dtype -> kv_fmt of the paged entry points
+
+
+def _pools(kpool, vpool, table, who):
+    """the checks of the pools and the block table the library would not make for itself; returns (num_pages, nkv, page_size, hd)"""
+    if kpool.dim() != 4 or kpool.shape != vpool.shape:
+        raise QpalError(f"{who}: kpool / vpool must both have shape [num_pages, nkv, page_size, hd]")
+    _cache_dtype(kpool, vpool, who)
+    num_pages, nkv, page_size, hd = kpool.shape
+    if page_size not in PAGE_SIZES:
+        raise QpalError(f"{who}: page_size must be one of {PAGE_SIZES}, got {page_size}")
+    if table.dtype != torch.int32:
+        raise QpalError(f"{who}: the block table must be int32, got {table.dtype}")
+    if table.device != kpool.device:
+        raise QpalError(f"{who}: the block table must be on the pools' device {kpool.device}, got {table.device}")
+    if table.stride(-1) != 1:
+        raise QpalError(f"{who}: the block table's rows must be contiguous")
+    _cache_entry(kpool, vpool, who)
+    return num_pages, nkv, page_size, hd
+
+
+def paged_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, scale=None, out=None, ws=None):
+    """decode_attention on a paged cache: kpool / vpool [num_pages, nkv, page_size, hd] (fp16 or float8_e4m3fn, contiguous, 16-byte
+    aligned, page_size in {16, 32, 64, 128, 256}), block_table int32 [B, max_pages] on the device with contiguous rows (a row
+    stride >= max_pages): entry j of row b is the page of positions j * page_size .. of sequence b.  Everything else, and every
+    rule, is decode_attention's with max_len = max_pages * page_size (ws: attention_workspace of that max_len); the result is bit
+    for bit that launch's on the gathered cache.  Only entries that cover positions 0 .. pos[b] are read.  An entry in use outside
+    [0, num_pages) (an unreserved -1): reads go to page 0, the new row is dropped, that sequence's out row is unspecified."""
+    who = "paged_decode_attention"
+    num_pages, nkv, page_size, hd = _pools(kpool, vpool, block_table, who)
+    if block_table.dim() != 2 or block_table.shape[1] < 1:
+        raise QpalError(f"{who}: block_table must have shape [B, max_pages >= 1], got {list(block_table.shape)}")
+    B, max_pages = block_table.shape
+    ld_table = block_table.stride(0) if B > 1 else max_pages
+    if ld_table < max_pages:
+        raise QpalError(f"{who}: the block table's row stride must be at least max_pages")
+    paged = (block_table.data_ptr(), ld_table, num_pages, page_size, max_pages, _KV_FMT[kpool.dtype])
+    return _decode("qpal_attn_rope_decode_batch_paged", q, k, v, kpool, vpool, pos, inv_freq, scale, out, ws, B, nkv,
+                   max_pages * page_size, hd, paged)
+
+
+def paged_prefill_attention(q, k, v, kpool, vpool, block_row, pos0, inv_freq, scale=None, out=None, ws=None):
+    """prefill_attention on a paged cache: the pools of paged_decode_attention and block_row int32 [max_pages], the block-table row
+    of the ONE sequence (``block_table[b]``).  Every rule is prefill_attention's with max_len = max_pages * page_size (ws:
+    prefill_workspace of that max_len); bit for bit that launch's result on the gathered cache, and the pools end up byte for byte
+    as paged_decode_attention would have filled them token by token.  Only entries that cover positions 0 .. pos0 + T - 1 are read;
+    the guard on entries outside [0, num_pages) is paged_decode_attention's."""
+    who = "paged_prefill_attention"
+    num_pages, nkv, page_size, hd = _pools(kpool, vpool, block_row, who)
+    if block_row.dim() != 1 or block_row.shape[0] < 1:
+        raise QpalError(f"{who}: block_row must have shape [max_pages >= 1], got {list(block_row.shape)}")
+    max_pages = block_row.shape[0]
+    paged = (block_row.data_ptr(), num_pages, page_size, max_pages, _KV_FMT[kpool.dtype])
+    return _prefill(who, "qpal_attn_rope_prefill_paged", q, k, v, kpool, vpool, pos0, inv_freq, scale, out, ws, nkv,
+                    max_pages * page_size, hd, paged)

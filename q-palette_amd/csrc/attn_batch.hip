@@ -17,11 +17,18 @@
 // (qpal_attn_rope_decode_batch_kv8, kv8.h).  The e4m3 instantiation differs at the load, convert and store sites
 // only: a byte row is converted exactly to the fp16 values the matrix pipe and the value loop take today, the new row is quantised
 // once and takes part at its stored value.  LDS layout, workspace and grid do not depend on CT.
+//
+// PAGED (qpal_attn_rope_decode_batch_paged, kv_paged.h): the caches are pools [num_pages][nkv][page_size][HD] and a
+// sequence's position n lives in page table[b][n / page_size].  The instantiation differs in the address of a cache row only:
+// every load and store site takes its row through paged_row(); the page ids of a step are loaded one step ahead of the rows they
+// address (the first step's before the rotary embedding), so the lookup is not in front of the K / V loads.  Arithmetic, its order,
+// LDS layout, workspace and grid are those of the contiguous launch with max_len = max_pages * page_size.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
 #include "kv8.h"
+#include "kv_paged.h"
 #include "qpal_common.h"
 
 namespace qpal {
@@ -50,6 +57,10 @@ struct AttnBatchParams {
     unsigned *tickets;          // [kBatchMax * nkv] (zero-filled once)
     float *part;                // [B * nkv * nsplit][REP][HD + 2] partials
     int nsplit, chunk;          // chunk: LDS score capacity per head (multiple of 64, nsplit * chunk >= max_len)
+    // PAGED only: kcache / vcache are the pools [num_pages][nkv][1 << page_shift][HD], max_len = max_pages << page_shift
+    const int *table;           // int32 [B][ld_table], device
+    long ld_table;
+    int num_pages, page_shift;
 };
 
 __device__ __forceinline__ void st_agent(float *p, float v) {
@@ -59,7 +70,7 @@ __device__ __forceinline__ float ld_agent(const float *p) {
     return __builtin_bit_cast(float, __hip_atomic_load(as_global(reinterpret_cast<const unsigned *>(p)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
-template <class CT, int HD, int REP>
+template <class CT, bool PAGED, int HD, int REP>
 __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const AttnBatchParams<CT> p) {
     constexpr bool KV8 = kIsKv8<CT>;
     constexpr int NW = kBatchNW, NT = 64 * NW, HALF = HD / 2;
@@ -94,8 +105,39 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
     const bool owner = split == neff - 1;                    // this chunk holds the new position
     const long cend = pos < c0 + cld ? pos : c0 + cld;       // cached positions of the chunk: [c0, cend)
     const int nc = cend > c0 ? (int)(cend - c0) : 0;
-    const long kvoff = ((long)b * p.nkv + kh) * p.max_len * HD;
+    const long kvoff = PAGED ? 0 : ((long)b * p.nkv + kh) * p.max_len * HD;
     const gptr<const CT> K = as_global(p.kcache) + kvoff, V = as_global(p.vcache) + kvoff;
+    // element offset of the new row from the cache base, and whether it is stored (PAGED: a page id outside the pool drops it)
+    [[maybe_unused]] long newoff_pg = 0;
+    [[maybe_unused]] bool new_ok = true;
+    auto new_k_row = [&] {
+        if constexpr (PAGED) return p.kcache + newoff_pg;
+        else return p.kcache + kvoff + pos * HD;
+    };
+    auto new_off = [&] {
+        if constexpr (PAGED) return newoff_pg;
+        else return kvoff + pos * HD;
+    };
+    [[maybe_unused]] const int *tab = nullptr;
+    [[maybe_unused]] int kpg[KV8 ? 4 : 2];  // PAGED: this lane's page ids of the next step of the score loop
+    // offset of cached row c0 + t of this chunk: PAGED through page id `page` (outside the pool: page 0 is read instead)
+    auto row_off = [&](long n, [[maybe_unused]] int page) {
+        if constexpr (PAGED) return paged_row<HD>(page_ok(page, p.num_pages) ? page : 0, p.nkv, kh, p.page_shift, n);
+        else return n * HD;
+    };
+    if constexpr (PAGED) {
+        tab = p.table + (long)b * p.ld_table;
+        if (owner) {
+            const int pg = tab[pos >> p.page_shift];
+            new_ok = page_ok(pg, p.num_pages);
+            newoff_pg = paged_row<HD>(pg, p.nkv, kh, p.page_shift, pos);
+        }
+#pragma unroll
+        for (int u = 0; u < (KV8 ? 4 : 2); u++) {  // (positions clamped to the chunk's first: entries <= pos only)
+            const int t = (tid >> 6) * 16 + u * NW * 16 + (tid & 15);
+            kpg[u] = tab[(c0 + (t < nc ? t : 0)) >> p.page_shift];
+        }
+    }
     const float *qrow = p.q + (long)b * p.ld_qkv, *krow = p.k + (long)b * p.ld_qkv, *vrow = p.v + (long)b * p.ld_qkv;
     uint16_t *orow = p.out + (long)b * p.ld_out + (long)kh * REP * HD;
     const long slot = ((long)b * p.nkv + kh) * p.nsplit;
@@ -118,17 +160,19 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
                 const uint32_t b8 = e4m3_pack2(o1, o2), h2 = e4m3_half2<false>(b8);
                 dst16[i] = (uint16_t)h2;
                 dst16[i + HALF] = (uint16_t)(h2 >> 16);
-                CT *dst = p.kcache + kvoff + pos * HD;
-                dst[i] = (CT)b8;
-                dst[i + HALF] = (CT)(b8 >> 8);
+                CT *dst = new_k_row();
+                if (!PAGED || new_ok) {
+                    dst[i] = (CT)b8;
+                    dst[i + HALF] = (CT)(b8 >> 8);
+                }
                 continue;
             }
         }
         dst16[i] = __builtin_bit_cast(uint16_t, o1);
         dst16[i + HALF] = __builtin_bit_cast(uint16_t, o2);
         if constexpr (!KV8) {
-            if (is_k) {
-                uint16_t *dst = p.kcache + kvoff + pos * HD;
+            if (is_k && (!PAGED || new_ok)) {
+                uint16_t *dst = new_k_row();
                 dst[i] = __builtin_bit_cast(uint16_t, o1);
                 dst[i + HALF] = __builtin_bit_cast(uint16_t, o2);
             }
@@ -140,10 +184,10 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
             if constexpr (KV8) {
                 const uint32_t b8 = e4m3_pack2(hv, hv);
                 vn[d] = e4m3_float2<false>(b8).x;
-                p.vcache[kvoff + pos * HD + d] = (CT)b8;
+                if (!PAGED || new_ok) p.vcache[new_off() + d] = (CT)b8;
             } else {
                 vn[d] = (float)hv;
-                p.vcache[kvoff + pos * HD + d] = __builtin_bit_cast(uint16_t, hv);
+                if (!PAGED || new_ok) p.vcache[new_off() + d] = __builtin_bit_cast(uint16_t, hv);
             }
         }
     }
@@ -174,9 +218,16 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const int t = t0 + u * NW * 16 + mi;
-                const gptr<const CT> row = K + (c0 + (t < nc ? t : 0)) * HD + 8 * mq;
+                const gptr<const CT> row = K + row_off(c0 + (t < nc ? t : 0), kpg[u]) + 8 * mq;
 #pragma unroll
                 for (int kc = 0; kc < KC; kc++) kb[u][kc] = *(gptr<const KB>)(row + 32 * kc);
+            }
+            if constexpr (PAGED) {  // the next step's page ids, behind this step's row loads
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const int t = t0 + (U + u) * NW * 16 + mi;
+                    kpg[u] = tab[(c0 + (t < nc ? t : 0)) >> p.page_shift];
+                }
             }
 #pragma unroll
             for (int u = 0; u < U; u++) {
@@ -200,6 +251,22 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
             }
         }
     }
+    // rows in flight per wave (e4m3: a lane's DPL bytes, so twice the rows while their REP weights each stay within 32 registers)
+    constexpr int UV16 = REP * DPL > 16 ? 2 : 4, UV = !KV8 ? UV16 : (2 * UV16 * REP > 32 ? 32 / REP : 2 * UV16);
+    // PAGED: a row of the value loop belongs to one wave, so its page id is wave-uniform (a scalar load); ids one step ahead, the
+    // first step's here: in front of the reductions
+    [[maybe_unused]] int vpg[UV];
+    [[maybe_unused]] const int wv = PAGED ? __builtin_amdgcn_readfirstlane(wave) : wave;
+    auto v_pages = [&]([[maybe_unused]] int t0) {
+        if constexpr (PAGED) {
+#pragma unroll
+            for (int u = 0; u < UV; u++) {
+                const int t = t0 + u * NW;
+                vpg[u] = tab[(c0 + (t < nc ? t : 0)) >> p.page_shift];
+            }
+        }
+    };
+    v_pages(wv);
     if (owner && wave == NW - 1) {  // the new position, from LDS (parked apart: the chunk's nc may equal CL)
         u32x4 kn = u32x4{0u, 0u, 0u, 0u};
         if (grp == 0) kn = *reinterpret_cast<const u32x4 *>(knh + 4 * sl);
@@ -259,14 +326,12 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
     for (int h = 0; h < REP; h++)
 #pragma unroll
         for (int e = 0; e < DPL; e++) acc[h][e] = 0.f;
-    // rows in flight per wave (e4m3: a lane's DPL bytes, so twice the rows while their REP weights each stay within 32 registers)
-    constexpr int UV16 = REP * DPL > 16 ? 2 : 4, UV = !KV8 ? UV16 : (2 * UV16 * REP > 32 ? 32 / REP : 2 * UV16);
-    for (int t0 = wave; t0 < nc; t0 += NW * UV) {
+    for (int t0 = PAGED ? wv : wave; t0 < nc; t0 += NW * UV) {
         std::conditional_t<KV8, uint32_t, uint16_t> raw[UV][KV8 ? 1 : DPL];  // (e4m3: the DPL bytes in one register)
 #pragma unroll
         for (int u = 0; u < UV; u++) {
             const int t = t0 + u * NW;
-            const gptr<const CT> row = V + (c0 + (t < nc ? t : 0)) * HD + DPL * lane;
+            const gptr<const CT> row = V + row_off(c0 + (t < nc ? t : 0), vpg[u]) + DPL * lane;
             if constexpr (KV8) {
                 if constexpr (DPL == 1) raw[u][0] = row[0];
                 else if constexpr (DPL == 2) raw[u][0] = *(gptr<const uint16_t>)row;
@@ -275,6 +340,7 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
             else if constexpr (DPL == 2) { const uint32_t r = *(gptr<const uint32_t>)row; raw[u][0] = (uint16_t)r; raw[u][1] = (uint16_t)(r >> 16); }
             else { const u32x2 r = *(gptr<const u32x2>)row; raw[u][0] = (uint16_t)r.x; raw[u][1] = (uint16_t)(r.x >> 16); raw[u][2] = (uint16_t)r.y; raw[u][3] = (uint16_t)(r.y >> 16); }
         }
+        v_pages(t0 + NW * UV);
 #pragma unroll
         for (int u = 0; u < UV; u++) {
             const int t = t0 + u * NW;
@@ -415,9 +481,9 @@ int batch_geometry(int B, int nq, int nkv, int hd, long max_len, BatchGeometry &
     return QPAL_OK;
 }
 
-template <class CT, int HD, int REP>
+template <class CT, bool PAGED, int HD, int REP>
 int launch_batch(const AttnBatchParams<CT> &p, int grid, size_t lds, void *stream) {
-    const auto kern = attn_rope_batch_kernel<CT, HD, REP>;
+    const auto kern = attn_rope_batch_kernel<CT, PAGED, HD, REP>;
     static bool attr_set[64] = {};  // one latch per instantiation and device
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
@@ -430,11 +496,12 @@ int launch_batch(const AttnBatchParams<CT> &p, int grid, size_t lds, void *strea
     return (int)hipGetLastError();
 }
 
-// the two entry points: the same checks, geometry and launch, the cache element type apart
-template <class CT>
+// the entry points: the same checks, geometry and launch, the cache element type and the row addressing apart (PAGED: kcache /
+// vcache are the pools, `pg` the block table, max_len = max_pages * page_size)
+template <class CT, bool PAGED>
 int attn_rope_decode_batch(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16,
                            long ld_out, const long *pos, const float *inv_freq, int B, int nq, int nkv, int hd, long max_len,
-                           float scale, void *ws, long ws_bytes, void *stream) {
+                           float scale, void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0) {
     if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
     BatchGeometry g;
     const int rc = batch_geometry(B, nq, nkv, hd, max_len, g);
@@ -445,6 +512,7 @@ int attn_rope_decode_batch(const float *q, const float *k, const float *v, long 
          reinterpret_cast<uintptr_t>(inv_freq) | reinterpret_cast<uintptr_t>(pos)) & 3)
         return QPAL_E_ALIGN;
     if (reinterpret_cast<uintptr_t>(out_f16) & 1) return QPAL_E_ALIGN;
+    if (PAGED && (reinterpret_cast<uintptr_t>(pg->table) & 3)) return QPAL_E_ALIGN;
     if (g.ws_bytes) {
         if (!ws) return QPAL_E_NULL;
         if (ws_bytes < (long)g.ws_bytes) return QPAL_E_SHAPE;
@@ -455,9 +523,10 @@ int attn_rope_decode_batch(const float *q, const float *k, const float *v, long 
                           static_cast<uint16_t *>(out_f16), ld_out, pos, inv_freq, nkv, max_len, scale,
                           g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr, g.ws_bytes ? wsf + (long)kBatchMax * nkv : nullptr,
                           g.nsplit, g.chunk};
+    if constexpr (PAGED) p.table = pg->table, p.ld_table = pg->ld_table, p.num_pages = pg->num_pages, p.page_shift = shift;
     const int grid = B * nkv * g.nsplit, rep = nq / nkv;
 #define QPAL_BATCH(HD_, REP_) \
-    if (hd == HD_ && rep == REP_) return launch_batch<CT, HD_, REP_>(p, grid, g.lds, stream);
+    if (hd == HD_ && rep == REP_) return launch_batch<CT, PAGED, HD_, REP_>(p, grid, g.lds, stream);
     QPAL_BATCH(64, 1) QPAL_BATCH(64, 2) QPAL_BATCH(64, 4) QPAL_BATCH(64, 8)
     QPAL_BATCH(128, 1) QPAL_BATCH(128, 2) QPAL_BATCH(128, 4) QPAL_BATCH(128, 8)
     QPAL_BATCH(256, 1) QPAL_BATCH(256, 2) QPAL_BATCH(256, 4)
@@ -480,7 +549,7 @@ extern "C" long qpal_attn_batch_ws_bytes(int B, int nq, int nkv, int hd, long ma
 extern "C" int qpal_attn_rope_decode_batch(const float *q, const float *k, const float *v, long ld_qkv, void *kcache_f16, void *vcache_f16,
                                            void *out_f16, long ld_out, const long *pos, const float *inv_freq, int B, int nq, int nkv,
                                            int hd, long max_len, float scale, void *ws, long ws_bytes, void *stream) {
-    return attn_rope_decode_batch<uint16_t>(q, k, v, ld_qkv, kcache_f16, vcache_f16, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd,
+    return attn_rope_decode_batch<uint16_t, false>(q, k, v, ld_qkv, kcache_f16, vcache_f16, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd,
                                             max_len, scale, ws, ws_bytes, stream);
 }
 
@@ -488,6 +557,26 @@ extern "C" int qpal_attn_rope_decode_batch_kv8(const float *q, const float *k, c
                                                void *vcache_e4m3, void *out_f16, long ld_out, const long *pos, const float *inv_freq,
                                                int B, int nq, int nkv, int hd, long max_len, float scale, void *ws, long ws_bytes,
                                                void *stream) {
-    return attn_rope_decode_batch<uint8_t>(q, k, v, ld_qkv, kcache_e4m3, vcache_e4m3, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd,
+    return attn_rope_decode_batch<uint8_t, false>(q, k, v, ld_qkv, kcache_e4m3, vcache_e4m3, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd,
                                            max_len, scale, ws, ws_bytes, stream);
+}
+
+extern "C" int qpal_attn_rope_decode_batch_paged(const float *q, const float *k, const float *v, long ld_qkv, void *kpool, void *vpool,
+                                                 void *out_f16, long ld_out, const long *pos, const float *inv_freq,
+                                                 const int *block_table, long ld_table, int num_pages, int page_size, int max_pages,
+                                                 int kv_fmt, int B, int nq, int nkv, int hd, float scale, void *ws, long ws_bytes,
+                                                 void *stream) {
+    if (!block_table) return QPAL_E_NULL;
+    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
+    int shift;
+    long max_len;
+    // (the siblings' order: their null checks come first, so a null among q .. inv_freq wins over a paged shape error)
+    if (!q || !k || !v || !kpool || !vpool || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
+    const int rc = paged_shape(pg, kv_fmt, shift, max_len);
+    if (rc != QPAL_OK) return rc;
+    if (kv_fmt == 1)
+        return attn_rope_decode_batch<uint8_t, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd, max_len,
+                                                     scale, ws, ws_bytes, stream, &pg, shift);
+    return attn_rope_decode_batch<uint16_t, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd, max_len,
+                                                  scale, ws, ws_bytes, stream, &pg, shift);
 }

@@ -22,11 +22,16 @@
 // it; the register prefetch holds bytes (cached rows as loaded, new rows quantised by the thread that rotates them, which also
 // stores them where its tile owns them) and the bytes are converted exactly on their way into LDS — a new row takes part at its
 // stored value.  Workspace and grid do not depend on CT.
+//
+// PAGED (qpal_attn_rope_prefill_paged, kv_paged.h): the caches are pools [num_pages][nkv][page_size][HD] and position
+// n lives in page block_row[n / page_size].  Only the address of a cache row differs: a 32-key tile starts at a multiple of 32, so
+// its two 16-key halves have one page id each, workgroup-uniform and fetched one tile ahead of the rows.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
 #include "kv8.h"
+#include "kv_paged.h"
 #include "qpal_common.h"
 
 namespace qpal {
@@ -55,6 +60,9 @@ struct AttnPrefillParams {
     unsigned *tickets;          // [nkv * kPfMaxTiles] (zero-filled once)
     float *part;                // [nkv * ntile * nsplit][rows of a tile][HD + 2] partials
     int nsplit, ntile;
+    // PAGED only: kcache / vcache are the pools [num_pages][nkv][1 << page_shift][HD], max_len = max_pages << page_shift
+    const int *table;           // int32 [max_pages] of this sequence, device
+    int num_pages, page_shift;
 };
 
 __device__ __forceinline__ void st_agent(float *p, float v) {
@@ -99,7 +107,7 @@ __device__ __forceinline__ u32x4 rope_chunk(const float *src, int ch, long pos, 
     return val;
 }
 
-template <class CT, int HD, int REP>
+template <class CT, bool PAGED, int HD, int REP>
 __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(const AttnPrefillParams<CT> p) {
     constexpr bool KV8 = kIsKv8<CT>;
     using KR = std::conditional_t<KV8, u32x2, u32x4>;  // eight elements of a cache row as prefetched
@@ -136,8 +144,30 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(con
     const int head = kh * REP + hh;
     const int trow = t0 + qsub * 16 + mi;  // this lane's query row (a column of S^T)
     const long qpos = pos0 + trow;
-    const long kvoff = (long)kh * p.max_len * HD;
+    const long kvoff = PAGED ? 0 : (long)kh * p.max_len * HD;
     const gptr<const CT> Kc = as_global(p.kcache) + kvoff, Vc = as_global(p.vcache) + kvoff;
+    // PAGED: the page ids of keys kt0 .. kt0 + 15 and kt0 + 16 .. kt0 + 31 of the tile about to be fetched (the second only where
+    // the chunk reaches it: entries past the launch's last position are never read)
+    [[maybe_unused]] int pg0 = 0, pg1 = 0;
+    auto tile_pages = [&]([[maybe_unused]] long kt0) {
+        if constexpr (PAGED) {
+            if (kt0 < c1) {
+                pg0 = p.table[kt0 >> p.page_shift];
+                pg1 = kt0 + 16 < c1 ? p.table[(kt0 + 16) >> p.page_shift] : pg0;
+            }
+        }
+    };
+    tile_pages(c0);
+    // element offset of row n (key rr of its tile) from the cache base, and whether a new row may be stored there
+    auto row_off = [&](long n, [[maybe_unused]] int rr, [[maybe_unused]] bool &ok) {
+        if constexpr (PAGED) {
+            const int pg = rr < 16 ? pg0 : pg1;
+            ok = page_ok(pg, p.num_pages);
+            return paged_row<HD>(ok ? pg : 0, p.nkv, kh, p.page_shift, n);
+        } else {
+            return n * HD;
+        }
+    };
 
     // ---- the wave's 16 query rows after the rotary embedding, through LDS into B fragments (rows >= T: zeros)
     for (int idx = lane; idx < 16 * HALF; idx += 64) {
@@ -172,8 +202,9 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(con
             const long n = kt0 + rr;
             KR val{};
             if (n < c1) {
+                [[maybe_unused]] bool st_ok = true;  // (PAGED: a new row behind an entry outside the pool is not stored)
                 if (n < pos0) {
-                    val = *(gptr<const KR>)((isv ? Vc : Kc) + n * HD + 8 * ch);
+                    val = *(gptr<const KR>)((isv ? Vc : Kc) + row_off(n, rr, st_ok) + 8 * ch);
                 } else if constexpr (KV8) {
                     const int tn = (int)(n - pos0);  // < tend <= T
                     u32x4 h16;
@@ -188,7 +219,10 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(con
                         h16 = rope_chunk<HD>(p.k + (long)tn * p.ld_qkv + (long)kh * HD, ch, n, p.inv_freq);
                     }
                     val = e4m3_pack8(h16);  // quantised once: these bytes reach the cache and, converted back, the LDS image
-                    if (tn >= t0) *reinterpret_cast<u32x2 *>((isv ? p.vcache : p.kcache) + kvoff + n * HD + 8 * ch) = val;
+                    {
+                        const long noff = row_off(n, rr, st_ok);
+                        if (tn >= t0 && (!PAGED || st_ok)) *reinterpret_cast<u32x2 *>((isv ? p.vcache : p.kcache) + kvoff + noff + 8 * ch) = val;
+                    }
                 } else {
                     const int tn = (int)(n - pos0);  // < tend <= T
                     if (isv) {
@@ -201,7 +235,10 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(con
                     } else {
                         val = rope_chunk<HD>(p.k + (long)tn * p.ld_qkv + (long)kh * HD, ch, n, p.inv_freq);
                     }
-                    if (tn >= t0) *reinterpret_cast<u32x4 *>((isv ? p.vcache : p.kcache) + kvoff + n * HD + 8 * ch) = val;
+                    {
+                        const long noff = row_off(n, rr, st_ok);
+                        if (tn >= t0 && (!PAGED || st_ok)) *reinterpret_cast<u32x4 *>((isv ? p.vcache : p.kcache) + kvoff + noff + 8 * ch) = val;
+                    }
                 }
             }
             regs[u] = val;
@@ -225,7 +262,10 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(con
     // per step: fetch tile k into registers (loads in flight), products of tile k - 1 from LDS, then tile k into LDS
     for (long kt0 = c0;; kt0 += kPfKT) {
         const bool more = kt0 < c1;
-        if (more) fetch(kt0, regs);
+        if (more) {
+            fetch(kt0, regs);
+            tile_pages(kt0 + kPfKT);  // the next tile's, behind this tile's row loads
+        }
         if (kt0 > c0) {
             // S^T: lane holds keys kt0 + 16 kt + 4 mq + r of query mi
             float4_t s[2];
@@ -380,11 +420,12 @@ int prefill_geometry(int T, int nq, int nkv, int hd, long max_len, PrefillGeomet
     return QPAL_OK;
 }
 
-// the two entry points: the same checks, geometry and launch, the cache element type apart
-template <class CT>
+// the entry points: the same checks, geometry and launch, the cache element type and the row addressing apart (PAGED: kcache /
+// vcache are the pools, `pg` the sequence's block-table row, max_len = max_pages * page_size)
+template <class CT, bool PAGED>
 int attn_rope_prefill(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16,
                       long ld_out, const long *pos0, const float *inv_freq, int T, int nq, int nkv, int hd, long max_len, float scale,
-                      void *ws, long ws_bytes, void *stream) {
+                      void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0) {
     if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos0 || !inv_freq) return QPAL_E_NULL;
     PrefillGeometry g;
     const int rc = prefill_geometry(T, nq, nkv, hd, max_len, g);
@@ -395,6 +436,7 @@ int attn_rope_prefill(const float *q, const float *k, const float *v, long ld_qk
          reinterpret_cast<uintptr_t>(inv_freq) | reinterpret_cast<uintptr_t>(pos0)) & 3)
         return QPAL_E_ALIGN;
     if (reinterpret_cast<uintptr_t>(out_f16) & 1) return QPAL_E_ALIGN;
+    if (PAGED && (reinterpret_cast<uintptr_t>(pg->table) & 3)) return QPAL_E_ALIGN;
     if (g.ws_bytes) {
         if (!ws) return QPAL_E_NULL;
         if (ws_bytes < (long)g.ws_bytes) return QPAL_E_SHAPE;
@@ -405,10 +447,11 @@ int attn_rope_prefill(const float *q, const float *k, const float *v, long ld_qk
                             static_cast<uint16_t *>(out_f16), ld_out, pos0, inv_freq, T, nkv, max_len, scale,
                             g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr, g.ws_bytes ? wsf + (long)nkv * kPfMaxTiles : nullptr,
                             g.nsplit, g.ntile};
+    if constexpr (PAGED) p.table = pg->table, p.num_pages = pg->num_pages, p.page_shift = shift;
     const int grid = nkv * g.ntile * g.nsplit, rep = nq / nkv;
 #define QPAL_PREFILL(HD_, REP_)                                                                                                    \
     if (hd == HD_ && rep == REP_) {                                                                                                \
-        hipLaunchKernelGGL((attn_prefill_kernel<CT, HD_, REP_>), dim3(grid), dim3(64 * REP_ * pf_qs(REP_)), 0,                     \
+        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, HD_, REP_>), dim3(grid), dim3(64 * REP_ * pf_qs(REP_)), 0,              \
                            static_cast<hipStream_t>(stream), p);                                                                   \
         return (int)hipGetLastError();                                                                                             \
     }
@@ -434,13 +477,31 @@ extern "C" long qpal_attn_prefill_ws_bytes(int T, int nq, int nkv, int hd, long 
 extern "C" int qpal_attn_rope_prefill(const float *q, const float *k, const float *v, long ld_qkv, void *kcache_f16, void *vcache_f16,
                                       void *out_f16, long ld_out, const long *pos0, const float *inv_freq, int T, int nq, int nkv,
                                       int hd, long max_len, float scale, void *ws, long ws_bytes, void *stream) {
-    return attn_rope_prefill<uint16_t>(q, k, v, ld_qkv, kcache_f16, vcache_f16, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, max_len,
+    return attn_rope_prefill<uint16_t, false>(q, k, v, ld_qkv, kcache_f16, vcache_f16, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, max_len,
                                        scale, ws, ws_bytes, stream);
 }
 
 extern "C" int qpal_attn_rope_prefill_kv8(const float *q, const float *k, const float *v, long ld_qkv, void *kcache_e4m3,
                                           void *vcache_e4m3, void *out_f16, long ld_out, const long *pos0, const float *inv_freq, int T,
                                           int nq, int nkv, int hd, long max_len, float scale, void *ws, long ws_bytes, void *stream) {
-    return attn_rope_prefill<uint8_t>(q, k, v, ld_qkv, kcache_e4m3, vcache_e4m3, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, max_len,
+    return attn_rope_prefill<uint8_t, false>(q, k, v, ld_qkv, kcache_e4m3, vcache_e4m3, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, max_len,
                                       scale, ws, ws_bytes, stream);
+}
+
+extern "C" int qpal_attn_rope_prefill_paged(const float *q, const float *k, const float *v, long ld_qkv, void *kpool, void *vpool,
+                                            void *out_f16, long ld_out, const long *pos0, const float *inv_freq, const int *block_row,
+                                            int num_pages, int page_size, int max_pages, int kv_fmt, int T, int nq, int nkv, int hd,
+                                            float scale, void *ws, long ws_bytes, void *stream) {
+    if (!block_row) return QPAL_E_NULL;
+    const PageArgs pg{block_row, max_pages, num_pages, page_size, max_pages};
+    int shift;
+    long max_len;
+    if (!q || !k || !v || !kpool || !vpool || !out_f16 || !pos0 || !inv_freq) return QPAL_E_NULL;
+    const int rc = paged_shape(pg, kv_fmt, shift, max_len);
+    if (rc != QPAL_OK) return rc;
+    if (kv_fmt == 1)
+        return attn_rope_prefill<uint8_t, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, max_len,
+                                                scale, ws, ws_bytes, stream, &pg, shift);
+    return attn_rope_prefill<uint16_t, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, max_len, scale,
+                                             ws, ws_bytes, stream, &pg, shift);
 }

@@ -29,6 +29,10 @@ in chunks of at most 128 rows, with `prefill_attention` (causal, rows appended t
     sc = Score(layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128)
     lp = sc(tokens, slot=0, pos0=0)         # fp32 [N - 1]: lp[t] = log p(tokens[t + 1] | tokens[0 .. t])
     ppl, loss = perplexity(sc, windows)     # windows int64 [W, N]
+
+All three take `block_table=` for a paged cache (paging.PagedKVCache): kcache / vcache are then the per-layer page
+pools [num_pages, nkv, page_size, hd], the table is int32 [B, max_pages], and context = max_pages * page_size.  The caller reserves
+pages for every position a call, or a run of graph replays, will reach before it starts: nothing in here allocates or synchronises.
 """
 import math
 
@@ -37,7 +41,8 @@ import torch
 from . import _native as nat
 from . import hadamard as had
 from . import linear, ops, sampling
-from .attention import attention_workspace, decode_attention, prefill_attention, prefill_workspace
+from .attention import (attention_workspace, decode_attention, paged_decode_attention, paged_prefill_attention, prefill_attention,
+                        prefill_workspace)
 from .linear import multi_gemv
 
 
@@ -83,11 +88,18 @@ class DecodeStep:
     split_attention switch single fusions of the batch-1 step off (profiling).  sampler: a sampling.Sampler of B slots — the tail
     becomes lm_head logits of all B rows + one draw per active row with the counter pos[b] (two launches); None: argmax.  A sampler
     built with logprobs=True adds a third launch: sampler.logprob[b] = the log-probability of out_tok[b] under the plain softmax of
-    sampler.logits[b], for the rows that drew (pos[b] >= 0 — the positions are the launch's `active` vector; other slots keep theirs)."""
+    sampler.logits[b], for the rows that drew (pos[b] >= 0 — the positions are the launch's `active` vector; other slots keep theirs).
+    block_table: int32 [B, max_pages] on the device — kcache / vcache are then the per-layer page pools [num_pages, nkv, page_size, hd]
+    of a paged cache, context = max_pages * page_size, and the attention launch is paged_decode_attention (a batch of one as well:
+    the fused single-sequence kernel reads contiguous caches only).  The caller has reserved a page for every position the step, or
+    a run of replays of the captured step, will write: the step reads the table on the device and never allocates."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok, generic=False,
-                 swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True, sampler=None):
+                 swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True, sampler=None, block_table=None):
         B = tok.shape[0]
+        if block_table is not None and (block_table.dim() != 2 or block_table.shape[0] != B):
+            raise nat.QpalError(f"DecodeStep: block_table must be int32 [{B}, max_pages], got {list(block_table.shape)}")
+        self.block_table = block_table
         self.tok, self.pos, self.out_tok = tok, pos, out_tok
         self.sampler = self._check_sampler(sampler, B, embed, lm_head)
         self.batch1 = B == 1 and not generic
@@ -108,7 +120,7 @@ class DecodeStep:
                                    k28_fusion and k28_in_gemv(m)))
         # the fused single-sequence attention kernel reads fp16 caches only: on float8_e4m3fn caches the batch-1 step keeps its GEMV
         # fusions and launches decode_attention at B = 1 (same launch count)
-        self.attn_batch = not self.batch1 or kcache[0].dtype != torch.float16
+        self.attn_batch = not self.batch1 or kcache[0].dtype != torch.float16 or block_table is not None
         if self.batch1:
             # long caches: split-context attention (one workspace serves every layer: launches are stream-ordered)
             self.attn_ws_bytes = nat.lib().qpal_attn_ws_bytes(self.nq, self.nkv, self.head_dim, self.context) if split_attention else 0
@@ -152,6 +164,10 @@ class DecodeStep:
         self.layers, self.embed, self.norm, self.lm_head, self.inv_freq = layers, embed, norm, lm_head, inv_freq
         self.kcache, self.vcache = kcache, vcache
         self.nq, self.nkv, self.head_dim, self.context = att.num_heads, att.num_key_value_heads, att.head_dim, kcache[0].shape[2]
+        if getattr(self, "block_table", None) is not None:  # paged: the pools' third dimension is the page size
+            self.context = self.block_table.shape[1] * kcache[0].shape[2]
+        else:
+            self.block_table = None
         self.eps = layers[0].input_layernorm.eps
         self.rot_in_gemv = self.batch1 and ops.can_fuse_rotation(1, H)  # k in {2048, 4096}: the GEMV staging rotates x itself
         hk, self.hidden_K = had.get_hadK(H)
@@ -183,6 +199,10 @@ class DecodeStep:
 
     def _attention(self, i, q, k, v):
         scale = 1.0 / math.sqrt(self.head_dim)
+        if self.block_table is not None:
+            paged_decode_attention(q, k, v, self.kcache[i], self.vcache[i], self.block_table, self.pos, self.inv_freq, scale=scale,
+                                   out=self.a16, ws=self.attn_ws)
+            return
         if self.attn_batch:
             decode_attention(q, k, v, self.kcache[i], self.vcache[i], self.pos, self.inv_freq, scale=scale, out=self.a16, ws=self.attn_ws)
             return
@@ -262,13 +282,21 @@ class Prefill(DecodeStep):
     sampler: the sampling.Sampler of the DecodeStep whose caches this fills (one slot per sequence of the caches).  The token is then
     drawn with slot `slot`'s parameters and the counter of the last prompt row's position, pos0 + N - 1 (computed on the device):
     the counter a DecodeStep would have used had it fed that token.  sampler.logits[slot] holds the logits, and with a sampler
-    built with logprobs=True sampler.logprob[slot] the token's log-probability."""
+    built with logprobs=True sampler.logprob[slot] the token's log-probability.
 
-    def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, native_lm_head=True, sampler=None):
+    block_table: int32 [B, max_pages] — kcache / vcache are the per-layer page pools of a paged cache, the slot's row block_table[slot]
+    addresses them (paged_prefill_attention), context = max_pages * page_size.  The caller has reserved pages for positions pos0 ..
+    pos0 + N - 1 of the slot (PagedKVCache.reserve(slot, pos0 + N)) before the call."""
+
+    def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, native_lm_head=True, sampler=None,
+                 block_table=None):
         if not 1 <= int(chunk) <= 128:
             raise nat.QpalError(f"Prefill: chunk must be in 1 .. 128, got {chunk}")
-        self.chunk, self.batch1 = int(chunk), False
-        self.sampler = self._check_sampler(sampler, kcache[0].shape[0], embed, lm_head)
+        if block_table is not None and block_table.dim() != 2:
+            raise nat.QpalError(f"Prefill: block_table must be int32 [B, max_pages], got {list(block_table.shape)}")
+        self.chunk, self.batch1, self.block_table = int(chunk), False, block_table
+        self.slots = kcache[0].shape[0] if block_table is None else block_table.shape[0]  # sequences of the caches
+        self.sampler = self._check_sampler(sampler, self.slots, embed, lm_head)
         self._setup_rows(layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.chunk)
         dev, H = embed.device, self.h32.shape[1]
         self._full = (self.h32, self.a16, self.qkv32, self.ug32)
@@ -287,6 +315,10 @@ class Prefill(DecodeStep):
         raise nat.QpalError("Prefill: launches are per chunk (9 per layer), not per token")
 
     def _attention(self, i, q, k, v):
+        if self.block_table is not None:
+            paged_prefill_attention(q, k, v, self.kcache[i], self.vcache[i], self.block_table[self.slot], self.pos, self.inv_freq,
+                                    scale=1.0 / math.sqrt(self.head_dim), out=self.a16, ws=self.attn_ws)
+            return
         prefill_attention(q, k, v, self.kcache[i][self.slot], self.vcache[i][self.slot], self.pos, self.inv_freq,
                           scale=1.0 / math.sqrt(self.head_dim), out=self.a16, ws=self.attn_ws)
 
@@ -300,8 +332,8 @@ class Prefill(DecodeStep):
         if tokens.dim() != 1 or tokens.shape[0] < least or tokens.dtype != torch.int64 or tokens.device != self.embed.device:
             raise nat.QpalError(f"{who}: tokens must be int64 [N >= {least}] on {self.embed.device}")
         N = tokens.shape[0]
-        if not 0 <= int(slot) < self.kcache[0].shape[0]:
-            raise nat.QpalError(f"{who}: slot {slot} outside the caches' {self.kcache[0].shape[0]} sequences")
+        if not 0 <= int(slot) < self.slots:
+            raise nat.QpalError(f"{who}: slot {slot} outside the caches' {self.slots} sequences")
         self.slot = int(slot)
         if isinstance(pos0, torch.Tensor):
             self.pos.copy_(pos0.reshape(1))
@@ -359,11 +391,13 @@ class Score(Prefill):
     The logits live in ONE fp32 [chunk, vocab] buffer (sc.logits: the last chunk's n rows); lp and sc.rank are views of buffers of
     max_tokens entries (default: the caches' context) that the next call overwrites.  No host synchronisation inside the call.  The
     last row has no next token: its logits are computed, its row of the log-prob launch is inactive.  The slot is left as Prefill
-    leaves it: a DecodeStep can continue at position pos0 + N.  The lm_head must suit qpal_lm_head_logits (a sampler's demands)."""
+    leaves it: a DecodeStep can continue at position pos0 + N.  The lm_head must suit qpal_lm_head_logits (a sampler's demands).
+    block_table: as for Prefill (a paged cache; the caller reserves the slot's pages for pos0 .. pos0 + N - 1)."""
 
-    def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, max_tokens=None):
+    def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, max_tokens=None, block_table=None):
         self._check_lm_head("Score", embed, lm_head)
-        super().__init__(layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=chunk, native_lm_head=False)
+        super().__init__(layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=chunk, native_lm_head=False,
+                         block_table=block_table)
         self.max_tokens = self.context if max_tokens is None else int(max_tokens)
         if self.max_tokens < 2:
             raise nat.QpalError(f"Score: max_tokens must be at least 2, got {max_tokens}")
