@@ -401,6 +401,41 @@ int qpal_attn_rope_prefill_paged(const float *q, const float *k, const float *v,
                                  int num_pages, int page_size, int max_pages, int kv_fmt,
                                  int T, int nq, int nkv, int hd, float scale, void *ws, long ws_bytes, void *stream);
 
+/* RAGGED prefill (csrc/attn_ragged.hip): rows of SEVERAL sequences in one launch.  q / k / v / out have R rows (1 <= R
+ * <= 128) cut into S segments (1 <= S <= 128) that three DEVICE arrays describe — never read by the host, so a captured launch can
+ * be replayed while segment lengths, sequences and positions change:
+ *   seq int32 [S], row0 int32 [S + 1] (cumulative, row0[0] = 0), pos0 int64 [S]
+ * Segment s is rows row0[s] .. row0[s + 1] - 1 (T_s rows), the tokens of sequence seq[s] at positions pos0[s] .. pos0[s] + T_s - 1.
+ * For each segment the launch does exactly what qpal_attn_rope_prefill does for T = T_s rows on the cache of sequence seq[s]: the
+ * rotary embedding, k / v appended (kv_fmt 0: fp16; 1: e4m3fn at the _kv8 store rule), causal attention of row t over positions 0 ..
+ * pos0[s] + t of ITS sequence.  A decode token is a segment of one row.  Caches: [B][nkv][max_len][hd], 16-byte aligned; paged:
+ * the pools and the block table [B][ld_table] of qpal_attn_rope_decode_batch_paged, max_len = max_pages * page_size.
+ * A segment with T_s <= 0, row0[s] < 0, row0[s + 1] > R, seq[s] outside [0, B), pos0[s] < 0 or pos0[s] + T_s > max_len is inactive:
+ * no cache byte and no out byte is written for it.  Out rows of no active segment keep what they held.  Two active segments that
+ * name one sequence: the caller's error — that sequence's result is unspecified; no byte outside caches / pools, out and ws is
+ * touched.  Paged: the guard on table entries outside [0, num_pages) is the paged siblings'.
+ * A query tile never straddles two segments (tile j of a segment starts at its row j * TQ, TQ = 16 query rows, 32 / 64 for nq / nkv
+ * = 2 / 1): per segment, chunks, partials and merge are those of the one-sequence launch of the same nsplit, so with one chunk
+ * (max_len < 512) out is bit for bit that launch's.  The grid is fixed from (R, S, heads, max_len).  ws:
+ * qpal_attn_ragged_ws_bytes(R, S, ...) bytes, 4-byte aligned, zero-filled ONCE, kept across launches; monotone in R, S and max_len,
+ * 0 (pass NULL) for max_len < 512.  The tickets sit at a fixed offset (128 * nkv words in front of the partials), so a workspace
+ * sized for (R, S, max_len) serves every launch of the same nq, nkv, hd with fewer rows, fewer segments or a shorter cache, in
+ * either format, in any order (launches on one stream may share it); its layout is the ragged launches' own (a prefill workspace
+ * does not stand in).  Two launches on the same input are bitwise equal.  Checks and codes are the siblings' (seq / row0: null QPAL_E_NULL, 4-byte aligned); in
+ * addition S outside 1 .. 128, B < 1, kv_fmt not 0 / 1: QPAL_E_SHAPE. */
+long qpal_attn_ragged_ws_bytes(int R, int S, int nq, int nkv, int hd, long max_len);
+int qpal_attn_rope_prefill_ragged(const float *q, const float *k, const float *v, long ld_qkv,
+                                  void *kcache, void *vcache, void *out_f16, long ld_out,
+                                  const int *seq, const int *row0, const long *pos0, const float *inv_freq,
+                                  int kv_fmt /* 0 fp16, 1 e4m3fn */, int R, int S, int B, int nq, int nkv, int hd,
+                                  long max_len, float scale, void *ws, long ws_bytes, void *stream);
+int qpal_attn_rope_prefill_ragged_paged(const float *q, const float *k, const float *v, long ld_qkv,
+                                        void *kpool, void *vpool, void *out_f16, long ld_out,
+                                        const int *seq, const int *row0, const long *pos0, const float *inv_freq,
+                                        const int *block_table, long ld_table, int num_pages, int page_size, int max_pages,
+                                        int kv_fmt, int R, int S, int B, int nq, int nkv, int hd,
+                                        float scale, void *ws, long ws_bytes, void *stream);
+
 /* Final norm + fp16 lm_head for `rows` rows of the residual stream at once, on the matrix pipe (csrc/lm_head_batch.hip): the
  * logits a sampler needs, and the batch-B tail of a decode step.  h_f32 fp32 [rows][ld_h] (ld_h >= k, in elements), 1 <= rows <=
  * 128; k a multiple of 512, 512 <= k <= 8192; w_f16 the lm_head fp16 [vocab][k]; logits_f32 fp32 [rows][ld_logits], ld_logits >=

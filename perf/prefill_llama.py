@@ -15,6 +15,10 @@ Checks (max |diff| of the last row's final-norm state): Prefill vs torch glue; t
 and one batched DecodeStep continuing the prefilled slot against the torch-glue continuation.
 
     python perf/prefill_llama.py [--model 3_8b] [--prompt 16 128 512 2048] [--context 4096] [--slots 1] [--slot 0] [--no-time]
+
+--ragged S N: instead of the above, S prompts of N tokens (S * N <= 128) into slots 0 .. S - 1 from empty contexts, in the same call
+through ONE RaggedStep (one 128-row step, ragged_prefill_attention) and through S Prefill calls, both captured in a
+graph and replayed: ms of each, and whether the S next tokens agree.
 """
 import argparse
 import json
@@ -44,6 +48,7 @@ def main(argv=None, quiet=False):
     ap.add_argument("--iters", type=int, default=5, help="timed replays of Prefill and of the torch-glue step")
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--no-time", action="store_true", help="checks only")
+    ap.add_argument("--ragged", type=int, nargs=2, default=None, metavar=("S", "N"), help="S prompts of N tokens: RaggedStep vs S Prefill calls")
     ap.add_argument("--no-existing-paths", action="store_true", help="skip the eager token-by-token DecodeStep(generic=True) check")
     ap.add_argument("--progress", action="store_true", help="one line per phase on stderr")
     args = ap.parse_args(argv)
@@ -64,6 +69,28 @@ def main(argv=None, quiet=False):
     cfg, layers, embed, lm_head, norm, inv_freq = m.cfg, m.layers, m.embed, m.lm_head, m.norm, m.inv_freq
     H, nkv, head_dim, nlayers = cfg.hidden_size, cfg.num_key_value_heads, cfg.head_dim, len(layers)
     B, slot, ctx = args.slots, args.slot, args.context
+    if args.ragged:
+        S, N = args.ragged
+        if S < 1 or N < 1 or S * N > 128 or N > ctx:
+            raise SystemExit("--ragged S N: S * N <= 128 rows, N inside --context")
+        kc = [torch.zeros(S, nkv, ctx, head_dim, dtype=torch.float16, device=dev) for _ in range(nlayers)]
+        vc = [torch.zeros(S, nkv, ctx, head_dim, dtype=torch.float16, device=dev) for _ in range(nlayers)]
+        rs = qp.RaggedStep(layers, embed, norm, lm_head, kc, vc, inv_freq, rows=128, segments=S)
+        pf = qp.Prefill(layers, embed, norm, lm_head, kc, vc, inv_freq, chunk=args.chunk)
+        g = torch.Generator().manual_seed(args.seed)
+        prompts = [torch.randint(0, args.vocab, (N,), generator=g).to(dev) for _ in range(S)]
+        packed = rs.pack([(b, prompts[b], 0) for b in range(S)])
+        toks_r = rs(*packed).tolist()
+        toks_p = [int(pf(prompts[b], slot=b, pos0=0)) for b in range(S)]
+        out = {"what": "S prompts of N tokens: one RaggedStep vs S Prefill calls (graph replays, same call)", "model": args.model,
+               "layers": nlayers, "quantizer": args.qdict or args.quantizer, "context": ctx, "S": S, "N": N,
+               "next_tokens_agree": toks_r == toks_p, "ms_ragged_step": None, "ms_prefill_calls": None}
+        if not args.no_time:
+            out["ms_ragged_step"] = time_graph(lambda: rs(*packed), args.iters, dev)
+            out["ms_prefill_calls"] = time_graph(lambda: [pf(prompts[b], slot=b, pos0=0) for b in range(S)], args.iters, dev)
+        if not quiet:
+            print(json.dumps(out))
+        return out
     ar = torch.arange(ctx, device=dev)
     cg = torch.Generator(device=dev).manual_seed(args.seed)
     kc = [(torch.randn(B, nkv, ctx, head_dim, device=dev, generator=cg) * 0.5).half() for _ in range(nlayers)]

@@ -11,11 +11,14 @@ Layout:
   linear/incoherent_linear.py  IncoherentLinear / IncoherentMLP / IncoherentSdpaAttention (lib/linear/incoherent_linear.py)
   attention.py     decode_attention / attention_workspace: rope + KV append + GQA attention of B sequences, one launch;
                    prefill_attention / prefill_workspace: the same for up to 128 new tokens of one sequence, causal;
-                   paged_decode_attention / paged_prefill_attention: both on page pools behind a block table
+                   paged_decode_attention / paged_prefill_attention: both on page pools behind a block table;
+                   ragged_prefill_attention / paged_ragged_prefill_attention / ragged_workspace: up to 128 rows of SEVERAL
+                   sequences in one launch (segments described on the device)
   paging.py        PagedKVCache: per-layer page pools, the block table and the host-side page allocator (reserve / release / fork)
   decoder.py       DecodeStep: the whole-model decode step at batch B >= 1 on the kernels above (per-layer launch sequence,
                    scratch buffers, final norm + lm_head + argmax, launches per token); Prefill: a prompt into one cache slot;
-                   Score: the log-probability of every next token of a sequence, nll and perplexity
+                   Score: the log-probability of every next token of a sequence, nll and perplexity;
+                   RaggedStep: prompt chunks and decode tokens of several slots in ONE 128-row step
   sampling.py      lm_head_logits (final norm + lm_head for up to 128 rows), sample / Sampler (temperature, top-k, top-p, seeded
                    draw; per-slot parameters on the device), reference_draw (the draw's contract in numpy fp64);
                    token_logprobs (log softmax of a row at one token, csrc/logprob.hip) and its contract reference_logprob
@@ -54,12 +57,13 @@ from . import quantize_layer  # noqa: F401
 from . import attention  # noqa: F401
 from .attention import attention_workspace, decode_attention, prefill_attention, prefill_workspace  # noqa: F401
 from .attention import paged_decode_attention, paged_prefill_attention  # noqa: F401
+from .attention import paged_ragged_prefill_attention, ragged_prefill_attention, ragged_workspace  # noqa: F401
 from . import paging  # noqa: F401
 from .paging import PagedKVCache  # noqa: F401
 from . import sampling  # noqa: F401
 from .sampling import Sampler, lm_head_logits, reference_draw, reference_logprob, sample, token_logprobs  # noqa: F401
 from . import decoder  # noqa: F401
-from .decoder import DecodeStep, Prefill, Score, perplexity  # noqa: F401
+from .decoder import DecodeStep, Prefill, RaggedStep, Score, perplexity  # noqa: F401
 from .quantize_layer import incoherent_preprocess, layer_file_path, load_hessian, quantize_linear  # noqa: F401
 
 __version__ = "0.1.0"

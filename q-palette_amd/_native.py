@@ -74,6 +74,11 @@ _SIGNATURES = {
                                           _I, _I, _I, _I, _F, _P, ctypes.c_long, _P],
     "qpal_attn_rope_prefill_paged": [_P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _P, _P, _I, _I, _I, _I,
                                      _I, _I, _I, _I, _F, _P, ctypes.c_long, _P],
+    "qpal_attn_ragged_ws_bytes": [_I, _I, _I, _I, _I, ctypes.c_long],
+    "qpal_attn_rope_prefill_ragged": [_P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I,
+                                      ctypes.c_long, _F, _P, ctypes.c_long, _P],
+    "qpal_attn_rope_prefill_ragged_paged": [_P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _P, _P, _P, _P, ctypes.c_long, _I,
+                                            _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, ctypes.c_long, _P],
     "qpal_lm_head_argmax": [_P, _P, _F, _P, _P, _P, _P, ctypes.c_long, _I, _I, _P],
     "qpal_lm_head_ws_bytes": [_I],
     "qpal_lm_head_logits": [_P, ctypes.c_long, _P, _F, _P, _P, ctypes.c_long, _I, _I, _I, _P],
@@ -124,6 +129,7 @@ def lib():
         l.qpal_attn_ws_bytes.restype = ctypes.c_long
         l.qpal_attn_batch_ws_bytes.restype = ctypes.c_long
         l.qpal_attn_prefill_ws_bytes.restype = ctypes.c_long
+        l.qpal_attn_ragged_ws_bytes.restype = ctypes.c_long
         l.qpal_lm_head_ws_bytes.restype = ctypes.c_long
         l.qpal_tcq_viterbi_ws_bytes.restype = ctypes.c_long
         _lib = l

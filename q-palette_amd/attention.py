@@ -25,6 +25,13 @@ the workspaces of that max_len serve the paged launches, and the result is bit f
 
     out = paged_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, ws=ws)
     out = paged_prefill_attention(q, k, v, kpool, vpool, block_table[b], pos0, inv_freq, ws=ws)
+
+Ragged prefill (``qpal_attn_rope_prefill_ragged`` / ``_paged``, csrc/attn_ragged.hip): up to 128 rows of SEVERAL
+sequences in one launch — prompt chunks and decode tokens side by side — cut into segments that three device tensors describe.
+
+    ws = ragged_workspace(128, S, nq, nkv, hd, max_len, device)
+    out = ragged_prefill_attention(q, k, v, kcache, vcache, seq, row0, pos0, inv_freq, ws=ws)
+    out = paged_ragged_prefill_attention(q, k, v, kpool, vpool, block_table, seq, row0, pos0, inv_freq, ws=ws)
 """
 import math
 
@@ -166,8 +173,9 @@ def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=N
     return _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, None)
 
 
-def _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, paged):
-    """the checks and the launch both prefill entry points share; paged: None, or the arguments that take max_len's place"""
+def _prefill_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos0=None):
+    """the checks of q / k / v / inv_freq / out every prefill launch shares, and of the one-sequence launches' pos0 where one is
+    given; returns (T, nq, ld_qkv, out, ld_out)"""
     if q.dim() != 2 or not 1 <= q.shape[0] <= 128 or q.shape[1] % hd:
         raise QpalError(f"{who}: q must have shape [T, nq*{hd}] with 1 <= T <= 128, got {list(q.shape)}")
     T, nq = q.shape[0], q.shape[1] // hd
@@ -175,7 +183,7 @@ def _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws
     for name, t in (("k", k), ("v", v)):
         if _rows(t, name, T, nkv * hd, who) != ld and T > 1:
             raise QpalError(f"{who}: q, k and v must share one row stride")
-    if pos0.dtype != torch.int64 or pos0.numel() != 1 or pos0.device != kcache.device:
+    if pos0 is not None and (pos0.dtype != torch.int64 or pos0.numel() != 1 or pos0.device != kcache.device):
         raise QpalError(f"{who}: pos0 must be an int64 tensor of one element on {kcache.device}")
     if inv_freq.dtype != torch.float32 or inv_freq.numel() != hd // 2 or inv_freq.device != kcache.device or not inv_freq.is_contiguous():
         raise QpalError(f"{who}: inv_freq must be a contiguous fp32 [{hd // 2}] tensor on {kcache.device}")
@@ -185,21 +193,31 @@ def _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws
         out = torch.empty(T, nq * hd, dtype=torch.float16, device=kcache.device)
     elif out.dtype != torch.float16 or out.dim() != 2 or out.shape != (T, nq * hd) or out.stride(1) != 1 or out.device != kcache.device:
         raise QpalError(f"{who}: out must be fp16 [{T}, {nq * hd}] with contiguous rows on {kcache.device}")
-    ld_out = out.stride(0) if T > 1 else nq * hd
+    return T, nq, ld, out, out.stride(0) if T > 1 else nq * hd
+
+
+def _prefill_ws(who, need, ws, kcache, maker):
+    """(pointer, bytes) of the workspace a launch that needs `need` bytes is given"""
+    if need <= 0:
+        return None, 0
+    if ws is None:
+        raise QpalError(f"{who}: this shape needs a workspace ({maker}(...))")
+    if ws.device != kcache.device or ws.numel() * ws.element_size() < need or not ws.is_contiguous():
+        raise QpalError(f"{who}: ws must be a contiguous device buffer of >= {need} bytes on {kcache.device}")
+    return ws.data_ptr(), ws.numel() * ws.element_size()
+
+
+def _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, paged):
+    """the checks and the launch both prefill entry points share; paged: None, or the arguments that take max_len's place"""
+    T, nq, ld, out, ld_out = _prefill_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos0)
     lib = _native.lib()
-    need = lib.qpal_attn_prefill_ws_bytes(T, nq, nkv, hd, max_len)
-    if need > 0:
-        if ws is None:
-            raise QpalError(f"{who}: this shape needs a workspace (prefill_workspace(...))")
-        if ws.device != kcache.device or ws.numel() * ws.element_size() < need or not ws.is_contiguous():
-            raise QpalError(f"{who}: ws must be a contiguous device buffer of >= {need} bytes on {kcache.device}")
+    ws_ptr, ws_bytes = _prefill_ws(who, lib.qpal_attn_prefill_ws_bytes(T, nq, nkv, hd, max_len), ws, kcache, "prefill_workspace")
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
     with torch.cuda.device(kcache.device):
         rc = getattr(lib, entry)(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
             pos0.data_ptr(), inv_freq.data_ptr(), *((T, nq, nkv, hd, max_len) if paged is None else paged + (T, nq, nkv, hd)), scale,
-            ws.data_ptr() if need > 0 else None, ws.numel() * ws.element_size() if need > 0 else 0,
-            torch.cuda.current_stream(kcache.device).cuda_stream)
+            ws_ptr, ws_bytes, torch.cuda.current_stream(kcache.device).cuda_stream)
     _native.check(rc, entry)
     return out
 
@@ -260,3 +278,87 @@ def paged_prefill_attention(q, k, v, kpool, vpool, block_row, pos0, inv_freq, sc
     paged = (block_row.data_ptr(), num_pages, page_size, max_pages, _KV_FMT[kpool.dtype])
     return _prefill(who, "qpal_attn_rope_prefill_paged", q, k, v, kpool, vpool, pos0, inv_freq, scale, out, ws, nkv,
                     max_pages * page_size, hd, paged)
+
+
+def ragged_workspace(R, S, nq, nkv, hd, max_len, device):
+    """The zero-filled workspace ``ragged_prefill_attention`` needs for launches of up to R rows in up to S segments on caches of
+    up to max_len positions (same nq, nkv, hd), or None where no launch of that shape needs one (max_len < 512).  Keep it across
+    launches: every launch leaves its tickets at zero, and they sit at a fixed offset, so launches of fewer rows, fewer segments
+    or a shorter cache may share it in any order.  It is laid out for ragged launches: a prefill_workspace does not stand in."""
+    n = _native.lib().qpal_attn_ragged_ws_bytes(int(R), int(S), int(nq), int(nkv), int(hd), int(max_len))
+    if n <= 0:
+        return None
+    return torch.zeros((n + 3) // 4, dtype=torch.float32, device=device)
+
+
+def _segments(who, seq, row0, pos0, dev):
+    """the checks of the three segment descriptors; returns S"""
+    if seq.dtype != torch.int32 or seq.dim() != 1 or not 1 <= seq.shape[0] <= 128 or not seq.is_contiguous():
+        raise QpalError(f"{who}: seq must be a contiguous int32 [S] tensor with 1 <= S <= 128, got {seq.dtype} {list(seq.shape)}")
+    S = seq.shape[0]
+    if row0.dtype != torch.int32 or row0.shape != (S + 1,) or not row0.is_contiguous():
+        raise QpalError(f"{who}: row0 must be a contiguous int32 [{S + 1}] tensor, got {row0.dtype} {list(row0.shape)}")
+    if pos0.dtype != torch.int64 or pos0.shape != (S,) or not pos0.is_contiguous():
+        raise QpalError(f"{who}: pos0 must be a contiguous int64 [{S}] tensor, got {pos0.dtype} {list(pos0.shape)}")
+    for name, t in (("seq", seq), ("row0", row0), ("pos0", pos0)):
+        if t.device != dev:
+            raise QpalError(f"{who}: {name} must be on the caches' device {dev}, got {t.device}")
+    return S
+
+
+def _ragged(who, entry, q, k, v, kcache, vcache, seq, row0, pos0, S, inv_freq, scale, out, ws, B, nkv, max_len, hd, head, tail):
+    """the checks (behind _segments, which gave S) and the launch both ragged entry points share; head / tail: the arguments in
+    front of and behind (R, S, B, nq, nkv, hd)"""
+    R, nq, ld, out, ld_out = _prefill_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd)
+    lib = _native.lib()
+    ws_ptr, ws_bytes = _prefill_ws(who, lib.qpal_attn_ragged_ws_bytes(R, S, nq, nkv, hd, max_len), ws, kcache, "ragged_workspace")
+    scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
+    with torch.cuda.device(kcache.device):
+        rc = getattr(lib, entry)(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
+            seq.data_ptr(), row0.data_ptr(), pos0.data_ptr(), inv_freq.data_ptr(), *head, R, S, B, nq, nkv, hd, *tail, scale,
+            ws_ptr, ws_bytes, torch.cuda.current_stream(kcache.device).cuda_stream)
+    _native.check(rc, entry)
+    return out
+
+
+def ragged_prefill_attention(q, k, v, kcache, vcache, seq, row0, pos0, inv_freq, scale=None, out=None, ws=None):
+    """prefill_attention for rows of SEVERAL sequences in one launch (``qpal_attn_rope_prefill_ragged``).  q fp32 [R,
+    nq*hd], k / v fp32 [R, nkv*hd], 1 <= R <= 128 (strided rows as for prefill_attention); kcache / vcache [B, nkv, max_len, hd],
+    fp16 or float8_e4m3fn, contiguous, 16-byte aligned.  The rows are cut into S <= 128 segments described ON THE DEVICE (never read
+    by the host: a captured launch can be replayed while they change): seq int32 [S], row0 int32 [S + 1] (cumulative, row0[0] = 0),
+    pos0 int64 [S] — segment s is rows row0[s] .. row0[s + 1] - 1, the tokens of sequence seq[s] at positions pos0[s] ...  Per
+    segment the launch does what prefill_attention does for those rows on kcache[seq[s]]: rotary embedding, append, causal
+    attention over that sequence only.  A decode token is a segment of one row.
+
+    A segment with no rows, row0[s + 1] > R, seq[s] outside [0, B), pos0[s] < 0 or pos0[s] + rows > max_len is inactive: no cache
+    byte and no out byte is written for it; out rows of no active segment keep what they held.  Two active segments naming one
+    sequence: the caller's error, that sequence's result is unspecified.  ws: ragged_workspace(R, S, ...)."""
+    who = "ragged_prefill_attention"
+    if kcache.dim() != 4 or kcache.shape != vcache.shape:
+        raise QpalError(f"{who}: kcache / vcache must both have shape [B, nkv, max_len, hd]")
+    B, nkv, max_len, hd = kcache.shape
+    S = _segments(who, seq, row0, pos0, kcache.device)  # (first: these checks need no device)
+    _cache_entry(kcache, vcache, who)
+    return _ragged(who, "qpal_attn_rope_prefill_ragged", q, k, v, kcache, vcache, seq, row0, pos0, S, inv_freq, scale, out, ws, B,
+                   nkv, max_len, hd, (_KV_FMT[kcache.dtype],), (max_len,))
+
+
+def paged_ragged_prefill_attention(q, k, v, kpool, vpool, block_table, seq, row0, pos0, inv_freq, scale=None, out=None, ws=None):
+    """ragged_prefill_attention on a paged cache (``qpal_attn_rope_prefill_ragged_paged``): the pools and the block table int32 [B,
+    max_pages] of paged_decode_attention; segment s uses row seq[s] of the table.  Every rule is ragged_prefill_attention's with
+    max_len = max_pages * page_size (ws: ragged_workspace of that max_len); bit for bit that launch's result on the gathered cache.
+    Only entries that cover positions 0 .. pos0[s] + rows - 1 of an active segment are read; the guard on entries outside [0,
+    num_pages) is paged_decode_attention's."""
+    who = "paged_ragged_prefill_attention"
+    S = _segments(who, seq, row0, pos0, kpool.device)
+    num_pages, nkv, page_size, hd = _pools(kpool, vpool, block_table, who)
+    if block_table.dim() != 2 or block_table.shape[1] < 1:
+        raise QpalError(f"{who}: block_table must have shape [B, max_pages >= 1], got {list(block_table.shape)}")
+    B, max_pages = block_table.shape
+    ld_table = block_table.stride(0) if B > 1 else max_pages
+    if ld_table < max_pages:
+        raise QpalError(f"{who}: the block table's row stride must be at least max_pages")
+    head = (block_table.data_ptr(), ld_table, num_pages, page_size, max_pages, _KV_FMT[kpool.dtype])
+    return _ragged(who, "qpal_attn_rope_prefill_ragged_paged", q, k, v, kpool, vpool, seq, row0, pos0, S, inv_freq, scale, out, ws, B,
+                   nkv, max_pages * page_size, hd, head, ())

@@ -1,0 +1,108 @@
+// Ragged prefill attention (qpal_attn_rope_prefill_ragged, qpal_attn_rope_prefill_ragged_paged): ONE launch for R
+// <= 128 rows of q | k | v cut into S <= 128 segments, segment s = rows row0[s] .. row0[s + 1] - 1 of sequence seq[s] at positions
+// pos0[s] ..  Per segment the launch is attn_prefill.hip's launch of T = row0[s + 1] - row0[s] rows on that sequence's cache: the
+// same body (attn_prefill.h), with the per-sequence values — pos0, T, the q / k / v / out row base, the cache base or the block-
+// table row — found per workgroup instead of read from the arguments.
+//
+// seq, row0 and pos0 live on the device and the host never reads them: the grid is fixed from (R, S, heads, max_len).  A query
+// tile never straddles two segments (tile j of a segment starts at its row j * TQ), so a launch has at most ntile = min(R, (R +
+// S (TQ - 1)) / TQ) tiles per kv head, and workgroup (kv head, tile jg, chunk) finds the segment that holds tile jg: thread s counts
+// the tiles of segment s (none if it is inactive), sums the counts before it out of LDS, and the one thread whose range holds jg
+// publishes (s, jg - first tile of s).  No such segment: the workgroup leaves.  Tickets and partials are indexed by (kv head, jg);
+// the tickets sit at kh * 128 + jg in front of the partials, whatever this launch's ntile, so that one zero-filled workspace serves
+// launches of different (R, S): every launch finds every ticket word at zero and leaves it there.
+#include "attn_prefill.h"
+
+namespace qpal {
+
+namespace {
+
+// Launch geometry from (R, S, heads, max_len) only: ntile bounds the sum over segments of ceil(T_s / TQ) for segments that share R
+// rows; chunks and workspace by prefill_split with nkv * kPfRaggedTiles tickets.  ws_bytes is monotone in R, S and max_len.
+int ragged_geometry(int R, int S, int nq, int nkv, int hd, long max_len, PrefillGeometry &g) {
+    g = PrefillGeometry{0, 0, 0};
+    const int rc = prefill_shape(R, nq, nkv, hd, max_len);
+    if (rc != QPAL_OK) return rc;
+    if (S < 1 || S > kPfMaxT) return QPAL_E_SHAPE;
+    const int tq = 16 * pf_qs(nq / nkv);
+    const long bound = ((long)R + (long)S * (tq - 1)) / tq, ntile = bound < R ? bound : R;
+    prefill_split(ntile, (long)nkv * kPfRaggedTiles, nq, nkv, hd, max_len, g);
+    return QPAL_OK;
+}
+
+template <class CT, bool PAGED>
+int attn_rope_ragged(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16, long ld_out,
+                     const int *seq, const int *row0, const long *pos0, const float *inv_freq, int R, int S, int B, int nq, int nkv, int hd,
+                     long max_len, float scale, void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0) {
+    PrefillGeometry g;
+    int rc = ragged_geometry(R, S, nq, nkv, hd, max_len, g);
+    if (rc != QPAL_OK) return rc;
+    if (B < 1) return QPAL_E_SHAPE;
+    rc = prefill_args(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, nq, hd, g, ws, ws_bytes, PAGED ? pg->table : nullptr);
+    if (rc != QPAL_OK) return rc;
+    if ((reinterpret_cast<uintptr_t>(seq) | reinterpret_cast<uintptr_t>(row0)) & 3) return QPAL_E_ALIGN;
+    float *wsf = static_cast<float *>(ws);
+    AttnRaggedParams<CT> p{};
+    static_cast<AttnPrefillParams<CT> &>(p) = AttnPrefillParams<CT>{
+        q, k, v, ld_qkv, static_cast<CT *>(kcache), static_cast<CT *>(vcache), static_cast<uint16_t *>(out_f16), ld_out, pos0, inv_freq,
+        R, nkv, max_len, scale, g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr,
+        g.ws_bytes ? wsf + (long)nkv * kPfRaggedTiles : nullptr, g.nsplit, g.ntile};
+    p.seq = seq, p.row0 = row0, p.S = S, p.B = B;
+    if constexpr (PAGED) p.table = pg->table, p.num_pages = pg->num_pages, p.page_shift = shift, p.ld_table = pg->ld_table;
+    const int grid = nkv * g.ntile * g.nsplit, rep = nq / nkv;
+#define QPAL_RAGGED(HD_, REP_)                                                                                                     \
+    if (hd == HD_ && rep == REP_) {                                                                                                \
+        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, true, HD_, REP_>), dim3(grid), dim3(64 * REP_ * pf_qs(REP_)), 0,               \
+                           static_cast<hipStream_t>(stream), p);                                                                   \
+        return (int)hipGetLastError();                                                                                             \
+    }
+    QPAL_RAGGED(64, 1) QPAL_RAGGED(64, 2) QPAL_RAGGED(64, 4) QPAL_RAGGED(64, 8)
+    QPAL_RAGGED(128, 1) QPAL_RAGGED(128, 2) QPAL_RAGGED(128, 4) QPAL_RAGGED(128, 8)
+    QPAL_RAGGED(256, 1) QPAL_RAGGED(256, 2) QPAL_RAGGED(256, 4)
+#undef QPAL_RAGGED
+    return QPAL_E_SHAPE;
+}
+
+}  // namespace
+
+}  // namespace qpal
+
+using namespace qpal;
+
+extern "C" long qpal_attn_ragged_ws_bytes(int R, int S, int nq, int nkv, int hd, long max_len) {
+    PrefillGeometry g;
+    if (ragged_geometry(R, S, nq, nkv, hd, max_len, g) != QPAL_OK) return 0;
+    return (long)g.ws_bytes;
+}
+
+extern "C" int qpal_attn_rope_prefill_ragged(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache,
+                                             void *out_f16, long ld_out, const int *seq, const int *row0, const long *pos0,
+                                             const float *inv_freq, int kv_fmt, int R, int S, int B, int nq, int nkv, int hd, long max_len,
+                                             float scale, void *ws, long ws_bytes, void *stream) {
+    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !seq || !row0 || !pos0 || !inv_freq) return QPAL_E_NULL;
+    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
+    if (kv_fmt == 1)
+        return attn_rope_ragged<uint8_t, false>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B, nq, nkv,
+                                                hd, max_len, scale, ws, ws_bytes, stream);
+    return attn_rope_ragged<uint16_t, false>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B, nq, nkv, hd,
+                                             max_len, scale, ws, ws_bytes, stream);
+}
+
+extern "C" int qpal_attn_rope_prefill_ragged_paged(const float *q, const float *k, const float *v, long ld_qkv, void *kpool, void *vpool,
+                                                   void *out_f16, long ld_out, const int *seq, const int *row0, const long *pos0,
+                                                   const float *inv_freq, const int *block_table, long ld_table, int num_pages,
+                                                   int page_size, int max_pages, int kv_fmt, int R, int S, int B, int nq, int nkv, int hd,
+                                                   float scale, void *ws, long ws_bytes, void *stream) {
+    if (!block_table) return QPAL_E_NULL;
+    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
+    int shift;
+    long max_len;
+    if (!q || !k || !v || !kpool || !vpool || !out_f16 || !seq || !row0 || !pos0 || !inv_freq) return QPAL_E_NULL;
+    const int rc = paged_shape(pg, kv_fmt, shift, max_len);
+    if (rc != QPAL_OK) return rc;
+    if (kv_fmt == 1)
+        return attn_rope_ragged<uint8_t, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B, nq, nkv, hd,
+                                               max_len, scale, ws, ws_bytes, stream, &pg, shift);
+    return attn_rope_ragged<uint16_t, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B, nq, nkv, hd,
+                                            max_len, scale, ws, ws_bytes, stream, &pg, shift);
+}

@@ -30,7 +30,13 @@ in chunks of at most 128 rows, with `prefill_attention` (causal, rows appended t
     lp = sc(tokens, slot=0, pos0=0)         # fp32 [N - 1]: lp[t] = log p(tokens[t + 1] | tokens[0 .. t])
     ppl, loss = perplexity(sc, windows)     # windows int64 [W, N]
 
-All three take `block_table=` for a paged cache (paging.PagedKVCache): kcache / vcache are then the per-layer page
+`RaggedStep` puts rows of SEVERAL slots into one step of up to 128 rows — prompt chunks of some, one decode token of others — with
+`ragged_prefill_attention` in the attention's place and one next token per segment.
+
+    rs = RaggedStep(layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=128, segments=16)
+    next_toks = rs(*rs.pack([(slot, tokens_1d, pos0), ...]))    # int64 [segments]; capturable with the four tensors rewritten
+
+All of them take `block_table=` for a paged cache (paging.PagedKVCache): kcache / vcache are then the per-layer page
 pools [num_pages, nkv, page_size, hd], the table is int32 [B, max_pages], and context = max_pages * page_size.  The caller reserves
 pages for every position a call, or a run of graph replays, will reach before it starts: nothing in here allocates or synchronises.
 """
@@ -41,8 +47,8 @@ import torch
 from . import _native as nat
 from . import hadamard as had
 from . import linear, ops, sampling
-from .attention import (attention_workspace, decode_attention, paged_decode_attention, paged_prefill_attention, prefill_attention,
-                        prefill_workspace)
+from .attention import (attention_workspace, decode_attention, paged_decode_attention, paged_prefill_attention,
+                        paged_ragged_prefill_attention, prefill_attention, prefill_workspace, ragged_prefill_attention, ragged_workspace)
 from .linear import multi_gemv
 
 
@@ -424,6 +430,125 @@ class Score(Prefill):
     def nll(self, tokens, slot=0, pos0=0):
         """device scalar (fp64): the mean of -lp over the N - 1 predicted tokens — the cross-entropy loss of one window"""
         return -self(tokens, slot=slot, pos0=pos0).double().mean()
+
+
+class RaggedStep(DecodeStep):
+    """ONE step on `rows` <= 128 rows that belong to up to `segments` <= 128 slots of the caches a DecodeStep is built on: segment s
+    is rows row0[s] .. row0[s + 1] - 1, the tokens of slot seq[s] at positions pos0[s] .. (a prompt chunk; one row: a decode token).
+    DecodeStep's batch-B layer on all rows with `ragged_prefill_attention` in the attention's place, then per segment the final
+    norm and lm_head of its LAST row and one draw.
+
+        out_tok = rs(tokens, seq, row0, pos0)   # tokens int64 [rows], seq int32 [segments], row0 int32 [segments + 1], pos0 int64
+                                                # [segments], all on the device; returns rs.out_tok int64 [segments]
+
+    Nothing in a call reads the device or synchronises: it can be captured, and the four tensors rewritten between replays.  The
+    segment rules are ragged_prefill_attention's; an inactive segment keeps its out_tok.  Rows that belong to no segment are
+    computed by the linears and ignored: their tokens must be valid ids.  Two active segments of one slot are the caller's error.
+
+    sampler: the sampling.Sampler of the caches' slots; segment s draws with slot seq[s]'s parameters (gathered on the device into
+    rs.draw, a Sampler of `segments` rows the step owns) and the counter of its last row's position, pos0[s] + rows of s - 1 —
+    the draw Prefill or DecodeStep would have made.  None: argmax.  rs.draw.logits [segments, vocab] holds the logits, and with a
+    sampler built with logprobs=True rs.draw.logprob the drawn tokens' log-probabilities.
+
+    block_table: int32 [B, max_pages] — a paged cache, as for DecodeStep; the caller has reserved the pages of every position the
+    step writes."""
+
+    def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=128, segments=16, sampler=None, block_table=None):
+        if not 1 <= int(rows) <= 128 or not 1 <= int(segments) <= 128:
+            raise nat.QpalError(f"RaggedStep: rows and segments must be in 1 .. 128, got {rows}, {segments}")
+        if block_table is not None and block_table.dim() != 2:
+            raise nat.QpalError(f"RaggedStep: block_table must be int32 [B, max_pages], got {list(block_table.shape)}")
+        self.rows, self.segments, self.batch1, self.block_table = int(rows), int(segments), False, block_table
+        self.slots = kcache[0].shape[0] if block_table is None else block_table.shape[0]  # sequences of the caches
+        self.sampler = self._check_sampler(sampler, self.slots, embed, lm_head)
+        self._check_lm_head("RaggedStep", embed, lm_head)
+        self._setup_rows(layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.rows)
+        dev, S = embed.device, self.segments
+        self.seq = self.row0 = self.pos0 = None  # the descriptors of the call under way
+        self.out_tok = torch.zeros(S, dtype=torch.int64, device=dev)
+        self.ctr = torch.full((S,), -1, dtype=torch.int64, device=dev)  # the last row's position; -1: the segment is inactive
+        self._inactive = torch.full((S,), -1, dtype=torch.int64, device=dev)
+        self.last32 = torch.zeros(S, self.h32.shape[1], dtype=torch.float32, device=dev)  # each segment's last row of the stream
+        # the draw's per-segment parameters: greedy, or gathered from the sampler's slots seq[s] in every call
+        self.draw = sampling.Sampler(S, lm_head.shape[0], dev, temperature=0.0,
+                                     logprobs=sampler is not None and sampler.logprob is not None)
+        self.attn_ws = ragged_workspace(self.rows, S, self.nq, self.nkv, self.head_dim, self.context, dev)
+
+    @property
+    def launches_per_token(self):
+        raise nat.QpalError("RaggedStep: launches are per step (9 per layer), not per token")
+
+    def _attention(self, i, q, k, v):
+        scale = 1.0 / math.sqrt(self.head_dim)
+        if self.block_table is not None:
+            paged_ragged_prefill_attention(q, k, v, self.kcache[i], self.vcache[i], self.block_table, self.seq, self.row0, self.pos0,
+                                           self.inv_freq, scale=scale, out=self.a16, ws=self.attn_ws)
+            return
+        ragged_prefill_attention(q, k, v, self.kcache[i], self.vcache[i], self.seq, self.row0, self.pos0, self.inv_freq, scale=scale,
+                                 out=self.a16, ws=self.attn_ws)
+
+    def hidden(self):
+        """fp16 [segments, H]: the final norm of each segment's last row (rows of inactive segments mean nothing)"""
+        return self.norm(self.last32.half())
+
+    @staticmethod
+    def pack_host(items, rows, segments, slots, context):
+        """pack's checks and layout on the host: (tokens int64 [rows], seq int32 [segments], row0 int32 [segments + 1], pos0 int64
+        [segments]) as CPU tensors.  Unused rows hold token 0; unused segments have no rows and seq = -1."""
+        if len(items) > segments:
+            raise nat.QpalError(f"RaggedStep.pack: {len(items)} items, built for {segments} segments")
+        tokens = torch.zeros(rows, dtype=torch.int64)
+        seq = torch.full((segments,), -1, dtype=torch.int32)
+        row0 = torch.zeros(segments + 1, dtype=torch.int32)
+        pos0 = torch.zeros(segments, dtype=torch.int64)
+        at, seen = 0, set()
+        for s, (slot, toks, p0) in enumerate(items):
+            slot, p0 = int(slot), int(p0)
+            if toks.dim() != 1 or toks.shape[0] < 1 or toks.dtype != torch.int64:
+                raise nat.QpalError(f"RaggedStep.pack: item {s}: tokens must be int64 [n >= 1]")
+            n = toks.shape[0]
+            if not 0 <= slot < slots or slot in seen:
+                raise nat.QpalError(f"RaggedStep.pack: item {s}: slot {slot} is outside the caches' {slots} sequences or named twice")
+            if p0 < 0 or p0 + n > context:
+                raise nat.QpalError(f"RaggedStep.pack: item {s}: {n} tokens from position {p0} do not fit a cache of {context} positions")
+            if at + n > rows:
+                raise nat.QpalError(f"RaggedStep.pack: {at + n} rows and more, built for {rows}")
+            seen.add(slot)
+            tokens[at:at + n] = toks.cpu()
+            seq[s], pos0[s] = slot, p0
+            at += n
+            row0[s + 1] = at
+        row0[len(items) + 1:] = at
+        return tokens, seq, row0, pos0
+
+    def pack(self, items):
+        """[(slot, tokens int64 [n], pos0), ...] -> (tokens, seq, row0, pos0) on the device, padded to rows / segments: the arguments
+        of a call.  Checked on the host: distinct slots of the caches, at most `segments` items and `rows` rows, every item inside
+        the cache.  A host convenience (it copies to the device): not part of a captured step."""
+        return tuple(t.to(self.embed.device) for t in self.pack_host(items, self.rows, self.segments, self.slots, self.context))
+
+    def __call__(self, tokens, seq, row0, pos0):
+        dev, S = self.embed.device, self.segments
+        for name, t, dtype, n in (("tokens", tokens, torch.int64, self.rows), ("seq", seq, torch.int32, S),
+                                  ("row0", row0, torch.int32, S + 1), ("pos0", pos0, torch.int64, S)):
+            if t.dtype != dtype or t.shape != (n,) or t.device != dev or not t.is_contiguous():
+                raise nat.QpalError(f"RaggedStep: {name} must be a contiguous {dtype} [{n}] tensor on {dev}")
+        self.seq, self.row0, self.pos0 = seq, row0, pos0
+        self.h32.copy_(self.embed[tokens])
+        for i in range(len(self.layers)):
+            self._layer(i)
+        # ---- the tail, on the device: which segments are active (the kernel's rules), their last rows and counters
+        first, end = row0[:-1], row0[1:]
+        n = (end - first).to(torch.int64)
+        active = (first >= 0) & (n > 0) & (end <= self.rows) & (seq >= 0) & (seq < self.slots) & (pos0 >= 0) & (pos0 + n <= self.context)
+        torch.where(active, pos0 + n - 1, self._inactive, out=self.ctr)
+        torch.index_select(self.h32, 0, (end.to(torch.int64) - 1).clamp(0, self.rows - 1), out=self.last32)
+        if self.sampler is not None:
+            slot = seq.to(torch.int64).clamp(0, self.slots - 1)
+            for name in ("temperature", "top_k", "top_p", "seed"):
+                torch.index_select(getattr(self.sampler, name), 0, slot, out=getattr(self.draw, name))
+        self._sample_tail(self.last32, self.draw, self.ctr, self.out_tok)
+        return self.out_tok
 
 
 def perplexity(score, windows, slot=0, out=None):
