@@ -481,6 +481,45 @@ int qpal_sample(const float *logits_f32, long ld_logits, int rows, int vocab, co
 int qpal_token_logprob(const float *logits_f32, long ld_logits, int rows, int vocab, const long long *token, float *logprob,
                        float *lse, int *rank, const long long *active, void *stream);
 
+/* SPECULATIVE decoding (csrc/spec.hip): the two ends of a step that feeds, per sequence, its pending token and up to
+ * K guessed tokens as ONE segment of a ragged step (§18), draws at every row, and keeps the guesses that equal the draws.
+ * Everything is on the device and never read by the host (a captured step is replayed while the state moves); no workspace, no
+ * global atomics, one writer per word: two launches on one state are bitwise equal.  State of slot b of B (1 .. 128):
+ *   hist int32 [B][ld_hist]  the tokens of the sequence          n_tok int64 [B]  how many are known; the last one, at position
+ *   limit int64 [B]          the bound n_tok may reach                            n_tok - 1, is PENDING: known, not yet fed
+ *   eos   int64 [B]          the stop token, -1: none
+ * Slot b is ACTIVE iff 1 <= n_tok[b] < limit[b], n_tok[b] <= max_len and n_tok[b] <= ld_hist.
+ *
+ * qpal_spec_draft builds the step's inputs.  K 0 .. 15, 1 <= gmin <= gmax <= 8, B <= R <= 128 (the step's rows), max_len >= 1 (cache
+ * positions), 1 <= ld_hist < 2^31.  For an active slot with n = n_tok[b]: d_max = max(0, min(K, limit - n - 1, max_len - n)).
+ *   ext_draft != NULL (int64 [B][K], ext_n int32 [B]): the drafts are ext_draft[b][0 .. min(ext_n[b], d_max)); an entry outside
+ *     [0, 2^30) ends them there.
+ *   ext_draft == NULL: prompt lookup.  For g = gmax down to gmin with g < n: the largest j with j + g < n and hist[j .. j + g) ==
+ *     hist[n - g .. n); the first g that has one gives the drafts hist[j + g .. min(j + g + d_max, n)); none: no drafts.
+ * Packing: segment b is slot b.  row0[0] = 0, row0[b + 1] = row0[b] + (active ? 1 + n_draft[b] : 0); every active slot has its one
+ * row (R >= B) and drafts are handed out in slot order until R is full: slot b keeps min(its drafts, R - (active slots) - (drafts
+ * kept by slots before it)).  Outputs: tokens int64 [R] (per segment the pending token, then its drafts; 0 in unused rows), seq int32
+ * [B] (b, or -1: inactive), row0 int32 [B + 1], pos0 int64 [B] = n_tok - 1 — the descriptors of qpal_attn_rope_prefill_ragged with S
+ * = B; row_slot int32 [R] (the slot of each row, -1: unused), row_ctr int64 [R] (the row's position = qpal_sample's ctr, -1: unused),
+ * n_draft int32 [B] (0: a plain decode token).  Two stream-ordered launches (search, pack); between them n_draft / pos0 hold the
+ * search's interim result.
+ *
+ * qpal_spec_accept takes drawn int64 [R] (the sampler's token per row) and tokens / seq / row0 as the draft call wrote them.  A
+ * segment counts iff seq[b] == b, it has T in 1 .. K + 1 rows inside [0, R] and 1 <= n_tok[b] < limit[b].  With r = row0[b]:
+ *   m = the largest value <= T - 1 with tokens[r + i + 1] == drawn[r + i] for all i < m           (the accepted drafts)
+ *   emitted = drawn[r .. r + m], cut to limit - n_tok tokens and after the first token equal to eos[b] when eos[b] >= 0
+ * The emitted tokens are appended to hist (a token that would land at or past ld_hist is emitted but not recorded; the slot is
+ * inactive from then on) and n_tok advances; an emitted eos sets limit[b] = n_tok[b].  out_tok int64 [B][K + 1]: the emitted tokens,
+ * entries past n_out keep what they held; n_out int32 [B] (>= 1; 0: the segment did not count, nothing else of it changes); n_acc
+ * int32 [B] = m before the cut.
+ * Codes are qpal_sample's: a null pointer (ext_draft may be NULL; then ext_n is ignored) QPAL_E_NULL; a range above QPAL_E_SHAPE;
+ * int32 arrays 4-byte, int64 arrays 8-byte aligned, else QPAL_E_ALIGN — all decided on the host before any stream work. */
+int qpal_spec_draft(const int *hist, long ld_hist, const long *n_tok, const long *limit, const long *ext_draft, const int *ext_n,
+                    int B, int K, int gmin, int gmax, int R, long max_len, long *tokens, int *seq, int *row0, long *pos0,
+                    int *row_slot, long *row_ctr, int *n_draft, void *stream);
+int qpal_spec_accept(const long *tokens, const long *drawn, const int *seq, const int *row0, int *hist, long ld_hist, long *n_tok,
+                     long *limit, const long *eos, int B, int K, int R, long *out_tok, int *n_out, int *n_acc, void *stream);
+
 /* The launch planner of the fused GEMV entry points, on its own (host code, no GPU call; what tests and tools inspect).
  * A launch of njobs jobs — rows[j] supertile rows (m / 32) of steps1[j] + steps2[j] steps (a step = 128 columns; steps2 = 0: one
  * stream) — is cut into workgroup-sized pieces: a GROUP of G = 1 << lg_g workgroups (`waves` = 16 or 8 waves each) owns rg

@@ -18,7 +18,10 @@ Layout:
   decoder.py       DecodeStep: the whole-model decode step at batch B >= 1 on the kernels above (per-layer launch sequence,
                    scratch buffers, final norm + lm_head + argmax, launches per token); Prefill: a prompt into one cache slot;
                    Score: the log-probability of every next token of a sequence, nll and perplexity;
-                   RaggedStep: prompt chunks and decode tokens of several slots in ONE 128-row step
+                   RaggedStep: prompt chunks and decode tokens of several slots in ONE 128-row step;
+                   SpeculativeStep: the pending token + guessed tokens of every slot in one step, several tokens out per slot
+  speculative.py   spec_draft / spec_accept (csrc/spec.hip): prompt-lookup drafts and the packing of a verify step, exact-match
+                   acceptance and the state update, all on the device; reference_spec_draft / reference_spec_accept: the contracts
   sampling.py      lm_head_logits (final norm + lm_head for up to 128 rows), sample / Sampler (temperature, top-k, top-p, seeded
                    draw; per-slot parameters on the device), reference_draw (the draw's contract in numpy fp64);
                    token_logprobs (log softmax of a row at one token, csrc/logprob.hip) and its contract reference_logprob
@@ -63,7 +66,9 @@ from .paging import PagedKVCache  # noqa: F401
 from . import sampling  # noqa: F401
 from .sampling import Sampler, lm_head_logits, reference_draw, reference_logprob, sample, token_logprobs  # noqa: F401
 from . import decoder  # noqa: F401
-from .decoder import DecodeStep, Prefill, RaggedStep, Score, perplexity  # noqa: F401
+from .decoder import DecodeStep, Prefill, RaggedStep, Score, SpeculativeStep, perplexity  # noqa: F401
+from . import speculative  # noqa: F401
+from .speculative import reference_spec_accept, reference_spec_draft, spec_accept, spec_draft  # noqa: F401
 from .quantize_layer import incoherent_preprocess, layer_file_path, load_hessian, quantize_linear  # noqa: F401
 
 __version__ = "0.1.0"

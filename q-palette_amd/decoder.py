@@ -36,6 +36,14 @@ in chunks of at most 128 rows, with `prefill_attention` (causal, rows appended t
     rs = RaggedStep(layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=128, segments=16)
     next_toks = rs(*rs.pack([(slot, tokens_1d, pos0), ...]))    # int64 [segments]; capturable with the four tensors rewritten
 
+`SpeculativeStep` is a RaggedStep whose segments are built on the device: per slot the pending token and up to `draft` guessed
+tokens (prompt lookup, or the caller's), a draw at every row, and the guesses that equal the draws kept — several tokens per slot
+and step, the same stream as one-token sampling.
+
+    ss = SpeculativeStep(layers, embed, norm, lm_head, kcache, vcache, inv_freq, draft=4, gram=(2, 4))
+    ss.begin(slot, tokens)                  # tokens[:-1] are in the cache, the last one is pending
+    out_tok, n_out = ss()                   # int64 [B, draft + 1], int32 [B]; capturable
+
 All of them take `block_table=` for a paged cache (paging.PagedKVCache): kcache / vcache are then the per-layer page
 pools [num_pages, nkv, page_size, hd], the table is int32 [B, max_pages], and context = max_pages * page_size.  The caller reserves
 pages for every position a call, or a run of graph replays, will reach before it starts: nothing in here allocates or synchronises.
@@ -549,6 +557,124 @@ class RaggedStep(DecodeStep):
                 torch.index_select(getattr(self.sampler, name), 0, slot, out=getattr(self.draw, name))
         self._sample_tail(self.last32, self.draw, self.ctr, self.out_tok)
         return self.out_tok
+
+
+class SpeculativeStep(RaggedStep):
+    """ONE step that can emit several tokens per slot: slot b feeds its pending token and up to `draft` guessed
+    tokens as one segment of a ragged step, every row draws the token the model would have drawn at its position, and the guesses
+    that equal the draws are kept — the first draw that differs is the correction, the draw after a fully accepted draft the bonus.
+    The stream of a slot is token for token what DecodeStep sampling emits on the same logits, greedy or seeded.
+
+        ss = SpeculativeStep(layers, embed, norm, lm_head, kcache, vcache, inv_freq, draft=4, gram=(2, 4))
+        ss.begin(slot, tokens, limit=len(tokens) + 64, eos=2)   # tokens[:-1] are in the cache (Prefill / RaggedStep); the last is pending
+        out_tok, n_out = ss()                                    # int64 [B, draft + 1], int32 [B]: out_tok[b, :n_out[b]] are new
+        out_tok, n_out = ss(ext_draft, ext_n)                    # the caller's drafts (int64 [B, draft], int32 [B]) instead of lookup
+
+    Without arguments the drafts are prompt lookup: the tokens that followed the most recent earlier occurrence of the last gram[1]
+    (down to gram[0]) tokens.  The step owns the state — hist int32 [B, history], n_tok / limit / eos int64 [B] — and ss.n_acc int32
+    [B], the accepted drafts of the last call.  A slot with n_tok >= limit (finished, released, never begun) has no rows.  Nothing
+    in a call reads the device: it can be captured, and `begin` / `release` (host conveniences, not part of a captured step) may
+    run between replays.
+
+    rows: the step's rows, B <= rows <= 128 (default min(128, B * (draft + 1))); drafts are cut where the rows are full.  sampler:
+    the sampling.Sampler of the caches' slots — row r draws with its slot's parameters (gathered into ss.draw, a Sampler of `rows`
+    rows) and the counter of its position; None: greedy.  A sampler built with logprobs=True: the call returns (out_tok, n_out,
+    logprob fp32 [B, draft + 1]), the emitted tokens' log-probabilities, from one token_logprobs launch on the rows.
+    No cache rollback: the next step starts at the new pending position and rewrites the K / V rows a rejected draft left before
+    anything reads them.  block_table: a paged cache as for DecodeStep; the caller has reserved the pages of min(limit, n_tok +
+    draft) positions of every slot before the call."""
+
+    def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, draft=4, gram=(2, 4), rows=None, sampler=None,
+                 block_table=None, history=None):
+        if block_table is not None and block_table.dim() != 2:
+            raise nat.QpalError(f"SpeculativeStep: block_table must be int32 [B, max_pages], got {list(block_table.shape)}")
+        self.slots = kcache[0].shape[0] if block_table is None else block_table.shape[0]
+        B, K = self.slots, int(draft)
+        if not 0 <= K <= 15 or len(gram) != 2 or not 1 <= int(gram[0]) <= int(gram[1]) <= 8:
+            raise nat.QpalError(f"SpeculativeStep: draft must be in 0 .. 15 and 1 <= gram[0] <= gram[1] <= 8, got {draft}, {gram}")
+        rows = min(128, B * (K + 1)) if rows is None else int(rows)
+        if not 1 <= B <= rows <= 128:
+            raise nat.QpalError(f"SpeculativeStep: rows must be in B = {B} .. 128, got {rows}")
+        self.draft_len, self.gram = K, (int(gram[0]), int(gram[1]))
+        self.rows, self.segments, self.batch1, self.block_table = rows, B, False, block_table
+        self.sampler = self._check_sampler(sampler, B, embed, lm_head)
+        self._check_lm_head("SpeculativeStep", embed, lm_head)
+        self._setup_rows(layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows)
+        dev = embed.device
+        self.history = self.context if history is None else int(history)
+        if self.history < 1:
+            raise nat.QpalError(f"SpeculativeStep: history must be at least 1, got {history}")
+        i32, i64 = torch.int32, torch.int64
+        self.hist = torch.zeros(B, self.history, dtype=i32, device=dev)
+        self.n_tok, self.limit = torch.zeros(B, dtype=i64, device=dev), torch.zeros(B, dtype=i64, device=dev)
+        self.eos = torch.full((B,), -1, dtype=i64, device=dev)
+        self.tokens, self.drawn = torch.zeros(rows, dtype=i64, device=dev), torch.zeros(rows, dtype=i64, device=dev)
+        self.seq, self.row0 = torch.full((B,), -1, dtype=i32, device=dev), torch.zeros(B + 1, dtype=i32, device=dev)
+        self.pos0 = torch.zeros(B, dtype=i64, device=dev)
+        self.row_slot, self.row_ctr = torch.full((rows,), -1, dtype=i32, device=dev), torch.full((rows,), -1, dtype=i64, device=dev)
+        self.n_draft, self.n_out, self.n_acc = (torch.zeros(B, dtype=i32, device=dev) for _ in range(3))
+        self.out_tok = torch.zeros(B, K + 1, dtype=i64, device=dev)
+        logprobs = sampler is not None and sampler.logprob is not None
+        self.draw = sampling.Sampler(rows, lm_head.shape[0], dev, temperature=0.0, logprobs=logprobs)  # greedy unless gathered
+        self.out_logprob = torch.zeros(B, K + 1, dtype=torch.float32, device=dev) if logprobs else None
+        self._lane = torch.arange(K + 1, dtype=i64, device=dev)
+        self._gather = torch.zeros(rows, dtype=i64, device=dev)  # the rows' embedding indices when the caller drafts
+        self.attn_ws = ragged_workspace(rows, B, self.nq, self.nkv, self.head_dim, self.context, dev)
+
+    def hidden(self):
+        """fp16 [rows, H]: the final norm of every row of the last step (rows of no segment mean nothing)"""
+        return self.norm(self.h32.half())
+
+    def begin(self, slot, tokens, limit=None, eos=-1):
+        """a new sequence in `slot`: tokens (ints, at least one) are its known tokens, the last one pending — the caller has put the
+        others into the slot's cache at positions 0 .. len - 2.  limit: the length generation stops at (default: all the history and
+        the cache hold), eos: the stop token or -1.  Copies to the device: not part of a captured step."""
+        toks = torch.as_tensor(tokens, dtype=torch.int64).reshape(-1).cpu()
+        n, top = toks.shape[0], min(self.history, self.context)
+        limit = top if limit is None else int(limit)
+        if not 0 <= int(slot) < self.slots:
+            raise nat.QpalError(f"SpeculativeStep.begin: slot {slot} outside the caches' {self.slots} sequences")
+        if not 1 <= n <= limit <= top:
+            raise nat.QpalError(f"SpeculativeStep.begin: {n} tokens and limit {limit} must satisfy 1 <= tokens <= limit <= {top}")
+        if int(toks.min()) < 0 or int(toks.max()) >= self.lm_head.shape[0]:
+            raise nat.QpalError(f"SpeculativeStep.begin: token ids must be in 0 .. {self.lm_head.shape[0] - 1}")
+        self.hist[int(slot), :n] = toks.to(torch.int32).to(self.hist.device)
+        if not -1 <= int(eos) < self.lm_head.shape[0]:
+            raise nat.QpalError(f"SpeculativeStep.begin: eos must be -1 or a token id below {self.lm_head.shape[0]}, got {eos}")
+        self.n_tok[int(slot)], self.limit[int(slot)], self.eos[int(slot)] = n, limit, int(eos)
+
+    def release(self, slot):
+        """the slot has no sequence: no rows in the steps that follow"""
+        if not 0 <= int(slot) < self.slots:
+            raise nat.QpalError(f"SpeculativeStep.release: slot {slot} outside the caches' {self.slots} sequences")
+        self.n_tok[int(slot)], self.limit[int(slot)], self.eos[int(slot)] = 0, 0, -1
+
+    def __call__(self, ext_draft=None, ext_n=None):
+        from . import speculative as spec
+        if ext_draft is None and ext_n is not None:
+            raise nat.QpalError("SpeculativeStep: ext_n without ext_draft")
+        spec.spec_draft(self.hist, self.n_tok, self.limit, self.draft_len, self.gram, self.context, self.tokens, self.seq, self.row0,
+                        self.pos0, self.row_slot, self.row_ctr, self.n_draft, ext_draft=ext_draft, ext_n=ext_n)
+        # a caller's draft may be no token of the model: it can equal no draw, so any valid row of the embedding stands in for it
+        tokens = self.tokens if ext_draft is None else torch.clamp(self.tokens, max=self.embed.shape[0] - 1, out=self._gather)
+        self.h32.copy_(self.embed[tokens])
+        for i in range(len(self.layers)):
+            self._layer(i)
+        sampling.lm_head_logits(self.h32, self.norm.weight, self.norm.eps, self.lm_head, out=self.draw.logits)
+        if self.sampler is not None:
+            slot = self.row_slot.to(torch.int64).clamp(min=0)
+            for name in ("temperature", "top_k", "top_p", "seed"):
+                torch.index_select(getattr(self.sampler, name), 0, slot, out=getattr(self.draw, name))
+        sampling.sample(self.draw.logits, self.draw, self.row_ctr, out=self.drawn)
+        if self.out_logprob is not None:
+            sampling.token_logprobs(self.draw.logits, self.drawn, out=self.draw.logprob, active=self.row_ctr)
+            rows = (self.row0[:-1].to(torch.int64)[:, None] + self._lane[None, :]).clamp(max=self.rows - 1)
+            torch.index_select(self.draw.logprob, 0, rows.reshape(-1), out=self.out_logprob.view(-1))
+        spec.spec_accept(self.tokens, self.drawn, self.seq, self.row0, self.hist, self.n_tok, self.limit, self.eos, self.out_tok,
+                         self.n_out, self.n_acc)
+        if self.out_logprob is not None:
+            return self.out_tok, self.n_out, self.out_logprob
+        return self.out_tok, self.n_out
 
 
 def perplexity(score, windows, slot=0, out=None):
