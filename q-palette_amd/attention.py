@@ -78,7 +78,7 @@ def _cache_entry(kcache, vcache, who):
     return _CACHE_ENTRY[kcache.dtype]
 
 
-def _rows(t, name, B, width, who="decode_attention"):
+def _rows(t, name, B, width, who):
     if t.dtype != torch.float32 or not t.is_cuda:
         raise QpalError(f"{who}: {name} must be an fp32 device tensor, got {t.dtype} on {t.device}")
     if t.dim() != 2 or t.shape[0] != B or t.shape[1] != width:
@@ -102,36 +102,36 @@ def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=Non
         raise QpalError("decode_attention: kcache / vcache must both have shape [B, nkv, max_len, hd]")
     B, nkv, max_len, hd = kcache.shape
     entry = "qpal_attn_rope_decode_batch" + _cache_entry(kcache, vcache, "decode_attention")
-    return _decode(entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, None)
+    return _decode("decode_attention", entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, None)
 
 
-def _decode(entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, paged):
+def _decode(who, entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, paged):
     """the checks and the launch both decode entry points share; paged: None, or the arguments that take max_len's place"""
     if q.dim() != 2 or q.shape[0] != B or q.shape[1] % hd:
-        raise QpalError(f"decode_attention: q must have shape [{B}, nq*{hd}], got {list(q.shape)}")
+        raise QpalError(f"{who}: q must have shape [{B}, nq*{hd}], got {list(q.shape)}")
     nq = q.shape[1] // hd
-    ld = _rows(q, "q", B, nq * hd)
+    ld = _rows(q, "q", B, nq * hd, who)
     for name, t in (("k", k), ("v", v)):
-        if _rows(t, name, B, nkv * hd) != ld and B > 1:
-            raise QpalError("decode_attention: q, k and v must share one row stride")
+        if _rows(t, name, B, nkv * hd, who) != ld and B > 1:
+            raise QpalError(f"{who}: q, k and v must share one row stride")
     if pos.dtype != torch.int64 or pos.shape != (B,) or pos.device != kcache.device or not pos.is_contiguous():
-        raise QpalError(f"decode_attention: pos must be a contiguous int64 [{B}] tensor on {kcache.device}")
+        raise QpalError(f"{who}: pos must be a contiguous int64 [{B}] tensor on {kcache.device}")
     if inv_freq.dtype != torch.float32 or inv_freq.numel() != hd // 2 or inv_freq.device != kcache.device or not inv_freq.is_contiguous():
-        raise QpalError(f"decode_attention: inv_freq must be a contiguous fp32 [{hd // 2}] tensor on {kcache.device}")
+        raise QpalError(f"{who}: inv_freq must be a contiguous fp32 [{hd // 2}] tensor on {kcache.device}")
     if any(t.device != kcache.device for t in (q, k, v)):
-        raise QpalError("decode_attention: every tensor must be on the caches' device")
+        raise QpalError(f"{who}: every tensor must be on the caches' device")
     if out is None:
         out = torch.empty(B, nq * hd, dtype=torch.float16, device=kcache.device)
     elif out.dtype != torch.float16 or out.dim() != 2 or out.shape != (B, nq * hd) or out.stride(1) != 1 or out.device != kcache.device:
-        raise QpalError(f"decode_attention: out must be fp16 [{B}, {nq * hd}] with contiguous rows on {kcache.device}")
+        raise QpalError(f"{who}: out must be fp16 [{B}, {nq * hd}] with contiguous rows on {kcache.device}")
     ld_out = out.stride(0) if B > 1 else nq * hd
     lib = _native.lib()
     need = lib.qpal_attn_batch_ws_bytes(B, nq, nkv, hd, max_len)
     if need > 0:
         if ws is None:
-            raise QpalError("decode_attention: this shape needs a workspace (attention_workspace(...))")
+            raise QpalError(f"{who}: this shape needs a workspace (attention_workspace(...))")
         if ws.device != kcache.device or ws.numel() * ws.element_size() < need or not ws.is_contiguous():
-            raise QpalError(f"decode_attention: ws must be a contiguous device buffer of >= {need} bytes on {kcache.device}")
+            raise QpalError(f"{who}: ws must be a contiguous device buffer of >= {need} bytes on {kcache.device}")
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
     with torch.cuda.device(kcache.device):
         rc = getattr(lib, entry)(
@@ -244,6 +244,19 @@ def _pools(kpool, vpool, table, who):
     return num_pages, nkv, page_size, hd
 
 
+def _pools_2d(kpool, vpool, block_table, who):
+    """_pools, then the checks of a block table [B, max_pages]; returns (B, nkv, max_len, hd, the launch arguments that take max_len's
+    place)"""
+    num_pages, nkv, page_size, hd = _pools(kpool, vpool, block_table, who)
+    if block_table.dim() != 2 or block_table.shape[1] < 1:
+        raise QpalError(f"{who}: block_table must have shape [B, max_pages >= 1], got {list(block_table.shape)}")
+    B, max_pages = block_table.shape
+    ld_table = block_table.stride(0) if B > 1 else max_pages
+    if ld_table < max_pages:
+        raise QpalError(f"{who}: the block table's row stride must be at least max_pages")
+    return B, nkv, max_pages * page_size, hd, (block_table.data_ptr(), ld_table, num_pages, page_size, max_pages, _KV_FMT[kpool.dtype])
+
+
 def paged_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, scale=None, out=None, ws=None):
     """decode_attention on a paged cache: kpool / vpool [num_pages, nkv, page_size, hd] (fp16 or float8_e4m3fn, contiguous, 16-byte
     aligned, page_size in {16, 32, 64, 128, 256}), block_table int32 [B, max_pages] on the device with contiguous rows (a row
@@ -252,16 +265,9 @@ def paged_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, sc
     for bit that launch's on the gathered cache.  Only entries that cover positions 0 .. pos[b] are read.  An entry in use outside
     [0, num_pages) (an unreserved -1): reads go to page 0, the new row is dropped, that sequence's out row is unspecified."""
     who = "paged_decode_attention"
-    num_pages, nkv, page_size, hd = _pools(kpool, vpool, block_table, who)
-    if block_table.dim() != 2 or block_table.shape[1] < 1:
-        raise QpalError(f"{who}: block_table must have shape [B, max_pages >= 1], got {list(block_table.shape)}")
-    B, max_pages = block_table.shape
-    ld_table = block_table.stride(0) if B > 1 else max_pages
-    if ld_table < max_pages:
-        raise QpalError(f"{who}: the block table's row stride must be at least max_pages")
-    paged = (block_table.data_ptr(), ld_table, num_pages, page_size, max_pages, _KV_FMT[kpool.dtype])
-    return _decode("qpal_attn_rope_decode_batch_paged", q, k, v, kpool, vpool, pos, inv_freq, scale, out, ws, B, nkv,
-                   max_pages * page_size, hd, paged)
+    B, nkv, max_len, hd, paged = _pools_2d(kpool, vpool, block_table, who)
+    return _decode(who, "qpal_attn_rope_decode_batch_paged", q, k, v, kpool, vpool, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd,
+                   paged)
 
 
 def paged_prefill_attention(q, k, v, kpool, vpool, block_row, pos0, inv_freq, scale=None, out=None, ws=None):
@@ -352,13 +358,6 @@ def paged_ragged_prefill_attention(q, k, v, kpool, vpool, block_table, seq, row0
     num_pages) is paged_decode_attention's."""
     who = "paged_ragged_prefill_attention"
     S = _segments(who, seq, row0, pos0, kpool.device)
-    num_pages, nkv, page_size, hd = _pools(kpool, vpool, block_table, who)
-    if block_table.dim() != 2 or block_table.shape[1] < 1:
-        raise QpalError(f"{who}: block_table must have shape [B, max_pages >= 1], got {list(block_table.shape)}")
-    B, max_pages = block_table.shape
-    ld_table = block_table.stride(0) if B > 1 else max_pages
-    if ld_table < max_pages:
-        raise QpalError(f"{who}: the block table's row stride must be at least max_pages")
-    head = (block_table.data_ptr(), ld_table, num_pages, page_size, max_pages, _KV_FMT[kpool.dtype])
+    B, nkv, max_len, hd, head = _pools_2d(kpool, vpool, block_table, who)
     return _ragged(who, "qpal_attn_rope_prefill_ragged_paged", q, k, v, kpool, vpool, seq, row0, pos0, S, inv_freq, scale, out, ws, B,
-                   nkv, max_pages * page_size, hd, head, ())
+                   nkv, max_len, hd, head, ())

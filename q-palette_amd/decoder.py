@@ -94,7 +94,130 @@ def k28_in_gemv(mlp):
     return isinstance(d, (linear.QTIPLinearTCQ, linear.CombtLinearTCQ)) and linear._codec_key(d)[0] != "single"
 
 
-class DecodeStep:
+class _Rows:
+    """What the step classes share: the model and its caches, the rotation of the hidden width, the fp32 / fp16 row buffers of one
+    layer on up to `rows` rows of the residual stream, the layer as every batch runs it, and the tails.  A class adds its attention
+    launch (`_attention(i, q, k, v, out)`), that launch's workspace `attn_ws`, and its call."""
+
+    _launches_per = None  # "<class>: launches are per <what>" where a step has no launches per token
+
+    def __init__(self, who, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows, sampler, block_table, slots=None,
+                 logits_tail=False, native_argmax=False):
+        """slots: the sequences of the caches where the caller fixes them (DecodeStep's B), else read off the caches or the table;
+        logits_tail: the tail is qpal_lm_head_logits without a sampler too; native_argmax: `_argmax_tail` is the one-launch kernel"""
+        self.block_table = block_table
+        self.slots = self._check_table(who, kcache, block_table, slots)
+        self.sampler = self._check_sampler(sampler, self.slots, embed, lm_head)
+        if logits_tail:
+            self._check_lm_head(who, embed, lm_head)
+        att, mlp = layers[0].self_attn, layers[0].mlp
+        H, dev = att.hidden_size, embed.device
+        self.layers, self.embed, self.norm, self.lm_head, self.inv_freq = layers, embed, norm, lm_head, inv_freq
+        self.kcache, self.vcache = kcache, vcache
+        self.nq, self.nkv, self.head_dim = att.num_heads, att.num_key_value_heads, att.head_dim
+        # paged: the pools' third dimension is the page size
+        self.context = kcache[0].shape[2] * (1 if block_table is None else block_table.shape[1])
+        self.eps, self.attn_scale = layers[0].input_layernorm.eps, 1.0 / math.sqrt(att.head_dim)
+        hk, self.hidden_K = had.get_hadK(H)
+        self.hidden_hadT = None if hk is None else hk.T.contiguous().half().to(dev)
+        self.h32 = torch.zeros(rows, H, dtype=torch.float32, device=dev)
+        self.a16 = torch.zeros(rows, H, dtype=torch.float16, device=dev)
+        self.qkv32 = torch.zeros(rows, H + 2 * att.kv_out, dtype=torch.float32, device=dev)
+        self.ug32 = torch.zeros(rows, 2 * mlp.intermediate_size, dtype=torch.float32, device=dev)
+        self.lm_ws = None
+        if native_argmax:
+            self.lm_ws_bytes = nat.lib().qpal_lm_head_ws_bytes(lm_head.shape[0])
+            self.lm_ws = torch.zeros(self.lm_ws_bytes // 4, dtype=torch.float32, device=dev)
+
+    @staticmethod
+    def _check_table(who, kcache, block_table, B=None):
+        """the block table's shape against B sequences (None: any number); returns the sequences of the caches"""
+        if block_table is None:
+            return kcache[0].shape[0] if B is None else B
+        if block_table.dim() != 2 or B not in (None, block_table.shape[0]):
+            raise nat.QpalError(f"{who}: block_table must be int32 [{'B' if B is None else B}, max_pages], got {list(block_table.shape)}")
+        return block_table.shape[0]
+
+    @staticmethod
+    def _check_lm_head(who, embed, lm_head):
+        H = embed.shape[1]
+        if H % 512 or H > 8192 or lm_head.data_ptr() % 16 or not lm_head.is_contiguous():
+            raise nat.QpalError(f"{who}: qpal_lm_head_logits needs a hidden width that is a multiple of 512 up to 8192 and a "
+                                "contiguous 16-byte aligned lm_head")
+
+    @staticmethod
+    def _check_sampler(sampler, B, embed, lm_head):
+        if sampler is None:
+            return None
+        if sampler.B != B or sampler.vocab != lm_head.shape[0] or sampler.device != embed.device:
+            raise nat.QpalError(f"sampler: built for {sampler.B} slots of {sampler.vocab} logits on {sampler.device}, "
+                                f"the step has {B} of {lm_head.shape[0]} on {embed.device}")
+        _Rows._check_lm_head("sampler", embed, lm_head)
+        return sampler
+
+    @property
+    def launches_per_token(self):
+        raise nat.QpalError(f"{self._launches_per} (9 per layer), not per token")
+
+    def _gemv(self, proj, x, su, scale, rms=None, **kw):
+        """multi_gemv of one projection group on rotate(RMSNorm(x) * su) / scale: RMSNorm + rotation as ONE launch, then the plain GEMV
+        launch"""
+        xr = had.rotate(x, hadK=self.hidden_hadT, K=self.hidden_K, su=su, post_scale=1.0 / scale, rms=rms,
+                        in_mode=had.IN_F32 if x.dtype == torch.float32 else had.IN_F16)
+        return multi_gemv(proj, xr, oscale=scale, **kw)
+
+    def _layer(self, i, h32, a16, qkv32, ug32):
+        """layer i on the rows of h32: the row buffers, or their first n rows"""
+        layer = self.layers[i]
+        att = layer.self_attn
+        proj, wsc, blocks = att._qkv_layout()
+        self._gemv(proj, h32, att.SU_qkv, att.scale, rms=(self.eps, layer.input_layernorm.weight), wscales=wsc,
+                   outs=list(qkv32.split([l.out_features for l in proj], dim=1)))
+        parts = dict(zip([b[0] for b in blocks], qkv32.split([b[1] for b in blocks], dim=1)))
+        self._attention(i, parts["q"], parts["k"], parts["v"], a16)
+        self._gemv([att.o_proj], a16, att.SU_o, att.scale, wscales=[att.Wscale_o], outs=[h32], accumulate=True)
+        self._mlp(i, h32, ug32)
+
+    def _mlp(self, i, h32, ug32):
+        mlp, rms = self.layers[i].mlp, (self.eps, self.layers[i].post_attention_layernorm.weight)
+        ugl, ugw = ug_layout(mlp)
+        self._gemv(ugl, h32, mlp.SU_ug, mlp.scale, rms=rms, wscales=ugw, outs=list(ug32.split([l.out_features for l in ugl], dim=1)))
+        x = had.rotate(ug32, in_mode=had.IN_SWIGLU_F32, hadK=mlp.had_left_dp_T, K=mlp.inter_K, su=mlp.SU_dp, post_scale=1.0 / mlp.scale)
+        multi_gemv([mlp.down_proj], x, outs=[h32], wscales=[mlp.Wscale_dp], oscale=mlp.scale, accumulate=True)
+
+    def _run_layers(self, tokens, n=None):
+        """the embedding rows of `tokens` through every layer, in the row buffers or (n: a short chunk) their first n rows; returns
+        those rows of the residual stream"""
+        bufs = (self.h32, self.a16, self.qkv32, self.ug32)
+        if n is not None:
+            bufs = tuple(t[:n] for t in bufs)
+        bufs[0].copy_(self.embed[tokens])
+        for i in range(len(self.layers)):
+            self._layer(i, *bufs)
+        return bufs[0]
+
+    def _sample_tail(self, h32, smp, ctr, out_tok):
+        """final norm + lm_head of every row of h32 into smp.logits, then one draw per row with the counters ctr: two launches; with
+        smp.logprob a third, the log-probability of the tokens just drawn (rows with ctr < 0 drew nothing and keep theirs)"""
+        sampling.lm_head_logits(h32, self.norm.weight, self.norm.eps, self.lm_head, out=smp.logits)
+        sampling.sample(smp.logits, smp, ctr, out=out_tok)
+        if smp.logprob is not None:
+            sampling.token_logprobs(smp.logits, out_tok, out=smp.logprob, active=ctr)
+
+    def _argmax_tail(self, rows32, out_tok):
+        """final norm + lm_head + argmax of the rows: one launch (ONE row) where the class found the kernel available, else torch ops"""
+        if self.lm_ws is None:
+            out_tok.copy_((self.norm(rows32.half()) @ self.lm_head.T).argmax(-1))
+            return
+        dev = rows32.device
+        with torch.cuda.device(dev):
+            rc = nat.lib().qpal_lm_head_argmax(rows32.data_ptr(), self.norm.weight.data_ptr(), self.norm.eps, self.lm_head.data_ptr(),
+                                               None, out_tok.data_ptr(), self.lm_ws.data_ptr(), self.lm_ws_bytes,
+                                               self.lm_head.shape[0], rows32.shape[1], torch.cuda.current_stream(dev).cuda_stream)
+        nat.check(rc, "qpal_lm_head_argmax")
+
+
+class DecodeStep(_Rows):
     """layers: modules with self_attn (IncoherentSdpaAttention), mlp (IncoherentMLP), input_layernorm, post_attention_layernorm;
     embed / lm_head fp16 [vocab, H]; norm: the final RMSNorm; kcache / vcache: per-layer fp16 or float8_e4m3fn [B, nkv, context, hd]; inv_freq fp32
     [hd / 2]; tok, pos, out_tok int64 [B] (pos[b] outside the cache: sequence b is inactive).  The caller owns the caches and
@@ -111,17 +234,15 @@ class DecodeStep:
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok, generic=False,
                  swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True, sampler=None, block_table=None):
         B = tok.shape[0]
-        if block_table is not None and (block_table.dim() != 2 or block_table.shape[0] != B):
-            raise nat.QpalError(f"DecodeStep: block_table must be int32 [{B}, max_pages], got {list(block_table.shape)}")
-        self.block_table = block_table
-        self.tok, self.pos, self.out_tok = tok, pos, out_tok
-        self.sampler = self._check_sampler(sampler, B, embed, lm_head)
         self.batch1 = B == 1 and not generic
+        super().__init__("DecodeStep", layers, embed, norm, lm_head, kcache, vcache, inv_freq, B, sampler, block_table, slots=B,
+                         native_argmax=self.batch1 and native_lm_head)
         if self.batch1 and not fusable(layers):
             raise nat.QpalError("DecodeStep: these layers have no batch-1 step (fusable(layers))")
-        self._setup_rows(layers, embed, norm, lm_head, kcache, vcache, inv_freq, B)
-        att, mlp = layers[0].self_attn, layers[0].mlp
-        H, dev = att.hidden_size, embed.device
+        self.tok, self.pos, self.out_tok = tok, pos, out_tok
+        mlp, dev = layers[0].mlp, embed.device
+        self.rot_in_gemv = self.batch1 and ops.can_fuse_rotation(1, self.h32.shape[1])  # k in {2048, 4096}: the GEMV staging rotates x
+        self.ug_il = None
         if self.rot_in_gemv and swiglu_epilogue:
             # up | gate as ONE layer with interleaved supertile rows: the launch's epilogue writes fp16 silu(gate) * up itself
             self.act16 = torch.zeros(1, mlp.intermediate_size, dtype=torch.float16, device=dev)
@@ -132,65 +253,15 @@ class DecodeStep:
                 inter = m.intermediate_size
                 self.ug_il.append((il, linear.interleave_rows(m.Wscale_ug[:inter], m.Wscale_ug[inter:]),
                                    k28_fusion and k28_in_gemv(m)))
-        # the fused single-sequence attention kernel reads fp16 caches only: on float8_e4m3fn caches the batch-1 step keeps its GEMV
-        # fusions and launches decode_attention at B = 1 (same launch count)
+        # the fused single-sequence attention kernel reads contiguous fp16 caches only: on float8_e4m3fn or paged caches the batch-1
+        # step keeps its GEMV fusions and launches the batched attention at B = 1 (same launch count)
         self.attn_batch = not self.batch1 or kcache[0].dtype != torch.float16 or block_table is not None
-        if self.batch1:
+        if self.attn_batch:
+            self.attn_ws = attention_workspace(B, self.nq, self.nkv, self.head_dim, self.context, dev)
+        else:
             # long caches: split-context attention (one workspace serves every layer: launches are stream-ordered)
             self.attn_ws_bytes = nat.lib().qpal_attn_ws_bytes(self.nq, self.nkv, self.head_dim, self.context) if split_attention else 0
             self.attn_ws = torch.zeros(max(self.attn_ws_bytes, 4) // 4, dtype=torch.float32, device=dev)
-            if native_lm_head:
-                self.lm_ws_bytes = nat.lib().qpal_lm_head_ws_bytes(lm_head.shape[0])
-                self.lm_ws = torch.zeros(self.lm_ws_bytes // 4, dtype=torch.float32, device=dev)
-        if self.attn_batch:
-            self.attn_ws = attention_workspace(B, self.nq, self.nkv, self.head_dim, self.context, dev)
-
-    @staticmethod
-    def _check_lm_head(who, embed, lm_head):
-        H = embed.shape[1]
-        if H % 512 or H > 8192 or lm_head.data_ptr() % 16 or not lm_head.is_contiguous():
-            raise nat.QpalError(f"{who}: qpal_lm_head_logits needs a hidden width that is a multiple of 512 up to 8192 and a "
-                                "contiguous 16-byte aligned lm_head")
-
-    @staticmethod
-    def _check_sampler(sampler, B, embed, lm_head):
-        if sampler is None:
-            return None
-        if sampler.B != B or sampler.vocab != lm_head.shape[0] or sampler.device != embed.device:
-            raise nat.QpalError(f"sampler: built for {sampler.B} slots of {sampler.vocab} logits on {sampler.device}, "
-                                f"the step has {B} of {lm_head.shape[0]} on {embed.device}")
-        DecodeStep._check_lm_head("sampler", embed, lm_head)
-        return sampler
-
-    def _sample_tail(self, h32, smp, ctr, out_tok):
-        """final norm + lm_head of every row of h32 into smp.logits, then one draw per row with the counters ctr: two launches; with
-        smp.logprob a third, the log-probability of the tokens just drawn (rows with ctr < 0 drew nothing and keep theirs)"""
-        sampling.lm_head_logits(h32, self.norm.weight, self.norm.eps, self.lm_head, out=smp.logits)
-        sampling.sample(smp.logits, smp, ctr, out=out_tok)
-        if smp.logprob is not None:
-            sampling.token_logprobs(smp.logits, out_tok, out=smp.logprob, active=ctr)
-
-    def _setup_rows(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows):
-        """what every step on `rows` rows of the residual stream needs (self.batch1 is set): the model, the rotation of the hidden
-        width and the fp32 / fp16 row buffers of one layer"""
-        att, mlp = layers[0].self_attn, layers[0].mlp
-        H, dev = att.hidden_size, embed.device
-        self.layers, self.embed, self.norm, self.lm_head, self.inv_freq = layers, embed, norm, lm_head, inv_freq
-        self.kcache, self.vcache = kcache, vcache
-        self.nq, self.nkv, self.head_dim, self.context = att.num_heads, att.num_key_value_heads, att.head_dim, kcache[0].shape[2]
-        if getattr(self, "block_table", None) is not None:  # paged: the pools' third dimension is the page size
-            self.context = self.block_table.shape[1] * kcache[0].shape[2]
-        else:
-            self.block_table = None
-        self.eps = layers[0].input_layernorm.eps
-        self.rot_in_gemv = self.batch1 and ops.can_fuse_rotation(1, H)  # k in {2048, 4096}: the GEMV staging rotates x itself
-        hk, self.hidden_K = had.get_hadK(H)
-        self.hidden_hadT = None if hk is None else hk.T.contiguous().half().to(dev)
-        self.h32 = torch.zeros(rows, H, dtype=torch.float32, device=dev)
-        self.a16 = torch.zeros(rows, H, dtype=torch.float16, device=dev)
-        self.qkv32 = torch.zeros(rows, H + 2 * att.kv_out, dtype=torch.float32, device=dev)
-        self.ug32 = torch.zeros(rows, 2 * mlp.intermediate_size, dtype=torch.float32, device=dev)
-        self.ug_il = self.lm_ws = None
 
     @property
     def launches_per_token(self):
@@ -203,59 +274,39 @@ class DecodeStep:
         return per_layer * len(self.layers) + tail
 
     def _gemv(self, proj, x, su, scale, rms=None, **kw):
-        """multi_gemv of one projection group on rotate(RMSNorm(x) * su) / scale: RMSNorm + rotation inside the GEMV launch, or
-        (wider hidden sizes, 70B: 8192, and every batch > 1) as ONE launch of their own, then the plain GEMV launch"""
+        """batch 1, k in {2048, 4096}: RMSNorm + rotation inside the GEMV launch; else (70B: 8192, every batch > 1) the launch pair"""
         if self.rot_in_gemv:
             return multi_gemv(proj, x, oscale=scale, x_rot=(su, 1.0 / scale), x_rms=rms, **kw)
-        xr = had.rotate(x, hadK=self.hidden_hadT, K=self.hidden_K, su=su, post_scale=1.0 / scale, rms=rms,
-                        in_mode=had.IN_F32 if x.dtype == torch.float32 else had.IN_F16)
-        return multi_gemv(proj, xr, oscale=scale, **kw)
+        return super()._gemv(proj, x, su, scale, rms=rms, **kw)
 
-    def _attention(self, i, q, k, v):
-        scale = 1.0 / math.sqrt(self.head_dim)
-        if self.block_table is not None:
-            paged_decode_attention(q, k, v, self.kcache[i], self.vcache[i], self.block_table, self.pos, self.inv_freq, scale=scale,
-                                   out=self.a16, ws=self.attn_ws)
-            return
-        if self.attn_batch:
-            decode_attention(q, k, v, self.kcache[i], self.vcache[i], self.pos, self.inv_freq, scale=scale, out=self.a16, ws=self.attn_ws)
-            return
-        dev = self.h32.device
-        with torch.cuda.device(dev):
-            rc = nat.lib().qpal_attn_rope_decode(q.data_ptr(), k.data_ptr(), v.data_ptr(), self.kcache[i].data_ptr(),
-                                                 self.vcache[i].data_ptr(), self.a16.data_ptr(), self.pos.data_ptr(),
-                                                 self.inv_freq.data_ptr(), self.nq, self.nkv, self.head_dim, self.context, scale,
-                                                 self.attn_ws.data_ptr() if self.attn_ws_bytes else None, self.attn_ws_bytes,
-                                                 torch.cuda.current_stream(dev).cuda_stream)
-        nat.check(rc, "qpal_attn_rope_decode")
-
-    def _layer(self, i):
-        layer, h32 = self.layers[i], self.h32
-        att, mlp = layer.self_attn, layer.mlp
-        proj, wsc, blocks = att._qkv_layout()
-        self._gemv(proj, h32, att.SU_qkv, att.scale, rms=(self.eps, layer.input_layernorm.weight), wscales=wsc,
-                   outs=list(self.qkv32.split([l.out_features for l in proj], dim=1)))
-        parts = dict(zip([b[0] for b in blocks], self.qkv32.split([b[1] for b in blocks], dim=1)))
-        self._attention(i, parts["q"], parts["k"], parts["v"])
-        self._gemv([att.o_proj], self.a16, att.SU_o, att.scale, wscales=[att.Wscale_o], outs=[h32], accumulate=True)
-        rms = (self.eps, layer.post_attention_layernorm.weight)
-        dp_rot = dict(hadK=mlp.had_left_dp_T, K=mlp.inter_K, su=mlp.SU_dp, post_scale=1.0 / mlp.scale)
-        x_rot = None
-        if self.ug_il:
-            il, il_w, fuse28 = self.ug_il[i]
-            # with the fused rotation the gate|up epilogue also applies down_proj's sign vector (a sign flip: exact), so the rotation
-            # inside every down_proj workgroup reads one 28 KiB vector instead of two
-            self._gemv([il], h32, mlp.SU_ug, mlp.scale, rms=rms, wscales=[il_w], act_out=self.act16,
-                       act_su=mlp.SU_dp if fuse28 else None)
-            if fuse28:  # the 28 x 512 rotation inside down_proj's x staging (csrc/rot_k28.h): no launch of its own
-                x, x_rot = self.act16, (None, 1.0 / mlp.scale, mlp.had_left_dp_T, mlp.inter_K)
-            else:
-                x = had.rotate(self.act16, **dp_rot)
+    def _attention(self, i, q, k, v, out):
+        kc, vc = self.kcache[i], self.vcache[i]
+        if not self.attn_batch:  # one sequence on contiguous fp16 caches: the fused kernel
+            dev = out.device
+            with torch.cuda.device(dev):
+                rc = nat.lib().qpal_attn_rope_decode(q.data_ptr(), k.data_ptr(), v.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
+                                                     self.pos.data_ptr(), self.inv_freq.data_ptr(), self.nq, self.nkv, self.head_dim,
+                                                     self.context, self.attn_scale, self.attn_ws.data_ptr() if self.attn_ws_bytes else None,
+                                                     self.attn_ws_bytes, torch.cuda.current_stream(dev).cuda_stream)
+            return nat.check(rc, "qpal_attn_rope_decode")
+        if self.block_table is None:
+            attend, cache = decode_attention, (kc, vc)
         else:
-            ugl, ugw = ug_layout(mlp)
-            self._gemv(ugl, h32, mlp.SU_ug, mlp.scale, rms=rms, wscales=ugw,
-                       outs=list(self.ug32.split([l.out_features for l in ugl], dim=1)))
-            x = had.rotate(self.ug32, in_mode=had.IN_SWIGLU_F32, **dp_rot)
+            attend, cache = paged_decode_attention, (kc, vc, self.block_table)
+        attend(q, k, v, *cache, self.pos, self.inv_freq, scale=self.attn_scale, out=out, ws=self.attn_ws)
+
+    def _mlp(self, i, h32, ug32):
+        if not self.ug_il:
+            return super()._mlp(i, h32, ug32)
+        mlp, rms = self.layers[i].mlp, (self.eps, self.layers[i].post_attention_layernorm.weight)
+        il, il_w, fuse28 = self.ug_il[i]
+        # with the fused rotation the gate|up epilogue also applies down_proj's sign vector (a sign flip: exact), so the rotation
+        # inside every down_proj workgroup reads one 28 KiB vector instead of two
+        self._gemv([il], h32, mlp.SU_ug, mlp.scale, rms=rms, wscales=[il_w], act_out=self.act16, act_su=mlp.SU_dp if fuse28 else None)
+        if fuse28:  # the 28 x 512 rotation inside down_proj's x staging (csrc/rot_k28.h): no launch of its own
+            x, x_rot = self.act16, (None, 1.0 / mlp.scale, mlp.had_left_dp_T, mlp.inter_K)
+        else:
+            x, x_rot = had.rotate(self.act16, hadK=mlp.had_left_dp_T, K=mlp.inter_K, su=mlp.SU_dp, post_scale=1.0 / mlp.scale), None
         multi_gemv([mlp.down_proj], x, outs=[h32], wscales=[mlp.Wscale_dp], oscale=mlp.scale, x_rot=x_rot, accumulate=True)
 
     def hidden(self):
@@ -263,25 +314,14 @@ class DecodeStep:
         return self.norm(self.h32.half())
 
     def __call__(self):
-        self.h32.copy_(self.embed[self.tok])
-        for i in range(len(self.layers)):
-            self._layer(i)
+        self._run_layers(self.tok)
         if self.sampler is not None:
             self._sample_tail(self.h32, self.sampler, self.pos, self.out_tok)
-            return
-        if self.lm_ws is None:
-            self.out_tok.copy_((self.hidden() @ self.lm_head.T).argmax(-1))
-            return
-        dev = self.h32.device
-        with torch.cuda.device(dev):  # final RMSNorm + lm_head GEMV + argmax: one launch
-            rc = nat.lib().qpal_lm_head_argmax(self.h32.data_ptr(), self.norm.weight.data_ptr(), self.norm.eps, self.lm_head.data_ptr(),
-                                               None, self.out_tok.data_ptr(), self.lm_ws.data_ptr(), self.lm_ws_bytes,
-                                               self.lm_head.shape[0], self.h32.shape[1],
-                                               torch.cuda.current_stream(dev).cuda_stream)
-        nat.check(rc, "qpal_lm_head_argmax")
+        else:
+            self._argmax_tail(self.h32, self.out_tok)
 
 
-class Prefill(DecodeStep):
+class Prefill(_Rows):
     """A prompt into ONE slot of the caches a DecodeStep is built on (per-layer fp16 or float8_e4m3fn [B, nkv, context, hd]): chunks of at most
     `chunk` <= 128 rows, each through DecodeStep's batch-B layer with rows = consecutive positions and `prefill_attention` on
     kcache[i][slot] / vcache[i][slot] (rotary embedding at pos0 + row, rows appended, causal); final norm, lm_head and argmax for
@@ -302,39 +342,30 @@ class Prefill(DecodeStep):
     addresses them (paged_prefill_attention), context = max_pages * page_size.  The caller has reserved pages for positions pos0 ..
     pos0 + N - 1 of the slot (PagedKVCache.reserve(slot, pos0 + N)) before the call."""
 
+    _launches_per = "Prefill: launches are per chunk"
+
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, native_lm_head=True, sampler=None,
                  block_table=None):
         if not 1 <= int(chunk) <= 128:
             raise nat.QpalError(f"Prefill: chunk must be in 1 .. 128, got {chunk}")
-        if block_table is not None and block_table.dim() != 2:
-            raise nat.QpalError(f"Prefill: block_table must be int32 [B, max_pages], got {list(block_table.shape)}")
-        self.chunk, self.batch1, self.block_table = int(chunk), False, block_table
-        self.slots = kcache[0].shape[0] if block_table is None else block_table.shape[0]  # sequences of the caches
-        self.sampler = self._check_sampler(sampler, self.slots, embed, lm_head)
-        self._setup_rows(layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.chunk)
-        dev, H = embed.device, self.h32.shape[1]
-        self._full = (self.h32, self.a16, self.qkv32, self.ug32)
+        self.chunk = int(chunk)
+        dev, H = embed.device, embed.shape[1]
+        super().__init__("Prefill", layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.chunk, sampler, block_table,
+                         native_argmax=native_lm_head and H in (2048, 4096, 8192) and lm_head.data_ptr() % 16 == 0)
         self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
         self.out_tok = torch.zeros(1, dtype=torch.int64, device=dev)
         self.ctr = torch.zeros(1, dtype=torch.int64, device=dev)  # with a sampler: the last prompt row's position
         self.last32 = torch.zeros(1, H, dtype=torch.float32, device=dev)  # the last prompt row of the residual stream
         self.slot = 0
         self.attn_ws = prefill_workspace(self.chunk, self.nq, self.nkv, self.head_dim, self.context, dev)
-        if native_lm_head and H in (2048, 4096, 8192) and lm_head.data_ptr() % 16 == 0:
-            self.lm_ws_bytes = nat.lib().qpal_lm_head_ws_bytes(lm_head.shape[0])
-            self.lm_ws = torch.zeros(self.lm_ws_bytes // 4, dtype=torch.float32, device=dev)
 
-    @property
-    def launches_per_token(self):
-        raise nat.QpalError("Prefill: launches are per chunk (9 per layer), not per token")
-
-    def _attention(self, i, q, k, v):
-        if self.block_table is not None:
-            paged_prefill_attention(q, k, v, self.kcache[i], self.vcache[i], self.block_table[self.slot], self.pos, self.inv_freq,
-                                    scale=1.0 / math.sqrt(self.head_dim), out=self.a16, ws=self.attn_ws)
-            return
-        prefill_attention(q, k, v, self.kcache[i][self.slot], self.vcache[i][self.slot], self.pos, self.inv_freq,
-                          scale=1.0 / math.sqrt(self.head_dim), out=self.a16, ws=self.attn_ws)
+    def _attention(self, i, q, k, v, out):
+        kc, vc = self.kcache[i], self.vcache[i]
+        if self.block_table is None:
+            attend, cache = prefill_attention, (kc[self.slot], vc[self.slot])
+        else:
+            attend, cache = paged_prefill_attention, (kc, vc, self.block_table[self.slot])
+        attend(q, k, v, *cache, self.pos, self.inv_freq, scale=self.attn_scale, out=out, ws=self.attn_ws)
 
     def hidden(self):
         """fp16 [1, H]: the final norm of the last prompt row"""
@@ -358,20 +389,13 @@ class Prefill(DecodeStep):
         return N
 
     def _chunks(self, tokens, N):
-        """runs the layers chunk by chunk; yields (c, n) after chunk tokens[c : c + n], with self.h32 its n rows of the residual
-        stream.  The full-size row buffers are back in place when the generator ends, however it ends."""
-        try:
-            for c in range(0, N, self.chunk):
-                n = min(self.chunk, N - c)
-                self.h32, self.a16, self.qkv32, self.ug32 = (t[:n] for t in self._full)
-                self.h32.copy_(self.embed[tokens[c:c + n]])
-                for i in range(len(self.layers)):
-                    self._layer(i)
-                self.pos += n
-                yield c, n
-            self.last32.copy_(self.h32[n - 1:n])
-        finally:
-            self.h32, self.a16, self.qkv32, self.ug32 = self._full
+        """runs the layers chunk by chunk; yields (c, h32) after chunk tokens[c : c + n], h32 its n rows of the residual stream"""
+        for c in range(0, N, self.chunk):
+            n = min(self.chunk, N - c)
+            h32 = self._run_layers(tokens[c:c + n], n)
+            self.pos += n
+            yield c, h32
+        self.last32.copy_(h32[n - 1:n])
 
     def __call__(self, tokens, slot=0, pos0=0):
         N = self._begin(tokens, slot, pos0)
@@ -380,17 +404,8 @@ class Prefill(DecodeStep):
         if self.sampler is not None:
             torch.sub(self.pos, 1, out=self.ctr)
             self._sample_tail(self.last32, self.sampler.slot(self.slot), self.ctr, self.out_tok)
-            return self.out_tok
-        if self.lm_ws is None:
-            self.out_tok.copy_((self.hidden() @ self.lm_head.T).argmax(-1))
-            return self.out_tok
-        dev = self.embed.device
-        with torch.cuda.device(dev):  # final RMSNorm + lm_head GEMV + argmax of the last row: one launch
-            rc = nat.lib().qpal_lm_head_argmax(self.last32.data_ptr(), self.norm.weight.data_ptr(), self.norm.eps,
-                                               self.lm_head.data_ptr(), None, self.out_tok.data_ptr(), self.lm_ws.data_ptr(),
-                                               self.lm_ws_bytes, self.lm_head.shape[0], self.last32.shape[1],
-                                               torch.cuda.current_stream(dev).cuda_stream)
-        nat.check(rc, "qpal_lm_head_argmax")
+        else:
+            self._argmax_tail(self.last32, self.out_tok)
         return self.out_tok
 
 
@@ -428,9 +443,10 @@ class Score(Prefill):
             raise nat.QpalError(f"Score: {N} tokens, built for max_tokens = {self.max_tokens}")
         self._targets[:N - 1].copy_(tokens[1:])
         self._targets[N - 1:N].fill_(-1)
-        for c, n in self._chunks(tokens, N):
+        for c, h32 in self._chunks(tokens, N):
+            n = h32.shape[0]
             self.logits = self._logits[:n]
-            sampling.lm_head_logits(self.h32, self.norm.weight, self.norm.eps, self.lm_head, out=self.logits)
+            sampling.lm_head_logits(h32, self.norm.weight, self.norm.eps, self.lm_head, out=self.logits)
             sampling.token_logprobs(self.logits, self._targets[c:c + n], out=self._lp[c:c + n], rank=self._rank[c:c + n])
         self.rank = self._rank[:N - 1]
         return self._lp[:N - 1]
@@ -440,7 +456,7 @@ class Score(Prefill):
         return -self(tokens, slot=slot, pos0=pos0).double().mean()
 
 
-class RaggedStep(DecodeStep):
+class RaggedStep(_Rows):
     """ONE step on `rows` <= 128 rows that belong to up to `segments` <= 128 slots of the caches a DecodeStep is built on: segment s
     is rows row0[s] .. row0[s + 1] - 1, the tokens of slot seq[s] at positions pos0[s] .. (a prompt chunk; one row: a decode token).
     DecodeStep's batch-B layer on all rows with `ragged_prefill_attention` in the attention's place, then per segment the final
@@ -461,39 +477,41 @@ class RaggedStep(DecodeStep):
     block_table: int32 [B, max_pages] — a paged cache, as for DecodeStep; the caller has reserved the pages of every position the
     step writes."""
 
+    _launches_per = "RaggedStep: launches are per step"
+
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=128, segments=16, sampler=None, block_table=None):
+        who = type(self).__name__
         if not 1 <= int(rows) <= 128 or not 1 <= int(segments) <= 128:
-            raise nat.QpalError(f"RaggedStep: rows and segments must be in 1 .. 128, got {rows}, {segments}")
-        if block_table is not None and block_table.dim() != 2:
-            raise nat.QpalError(f"RaggedStep: block_table must be int32 [B, max_pages], got {list(block_table.shape)}")
-        self.rows, self.segments, self.batch1, self.block_table = int(rows), int(segments), False, block_table
-        self.slots = kcache[0].shape[0] if block_table is None else block_table.shape[0]  # sequences of the caches
-        self.sampler = self._check_sampler(sampler, self.slots, embed, lm_head)
-        self._check_lm_head("RaggedStep", embed, lm_head)
-        self._setup_rows(layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.rows)
-        dev, S = embed.device, self.segments
+            raise nat.QpalError(f"{who}: rows and segments must be in 1 .. 128, got {rows}, {segments}")
+        self.rows, self.segments = int(rows), int(segments)
+        super().__init__(who, layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.rows, sampler, block_table, logits_tail=True)
+        dev = embed.device
         self.seq = self.row0 = self.pos0 = None  # the descriptors of the call under way
+        self.attn_ws = ragged_workspace(self.rows, self.segments, self.nq, self.nkv, self.head_dim, self.context, dev)
+        self._setup_tail(lm_head.shape[0], dev, sampler is not None and sampler.logprob is not None)
+
+    def _setup_tail(self, vocab, dev, logprobs):
+        """what the tail of the step owns: per SEGMENT its last row of the stream, that row's counter, a draw and a token"""
+        S = self.segments
         self.out_tok = torch.zeros(S, dtype=torch.int64, device=dev)
         self.ctr = torch.full((S,), -1, dtype=torch.int64, device=dev)  # the last row's position; -1: the segment is inactive
         self._inactive = torch.full((S,), -1, dtype=torch.int64, device=dev)
         self.last32 = torch.zeros(S, self.h32.shape[1], dtype=torch.float32, device=dev)  # each segment's last row of the stream
         # the draw's per-segment parameters: greedy, or gathered from the sampler's slots seq[s] in every call
-        self.draw = sampling.Sampler(S, lm_head.shape[0], dev, temperature=0.0,
-                                     logprobs=sampler is not None and sampler.logprob is not None)
-        self.attn_ws = ragged_workspace(self.rows, S, self.nq, self.nkv, self.head_dim, self.context, dev)
+        self.draw = sampling.Sampler(S, vocab, dev, temperature=0.0, logprobs=logprobs)
 
-    @property
-    def launches_per_token(self):
-        raise nat.QpalError("RaggedStep: launches are per step (9 per layer), not per token")
+    def _attention(self, i, q, k, v, out):
+        kc, vc = self.kcache[i], self.vcache[i]
+        if self.block_table is None:
+            attend, cache = ragged_prefill_attention, (kc, vc)
+        else:
+            attend, cache = paged_ragged_prefill_attention, (kc, vc, self.block_table)
+        attend(q, k, v, *cache, self.seq, self.row0, self.pos0, self.inv_freq, scale=self.attn_scale, out=out, ws=self.attn_ws)
 
-    def _attention(self, i, q, k, v):
-        scale = 1.0 / math.sqrt(self.head_dim)
-        if self.block_table is not None:
-            paged_ragged_prefill_attention(q, k, v, self.kcache[i], self.vcache[i], self.block_table, self.seq, self.row0, self.pos0,
-                                           self.inv_freq, scale=scale, out=self.a16, ws=self.attn_ws)
-            return
-        ragged_prefill_attention(q, k, v, self.kcache[i], self.vcache[i], self.seq, self.row0, self.pos0, self.inv_freq, scale=scale,
-                                 out=self.a16, ws=self.attn_ws)
+    def _gather_draw(self, slot):
+        """the sampler's parameters of the slots `slot` (int64, one per row of self.draw) into self.draw, on the device"""
+        for name in ("temperature", "top_k", "top_p", "seed"):
+            torch.index_select(getattr(self.sampler, name), 0, slot, out=getattr(self.draw, name))
 
     def hidden(self):
         """fp16 [segments, H]: the final norm of each segment's last row (rows of inactive segments mean nothing)"""
@@ -542,9 +560,7 @@ class RaggedStep(DecodeStep):
             if t.dtype != dtype or t.shape != (n,) or t.device != dev or not t.is_contiguous():
                 raise nat.QpalError(f"RaggedStep: {name} must be a contiguous {dtype} [{n}] tensor on {dev}")
         self.seq, self.row0, self.pos0 = seq, row0, pos0
-        self.h32.copy_(self.embed[tokens])
-        for i in range(len(self.layers)):
-            self._layer(i)
+        self._run_layers(tokens)
         # ---- the tail, on the device: which segments are active (the kernel's rules), their last rows and counters
         first, end = row0[:-1], row0[1:]
         n = (end - first).to(torch.int64)
@@ -552,9 +568,7 @@ class RaggedStep(DecodeStep):
         torch.where(active, pos0 + n - 1, self._inactive, out=self.ctr)
         torch.index_select(self.h32, 0, (end.to(torch.int64) - 1).clamp(0, self.rows - 1), out=self.last32)
         if self.sampler is not None:
-            slot = seq.to(torch.int64).clamp(0, self.slots - 1)
-            for name in ("temperature", "top_k", "top_p", "seed"):
-                torch.index_select(getattr(self.sampler, name), 0, slot, out=getattr(self.draw, name))
+            self._gather_draw(seq.to(torch.int64).clamp(0, self.slots - 1))
         self._sample_tail(self.last32, self.draw, self.ctr, self.out_tok)
         return self.out_tok
 
@@ -586,20 +600,15 @@ class SpeculativeStep(RaggedStep):
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, draft=4, gram=(2, 4), rows=None, sampler=None,
                  block_table=None, history=None):
-        if block_table is not None and block_table.dim() != 2:
-            raise nat.QpalError(f"SpeculativeStep: block_table must be int32 [B, max_pages], got {list(block_table.shape)}")
-        self.slots = kcache[0].shape[0] if block_table is None else block_table.shape[0]
-        B, K = self.slots, int(draft)
+        B, K = self._check_table("SpeculativeStep", kcache, block_table), int(draft)
         if not 0 <= K <= 15 or len(gram) != 2 or not 1 <= int(gram[0]) <= int(gram[1]) <= 8:
             raise nat.QpalError(f"SpeculativeStep: draft must be in 0 .. 15 and 1 <= gram[0] <= gram[1] <= 8, got {draft}, {gram}")
         rows = min(128, B * (K + 1)) if rows is None else int(rows)
         if not 1 <= B <= rows <= 128:
             raise nat.QpalError(f"SpeculativeStep: rows must be in B = {B} .. 128, got {rows}")
         self.draft_len, self.gram = K, (int(gram[0]), int(gram[1]))
-        self.rows, self.segments, self.batch1, self.block_table = rows, B, False, block_table
-        self.sampler = self._check_sampler(sampler, B, embed, lm_head)
-        self._check_lm_head("SpeculativeStep", embed, lm_head)
-        self._setup_rows(layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows)
+        super().__init__(layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=rows, segments=B, sampler=sampler,
+                         block_table=block_table)
         dev = embed.device
         self.history = self.context if history is None else int(history)
         if self.history < 1:
@@ -608,18 +617,21 @@ class SpeculativeStep(RaggedStep):
         self.hist = torch.zeros(B, self.history, dtype=i32, device=dev)
         self.n_tok, self.limit = torch.zeros(B, dtype=i64, device=dev), torch.zeros(B, dtype=i64, device=dev)
         self.eos = torch.full((B,), -1, dtype=i64, device=dev)
-        self.tokens, self.drawn = torch.zeros(rows, dtype=i64, device=dev), torch.zeros(rows, dtype=i64, device=dev)
+        self.tokens = torch.zeros(rows, dtype=i64, device=dev)
         self.seq, self.row0 = torch.full((B,), -1, dtype=i32, device=dev), torch.zeros(B + 1, dtype=i32, device=dev)
         self.pos0 = torch.zeros(B, dtype=i64, device=dev)
         self.row_slot, self.row_ctr = torch.full((rows,), -1, dtype=i32, device=dev), torch.full((rows,), -1, dtype=i64, device=dev)
         self.n_draft, self.n_out, self.n_acc = (torch.zeros(B, dtype=i32, device=dev) for _ in range(3))
-        self.out_tok = torch.zeros(B, K + 1, dtype=i64, device=dev)
-        logprobs = sampler is not None and sampler.logprob is not None
-        self.draw = sampling.Sampler(rows, lm_head.shape[0], dev, temperature=0.0, logprobs=logprobs)  # greedy unless gathered
-        self.out_logprob = torch.zeros(B, K + 1, dtype=torch.float32, device=dev) if logprobs else None
-        self._lane = torch.arange(K + 1, dtype=i64, device=dev)
         self._gather = torch.zeros(rows, dtype=i64, device=dev)  # the rows' embedding indices when the caller drafts
-        self.attn_ws = ragged_workspace(rows, B, self.nq, self.nkv, self.head_dim, self.context, dev)
+
+    def _setup_tail(self, vocab, dev, logprobs):
+        """a draw at every ROW and up to draft + 1 tokens per slot: no last rows, no per-segment counters"""
+        B, K = self.segments, self.draft_len
+        self.drawn = torch.zeros(self.rows, dtype=torch.int64, device=dev)
+        self.out_tok = torch.zeros(B, K + 1, dtype=torch.int64, device=dev)
+        self.draw = sampling.Sampler(self.rows, vocab, dev, temperature=0.0, logprobs=logprobs)  # greedy unless gathered
+        self.out_logprob = torch.zeros(B, K + 1, dtype=torch.float32, device=dev) if logprobs else None
+        self._lane = torch.arange(K + 1, dtype=torch.int64, device=dev)
 
     def hidden(self):
         """fp16 [rows, H]: the final norm of every row of the last step (rows of no segment mean nothing)"""
@@ -657,14 +669,10 @@ class SpeculativeStep(RaggedStep):
                         self.pos0, self.row_slot, self.row_ctr, self.n_draft, ext_draft=ext_draft, ext_n=ext_n)
         # a caller's draft may be no token of the model: it can equal no draw, so any valid row of the embedding stands in for it
         tokens = self.tokens if ext_draft is None else torch.clamp(self.tokens, max=self.embed.shape[0] - 1, out=self._gather)
-        self.h32.copy_(self.embed[tokens])
-        for i in range(len(self.layers)):
-            self._layer(i)
+        self._run_layers(tokens)
         sampling.lm_head_logits(self.h32, self.norm.weight, self.norm.eps, self.lm_head, out=self.draw.logits)
         if self.sampler is not None:
-            slot = self.row_slot.to(torch.int64).clamp(min=0)
-            for name in ("temperature", "top_k", "top_p", "seed"):
-                torch.index_select(getattr(self.sampler, name), 0, slot, out=getattr(self.draw, name))
+            self._gather_draw(self.row_slot.to(torch.int64).clamp(min=0))
         sampling.sample(self.draw.logits, self.draw, self.row_ctr, out=self.drawn)
         if self.out_logprob is not None:
             sampling.token_logprobs(self.draw.logits, self.drawn, out=self.draw.logprob, active=self.row_ctr)
