@@ -520,6 +520,24 @@ int qpal_spec_draft(const int *hist, long ld_hist, const long *n_tok, const long
 int qpal_spec_accept(const long *tokens, const long *drawn, const int *seq, const int *row0, int *hist, long ld_hist, long *n_tok,
                      long *limit, const long *eos, int B, int K, int R, long *out_tok, int *n_out, int *n_acc, void *stream);
 
+/* PROXY HESSIAN of a linear layer's inputs (csrc/hessian.hip):  H += X^T X  and  colsum += 1^T X  in one launch.
+ *   X       fp16 [rows, n] row-major, row stride ld_x >= n elements (a column slice of a wider buffer is passed as it lies);
+ *           base 16-byte aligned, ld_x a multiple of 8
+ *   H       fp64 [n, n] row-major.  H is cut into tiles of QPAL_HESSIAN_TILE rows and columns (the last one is half as wide when
+ *           n % 128 == 64); the call touches the tiles on and below the diagonal only, diagonal tiles in full.  Tiles above the
+ *           diagonal are neither read nor written: the caller mirrors the lower triangle when it needs the whole matrix
+ *   colsum  fp64 [n], may be NULL
+ *   n       a multiple of 64, 64 .. 32768;  rows >= 0 (0: success, nothing is launched)
+ * For every element it owns  H[i][j] += sum_r X[r][i] X[r][j],  colsum[j] += sum_r X[r][j].  The fp16 products are exact in the
+ * fp32 accumulator of v_mfma_f32_16x16x32_f16; at most 256 consecutive rows are summed in fp32 before the partial sum is added to
+ * an fp64 copy of the tile that stays in registers, and H is read and written once per call:
+ *   |error of H[i][j]| <= 256 * 2^-23 * sum_r |X[r][i]| |X[r][j]|   (colsum: sum_r |X[r][j]|), plus fp64 rounding.
+ * One workgroup owns a tile for the whole call — no atomics, no split over rows — so equal sequences of calls give equal bits.
+ * Never synchronises, capturable.  Codes: H or X null QPAL_E_NULL; n, rows out of range or ld_x < n QPAL_E_SHAPE; X not 16-byte
+ * aligned, ld_x % 8, H or colsum not 8-byte aligned QPAL_E_ALIGN — all decided before any stream work. */
+#define QPAL_HESSIAN_TILE 128
+int qpal_hessian_accum(double *H, double *colsum, const void *X_f16, long ld_x, int rows, int n, void *stream);
+
 /* The launch planner of the fused GEMV entry points, on its own (host code, no GPU call; what tests and tools inspect).
  * A launch of njobs jobs — rows[j] supertile rows (m / 32) of steps1[j] + steps2[j] steps (a step = 128 columns; steps2 = 0: one
  * stream) — is cut into workgroup-sized pieces: a GROUP of G = 1 << lg_g workgroups (`waves` = 16 or 8 waves each) owns rg

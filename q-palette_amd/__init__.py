@@ -30,6 +30,8 @@ Layout:
                    VQ / SQ quantiser: nearest-codeword LDLQ encoder (csrc/vq_encode.hip) -> VQLinearPack{TensorCore,SIMT}
   quantize_layer.py  whole layers: incoherence preprocessing (fp32 rotation, csrc/hadamard_f32.hip), comb / combt LDLQ,
                    quantize_linear (tcq_* / tcomb_* / comb_* / ldlq_* strings) -> IncoherentLinear + layer file
+  calibrate.py     HessianAccumulator (csrc/hessian.hip: H += X^T X of fp16 rows, fp64 sums), collect_hessians over token windows of a
+                   DenseModel, quantize_model: the seven quantize_linear calls per layer -> the layers the step classes take
   shard.py         row-sharding of packed layers across GPUs (torch.distributed / RCCL)
 
 There is deliberately no CPU implementation here: the CPU restatement lives in /oracle and is test
@@ -70,5 +72,14 @@ from .decoder import DecodeStep, Prefill, RaggedStep, Score, SpeculativeStep, pe
 from . import speculative  # noqa: F401
 from .speculative import reference_spec_accept, reference_spec_draft, spec_accept, spec_draft  # noqa: F401
 from .quantize_layer import incoherent_preprocess, layer_file_path, load_hessian, quantize_linear  # noqa: F401
+from . import calibrate  # noqa: F401
+from .calibrate import (  # noqa: F401
+    DenseModel,
+    HessianAccumulator,
+    collect_hessians,
+    quantize_model,
+    random_dense_model,
+    reference_hessian,
+)
 
 __version__ = "0.1.0"
