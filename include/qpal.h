@@ -538,6 +538,34 @@ int qpal_spec_accept(const long *tokens, const long *drawn, const int *seq, cons
 #define QPAL_HESSIAN_TILE 128
 int qpal_hessian_accum(double *H, double *colsum, const void *X_f16, long ld_x, int rows, int n, void *stream);
 
+/* MULTI-ADAPTER LoRA on one projection group (csrc/lora.hip):  out[i] += B[a] (A[a] xin[i])  with a = row_adapter[i],
+ * shrink and expand in ONE launch, no workspace, no atomics.  For every row i < rows whose a lies in [0, N):
+ *   xin     the row's input under in_mode, NOT rounded to fp16:
+ *             QPAL_IN_F16         `in` fp16 [rows][k], as is
+ *             QPAL_IN_F32         `in` fp32 [rows][k], as is; with rms_eps >= 0:  x * rsqrt(mean(x^2) + rms_eps) * w,  w = rms_weight
+ *                                 fp16 [k] or NULL (no weight).  rms_eps < 0: no norm (rms_weight must then be NULL)
+ *             QPAL_IN_SWIGLU_F32  `in` fp32 [rows][2k] = up | gate:  silu(gate) * up  (qpal_hadamard's convention)
+ *           the norm exists for QPAL_IN_F32 only: rms_eps >= 0 or a weight with another mode is QPAL_E_PARAM
+ *   shrink  t = A[a] xin.  A fp16 [N][P * R][k] row-major, block p owning rows p R .. p R + R - 1; fp32 sums
+ *   expand  for p < P, j < blk_m[p]:  out[i][blk_off[p] + j] += sum_r B[a][boff_p + j][r] t[p R + r].  B fp16 [N][sum blk_m][R]
+ *           row-major, the blocks in order (boff_p = blk_m[0] + .. + blk_m[p - 1]); the adapter's scale alpha / r is folded into B
+ *           by the caller.  out fp32, row stride ld_out elements; the add is one fp32 read-modify-write by the element's one owner
+ * A row whose row_adapter[i] is outside [0, N) (-1: no adapter) has none of its out bytes read or written; a launch of such rows
+ * reads row_adapter and leaves.  Columns outside the blocks are never touched.
+ *   blk_off, blk_m  HOST arrays of P ints (read before the call returns); row_adapter int32 [rows] on the device
+ * Limits: rows 1 .. 128;  R a multiple of 8, 8 .. 64;  P 1 .. 3;  k a multiple of 64, 64 .. 32768;  N >= 1;  blk_m multiples of 16;
+ * blk_off >= 0, blk_off + blk_m <= ld_out, the blocks' column ranges disjoint;  in, A, B, rms_weight 16-byte aligned, out and
+ * row_adapter 4-byte aligned;  out must not overlap in.
+ * Error against exact arithmetic on the stored values:  <= 2e-5 * sum_r |B_jr| * sum_l |A_rl xin_l|  +  2^-23 |out|  per element.
+ * Equal launches give equal bits, and a row's out bits depend on its input, its adapter and its out value only — not on its row
+ * index, the other rows or their adapters.  Never reads device memory on the host, never synchronises: capturable.
+ * Codes, all decided before any stream work (out untouched): a null pointer QPAL_E_NULL; rows, k, R, P, N, blk_m, blk_off or
+ * ld_out outside the limits QPAL_E_SHAPE; an unknown in_mode, a norm outside QPAL_IN_F32, out overlapping in QPAL_E_PARAM; a
+ * misaligned pointer QPAL_E_ALIGN. */
+int qpal_lora_apply(float *out_f32, long ld_out, const void *in, int in_mode, float rms_eps, const void *rms_weight, const void *A,
+                    const void *B, const int *blk_off, const int *blk_m, int P, const int *row_adapter, int rows, int k, int R, int N,
+                    void *stream);
+
 /* The launch planner of the fused GEMV entry points, on its own (host code, no GPU call; what tests and tools inspect).
  * A launch of njobs jobs — rows[j] supertile rows (m / 32) of steps1[j] + steps2[j] steps (a step = 128 columns; steps2 = 0: one
  * stream) — is cut into workgroup-sized pieces: a GROUP of G = 1 << lg_g workgroups (`waves` = 16 or 8 waves each) owns rg

@@ -32,6 +32,9 @@ Layout:
                    quantize_linear (tcq_* / tcomb_* / comb_* / ldlq_* strings) -> IncoherentLinear + layer file
   calibrate.py     HessianAccumulator (csrc/hessian.hip: H += X^T X of fp16 rows, fp64 sums), collect_hessians over token windows of a
                    DenseModel, quantize_model: the seven quantize_linear calls per layer -> the layers the step classes take
+  lora.py          low-rank adapters on the quantised base: lora_apply (csrc/lora.hip: out += B[a] (A[a] xin) with the adapter a
+                   per row, shrink and expand in one launch), its contract reference_lora, LoraBank (the packed adapters and
+                   the slot -> adapter vector the step classes take as `adapters=`), load_peft_adapter
   shard.py         row-sharding of packed layers across GPUs (torch.distributed / RCCL)
 
 There is deliberately no CPU implementation here: the CPU restatement lives in /oracle and is test
@@ -81,5 +84,7 @@ from .calibrate import (  # noqa: F401
     random_dense_model,
     reference_hessian,
 )
+from . import lora  # noqa: F401
+from .lora import LoraBank, load_peft_adapter, lora_apply, reference_lora  # noqa: F401
 
 __version__ = "0.1.0"

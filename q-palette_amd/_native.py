@@ -98,6 +98,7 @@ _SIGNATURES = {
     "qpal_tcq_viterbi_ws_bytes": [_I],
     "qpal_vq_encode": [_P, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P],
     "qpal_hessian_accum": [_P, _P, _P, ctypes.c_long, _I, _I, _P],
+    "qpal_lora_apply": [_P, ctypes.c_long, _P, _I, _F, _P, _P, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, _P, _I, _I, _I, _I, _P],
 }
 
 HESSIAN_TILE = 128  # QPAL_HESSIAN_TILE

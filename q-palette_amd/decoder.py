@@ -47,6 +47,11 @@ and step, the same stream as one-token sampling.
 All of them take `block_table=` for a paged cache (paging.PagedKVCache): kcache / vcache are then the per-layer page
 pools [num_pages, nkv, page_size, hd], the table is int32 [B, max_pages], and context = max_pages * page_size.  The caller reserves
 pages for every position a call, or a run of graph replays, will reach before it starts: nothing in here allocates or synchronises.
+
+All of them take `adapters=` too, a lora.LoraBank of the caches' slots: every row then runs with the low-rank
+adapter of its slot, bank.slot_adapter[slot] (-1: none) — one `lora_apply` launch behind the GEMV of each projection group, four
+per layer.  The rows' adapters are looked up on the device in every call, so bank.set(slot, adapter) between replays of a captured
+step takes effect without a new capture.
 """
 import math
 
@@ -54,7 +59,7 @@ import torch
 
 from . import _native as nat
 from . import hadamard as had
-from . import linear, ops, sampling
+from . import linear, lora, ops, sampling
 from .attention import (attention_workspace, decode_attention, paged_decode_attention, paged_prefill_attention,
                         paged_ragged_prefill_attention, prefill_attention, prefill_workspace, ragged_prefill_attention, ragged_workspace)
 from .linear import multi_gemv
@@ -102,11 +107,15 @@ class _Rows:
     _launches_per = None  # "<class>: launches are per <what>" where a step has no launches per token
 
     def __init__(self, who, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows, sampler, block_table, slots=None,
-                 logits_tail=False, native_argmax=False):
+                 logits_tail=False, native_argmax=False, adapters=None):
         """slots: the sequences of the caches where the caller fixes them (DecodeStep's B), else read off the caches or the table;
-        logits_tail: the tail is qpal_lm_head_logits without a sampler too; native_argmax: `_argmax_tail` is the one-launch kernel"""
+        logits_tail: the tail is qpal_lm_head_logits without a sampler too; native_argmax: `_argmax_tail` is the one-launch kernel;
+        adapters: a lora.LoraBank of these layers and slots, or None"""
         self.block_table = block_table
         self.slots = self._check_table(who, kcache, block_table, slots)
+        self.adapters = self._check_adapters(who, adapters, self.slots, layers, embed)
+        # the adapter of every row, looked up on the device before the layers run (DecodeStep: the bank's own vector, row = slot)
+        self.row_adapter = None if adapters is None else torch.full((rows,), -1, dtype=torch.int32, device=embed.device)
         self.sampler = self._check_sampler(sampler, self.slots, embed, lm_head)
         if logits_tail:
             self._check_lm_head(who, embed, lm_head)
@@ -139,6 +148,14 @@ class _Rows:
         return block_table.shape[0]
 
     @staticmethod
+    def _check_adapters(who, bank, B, layers, embed):
+        if bank is None:
+            return None
+        if not isinstance(bank, lora.LoraBank) or bank.slots != B or len(bank.groups) != len(layers) or bank.device != embed.device:
+            raise nat.QpalError(f"{who}: adapters must be a LoraBank of {len(layers)} layers and {B} slots on {embed.device}")
+        return bank
+
+    @staticmethod
     def _check_lm_head(who, embed, lm_head):
         H = embed.shape[1]
         if H % 512 or H > 8192 or lm_head.data_ptr() % 16 or not lm_head.is_contiguous():
@@ -166,24 +183,34 @@ class _Rows:
                         in_mode=had.IN_F32 if x.dtype == torch.float32 else had.IN_F16)
         return multi_gemv(proj, xr, oscale=scale, **kw)
 
+    def _lora(self, i, group, x, out, in_mode, rms=None):
+        """with a bank: the low-rank update of one projection group of layer i on the rows of x, added to out (one launch)"""
+        if self.adapters is not None:
+            g = self.adapters.group(i, group)
+            lora.lora_apply(out, x, in_mode, rms, g.A, g.B, g.blk_off, g.blk_m, self.row_adapter[:x.shape[0]])
+
     def _layer(self, i, h32, a16, qkv32, ug32):
         """layer i on the rows of h32: the row buffers, or their first n rows"""
         layer = self.layers[i]
         att = layer.self_attn
         proj, wsc, blocks = att._qkv_layout()
-        self._gemv(proj, h32, att.SU_qkv, att.scale, rms=(self.eps, layer.input_layernorm.weight), wscales=wsc,
-                   outs=list(qkv32.split([l.out_features for l in proj], dim=1)))
+        rms = (self.eps, layer.input_layernorm.weight)
+        self._gemv(proj, h32, att.SU_qkv, att.scale, rms=rms, wscales=wsc, outs=list(qkv32.split([l.out_features for l in proj], dim=1)))
+        self._lora(i, "qkv", h32, qkv32, had.IN_F32, rms)
         parts = dict(zip([b[0] for b in blocks], qkv32.split([b[1] for b in blocks], dim=1)))
         self._attention(i, parts["q"], parts["k"], parts["v"], a16)
         self._gemv([att.o_proj], a16, att.SU_o, att.scale, wscales=[att.Wscale_o], outs=[h32], accumulate=True)
+        self._lora(i, "o", a16, h32, had.IN_F16)  # before up|gate reads the stream
         self._mlp(i, h32, ug32)
 
     def _mlp(self, i, h32, ug32):
         mlp, rms = self.layers[i].mlp, (self.eps, self.layers[i].post_attention_layernorm.weight)
         ugl, ugw = ug_layout(mlp)
         self._gemv(ugl, h32, mlp.SU_ug, mlp.scale, rms=rms, wscales=ugw, outs=list(ug32.split([l.out_features for l in ugl], dim=1)))
+        self._lora(i, "ug", h32, ug32, had.IN_F32, rms)
         x = had.rotate(ug32, in_mode=had.IN_SWIGLU_F32, hadK=mlp.had_left_dp_T, K=mlp.inter_K, su=mlp.SU_dp, post_scale=1.0 / mlp.scale)
         multi_gemv([mlp.down_proj], x, outs=[h32], wscales=[mlp.Wscale_dp], oscale=mlp.scale, accumulate=True)
+        self._lora(i, "down", ug32, h32, had.IN_SWIGLU_F32)  # reads up | gate with their own update in
 
     def _run_layers(self, tokens, n=None):
         """the embedding rows of `tokens` through every layer, in the row buffers or (n: a short chunk) their first n rows; returns
@@ -229,14 +256,20 @@ class DecodeStep(_Rows):
     block_table: int32 [B, max_pages] on the device — kcache / vcache are then the per-layer page pools [num_pages, nkv, page_size, hd]
     of a paged cache, context = max_pages * page_size, and the attention launch is paged_decode_attention (a batch of one as well:
     the fused single-sequence kernel reads contiguous caches only).  The caller has reserved a page for every position the step, or
-    a run of replays of the captured step, will write: the step reads the table on the device and never allocates."""
+    a run of replays of the captured step, will write: the step reads the table on the device and never allocates.
+    adapters: a lora.LoraBank of B slots — row b runs with adapter bank.slot_adapter[b], read by the launches themselves: four more
+    launches per layer.  At batch 1 the interleaved up|gate epilogue and down_proj's staged rotation are then off (they never put
+    up | gate into memory: the swiglu_epilogue=False step); RMSNorm and the rotation stay inside the GEMV staging."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok, generic=False,
-                 swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True, sampler=None, block_table=None):
+                 swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True, sampler=None, block_table=None,
+                 adapters=None):
         B = tok.shape[0]
         self.batch1 = B == 1 and not generic
         super().__init__("DecodeStep", layers, embed, norm, lm_head, kcache, vcache, inv_freq, B, sampler, block_table, slots=B,
-                         native_argmax=self.batch1 and native_lm_head)
+                         native_argmax=self.batch1 and native_lm_head, adapters=adapters)
+        if adapters is not None:
+            self.row_adapter, swiglu_epilogue = adapters.slot_adapter, False  # row = slot
         if self.batch1 and not fusable(layers):
             raise nat.QpalError("DecodeStep: these layers have no batch-1 step (fusable(layers))")
         self.tok, self.pos, self.out_tok = tok, pos, out_tok
@@ -268,8 +301,9 @@ class DecodeStep(_Rows):
         """kernel launches of one step: per layer q|k|v, attention, o, up|gate, SwiGLU rotation, down (+ a rotation in front of
         q|k|v, o and up|gate where the GEMV cannot rotate; - the SwiGLU rotation where down_proj's staging runs it); + the norm /
         lm_head / argmax launch, or the lm_head logits and the draw with a sampler, + the log-probability launch of a sampler with
-        logprobs (the embedding row copy is a memcpy node)"""
+        logprobs (the embedding row copy is a memcpy node); with adapters + 4 per layer, one per projection group"""
         per_layer = (5 if self.ug_il and self.ug_il[0][2] else 6) if self.rot_in_gemv else 9
+        per_layer += 4 if getattr(self, "adapters", None) is not None else 0  # (arithmetic on the configuration: stand-ins may lack it)
         tail = 1 if self.sampler is None else (2 if self.sampler.logprob is None else 3)
         return per_layer * len(self.layers) + tail
 
@@ -340,18 +374,20 @@ class Prefill(_Rows):
 
     block_table: int32 [B, max_pages] — kcache / vcache are the per-layer page pools of a paged cache, the slot's row block_table[slot]
     addresses them (paged_prefill_attention), context = max_pages * page_size.  The caller has reserved pages for positions pos0 ..
-    pos0 + N - 1 of the slot (PagedKVCache.reserve(slot, pos0 + N)) before the call."""
+    pos0 + N - 1 of the slot (PagedKVCache.reserve(slot, pos0 + N)) before the call.
+
+    adapters: a lora.LoraBank of the caches' slots — every row of the call runs with bank.slot_adapter[slot], copied on the device."""
 
     _launches_per = "Prefill: launches are per chunk"
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, native_lm_head=True, sampler=None,
-                 block_table=None):
+                 block_table=None, adapters=None):
         if not 1 <= int(chunk) <= 128:
             raise nat.QpalError(f"Prefill: chunk must be in 1 .. 128, got {chunk}")
         self.chunk = int(chunk)
         dev, H = embed.device, embed.shape[1]
         super().__init__("Prefill", layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.chunk, sampler, block_table,
-                         native_argmax=native_lm_head and H in (2048, 4096, 8192) and lm_head.data_ptr() % 16 == 0)
+                         native_argmax=native_lm_head and H in (2048, 4096, 8192) and lm_head.data_ptr() % 16 == 0, adapters=adapters)
         self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
         self.out_tok = torch.zeros(1, dtype=torch.int64, device=dev)
         self.ctr = torch.zeros(1, dtype=torch.int64, device=dev)  # with a sampler: the last prompt row's position
@@ -380,6 +416,8 @@ class Prefill(_Rows):
         if not 0 <= int(slot) < self.slots:
             raise nat.QpalError(f"{who}: slot {slot} outside the caches' {self.slots} sequences")
         self.slot = int(slot)
+        if self.adapters is not None:
+            self.row_adapter.copy_(self.adapters.slot_adapter[self.slot:self.slot + 1].expand(self.chunk))
         if isinstance(pos0, torch.Tensor):
             self.pos.copy_(pos0.reshape(1))
         else:
@@ -421,12 +459,14 @@ class Score(Prefill):
     max_tokens entries (default: the caches' context) that the next call overwrites.  No host synchronisation inside the call.  The
     last row has no next token: its logits are computed, its row of the log-prob launch is inactive.  The slot is left as Prefill
     leaves it: a DecodeStep can continue at position pos0 + N.  The lm_head must suit qpal_lm_head_logits (a sampler's demands).
-    block_table: as for Prefill (a paged cache; the caller reserves the slot's pages for pos0 .. pos0 + N - 1)."""
+    block_table: as for Prefill (a paged cache; the caller reserves the slot's pages for pos0 .. pos0 + N - 1).  adapters: as for
+    Prefill."""
 
-    def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, max_tokens=None, block_table=None):
+    def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, max_tokens=None, block_table=None,
+                 adapters=None):
         self._check_lm_head("Score", embed, lm_head)
         super().__init__(layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=chunk, native_lm_head=False,
-                         block_table=block_table)
+                         block_table=block_table, adapters=adapters)
         self.max_tokens = self.context if max_tokens is None else int(max_tokens)
         if self.max_tokens < 2:
             raise nat.QpalError(f"Score: max_tokens must be at least 2, got {max_tokens}")
@@ -475,17 +515,24 @@ class RaggedStep(_Rows):
     sampler built with logprobs=True rs.draw.logprob the drawn tokens' log-probabilities.
 
     block_table: int32 [B, max_pages] — a paged cache, as for DecodeStep; the caller has reserved the pages of every position the
-    step writes."""
+    step writes.
+
+    adapters: a lora.LoraBank of the caches' slots — a row of segment s runs with bank.slot_adapter[seq[s]], rows of no segment
+    with none; the map row -> segment -> slot -> adapter is made on the device in every call."""
 
     _launches_per = "RaggedStep: launches are per step"
 
-    def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=128, segments=16, sampler=None, block_table=None):
+    def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=128, segments=16, sampler=None, block_table=None,
+                 adapters=None):
         who = type(self).__name__
         if not 1 <= int(rows) <= 128 or not 1 <= int(segments) <= 128:
             raise nat.QpalError(f"{who}: rows and segments must be in 1 .. 128, got {rows}, {segments}")
         self.rows, self.segments = int(rows), int(segments)
-        super().__init__(who, layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.rows, sampler, block_table, logits_tail=True)
+        super().__init__(who, layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.rows, sampler, block_table, logits_tail=True,
+                         adapters=adapters)
         dev = embed.device
+        self._row_id = torch.arange(self.rows, dtype=torch.int32, device=dev)
+        self._no_adapter = torch.full((self.rows,), -1, dtype=torch.int32, device=dev)
         self.seq = self.row0 = self.pos0 = None  # the descriptors of the call under way
         self.attn_ws = ragged_workspace(self.rows, self.segments, self.nq, self.nkv, self.head_dim, self.context, dev)
         self._setup_tail(lm_head.shape[0], dev, sampler is not None and sampler.logprob is not None)
@@ -507,6 +554,17 @@ class RaggedStep(_Rows):
         else:
             attend, cache = paged_ragged_prefill_attention, (kc, vc, self.block_table)
         attend(q, k, v, *cache, self.seq, self.row0, self.pos0, self.inv_freq, scale=self.attn_scale, out=out, ws=self.attn_ws)
+
+    def _map_rows(self, seq, row0):
+        """with a bank: self.row_adapter[r] = the adapter of the slot whose segment holds row r, -1 for rows of no segment or of a
+        segment without a valid slot; torch ops on the device, no synchronisation"""
+        if self.adapters is None:
+            return
+        S = self.segments
+        seg = torch.searchsorted(row0[1:], self._row_id, right=True).clamp(max=S - 1)  # the segments that end at or before r
+        slot = seq[seg]
+        held = (self._row_id >= row0[seg]) & (self._row_id < row0[seg + 1]) & (slot >= 0) & (slot < self.slots)
+        torch.where(held, self.adapters.slot_adapter[slot.clamp(0, self.slots - 1).to(torch.int64)], self._no_adapter, out=self.row_adapter)
 
     def _gather_draw(self, slot):
         """the sampler's parameters of the slots `slot` (int64, one per row of self.draw) into self.draw, on the device"""
@@ -560,6 +618,7 @@ class RaggedStep(_Rows):
             if t.dtype != dtype or t.shape != (n,) or t.device != dev or not t.is_contiguous():
                 raise nat.QpalError(f"RaggedStep: {name} must be a contiguous {dtype} [{n}] tensor on {dev}")
         self.seq, self.row0, self.pos0 = seq, row0, pos0
+        self._map_rows(seq, row0)
         self._run_layers(tokens)
         # ---- the tail, on the device: which segments are active (the kernel's rules), their last rows and counters
         first, end = row0[:-1], row0[1:]
@@ -596,10 +655,10 @@ class SpeculativeStep(RaggedStep):
     logprob fp32 [B, draft + 1]), the emitted tokens' log-probabilities, from one token_logprobs launch on the rows.
     No cache rollback: the next step starts at the new pending position and rewrites the K / V rows a rejected draft left before
     anything reads them.  block_table: a paged cache as for DecodeStep; the caller has reserved the pages of min(limit, n_tok +
-    draft) positions of every slot before the call."""
+    draft) positions of every slot before the call.  adapters: as for RaggedStep (the rows of slot b run with slot b's adapter)."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, draft=4, gram=(2, 4), rows=None, sampler=None,
-                 block_table=None, history=None):
+                 block_table=None, history=None, adapters=None):
         B, K = self._check_table("SpeculativeStep", kcache, block_table), int(draft)
         if not 0 <= K <= 15 or len(gram) != 2 or not 1 <= int(gram[0]) <= int(gram[1]) <= 8:
             raise nat.QpalError(f"SpeculativeStep: draft must be in 0 .. 15 and 1 <= gram[0] <= gram[1] <= 8, got {draft}, {gram}")
@@ -608,7 +667,7 @@ class SpeculativeStep(RaggedStep):
             raise nat.QpalError(f"SpeculativeStep: rows must be in B = {B} .. 128, got {rows}")
         self.draft_len, self.gram = K, (int(gram[0]), int(gram[1]))
         super().__init__(layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=rows, segments=B, sampler=sampler,
-                         block_table=block_table)
+                         block_table=block_table, adapters=adapters)
         dev = embed.device
         self.history = self.context if history is None else int(history)
         if self.history < 1:
@@ -669,6 +728,7 @@ class SpeculativeStep(RaggedStep):
                         self.pos0, self.row_slot, self.row_ctr, self.n_draft, ext_draft=ext_draft, ext_n=ext_n)
         # a caller's draft may be no token of the model: it can equal no draw, so any valid row of the embedding stands in for it
         tokens = self.tokens if ext_draft is None else torch.clamp(self.tokens, max=self.embed.shape[0] - 1, out=self._gather)
+        self._map_rows(self.seq, self.row0)
         self._run_layers(tokens)
         sampling.lm_head_logits(self.h32, self.norm.weight, self.norm.eps, self.lm_head, out=self.draw.logits)
         if self.sampler is not None:
