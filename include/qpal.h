@@ -520,6 +520,48 @@ int qpal_spec_draft(const int *hist, long ld_hist, const long *n_tok, const long
 int qpal_spec_accept(const long *tokens, const long *drawn, const int *seq, const int *row0, int *hist, long ld_hist, long *n_tok,
                      long *limit, const long *eos, int B, int K, int R, long *out_tok, int *n_out, int *n_acc, void *stream);
 
+/* LOGIT PROCESSORS (csrc/logit_proc.hip): token masks, a sparse logit bias and repetition / presence / frequency
+ * penalties, applied to the logits between qpal_lm_head_logits and qpal_sample.  State of slot b of `slots` (1 .. 128), all on the
+ * device and never read by the host (a captured launch is replayed while the caller rewrites the state):
+ *   count int32 [slots][ld_count]          how often token i has been counted for the slot (ld_count >= vocab)
+ *   repetition, presence, frequency fp32 [slots]      neutral: 1, 0, 0; repetition > 0, all finite
+ *   mask uint32 [slots][ld_mask]           bit i & 31 of word i >> 5 set: token i is allowed (ld_mask >= ceil(vocab / 32))
+ *   mask_on int32 [slots]                  0: the slot's mask is ignored
+ *   bias_id int32 [slots][bias_slots], bias_val fp32 [slots][bias_slots], bias_n int32 [slots]       the first bias_n[b] (clamped
+ *                                          to 0 .. bias_slots) entries are the slot's bias; their ids are distinct, values finite
+ *
+ * qpal_logit_process: logits fp32 [rows][ld_logits] -> out fp32 [rows][ld_out], 1 <= rows <= 128, 1 <= vocab <= 2^30, both strides
+ * >= vocab.  out == logits with ld_out == ld_logits is the in-place form; any other overlap is QPAL_E_PARAM.  Row r belongs to slot
+ * b = row_slot[r] (int32 [rows]).  It is INACTIVE, and no word of out's row is written, when ctr[r] < 0 (int64 [rows]: qpal_sample's
+ * counters), when b is outside [0, slots), or (tokens != NULL) when r - row0[b] is outside 0 .. 15 or row0[b] < 0.  For an active
+ * row with logits l[0 .. vocab):
+ *  1. c[i] = count[b][i] + #{extra tokens of the row equal to i}.  Extras exist only with tokens != NULL (int64 [rows], row0 int32
+ *     [slots + 1]: qpal_spec_draft's): tokens[row0[b] + 1 .. r], the guessed tokens in front of row r in its segment, at most 15;
+ *     an extra outside [0, vocab) counts for nothing.
+ *  2. Where c[i] > 0 and l is no NaN:  l = l > 0 ? l / repetition : l * repetition;  then  l = l - (presence + frequency * float(c)).
+ *     Four fp32 operations, each rounded once to nearest, in exactly this order, no fused multiply-add.  Where c[i] == 0, and under
+ *     neutral parameters, l keeps its bits.
+ *  3. mask_on[b] != 0 and the bit of i clear: l = -inf (a NaN too).
+ *  4. l[bias_id[b][j]] += bias_val[b][j] for j < bias_n[b] (ids outside [0, vocab) are skipped; -inf stays -inf, a NaN stays).
+ * A NaN logit passes through 2 and 4 with its bits; qpal_sample reads it as -inf.  Columns vocab .. ld_out are not written.
+ * Elementwise over (vocab tiles) x rows workgroups; no workspace, no atomics, one writer per word: two launches are bitwise equal,
+ * and equal to logits.reference_process (numpy fp32, the same operations) bit for bit.
+ *
+ * qpal_logit_observe: count[s][tokens[r]] += 1 for r < n (1 .. 2048), s = slot[r] (int32 [n]) or, with slot == NULL, slot0 for
+ * every row.  A row is skipped when s is outside [0, slots), when active != NULL and active[r] < 0 (int64 [n]), or when tokens[r]
+ * (int64 [n]) is outside [0, vocab).  Integer atomic adds: the result does not depend on their order.
+ *
+ * Codes, all decided on the host before any stream work: a null pointer QPAL_E_NULL (tokens and row0 are NULL together; the three
+ * bias arrays may be NULL when bias_slots == 0; slot and active may be NULL); rows, n, slots, vocab, a stride below its width or
+ * bias_slots outside 0 .. 1024, slot0 outside [0, slots) when slot == NULL: QPAL_E_SHAPE; fp32 / int32 arrays 4-byte, int64 arrays
+ * 8-byte aligned, else QPAL_E_ALIGN. */
+int qpal_logit_process(const float *logits_f32, long ld_logits, float *out_f32, long ld_out, int rows, int vocab, const int *row_slot,
+                       const long *ctr, int slots, const int *count, long ld_count, const float *repetition, const float *presence,
+                       const float *frequency, const unsigned *mask, long ld_mask, const int *mask_on, const int *bias_id,
+                       const float *bias_val, const int *bias_n, int bias_slots, const long *tokens, const int *row0, void *stream);
+int qpal_logit_observe(int *count, long ld_count, int slots, int vocab, const int *slot, int slot0, const long *tokens,
+                       const long *active, int n, void *stream);
+
 /* PROXY HESSIAN of a linear layer's inputs (csrc/hessian.hip):  H += X^T X  and  colsum += 1^T X  in one launch.
  *   X       fp16 [rows, n] row-major, row stride ld_x >= n elements (a column slice of a wider buffer is passed as it lies);
  *           base 16-byte aligned, ld_x a multiple of 8

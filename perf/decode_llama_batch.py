@@ -20,13 +20,17 @@ rotary embedding, a per-sequence cache write, SDPA with a per-sequence mask), wh
 --sample adds the sampled step (DecodeStep(sampler=...): qpal_lm_head_logits + qpal_sample in the torch tail's place) at temperature
 0.6 / top-k 5 (the setting of the decode loop this was modelled on) and 0.8 / top-p 0.95, timed in the same call as the greedy step.
 
+--process (with --sample) also times each sampled step with a logits.LogitProcessor: repetition 1.3, presence 0.5,
+frequency 0.3, a mask that allows every second token and 64 bias entries in every slot — observe + process, two more launches —
+next to the same step without one, in the same call.
+
 --kv fp8 keeps the caches as torch.float8_e4m3fn.  The torch-glue reference then keeps fp16 caches of its own that
 hold e4m3 values only: `BatchKV.update` stores a new row through the round trip clamp(-448, 448) -> float8_e4m3fn -> half and the
 step attends to the round-tripped cache, as the kernels do.  The check also reports how far the fp16-cache step lies from that
 reference (what the format itself moves; not a gate).
 
     python perf/decode_llama_batch.py [--model 3_8b] [--batch 1 8 16 32 64] [--context 1024] [--tokens 64] [--inactive 0] [--sample]
-                                      [--kv fp16|fp8] [--paged PAGE_SIZE]
+                                      [--process] [--kv fp16|fp8] [--paged PAGE_SIZE]
 """
 import argparse
 import json
@@ -83,6 +87,7 @@ def main(argv=None, quiet=False):
     ap.add_argument("--seed", type=int, default=7, help="seed of the ragged positions")
     ap.add_argument("--no-torch-glue", action="store_true", help="skip the torch-glue step (its timing and the check)")
     ap.add_argument("--sample", action="store_true", help="also time the step with a sampler (0.6 / top-k 5 and 0.8 / top-p 0.95)")
+    ap.add_argument("--process", action="store_true", help="with --sample: also time the sampled step with a logit processor")
     ap.add_argument("--kv", default="fp16", choices=["fp16", "fp8"], help="KV-cache element format (fp8: OCP e4m3fn, no scales)")
     ap.add_argument("--paged", type=int, default=0, metavar="PAGE_SIZE",
                     help="also time the step on a paged cache of this page size (pages in a seeded random order; DESIGN.md §17)")
@@ -90,6 +95,8 @@ def main(argv=None, quiet=False):
     kv8 = args.kv == "fp8"
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
+    if args.process and not args.sample:
+        raise SystemExit("--process: the processor works on a sampler's logits, add --sample")
     if args.context % 4 or args.context < args.tokens + 16:
         raise SystemExit("--context: a multiple of 4, at least --tokens + 16")
     if args.paged and (args.paged not in qp.attention.PAGE_SIZES or args.context % args.paged):
@@ -216,6 +223,20 @@ def main(argv=None, quiet=False):
                 ms = timed(sstep)
                 sampled.append({"temperature": temperature, "top_k": top_k, "top_p": top_p, "ms_step": ms, "ms_minus_greedy": ms - ms_step,
                                 "tokens_per_s": nact / ms * 1e3})
+                if args.process:
+                    # every stage on in every slot; the step without a processor is timed again behind it (the spread of the call)
+                    proc = qp.LogitProcessor(B, args.vocab, dev)
+                    half = torch.arange(0, args.vocab, 2)
+                    for b in range(B):
+                        proc.set(b, repetition=1.3, presence=0.5, frequency=0.3)
+                        proc.set_mask(b, half)
+                        proc.set_bias(b, {int(i): 1.0 for i in half[:proc.bias_slots]})
+                    pstep = qp.DecodeStep(layers, embed, norm, lm_head, kc, vc, inv_freq, tok, pos, out_tok, generic=True, sampler=smp,
+                                          processor=proc)
+                    ms_p, ms_again = timed(pstep), timed(sstep)
+                    sampled[-1].update({"ms_step_processor": ms_p, "ms_step_again": ms_again, "ms_processor_minus_plain": ms_p - 0.5 * (ms + ms_again),
+                                        "launches_per_token": [sstep.launches_per_token, pstep.launches_per_token]})
+                    del pstep, proc
                 del sstep, smp
         res = {"batch": B, "active": nact, "ms_step": ms_step, "tokens_per_s": nact / ms_step * 1e3,
                "ms_linears_only": ms_lin, "ms_torch_glue": ms_torch,

@@ -3,6 +3,9 @@
 8, 64, 128.  Event-timed here (us per launch over --iters launches after --warmup); run it under
 `rocprofv3 --kernel-trace --stats -- python perf/sampling_kernels.py` for the per-kernel figures.  Beside them: the lm_head stream floor
 (vocab * k * 2 bytes at the stream rate qpal_calib_stream_read measures in this run) and the torch tail (norm, matmul, argmax).
+Also qpal_logit_process in place on the same logits, with a neutral processor and with every stage on (penalties on
+counted tokens, a mask, 64 bias entries per slot), beside a qpal_calib_stream_read of the bytes it moves: logits read, logits
+written, counts read = 12 bytes per logit.
 
     python perf/sampling_kernels.py [--vocab 128256] [--k 4096] [--rows 1 8 64 128] [--iters 20] [--warmup 5]
 """
@@ -66,6 +69,27 @@ def main(argv=None):
                                 "t0.8_p0.95": (0.8, 0, 0.95), "t0.7_k50_p0.9": (0.7, 50, 0.9)}.items():
             smp.temperature.fill_(t); smp.top_k.fill_(k); smp.top_p.fill_(p)
             res["us_sample_" + name] = timed(lambda: qp.sample(smp.logits, smp, ctr, out=tok), args.iters, args.warmup)
+        # the logit processor on these logits, in place; the stream yardstick reads as many bytes as it reads and writes
+        slots = torch.arange(rows, dtype=torch.int32, device=dev)
+        for name in ("neutral", "all_stages"):
+            proc = qp.LogitProcessor(rows, args.vocab, dev)
+            if name == "all_stages":
+                proc.count.copy_(torch.randint(0, 3, proc.count.shape, device=dev, generator=gen, dtype=torch.int32))
+                half = torch.arange(0, args.vocab, 2)
+                for b in range(rows):
+                    proc.set(b, repetition=1.3, presence=0.5, frequency=0.3)
+                    proc.set_mask(b, half)
+                    proc.set_bias(b, {int(i): 1.0 for i in half[:proc.bias_slots]})
+            res["us_logit_process_" + name] = timed(lambda: qp.logits.process(smp.logits, proc, slots, ctr), args.iters, args.warmup)
+            if name == "neutral":
+                moved = 3 * rows * args.vocab * 4
+                scratch = torch.zeros((moved + 15) // 16 * 4, dtype=torch.int32, device=dev)
+                s2, n2 = (ctypes.c_void_p * 1)(scratch.data_ptr()), (ctypes.c_long * 1)(scratch.numel() * 4)
+                res["logit_process_bytes"] = moved
+                res["us_stream_read_same_bytes"] = timed(
+                    lambda: qp._native.check(lib.qpal_calib_stream_read(s2, n2, 1, sink.data_ptr(), 2048, stream), "stream"), args.iters, args.warmup)
+                del scratch
+            del proc
         norm = lambda: torch.nn.functional.rms_norm(h.half(), (args.k,), w_ln, 1e-5)
         res["us_torch_tail_norm_matmul_argmax"] = timed(lambda: (norm() @ W.T).argmax(-1), args.iters, args.warmup)
         out["rows"].append(res)

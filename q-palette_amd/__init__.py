@@ -25,6 +25,9 @@ Layout:
   sampling.py      lm_head_logits (final norm + lm_head for up to 128 rows), sample / Sampler (temperature, top-k, top-p, seeded
                    draw; per-slot parameters on the device), reference_draw (the draw's contract in numpy fp64);
                    token_logprobs (log softmax of a row at one token, csrc/logprob.hip) and its contract reference_logprob
+  logits.py        logit processors between the lm_head and the draw: LogitProcessor (per-slot token mask, sparse bias, repetition /
+                   presence / frequency penalties and token counts on the device), process / observe (csrc/logit_proc.hip) and the
+                   contract reference_process (numpy fp32, bit for bit)
   packers.py       pack_trellis / pack_qweight / pack_qweight_{sq,vq}_simt on the C-ABI's host-side encoders
   quantize.py      TCQ quantiser: tail-biting Viterbi encoder (csrc/tcq_viterbi.hip) + LDLQ -> QTIPLinearTCQ
                    VQ / SQ quantiser: nearest-codeword LDLQ encoder (csrc/vq_encode.hip) -> VQLinearPack{TensorCore,SIMT}
@@ -70,6 +73,8 @@ from . import paging  # noqa: F401
 from .paging import PagedKVCache  # noqa: F401
 from . import sampling  # noqa: F401
 from .sampling import Sampler, lm_head_logits, reference_draw, reference_logprob, sample, token_logprobs  # noqa: F401
+from . import logits  # noqa: F401
+from .logits import LogitProcessor, reference_process  # noqa: F401
 from . import decoder  # noqa: F401
 from .decoder import DecodeStep, Prefill, RaggedStep, Score, SpeculativeStep, perplexity  # noqa: F401
 from . import speculative  # noqa: F401

@@ -52,6 +52,11 @@ All of them take `adapters=` too, a lora.LoraBank of the caches' slots (DESIGN.m
 adapter of its slot, bank.slot_adapter[slot] (-1: none) — one `lora_apply` launch behind the GEMV of each projection group, four
 per layer.  The rows' adapters are looked up on the device in every call, so bank.set(slot, adapter) between replays of a captured
 step takes effect without a new capture.
+
+`DecodeStep`, `Prefill` and `SpeculativeStep` take `processor=`, a logits.LogitProcessor of the caches' slots: token
+masks, a sparse logit bias and repetition / presence / frequency penalties between the lm_head and the draw.  A step counts the
+tokens it feeds (`qpal_logit_observe`), then processes the logits in place (`qpal_logit_process`), then draws: two more launches,
+everything on the device, and the processor's setters between replays of a captured step change the next draw.
 """
 import math
 
@@ -59,7 +64,7 @@ import torch
 
 from . import _native as nat
 from . import hadamard as had
-from . import linear, lora, ops, sampling
+from . import linear, logits, lora, ops, sampling
 from .attention import (attention_workspace, decode_attention, paged_decode_attention, paged_prefill_attention,
                         paged_ragged_prefill_attention, prefill_attention, prefill_workspace, ragged_prefill_attention, ragged_workspace)
 from .linear import multi_gemv
@@ -107,10 +112,10 @@ class _Rows:
     _launches_per = None  # "<class>: launches are per <what>" where a step has no launches per token
 
     def __init__(self, who, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows, sampler, block_table, slots=None,
-                 logits_tail=False, native_argmax=False, adapters=None):
+                 logits_tail=False, native_argmax=False, adapters=None, processor=None):
         """slots: the sequences of the caches where the caller fixes them (DecodeStep's B), else read off the caches or the table;
         logits_tail: the tail is qpal_lm_head_logits without a sampler too; native_argmax: `_argmax_tail` is the one-launch kernel;
-        adapters: a lora.LoraBank of these layers and slots, or None"""
+        adapters: a lora.LoraBank of these layers and slots, or None; processor: a logits.LogitProcessor of these slots, or None"""
         self.block_table = block_table
         self.slots = self._check_table(who, kcache, block_table, slots)
         self.adapters = self._check_adapters(who, adapters, self.slots, layers, embed)
@@ -119,6 +124,7 @@ class _Rows:
         self.sampler = self._check_sampler(sampler, self.slots, embed, lm_head)
         if logits_tail:
             self._check_lm_head(who, embed, lm_head)
+        self.processor = self._check_processor(who, processor, self.slots, embed, lm_head, sampler is not None or logits_tail)
         att, mlp = layers[0].self_attn, layers[0].mlp
         H, dev = att.hidden_size, embed.device
         self.layers, self.embed, self.norm, self.lm_head, self.inv_freq = layers, embed, norm, lm_head, inv_freq
@@ -172,6 +178,16 @@ class _Rows:
         _Rows._check_lm_head("sampler", embed, lm_head)
         return sampler
 
+    @staticmethod
+    def _check_processor(who, proc, B, embed, lm_head, logits_tail):
+        if proc is None:
+            return None
+        if not logits_tail:
+            raise nat.QpalError(f"{who}: a processor works on the logits of a sampler's tail: give the step a sampler")
+        if not isinstance(proc, logits.LogitProcessor) or proc.B != B or proc.vocab != lm_head.shape[0] or proc.device != embed.device:
+            raise nat.QpalError(f"{who}: processor must be a LogitProcessor of {B} slots of {lm_head.shape[0]} logits on {embed.device}")
+        return proc
+
     @property
     def launches_per_token(self):
         raise nat.QpalError(f"{self._launches_per} (9 per layer), not per token")
@@ -223,10 +239,16 @@ class _Rows:
             self._layer(i, *bufs)
         return bufs[0]
 
-    def _sample_tail(self, h32, smp, ctr, out_tok):
+    def _sample_tail(self, h32, smp, ctr, out_tok, row_slot=None, fed=None):
         """final norm + lm_head of every row of h32 into smp.logits, then one draw per row with the counters ctr: two launches; with
-        smp.logprob a third, the log-probability of the tokens just drawn (rows with ctr < 0 drew nothing and keep theirs)"""
+        smp.logprob a third, the log-probability of the tokens just drawn (rows with ctr < 0 drew nothing and keep theirs).  With a
+        processor (row_slot: the rows' slots) two launches in between: the tokens `fed` to the rows are counted where given, and the
+        logits are processed in place — the draw and the log-probabilities are those of the processed logits"""
         sampling.lm_head_logits(h32, self.norm.weight, self.norm.eps, self.lm_head, out=smp.logits)
+        if self.processor is not None:
+            if fed is not None:
+                logits.observe(self.processor, fed, row_slot, active=ctr)
+            logits.process(smp.logits, self.processor, row_slot, ctr)
         sampling.sample(smp.logits, smp, ctr, out=out_tok)
         if smp.logprob is not None:
             sampling.token_logprobs(smp.logits, out_tok, out=smp.logprob, active=ctr)
@@ -259,15 +281,20 @@ class DecodeStep(_Rows):
     a run of replays of the captured step, will write: the step reads the table on the device and never allocates.
     adapters: a lora.LoraBank of B slots — row b runs with adapter bank.slot_adapter[b], read by the launches themselves: four more
     launches per layer.  At batch 1 the interleaved up|gate epilogue and down_proj's staged rotation are then off (they never put
-    up | gate into memory: the swiglu_epilogue=False step); RMSNorm and the rotation stay inside the GEMV staging."""
+    up | gate into memory: the swiglu_epilogue=False step); RMSNorm and the rotation stay inside the GEMV staging.
+    processor: a logits.LogitProcessor of B slots (needs a sampler).  The tail becomes lm_head logits, observe — every active row's
+    fed token tok[b] is counted for slot b —, process in place on sampler.logits, the draw, then the log-probability launch of a
+    sampler with logprobs: sampler.logits and sampler.logprob are then the PROCESSED logits and the log-probabilities under them.
+    Two more launches.  The step counts every token it feeds, whatever the processor's count_prompt."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok, generic=False,
                  swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True, sampler=None, block_table=None,
-                 adapters=None):
+                 adapters=None, processor=None):
         B = tok.shape[0]
         self.batch1 = B == 1 and not generic
         super().__init__("DecodeStep", layers, embed, norm, lm_head, kcache, vcache, inv_freq, B, sampler, block_table, slots=B,
-                         native_argmax=self.batch1 and native_lm_head, adapters=adapters)
+                         native_argmax=self.batch1 and native_lm_head, adapters=adapters, processor=processor)
+        self._row_slot = None if processor is None else torch.arange(B, dtype=torch.int32, device=embed.device)  # row = slot
         if adapters is not None:
             self.row_adapter, swiglu_epilogue = adapters.slot_adapter, False  # row = slot
         if self.batch1 and not fusable(layers):
@@ -301,10 +328,12 @@ class DecodeStep(_Rows):
         """kernel launches of one step: per layer q|k|v, attention, o, up|gate, SwiGLU rotation, down (+ a rotation in front of
         q|k|v, o and up|gate where the GEMV cannot rotate; - the SwiGLU rotation where down_proj's staging runs it); + the norm /
         lm_head / argmax launch, or the lm_head logits and the draw with a sampler, + the log-probability launch of a sampler with
-        logprobs (the embedding row copy is a memcpy node); with adapters + 4 per layer, one per projection group"""
+        logprobs (the embedding row copy is a memcpy node); with adapters + 4 per layer, one per projection group; with a
+        processor + 2, observe and process"""
         per_layer = (5 if self.ug_il and self.ug_il[0][2] else 6) if self.rot_in_gemv else 9
         per_layer += 4 if getattr(self, "adapters", None) is not None else 0  # (arithmetic on the configuration: stand-ins may lack it)
         tail = 1 if self.sampler is None else (2 if self.sampler.logprob is None else 3)
+        tail += 2 if getattr(self, "processor", None) is not None else 0
         return per_layer * len(self.layers) + tail
 
     def _gemv(self, proj, x, su, scale, rms=None, **kw):
@@ -350,7 +379,7 @@ class DecodeStep(_Rows):
     def __call__(self):
         self._run_layers(self.tok)
         if self.sampler is not None:
-            self._sample_tail(self.h32, self.sampler, self.pos, self.out_tok)
+            self._sample_tail(self.h32, self.sampler, self.pos, self.out_tok, row_slot=self._row_slot, fed=self.tok)
         else:
             self._argmax_tail(self.h32, self.out_tok)
 
@@ -376,18 +405,24 @@ class Prefill(_Rows):
     addresses them (paged_prefill_attention), context = max_pages * page_size.  The caller has reserved pages for positions pos0 ..
     pos0 + N - 1 of the slot (PagedKVCache.reserve(slot, pos0 + N)) before the call.
 
-    adapters: a lora.LoraBank of the caches' slots — every row of the call runs with bank.slot_adapter[slot], copied on the device."""
+    adapters: a lora.LoraBank of the caches' slots — every row of the call runs with bank.slot_adapter[slot], copied on the device.
+
+    processor: the logits.LogitProcessor of that DecodeStep (needs a sampler).  With processor.count_prompt the tokens of the call
+    are counted for the slot, chunk by chunk (one observe launch each); the last row's logits are processed with the slot's state
+    before the draw.  The counts are not reset: a new request calls processor.reset(slot) first."""
 
     _launches_per = "Prefill: launches are per chunk"
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, native_lm_head=True, sampler=None,
-                 block_table=None, adapters=None):
+                 block_table=None, adapters=None, processor=None):
         if not 1 <= int(chunk) <= 128:
             raise nat.QpalError(f"Prefill: chunk must be in 1 .. 128, got {chunk}")
         self.chunk = int(chunk)
         dev, H = embed.device, embed.shape[1]
         super().__init__("Prefill", layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.chunk, sampler, block_table,
-                         native_argmax=native_lm_head and H in (2048, 4096, 8192) and lm_head.data_ptr() % 16 == 0, adapters=adapters)
+                         native_argmax=native_lm_head and H in (2048, 4096, 8192) and lm_head.data_ptr() % 16 == 0, adapters=adapters,
+                         processor=processor)
+        self._row_slot = None if processor is None else torch.zeros(1, dtype=torch.int32, device=dev)  # the call's slot
         self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
         self.out_tok = torch.zeros(1, dtype=torch.int64, device=dev)
         self.ctr = torch.zeros(1, dtype=torch.int64, device=dev)  # with a sampler: the last prompt row's position
@@ -416,6 +451,8 @@ class Prefill(_Rows):
         if not 0 <= int(slot) < self.slots:
             raise nat.QpalError(f"{who}: slot {slot} outside the caches' {self.slots} sequences")
         self.slot = int(slot)
+        if self.processor is not None:
+            self._row_slot.fill_(self.slot)
         if self.adapters is not None:
             self.row_adapter.copy_(self.adapters.slot_adapter[self.slot:self.slot + 1].expand(self.chunk))
         if isinstance(pos0, torch.Tensor):
@@ -431,6 +468,8 @@ class Prefill(_Rows):
         for c in range(0, N, self.chunk):
             n = min(self.chunk, N - c)
             h32 = self._run_layers(tokens[c:c + n], n)
+            if self.processor is not None and self.processor.count_prompt:
+                logits.observe(self.processor, tokens[c:c + n], self.slot)
             self.pos += n
             yield c, h32
         self.last32.copy_(h32[n - 1:n])
@@ -441,7 +480,7 @@ class Prefill(_Rows):
             pass
         if self.sampler is not None:
             torch.sub(self.pos, 1, out=self.ctr)
-            self._sample_tail(self.last32, self.sampler.slot(self.slot), self.ctr, self.out_tok)
+            self._sample_tail(self.last32, self.sampler.slot(self.slot), self.ctr, self.out_tok, row_slot=self._row_slot)
         else:
             self._argmax_tail(self.last32, self.out_tok)
         return self.out_tok
@@ -518,18 +557,22 @@ class RaggedStep(_Rows):
     step writes.
 
     adapters: a lora.LoraBank of the caches' slots — a row of segment s runs with bank.slot_adapter[seq[s]], rows of no segment
-    with none; the map row -> segment -> slot -> adapter is made on the device in every call."""
+    with none; the map row -> segment -> slot -> adapter is made on the device in every call.
+
+    processor: not on a RaggedStep (QpalError): a prompt chunk's rows would have to be counted row by row; SpeculativeStep has one."""
 
     _launches_per = "RaggedStep: launches are per step"
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=128, segments=16, sampler=None, block_table=None,
-                 adapters=None):
+                 adapters=None, processor=None):
         who = type(self).__name__
+        if processor is not None and not isinstance(self, SpeculativeStep):
+            raise nat.QpalError("RaggedStep: no processor on a ragged step (DecodeStep, Prefill and SpeculativeStep take one)")
         if not 1 <= int(rows) <= 128 or not 1 <= int(segments) <= 128:
             raise nat.QpalError(f"{who}: rows and segments must be in 1 .. 128, got {rows}, {segments}")
         self.rows, self.segments = int(rows), int(segments)
         super().__init__(who, layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.rows, sampler, block_table, logits_tail=True,
-                         adapters=adapters)
+                         adapters=adapters, processor=processor)
         dev = embed.device
         self._row_id = torch.arange(self.rows, dtype=torch.int32, device=dev)
         self._no_adapter = torch.full((self.rows,), -1, dtype=torch.int32, device=dev)
@@ -655,10 +698,19 @@ class SpeculativeStep(RaggedStep):
     logprob fp32 [B, draft + 1]), the emitted tokens' log-probabilities, from one token_logprobs launch on the rows.
     No cache rollback: the next step starts at the new pending position and rewrites the K / V rows a rejected draft left before
     anything reads them.  block_table: a paged cache as for DecodeStep; the caller has reserved the pages of min(limit, n_tok +
-    draft) positions of every slot before the call.  adapters: as for RaggedStep (the rows of slot b run with slot b's adapter)."""
+    draft) positions of every slot before the call.  adapters: as for RaggedStep (the rows of slot b run with slot b's adapter).
+
+    processor: a logits.LogitProcessor of the caches' slots.  A fed draft may be rejected, so nothing is counted
+    when feeding: `begin` resets the slot's counts and counts the known tokens, the pending one included (count_prompt=False: it
+    only resets); every row's logits are processed with its slot's state and, as extras, the guessed tokens in front of it in its
+    segment — what sequential decoding would have counted by then; after the accept the emitted tokens are counted.  So count[b] is
+    always the histogram of the counted part of hist[b][0 .. n_tok[b]), and the stream stays the sequential one.  `release` leaves
+    the counts alone.  A slot's mask holds for all rows of its segment: it cannot follow a grammar inside a multi-token step — a
+    grammar-driven caller uses DecodeStep, or draft=0.  More launches per step: process, observe, and two small torch ops that build
+    observe's active vector from n_out."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, draft=4, gram=(2, 4), rows=None, sampler=None,
-                 block_table=None, history=None, adapters=None):
+                 block_table=None, history=None, adapters=None, processor=None):
         B, K = self._check_table("SpeculativeStep", kcache, block_table), int(draft)
         if not 0 <= K <= 15 or len(gram) != 2 or not 1 <= int(gram[0]) <= int(gram[1]) <= 8:
             raise nat.QpalError(f"SpeculativeStep: draft must be in 0 .. 15 and 1 <= gram[0] <= gram[1] <= 8, got {draft}, {gram}")
@@ -667,7 +719,7 @@ class SpeculativeStep(RaggedStep):
             raise nat.QpalError(f"SpeculativeStep: rows must be in B = {B} .. 128, got {rows}")
         self.draft_len, self.gram = K, (int(gram[0]), int(gram[1]))
         super().__init__(layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=rows, segments=B, sampler=sampler,
-                         block_table=block_table, adapters=adapters)
+                         block_table=block_table, adapters=adapters, processor=processor)
         dev = embed.device
         self.history = self.context if history is None else int(history)
         if self.history < 1:
@@ -682,6 +734,10 @@ class SpeculativeStep(RaggedStep):
         self.row_slot, self.row_ctr = torch.full((rows,), -1, dtype=i32, device=dev), torch.full((rows,), -1, dtype=i64, device=dev)
         self.n_draft, self.n_out, self.n_acc = (torch.zeros(B, dtype=i32, device=dev) for _ in range(3))
         self._gather = torch.zeros(rows, dtype=i64, device=dev)  # the rows' embedding indices when the caller drafts
+        if processor is not None:  # the observe launch behind the accept: entry (b, i) of out_tok counts for slot b iff i < n_out[b]
+            self._obs_slot = torch.arange(B, dtype=i32, device=dev).repeat_interleave(K + 1).contiguous()
+            self._obs_active = torch.zeros(B * (K + 1), dtype=i64, device=dev)
+            self._lane1 = torch.arange(1, K + 2, dtype=i64, device=dev)
 
     def _setup_tail(self, vocab, dev, logprobs):
         """a draw at every ROW and up to draft + 1 tokens per slot: no last rows, no per-segment counters"""
@@ -713,6 +769,10 @@ class SpeculativeStep(RaggedStep):
         if not -1 <= int(eos) < self.lm_head.shape[0]:
             raise nat.QpalError(f"SpeculativeStep.begin: eos must be -1 or a token id below {self.lm_head.shape[0]}, got {eos}")
         self.n_tok[int(slot)], self.limit[int(slot)], self.eos[int(slot)] = n, limit, int(eos)
+        if self.processor is not None:
+            self.processor.reset(slot)
+            if self.processor.count_prompt:
+                self.processor.count_tokens(slot, toks)
 
     def release(self, slot):
         """the slot has no sequence: no rows in the steps that follow"""
@@ -731,6 +791,8 @@ class SpeculativeStep(RaggedStep):
         self._map_rows(self.seq, self.row0)
         self._run_layers(tokens)
         sampling.lm_head_logits(self.h32, self.norm.weight, self.norm.eps, self.lm_head, out=self.draw.logits)
+        if self.processor is not None:
+            logits.process(self.draw.logits, self.processor, self.row_slot, self.row_ctr, tokens=self.tokens, row0=self.row0)
         if self.sampler is not None:
             self._gather_draw(self.row_slot.to(torch.int64).clamp(min=0))
         sampling.sample(self.draw.logits, self.draw, self.row_ctr, out=self.drawn)
@@ -740,6 +802,9 @@ class SpeculativeStep(RaggedStep):
             torch.index_select(self.draw.logprob, 0, rows.reshape(-1), out=self.out_logprob.view(-1))
         spec.spec_accept(self.tokens, self.drawn, self.seq, self.row0, self.hist, self.n_tok, self.limit, self.eos, self.out_tok,
                          self.n_out, self.n_acc)
+        if self.processor is not None:
+            torch.sub(self.n_out.to(torch.int64)[:, None], self._lane1[None, :], out=self._obs_active.view(-1, self.draft_len + 1))
+            logits.observe(self.processor, self.out_tok.view(-1), self._obs_slot, active=self._obs_active)
         if self.out_logprob is not None:
             return self.out_tok, self.n_out, self.out_logprob
         return self.out_tok, self.n_out
