@@ -737,6 +737,36 @@ __device__ __forceinline__ void dispatch_kv(int kv, F &&f) {
     });
 }
 
+// The row finish of the fused kernel: the lead wave's sum of its run's partials f[0], f[stride], ..., f[(run - 1) * stride] (LDS), added
+// in wave order — v = 0; v += p0; v += p1; ... — the order every output is pinned to.  The run length is a runtime value (wave-uniform,
+// <= 16); as a rolled loop this was one LDS round trip per partial, each waited for before the next was requested, at the very end of
+// the launch.  Here the run is cut into uniform blocks of 16, 8, 4, 2 and 1 partials after the bits of its length, walked from the
+// first partial upwards: the loads of a block are all requested before its first add, so a run of 16 costs one round trip and sixteen
+// dependent adds.  ONE: stride is the constant 32 (batch 1: the offsets inside a block are immediates).
+template <int N, bool ONE>
+__device__ __forceinline__ float run_sum_block(const float *f, int stride, float v) {
+    float t[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) t[i] = f[i * (ONE ? 32 : stride)];
+    // (left alone the scheduler issues the second half of a block of 16 — a second base address — behind the first adds: two round trips)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < N; i++) v += t[i];
+    return v;
+}
+template <bool ONE>
+__device__ __forceinline__ float run_sum(const float *f, int stride, int run_waves) {
+    float v = 0.f;
+    static_for<0, 5>([&](auto ic) {
+        constexpr int N = 16 >> decltype(ic)::value;
+        if (run_waves & N) {  // (wave-uniform)
+            v = run_sum_block<N, ONE>(f, stride, v);
+            f += N * (ONE ? 32 : stride);
+        }
+    });
+    return v;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Fused decode + GEMV / skinny GEMM, 1 <= n <= 8*NBG.  1024 threads (16 waves, 4 per SIMD), one workgroup per
 // CU (LDS-bound).  C2 == void: single stream.  Otherwise combt (columns [0,col2) from c1 via C1, the rest from
@@ -1444,8 +1474,7 @@ __global__ QPAL_GEMV_BOUNDS(NBG) void tc_gemv_kernel(const uint16_t *ex, const v
             const float osc = fosc;
             if constexpr (ROT == 1) {
                 if (p.act_out) {  // SwiGLU of an interleaved up | gate layer: up row in lanes r, the gate row behind it in lanes r + 32
-                    float v = 0.f;
-                    for (int qq = 0; qq < run_waves; qq++) v += fred[qq * 32];
+                    const float v = run_sum<true>(fred, 32, run_waves);
                     const float mine = (float)(_Float16)(v * osc);           // the reference's fp16 up / gate
                     const float gate = lane_xor<32>(mine);  // (lanes r < 32 read lane r + 32: a permlane swap, not an LDS permute)
                     if (fin && fhi == 0 && lead2) {  // (the gate row's own lead wave has nothing to do here)
@@ -1457,15 +1486,28 @@ __global__ QPAL_GEMV_BOUNDS(NBG) void tc_gemv_kernel(const uint16_t *ex, const v
                     continue_item = true;
                 }
             }
-            if (!continue_item && fin)
-            for (int b = 0; b < p.n; b++) {
-                float v = 0.f;
-                for (int qq = 0; qq < run_waves; qq++) v += fred[(qq * p.n + b) * 32];
-                float *dst = fdst + (long)b * p.ldo;
-                v *= osc;
-                if (row_shared) atomicAdd(dst, v);
-                else if (p.accumulate) *dst += v;  // the residual add of a decoder block: out is the fp32 residual stream
-                else *dst = v;
+            if (!continue_item && fin) {
+                // (run_sum: the run's partials requested together, added in wave order; batch 1 reads them at immediate offsets)
+                auto put = [&](int b, float v) {
+                    float *dst = fdst + (long)b * p.ldo;
+                    v *= osc;
+                    if (row_shared) atomicAdd(dst, v);
+                    else if (p.accumulate) *dst += v;  // the residual add of a decoder block: out is the fp32 residual stream
+                    else *dst = v;
+                };
+                // (the rotating kernels run at batch 1 only — host: rot_ok — and have no registers to spare for the strides of the
+                // general form: it stays the rolled loop there)
+                if (NBG == 1 && p.n == 1) put(0, run_sum<true>(fred, 32, run_waves));
+                else
+                    for (int b = 0; b < p.n; b++) {
+                        if constexpr (ROT == 1 || ROT == 2) {
+                            float v = 0.f;
+                            for (int qq = 0; qq < run_waves; qq++) v += fred[(qq * p.n + b) * 32];
+                            put(b, v);
+                        } else {
+                            put(b, run_sum<false>(fred + b * 32, p.n * 32, run_waves));
+                        }
+                    }
             }
         }
         QPAL_STAMP(7);
