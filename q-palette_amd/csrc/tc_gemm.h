@@ -9,18 +9,16 @@
 // layout the MFMA B fragments are read in (one ds_read_b128 per batch group and ksub).  A wave sees its whole K range, so
 // there is no cross-wave reduction; split-K over workgroups (atomics) only where a layer has too few rows to fill the chip.
 //
-// Decode, MFMA mapping (virtual rows: tile row x column half), codecs and packed formats are tc_kernels.h's — same arithmetic
-// order per (row, batch) up to the K split.  Replaces, for bs > 8, the reference's decode-to-HBM + cuBLAS path
+// ONE kernel body, tc_gemm_kernel<C1, C2, Map>: the MFMA fragment mapping is a parameter — GemmHalves below (batches <= 16: the GEMV's
+// virtual rows, tile row x column half) or G16Map (tc_gemm16.h: 16 real rows x 16 batch rows, batches 17..128).  Decode, codecs and
+// packed formats are tc_kernels.h's — same arithmetic order per (row, batch) up to the K split.  Replaces, for bs > 8, the reference's decode-to-HBM + cuBLAS path
 // (lib/linear/tcq_linear.py:75-84, vq_linear.py:60-66) up to the batch where that path wins again.
 #pragma once
 #include "tc_kernels.h"
 
 namespace qpal {
 
-#ifndef QPAL_GEMM_WAVES  // (experiment: -DQPAL_GEMM_WAVES=16 — four waves per SIMD, <= 128 VGPRs)
-#define QPAL_GEMM_WAVES 8
-#endif
-constexpr int kGemmWaves = QPAL_GEMM_WAVES;
+constexpr int kGemmWaves = 8;               // waves = supertile rows of a workgroup
 constexpr int kGemmXRow = 144;              // bytes per (batch row, column half) row of a step's x tile: 128 + 16 pad (bank spread)
 constexpr int kGemmXGroup = 16 * kGemmXRow;  // one batch group (8 rows x 2 column halves)
 
@@ -38,27 +36,13 @@ inline int gemm_item_table(const TcMultiParams &mp) {
 // geometry of one job (host: plan_gemm): items = ceil(nrows / 8) * sk, item -> (row group, K split)
 //   uses TcParams: nrows, nsc1/2, st1/2, col2, sk, out/ldo, wscale/oscale, accumulate, c1/c2, x, tab, n, k
 
-// Software-pipelined step (QPAL_GEMM_PIPE, default): a wave issues in order, and the compiler's own order per A fragment is
+// Software-pipelined step: a wave issues in order, and the compiler's own order per A fragment is
 // decode -> wait for the gathers -> NBG MFMAs, which leaves the matrix pipe idle during the decode and the VALU / LDS idle during
 // the MFMAs unless the SIMD's other wave fills the gaps.  Here fragment t + 1 (t = 4 ksub + 2 msub + jl) is decoded BETWEEN the
 // MFMAs of fragment t — the order is pinned with sched_barrier fences, one weight pair in front of each of the first MFMAs, the
 // rest of the MFMAs cover the gather latency — and the B fragments of ksub 1 replace those of ksub 0 one batch group at a time
 // behind their last use.  Measured: +-0.5 % at every batch (profiles/r03_gemm_knockouts.txt) — the two waves of a SIMD did
 // overlap each other's phases; what a step loses is the lockstep wait at the barrier.
-#ifndef QPAL_GEMM_PIPE
-#define QPAL_GEMM_PIPE 1
-#endif
-// Timing experiments only (results invalid): QPAL_GEMM_KO bit 1: no MFMAs (operands xor-folded), 2: no B-fragment reads, 4: no x
-// staging inside the loop, 8: no per-step barrier, 32: no weight loads inside the loop, 64: no output stores / atomics, 128: no codebook image build, 256: no steps at all (what a launch costs before and after them); -DQPAL_KO_GATHER: no codebook gathers.
-#ifndef QPAL_GEMM_SLOTS
-#define QPAL_GEMM_SLOTS 4
-#endif
-#ifndef QPAL_GEMM_BUILD_U
-#define QPAL_GEMM_BUILD_U 1
-#endif
-#ifndef QPAL_GEMM_KO
-#define QPAL_GEMM_KO 0
-#endif
 template <class Codec, int T, int I>
 __device__ __forceinline__ uint32_t gemm_pair(const uint32_t *lut, uint32_t laneoff, const uint32_t (&w)[Codec::NW]) {
     constexpr int g = T >> 1, jl = T & 1;
@@ -69,78 +53,86 @@ __device__ __forceinline__ uint32_t gemm_pair(const uint32_t *lut, uint32_t lane
 }
 
 template <class Codec, int NBG>
-__device__ __forceinline__ void gemm_step_pipe(const uint32_t *lut, uint32_t laneoff, const uint32_t (&w)[Codec::NW],
-                                               const unsigned char *xt, int lane, Acc<NBG> &acc) {
+__device__ __forceinline__ void gemm_step(const uint32_t *lut, uint32_t laneoff, const uint32_t (&w)[Codec::NW],
+                                          const unsigned char *xt, int lane, float4_t (&acc)[NBG][4]) {
     const unsigned char *xl = xt + (lane & 15) * kGemmXRow + (lane >> 4) * 32;
     u32x4 xb[NBG];
     static_for<0, NBG>([&](auto bc) {
-        if constexpr (QPAL_GEMM_KO & 2) xb[decltype(bc)::value] = u32x4{laneoff, (uint32_t)lane, laneoff, (uint32_t)lane};
-        else xb[decltype(bc)::value] = *reinterpret_cast<const u32x4 *>(xl + decltype(bc)::value * kGemmXGroup);
+        xb[decltype(bc)::value] = *reinterpret_cast<const u32x4 *>(xl + decltype(bc)::value * kGemmXGroup);
     });
     uint32_t a[4], an[4];
     static_for<0, 4>([&](auto ic) { a[decltype(ic)::value] = gemm_pair<Codec, 0, decltype(ic)::value>(lut, laneoff, w); });
-    // pairs of the next fragment decoded in front of MFMA m of this one: all four in front of the first half of the MFMAs
-    constexpr int PER = NBG >= 8 ? 1 : NBG >= 4 ? 2 : 4;  // pairs per slot
+    // the four pairs of the next fragment are decoded in front of the first MFMA of this one
     static_for<0, 8>([&](auto tc) {
         constexpr int t = decltype(tc)::value;
         constexpr int msub = (t >> 1) & 1, jl = t & 1;
         static_for<0, NBG>([&](auto bc) {
             constexpr int m = decltype(bc)::value;
-            if constexpr (t < 7 && m * PER < 4) {
-                static_for<0, PER>([&](auto ic) {
-                    constexpr int i = m * PER + decltype(ic)::value;
-                    an[i] = gemm_pair<Codec, t + 1, i>(lut, laneoff, w);
-                });
+            if constexpr (t < 7 && m == 0) {
+                static_for<0, 4>([&](auto ic) { an[decltype(ic)::value] = gemm_pair<Codec, t + 1, decltype(ic)::value>(lut, laneoff, w); });
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (QPAL_GEMM_KO & 1) {
-                if constexpr (m == 0 || t == 0 || t == 4) {
-                    const uint32_t f = m == 0 ? a[0] ^ a[1] ^ a[2] ^ a[3] : 0u;
-                    const uint32_t fx = (t == 0 || t == 4) ? xb[m].x ^ xb[m].y ^ xb[m].z ^ xb[m].w : 0u;
-                    acc.v[m][msub * 2 + jl][0] = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, acc.v[m][msub * 2 + jl][0]) ^ f ^ fx);
-                }
-            } else
-            acc.v[m][msub * 2 + jl] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                __builtin_bit_cast(half8_t, u32x4{a[0], a[1], a[2], a[3]}), __builtin_bit_cast(half8_t, xb[m]), acc.v[m][msub * 2 + jl], 0, 0, 0);
-            if constexpr (t == 3 && !(QPAL_GEMM_KO & 2)) xb[m] = *reinterpret_cast<const u32x4 *>(xl + m * kGemmXGroup + 16);  // ksub 1, behind the last use of ksub 0
+            acc[m][msub * 2 + jl] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                __builtin_bit_cast(half8_t, u32x4{a[0], a[1], a[2], a[3]}), __builtin_bit_cast(half8_t, xb[m]), acc[m][msub * 2 + jl], 0, 0, 0);
+            if constexpr (t == 3) xb[m] = *reinterpret_cast<const u32x4 *>(xl + m * kGemmXGroup + 16);  // ksub 1, behind the last use of ksub 0
             __builtin_amdgcn_sched_barrier(0);
         });
         static_for<0, 4>([&](auto ic) { a[decltype(ic)::value] = an[decltype(ic)::value]; });
     });
 }
 
-template <class Codec, int NBG>
-__device__ __forceinline__ void gemm_step(const uint32_t *lut, uint32_t laneoff, const uint32_t (&w)[Codec::NW],
-                                          const unsigned char *xt, int lane, Acc<NBG> &acc) {
-    if constexpr (QPAL_GEMM_PIPE != 0) return gemm_step_pipe<Codec, NBG>(lut, laneoff, w, xt, lane, acc);
-    const unsigned char *xl = xt + (lane & 15) * kGemmXRow + (lane >> 4) * 32;
-    static_for<0, 2>([&](auto kc) {
-        constexpr int ksub = decltype(kc)::value;
-        __builtin_amdgcn_sched_barrier(0);  // one ksub's B fragments at a time (hoisting the second set spills at 8 batch groups)
-        u32x4 xb[NBG];
-        static_for<0, NBG>([&](auto bc) {
-            constexpr int grp = decltype(bc)::value;
-            xb[grp] = *reinterpret_cast<const u32x4 *>(xl + grp * kGemmXGroup + ksub * 16);
-        });
-        static_for<0, 2>([&](auto mc) {
-            constexpr int msub = decltype(mc)::value;
-            constexpr int g = ksub * 2 + msub;
-            uint32_t nh = 0u;
-            if constexpr (Codec::kNeedsNext) nh = row16_next(Codec::template head<g>(w));
-            static_for<0, 2>([&](auto jc) {
-                constexpr int jl = decltype(jc)::value;
-                const u32x4 a{Codec::template pair<g, jl>(lut, laneoff, w, nh), Codec::template pair<g, jl + 4>(lut, laneoff, w, nh),
-                              Codec::template pair<g, jl + 2>(lut, laneoff, w, nh), Codec::template pair<g, jl + 6>(lut, laneoff, w, nh)};
-                const half8_t afrag = __builtin_bit_cast(half8_t, a);
-                static_for<0, NBG>([&](auto bc) {
-                    constexpr int grp = decltype(bc)::value;
-                    acc.v[grp][msub * 2 + jl] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                        afrag, __builtin_bit_cast(half8_t, xb[grp]), acc.v[grp][msub * 2 + jl], 0, 0, 0);
-                });
+// ---- The fragment mapping of a kernel instance: a struct of constants and functions, everything ELSE is written once in
+// tc_gemm_kernel.  A mapping decides how many batch rows a group has and where a staged 16-byte chunk of x lands in LDS, the
+// accumulators' shape, the step, which way a dead chunk of a tile becomes zeros, and how a group's accumulators reach the per-wave
+// [ROWS][32] fp32 scratch of the epilogue.
+// GemmHalves<NBG> (batches <= 16): the GEMV's mapping — an MFMA's 16 rows are 8 tile rows x 2 column halves, its 16 columns 8 batch
+// rows x 2 halves.  G16Map<NG> (tc_gemm16.h): 16 real rows x 16 batch rows.  gemm_map<NBG> (tc_gemm16.h) picks one.
+template <int NBG>
+struct GemmHalves {
+    static_assert(NBG == 1 || NBG == 2, "more batch groups run on the 16-row mapping (tc_gemm16.h)");
+    static constexpr int ROWS = 8, GROUPS = NBG;    // batch rows per group, groups
+    static constexpr int XBUF = NBG * kGemmXGroup;  // bytes of one step's x tile
+    static constexpr int SCRATCH = 1024;            // bytes of a wave's epilogue scratch
+    struct Accum {
+        float4_t v[NBG][4];  // [group][msub * 2 + jl]
+        __device__ __forceinline__ void zero() {
+            static_for<0, NBG>([&](auto bc) {
+                static_for<0, 4>([&](auto ac) { v[decltype(bc)::value][decltype(ac)::value] = float4_t{0.f, 0.f, 0.f, 0.f}; });
             });
+        }
+    };
+    // staging lane j of a batch row -> its 16-byte piece q of the step's 128 columns
+    // (Q_PERMUTED = false: the kernel then uses j itself.  Through a function, however trivial, the compiler meets the identity only
+    // after its early common-subexpression pass, and 15 of the VQ/SQ kernels end up with a 64-bit multiply-add and 2 more VGPRs)
+    static constexpr bool Q_PERMUTED = false;
+    static __device__ __forceinline__ int chunk_q(int j) { return j; }
+    // piece q = (supertile col sc = q >> 2, ksub = (q >> 1) & 1, jh = q & 1): halves 0..3 belong to column half u = 0, 4..7 to u = 1
+    static __device__ __forceinline__ void store_chunk(unsigned char *buf, int b, int q, const u32x4 &v) {
+        unsigned char *d = buf + (b >> 3) * kGemmXGroup + (2 * (b & 7)) * kGemmXRow + (q >> 2) * 32 + ((q >> 1) & 1) * 16 + (q & 1) * 8;
+        *reinterpret_cast<u32x2 *>(d) = u32x2{v.x, v.y};
+        *reinterpret_cast<u32x2 *>(d + kGemmXRow) = u32x2{v.z, v.w};
+    }
+    // a dead chunk of a tile (batch row >= n, column past the stream) is zeroed in its staging register, not selected at the store:
+    // see store_x in tc_gemm_kernel
+    static constexpr bool ZERO_IN_REG = true;
+    template <class Codec>
+    static __device__ __forceinline__ void step(const uint32_t *lut, uint32_t laneoff, const uint32_t (&w)[Codec::NW], const unsigned char *xt,
+                                                int lane, Accum &acc) {
+        gemm_step<Codec, NBG>(lut, laneoff, w, xt, lane, acc.v);
+    }
+    // lane (q, cidx = 2 b' + u) holds, for batch row 8 GRP + b' and a = msub * 2 + jl, D[4 q + r][cidx]; valid where (r & 1) == u: on
+    // even lanes own r = 0 / 2 plus the odd neighbour's r = 1 / 3 are tile rows 8 a + 2 q + {0, 1}
+    template <int GRP>
+    static __device__ __forceinline__ void scatter(float *scr, const Accum &acc, int q, int cidx) {
+        static_for<0, 4>([&](auto ac) {
+            constexpr int a = decltype(ac)::value;
+            const float4_t d = acc.v[GRP][a];
+            const float v0 = d[0] + lane_xor<1>(d[1]);
+            const float v1 = d[2] + lane_xor<1>(d[3]);
+            if ((cidx & 1) == 0) *reinterpret_cast<float2 *>(scr + (cidx >> 1) * 32 + 8 * a + 2 * q) = float2{v0, v1};
         });
-    });
-}
+    }
+};
 
 // which stream a global step of a row belongs to, and where its columns start
 struct GemmStep {
@@ -166,7 +158,7 @@ __device__ __forceinline__ GemmStep gemm_where(const TcParams &p, int g) {
 // offset, and the range check of the descriptor does the clamping: batch rows >= n, supertile columns past the end of a stream and
 // the re-read of dead chunks all return zeros (the per-step part is added to the VECTOR offset: the scalar offset is not range-checked).
 // (the helpers — buf_rsrc_t, gemm_rsrc, buf_load_words_nt, gemm_w_lane_off, gemm_w_step_bytes — live in tc_kernels.h: the fused GEMV uses them too)
-template <class C1, class C2, int NBG>
+template <class C1, class C2, class Map>
 // eie: the launch's item table packed into one PRELOADED dword (gemm_item_table; tc_kernels.h early_args does the same for the GEMV
 // kernels): a workgroup knows the job of its first item before the kernel-argument block has arrived and fetches THAT job's
 // parameters in the first scalar-load round trip (every workgroup used to scan the table after one round trip and fetch its job
@@ -175,17 +167,17 @@ __global__ __launch_bounds__(64 * kGemmWaves) void tc_gemm_kernel(const int eie,
     constexpr bool TWO = !std::is_void_v<C2>;
     using CB = std::conditional_t<TWO, C2, C1>;
     constexpr int W = kGemmWaves, NT = 64 * W;
-    constexpr int XBUF = NBG * kGemmXGroup;
-    constexpr int NCH = NBG * 8 * 16;                   // 16-byte chunks of one step's x tile
+    constexpr int XBUF = Map::XBUF;
+    constexpr int NCH = Map::GROUPS * Map::ROWS * 16;   // 16-byte chunks of one step's x tile
     constexpr int CPT = (NCH + NT - 1) / NT;            // chunks per thread
     constexpr int NWMAX = C1::NW > CB::NW ? C1::NW : CB::NW;
     // Tile slots: 4 where they fit beside the codebook image (two steps per buffer: the workgroup barrier — 9 % of a batch-64 token
-    // as a per-step barrier, knock-out 8 — falls after every SECOND step, tiles are staged two steps ahead), else 2 (one per step)
+    // as a per-step barrier — falls after every SECOND step, tiles are staged two steps ahead), else 2 (one per step)
     // (round 5, measured and not kept: two batch groups on TWO slots — 73 KiB of LDS, < 128 VGPRs — so that two workgroups share a CU as at
     // one batch group: +-0 on Llama-8B at batch 12 / 16, -7 % on the 70B shapes at batch 16; profiles/r05_ab_batched_path.txt)
-    constexpr int NSLOT = (QPAL_GEMM_SLOTS == 4 && C1::LDS_DWORDS * 4 + 4 * XBUF <= 156 * 1024) ? 4 : 2;
+    constexpr int NSLOT = C1::LDS_DWORDS * 4 + 4 * XBUF <= 156 * 1024 ? 4 : 2;
     constexpr int AHEAD = NSLOT / 2;
-    constexpr int XT = NSLOT * XBUF >= W * 1024 ? NSLOT * XBUF : W * 1024;  // the x buffers double as the epilogue's per-wave transposition scratch
+    constexpr int XT = NSLOT * XBUF >= W * Map::SCRATCH ? NSLOT * XBUF : W * Map::SCRATCH;  // the x buffers double as the epilogue's per-wave transposition scratch
     // ONE block, the codebook image FIRST: at LDS address 0 a gather address is one v_and_or_b32 (hash bits | copy of this lane); as two
     // arrays the compiler put the tiles first and every gather paid a v_and_b32 + v_add_u32 (32 more vector instructions per step)
     __shared__ __attribute__((aligned(16))) unsigned char smem[C1::LDS_DWORDS * 4 + XT];
@@ -246,41 +238,55 @@ __global__ __launch_bounds__(64 * kGemmWaves) void tc_gemm_kernel(const int eie,
         const buf_rsrc_t rs_w1 = gemm_rsrc(sv1.base, sv1.nsc * 64 * C1::NW);
         const buf_rsrc_t rs_w2 = gemm_rsrc(sv2.base, sv2.nsc * 64 * CB::NW);
         const uint32_t wl1 = gemm_w_lane_off<C1::NW>(lane), wl2 = gemm_w_lane_off<CB::NW>(lane);
+        // (the chunk's column block is spelled out at each of its four uses: through one helper, a kernel-local lambda included, the
+        // compiler inlines it after its early passes and the kernels of every mapping come out different from the two-kernel build)
         uint32_t xvo[CPT];  // byte offset of this thread's chunk r inside x, without the step's column base
 #pragma unroll
         for (int r = 0; r < CPT; r++) {
             const int id = tid + r * NT, b = id >> 4;
-            xvo[r] = (id < NCH && b < p.n) ? (uint32_t)(b * p.k + 8 * (id & 15)) * 2u : kBufDead;
+            xvo[r] = (id < NCH && b < p.n) ? (uint32_t)(b * p.k + 8 * (Map::Q_PERMUTED ? Map::chunk_q(id & 15) : (id & 15))) * 2u : kBufDead;
         }
         auto load_w = [&](int g, uint32_t(&dst)[NWMAX]) {
             const GemmStep st = gemm_where(p, g);
             if (TWO && st.on2) buf_load_words_nt<CB::NW>(rs_w2, wl2 + (uint32_t)st.s * gemm_w_step_bytes<CB::NW>(), reinterpret_cast<uint32_t(&)[CB::NW]>(dst));
             else buf_load_words_nt<C1::NW>(rs_w1, wl1 + (uint32_t)st.s * gemm_w_step_bytes<C1::NW>(), reinterpret_cast<uint32_t(&)[C1::NW]>(dst));
         };
-        // chunk id -> (batch row b = id >> 4, 16-byte piece q = id & 15 of the step's 128 columns)
+        // chunk id -> (batch row b = id >> 4, 16-byte piece q = chunk_q(id & 15) of the step's 128 columns)
         // (unconditional loads from clamped addresses — a dead chunk re-reads x[0..7] and is zeroed when it is stored: a load under a
         // condition makes the compiler's wait counts conservative, and the wait for a tile then waits for the weights behind it)
-        auto x_live = [&](int g, int r) {
-            const GemmStep st = gemm_where(p, g);
-            const int id = tid + r * NT;
-            return id < NCH && (id >> 4) < p.n && st.col_base + 8 * (id & 15) < st.col_end;
-        };
-        auto load_x = [&](int g) {  // (columns past the end of the stream are zeroed when the chunk is stored: x_live)
+        auto load_x = [&](int g) {  // (columns past the end of the stream are zeroed when the chunk is stored)
             const GemmStep st = gemm_where(p, g);
 #pragma unroll
             for (int r = 0; r < CPT; r++) xr[r] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, xvo[r] + (uint32_t)st.col_base * 2u, 0, 0);
         };
+        // Dead chunks are stored as zeros, in one of two forms the mapping names (Map::ZERO_IN_REG).  hipcc builds the whole step loop
+        // around this choice — with the select the tile and weight loads sit in the MFMA blocks, with the zeroed register the loop is
+        // versioned — and each mapping's loop was tuned on its own form: GemmHalves on the other's select +4..7 VALU per MFMA block,
+        // G16Map on the zeroed register -0.7 ... -3.0 % at batches 32..128 (profiles/r06_ab_lockstep_one_body.txt)
+        auto x_live = [&](int g, int r) {
+            const GemmStep st = gemm_where(p, g);
+            const int id = tid + r * NT;
+            return id < NCH && (id >> 4) < p.n && st.col_base + 8 * (Map::Q_PERMUTED ? Map::chunk_q(id & 15) : (id & 15)) < st.col_end;
+        };
         auto store_x = [&](unsigned char *buf, int g) {
+            if constexpr (Map::ZERO_IN_REG) {
 #pragma unroll
-            for (int r = 0; r < CPT; r++) {
-                const int id = tid + r * NT;
-                if (!x_live(g, r)) xr[r] = u32x4{0u, 0u, 0u, 0u};
-                if (id < NCH) {
-                    const int b = id >> 4, q = id & 15;
-                    // piece q = (supertile col sc = q >> 2, ksub = (q >> 1) & 1, jh = q & 1): halves 0..3 belong to column half u = 0, 4..7 to u = 1
-                    unsigned char *d = buf + (b >> 3) * kGemmXGroup + (2 * (b & 7)) * kGemmXRow + (q >> 2) * 32 + ((q >> 1) & 1) * 16 + (q & 1) * 8;
-                    *reinterpret_cast<u32x2 *>(d) = u32x2{xr[r].x, xr[r].y};
-                    *reinterpret_cast<u32x2 *>(d + kGemmXRow) = u32x2{xr[r].z, xr[r].w};
+                for (int r = 0; r < CPT; r++) {
+                    const int id = tid + r * NT;
+                    if (!x_live(g, r)) xr[r] = u32x4{0u, 0u, 0u, 0u};
+                    if (id < NCH) {
+                        const int b = id >> 4, q = (Map::Q_PERMUTED ? Map::chunk_q(id & 15) : (id & 15));
+                        Map::store_chunk(buf, b, q, xr[r]);
+                    }
+                }
+            } else {
+                const GemmStep st = gemm_where(p, g);
+#pragma unroll
+                for (int r = 0; r < CPT; r++) {
+                    const int id = tid + r * NT;
+                    const int b = id >> 4, q = (Map::Q_PERMUTED ? Map::chunk_q(id & 15) : (id & 15));
+                    const bool ok = id < NCH && b < p.n && st.col_base + 8 * q < st.col_end;
+                    if (id < NCH) Map::store_chunk(buf, b, q, ok ? xr[r] : u32x4{0u, 0u, 0u, 0u});
                 }
             }
         };
@@ -296,10 +302,10 @@ __global__ __launch_bounds__(64 * kGemmWaves) void tc_gemm_kernel(const int eie,
         if (gitem == (int)blockIdx.x && mp.zero_chunks > 0) {  // pre-zero a buffer for a later split-K launch on this stream
             for (int i = blockIdx.x * NT + tid; i < mp.zero_chunks; i += gridDim.x * NT) mp.zero[i] = u32x4{0u, 0u, 0u, 0u};
         }
-        if (p.tab != cur_tab && (!(QPAL_GEMM_KO & 128) || p.n == 12345)) {  // workgroup-uniform
+        if (p.tab != cur_tab) {  // workgroup-uniform
             // (the 128 KiB image is 16 chunks per thread: two batches of 8 table reads instead of 16 dependent round trips)
-            if constexpr (C1::LDS_DWORDS * 4 > 64 * 1024 && NBG <= 4) C1::template build<8>(lut, p.tab, tid, NT);
-            else C1::template build<QPAL_GEMM_BUILD_U>(lut, p.tab, tid, NT);
+            if constexpr (C1::LDS_DWORDS * 4 > 64 * 1024) C1::template build<8>(lut, p.tab, tid, NT);
+            else C1::build(lut, p.tab, tid, NT);
             cur_tab = p.tab;
         }
         if constexpr (AHEAD == 2) {
@@ -308,10 +314,8 @@ __global__ __launch_bounds__(64 * kGemmWaves) void tc_gemm_kernel(const int eie,
             for (int r = 0; r < CPT; r++) xr[r] = xr1[r];
         }
         store_x(xt, g0);
-        Acc<NBG> acc;
-        static_for<0, NBG>([&](auto bc) {
-            static_for<0, 4>([&](auto ac) { acc.v[decltype(bc)::value][decltype(ac)::value] = float4_t{0.f, 0.f, 0.f, 0.f}; });
-        });
+        typename Map::Accum acc;
+        acc.zero();
         __syncthreads();
 
         // the steps of ONE stream (one codec: no branch inside the loop body); the prefetch of the step after the last one
@@ -326,24 +330,17 @@ __global__ __launch_bounds__(64 * kGemmWaves) void tc_gemm_kernel(const int eie,
                 // tile loads the compiler waited `vmcnt(0)` before the tile's LDS stores: every step waited for the NEXT step's
                 // weights, a full HBM round trip where the step is shorter than that (batches 4..32).
                 const int xg = g + AHEAD < g1 ? g + AHEAD : g1 - 1;
-                if constexpr (!(QPAL_GEMM_KO & 4)) load_x(xg);
-                if constexpr (QPAL_GEMM_KO & 32) {
-#pragma unroll
-                    for (int i = 0; i < NWMAX; i++) wn[i] = wc[i] + 1;
-                } else {
-                    const int gn = g + 1 < gb ? g + 1 : g;
-                    if constexpr (SECOND) buf_load_words_nt<CC::NW>(rs_w2, wl2 + (uint32_t)(gn - p.st1) * gemm_w_step_bytes<CC::NW>(), reinterpret_cast<uint32_t(&)[CC::NW]>(wn));
-                    else buf_load_words_nt<CC::NW>(rs_w1, wl1 + (uint32_t)gn * gemm_w_step_bytes<CC::NW>(), reinterpret_cast<uint32_t(&)[CC::NW]>(wn));
-                }
+                load_x(xg);
+                const int gn = g + 1 < gb ? g + 1 : g;
+                if constexpr (SECOND) buf_load_words_nt<CC::NW>(rs_w2, wl2 + (uint32_t)(gn - p.st1) * gemm_w_step_bytes<CC::NW>(), reinterpret_cast<uint32_t(&)[CC::NW]>(wn));
+                else buf_load_words_nt<CC::NW>(rs_w1, wl1 + (uint32_t)gn * gemm_w_step_bytes<CC::NW>(), reinterpret_cast<uint32_t(&)[CC::NW]>(wn));
                 __builtin_amdgcn_sched_barrier(0);
                 const int i = g - g0;
                 if (live)  // (wave-uniform: a row past the end of the layer only keeps the staging and the barriers company)
-                    gemm_step<CC, NBG>(lut, laneoff, reinterpret_cast<uint32_t(&)[CC::NW]>(wc), xt + (i & (NSLOT - 1)) * XBUF, lane, acc);
+                    Map::template step<CC>(lut, laneoff, reinterpret_cast<uint32_t(&)[CC::NW]>(wc), xt + (i & (NSLOT - 1)) * XBUF, lane, acc);
                 // slot of step i + AHEAD: last read AHEAD steps ago, i.e. before the latest barrier
-                if constexpr (!(QPAL_GEMM_KO & 4)) store_x(xt + ((i + AHEAD) & (NSLOT - 1)) * XBUF, xg);
-                if constexpr (!(QPAL_GEMM_KO & 8)) {
-                    if (AHEAD == 1 || (i & 1)) __syncthreads();
-                }
+                store_x(xt + ((i + AHEAD) & (NSLOT - 1)) * XBUF, xg);
+                if (AHEAD == 1 || (i & 1)) __syncthreads();
             };
             // two steps per trip: the prefetched weights become the current ones by NAME (no register copies); an odd count ends on a
             // single step, and whoever continues (the other stream's run) loads its first step into wcur itself
@@ -354,46 +351,36 @@ __global__ __launch_bounds__(64 * kGemmWaves) void tc_gemm_kernel(const int eie,
             }
             if (g < gb) one_step(g, wcur, wnext);
         };
-        if constexpr (!(QPAL_GEMM_KO & 256)) {
-            const int mid = g1 < p.st1 ? g1 : (g0 > p.st1 ? g0 : p.st1);
-            if (g0 < mid) run(std::type_identity<C1>{}, g0, mid);
-            if constexpr (TWO) {
-                if (mid < g1) {
-                    if (g0 < mid) load_w(mid, wcur);  // the switch to stream 2 inside an item: its first step, requested here (one exposed round trip)
-                    run(std::type_identity<CB>{}, mid, g1);
-                }
+        const int mid = g1 < p.st1 ? g1 : (g0 > p.st1 ? g0 : p.st1);
+        if (g0 < mid) run(std::type_identity<C1>{}, g0, mid);
+        if constexpr (TWO) {
+            if (mid < g1) {
+                if (g0 < mid) load_w(mid, wcur);  // the switch to stream 2 inside an item: its first step, requested here (one exposed round trip)
+                run(std::type_identity<CB>{}, mid, g1);
             }
         }
 
         if constexpr (AHEAD == 2) __syncthreads();  // (an odd number of steps ends without one: the scratch below overlays the tiles)
-        // ---- epilogue: lane (q = lane >> 4, cidx = lane & 15 = 2 b' + u) holds, for batch row 8 grp + b' and a = msub * 2 + jl,
-        // D[4 q + r][cidx]; valid where (r & 1) == u: on even lanes own r = 0 / 2 plus the odd neighbour's r = 1 / 3 are tile rows
-        // 8 a + 2 q + {0, 1}.  One batch group at a time goes through a per-wave [8][32] fp32 scratch and leaves as 128-byte runs.
-        float *scr = reinterpret_cast<float *>(xt) + wave * 256;
+        // ---- epilogue: lane (q = lane >> 4, c = lane & 15) holds rows 4 q .. 4 q + 3 of column c of every accumulator (the MFMA's D
+        // layout).  One batch group at a time goes through a per-wave [ROWS][32] fp32 scratch (Map::scatter) and leaves as 128-byte runs.
+        float *scr = reinterpret_cast<float *>(xt) + wave * (Map::SCRATCH / 4);
         int lane_e = lane;
         asm volatile("" : "+v"(lane_e));  // the epilogue's addresses are computed HERE: hoisted out of the item loop they sat in
-                                          // registers through the steps (1 spilled VGPR at 8 batch groups = scratch set-up per launch)
-        const int q = lane_e >> 4, cidx = lane_e & 15;
-        const int r32 = lane_e & 31;
+                                          // registers through the steps
+        const int q = lane_e >> 4, c = lane_e & 15, r32 = lane_e & 31;
         float osc = p.oscale;
         if (p.wscale && live) osc *= (float)__builtin_bit_cast(_Float16, p.wscale[sr * 32 + r32]);
         auto epilogue = [&](auto mode_c) {
             constexpr int mode = decltype(mode_c)::value;  // 0: store, 1: out += (residual add), 2: split-K atomics
-            static_for<0, NBG>([&](auto bc) {
+            static_for<0, Map::GROUPS>([&](auto bc) {
                 constexpr int grp = decltype(bc)::value;
-                static_for<0, 4>([&](auto ac) {
-                    constexpr int a = decltype(ac)::value;
-                    const float4_t d = acc.v[grp][a];
-                    const float v0 = d[0] + lane_xor<1>(d[1]);
-                    const float v1 = d[2] + lane_xor<1>(d[3]);
-                    if ((cidx & 1) == 0) *reinterpret_cast<float2 *>(scr + (cidx >> 1) * 32 + 8 * a + 2 * q) = float2{v0, v1};
-                });
+                Map::template scatter<grp>(scr, acc, q, c);
                 // (wave-private scratch: LDS operations of one wave complete in order)
 #pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int bl = 2 * i + (lane_e >> 5), b = 8 * grp + bl;
+                for (int i = 0; i < Map::ROWS / 2; i++) {
+                    const int bl = 2 * i + (lane_e >> 5), b = Map::ROWS * grp + bl;
                     const float v = scr[bl * 32 + r32] * osc;
-                    if (live && b < p.n && (!(QPAL_GEMM_KO & 64) || v == 12345.678f)) {
+                    if (live && b < p.n) {
                         float *dst = p.out + (long)b * p.ldo + (long)sr * 32 + r32;
                         if constexpr (mode == 2) atomicAdd(dst, v);
                         else if constexpr (mode == 1) *dst += v;

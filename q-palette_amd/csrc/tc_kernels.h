@@ -123,16 +123,6 @@ struct TcMultiParams {
 // (512 instead of 4 096 reads of the 2 KiB table, its 8 chunk writes in a burst, early staging for every image size) cost the
 // wrapper 3.4 % and the plain token 0.6 % (and moved the k / v latency-table entries of the 128 KiB images by -0.9 ... +1.1 us).
 // The slow trickle of this loop stays out of the way of the loads and LDS traffic that ARE on the critical path.  U = 1.
-#ifndef QPAL_BUILD_U
-#define QPAL_BUILD_U 1
-#endif
-#ifndef QPAL_XPERM_PLAIN  // the permuted x layout in the plain GEMV kernels (see xs_put)
-#define QPAL_XPERM_PLAIN 1
-#endif
-#ifndef QPAL_ROT_BUILD_U  // the image build of the rotating kernels' builder waves (12 of 16 at k = 4096) only
-#define QPAL_ROT_BUILD_U 1
-#endif
-constexpr int kBuildInFlight = QPAL_BUILD_U;
 template <int CHUNKS, int LOG2C, int U, class Entry>
 __device__ __forceinline__ void build_image(uint32_t *lds, int tid, int nthreads, Entry &&entry) {
     for (int c0 = tid; c0 < CHUNKS; c0 += U * nthreads) {
@@ -189,7 +179,7 @@ struct TcqCodec {
     static __device__ __forceinline__ uint32_t entry(const void *tab, int e) {
         return as_global(static_cast<const uint32_t *>(tab))[e & ((1 << S) - 1)] ^ (((uint32_t)e >> S) << 15);
     }
-    template <int U = kBuildInFlight>  // table reads in flight per thread
+    template <int U = 1>  // table reads in flight per thread
     static __device__ __forceinline__ void build(uint32_t *lds, const void *tab, int tid, int nthreads) {
         build_image<CHUNKS, LOG2C, U>(lds, tid, nthreads, [&](int e) { return entry(tab, e); });
     }
@@ -321,7 +311,7 @@ struct LutCodec {
         else if constexpr (PAIR) return (uint32_t)l16[e & ((1 << BITS) - 1)] | ((uint32_t)l16[e >> BITS] << 16);
         else return l16[e];
     }
-    template <int U = kBuildInFlight>  // table reads in flight per thread
+    template <int U = 1>  // table reads in flight per thread
     static __device__ __forceinline__ void build(uint32_t *lds, const void *tab, int tid, int nthreads) {
         build_image<CHUNKS, LOG2C, U>(lds, tid, nthreads, [&](int e) { return entry(tab, e); });
     }
@@ -500,9 +490,6 @@ __device__ __forceinline__ int xs_index(int i) {
 // (the staged x's zero pad, one broadcast LDS read) its switching power goes down — measured with perf/power_probe.hip: the 8 matrix
 // instructions of a step are ~200 W of the ~1 100 W the decode draws, and the token runs into the card's power limit (shader clock 2.15
 // instead of 2.4 GHz while tokens replay back to back, profiles/r05_power_and_clock.txt).
-#ifndef QPAL_ZERO_B
-#define QPAL_ZERO_B 1
-#endif
 // MFMA B operand of a step.  Lane (kb = lane>>4, c = lane&15) supplies, for batch row b = 8*grp + (c>>1) and
 // column half u = c&1, the 8 activations  x[b][col0 + 32*sc + 16*ksub + 8*jh + 4*u + 0..3], jh = 0,1
 // (order matches the A fragment: jh-major, then the reference lanes A|B, then the element of the pair).
@@ -521,7 +508,7 @@ __device__ __forceinline__ void load_step_x(const StreamView &sv, const uint16_t
         int b = 8 * grp + (c >> 1);
         b = b < n ? b : n - 1;
         const int off = b * k + sv.col0 + sc * 32 + 4 * (c & 1);
-        [[maybe_unused]] const bool real = QPAL_ZERO_B == 0 || 8 * grp + (c >> 1) < n;  // (see QPAL_ZERO_B)
+        [[maybe_unused]] const bool real = 8 * grp + (c >> 1) < n;  // (zeros for a batch row that does not exist: see above)
         if constexpr (XLDS == 2) {
             // staged x is PERMUTED inside every 32-half block (xs_put<true>): the four 8-byte pieces a lane needs are
             // contiguous, so the B operand of a step is two ds_read_b128 (4 LDS cycles each) instead of two ds_read2_b64 (8)
@@ -578,13 +565,10 @@ __device__ __forceinline__ void gemv_step(const uint32_t *lut, uint32_t laneoff,
     });
 }
 
-// Software-pipelined form of the step (QPAL_GEMV_PIPE, batch group count 1, codecs with `addr`): the compiler's own order per
+// Software-pipelined form of the step (batch group count 1, codecs with `addr`): the compiler's own order per
 // tile group is  8 addresses (VALU) -> 8 gathers -> wait -> 2 MFMAs,  i.e. a wave has no VALU work while its gathers are in flight
 // and no gathers in flight while it computes addresses; here the addresses of group g + 1 are computed between the gathers of
 // group g and the MFMAs that consume them (order pinned by sched_barrier fences).
-#ifndef QPAL_GEMV_PIPE
-#define QPAL_GEMV_PIPE 1
-#endif
 template <class Codec>
 constexpr bool has_addr_v = requires(const uint32_t (&w)[Codec::NW]) { Codec::template addr<0, 0>(0u, w, 0u); };
 template <class Codec>
@@ -637,7 +621,7 @@ __device__ __forceinline__ void gemv_step_pipe(const uint32_t *lut, uint32_t lan
 template <class Codec, int NBG>
 __device__ __forceinline__ void gemv_step_any(const uint32_t *lut, uint32_t laneoff, const uint32_t (&w)[Codec::NW],
                                               const u32x4 (&xb)[NBG][2], Acc<NBG> &acc) {
-    if constexpr (QPAL_GEMV_PIPE != 0 && NBG == 1 && has_addr_v<Codec>) gemv_step_pipe<Codec>(lut, laneoff, w, xb, acc);
+    if constexpr (NBG == 1 && has_addr_v<Codec>) gemv_step_pipe<Codec>(lut, laneoff, w, xb, acc);
     else gemv_step<Codec, NBG>(lut, laneoff, w, xb, acc);
 }
 
@@ -668,7 +652,7 @@ __device__ __forceinline__ void gemv_run(uint32_t (&w)[Codec::NW], const uint32_
         xl = reinterpret_cast<const char *>(xs) + (b * k + sv.col0 + (lane >> 4) * 32 + 16 * (c & 1)) * 2;
         xz = reinterpret_cast<const char *>(xs) + zero_off * 2;
         dead = (sv.nsc - (lane >> 4) + 3) >> 2;  // first step whose supertile column 4 s + (lane >> 4) is >= nsc
-        if (QPAL_ZERO_B != 0 && (c >> 1) >= n) dead = 0;  // a batch row that does not exist: zeros from the first step on (see QPAL_ZERO_B)
+        if ((c >> 1) >= n) dead = 0;  // a batch row that does not exist: zeros from the first step on (see load_step_x)
     }
     auto step_x = [&](int s, u32x4(&xb)[NBG][2]) {
         if constexpr (XLDS == 2 && NBG == 1) {
@@ -910,12 +894,11 @@ __global__ QPAL_GEMV_BOUNDS(NBG) void tc_gemv_kernel(const uint16_t *ex, const v
     // across their seven decode loops' set-up spilled 16-28 VGPRs, and a kernel that touches scratch at all pays ~1 us per
     // launch — without early staging they have no spills and the q | k | v launch of a mixed-scheme model takes 7.1 instead of
     // 8.3 us (llama3.1-8b_figure1c 651 -> 707 tok/s, mem3p25 678 -> 722, one box: profiles/r03_ab_any_spills.txt).
-    constexpr bool kXPerm = QPAL_XPERM_PLAIN != 0 && (ROT == 0 || ROT == 3);  // staged x in the permuted layout (xs_put)
+    constexpr bool kXPerm = ROT == 0 || ROT == 3;  // staged x in the permuted layout (xs_put): the plain kernels only
     constexpr int kXL = kXPerm ? 2 : 1;
-#ifndef QPAL_ANY_EARLY
-#define QPAL_ANY_EARLY 1  // round 4: with the early loads outside the compiler's bookkeeping (inline asm) and the first item as its own
-#endif                    // body, the any-KV kernels hold them without spilling (round 3: 16-28 spilled VGPRs, early staging off)
-    constexpr bool kEarly = NBG == 1 && (ROT == 0 || ROT == 3) && NV * NT <= 4096 && (QPAL_ANY_EARLY || !is_any_v<C1>);
+    // (round 4: with the early loads outside the compiler's bookkeeping (inline asm) and the first item as its own body, the any-KV
+    // kernels hold them without spilling too)
+    constexpr bool kEarly = NBG == 1 && (ROT == 0 || ROT == 3) && NV * NT <= 4096;
     constexpr int EV = NV < 4 ? NV : 4;  // image entries a thread holds across the argument fetch; the rest are built after it
     constexpr int XR = kEarlyXChunks;    // 16-byte chunks of x a thread holds likewise
     [[maybe_unused]] u32x4 exr[XR];
@@ -929,10 +912,6 @@ __global__ QPAL_GEMV_BOUNDS(NBG) void tc_gemv_kernel(const uint16_t *ex, const v
     // (What round 3 and the first half of round 4 found again and again: every way of making the rotation's or the image's loads
     // "faster" that put them beside or in front of the weight stream made the token slower.)
     constexpr int kRotTab = 6;  // table entries a builder thread holds: 4 096 chunks over 1 024 - 64 x_rot threads
-#ifndef QPAL_ROT_TAB_EARLY
-#define QPAL_ROT_TAB_EARLY 1
-#endif
-    constexpr bool kRotTabEarly = QPAL_ROT_TAB_EARLY != 0;  // (6 more registers held across the prologue: spills in most instantiations)
     [[maybe_unused]] u32x4 rq_e[2][4];  // per 32-column half kc: x (two chunks when fp32), RMSNorm weight, sign vector
     [[maybe_unused]] uint32_t rtv[kRotTab][C1::RAWN];
     // (not for the widest two-stream codecs — 8 | 9 and 9 | 10 dwords per lane: their first weight step and the early registers
@@ -970,7 +949,7 @@ __global__ QPAL_GEMV_BOUNDS(NBG) void tc_gemv_kernel(const uint16_t *ex, const v
                 wht_float4 *d1buf_e = reinterpret_cast<wht_float4 *>(xs_e + ((en * ek + 32 + 7) & ~7));
                 rot_stage1_regs(rq_e, (eon & 4) != 0, (eon & 8) != 0, erw != nullptr, esu != nullptr, wave, lane, d1buf_e,
                                 reinterpret_cast<float *>(d1buf_e + 4 * 4 * 64));
-            } else if constexpr (kRotTabEarly) {
+            } else {
                 const int bt = tid - 64 * e_rot, nb = 1024 - 64 * e_rot;
 #pragma unroll
                 for (int r = 0; r < kRotTab; r++) {
@@ -1153,12 +1132,10 @@ __global__ QPAL_GEMV_BOUNDS(NBG) void tc_gemv_kernel(const uint16_t *ex, const v
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             if (FIRST && rot_early) {  // the rotation's inputs / the image's table entries, requested at the wave's first instruction
-                if constexpr (kRotTabEarly) {
 #pragma unroll
-                    for (int r = 0; r < kRotTab; r++) {
+                for (int r = 0; r < kRotTab; r++) {
 #pragma unroll
-                        for (int q = 0; q < C1::RAWN; q++) asm volatile("" : "+v"(rtv[r][q]));
-                    }
+                    for (int q = 0; q < C1::RAWN; q++) asm volatile("" : "+v"(rtv[r][q]));
                 }
             }
         }
@@ -1334,7 +1311,7 @@ __global__ QPAL_GEMV_BOUNDS(NBG) void tc_gemv_kernel(const uint16_t *ex, const v
                     }
                     if (p.tab != cur_tab) {
                         bool built = false;
-                        if constexpr (kRotEarly && kRotTabEarly) {
+                        if constexpr (kRotEarly) {
                             if (FIRST && rot_early) {  // (host: every job of the launch has job 0's codebook)
                                 if (wave >= p.x_rot) {
                                     const int bt = tid - 64 * p.x_rot, nb = 1024 - 64 * p.x_rot;
@@ -1348,7 +1325,7 @@ __global__ QPAL_GEMV_BOUNDS(NBG) void tc_gemv_kernel(const uint16_t *ex, const v
                                 built = true;
                             }
                         }
-                        if (!built && wave >= p.x_rot) C1::template build<QPAL_ROT_BUILD_U>(lut, p.tab, tid - 64 * p.x_rot, 1024 - 64 * p.x_rot);
+                        if (!built && wave >= p.x_rot) C1::build(lut, p.tab, tid - 64 * p.x_rot, 1024 - 64 * p.x_rot);
                         cur_tab = p.tab;
                     }
                     if (tid < 32) xs[total + tid] = 0;
