@@ -562,6 +562,58 @@ int qpal_logit_process(const float *logits_f32, long ld_logits, float *out_f32, 
 int qpal_logit_observe(int *count, long ld_count, int slots, int vocab, const int *slot, int slot0, const long *tokens,
                        const long *active, int n, void *stream);
 
+/* GRAMMAR-CONSTRAINED DECODING (csrc/grammar.hip): a byte-level deterministic automaton per slot, followed on the
+ * device.  An automaton of S states (1 .. 65534; state 0 is the start):
+ *   trans uint16 [S][256]      the state byte c leads to from state s, 0xFFFF: none (any value >= S is read as none)
+ *   accept uint8 [S]           != 0: the text may end here
+ * The vocabulary: tok_off int32 [vocab + 1] and tok_bytes uint8 [total_bytes] — token t is the bytes tok_off[t] .. tok_off[t + 1];
+ * a token without bytes (or whose offsets do not lie in 0 <= tok_off[t] < tok_off[t + 1] <= total_bytes) is never allowed; eos in
+ * [0, vocab) ends a text, whatever bytes it has.  A slot's state is an int32: 0 .. S - 1 a state of its automaton, S FINISHED (eos
+ * has been emitted), -1 DEAD; any other value is read as dead.
+ *   step(s, t):  s dead: dead.  s == S: t == eos ? S : dead.  t == eos: accept[s] ? S : dead.  t outside [0, vocab): dead.
+ *                Else follow t's bytes through trans; a byte without a transition, or an empty token: dead.
+ *
+ * qpal_grammar_compile: allow uint32 [S + 1][ld_allow] (ld_allow >= ceil(vocab / 32); bit t & 31 of word t >> 5 — the layout of
+ * qpal_logit_process's mask).  Row s < S: bit t set iff step(s, t) is not dead; row S: the eos bit only.  Words ceil(vocab / 32) ..
+ * ld_allow of a row are not written; the bits past vocab in a row's last word are written as 0.  One thread per (state, token),
+ * a wave's 64 verdicts are one ballot = two words; runs once when an automaton is loaded, never in a step.
+ *
+ * A bank: trans uint16 [grammars][max_states][256], accept uint8 [grammars][max_states], n_states int32 [grammars], allow uint32
+ * [grammars][max_states + 1][ld_allow], and per slot gram int32 [slots] (-1: no grammar) and state int32 [slots].  A slot HAS a
+ * grammar when gram[b] lies in [0, grammars) and n_states[gram[b]] in [1, max_states]; 1 <= slots <= 128, grammars <= 1024.
+ *
+ * qpal_grammar_rows: a speculative step's segments (tokens int64 [rows], row0 int32 [slots + 1]: qpal_spec_draft's) ->
+ * row_state int32 [rows], 1 <= rows <= 128.  EVERY row is written: -1, except that for a slot b with a grammar, a segment
+ * (0 <= row0[b] < row0[b + 1] <= rows, at most 16 rows) and state[b] in [0, S], row row0[b] + j gets
+ * step(.. step(state[b], tokens[row0[b] + 1]) .., tokens[row0[b] + j]) — the pending token at row0[b] is already in state[b].
+ *
+ * qpal_grammar_mask: in place on logits fp32 [rows][ld_logits] (ld_logits >= vocab, 1 <= rows <= 128).  Row r with b = row_slot[r]
+ * is SKIPPED, no word of it written, when ctr[r] < 0, b is outside [0, slots), slot b has no grammar, or row_state[r] is outside
+ * [0, S].  Else l[t] = -inf for every t < vocab whose bit in allow[gram[b]][row_state[r]] is clear (a NaN too), and nothing else is
+ * written; the logits are not read.  A decode step passes state as row_state (row = slot).
+ *
+ * qpal_grammar_advance: state[b] = step(.. step(state[b], tokens[b][0]) .., tokens[b][m - 1]) over tokens int64 [slots][width]
+ * (1 <= width <= 16), m = n[b] clamped to 0 .. width, or width with n == NULL.  Slot b is skipped — state[b] is not written — when
+ * it has no grammar, when active != NULL and active[b] < 0 (int64 [slots]), or when m == 0.
+ *
+ * rows, mask and advance read their state on the device, never synchronise and write each word by one thread: capturable, and
+ * equal launches leave equal bits.  Codes, all decided on the host before any stream work: a null pointer (n and active may be
+ * NULL) QPAL_E_NULL; n_states, max_states, grammars, slots, rows, width, vocab, total_bytes < 0, eos outside [0, vocab) or a stride
+ * below its width QPAL_E_SHAPE; uint16 arrays 2-byte, fp32 / int32 / uint32 arrays 4-byte, int64 arrays 8-byte aligned, else
+ * QPAL_E_ALIGN. */
+int qpal_grammar_compile(const unsigned short *trans, const unsigned char *accept, int n_states, const int *tok_off,
+                         const unsigned char *tok_bytes, int vocab, int total_bytes, int eos, unsigned *allow, long ld_allow,
+                         void *stream);
+int qpal_grammar_rows(const unsigned short *trans, const unsigned char *accept, const int *n_states, int grammars, int max_states,
+                      const int *tok_off, const unsigned char *tok_bytes, int vocab, int total_bytes, int eos, const int *gram,
+                      const int *state, int slots, const long *tokens, const int *row0, int rows, int *row_state, void *stream);
+int qpal_grammar_mask(float *logits_f32, long ld_logits, int rows, int vocab, const int *row_slot, const long *ctr,
+                      const int *row_state, const int *gram, int slots, const int *n_states, int grammars, int max_states,
+                      const unsigned *allow, long ld_allow, void *stream);
+int qpal_grammar_advance(const unsigned short *trans, const unsigned char *accept, const int *n_states, int grammars, int max_states,
+                         const int *tok_off, const unsigned char *tok_bytes, int vocab, int total_bytes, int eos, const int *gram,
+                         int *state, int slots, const long *tokens, int width, const int *n, const long *active, void *stream);
+
 /* PROXY HESSIAN of a linear layer's inputs (csrc/hessian.hip):  H += X^T X  and  colsum += 1^T X  in one launch.
  *   X       fp16 [rows, n] row-major, row stride ld_x >= n elements (a column slice of a wider buffer is passed as it lies);
  *           base 16-byte aligned, ld_x a multiple of 8

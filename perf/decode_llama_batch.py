@@ -24,13 +24,17 @@ rotary embedding, a per-sequence cache write, SDPA with a per-sequence mask), wh
 frequency 0.3, a mask that allows every second token and 64 bias entries in every slot — observe + process, two more launches —
 next to the same step without one, in the same call.
 
+--grammar (with --sample) also times each sampled step with a grammar.GrammarBank: every slot follows a number
+pattern on a synthetic vocabulary (perf/sampling_kernels.py's) — mask + advance, two more launches — next to the same step without
+one, in the same call.
+
 --kv fp8 keeps the caches as torch.float8_e4m3fn.  The torch-glue reference then keeps fp16 caches of its own that
 hold e4m3 values only: `BatchKV.update` stores a new row through the round trip clamp(-448, 448) -> float8_e4m3fn -> half and the
 step attends to the round-tripped cache, as the kernels do.  The check also reports how far the fp16-cache step lies from that
 reference (what the format itself moves; not a gate).
 
     python perf/decode_llama_batch.py [--model 3_8b] [--batch 1 8 16 32 64] [--context 1024] [--tokens 64] [--inactive 0] [--sample]
-                                      [--process] [--kv fp16|fp8] [--paged PAGE_SIZE]
+                                      [--process] [--grammar] [--kv fp16|fp8] [--paged PAGE_SIZE]
 """
 import argparse
 import json
@@ -88,6 +92,7 @@ def main(argv=None, quiet=False):
     ap.add_argument("--no-torch-glue", action="store_true", help="skip the torch-glue step (its timing and the check)")
     ap.add_argument("--sample", action="store_true", help="also time the step with a sampler (0.6 / top-k 5 and 0.8 / top-p 0.95)")
     ap.add_argument("--process", action="store_true", help="with --sample: also time the sampled step with a logit processor")
+    ap.add_argument("--grammar", action="store_true", help="with --sample: also time the sampled step with a grammar in every slot")
     ap.add_argument("--kv", default="fp16", choices=["fp16", "fp8"], help="KV-cache element format (fp8: OCP e4m3fn, no scales)")
     ap.add_argument("--paged", type=int, default=0, metavar="PAGE_SIZE",
                     help="also time the step on a paged cache of this page size (pages in a seeded random order; DESIGN.md §17)")
@@ -95,6 +100,8 @@ def main(argv=None, quiet=False):
     kv8 = args.kv == "fp8"
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
+    if args.grammar and not args.sample:
+        raise SystemExit("--grammar: the grammar masks a sampler's logits, add --sample")
     if args.process and not args.sample:
         raise SystemExit("--process: the processor works on a sampler's logits, add --sample")
     if args.context % 4 or args.context < args.tokens + 16:
@@ -237,6 +244,21 @@ def main(argv=None, quiet=False):
                     sampled[-1].update({"ms_step_processor": ms_p, "ms_step_again": ms_again, "ms_processor_minus_plain": ms_p - 0.5 * (ms + ms_again),
                                         "launches_per_token": [sstep.launches_per_token, pstep.launches_per_token]})
                     del pstep, proc
+                if args.grammar:
+                    # a number in every slot; the step without a bank is timed again behind it (the spread of the call)
+                    from sampling_kernels import NUMBER, synthetic_table
+                    bank = qp.GrammarBank(B, synthetic_table(args.vocab), dev, grammars=1, max_states=8)
+                    bank.load(0, NUMBER)
+                    for b in range(B):
+                        bank.set(b, 0)
+                    gstep = qp.DecodeStep(layers, embed, norm, lm_head, kc, vc, inv_freq, tok, pos, out_tok, generic=True, sampler=smp,
+                                          grammar=bank)
+                    ms_g, ms_again = timed(gstep), timed(sstep)
+                    sampled[-1].update({"ms_step_grammar": ms_g, "ms_step_again_behind_grammar": ms_again,
+                                        "ms_grammar_minus_plain": ms_g - 0.5 * (ms + ms_again),
+                                        "grammar_launches_per_token": [sstep.launches_per_token, gstep.launches_per_token],
+                                        "grammar_slots_alive_at_the_end": int((bank.state >= 0).sum())})
+                    del gstep, bank
                 del sstep, smp
         res = {"batch": B, "active": nact, "ms_step": ms_step, "tokens_per_s": nact / ms_step * 1e3,
                "ms_linears_only": ms_lin, "ms_torch_glue": ms_torch,

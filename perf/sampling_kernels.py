@@ -6,14 +6,21 @@
 Also qpal_logit_process in place on the same logits, with a neutral processor and with every stage on (penalties on
 counted tokens, a mask, 64 bias entries per slot), beside a qpal_calib_stream_read of the bytes it moves: logits read, logits
 written, counts read = 12 bytes per logit.
+--grammar adds the launches of grammar-constrained decoding in the same call: qpal_grammar_mask on the same logits
+(every row in the start state of a number pattern) next to the processor launches above, qpal_grammar_rows and qpal_grammar_advance
+at 8 slots with drafts of 4 and 15 one-byte tokens (chains of dependent table reads), and GrammarBank.load of a 301-state automaton
+(upload, compile launch, the check's read) on a synthetic vocabulary of --vocab tokens.
 
-    python perf/sampling_kernels.py [--vocab 128256] [--k 4096] [--rows 1 8 64 128] [--iters 20] [--warmup 5]
+    python perf/sampling_kernels.py [--vocab 128256] [--k 4096] [--rows 1 8 64 128] [--iters 20] [--warmup 5] [--grammar]
 """
 import argparse
 import ctypes
 import json
 import os
 import sys
+import time
+
+import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -34,6 +41,64 @@ def timed(fn, iters, warmup):
     return e0.elapsed_time(e1) / iters * 1e3  # us
 
 
+NUMBER = r"-?(0|[1-9]\d*)(\.\d+)?"
+
+
+def synthetic_table(vocab, seed=0):
+    """a grammar.TokenTable of `vocab` made-up tokens: the 16 characters of "ab0123456789.-x " first, then strings of 1 .. 6 of them
+    (2 % special tokens without bytes); eos is the last id"""
+    rng = np.random.default_rng(seed)
+    alpha = np.frombuffer(b"ab0123456789.-x ", np.uint8)
+    lens = rng.integers(1, 7, size=vocab)
+    lens[rng.random(vocab) < 0.02] = 0
+    off = np.concatenate([[0], np.cumsum(lens)])
+    data = alpha[rng.integers(0, len(alpha), size=off[-1])].tobytes()
+    toks = [data[off[t]:off[t + 1]] for t in range(vocab)]
+    toks[:len(alpha)] = [bytes([c]) for c in alpha][:vocab]
+    toks[-1] = b"</s>"
+    return qp.TokenTable(toks, eos=vocab - 1)
+
+
+def grammar_launches(table, dev, iters, warmup):
+    """rows / advance at 8 slots and drafts of 4 and 15 one-byte tokens, and the load of a 301-state automaton"""
+    B, res = 8, {"slots": 8, "chains": []}
+    bank = qp.GrammarBank(B, table, dev, grammars=2, max_states=301)
+    bank.load(0, NUMBER)
+    one = table.tok_bytes[table.tok_off[:-1].clip(max=table.total - 1)] == ord("1")
+    digit = int(np.flatnonzero(one & (np.diff(table.tok_off) == 1))[0])      # the token "1": every draft stays alive
+    for K in (4, 15):
+        rows = B * (K + 1)
+        tokens = torch.full((rows,), digit, dtype=torch.int64, device=dev)
+        row0 = torch.arange(0, rows + 1, K + 1, dtype=torch.int32, device=dev)
+        row_state = torch.zeros(rows, dtype=torch.int32, device=dev)
+        out_tok, n_out = tokens.view(B, K + 1).clone(), torch.full((B,), K + 1, dtype=torch.int32, device=dev)
+
+        def advance():
+            bank.state.zero_()   # (a fill launch inside the timing, on both drafts alike: the walk starts at the start)
+            qp.grammar_advance(bank, out_tok, n=n_out)
+        for b in range(B):
+            bank.set(b, 0)
+        res["chains"].append({"draft": K, "rows": rows, "tokens_walked_per_slot": [K, K + 1],
+                              "dependent_reads_per_token": 3,   # tok_off -> tok_bytes -> trans, each needs the one before
+                              "us_grammar_rows": timed(lambda: qp.grammar_rows(bank, tokens, row0, row_state), iters, warmup),
+                              "us_grammar_advance_with_state_fill": timed(advance, iters, warmup),
+                              "us_state_fill_alone": timed(lambda: bank.state.zero_(), iters, warmup)})
+        assert int(row_state.min()) >= 0, "a draft died: the chains are shorter than stated"
+    dfa = qp.compile_regex("[ab]{300}")
+    ms = []
+    for _ in range(5):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        bank.load(1, dfa)        # upload, one compile launch, the check's read (a synchronisation)
+        ms.append((time.perf_counter() - t0) * 1e3)
+    res["load_301_states"] = {"ms_each": ms, "ms_median": sorted(ms)[2], "allow_bytes_written": 302 * bank.words * 4}
+    lib, stream = qp._native.lib(), torch.cuda.current_stream(dev).cuda_stream
+    res["load_301_states"]["us_compile_launch_alone"] = timed(lambda: qp._native.check(lib.qpal_grammar_compile(
+        bank.trans[1].data_ptr(), bank.accept[1].data_ptr(), 301, *bank._vocab_args(), bank.allow[1].data_ptr(), bank.words, stream),
+        "compile"), iters, warmup)
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--vocab", type=int, default=128256)
@@ -41,6 +106,7 @@ def main(argv=None):
     ap.add_argument("--rows", type=int, nargs="+", default=[1, 8, 64, 128])
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--grammar", action="store_true", help="also time the grammar launches (mask beside the processor, rows, advance, load)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
@@ -58,6 +124,7 @@ def main(argv=None):
     out = {"what": "qpal_lm_head_logits / qpal_sample alone, us per launch (events)", "vocab": args.vocab, "k": args.k,
            "lm_head_bytes": W.numel() * 2, "us_stream_read_of_lm_head": us_stream, "tb_per_s_stream": W.numel() * 2 / us_stream * 1e-6,
            "rows": []}
+    table = synthetic_table(args.vocab) if args.grammar else None
     for rows in args.rows:
         h = torch.randn(rows, args.k, device=dev, generator=gen)
         ctr = torch.arange(rows, dtype=torch.int64, device=dev)
@@ -90,10 +157,22 @@ def main(argv=None):
                     lambda: qp._native.check(lib.qpal_calib_stream_read(s2, n2, 1, sink.data_ptr(), 2048, stream), "stream"), args.iters, args.warmup)
                 del scratch
             del proc
+        if args.grammar:   # every row in the start state of NUMBER: the digits and "-" stay, everything else becomes -inf
+            bank = qp.GrammarBank(rows, table, dev, grammars=1, max_states=8)
+            bank.load(0, NUMBER)
+            for b in range(rows):
+                bank.set(b, 0)
+            res["us_grammar_mask"] = timed(lambda: qp.grammar_mask(smp.logits, bank, slots, ctr), args.iters, args.warmup)
+            res["grammar_mask_tokens_allowed"] = int(torch.isfinite(smp.logits[0]).sum())
+            proc = qp.LogitProcessor(rows, args.vocab, dev)
+            res["us_logit_process_neutral_again"] = timed(lambda: qp.logits.process(smp.logits, proc, slots, ctr), args.iters, args.warmup)
+            del bank, proc
         norm = lambda: torch.nn.functional.rms_norm(h.half(), (args.k,), w_ln, 1e-5)
         res["us_torch_tail_norm_matmul_argmax"] = timed(lambda: (norm() @ W.T).argmax(-1), args.iters, args.warmup)
         out["rows"].append(res)
         del smp
+    if args.grammar:
+        out["grammar"] = grammar_launches(table, dev, args.iters, args.warmup)
     print(json.dumps(out))
     return out
 

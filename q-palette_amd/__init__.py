@@ -28,6 +28,10 @@ Layout:
   logits.py        logit processors between the lm_head and the draw: LogitProcessor (per-slot token mask, sparse bias, repetition /
                    presence / frequency penalties and token counts on the device), process / observe (csrc/logit_proc.hip) and the
                    contract reference_process (numpy fp32, bit for bit)
+  grammar.py       grammar-constrained decoding: compile_regex (a regular expression -> a minimal, trimmed byte-level DFA), TokenTable,
+                   GrammarBank (the automata, their per-state token bitmasks and the slots' states on the device), grammar_rows /
+                   grammar_mask / grammar_advance (csrc/grammar.hip) and the contracts reference_allow / _step / _rows / _mask /
+                   _advance (numpy, bit for bit)
   packers.py       pack_trellis / pack_qweight / pack_qweight_{sq,vq}_simt on the C-ABI's host-side encoders
   quantize.py      TCQ quantiser: tail-biting Viterbi encoder (csrc/tcq_viterbi.hip) + LDLQ -> QTIPLinearTCQ
                    VQ / SQ quantiser: nearest-codeword LDLQ encoder (csrc/vq_encode.hip) -> VQLinearPack{TensorCore,SIMT}
@@ -75,6 +79,8 @@ from . import sampling  # noqa: F401
 from .sampling import Sampler, lm_head_logits, reference_draw, reference_logprob, sample, token_logprobs  # noqa: F401
 from . import logits  # noqa: F401
 from .logits import LogitProcessor, reference_process  # noqa: F401
+from . import grammar  # noqa: F401
+from .grammar import ByteDFA, GrammarBank, TokenTable, compile_regex, grammar_advance, grammar_mask, grammar_rows  # noqa: F401
 from . import decoder  # noqa: F401
 from .decoder import DecodeStep, Prefill, RaggedStep, Score, SpeculativeStep, perplexity  # noqa: F401
 from . import speculative  # noqa: F401

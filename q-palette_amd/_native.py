@@ -89,6 +89,10 @@ _SIGNATURES = {
     "qpal_logit_process": [_P, ctypes.c_long, _P, ctypes.c_long, _I, _I, _P, _P, _I, _P, ctypes.c_long, _P, _P, _P, _P, ctypes.c_long, _P,
                            _P, _P, _P, _I, _P, _P, _P],
     "qpal_logit_observe": [_P, ctypes.c_long, _I, _I, _P, _I, _P, _P, _I, _P],
+    "qpal_grammar_compile": [_P, _P, _I, _P, _P, _I, _I, _I, _P, ctypes.c_long, _P],
+    "qpal_grammar_rows": [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P],
+    "qpal_grammar_mask": [_P, ctypes.c_long, _I, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, ctypes.c_long, _P],
+    "qpal_grammar_advance": [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P],
     "qpal_peer_gather": [_P, ctypes.c_long, _I, ctypes.POINTER(_P), ctypes.POINTER(_P), _I, _I, _P],
     "qpal_peer_alloc": [ctypes.POINTER(_P), ctypes.c_long, _I],
     "qpal_peer_free": [_P],

@@ -57,6 +57,13 @@ step takes effect without a new capture.
 masks, a sparse logit bias and repetition / presence / frequency penalties between the lm_head and the draw.  A step counts the
 tokens it feeds (`qpal_logit_observe`), then processes the logits in place (`qpal_logit_process`), then draws: two more launches,
 everything on the device, and the processor's setters between replays of a captured step change the next draw.
+
+The same three take `grammar=`, a grammar.GrammarBank of the caches' slots: every slot with a grammar draws only
+tokens that keep its text a prefix of a match of its regular expression, and eos only where the text is a whole match.  The mask
+comes from the slot's automaton state on the device (`qpal_grammar_mask`, behind the processor and in front of the draw) and the
+drawn tokens advance that state (`qpal_grammar_advance`): two more launches, three in a SpeculativeStep, whose rows each carry the
+state their guessed tokens lead to (`qpal_grammar_rows`).  No host read in a step; bank.set / reset between replays of a captured
+step change the next draw.
 """
 import math
 
@@ -64,6 +71,7 @@ import torch
 
 from . import _native as nat
 from . import hadamard as had
+from . import grammar as gram_mod
 from . import linear, logits, lora, ops, sampling
 from .attention import (attention_workspace, decode_attention, paged_decode_attention, paged_prefill_attention,
                         paged_ragged_prefill_attention, prefill_attention, prefill_workspace, ragged_prefill_attention, ragged_workspace)
@@ -112,10 +120,11 @@ class _Rows:
     _launches_per = None  # "<class>: launches are per <what>" where a step has no launches per token
 
     def __init__(self, who, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows, sampler, block_table, slots=None,
-                 logits_tail=False, native_argmax=False, adapters=None, processor=None):
+                 logits_tail=False, native_argmax=False, adapters=None, processor=None, grammar=None):
         """slots: the sequences of the caches where the caller fixes them (DecodeStep's B), else read off the caches or the table;
         logits_tail: the tail is qpal_lm_head_logits without a sampler too; native_argmax: `_argmax_tail` is the one-launch kernel;
-        adapters: a lora.LoraBank of these layers and slots, or None; processor: a logits.LogitProcessor of these slots, or None"""
+        adapters: a lora.LoraBank of these layers and slots, or None; processor: a logits.LogitProcessor of these slots, or None;
+        grammar: a grammar.GrammarBank of these slots, or None"""
         self.block_table = block_table
         self.slots = self._check_table(who, kcache, block_table, slots)
         self.adapters = self._check_adapters(who, adapters, self.slots, layers, embed)
@@ -125,6 +134,7 @@ class _Rows:
         if logits_tail:
             self._check_lm_head(who, embed, lm_head)
         self.processor = self._check_processor(who, processor, self.slots, embed, lm_head, sampler is not None or logits_tail)
+        self.grammar = self._check_grammar(who, grammar, self.slots, embed, lm_head, sampler is not None)
         att, mlp = layers[0].self_attn, layers[0].mlp
         H, dev = att.hidden_size, embed.device
         self.layers, self.embed, self.norm, self.lm_head, self.inv_freq = layers, embed, norm, lm_head, inv_freq
@@ -188,6 +198,16 @@ class _Rows:
             raise nat.QpalError(f"{who}: processor must be a LogitProcessor of {B} slots of {lm_head.shape[0]} logits on {embed.device}")
         return proc
 
+    @staticmethod
+    def _check_grammar(who, bank, B, embed, lm_head, sampled):
+        if bank is None:
+            return None
+        if not sampled:
+            raise nat.QpalError(f"{who}: a grammar masks the logits of a sampler's tail: give the step a sampler (greedy: temperature 0)")
+        if not isinstance(bank, gram_mod.GrammarBank) or bank.B != B or bank.vocab != lm_head.shape[0] or bank.device != embed.device:
+            raise nat.QpalError(f"{who}: grammar must be a GrammarBank of {B} slots of {lm_head.shape[0]} tokens on {embed.device}")
+        return bank
+
     @property
     def launches_per_token(self):
         raise nat.QpalError(f"{self._launches_per} (9 per layer), not per token")
@@ -239,17 +259,24 @@ class _Rows:
             self._layer(i, *bufs)
         return bufs[0]
 
-    def _sample_tail(self, h32, smp, ctr, out_tok, row_slot=None, fed=None):
+    def _sample_tail(self, h32, smp, ctr, out_tok, row_slot=None, fed=None, gslot=None):
         """final norm + lm_head of every row of h32 into smp.logits, then one draw per row with the counters ctr: two launches; with
         smp.logprob a third, the log-probability of the tokens just drawn (rows with ctr < 0 drew nothing and keep theirs).  With a
         processor (row_slot: the rows' slots) two launches in between: the tokens `fed` to the rows are counted where given, and the
-        logits are processed in place — the draw and the log-probabilities are those of the processed logits"""
+        logits are processed in place — the draw and the log-probabilities are those of the processed logits.  With a grammar two
+        more: the mask of every row's automaton state behind the processor, and behind the draw the advance of the states by the
+        drawn tokens (gslot None: row = slot, all of them; an int: the one row is that slot's)"""
         sampling.lm_head_logits(h32, self.norm.weight, self.norm.eps, self.lm_head, out=smp.logits)
         if self.processor is not None:
             if fed is not None:
                 logits.observe(self.processor, fed, row_slot, active=ctr)
             logits.process(smp.logits, self.processor, row_slot, ctr)
+        if self.grammar is not None:
+            state = self.grammar.state if gslot is None else self.grammar.state[gslot:gslot + 1]
+            gram_mod.grammar_mask(smp.logits, self.grammar, row_slot, ctr, row_state=state)
         sampling.sample(smp.logits, smp, ctr, out=out_tok)
+        if self.grammar is not None:
+            gram_mod.grammar_advance(self.grammar, out_tok, active=ctr, slot0=gslot or 0)
         if smp.logprob is not None:
             sampling.token_logprobs(smp.logits, out_tok, out=smp.logprob, active=ctr)
 
@@ -285,16 +312,20 @@ class DecodeStep(_Rows):
     processor: a logits.LogitProcessor of B slots (needs a sampler).  The tail becomes lm_head logits, observe — every active row's
     fed token tok[b] is counted for slot b —, process in place on sampler.logits, the draw, then the log-probability launch of a
     sampler with logprobs: sampler.logits and sampler.logprob are then the PROCESSED logits and the log-probabilities under them.
-    Two more launches.  The step counts every token it feeds, whatever the processor's count_prompt."""
+    Two more launches.  The step counts every token it feeds, whatever the processor's count_prompt.
+    grammar: a grammar.GrammarBank of B slots (needs a sampler; greedy is temperature 0).  Behind the processor every active row of
+    a slot with a grammar is masked with the tokens its automaton state allows (bank.state[b], read by the launch), and behind the
+    draw out_tok[b] advances that state, with the positions as the active vector: two more launches.  sampler.logits and
+    sampler.logprob are then the MASKED logits and the log-probabilities under them.  The grammar sees generated tokens only."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok, generic=False,
                  swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True, sampler=None, block_table=None,
-                 adapters=None, processor=None):
+                 adapters=None, processor=None, grammar=None):
         B = tok.shape[0]
         self.batch1 = B == 1 and not generic
         super().__init__("DecodeStep", layers, embed, norm, lm_head, kcache, vcache, inv_freq, B, sampler, block_table, slots=B,
-                         native_argmax=self.batch1 and native_lm_head, adapters=adapters, processor=processor)
-        self._row_slot = None if processor is None else torch.arange(B, dtype=torch.int32, device=embed.device)  # row = slot
+                         native_argmax=self.batch1 and native_lm_head, adapters=adapters, processor=processor, grammar=grammar)
+        self._row_slot = None if processor is None and grammar is None else torch.arange(B, dtype=torch.int32, device=embed.device)  # row = slot
         if adapters is not None:
             self.row_adapter, swiglu_epilogue = adapters.slot_adapter, False  # row = slot
         if self.batch1 and not fusable(layers):
@@ -329,11 +360,12 @@ class DecodeStep(_Rows):
         q|k|v, o and up|gate where the GEMV cannot rotate; - the SwiGLU rotation where down_proj's staging runs it); + the norm /
         lm_head / argmax launch, or the lm_head logits and the draw with a sampler, + the log-probability launch of a sampler with
         logprobs (the embedding row copy is a memcpy node); with adapters + 4 per layer, one per projection group; with a
-        processor + 2, observe and process"""
+        processor + 2, observe and process; with a grammar + 2, mask and advance"""
         per_layer = (5 if self.ug_il and self.ug_il[0][2] else 6) if self.rot_in_gemv else 9
         per_layer += 4 if getattr(self, "adapters", None) is not None else 0  # (arithmetic on the configuration: stand-ins may lack it)
         tail = 1 if self.sampler is None else (2 if self.sampler.logprob is None else 3)
         tail += 2 if getattr(self, "processor", None) is not None else 0
+        tail += 2 if getattr(self, "grammar", None) is not None else 0
         return per_layer * len(self.layers) + tail
 
     def _gemv(self, proj, x, su, scale, rms=None, **kw):
@@ -409,20 +441,23 @@ class Prefill(_Rows):
 
     processor: the logits.LogitProcessor of that DecodeStep (needs a sampler).  With processor.count_prompt the tokens of the call
     are counted for the slot, chunk by chunk (one observe launch each); the last row's logits are processed with the slot's state
-    before the draw.  The counts are not reset: a new request calls processor.reset(slot) first."""
+    before the draw.  The counts are not reset: a new request calls processor.reset(slot) first.
+
+    grammar: the grammar.GrammarBank of that DecodeStep (needs a sampler).  The prompt is not walked: the last row's logits are
+    masked with the slot's state as it stands (bank.set / reset put it at the start) and the drawn token advances it."""
 
     _launches_per = "Prefill: launches are per chunk"
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, native_lm_head=True, sampler=None,
-                 block_table=None, adapters=None, processor=None):
+                 block_table=None, adapters=None, processor=None, grammar=None):
         if not 1 <= int(chunk) <= 128:
             raise nat.QpalError(f"Prefill: chunk must be in 1 .. 128, got {chunk}")
         self.chunk = int(chunk)
         dev, H = embed.device, embed.shape[1]
         super().__init__("Prefill", layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.chunk, sampler, block_table,
                          native_argmax=native_lm_head and H in (2048, 4096, 8192) and lm_head.data_ptr() % 16 == 0, adapters=adapters,
-                         processor=processor)
-        self._row_slot = None if processor is None else torch.zeros(1, dtype=torch.int32, device=dev)  # the call's slot
+                         processor=processor, grammar=grammar)
+        self._row_slot = None if processor is None and grammar is None else torch.zeros(1, dtype=torch.int32, device=dev)  # the call's slot
         self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
         self.out_tok = torch.zeros(1, dtype=torch.int64, device=dev)
         self.ctr = torch.zeros(1, dtype=torch.int64, device=dev)  # with a sampler: the last prompt row's position
@@ -451,7 +486,7 @@ class Prefill(_Rows):
         if not 0 <= int(slot) < self.slots:
             raise nat.QpalError(f"{who}: slot {slot} outside the caches' {self.slots} sequences")
         self.slot = int(slot)
-        if self.processor is not None:
+        if self._row_slot is not None:
             self._row_slot.fill_(self.slot)
         if self.adapters is not None:
             self.row_adapter.copy_(self.adapters.slot_adapter[self.slot:self.slot + 1].expand(self.chunk))
@@ -480,7 +515,7 @@ class Prefill(_Rows):
             pass
         if self.sampler is not None:
             torch.sub(self.pos, 1, out=self.ctr)
-            self._sample_tail(self.last32, self.sampler.slot(self.slot), self.ctr, self.out_tok, row_slot=self._row_slot)
+            self._sample_tail(self.last32, self.sampler.slot(self.slot), self.ctr, self.out_tok, row_slot=self._row_slot, gslot=self.slot)
         else:
             self._argmax_tail(self.last32, self.out_tok)
         return self.out_tok
@@ -559,20 +594,23 @@ class RaggedStep(_Rows):
     adapters: a lora.LoraBank of the caches' slots — a row of segment s runs with bank.slot_adapter[seq[s]], rows of no segment
     with none; the map row -> segment -> slot -> adapter is made on the device in every call.
 
-    processor: not on a RaggedStep (QpalError): a prompt chunk's rows would have to be counted row by row; SpeculativeStep has one."""
+    processor: not on a RaggedStep (QpalError): a prompt chunk's rows would have to be counted row by row; SpeculativeStep has one.
+    grammar: not on a RaggedStep either (QpalError); DecodeStep, Prefill and SpeculativeStep take one."""
 
     _launches_per = "RaggedStep: launches are per step"
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=128, segments=16, sampler=None, block_table=None,
-                 adapters=None, processor=None):
+                 adapters=None, processor=None, grammar=None):
         who = type(self).__name__
         if processor is not None and not isinstance(self, SpeculativeStep):
             raise nat.QpalError("RaggedStep: no processor on a ragged step (DecodeStep, Prefill and SpeculativeStep take one)")
+        if grammar is not None and not isinstance(self, SpeculativeStep):
+            raise nat.QpalError("RaggedStep: no grammar on a ragged step (DecodeStep, Prefill and SpeculativeStep take one)")
         if not 1 <= int(rows) <= 128 or not 1 <= int(segments) <= 128:
             raise nat.QpalError(f"{who}: rows and segments must be in 1 .. 128, got {rows}, {segments}")
         self.rows, self.segments = int(rows), int(segments)
         super().__init__(who, layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.rows, sampler, block_table, logits_tail=True,
-                         adapters=adapters, processor=processor)
+                         adapters=adapters, processor=processor, grammar=grammar)
         dev = embed.device
         self._row_id = torch.arange(self.rows, dtype=torch.int32, device=dev)
         self._no_adapter = torch.full((self.rows,), -1, dtype=torch.int32, device=dev)
@@ -705,12 +743,20 @@ class SpeculativeStep(RaggedStep):
     only resets); every row's logits are processed with its slot's state and, as extras, the guessed tokens in front of it in its
     segment — what sequential decoding would have counted by then; after the accept the emitted tokens are counted.  So count[b] is
     always the histogram of the counted part of hist[b][0 .. n_tok[b]), and the stream stays the sequential one.  `release` leaves
-    the counts alone.  A slot's mask holds for all rows of its segment: it cannot follow a grammar inside a multi-token step — a
-    grammar-driven caller uses DecodeStep, or draft=0.  More launches per step: process, observe, and two small torch ops that build
-    observe's active vector from n_out."""
+    the counts alone.  A slot's mask holds for all rows of its segment: a caller's own mask cannot change inside a multi-token
+    step — a grammar that must follow the text goes in as `grammar=`.  More launches per step: process, observe, and two small
+    torch ops that build observe's active vector from n_out.
+
+    grammar: a grammar.GrammarBank of the caches' slots (needs a sampler, greedy is temperature 0).  Behind the
+    draft every row gets the automaton state its guessed tokens lead to from bank.state[b] (`qpal_grammar_rows`; a row behind a
+    guess the grammar forbids is dead), every live row is masked with its own state behind the processor, and behind the accept
+    out_tok[b, :n_out[b]] advances bank.state[b]: three more launches.  A guess the grammar forbids at its position cannot equal
+    the masked draw of the row in front of it, so the draft is cut there, and every row before the cut carries the state sequential
+    decoding would have had: the stream is the sequential one.  `begin` puts the slot's state at the start; `release` leaves it
+    alone.  Give `begin` the table's eos as `eos`, so that the slot stops where its text ends."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, draft=4, gram=(2, 4), rows=None, sampler=None,
-                 block_table=None, history=None, adapters=None, processor=None):
+                 block_table=None, history=None, adapters=None, processor=None, grammar=None):
         B, K = self._check_table("SpeculativeStep", kcache, block_table), int(draft)
         if not 0 <= K <= 15 or len(gram) != 2 or not 1 <= int(gram[0]) <= int(gram[1]) <= 8:
             raise nat.QpalError(f"SpeculativeStep: draft must be in 0 .. 15 and 1 <= gram[0] <= gram[1] <= 8, got {draft}, {gram}")
@@ -719,8 +765,9 @@ class SpeculativeStep(RaggedStep):
             raise nat.QpalError(f"SpeculativeStep: rows must be in B = {B} .. 128, got {rows}")
         self.draft_len, self.gram = K, (int(gram[0]), int(gram[1]))
         super().__init__(layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=rows, segments=B, sampler=sampler,
-                         block_table=block_table, adapters=adapters, processor=processor)
+                         block_table=block_table, adapters=adapters, processor=processor, grammar=grammar)
         dev = embed.device
+        self._row_state = None if grammar is None else torch.full((rows,), -1, dtype=torch.int32, device=dev)
         self.history = self.context if history is None else int(history)
         if self.history < 1:
             raise nat.QpalError(f"SpeculativeStep: history must be at least 1, got {history}")
@@ -773,6 +820,8 @@ class SpeculativeStep(RaggedStep):
             self.processor.reset(slot)
             if self.processor.count_prompt:
                 self.processor.count_tokens(slot, toks)
+        if self.grammar is not None:
+            self.grammar.reset(slot)
 
     def release(self, slot):
         """the slot has no sequence: no rows in the steps that follow"""
@@ -786,6 +835,8 @@ class SpeculativeStep(RaggedStep):
             raise nat.QpalError("SpeculativeStep: ext_n without ext_draft")
         spec.spec_draft(self.hist, self.n_tok, self.limit, self.draft_len, self.gram, self.context, self.tokens, self.seq, self.row0,
                         self.pos0, self.row_slot, self.row_ctr, self.n_draft, ext_draft=ext_draft, ext_n=ext_n)
+        if self.grammar is not None:
+            gram_mod.grammar_rows(self.grammar, self.tokens, self.row0, self._row_state)
         # a caller's draft may be no token of the model: it can equal no draw, so any valid row of the embedding stands in for it
         tokens = self.tokens if ext_draft is None else torch.clamp(self.tokens, max=self.embed.shape[0] - 1, out=self._gather)
         self._map_rows(self.seq, self.row0)
@@ -793,6 +844,8 @@ class SpeculativeStep(RaggedStep):
         sampling.lm_head_logits(self.h32, self.norm.weight, self.norm.eps, self.lm_head, out=self.draw.logits)
         if self.processor is not None:
             logits.process(self.draw.logits, self.processor, self.row_slot, self.row_ctr, tokens=self.tokens, row0=self.row0)
+        if self.grammar is not None:
+            gram_mod.grammar_mask(self.draw.logits, self.grammar, self.row_slot, self.row_ctr, row_state=self._row_state)
         if self.sampler is not None:
             self._gather_draw(self.row_slot.to(torch.int64).clamp(min=0))
         sampling.sample(self.draw.logits, self.draw, self.row_ctr, out=self.drawn)
@@ -802,6 +855,8 @@ class SpeculativeStep(RaggedStep):
             torch.index_select(self.draw.logprob, 0, rows.reshape(-1), out=self.out_logprob.view(-1))
         spec.spec_accept(self.tokens, self.drawn, self.seq, self.row0, self.hist, self.n_tok, self.limit, self.eos, self.out_tok,
                          self.n_out, self.n_acc)
+        if self.grammar is not None:
+            gram_mod.grammar_advance(self.grammar, self.out_tok, n=self.n_out)
         if self.processor is not None:
             torch.sub(self.n_out.to(torch.int64)[:, None], self._lane1[None, :], out=self._obs_active.view(-1, self.draft_len + 1))
             logits.observe(self.processor, self.out_tok.view(-1), self._obs_slot, active=self._obs_active)
