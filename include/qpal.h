@@ -190,7 +190,9 @@ int qpal_hadamard(void *out_f16, const void *in, const void *su, const void *sv,
  * (the residual stream), rms(x) = sqrt(mean(x^2) + rms_eps), w = rms_w (fp16 [n]) or 1 — input_layernorm /
  * post_attention_layernorm (model/llama.py:119) followed by the left rotation of the incoherent wrappers, for the widths the
  * GEMV staging cannot rotate itself (qpal_can_fuse_rotation == 0: k = 8192, 5120, ...).  n = K * 2^p as for qpal_hadamard
- * (hd = n); the norm's scalar is applied after the transform (linear), one fp16 rounding of x * w * 2^-6 on the way in.   */
+ * (hd = n); the norm's scalar is applied after the transform (linear), one fp16 rounding of x * w * 2^-6 on the way in.  Held to
+ * the bound of DESIGN.md §25.3 for rows with rms(x) >= 2^-8 (as the x_rms staging of the GEMV launches is); smaller rows put
+ * x * w * 2^-6 into fp16 subnormals, which the matrix pipe keeps (measured down to rms 2^-12: same bound).                  */
 int qpal_hadamard_rms(void *out_f16, const float *in_f32, const void *rms_w, float rms_eps, const void *su, const void *hadk,
                       int rows, int n, int K, float post_scale, void *stream);
 
@@ -296,7 +298,8 @@ int qpal_rope_kv(const float *q, const float *k, const float *v, void *q_out_f16
 int qpal_attn_decode(const void *q_f16, const void *kcache_f16, const void *vcache_f16, void *out_f16, const long *pos,
                      int nq, int nkv, int hd, long max_len, float scale, void *stream);
 
-/* The tail of a greedy decode step as one launch: x = fp16(rmsnorm(h) [* rms_w]) (rms_eps = 0: x = fp16(h)), logits = W x with
+/* The tail of a greedy decode step as one launch: x = fp16(fp16(h * rsqrt(mean(h^2) + rms_eps)) * rms_w), two fp16 roundings like
+ * the reference's LlamaRMSNorm (rms_w_f16 == NULL: w = 1; rms_eps <= 0: no norm, x = fp16(h), rms_w_f16 ignored), logits = W x with
  * W the fp16 lm_head [vocab][k] (k in {2048, 4096, 8192}, 16-byte aligned), *token = argmax (lowest index on ties); logits
  * (fp32 [vocab]) are also written when the pointer is not NULL.  ws: qpal_lm_head_ws_bytes(vocab) bytes of device memory,
  * zero-filled once, kept across launches.  Replaces model.norm + lm_head + argmax of the reference's decode loop
@@ -440,9 +443,9 @@ int qpal_attn_rope_prefill_ragged_paged(const float *q, const float *k, const fl
  * logits a sampler needs, and the batch-B tail of a decode step.  h_f32 fp32 [rows][ld_h] (ld_h >= k, in elements), 1 <= rows <=
  * 128; k a multiple of 512, 512 <= k <= 8192; w_f16 the lm_head fp16 [vocab][k]; logits_f32 fp32 [rows][ld_logits], ld_logits >=
  * vocab: logits[b][v] for v < vocab is written, columns vocab .. ld_logits are left as they were.  Per row the arithmetic of
- * qpal_lm_head_argmax: x = fp16(h * rsqrt(mean(h^2) + rms_eps)), then * rms_w in fp16 (rms_eps <= 0 or rms_w_f16 == NULL: x =
- * fp16(h)); fp32 accumulation.  Every lm_head row is read once for all rows; no workspace, no atomics, one writer per logit: two
- * launches are bitwise equal.  Alignment: w_f16 and h_f32 16 bytes, ld_h % 4 == 0 when rows > 1, rms_w_f16 8 bytes, logits 4. */
+ * qpal_lm_head_argmax: x = fp16(h * rsqrt(mean(h^2) + rms_eps)), then * rms_w in fp16 (rms_w_f16 == NULL: w = 1; rms_eps <= 0: no
+ * norm, x = fp16(h), rms_w_f16 ignored); fp32 accumulation.  Every lm_head row is read once for all rows; no workspace, no
+ * atomics, one writer per logit: two launches are bitwise equal.  Alignment: w_f16 and h_f32 16 bytes, ld_h % 4 == 0 when rows > 1, rms_w_f16 8 bytes, logits 4. */
 int qpal_lm_head_logits(const float *h_f32, long ld_h, const void *rms_w_f16, float rms_eps, const void *w_f16, float *logits_f32,
                         long ld_logits, int rows, int vocab, int k, void *stream);
 

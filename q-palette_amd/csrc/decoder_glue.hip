@@ -951,7 +951,8 @@ extern "C" int qpal_lm_head_argmax(const float *h_f32, const void *rms_w_f16, fl
     if ((reinterpret_cast<uintptr_t>(w_f16) & 15) || (reinterpret_cast<uintptr_t>(ws) & 3) || (reinterpret_cast<uintptr_t>(h_f32) & 3) ||
         (rms_w_f16 && (reinterpret_cast<uintptr_t>(rms_w_f16) & 1)))
         return QPAL_E_ALIGN;
-    LmHeadParams p{h_f32, static_cast<const uint16_t *>(rms_w_f16), rms_eps > 0.f ? rms_eps : 0.f, static_cast<const uint16_t *>(w_f16),
+    const bool norm = rms_eps > 0.f;  // rms_eps <= 0: x = fp16(h), the weight belongs to the norm and goes with it
+    LmHeadParams p{h_f32, norm ? static_cast<const uint16_t *>(rms_w_f16) : nullptr, norm ? rms_eps : 0.f, static_cast<const uint16_t *>(w_f16),
                    logits_f32, token, static_cast<float *>(ws), vocab, k};
     const int grid = lm_head_grid(vocab);
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -20,8 +20,8 @@ typedef float float4_t __attribute__((ext_vector_type(4)));
 struct LmLogitsParams {
     const float *h;          // fp32 [rows][ld_h]
     long ld_h;
-    const uint16_t *rms_w;   // fp16 [k] or null
-    float rms_eps;           // 0: no norm (x = fp16(h))
+    const uint16_t *rms_w;   // fp16 [k] or null (w = 1)
+    float rms_eps;           // 0: no norm (x = fp16(h), rms_w null)
     const uint16_t *w;       // fp16 [vocab][k]
     float *logits;           // fp32 [rows][ld_logits]
     long ld_logits;
@@ -165,7 +165,7 @@ extern "C" int qpal_lm_head_logits(const float *h_f32, long ld_h, const void *rm
     if ((reinterpret_cast<uintptr_t>(w_f16) & 15) || (reinterpret_cast<uintptr_t>(h_f32) & 15) || (rows > 1 && ld_h % 4) ||
         (reinterpret_cast<uintptr_t>(logits_f32) & 3) || (rms_w_f16 && (reinterpret_cast<uintptr_t>(rms_w_f16) & 7)))
         return QPAL_E_ALIGN;
-    const bool norm = rms_eps > 0.f && rms_w_f16;
+    const bool norm = rms_eps > 0.f;  // no weight: w = 1, as in qpal_lm_head_argmax, x_rms and qpal_hadamard_rms
     LmLogitsParams p{h_f32, ld_h, norm ? static_cast<const uint16_t *>(rms_w_f16) : nullptr, norm ? rms_eps : 0.f,
                      static_cast<const uint16_t *>(w_f16), logits_f32, ld_logits, rows, vocab, k};
     const int grid = (vocab + 255) / 256;

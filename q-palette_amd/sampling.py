@@ -137,7 +137,8 @@ def _torch():
 
 
 def lm_head_logits(h32, norm_weight, eps, lm_head, out=None):
-    """logits fp32 [rows, vocab] = lm_head @ fp16(RMSNorm(h32) * norm_weight) per row (eps <= 0 or norm_weight None: fp16(h32)).
+    """logits fp32 [rows, vocab] = lm_head @ fp16(fp16(RMSNorm(h32)) * norm_weight) per row; norm_weight None: weight 1, as in the
+    other norm entry points; eps <= 0: no norm at all, x = fp16(h32), and norm_weight is ignored.
     h32 fp32 [rows, k] (rows may be strided), 1 <= rows <= 128, k a multiple of 512 up to 8192; lm_head fp16 [vocab, k] contiguous,
     16-byte aligned; out: fp32 [rows, >= vocab columns] with contiguous rows (columns past vocab are left alone).  Launches on the
     current stream."""
@@ -156,6 +157,7 @@ def lm_head_logits(h32, norm_weight, eps, lm_head, out=None):
     if lm_head.data_ptr() % 16 or h32.data_ptr() % 16 or ld_h % 4:
         raise QpalError(f"{who}: lm_head and h32 must be 16-byte aligned, the row stride of h32 a multiple of 4")
     w = None
+    eps = float(eps) if eps > 0 else 0.0
     if norm_weight is not None and eps > 0:
         w = norm_weight
         if w.dtype != torch.float16 or w.shape != (k,) or not w.is_contiguous() or w.device != h32.device or w.data_ptr() % 8:
@@ -167,7 +169,7 @@ def lm_head_logits(h32, norm_weight, eps, lm_head, out=None):
         raise QpalError(f"{who}: out must be fp32 [{rows}, >= {vocab}] with contiguous rows on {h32.device}")
     ld_out = out.stride(0) if rows > 1 else out.shape[1]
     with torch.cuda.device(h32.device):
-        rc = _native.lib().qpal_lm_head_logits(h32.data_ptr(), ld_h, w.data_ptr() if w is not None else None, float(eps) if w is not None else 0.0,
+        rc = _native.lib().qpal_lm_head_logits(h32.data_ptr(), ld_h, w.data_ptr() if w is not None else None, eps,
                                                lm_head.data_ptr(), out.data_ptr(), ld_out, rows, vocab, k,
                                                torch.cuda.current_stream(h32.device).cuda_stream)
     _native.check(rc, "qpal_lm_head_logits")

@@ -168,7 +168,10 @@ def test_rmsnorm_fp32_stream_and_accumulate_in_the_gemv_launch(qp, qstr):
     su = (torch.randint(0, 2, (k,), device=dev, generator=gen) * 2 - 1).half()
     wsc = (0.01 + 0.01 * torch.rand(m, device=dev, generator=gen)).half()
     eps, scale = 1e-5, 64.0
-    x_norm = torch.nn.functional.rms_norm(h32, (k,), w_ln.float(), eps).half()   # fp32 norm, one fp16 rounding (the reference)
+    # fp32 norm, ONE fp16 rounding, f16(h inv w): the rule the fused per-layer norm aims at (glue_reference.norm_one_rounding).  The
+    # reference's LlamaRMSNorm (model/llama.py:129-135) rounds twice, f16(f16(h inv) w) — the rule of the two lm_head kernels; the two
+    # differ by at most one fp16 ulp (test_glue_exact.py)
+    x_norm = torch.nn.functional.rms_norm(h32, (k,), w_ln.float(), eps).half()
     xr = qp.hadamard.rotate(x_norm, su=su, post_scale=1.0 / scale)
     (ref,) = qp.multi_gemv([layer], xr, wscales=[wsc], oscale=scale)
     (got,) = qp.multi_gemv([layer], h32, wscales=[wsc], oscale=scale, x_rot=(su, 1.0 / scale), x_rms=(eps, w_ln))
