@@ -569,18 +569,6 @@ int dequant_chunks(int nrows, int st1, int st2) {
     return nch;
 }
 
-// An accumulating job (out += y: the residual add of a decoder block) is never zeroed: its split-K atomics add onto what
-// `out` already holds, which IS the accumulation (a memset here would silently turn h + y into y).
-int zero_if_split(const TcParams &p, int m, hipStream_t stream, int out_zeroed = 0) {
-    if (p.sk > 1 && !out_zeroed && !p.accumulate) {
-        // ONE node for the whole [n][m] block (a batch of 64 used to cost 64 memset nodes per layer)
-        hipError_t e = p.ldo == m ? hipMemsetAsync(p.out, 0, sizeof(float) * (size_t)m * p.n, stream)
-                                  : hipMemset2DAsync(p.out, sizeof(float) * (size_t)p.ldo, 0, sizeof(float) * (size_t)m, (size_t)p.n, stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
-}
-
 int launch_tcq_gemm(const TcMultiParams &mp, int S, int KV1, int KV2, int nbg, int grid, hipStream_t stream) {
     return nbg == 1 ? launch_tcq_gemm_nbg1(mp, S, KV1, KV2, grid, stream)
          : nbg == 2 ? launch_tcq_gemm_nbg2(mp, S, KV1, KV2, grid, stream)
@@ -590,9 +578,10 @@ int launch_tcq_gemm(const TcMultiParams &mp, int S, int KV1, int KV2, int nbg, i
                     : launch_tcq_gemm_nbg16(mp, S, KV1, KV2, grid, stream);
 }
 
-// Zeroing of the split-K outputs of a multi-job launch: contiguous [n][m] outputs that follow each other in memory (how
+// Zeroing of the split-K outputs of a launch: contiguous [n][m] outputs that follow each other in memory (how
 // qpalette_amd.ops allocates the outputs of one launch) are zeroed by ONE memset node — a node costs ~5 us inside a graph, more
-// than filling a megabyte.
+// than filling a megabyte.  An accumulating job (out += y: the residual add of a decoder block) is never zeroed: its split-K
+// atomics add onto what `out` already holds, which IS the accumulation (a memset here would silently turn h + y into y).
 int zero_split_jobs(const TcMultiParams &mp, const int *ms, const int *zeroed, hipStream_t stream) {
     struct Span { char *p; size_t bytes; };
     Span spans[kMaxJobs];
@@ -601,8 +590,8 @@ int zero_split_jobs(const TcMultiParams &mp, const int *ms, const int *zeroed, h
         const TcParams &p = mp.job[j];
         if (p.act_out || p.sk <= 1 || zeroed[j] || p.accumulate) continue;
         if (p.ldo != ms[j]) {  // a column block of a wider buffer: its own 2-D fill
-            int rc = zero_if_split(p, ms[j], stream, 0);
-            if (rc) return rc;
+            hipError_t e = hipMemset2DAsync(p.out, sizeof(float) * (size_t)p.ldo, 0, sizeof(float) * (size_t)ms[j], (size_t)p.n, stream);
+            if (e != hipSuccess) return (int)e;
             continue;
         }
         spans[ns++] = Span{reinterpret_cast<char *>(p.out), sizeof(float) * (size_t)ms[j] * p.n};
@@ -621,28 +610,6 @@ int zero_split_jobs(const TcMultiParams &mp, const int *ms, const int *zeroed, h
     return 0;
 }
 
-int tcq_gemv_one(float *out, long ldo, const void *c1, const void *c2, const void *x, const void *tlut, int m, int n,
-                 int k, int k1, int k2, int S, int KV1, int KV2, hipStream_t stream) {
-    TcMultiParams mp{};
-    mp.njobs = 1;
-    tcq_fill(mp.job[0], out, ldo, c1, c2, x, tlut, m, n, k, k1, k2);
-    int grid;
-    const int nbg = nbg_of(n);
-    if (use_gemm(nbg, mp)) {
-        int ms[kMaxJobs] = {m}, zeroed[kMaxJobs] = {0};
-        const int rows = slice_gemm_batch(mp, ms, zeroed);
-        plan_gemm(mp, grid, nbg_of(rows) <= env_int("QPAL_GEMM_TWO_NBG", 1) && S == 9);
-        int rc = zero_split_jobs(mp, ms, zeroed, stream);
-        if (rc) return rc;
-        return launch_tcq_gemm(mp, S, KV1, KV2, nbg_of(rows), grid, stream);
-    }
-    if (nbg > 8) return QPAL_E_SHAPE;  // (batches 65..128: the lockstep kernel only — it needs 16-byte aligned x and k % 8 == 0)
-    plan_launch(mp, nullptr, grid, waves_of(nbg));
-    int rc = zero_if_split(mp.job[0], m, stream);
-    if (rc) return rc;
-    return launch_tcq_gemv(mp, S, KV1, KV2, nbg, grid, stream);
-}
-
 int tcq_check(const void *c1, const void *c2, const void *tlut, int m, int k, int S, int KV1, int KV2, int split) {
     if (!c1 || !tlut) return QPAL_E_NULL;
     if (split != QPAL_SPLIT_NONE && !c2) return QPAL_E_NULL;
@@ -656,90 +623,78 @@ int tcq_check(const void *c1, const void *c2, const void *tlut, int m, int k, in
     return QPAL_OK;
 }
 
-}  // namespace
+// ---- One host path for every fused GEMV / lockstep GEMM launch.  The entry points differ in their own argument checks and in
+// how a job becomes a TcParams (a job function per family: its checks in their order, then tcq_fill / lut_fill); everything
+// else — the fields qpal_tcq_job and qpal_lut_job carry under the same names, and all that follows the per-job loop — is
+// launch_jobs().  What still differs behind the loop is a family descriptor: TcqFamily / LutFamily below.
+// tests/capi_trace.hip runs this path without a GPU and pins every launch it computes.
 
-extern "C" {
-
-int qpal_tcq_gemv(float *out, const void *c1, const void *c2, const void *x, const void *tlut, int m, int n, int k,
-                  int S, int KV1, int KV2, int split, void *stream) {
-    int rc = tcq_check(c1, c2, tlut, m, k, S, KV1, KV2, split);
-    if (rc) return rc;
-    if (!out || !x) return QPAL_E_NULL;
-    if (n < 1 || n > kMaxBatch) return QPAL_E_SHAPE;
-    if (!aligned(x, 8) || !aligned(out, 4) || (k % 4)) return QPAL_E_ALIGN;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (split == QPAL_SPLIT_NONE) return tcq_gemv_one(out, m, c1, nullptr, x, tlut, m, n, k, k, 0, S, KV1, 0, s);
-    if (split == QPAL_SPLIT_COLS)
-        return tcq_gemv_one(out, m, c1, c2, x, tlut, m, n, k, k / 2, k / 2, S, KV1, KV2, s);
-    // row halves: two independent single-stream problems writing the two halves of each output row
-    rc = tcq_gemv_one(out, m, c1, nullptr, x, tlut, m / 2, n, k, k, 0, S, KV1, 0, s);
-    if (rc) return rc;
-    return tcq_gemv_one(out + m / 2, m, c2, nullptr, x, tlut, m / 2, n, k, k, 0, S, KV2, 0, s);
-}
-
-int qpal_tcq_gemv_multi(const qpal_tcq_job *jobs, int njobs, int n, int S, int KV1, int KV2, int split, void *prezero,
-                        long prezero_bytes, void *stream) {
+int multi_args_ok(const void *jobs, int njobs, const void *prezero, long prezero_bytes) {
     if (!jobs) return QPAL_E_NULL;
     if (njobs < 1 || njobs > kMaxJobs) return QPAL_E_SHAPE;
     if (prezero_bytes < 0 || prezero_bytes % 16 || (prezero_bytes && (!prezero || !aligned(prezero, 16)))) return QPAL_E_ALIGN;
-    if (split == QPAL_SPLIT_ROWS) return QPAL_E_PARAM;  // the two row halves use different codecs: one call each
-    if (n < 1 || n > kMaxBatch) return QPAL_E_SHAPE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    {   // a launch holds at most two row geometries (k, single / two streams): more -> one launch per geometry
-        long keys[kMaxJobs];
-        int nkeys = 0;
-        for (int j = 0; j < njobs; j++) {
-            const long key = (long)jobs[j].k * 2 + ((split == QPAL_SPLIT_COLS || (jobs[j].kv && jobs[j].kv2 && jobs[j].c2)) ? 1 : 0);
-            int i = 0;
-            while (i < nkeys && keys[i] != key) i++;
-            if (i == nkeys) keys[nkeys++] = key;
-        }
-        if (nkeys > 2) {
-            for (int i = 0; i < nkeys; i++) {
-                qpal_tcq_job sub[kMaxJobs];
-                int ns = 0;
-                for (int j = 0; j < njobs; j++)
-                    if ((long)jobs[j].k * 2 + ((split == QPAL_SPLIT_COLS || (jobs[j].kv && jobs[j].kv2 && jobs[j].c2)) ? 1 : 0) == keys[i]) sub[ns++] = jobs[j];
-                int rc = qpal_tcq_gemv_multi(sub, ns, n, S, KV1, KV2, split, i == 0 ? prezero : nullptr, i == 0 ? prezero_bytes : 0, stream);
-                if (rc) return rc;
-            }
-            return QPAL_OK;
-        }
+    return QPAL_OK;
+}
+
+// A launch holds at most two row geometries: with more, one launch per geometry (key), in the order of their first jobs;
+// prezero goes to the first one.
+template <class J, class Key, class Launch>
+int launch_per_geometry(const J *jobs, int njobs, void *prezero, long prezero_bytes, Key key, Launch launch) {
+    long keys[kMaxJobs];
+    int nkeys = 0;
+    for (int j = 0; j < njobs; j++) {
+        int i = 0;
+        while (i < nkeys && keys[i] != key(jobs[j])) i++;
+        if (i == nkeys) keys[nkeys++] = key(jobs[j]);
     }
+    if (nkeys <= 2) return launch(jobs, njobs, prezero, prezero_bytes);
+    for (int i = 0; i < nkeys; i++) {
+        J sub[kMaxJobs];
+        int ns = 0;
+        for (int j = 0; j < njobs; j++)
+            if (key(jobs[j]) == keys[i]) sub[ns++] = jobs[j];
+        int rc = launch(sub, ns, i == 0 ? prezero : nullptr, i == 0 ? prezero_bytes : 0);
+        if (rc) return rc;
+    }
+    return QPAL_OK;
+}
+
+// the job fields both families have, behind the family's own checks and fill (which set p.x, p.out, p.k)
+template <class J>
+int shared_job_fields(const J &jb, TcParams &p, int n, int image_bytes) {
+    if (jb.x_f32 && !jb.x_had) return QPAL_E_PARAM;  // fp32 input: rotation staging only
+    if (jb.act_out && (!jb.x_had || n != 1 || jb.accumulate || (jb.m % 64) || !aligned(jb.act_out, 2))) return QPAL_E_PARAM;
+    if ((jb.x && !aligned(jb.x, 8)) || !aligned(jb.out, 4)) return QPAL_E_ALIGN;
+    if (jb.wscale && !aligned(jb.wscale, 2)) return QPAL_E_ALIGN;
+    if (jb.ldo != 0 && jb.ldo < jb.m) return QPAL_E_SHAPE;
+    int rc = set_rotation(p, jb.x_had, jb.x_su, jb.x_post, n, jb.k, jb.x_f32, jb.x_rms_eps, jb.x_rms_w, jb.x_hadk, jb.x_K, image_bytes);
+    if (rc) return rc;
+    p.accumulate = jb.accumulate ? 1 : 0;
+    p.act_out = static_cast<uint16_t *>(jb.act_out);
+    p.act_su = jb.act_out ? static_cast<const uint16_t *>(jb.act_su) : nullptr;
+    return QPAL_OK;
+}
+
+// two lockstep workgroups per CU (plan_gemm): up to QPAL_GEMM_TWO_NBG batch groups, where the family's LDS use leaves the room
+bool gemm_two_per_cu(int nbg, bool family_has_room) {
+    static const int two_nbg = env_int("QPAL_GEMM_TWO_NBG", 1);
+    return nbg <= two_nbg && family_has_room;
+}
+
+// job_fn(job, TcParams &, fam) -> code: the family's checks and fill (it may note in fam what it saw: TcqFamily::mixed).  fam: image_bytes(), refuse(mp, n) -> code (shapes the family's
+// kernels do not have), lockstep() (may the lockstep kernel run this launch), two_per_cu(), gemm(...) and gemv(...) (the launchers).
+template <class J, class JobFn, class Fam>
+int launch_jobs(const J *jobs, int njobs, int n, void *prezero, long prezero_bytes, hipStream_t s, JobFn job_fn, Fam fam) {
     TcMultiParams mp{};
     mp.njobs = njobs;
-    int zeroed[kMaxJobs] = {0};
-    bool mixed = false;  // jobs with their own KV: the any-KV kernel of this S
+    int ms[kMaxJobs] = {0}, zeroed[kMaxJobs] = {0};
     for (int j = 0; j < njobs; j++) {
-        const qpal_tcq_job &jb = jobs[j];
-        const int kv = jb.kv ? jb.kv : KV1;
-        const bool job_two = split == QPAL_SPLIT_NONE && jb.kv && jb.kv2 && jb.c2;  // column-split layer in an any-KV launch
-        mixed = mixed || kv != KV1 || job_two;
-        if ((kv != KV1 || job_two) && (split != QPAL_SPLIT_NONE || jb.x_had)) return QPAL_E_PARAM;
-        if (jb.kv2 && !job_two) return QPAL_E_PARAM;
-        int rc = job_two ? tcq_check(jb.c1, jb.c2, jb.tlut, jb.m, jb.k, S, kv, jb.kv2, QPAL_SPLIT_COLS)
-                         : tcq_check(jb.c1, jb.c2, jb.tlut, jb.m, jb.k, S, kv, KV2, split);
+        int rc = job_fn(jobs[j], mp.job[j], fam);
         if (rc) return rc;
-        if ((!jb.out && !jb.act_out) || (!jb.x && !(jb.x_f32 && jb.x_had))) return QPAL_E_NULL;
-        if (jb.x_f32 && !jb.x_had) return QPAL_E_PARAM;  // fp32 input: rotation staging only
-        if (jb.act_out && (!jb.x_had || n != 1 || jb.accumulate || (jb.m % 64) || !aligned(jb.act_out, 2))) return QPAL_E_PARAM;
-        if ((jb.x && !aligned(jb.x, 8)) || !aligned(jb.out, 4) || (jb.k % 4)) return QPAL_E_ALIGN;
-        if (jb.wscale && !aligned(jb.wscale, 2)) return QPAL_E_ALIGN;
-        if (jb.ldo != 0 && jb.ldo < jb.m) return QPAL_E_SHAPE;
-        const long ldo = jb.ldo ? jb.ldo : jb.m;
-        if (split == QPAL_SPLIT_NONE && !job_two)
-            tcq_fill(mp.job[j], jb.out, ldo, jb.c1, nullptr, jb.x, jb.tlut, jb.m, n, jb.k, jb.k, 0, jb.wscale, jb.oscale);
-        else
-            tcq_fill(mp.job[j], jb.out, ldo, jb.c1, jb.c2, jb.x, jb.tlut, jb.m, n, jb.k, jb.k / 2, jb.k / 2, jb.wscale,
-                     jb.oscale);
-        mp.job[j].kv = kv;
-        mp.job[j].kv2 = job_two ? jb.kv2 : 0;
-        rc = set_rotation(mp.job[j], jb.x_had, jb.x_su, jb.x_post, n, jb.k, jb.x_f32, jb.x_rms_eps, jb.x_rms_w, jb.x_hadk, jb.x_K);
+        rc = shared_job_fields(jobs[j], mp.job[j], n, fam.image_bytes());
         if (rc) return rc;
-        mp.job[j].accumulate = jb.accumulate ? 1 : 0;
-        mp.job[j].act_out = static_cast<uint16_t *>(jb.act_out);
-        mp.job[j].act_su = jb.act_out ? static_cast<const uint16_t *>(jb.act_su) : nullptr;
-        zeroed[j] = jb.act_out ? 1 : jb.out_zeroed;  // (nothing to zero: `out` is not written; split-K is refused below)
+        ms[j] = jobs[j].m;
+        zeroed[j] = jobs[j].out_zeroed;  // (an act_out job does not write `out`: the planner shares no row of it, zero_split_jobs skips it)
     }
     // the kernel stages (or rotates) x once per distinct x pointer: jobs that share x must agree on how
     for (int j = 1; j < njobs; j++)
@@ -751,47 +706,120 @@ int qpal_tcq_gemv_multi(const qpal_tcq_job *jobs, int njobs, int n, int S, int K
                 return QPAL_E_PARAM;
     for (int j = 1; j < njobs; j++)  // one kernel per launch: the 14336-wide rotation has its own instantiation
         if ((mp.job[j].x_rot == kK28) != (mp.job[0].x_rot == kK28)) return QPAL_E_PARAM;
-    if (mixed) {
-        if (n > 8) return QPAL_E_SHAPE;
-        for (int j = 0; j < njobs; j++) {
-            for (const int kv : {mp.job[j].kv, mp.job[j].kv2})
-                if (kv && ((S == 9 && kv > 8) || (S == 10 && kv < 8) || (S == 11 && kv < 9))) return QPAL_E_PARAM;
-        }
-    }
+    int rc = fam.refuse(mp, n);
+    if (rc) return rc;
     mp.zero = static_cast<u32x4 *>(prezero);
     mp.zero_chunks = (int)(prezero_bytes / 16);
     int grid;
     const int nbg = nbg_of(n);
-    if (nbg >= 4)
-        for (int j = 0; j < njobs; j++)
-            if (jobs[j].x_had) return QPAL_E_SHAPE;  // fused rotation: batch 1
-    const bool gemm = !mixed && use_gemm(nbg, mp);
-    int ms[kMaxJobs] = {0};
-    if (gemm) {
-        for (int j = 0; j < njobs; j++) {
-            ms[j] = jobs[j].m;
-            zeroed[j] = jobs[j].out_zeroed;
-        }
+    if (fam.lockstep() && use_gemm(nbg, mp)) {
         const int rows = slice_gemm_batch(mp, ms, zeroed);
-        plan_gemm(mp, grid, nbg_of(rows) <= env_int("QPAL_GEMM_TWO_NBG", 1) && S == 9);
-        int rc = zero_split_jobs(mp, ms, zeroed, s);
+        plan_gemm(mp, grid, gemm_two_per_cu(nbg_of(rows), fam.two_per_cu()));
+        rc = zero_split_jobs(mp, ms, zeroed, s);
         if (rc) return rc;
-        return launch_tcq_gemm(mp, S, KV1, split == QPAL_SPLIT_NONE ? 0 : KV2, nbg_of(rows), grid, s);
+        return fam.gemm(mp, nbg_of(rows), grid, s);
     }
-    if (nbg > 8) return QPAL_E_SHAPE;  // (batches 65..128: the lockstep kernel only)
+    if (nbg > 8) return QPAL_E_SHAPE;  // (batches 65..128: the lockstep kernel only — it needs 16-byte aligned x and k % 8 == 0)
     plan_launch(mp, zeroed, grid, waves_of(nbg));
-    for (int j = 0; j < njobs; j++) {
-        ms[j] = jobs[j].m;
-        zeroed[j] = jobs[j].out_zeroed;
+    for (int j = 0; j < njobs; j++)
         // the SwiGLU epilogue pairs two supertile rows of one workgroup and has no shared-row form (the planner keeps to that)
         if (mp.job[j].act_out && (mp.job[j].sk != 1 || mp.plan[mp.job[j].cls].rg < 2)) return QPAL_E_SHAPE;
+    rc = zero_split_jobs(mp, ms, zeroed, s);
+    if (rc) return rc;
+    return fam.gemv(mp, nbg, grid, s);
+}
+
+struct TcqFamily {
+    int S, KV1, KV2;     // KV2: 0 for a single-stream launch
+    bool mixed = false;  // jobs with their own KV (noted by the job function while it fills them): the any-KV kernel of this S
+    int image_bytes() const { return 64 * 1024; }
+    bool lockstep() const { return !mixed; }
+    bool two_per_cu() const { return S == 9; }
+    int refuse(const TcMultiParams &mp, int n) const {
+        if (!mixed) return QPAL_OK;
+        if (n > 8) return QPAL_E_SHAPE;
+        for (int j = 0; j < mp.njobs; j++)
+            for (const int kv : {mp.job[j].kv, mp.job[j].kv2})
+                if (kv && S == 9 && kv > 8) return QPAL_E_PARAM;  // (the any-KV kernel of S = 9 stops at 8; S = 10, 11: tcq_check's ranges)
+        return QPAL_OK;
     }
-    {
-        int rc = zero_split_jobs(mp, ms, zeroed, s);
-        if (rc) return rc;
+    int gemm(const TcMultiParams &mp, int nbg, int grid, hipStream_t s) const { return launch_tcq_gemm(mp, S, KV1, KV2, nbg, grid, s); }
+    int gemv(const TcMultiParams &mp, int nbg, int grid, hipStream_t s) const {
+        return mixed ? launch_tcq_gemv_any(mp, S, grid, s) : launch_tcq_gemv(mp, S, KV1, KV2, nbg, grid, s);
     }
-    if (mixed) return launch_tcq_gemv_any(mp, S, grid, s);
-    return launch_tcq_gemv(mp, S, KV1, split == QPAL_SPLIT_NONE ? 0 : KV2, nbg, grid, s);
+};
+
+struct LutFamily {
+    int bits, vec;
+    int image_bytes() const { return lut_image_bytes(bits, vec); }
+    bool lockstep() const { return true; }
+    bool two_per_cu() const { return image_bytes() <= 64 * 1024; }
+    // the reduction buffer of 8 batch groups (64 KiB) does not fit beside a 128 KiB codebook image (the LDS holds the x tiles of 64 batch rows)
+    int refuse(const TcMultiParams &, int n) const { return nbg_of(n) >= 10 && image_bytes() > 64 * 1024 ? QPAL_E_SHAPE : QPAL_OK; }
+    int gemm(const TcMultiParams &mp, int nbg, int grid, hipStream_t s) const { return launch_lut_tc_gemm(mp, bits, vec, nbg, grid, s); }
+    int gemv(const TcMultiParams &mp, int nbg, int grid, hipStream_t s) const { return launch_lut_tc_gemv(mp, bits, vec, nbg, grid, s); }
+};
+
+}  // namespace
+
+extern "C" {
+
+int qpal_tcq_gemv(float *out, const void *c1, const void *c2, const void *x, const void *tlut, int m, int n, int k,
+                  int S, int KV1, int KV2, int split, void *stream) {
+    int rc = tcq_check(c1, c2, tlut, m, k, S, KV1, KV2, split);
+    if (rc) return rc;
+    if (!out || !x) return QPAL_E_NULL;
+    if (n < 1 || n > kMaxBatch) return QPAL_E_SHAPE;
+    if (!aligned(x, 8) || !aligned(out, 4)) return QPAL_E_ALIGN;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // one job; row halves: two independent single-stream problems writing the two halves of each output row
+    auto one = [&](float *o, const void *a, const void *b, int rows, int kva, int kvb) {
+        qpal_tcq_job jb{};
+        jb.out = o; jb.c1 = a; jb.c2 = b; jb.x = x; jb.tlut = tlut; jb.m = rows; jb.k = k; jb.ldo = m;
+        auto fill = [&](const qpal_tcq_job &j, TcParams &p, TcqFamily &) {
+            tcq_fill(p, j.out, j.ldo, j.c1, j.c2, j.x, j.tlut, j.m, n, k, b ? k / 2 : k, b ? k / 2 : 0);
+            return QPAL_OK;
+        };
+        return launch_jobs(&jb, 1, n, nullptr, 0, s, fill, TcqFamily{S, kva, kvb});
+    };
+    if (split == QPAL_SPLIT_NONE) return one(out, c1, nullptr, m, KV1, 0);
+    if (split == QPAL_SPLIT_COLS) return one(out, c1, c2, m, KV1, KV2);
+    rc = one(out, c1, nullptr, m / 2, KV1, 0);
+    if (rc) return rc;
+    return one(out + m / 2, c2, nullptr, m / 2, KV2, 0);
+}
+
+int qpal_tcq_gemv_multi(const qpal_tcq_job *jobs, int njobs, int n, int S, int KV1, int KV2, int split, void *prezero,
+                        long prezero_bytes, void *stream) {
+    int rc = multi_args_ok(jobs, njobs, prezero, prezero_bytes);
+    if (rc) return rc;
+    if (split == QPAL_SPLIT_ROWS) return QPAL_E_PARAM;  // the two row halves use different codecs: one call each
+    if (n < 1 || n > kMaxBatch) return QPAL_E_SHAPE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // column-split layer in an any-KV launch
+    auto job_two = [&](const qpal_tcq_job &jb) { return split == QPAL_SPLIT_NONE && jb.kv && jb.kv2 && jb.c2; };
+    // row geometry: k, single / two streams
+    auto key = [&](const qpal_tcq_job &jb) { return (long)jb.k * 2 + ((split == QPAL_SPLIT_COLS || (jb.kv && jb.kv2 && jb.c2)) ? 1 : 0); };
+    return launch_per_geometry(jobs, njobs, prezero, prezero_bytes, key, [&](const qpal_tcq_job *sub, int ns, void *pz, long pz_bytes) {
+        auto job_fn = [&](const qpal_tcq_job &jb, TcParams &p, TcqFamily &fam) -> int {
+            const int kv = jb.kv ? jb.kv : KV1;
+            const bool two = job_two(jb);
+            fam.mixed = fam.mixed || kv != KV1 || two;
+            if ((kv != KV1 || two) && (split != QPAL_SPLIT_NONE || jb.x_had)) return QPAL_E_PARAM;
+            if (jb.kv2 && !two) return QPAL_E_PARAM;
+            int rc = two ? tcq_check(jb.c1, jb.c2, jb.tlut, jb.m, jb.k, S, kv, jb.kv2, QPAL_SPLIT_COLS)
+                         : tcq_check(jb.c1, jb.c2, jb.tlut, jb.m, jb.k, S, kv, KV2, split);
+            if (rc) return rc;
+            if ((!jb.out && !jb.act_out) || (!jb.x && !(jb.x_f32 && jb.x_had))) return QPAL_E_NULL;
+            const bool single = split == QPAL_SPLIT_NONE && !two;
+            tcq_fill(p, jb.out, jb.ldo ? jb.ldo : jb.m, jb.c1, single ? nullptr : jb.c2, jb.x, jb.tlut, jb.m, n, jb.k,
+                     single ? jb.k : jb.k / 2, single ? 0 : jb.k / 2, jb.wscale, jb.oscale);
+            p.kv = kv;
+            p.kv2 = two ? jb.kv2 : 0;
+            return QPAL_OK;
+        };
+        return launch_jobs(sub, ns, n, pz, pz_bytes, s, job_fn, TcqFamily{S, KV1, split == QPAL_SPLIT_NONE ? 0 : KV2});
+    });
 }
 
 int qpal_tcq_dequant(void *out_f16, const void *c1, const void *c2, const void *tlut, int m, int k, int S, int KV1,
@@ -864,89 +892,19 @@ int qpal_lut_tc_gemv(float *out, const void *qweight, const void *x, const void 
 
 int qpal_lut_tc_gemv_multi(const qpal_lut_job *jobs, int njobs, int n, int bits, int vec, void *prezero,
                            long prezero_bytes, void *stream) {
-    if (!jobs) return QPAL_E_NULL;
-    if (njobs < 1 || njobs > kMaxJobs) return QPAL_E_SHAPE;
-    if (prezero_bytes < 0 || prezero_bytes % 16 || (prezero_bytes && (!prezero || !aligned(prezero, 16)))) return QPAL_E_ALIGN;
+    int rc = multi_args_ok(jobs, njobs, prezero, prezero_bytes);
+    if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    {   // a launch holds at most two row geometries (here: k): more -> one launch per k
-        int keys[kMaxJobs], nkeys = 0;
-        for (int j = 0; j < njobs; j++) {
-            int i = 0;
-            while (i < nkeys && keys[i] != jobs[j].k) i++;
-            if (i == nkeys) keys[nkeys++] = jobs[j].k;
-        }
-        if (nkeys > 2) {
-            for (int i = 0; i < nkeys; i++) {
-                qpal_lut_job sub[kMaxJobs];
-                int ns = 0;
-                for (int j = 0; j < njobs; j++)
-                    if (jobs[j].k == keys[i]) sub[ns++] = jobs[j];
-                int rc = qpal_lut_tc_gemv_multi(sub, ns, n, bits, vec, i == 0 ? prezero : nullptr, i == 0 ? prezero_bytes : 0, stream);
-                if (rc) return rc;
-            }
+    auto key = [](const qpal_lut_job &jb) { return (long)jb.k; };  // row geometry: k
+    return launch_per_geometry(jobs, njobs, prezero, prezero_bytes, key, [&](const qpal_lut_job *sub, int ns, void *pz, long pz_bytes) {
+        auto job_fn = [&](const qpal_lut_job &jb, TcParams &p, LutFamily &) -> int {
+            int rc = lut_args_ok(jb.out ? jb.out : jb.act_out, jb.qweight, jb.x ? jb.x : (jb.x_had ? jb.x_f32 : nullptr), jb.lut, jb.m, n, jb.k, bits, vec);
+            if (rc) return rc;
+            lut_fill(p, jb.out, jb.ldo ? jb.ldo : jb.m, jb.qweight, jb.x, jb.lut, jb.m, n, jb.k, jb.wscale, jb.oscale);
             return QPAL_OK;
-        }
-    }
-    TcMultiParams mp{};
-    mp.njobs = njobs;
-    int zeroed[kMaxJobs] = {0};
-    for (int j = 0; j < njobs; j++) {
-        const qpal_lut_job &jb = jobs[j];
-        int rc = lut_args_ok(jb.out ? jb.out : jb.act_out, jb.qweight, jb.x ? jb.x : (jb.x_had ? jb.x_f32 : nullptr), jb.lut, jb.m, n, jb.k, bits, vec);
-        if (rc) return rc;
-        if (jb.x_f32 && !jb.x_had) return QPAL_E_PARAM;  // fp32 input: rotation staging only
-        if (jb.act_out && (!jb.x_had || n != 1 || jb.accumulate || (jb.m % 64) || !aligned(jb.act_out, 2))) return QPAL_E_PARAM;
-        if (jb.wscale && !aligned(jb.wscale, 2)) return QPAL_E_ALIGN;
-        if (jb.ldo != 0 && jb.ldo < jb.m) return QPAL_E_SHAPE;
-        lut_fill(mp.job[j], jb.out, jb.ldo ? jb.ldo : jb.m, jb.qweight, jb.x, jb.lut, jb.m, n, jb.k, jb.wscale, jb.oscale);
-        rc = set_rotation(mp.job[j], jb.x_had, jb.x_su, jb.x_post, n, jb.k, jb.x_f32, jb.x_rms_eps, jb.x_rms_w, jb.x_hadk, jb.x_K,
-                          lut_image_bytes(bits, vec));
-        if (rc) return rc;
-        mp.job[j].accumulate = jb.accumulate ? 1 : 0;
-        mp.job[j].act_out = static_cast<uint16_t *>(jb.act_out);
-        mp.job[j].act_su = jb.act_out ? static_cast<const uint16_t *>(jb.act_su) : nullptr;
-        zeroed[j] = jb.act_out ? 1 : jb.out_zeroed;
-    }
-    for (int j = 1; j < njobs; j++)
-        for (int i = 0; i < j; i++)
-            if (mp.job[i].x == mp.job[j].x &&
-                (jobs[i].x_had != jobs[j].x_had || jobs[i].x_su != jobs[j].x_su || jobs[i].x_post != jobs[j].x_post ||
-                 jobs[i].k != jobs[j].k || jobs[i].x_rms_eps != jobs[j].x_rms_eps || jobs[i].x_rms_w != jobs[j].x_rms_w ||
-                 jobs[i].x_K != jobs[j].x_K || jobs[i].x_hadk != jobs[j].x_hadk))
-                return QPAL_E_PARAM;
-    for (int j = 1; j < njobs; j++)
-        if ((mp.job[j].x_rot == kK28) != (mp.job[0].x_rot == kK28)) return QPAL_E_PARAM;
-    mp.zero = static_cast<u32x4 *>(prezero);
-    mp.zero_chunks = (int)(prezero_bytes / 16);
-    int grid;
-    const int nbg = nbg_of(n);
-    // the reduction buffer of 8 batch groups (64 KiB) does not fit beside a 128 KiB codebook image
-    if (nbg >= 10 && lut_image_bytes(bits, vec) > 64 * 1024) return QPAL_E_SHAPE;  // (128 KiB image: the LDS holds the x tiles of 64 batch rows)
-    const bool gemm = use_gemm(nbg, mp);
-    int ms[kMaxJobs] = {0};
-    if (gemm) {
-        for (int j = 0; j < njobs; j++) {
-            ms[j] = jobs[j].m;
-            zeroed[j] = jobs[j].out_zeroed;
-        }
-        const int rows = slice_gemm_batch(mp, ms, zeroed);
-        plan_gemm(mp, grid, nbg_of(rows) <= env_int("QPAL_GEMM_TWO_NBG", 1) && lut_image_bytes(bits, vec) <= 64 * 1024);
-        int rc = zero_split_jobs(mp, ms, zeroed, s);
-        if (rc) return rc;
-        return launch_lut_tc_gemm(mp, bits, vec, nbg_of(rows), grid, s);
-    }
-    if (nbg > 8) return QPAL_E_SHAPE;  // (batches 65..128: the lockstep kernel only)
-    plan_launch(mp, zeroed, grid, waves_of(nbg));
-    for (int j = 0; j < njobs; j++) {
-        ms[j] = jobs[j].m;
-        zeroed[j] = jobs[j].out_zeroed;
-        if (mp.job[j].act_out && (mp.job[j].sk != 1 || mp.plan[mp.job[j].cls].rg < 2)) return QPAL_E_SHAPE;
-    }
-    {
-        int rc = zero_split_jobs(mp, ms, zeroed, s);
-        if (rc) return rc;
-    }
-    return launch_lut_tc_gemv(mp, bits, vec, nbg, grid, s);
+        };
+        return launch_jobs(sub, ns, n, pz, pz_bytes, s, job_fn, LutFamily{bits, vec});
+    });
 }
 
 int qpal_lut_tc_dequant(void *out_f16, const void *qweight, const void *lut, int m, int k, int bits, int vec,

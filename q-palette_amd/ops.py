@@ -334,6 +334,41 @@ def _rms_args(x_rms, k):
     return float(eps), (w.data_ptr() if w is not None else None)
 
 
+def _multi_gemv(entry, job_type, codec, layers, ms, pack, x, *, outs, outs_zeroed, prezero, wscales, oscale, x_rot, x_rms, accumulate,
+                act_outs, act_su):
+    """The body tcq_gemv_multi and lut_tc_gemv_multi share: the arguments of the input, one job struct per layer, the call.
+    pack(layer, k) -> (the family's own fields of job_type by name, the tensors they point into); ms: the layers' output rows;
+    codec: the entry point's arguments between the batch and prezero."""
+    n, k = x.shape
+    _chk(1 <= n <= MAX_FUSED_BATCH, "batch size must be in 1..128")
+    xh, x32 = _x_arg(x, x_rot)
+    had, xpost, xsu, xhadk, xK = _rot_args(x_rot, x, k)
+    rms_eps, rms_w = _rms_args(x_rms, k)
+    _chk(x_rms is None or x_rot is not None, "x_rms needs x_rot (the RMSNorm is fused into the rotation's input)")
+    jobs = (job_type * len(layers))()
+    results, keep = [], [xh, x32]  # (keep: what _dev may have copied stays alive until the call has returned)
+    if outs is None and act_outs is None and len(layers) > 1:
+        outs = _fresh_outs(ms, n, x.device)
+        outs_zeroed = False
+    for j, (layer, m) in enumerate(zip(layers, ms)):
+        own, tensors = pack(layer, k)
+        act = _act_arg(act_outs, j, n, m, x.device)
+        out = None if act is not None else _out_arg(outs, j, n, m, x.device)
+        jobs[j] = job_type(out=out.data_ptr() if out is not None else None, x=xh.data_ptr() if xh is not None else None, m=m, k=k,
+                           out_zeroed=1 if (outs is not None and outs_zeroed) else 0, wscale=_wscale_arg(wscales, j, m),
+                           oscale=float(oscale), ldo=_ldo(out, n, m) if out is not None else 0, x_had=had, x_post=xpost, x_su=xsu,
+                           x_f32=x32.data_ptr() if x32 is not None else None, x_rms_eps=rms_eps, x_rms_w=rms_w,
+                           accumulate=1 if accumulate else 0, act_out=act.data_ptr() if act is not None else None, x_hadk=xhadk,
+                           x_K=xK, act_su=_act_su_arg(act_su, act, m), **own)
+        results.append(out)
+        keep += tensors
+    zp, zb = _prezero_args(prezero)
+    with torch.cuda.device_of(x):
+        rc = getattr(nat.lib(), entry)(jobs, len(layers), n, *codec, zp, zb, _stream(x))
+    nat.check(rc, entry)
+    return results
+
+
 def tcq_gemv_multi(streams, x, S, KV1, KV2=0, split=0, outs=None, outs_zeroed=False, prezero=None, wscales=None,
                    oscale=1.0, x_rot=None, x_rms=None, accumulate=False, act_outs=None, act_su=None):
     """Several TCQ GEMVs of one codec and one input in ONE launch (C-ABI qpal_tcq_gemv_multi).
@@ -343,18 +378,7 @@ def tcq_gemv_multi(streams, x, S, KV1, KV2=0, split=0, outs=None, outs_zeroed=Fa
     also zeroes for a later split-K launch on the same stream.
     wscales / oscale: fused epilogue out = acc * wscales[j][row] * oscale (the incoherent wrappers' Wscale * scale).
     x_rot = (su, post): x is the un-rotated input; the kernel stages fp16(fp16(H (x * su) / sqrt(k)) * post) itself."""
-    n, k = x.shape
-    _chk(1 <= n <= MAX_FUSED_BATCH, "batch size must be in 1..128")
-    xh, x32 = _x_arg(x, x_rot)
-    had, xpost, xsu, xhadk, xK = _rot_args(x_rot, x, k)
-    rms_eps, rms_w = _rms_args(x_rms, k)
-    _chk(x_rms is None or x_rot is not None, "x_rms needs x_rot (the RMSNorm is fused into the rotation's input)")
-    jobs = (nat.TcqJob * len(streams))()
-    results, keep = [], [xh, x32]
-    if outs is None and act_outs is None and len(streams) > 1:
-        outs = _fresh_outs([st[3] for st in streams], n, x.device)
-        outs_zeroed = False
-    for j, stream in enumerate(streams):
+    def pack(stream, k):
         c1, c2, tlut, m = stream[:4]
         kv = stream[4] if len(stream) > 4 else 0
         kv2 = stream[5] if len(stream) > 5 else 0
@@ -372,54 +396,24 @@ def tcq_gemv_multi(streams, x, S, KV1, KV2=0, split=0, outs=None, outs_zeroed=Fa
             c2 = _dev(c2, "compressed2")
             _tcq_stream_ok(c1, m, k // 2, KV1, "compressed1")
             _tcq_stream_ok(c2, m, k // 2, KV2, "compressed2")
-        act = _act_arg(act_outs, j, n, m, x.device)
-        out = None if act is not None else _out_arg(outs, j, n, m, x.device)
-        jobs[j] = nat.TcqJob(out.data_ptr() if out is not None else None, c1.data_ptr(), c2.data_ptr() if c2 is not None else None,
-                             xh.data_ptr() if xh is not None else None, tl.data_ptr(), m, k,
-                             1 if (outs is not None and outs_zeroed) else 0,
-                             _wscale_arg(wscales, j, m), float(oscale), _ldo(out, n, m) if out is not None else 0, had, xpost, xsu, kv,
-                             x32.data_ptr() if x32 is not None else None, rms_eps, rms_w, 1 if accumulate else 0, kv2,
-                             act.data_ptr() if act is not None else None, xhadk, xK, _act_su_arg(act_su, act, m))
-        results.append(out)
-        keep += [c1, c2, tl]
-    zp, zb = _prezero_args(prezero)
-    with torch.cuda.device_of(x):
-        rc = nat.lib().qpal_tcq_gemv_multi(jobs, len(streams), n, S, KV1, KV2, split, zp, zb, _stream(x))
-    nat.check(rc, "qpal_tcq_gemv_multi")
-    return results
+        return dict(c1=c1.data_ptr(), c2=c2.data_ptr() if c2 is not None else None, tlut=tl.data_ptr(), kv=kv, kv2=kv2), [c1, c2, tl]
+
+    return _multi_gemv("qpal_tcq_gemv_multi", nat.TcqJob, (S, KV1, KV2, split), streams, [st[3] for st in streams], pack, x,
+                       outs=outs, outs_zeroed=outs_zeroed, prezero=prezero, wscales=wscales, oscale=oscale, x_rot=x_rot, x_rms=x_rms,
+                       accumulate=accumulate, act_outs=act_outs, act_su=act_su)
 
 
 def lut_tc_gemv_multi(layers, x, bits, vec, outs=None, outs_zeroed=False, prezero=None, wscales=None, oscale=1.0,
                       x_rot=None, x_rms=None, accumulate=False, act_outs=None, act_su=None):
     """Several VQ/SQ (tensor-core packing) GEMVs of one codec and one input in ONE launch.
     layers: list of (qweight, lut, m); x: [n, k].  outs / outs_zeroed / prezero as in tcq_gemv_multi."""
-    n, k = x.shape
-    _chk(1 <= n <= MAX_FUSED_BATCH, "batch size must be in 1..128")
-    xh, x32 = _x_arg(x, x_rot)
-    had, xpost, xsu, xhadk, xK = _rot_args(x_rot, x, k)
-    rms_eps, rms_w = _rms_args(x_rms, k)
-    _chk(x_rms is None or x_rot is not None, "x_rms needs x_rot (the RMSNorm is fused into the rotation's input)")
-    jobs = (nat.LutJob * len(layers))()
-    results, keep = [], [xh, x32]
-    if outs is None and act_outs is None and len(layers) > 1:
-        outs = _fresh_outs([l[2] for l in layers], n, x.device)
-        outs_zeroed = False
-    for j, (q, lut, m) in enumerate(layers):
-        q, cb = _lut_args(q, lut, m, k, bits, vec)
-        act = _act_arg(act_outs, j, n, m, x.device)
-        out = None if act is not None else _out_arg(outs, j, n, m, x.device)
-        jobs[j] = nat.LutJob(out.data_ptr() if out is not None else None, q.data_ptr(), xh.data_ptr() if xh is not None else None,
-                             cb.data_ptr(), m, k, 1 if (outs is not None and outs_zeroed) else 0, _wscale_arg(wscales, j, m),
-                             float(oscale), _ldo(out, n, m) if out is not None else 0, had, xpost, xsu,
-                             x32.data_ptr() if x32 is not None else None, rms_eps, rms_w, 1 if accumulate else 0,
-                             act.data_ptr() if act is not None else None, xhadk, xK, _act_su_arg(act_su, act, m))
-        results.append(out)
-        keep += [q, cb]
-    zp, zb = _prezero_args(prezero)
-    with torch.cuda.device_of(x):
-        rc = nat.lib().qpal_lut_tc_gemv_multi(jobs, len(layers), n, bits, vec, zp, zb, _stream(x))
-    nat.check(rc, "qpal_lut_tc_gemv_multi")
-    return results
+    def pack(layer, k):
+        q, cb = _lut_args(layer[0], layer[1], layer[2], k, bits, vec)
+        return dict(qweight=q.data_ptr(), lut=cb.data_ptr()), [q, cb]
+
+    return _multi_gemv("qpal_lut_tc_gemv_multi", nat.LutJob, (bits, vec), layers, [l[2] for l in layers], pack, x, outs=outs,
+                       outs_zeroed=outs_zeroed, prezero=prezero, wscales=wscales, oscale=oscale, x_rot=x_rot, x_rms=x_rms,
+                       accumulate=accumulate, act_outs=act_outs, act_su=act_su)
 
 
 def tc_to_simt(qweight_tc, m, k, bits, vec):

@@ -463,3 +463,24 @@ def test_gemv_launch_planner_tables():
     assert pl["lg"] == 0 and pl["rg"] in (2, 4, 8, 16) and all(j["sk"] == 1 for j in d["jobs"])
     leads = [(a & 255, (a >> 17) & 1) for a, b in pl["w"][0] if (a >> 9) & 1]
     assert leads and all(flag == (1 - row % 2) for row, flag in leads)
+
+
+def test_host_path_trace_matches_the_golden_record(tmp_path):
+    """The host side of every fused GEMV / lockstep GEMM launch (csrc/qpal_capi.hip: argument checks, the split per row geometry,
+    the planners, the memsets in front of split-K launches) never dereferences a device pointer, so it runs without a GPU:
+    tests/capi_trace.hip links qpal_capi.hip, compiled host-only, against recording stubs of the launchers and the memsets and sweeps
+    qpal_tcq_gemv, qpal_tcq_gemv_multi, qpal_lut_tc_gemv and qpal_lut_tc_gemv_multi with made-up addresses — every codec, batch
+    group, split, job variation and argument error, and a reduced sweep per knob in a process of its own.  Each case's return code
+    and the digest of its recorded calls (launcher, integer arguments, every field of the parameter block; memset pointers and
+    sizes) must be the golden file's: a host-path change that computes another launch for any case is caught here."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_capi_trace", os.path.join(ROOT, "tests", "golden", "make_golden_capi_trace.py"))
+    tr = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tr)
+    exe = tr.build(str(tmp_path))
+    got = tr.run_all(exe)
+    want = tr.read_golden()
+    assert [name for name, _, _ in tr.RUNS] == list(want), "the golden file's sections are the runs, in order"
+    assert len(got["default"]) >= 4000 and all(len(got[name]) >= 700 for name in got)
+    report = tr.compare(exe, got, want)
+    assert not report, report
