@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Steady-state in-kernel timeline of the headline token: the token's HIP graph is replayed and EVERY GEMV launch stamps into one
-buffer (STAMPS build, QPAL_STAMPS_BUF: csrc/tcq_launch.h), so the stamps read afterwards are those of the last launch of each
+buffer (STAMPS build, QPAL_STAMPS_BUF: csrc/gemv_stamps.h), so the stamps read afterwards are those of the last launch of each
 shape inside a replayed graph — not of an eager launch on a chip that was idle a moment ago (those show 2-4 us of wake-up).
     make -C q-palette_amd/csrc STAMPS=1 && python perf/stamps_replay.py [--layers 4]"""
 import argparse

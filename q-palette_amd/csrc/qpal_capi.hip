@@ -19,17 +19,7 @@ constexpr int kMaxBatch = 128;  // fused decode + skinny GEMM: up to 8 groups of
 // batch -> 8-row units the kernels are instantiated for: 1, 2 (16 waves per workgroup), 4, 8 (8 waves: tc_kernels.h gemv_waves);
 // 16 (batch 65..128): the lockstep kernel of tc_gemm16.h only
 int nbg_of(int n) { return n <= 8 ? 1 : n <= 16 ? 2 : n <= 32 ? 4 : n <= 64 ? 8 : n <= 80 ? 10 : 16; }
-int waves_of(int nbg) { return gemv_waves<1>() == 8 ? 8 : (nbg >= 4 ? 8 : 16); }
-// workgroups one launch round can hold: one per CU; two with the 8-wave experiment build (tc_kernels.h QPAL_W8), whose
-// batch <= 16 kernels leave room for a second workgroup's LDS and registers
-int round_capacity(int waves) {
-#if defined(QPAL_W8) && !defined(QPAL_W8_ONE)
-    return waves == 8 ? 2 * kNumCU : kNumCU;   // (the wide-batch kernels use 256 VGPRs: they would also fit twice, LDS allowing)
-#else
-    (void)waves;
-    return kNumCU;
-#endif
-}
+int waves_of(int nbg) { return nbg >= 4 ? gemv_waves<4>() : gemv_waves<1>(); }
 
 inline bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
@@ -56,24 +46,17 @@ bool simt_ok(int bits, int vec) {
 
 // reduction buffer [16 waves][n][32] fp32 + x [n][k] fp16 must fit the kernel's LDS scratch
 int x_fits_lds(int n, int k) {
-    static const int no_xlds = getenv("QPAL_NO_XLDS") != nullptr;
-    return !no_xlds && n <= 8 && gemv_waves<1>() * 32 * 4 * n + 2 * n * k + 64 <= kScratchBytes && (n * k) % 8 == 0;
+    return n <= 8 && gemv_waves<1>() * 32 * 4 * n + 2 * n * k + 64 <= kScratchBytes && (n * k) % 8 == 0;
 }
 
 // (k = 8192 would need the 8-row-tile transform: its registers do not fit the GEMV kernel's 128-VGPR budget)
 // and batch 1 only: the workgroup-wide transform needs 16 KiB of LDS beside x (larger batches: qpal_hadamard first)
 bool rot_ok(int n, int k) {
-#ifdef QPAL_W8
-    return false;  // the workgroup-wide transform is written for 16 waves
-#endif
     return n == 1 && (k == 2048 || k == 4096) && x_fits_lds(n, k);
 }
 
 // the 14336-wide rotation inside the staging (rot_k28.h): batch 1, x in LDS, a codebook image that can lend 40 KiB
 bool rot_k28_ok(int n, int k, int K, int image_bytes) {
-#ifdef QPAL_W8
-    return false;
-#endif
     return n == 1 && K == kK28 && k == kN28 && x_fits_lds(n, k) && image_bytes >= kP28 * kTbRow;
 }
 
@@ -128,8 +111,14 @@ int nb_of(int n) { return n <= 1 ? 1 : n <= 2 ? 2 : n <= 4 ? 4 : 8; }
 // builds the per-wave table of every candidate and keeps the cheapest: rounds of <= 256 workgroups x the busiest SIMD's steps
 // (waves w, w + 4, w + 8, w + 12 of a workgroup share a SIMD).  The kernel reads ITS table entry — 8 bytes per (member, wave) —
 // with the first kernel-argument round trip: no chunk arithmetic is left in its prologue.
-// experiment knobs (perf/ scripts only): QPAL_FORCE_G=<1|2|4>, QPAL_FORCE_RG=<rows per group>, QPAL_SHARE=0 (QPAL_PAIR=0): no
-// row sharing on zeroed outputs beyond what the memset rule below allows
+// Test hooks: environment variables, each read once per process.  They exist for the tests, the host-path trace
+// (tests/capi_trace.hip with tests/golden/make_golden_capi_trace.py) and bench.py; nothing else in the library reads the environment.
+//   QPAL_FORCE_G=<1|2|4>, QPAL_FORCE_RG=<rows per group>: pin the planner's candidate — tests/test_gemv_row_finish.py, the trace
+//   QPAL_SHARE=0 (older name QPAL_PAIR=0): no row sharing on zeroed outputs beyond what the memset rule below allows —
+//     tests/test_gpu_parity.py (QPAL_PAIR), the trace (both names), bench.py (reports it)
+//   QPAL_PLAN_LOG=1: one line per planned launch on stderr — tests/test_gpu_parity.py
+//   QPAL_GEMM_MIN_BATCH=<n>: the batch from which the lockstep kernel runs (use_gemm) — tests/test_gemv_row_finish.py, the trace,
+//     bench.py, perf/sweep_minbatch.sh, perf/ab_batch.sh
 static int env_int(const char *name, int dflt) {
     const char *v = getenv(name);
     return v ? atoi(v) : dflt;
@@ -309,7 +298,7 @@ void plan_launch(TcMultiParams &mp, const int *out_zeroed, int &grid, int waves 
     static const int force_g = env_int("QPAL_FORCE_G", 0);
     static const int force_rg = env_int("QPAL_FORCE_RG", 0);
     static const int share_on = env_int("QPAL_SHARE", env_int("QPAL_PAIR", 1));
-    const int cap = round_capacity(waves);
+    const int cap = kNumCU;  // workgroups one launch round can hold: one per CU
     // geometry classes: (st1, st2) — at most two per launch (the entry points split a launch that has more)
     int ncls = 0, cst1[2] = {0, 0}, cst2[2] = {0, 0};
     for (int j = 0; j < mp.njobs; j++) {
@@ -436,17 +425,16 @@ bool gemv_classes_ok(const TcMultiParams &mp) {
 
 // Geometry of the lockstep skinny-GEMM kernel (tc_gemm.h, batch > 8): a workgroup = 8 waves = 8 supertile rows that walk one K
 // range together; K is split over workgroups (float atomics into a zeroed output) only while the launch has too few row groups
-// to occupy the chip and every split keeps >= kGemmMinSteps steps.  QPAL_GEMM_SK=<n> forces the split (experiments).
+// to occupy the chip and every split keeps >= kGemmMinSteps steps.
 constexpr int kGemmMinSteps = 4;
+// work items a lockstep launch is split towards (plan_gemm: twice as many with two workgroups per CU); measured, 96 / 192 / 256 / 512:
+// 4.9 / 4.1 / 4.5 / 5.3 ms per Llama-8B step at batch 64 (profiles/r03_gemm_items_sweep.txt)
+constexpr int kGemmWantItems = 192;
 // two_per_cu: one batch group beside a 64 KiB codebook image (75 KiB of LDS, < 128 VGPRs): two workgroups share a CU — 4 waves per
 // SIMD hide each other's barrier waits — and the launch is planned for twice the items (batch 4 / 8: +3 % tokens/s, measured).
 void plan_gemm(TcMultiParams &mp, int &grid, bool two_per_cu = false) {
-    static const int force_sk = env_int("QPAL_GEMM_SK", 0);
-    static const int items_env = env_int("QPAL_GEMM_ITEMS", 0);  // measured: 96 / 192 / 256 / 512 -> 4.9 / 4.1 / 4.5 / 5.3 ms per Llama-8B step at batch 64
-    static const int mult_env = env_int("QPAL_GEMM_GRID_MULT", 0);
-    const int grid_mult = mult_env > 0 ? mult_env : (two_per_cu ? 2 : 1);
-    const int want_items = items_env > 0 ? items_env : 192 * grid_mult;
-    static const int min_steps = env_int("QPAL_GEMM_MINSTEPS", kGemmMinSteps);
+    const int grid_mult = two_per_cu ? 2 : 1;
+    const int want_items = kGemmWantItems * grid_mult;
     int groups = 0;
     for (int j = 0; j < mp.njobs; j++) groups += (mp.job[j].nrows + kGemmWaves - 1) / kGemmWaves;
     int total = 0;
@@ -455,11 +443,7 @@ void plan_gemm(TcMultiParams &mp, int &grid, bool two_per_cu = false) {
             TcParams &p = mp.job[j];
             const int T = p.st1 + p.st2;
             int sk = 1;
-            while (groups * sk < want_items && T / (sk * 2) >= min_steps && sk < 32) sk *= 2;
-            if (force_sk > 0) {  // (a power of two: the kernel shifts)
-                sk = 1;
-                while (sk * 2 <= force_sk) sk *= 2;
-            }
+            while (groups * sk < want_items && T / (sk * 2) >= kGemmMinSteps && sk < 32) sk *= 2;  // (a power of two: the kernel shifts)
             while (sk > 1 && sk > T) sk >>= 1;
             p.sk = sk;
             p.nitems = ((p.nrows + kGemmWaves - 1) / kGemmWaves) * sk;
@@ -475,21 +459,17 @@ void plan_gemm(TcMultiParams &mp, int &grid, bool two_per_cu = false) {
 // float atomics (o / down of Llama-8B at batch 64: 16 row groups -> K split 4 / 8, 64 / 128 of 256 CUs busy, the atomics 13 % of a
 // token).  Slices of the BATCH are independent instead — no reduction at all, the decode (cheap beside 8 batch groups of MFMAs
 // and B-fragment reads) repeated per slice: the launch runs them as jobs of their own (same weights, x and out moved by the
-// slice's first row), then K is split as before.  Returns the rows of the widest slice.  QPAL_GEMM_BS=<n> forces n slices.
+// slice's first row), then K is split as before.  Returns the rows of the widest slice.
 int slice_gemm_batch(TcMultiParams &mp, int *ms, int *zeroed) {
-    static const int force = env_int("QPAL_GEMM_BS", 0);
-    static const int min_rows = env_int("QPAL_GEMM_BS_MIN_ROWS", 16);
-    static const int want_items = env_int("QPAL_GEMM_ITEMS", 192);
     const int n = mp.job[0].n;
     int groups = 0;
     for (int j = 0; j < mp.njobs; j++) groups += (mp.job[j].nrows + kGemmWaves - 1) / kGemmWaves;
     // measured (Llama-8B tcomb_6_7, tokens/s without -> with, profiles/r03_gemm_batch_slices.txt): two slices of the few-row launches
     // (q|k|v, o, down) 64: 17 500 -> 18 870, 32: 13 270 -> 13 440; FOUR slices (16 rows each at 64) 17 650, slicing gate|up as well
     // 18 490, slices of 8 rows -9...-14 %: at most two, never below 16 rows
+    constexpr int kMaxSlices = 2, kMinSliceRows = 16;
     int bs = 1;
-    while (bs < (force > 0 ? force : 2) && mp.njobs * bs * 2 <= kMaxJobs && n / (bs * 2) >= min_rows &&
-           (force > 0 || groups * bs * 2 <= want_items))
-        bs *= 2;
+    while (bs < kMaxSlices && mp.njobs * bs * 2 <= kMaxJobs && n / (bs * 2) >= kMinSliceRows && groups * bs * 2 <= kGemmWantItems) bs *= 2;
     if (bs == 1) return n;
     const int rows = ((n + bs - 1) / bs + 15) & ~15;  // whole groups of 16 batch rows per slice
     const TcMultiParams src = mp;
@@ -514,15 +494,13 @@ int slice_gemm_batch(TcMultiParams &mp, int *ms, int *zeroed) {
     return rows;
 }
 
-// batches 9..64: which kernel.  QPAL_GEMM=0: the per-wave-K-chunk kernel (tc_gemv_kernel, x from L2 per wave);
-// 1 (default): the lockstep kernel with the step's activations shared through LDS (tc_gemm.h)
-bool use_gemm(int nbg, const TcMultiParams &mp) {
-    static const int on = env_int("QPAL_GEMM", 1);
+// which kernel: the lockstep kernel with the step's activations shared through LDS (tc_gemm.h) from batch QPAL_GEMM_MIN_BATCH on,
+// below it the per-wave-K-chunk kernel (tc_gemv_kernel; it ends at batch 64, so 129 selects it wherever it exists)
+bool use_gemm(const TcMultiParams &mp) {
     // the lockstep kernel from this batch on (measured, Llama-8B tcomb_6_7, ms per step old / new: batch 2 1.38 / 1.50, 3 1.48 / 1.51,
     // 4 1.68 / 1.51, 6 1.89 / 1.53, 8 2.09 / 1.55: profiles/r03_sweep_minbatch.txt)
     static const int min_n = env_int("QPAL_GEMM_MIN_BATCH", 4);
-    if (!on || mp.job[0].n < min_n) return false;
-    (void)nbg;
+    if (mp.job[0].n < min_n) return false;
     for (int j = 0; j < mp.njobs; j++) {
         const TcParams &p = mp.job[j];
         if (!aligned(p.x, 16) || (p.k % 8) || p.x_rot || p.act_out) return false;
@@ -675,11 +653,8 @@ int shared_job_fields(const J &jb, TcParams &p, int n, int image_bytes) {
     return QPAL_OK;
 }
 
-// two lockstep workgroups per CU (plan_gemm): up to QPAL_GEMM_TWO_NBG batch groups, where the family's LDS use leaves the room
-bool gemm_two_per_cu(int nbg, bool family_has_room) {
-    static const int two_nbg = env_int("QPAL_GEMM_TWO_NBG", 1);
-    return nbg <= two_nbg && family_has_room;
-}
+// two lockstep workgroups per CU (plan_gemm): one batch group, where the family's LDS use leaves the room
+bool gemm_two_per_cu(int nbg, bool family_has_room) { return nbg == 1 && family_has_room; }
 
 // job_fn(job, TcParams &, fam) -> code: the family's checks and fill (it may note in fam what it saw: TcqFamily::mixed).  fam: image_bytes(), refuse(mp, n) -> code (shapes the family's
 // kernels do not have), lockstep() (may the lockstep kernel run this launch), two_per_cu(), gemm(...) and gemv(...) (the launchers).
@@ -712,7 +687,7 @@ int launch_jobs(const J *jobs, int njobs, int n, void *prezero, long prezero_byt
     mp.zero_chunks = (int)(prezero_bytes / 16);
     int grid;
     const int nbg = nbg_of(n);
-    if (fam.lockstep() && use_gemm(nbg, mp)) {
+    if (fam.lockstep() && use_gemm(mp)) {
         const int rows = slice_gemm_batch(mp, ms, zeroed);
         plan_gemm(mp, grid, gemm_two_per_cu(nbg_of(rows), fam.two_per_cu()));
         rc = zero_split_jobs(mp, ms, zeroed, s);
@@ -842,7 +817,7 @@ int qpal_tcq_dequant(void *out_f16, const void *c1, const void *c2, const void *
         p.st1 = (p.nsc1 + 3) / 4;
         p.st2 = (p.nsc2 + 3) / 4;
         p.col2 = k1;
-        p.x_lds = aligned(w, 16) && (k % 8) == 0 && (k1 % 8) == 0 && !getenv("QPAL_DEQUANT_DIRECT");  // staged 16-byte stores
+        p.x_lds = aligned(w, 16) && (k % 8) == 0 && (k1 % 8) == 0;  // staged 16-byte stores
         p.sk = dequant_chunks(p.nrows, p.st1, p.st2);
         const int items = p.x_lds ? p.nrows * p.sk : p.nrows;
         const int grid = items < kNumCU ? items : kNumCU;
@@ -921,7 +896,7 @@ int qpal_lut_tc_dequant(void *out_f16, const void *qweight, const void *lut, int
     p.nrows = m / 32;
     p.nsc1 = k / 32;
     p.st1 = (p.nsc1 + 3) / 4;
-    p.x_lds = aligned(out_f16, 16) && (k % 8) == 0 && !getenv("QPAL_DEQUANT_DIRECT");  // staged 16-byte stores
+    p.x_lds = aligned(out_f16, 16) && (k % 8) == 0;  // staged 16-byte stores
     p.sk = dequant_chunks(p.nrows, p.st1, 0);
     const int items = p.x_lds ? p.nrows * p.sk : p.nrows;
     const int grid = items < kNumCU ? items : kNumCU;

@@ -76,10 +76,8 @@ __device__ __forceinline__ uint32_t ext32(const uint32_t (&w)[NW]) {
     const uint32_t lo = (i < NW) ? w[i < NW ? i : 0] : 0u;
     if constexpr (sh == 0) {
         return lo;
-#ifndef QPAL_NO_NARROW_EXT
     } else if constexpr (sh + WIDTH <= 32) {
         return lo >> sh;
-#endif
     } else {
         const uint32_t hi = (i + 1 < NW) ? w[(i + 1 < NW) ? i + 1 : 0] : 0u;
         return __builtin_amdgcn_alignbit(hi, lo, sh);

@@ -242,17 +242,11 @@ struct TcqCodec {
             if constexpr (t0 + 16 <= L4) {
                 return extw<base + L4 - 16 - t0, 16>(w);
             } else {
-#ifdef QPAL_NO_NARROW_EXT
-                constexpr int n = t0 + 16 - L4;
-                if constexpr (!ISB) return __builtin_amdgcn_alignbit(ext32<baseA<G>()>(w), ext32<baseB<G>() + L4 - 32>(w), 32 - n);
-                else return __builtin_amdgcn_alignbit(ext32<baseB<G>()>(w), next_head, 32 - n);
-#else
                 const uint32_t z = joined_next<G, ISB>(w, next_head);  // (CSE: one per chunk)
                 constexpr int sh = (3 - (I & 3)) * KV;
                 static_assert(sh + 16 <= 32, "state window inside the joined word");
                 if constexpr (sh == 0) return z;
                 else return z >> sh;
-#endif
             }
         }
     }
@@ -262,13 +256,7 @@ struct TcqCodec {
     static __device__ __forceinline__ uint32_t addr(uint32_t laneoff, const uint32_t (&w)[NW], uint32_t next_head) {
         const uint32_t s = window<G, I>(w, next_head);
         uint32_t h;
-#if defined(QPAL_KO_HASH)  // power experiment: no multiplier at all (results meaningless)
-        asm("v_add_u32 %0, %1, %1" : "=v"(h) : "v"(s));
-#elif defined(QPAL_HASH_PK16)  // power experiment (perf/power_probe.hip): two 16 x 16 multipliers instead of one 24 x 24 — the low half is the hash
-        asm("v_pk_mad_u16 %0, %1, %1, %1" : "=v"(h) : "v"(s));
-#else
         asm("v_mad_u32_u24 %0, %1, %1, %1" : "=v"(h) : "v"(s));  // s*s + s: low 16 bits exact
-#endif
         if constexpr (XS == 1) asm("v_add_u32 %0, %1, %1" : "=v"(h) : "v"(h));  // (h << 1 as a shift is a half-rate op)
         return (h & HMASK) | laneoff;
     }
@@ -277,11 +265,7 @@ struct TcqCodec {
     static __device__ __forceinline__ uint32_t pair(const uint32_t *lds, uint32_t laneoff, const uint32_t (&w)[NW],
                                                     uint32_t next_head) {
         const uint32_t a = addr<G, I>(laneoff, w, next_head);
-#ifdef QPAL_KO_GATHER  // timing experiment (tc_gemm.h): the address instead of the gathered entry
-        return a;
-#else
         return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(lds) + a);
-#endif
     }
 };
 
@@ -388,14 +372,9 @@ struct StreamView {
 #define QPAL_STAMP(i) do { } while (0)
 #endif
 
-// Experiment (make VARIANT=w8 EXTRA=-DQPAL_W8): TWO 8-wave workgroups per CU instead of one 16-wave one for the
-// batch <= 16 kernels — 64 KiB image + 15 KiB scratch each (x fits only for n * k <= ~7000: the k = 4096 launches at batch 1),
-// 128 VGPRs as before (4 waves per SIMD).  No fused rotation in this build.
-#if defined(QPAL_W8) && !defined(QPAL_W8_ONE)  // (QPAL_W8_ONE: ONE 8-wave workgroup per CU — half the waves to dispatch — keeps the full scratch)
-constexpr int kScratchBytes = 15 * 1024;
-#else
-constexpr int kScratchBytes = 31 * 1024;  // LDS left beside the 128 KiB codebook image: reduction buffer + x
-#endif
+// LDS left beside the 128 KiB codebook image: reduction buffer + x.  (Tried and not kept, docs/rounds/DESIGN_rounds_1_to_4.md §4.9: TWO 8-wave workgroups per CU
+// for the batch <= 16 kernels, 64 KiB image + 15 KiB scratch each — x then fitted only for n * k <= ~7000 — and no fused rotation.)
+constexpr int kScratchBytes = 31 * 1024;
 
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 typedef float float4_t __attribute__((ext_vector_type(4)));
@@ -487,7 +466,7 @@ __device__ __forceinline__ int xs_index(int i) {
 
 // The MFMA's 16 columns are 8 batch rows x 2 column halves; at batch n < 8 the columns of the batch rows that do not exist used to
 // carry COPIES of row n - 1 (results never stored).  The matrix pipe multiplies whatever it is given: with zeros in those columns
-// (the staged x's zero pad, one broadcast LDS read) its switching power goes down — measured with perf/power_probe.hip: the 8 matrix
+// (the staged x's zero pad, one broadcast LDS read) its switching power goes down — measured in round 5 with a probe build of this step: the 8 matrix
 // instructions of a step are ~200 W of the ~1 100 W the decode draws, and the token runs into the card's power limit (shader clock 2.15
 // instead of 2.4 GHz while tokens replay back to back, profiles/r05_power_and_clock.txt).
 // MFMA B operand of a step.  Lane (kb = lane>>4, c = lane&15) supplies, for batch row b = 8*grp + (c>>1) and
@@ -587,34 +566,15 @@ __device__ __forceinline__ void gemv_step_pipe(const uint32_t *lut, uint32_t lan
         constexpr int g = decltype(gc)::value;
         constexpr int ksub = g >> 1, msub = g & 1;
         uint32_t d[8];
-#ifdef QPAL_KO_GATHER  // power / timing experiments (perf/power_probe.hip): the address instead of the gathered entry
-        static_for<0, 8>([&](auto ic) { d[decltype(ic)::value] = ac[decltype(ic)::value]; });
-#else
         static_for<0, 8>([&](auto ic) { d[decltype(ic)::value] = *reinterpret_cast<const uint32_t *>(l8 + ac[decltype(ic)::value]); });
-#endif
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (g < 3) addrs(std::integral_constant<int, g + 1>{}, an);
         __builtin_amdgcn_sched_barrier(0);
-#ifdef QPAL_PROBE_MFMA444  // power / timing probe only (perf/power_probe.hip; the results are NOT the GEMV's): the step's MACs as 16 x 4x4x4
-        {                      // (16 blocks) matrix instructions — a quarter of the products of the 16 x 16 x 32 shape, twice the instructions
-            typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-            typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-            const u32x4 xq = xb[0][ksub];
-            const half4_t b0 = __builtin_bit_cast(half4_t, u32x2_t{xq.x, xq.y}), b1 = __builtin_bit_cast(half4_t, u32x2_t{xq.z, xq.w});
-            acc.v[0][msub * 2 + 0] = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, u32x2_t{d[0], d[4]}), b0, acc.v[0][msub * 2 + 0], 0, 0, 0);
-            acc.v[0][msub * 2 + 0] = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, u32x2_t{d[2], d[6]}), b1, acc.v[0][msub * 2 + 0], 0, 0, 0);
-            acc.v[0][msub * 2 + 1] = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, u32x2_t{d[1], d[5]}), b0, acc.v[0][msub * 2 + 1], 0, 0, 0);
-            acc.v[0][msub * 2 + 1] = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(half4_t, u32x2_t{d[3], d[7]}), b1, acc.v[0][msub * 2 + 1], 0, 0, 0);
-        }
-#elif defined(QPAL_KO_MFMA)  // (the decoded pairs consumed by nothing: no matrix instruction, no other instruction in their place)
-        asm volatile("" ::"v"(d[0]), "v"(d[1]), "v"(d[2]), "v"(d[3]), "v"(d[4]), "v"(d[5]), "v"(d[6]), "v"(d[7]), "v"(xb[0][ksub]));
-#else
         // fragment order (jh, isB): i = jl + 2*jh + 4*isB
         acc.v[0][msub * 2 + 0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, u32x4{d[0], d[4], d[2], d[6]}),
                                                                         __builtin_bit_cast(half8_t, xb[0][ksub]), acc.v[0][msub * 2 + 0], 0, 0, 0);
         acc.v[0][msub * 2 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, u32x4{d[1], d[5], d[3], d[7]}),
                                                                         __builtin_bit_cast(half8_t, xb[0][ksub]), acc.v[0][msub * 2 + 1], 0, 0, 0);
-#endif
         if constexpr (g < 3) static_for<0, 8>([&](auto ic) { ac[decltype(ic)::value] = an[decltype(ic)::value]; });
     });
 }
@@ -685,15 +645,8 @@ __device__ __forceinline__ void gemv_run(uint32_t (&w)[Codec::NW], const uint32_
 
 // Waves per workgroup of the fused kernel: 16 (4 per SIMD, 128 VGPRs) up to batch 16; 8 (2 per SIMD, 256 VGPRs: room for
 // the accumulators and activations of 4 / 8 batch groups) for batches 17..64, where every decoded step feeds 32 / 64 MFMAs
-#ifdef QPAL_W8
-template <int NBG>
-constexpr int gemv_waves() { return 8; }
-#define QPAL_GEMV_BOUNDS(NBG) __launch_bounds__(512, (NBG) <= 2 ? 4 : 2)
-#else
 template <int NBG>
 constexpr int gemv_waves() { return NBG >= 4 ? 8 : 16; }
-#define QPAL_GEMV_BOUNDS(NBG) __launch_bounds__(64 * gemv_waves<NBG>())
-#endif
 // LDS beside the 64 KiB codebook image: reduction buffer [waves][n][32] fp32 (+ x for batch <= 8)
 template <int NBG>
 constexpr int scratch_bytes() { return NBG == 1 ? kScratchBytes : gemv_waves<NBG>() * 32 * 4 * 8 * NBG; }
@@ -762,11 +715,7 @@ __device__ __forceinline__ float run_sum(const float *f, int stride, int run_wav
 // The leading scalar arguments are PRELOADED into SGPRs by the dispatcher (-mllvm -amdgpu-kernarg-preload-count, Makefile):
 // when every job of the launch reads the same activations and codebook (`early`), their loads are issued before the
 // kernel-argument block `mp` has even arrived (its fetch is a memory round trip on the critical path of a short kernel).
-#ifdef QPAL_W8
-constexpr int kEarlyXChunks = 1;
-#else
 constexpr int kEarlyXChunks = 2;
-#endif
 struct TcEarly {
     const uint16_t *x;  // shared by all jobs, staged in LDS
     const void *tab;    // shared codebook
@@ -864,7 +813,7 @@ __device__ __forceinline__ void rot_stage1_regs(const u32x4 (&rq)[2][4], bool f3
 // ROT: 0 plain; 1: can rotate x while staging it (k = 2048 / 4096, wht64.h); 2: the 14336-wide rotation of rot_k28.h (its own
 // instantiation: its registers would make the other rotating launches spill); 3: plain + pair mode (TcParams: sk == -1)
 template <class C1, class C2, int NBG, int ROT = 0>
-__global__ QPAL_GEMV_BOUNDS(NBG) void tc_gemv_kernel(const uint16_t *ex, const void *etab, int en, int ek, int eon, int eie,
+__global__ __launch_bounds__(64 * gemv_waves<NBG>()) void tc_gemv_kernel(const uint16_t *ex, const void *etab, int en, int ek, int eon, int eie,
                                                        const uint16_t *esu, const uint16_t *erw, const TcMultiParams mp) {
     constexpr bool TWO = !std::is_void_v<C2>;
     using CB = std::conditional_t<TWO, C2, C1>;

@@ -3,6 +3,9 @@
 #include "tc_kernels.h"
 
 namespace qpal {
+// second codec of a two-stream (comb / combt) launch; KV2 == 0: single stream, no second codec
+template <int S, int KV1, int KV2>
+using TcqSecond = std::conditional_t<KV2 == 0, void, TcqCodec<S, KV2 == 0 ? KV1 : KV2>>;
 int launch_tcq_gemv(const TcMultiParams &p, int S, int KV1, int KV2, int nbg, int grid, hipStream_t stream);
 int launch_tcq_gemv_wide(const TcMultiParams &p, int S, int KV1, int KV2, int nbg, int grid, hipStream_t stream);
 int launch_tcq_gemm_nbg1(const TcMultiParams &p, int S, int KV1, int KV2, int grid, hipStream_t stream);

@@ -1,7 +1,5 @@
 """VQ / non-uniform-SQ linears on the tensor-core-order packing and on the SIMT packing
 (reference: lib/linear/vq_linear.py:5-97, 99-208)."""
-import os
-
 import torch
 
 from .. import ops
@@ -45,7 +43,7 @@ class _VQBase(PackedLinearBase):
 class VQLinearPackTensorCore(_VQBase):
     """Codes stored in mma-tile order (quant_op.py:101-162).  forward() returns the input's dtype.  `_gemv` (internal) returns fp32 from
     the tensor-core-order kernel and fp16 from the SIMT-order twin that few-row layers keep (fp32 accumulation in both; which of the
-    two runs depends only on the layer's shape and QPAL_SIMT_TWIN, see _simt_twin)."""
+    two runs depends only on the layer's shape, see _simt_twin)."""
     max_fused_batch = 128
 
     def __init__(self, in_features, out_features, lut_bits, vec_sz=2, bias=False, dtype=torch.half, device=None):
@@ -73,8 +71,7 @@ class VQLinearPackTensorCore(_VQBase):
     SIMT_TWIN_MAX_ROWS = 2048
 
     def _twin_eligible(self):
-        return (self.out_features <= self.SIMT_TWIN_MAX_ROWS and self.qweight.is_cuda and os.environ.get("QPAL_SIMT_TWIN", "1") != "0"
-                and not (self.vec_sz == 2 and self.lut_bits < 3))
+        return self.out_features <= self.SIMT_TWIN_MAX_ROWS and self.qweight.is_cuda and not (self.vec_sz == 2 and self.lut_bits < 3)
 
     def _twin_key(self):
         q = self.qweight
@@ -83,7 +80,7 @@ class VQLinearPackTensorCore(_VQBase):
     def prepare(self):
         """(Re)build the SIMT-order twin of `qweight` now.  Called wherever this package writes the codes (gen_layer_from_info,
         .to() / .cuda(), load_state_dict); call it yourself after writing `qweight` through a path autograd's version counter
-        does not see (`qweight.data.copy_(...)`).  No-op for layers that keep no twin (many rows, CPU, QPAL_SIMT_TWIN=0)."""
+        does not see (`qweight.data.copy_(...)`).  No-op for layers that keep no twin (many rows, CPU)."""
         object.__setattr__(self, "_simt_qweight", None)  # (not a buffer: never part of the state dict)
         object.__setattr__(self, "_simt_key", None)
         if not self._twin_eligible():

@@ -484,3 +484,58 @@ def test_host_path_trace_matches_the_golden_record(tmp_path):
     assert len(got["default"]) >= 4000 and all(len(got[name]) >= 700 for name in got)
     report = tr.compare(exe, got, want)
     assert not report, report
+
+
+# every QPAL_* name the preprocessor may test (or the Makefile may define) in the native sources ...
+_QPAL_BUILD_SWITCHES = {
+    "QPAL_STAMPS",       # diagnostic build, make STAMPS=1
+    "QPAL_HESSIAN_KB",   # hessian.hip: the K block, overridable for its own measurements
+    "QPAL_TCQ", "QPAL_LUT", "QPAL_GEMM_NBG",  # X-macro names a unit #defines in front of a table / an instantiation file
+}
+# ... and every QPAL_* environment variable the library or the package may read
+_QPAL_ENV_SWITCHES = {
+    "QPAL_FORCE_G", "QPAL_FORCE_RG", "QPAL_SHARE", "QPAL_PAIR", "QPAL_PLAN_LOG", "QPAL_GEMM_MIN_BATCH",  # test hooks (qpal_capi.hip)
+    "QPAL_STAMPS_BUF", "QPAL_STAMPS_DUMP",  # the stamp build only (gemv_stamps.h)
+    "QPAL_LIB", "QPAL_LAZY_OPS",            # Python: which library, eager op registration
+}
+
+
+def _qpal_switches(text, makefile=False):
+    """(names tested by #if / #ifdef / #ifndef / #elif or defined by a -D flag of a Makefile, names read from the environment)"""
+    built, env = set(), set()
+    for line in text.splitlines():
+        if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+            built |= set(re.findall(r"\bQPAL_\w+", line.split("//")[0]))
+        if makefile:
+            built |= set(re.findall(r"-D(QPAL_\w+)", line.split("#")[0]))
+        if re.search(r"\b(getenv|env_int|environ)\b", line):
+            env |= set(re.findall(r"""["'](QPAL_\w+)["']""", line))
+    return built, env
+
+
+def test_experiment_switches_stay_out_of_the_product():
+    """The fused GEMV's headers once carried a second configuration and a handful of knock-out switches, and the library read eleven
+    environment variables nothing used.  They are gone; this keeps the list from growing back: every QPAL_* name a native source tests
+    in the preprocessor, and every QPAL_* name the library or the Python package reads from the environment, is spelled out above."""
+    csrc = os.path.join(ROOT, "q-palette_amd", "csrc")
+    files = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".h", ".hip", ".inc")) or f == "Makefile"]
+    for d, _, names in os.walk(os.path.join(ROOT, "q-palette_amd")):
+        files += [os.path.join(d, f) for f in sorted(names) if f.endswith(".py")]
+    assert len(files) >= 60 and any(f.endswith("Makefile") for f in files) and any(f.endswith("vq_linear.py") for f in files)
+    built, env, bad = set(), set(), []
+    for path in files:
+        with open(path) as fh:
+            b, e = _qpal_switches(fh.read(), makefile=path.endswith("Makefile"))
+        built |= b
+        env |= e
+        bad += [f"{os.path.relpath(path, ROOT)}: {n}" for n in sorted((b - _QPAL_BUILD_SWITCHES) | (e - _QPAL_ENV_SWITCHES))]
+    assert not bad, "QPAL_* switches outside the allow-lists:\n" + "\n".join(bad)
+    # the scan sees what is there (a scanner that finds nothing would pass anything) ...
+    assert {"QPAL_STAMPS", "QPAL_HESSIAN_KB"} <= built and _QPAL_ENV_SWITCHES <= env, (built, env)
+    # ... in every form the sources use
+    assert _qpal_switches('#if defined(QPAL_A) && !defined(QPAL_B)  // QPAL_C\n  # elif QPAL_D != 0\n#define QPAL_E 1\n#ifndef QPAL_F') == \
+        ({"QPAL_A", "QPAL_B", "QPAL_D", "QPAL_F"}, set())
+    assert _qpal_switches('x = getenv("QPAL_A") != nullptr; env_int("QPAL_B", env_int("QPAL_C", 1));\n'
+                          "os.environ.get('QPAL_D'); os.environ[\"QPAL_E\"]; 'QPAL_F' in os.environ\nQPAL_G = \"QPAL_H\"") == \
+        (set(), {"QPAL_A", "QPAL_B", "QPAL_C", "QPAL_D", "QPAL_E", "QPAL_F"})
+    assert _qpal_switches('CXXFLAGS += -DQPAL_A $(EXTRA)  # -DQPAL_B', makefile=True) == ({"QPAL_A"}, set())
