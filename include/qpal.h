@@ -404,6 +404,30 @@ int qpal_attn_rope_prefill_paged(const float *q, const float *k, const float *v,
                                  int num_pages, int page_size, int max_pages, int kv_fmt,
                                  int T, int nq, int nkv, int hd, float scale, void *ws, long ws_bytes, void *stream);
 
+/* SHARED-PREFIX paged decode attention (csrc/attn_prefix.hip + csrc/attn_batch.hip): qpal_attn_rope_decode_batch_paged
+ * for slots that share the pages of a common prefix, which is then read once per group instead of once per slot.  Three DEVICE
+ * arrays describe the sharing, never read by the host (a captured launch can be replayed while groups, lengths and positions change):
+ *   row_group int32 [B] (the group of slot b, or -1), grp_slot int32 [G] (a member whose table row addresses the group's shared
+ *   pages), grp_len int32 [G] (the shared positions), 1 <= G <= 16.
+ * Slot b is served as a member of g = row_group[b] iff 0 <= g < G, 0 <= grp_slot[g] < B, grp_len[g] > 0 and a multiple of page_size,
+ * grp_len[g] <= pos[b] and 0 <= pos[b] < max_len; every other slot is served bit for bit as the paged launch serves it.  A member
+ * reads positions [0, grp_len[g]) through table row grp_slot[g] and [grp_len[g], pos[b]] through its own row; the rotary embedding,
+ * the appended k / v rows (both formats), the inactive rule and the page guard are the paged launch's.  Two launches: the prefix
+ * phase leaves a partial (max, sum, unnormalised out) per (slot, query head) — softmax weights rounded to fp16 in front of the
+ * value product, as in the prefill kernels —, the suffix phase (the paged kernel over [grp_len, pos]) folds it in before the
+ * division; stream order is the only synchronisation.  A row's result does not depend on which other slots are in its group; two
+ * launches are bitwise equal.  ws: qpal_attn_prefix_ws_bytes(B, G, ...) bytes (max_len = max_pages * page_size; it contains the
+ * paged launch's workspace), 4-byte aligned, zero-filled ONCE, kept across launches, always needed.  Checks and codes are the paged
+ * sibling's; in addition a null row_group / grp_slot / grp_len: QPAL_E_NULL, G outside [1, 16]: QPAL_E_SHAPE, one of the three not
+ * 4-byte aligned: QPAL_E_ALIGN. */
+long qpal_attn_prefix_ws_bytes(int B, int G, int nq, int nkv, int hd, long max_len);
+int qpal_attn_rope_decode_batch_shared(const float *q, const float *k, const float *v, long ld_qkv,
+                                       void *kpool, void *vpool, void *out_f16, long ld_out,
+                                       const long *pos, const float *inv_freq, const int *block_table, long ld_table,
+                                       int num_pages, int page_size, int max_pages, int kv_fmt /* 0 fp16, 1 e4m3fn */,
+                                       const int *row_group, const int *grp_slot, const int *grp_len, int G,
+                                       int B, int nq, int nkv, int hd, float scale, void *ws, long ws_bytes, void *stream);
+
 /* RAGGED prefill (csrc/attn_ragged.hip): rows of SEVERAL sequences in one launch.  q / k / v / out have R rows (1 <= R
  * <= 128) cut into S segments (1 <= S <= 128) that three DEVICE arrays describe — never read by the host, so a captured launch can
  * be replayed while segment lengths, sequences and positions change:

@@ -12,7 +12,13 @@ random order) through qpalette_amd.paged_decode_attention, once per page size, t
 the spread the paged ones are read against).  "pool_bytes": what the pools of a cache that backs only the positions in
 use would take (sum_b ceil((pos[b] + 1) / page_size) pages), against "cache_bytes".
 
+--paged PAGE --shared-prefix P ...: the B slots share the pages of a P-position prefix and have 1 .. 256 seeded positions of
+their own each (max_len = P + 512; --context and --full are not used).  On ONE pair of pools, --repeats times in turn: the plain
+paged launch, then the shared pair (qpalette_amd.shared_prefix_decode_attention), 10 + iters launches each.  Under
+`rocprofv3 --kernel-trace` perf/shared_prefix_trace.py turns the trace of this call into per-block medians.
+
     python perf/attn_batch_bench.py [--batch 8 64] [--context 1024 4096] [--iters 200] [--full] [--kv fp16 fp8] [--paged 16 64]
+                                    [--shared-prefix 4096 1024] [--repeats 5]
 """
 import argparse
 import json
@@ -26,6 +32,60 @@ import qpalette_amd as qp
 from paged import random_table, scatter
 
 
+def shared_rows(args, dev, inv_freq):
+    """the plain paged launch and the shared pair in turn on the same pools, per (prefix, batch, format)"""
+    nq, nkv, hd, ps = args.nq, args.nkv, args.hd, args.paged[0]
+    rows = []
+    for P in args.shared_prefix:
+        for B in args.batch:
+            L = P + 512
+            mp, shared_pages = L // ps, P // ps
+            own = mp - shared_pages
+            num_pages = shared_pages + B * own
+            g = torch.Generator().manual_seed(B * 7 + P)
+            pos_h = P + torch.randint(1, 257, (B,), generator=g)
+            perm = torch.randperm(num_pages, generator=g).to(torch.int32)
+            table = torch.empty(B, mp, dtype=torch.int32)
+            table[:, :shared_pages] = perm[:shared_pages]
+            table[:, shared_pages:] = perm[shared_pages:].view(B, own)
+            table, pos = table.to(dev), pos_h.to(dev)
+            qkv = torch.randn(B, (nq + 2 * nkv) * hd, device=dev)
+            q, k, v = qkv.split([nq * hd, nkv * hd, nkv * hd], dim=1)
+            out = torch.empty(B, nq * hd, dtype=torch.float16, device=dev)
+            i32 = lambda x: torch.tensor(x, dtype=torch.int32, device=dev)  # noqa: E731
+            px = qp.SharedPrefix(i32([0] * B), i32([0]), i32([P]))
+            ws_plain = qp.attention_workspace(B, nq, nkv, hd, L, dev)
+            ws_shared = qp.shared_prefix_workspace(B, 1, nq, nkv, hd, L, dev)
+            for kv in args.kv:
+                dtype = torch.float16 if kv == "fp16" else torch.float8_e4m3fn
+                kp, vp = (torch.randn(num_pages, nkv, ps, hd, device=dev).half().to(dtype) for _ in range(2))
+                plain = lambda: qp.paged_decode_attention(q, k, v, kp, vp, table, pos, inv_freq, out=out, ws=ws_plain)  # noqa: E731
+                shared = lambda: qp.shared_prefix_decode_attention(q, k, v, kp, vp, table, pos, inv_freq, px, out=out, ws=ws_shared)  # noqa: E731
+                us = {"plain": [], "shared": []}
+                for _ in range(args.repeats):
+                    for name, launch in (("plain", plain), ("shared", shared)):
+                        for _ in range(10):
+                            launch()
+                        torch.cuda.synchronize()
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for _ in range(args.iters):
+                            launch()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        us[name].append(e0.elapsed_time(e1) * 1e3 / args.iters)
+                esz = kp.element_size()
+                rows.append({"batch": B, "prefix": P, "max_len": L, "page_size": ps, "kv": kv, "iters": args.iters, "repeats": args.repeats,
+                             "kv_rows_plain": int((pos_h + 1).sum()), "kv_rows_shared": int(P + (pos_h + 1 - P).sum()),
+                             "kv_MB_plain": int((pos_h + 1).sum()) * nkv * hd * 2 * esz / 1e6,
+                             "us_per_launch_events_plain": us["plain"], "us_per_launch_events_shared_pair": us["shared"],
+                             "workspace_bytes_plain": 0 if ws_plain is None else ws_plain.numel() * 4,
+                             "workspace_bytes_shared": ws_shared.numel() * 4})
+                del kp, vp
+            torch.cuda.empty_cache()
+    return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, nargs="+", default=[8, 64])
@@ -37,10 +97,19 @@ def main(argv=None):
     ap.add_argument("--full", action="store_true", help="every sequence at the last position of its cache")
     ap.add_argument("--kv", nargs="+", default=["fp16"], choices=["fp16", "fp8"], help="KV-cache element format(s), in this order per row")
     ap.add_argument("--paged", type=int, nargs="*", default=[], metavar="PAGE_SIZE", help="also time paged launches of these page sizes")
+    ap.add_argument("--shared-prefix", type=int, nargs="*", default=[], metavar="P",
+                    help="with --paged PAGE: slots that share a P-position prefix, the plain launch against the shared pair")
+    ap.add_argument("--repeats", type=int, default=5, help="--shared-prefix: timed blocks of each launch, in turn")
     args = ap.parse_args(argv)
+    if args.shared_prefix and (len(args.paged) != 1 or any(P % args.paged[0] or P < args.paged[0] for P in args.shared_prefix)):
+        raise SystemExit("--shared-prefix: with ONE --paged PAGE, prefixes that are multiples of it")
     dev = torch.device("cuda", 0)
     nq, nkv, hd = args.nq, args.nkv, args.hd
     inv_freq = 1.0 / (500000.0 ** (torch.arange(0, hd, 2, device=dev).float() / hd))
+    if args.shared_prefix:
+        print(json.dumps({"what": "paged decode attention of slots that share a prefix: the plain launch and the shared pair in turn",
+                          "nq": nq, "nkv": nkv, "hd": hd, "rows": shared_rows(args, dev, inv_freq)}))
+        return
     rows = []
     for L in args.context:
         for B in args.batch:

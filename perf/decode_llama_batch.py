@@ -33,8 +33,12 @@ hold e4m3 values only: `BatchKV.update` stores a new row through the round trip 
 step attends to the round-tripped cache, as the kernels do.  The check also reports how far the fp16-cache step lies from that
 reference (what the format itself moves; not a gate).
 
+--paged PAGE_SIZE --shared-prefix P: also the step on pools in which all B slots share the pages of a P-position prefix and have 1 ..
+256 seeded positions of their own each, timed both ways in the same call — DecodeStep(block_table=...) and DecodeStep(block_table=...,
+shared_prefix=...) —, the plain step again behind them, and how far the two steps' final hidden states lie apart.
+
     python perf/decode_llama_batch.py [--model 3_8b] [--batch 1 8 16 32 64] [--context 1024] [--tokens 64] [--inactive 0] [--sample]
-                                      [--process] [--grammar] [--kv fp16|fp8] [--paged PAGE_SIZE]
+                                      [--process] [--grammar] [--kv fp16|fp8] [--paged PAGE_SIZE] [--shared-prefix P]
 """
 import argparse
 import json
@@ -96,8 +100,13 @@ def main(argv=None, quiet=False):
     ap.add_argument("--kv", default="fp16", choices=["fp16", "fp8"], help="KV-cache element format (fp8: OCP e4m3fn, no scales)")
     ap.add_argument("--paged", type=int, default=0, metavar="PAGE_SIZE",
                     help="also time the step on a paged cache of this page size (pages in a seeded random order; DESIGN.md §17)")
+    ap.add_argument("--shared-prefix", type=int, default=0, metavar="P",
+                    help="with --paged: also time the step both ways on pools whose slots share a P-position prefix (DESIGN.md §26)")
     args = ap.parse_args(argv)
     kv8 = args.kv == "fp8"
+    if args.shared_prefix and (not args.paged or args.shared_prefix % args.paged or args.shared_prefix < args.paged
+                               or args.context < args.shared_prefix + 256 + args.tokens + 16):
+        raise SystemExit("--shared-prefix: with --paged, a multiple of the page size, and --context >= P + 256 + --tokens + 16")
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
     if args.grammar and not args.sample:
@@ -218,6 +227,47 @@ def main(argv=None, quiet=False):
             paged = {"page_size": ps, "ms_step": timed(pstep), "ms_step_contiguous_again": timed(kernel_step),
                      "pool_bytes": 2 * nlayers * qp.attention.kv_cache_bytes(pages, nkv, ps, head_dim, kc[0].dtype)}
             del pstep, kp, vp, table
+        shared = None
+        if args.shared_prefix:
+            P, ps, mp = args.shared_prefix, args.paged, args.context // args.paged
+            own = mp - P // ps
+            num_pages = P // ps + B * own
+            gs = torch.Generator().manual_seed(args.seed + B + 1)
+            spos0 = P + torch.randint(1, 257, (B,), generator=gs)
+            spos0[nact:] = -1
+            perm = torch.randperm(num_pages, generator=gs).to(torch.int32)
+            table = torch.empty(B, mp, dtype=torch.int32)
+            table[:, :P // ps] = perm[:P // ps]
+            table[:, P // ps:] = perm[P // ps:].view(B, own)
+            table, spos0 = table.to(dev), spos0.to(dev)
+            sinc, spos = (spos0 >= 0).long(), spos0.clone()
+            mk = lambda: [(torch.randn(num_pages, nkv, ps, head_dim, device=dev, generator=cg) * 0.5).half().to(kc[0].dtype)  # noqa: E731
+                          for _ in range(nlayers)]
+            kp, vp = mk(), mk()
+            i32 = lambda x: torch.tensor(x, dtype=torch.int32, device=dev)  # noqa: E731
+            px = qp.SharedPrefix(i32([0] * B), i32([0]), i32([P]))
+            steps = [qp.DecodeStep(layers, embed, norm, lm_head, kp, vp, inv_freq, tok, spos, out_tok, generic=True, block_table=table,
+                                   shared_prefix=sp) for sp in (None, px)]
+
+            def sfeed(i):
+                tok.copy_(out_tok)
+                torch.add(spos0, sinc, alpha=i, out=spos)
+
+            def stimed(fn):
+                ms = time_graph(fn, args.tokens, dev, sfeed)
+                spos.copy_(spos0)
+                return ms
+
+            hs = []
+            for st in steps:  # (both append the same rows at the same places: the second starts from what the first started from)
+                st()
+                hs.append(st.hidden().float()[:nact])
+            ms = [stimed(steps[0]), stimed(steps[1]), stimed(steps[0]), stimed(steps[1])]
+            shared = {"prefix": P, "page_size": ps, "ms_step_plain": [ms[0], ms[2]], "ms_step_shared": [ms[1], ms[3]],
+                      "launches_per_token": [st.launches_per_token for st in steps],
+                      "max_abs_diff_final_norm": float((hs[0] - hs[1]).abs().max()), "max_abs_ref": float(hs[0].abs().max()),
+                      "kv_rows_plain": int((spos0[:nact] + 1).sum()), "kv_rows_shared": int(P + (spos0[:nact] + 1 - P).sum())}
+            del steps, kp, vp, table, px
         ms_lin = timed(linears_only, None)
         ms_torch = None if args.no_torch_glue else timed(torch_step)
         sampled = None
@@ -269,6 +319,8 @@ def main(argv=None, quiet=False):
             res["sampled"] = sampled
         if paged is not None:
             res["paged"] = paged
+        if shared is not None:
+            res["shared_prefix"] = shared
         del kc, vc, kc_ref, vc_ref, ref_cache, kernel_step
         torch.cuda.empty_cache()
         return res

@@ -12,9 +12,11 @@ Layout:
   attention.py     decode_attention / attention_workspace: rope + KV append + GQA attention of B sequences, one launch;
                    prefill_attention / prefill_workspace: the same for up to 128 new tokens of one sequence, causal;
                    paged_decode_attention / paged_prefill_attention: both on page pools behind a block table;
+                   shared_prefix_decode_attention / shared_prefix_workspace: paged decode that reads a forked prefix once per group;
                    ragged_prefill_attention / paged_ragged_prefill_attention / ragged_workspace: up to 128 rows of SEVERAL
                    sequences in one launch (segments described on the device)
-  paging.py        PagedKVCache: per-layer page pools, the block table and the host-side page allocator (reserve / release / fork)
+  paging.py        PagedKVCache: per-layer page pools, the block table and the host-side page allocator (reserve / release / fork);
+                   SharedPrefix (cache.prefix): the groups of slots that share a forked prefix, as the shared-prefix launch reads them
   decoder.py       DecodeStep: the whole-model decode step at batch B >= 1 on the kernels above (per-layer launch sequence,
                    scratch buffers, final norm + lm_head + argmax, launches per token); Prefill: a prompt into one cache slot;
                    Score: the log-probability of every next token of a sequence, nll and perplexity;
@@ -72,9 +74,10 @@ from . import quantize_layer  # noqa: F401
 from . import attention  # noqa: F401
 from .attention import attention_workspace, decode_attention, prefill_attention, prefill_workspace  # noqa: F401
 from .attention import paged_decode_attention, paged_prefill_attention  # noqa: F401
+from .attention import reference_shared_rows, shared_prefix_decode_attention, shared_prefix_workspace  # noqa: F401
 from .attention import paged_ragged_prefill_attention, ragged_prefill_attention, ragged_workspace  # noqa: F401
 from . import paging  # noqa: F401
-from .paging import PagedKVCache  # noqa: F401
+from .paging import PagedKVCache, SharedPrefix  # noqa: F401
 from . import sampling  # noqa: F401
 from .sampling import Sampler, lm_head_logits, reference_draw, reference_logprob, sample, token_logprobs  # noqa: F401
 from . import logits  # noqa: F401

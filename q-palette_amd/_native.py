@@ -72,6 +72,9 @@ _SIGNATURES = {
                                    _P, ctypes.c_long, _P],
     "qpal_attn_rope_decode_batch_paged": [_P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _I, _I, _I, _I,
                                           _I, _I, _I, _I, _F, _P, ctypes.c_long, _P],
+    "qpal_attn_prefix_ws_bytes": [_I, _I, _I, _I, _I, ctypes.c_long],
+    "qpal_attn_rope_decode_batch_shared": [_P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _I, _I, _I, _I,
+                                           _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, ctypes.c_long, _P],
     "qpal_attn_rope_prefill_paged": [_P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _P, _P, _I, _I, _I, _I,
                                      _I, _I, _I, _I, _F, _P, ctypes.c_long, _P],
     "qpal_attn_ragged_ws_bytes": [_I, _I, _I, _I, _I, ctypes.c_long],
@@ -142,6 +145,7 @@ def lib():
         l.qpal_attn_ws_bytes.restype = ctypes.c_long
         l.qpal_attn_batch_ws_bytes.restype = ctypes.c_long
         l.qpal_attn_prefill_ws_bytes.restype = ctypes.c_long
+        l.qpal_attn_prefix_ws_bytes.restype = ctypes.c_long
         l.qpal_attn_ragged_ws_bytes.restype = ctypes.c_long
         l.qpal_lm_head_ws_bytes.restype = ctypes.c_long
         l.qpal_tcq_viterbi_ws_bytes.restype = ctypes.c_long

@@ -26,6 +26,12 @@ the workspaces of that max_len serve the paged launches, and the result is bit f
     out = paged_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, ws=ws)
     out = paged_prefill_attention(q, k, v, kpool, vpool, block_table[b], pos0, inv_freq, ws=ws)
 
+Slots of a paged cache that share the pages of a common prefix (``PagedKVCache.fork``) read it once per group
+(``qpal_attn_rope_decode_batch_shared``, csrc/attn_prefix.hip):
+
+    ws = shared_prefix_workspace(B, cache.prefix.G, nq, nkv, hd, max_len, device)
+    out = shared_prefix_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, cache.prefix, ws=ws)
+
 Ragged prefill (``qpal_attn_rope_prefill_ragged`` / ``_paged``, csrc/attn_ragged.hip): up to 128 rows of SEVERAL
 sequences in one launch — prompt chunks and decode tokens side by side — cut into segments that three device tensors describe.
 
@@ -105,8 +111,9 @@ def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=Non
     return _decode("decode_attention", entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, None)
 
 
-def _decode(who, entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, paged):
-    """the checks and the launch both decode entry points share; paged: None, or the arguments that take max_len's place"""
+def _decode(who, entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, paged, groups=None):
+    """the checks and the launch the decode entry points share; paged: None, or the arguments that take max_len's place; groups: None,
+    or the G of a shared-prefix launch (its workspace is shared_prefix_workspace's)"""
     if q.dim() != 2 or q.shape[0] != B or q.shape[1] % hd:
         raise QpalError(f"{who}: q must have shape [{B}, nq*{hd}], got {list(q.shape)}")
     nq = q.shape[1] // hd
@@ -126,10 +133,13 @@ def _decode(who, entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, 
         raise QpalError(f"{who}: out must be fp16 [{B}, {nq * hd}] with contiguous rows on {kcache.device}")
     ld_out = out.stride(0) if B > 1 else nq * hd
     lib = _native.lib()
-    need = lib.qpal_attn_batch_ws_bytes(B, nq, nkv, hd, max_len)
+    if groups is None:
+        need, maker = lib.qpal_attn_batch_ws_bytes(B, nq, nkv, hd, max_len), "attention_workspace"
+    else:
+        need, maker = lib.qpal_attn_prefix_ws_bytes(B, groups, nq, nkv, hd, max_len), "shared_prefix_workspace"
     if need > 0:
         if ws is None:
-            raise QpalError(f"{who}: this shape needs a workspace (attention_workspace(...))")
+            raise QpalError(f"{who}: this shape needs a workspace ({maker}(...))")
         if ws.device != kcache.device or ws.numel() * ws.element_size() < need or not ws.is_contiguous():
             raise QpalError(f"{who}: ws must be a contiguous device buffer of >= {need} bytes on {kcache.device}")
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
@@ -268,6 +278,71 @@ def paged_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, sc
     B, nkv, max_len, hd, paged = _pools_2d(kpool, vpool, block_table, who)
     return _decode(who, "qpal_attn_rope_decode_batch_paged", q, k, v, kpool, vpool, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd,
                    paged)
+
+
+MAX_GROUPS = 16  # groups of one shared-prefix launch
+
+
+def reference_shared_rows(row_group, grp_slot, grp_len, pos, page_size, max_len):
+    """The membership rule of the shared-prefix launch (csrc/attn_prefix.h: shared_prefix_len) restated in numpy.  row_group [B],
+    grp_slot / grp_len [G], pos [B] as integer arrays.  Returns (group, length) as int64 [B]: slot b is served as a member of
+    group[b] with length[b] > 0 shared positions, or group[b] = -1 and length[b] = 0 where it is an ordinary slot."""
+    import numpy as np
+
+    row_group, pos = np.asarray(row_group, dtype=np.int64).reshape(-1), np.asarray(pos, dtype=np.int64).reshape(-1)
+    grp_slot, grp_len = np.asarray(grp_slot, dtype=np.int64).reshape(-1), np.asarray(grp_len, dtype=np.int64).reshape(-1)
+    B, G = row_group.shape[0], grp_slot.shape[0]
+    in_range = (row_group >= 0) & (row_group < G)
+    g = np.where(in_range, row_group, 0)
+    gs, gl = (grp_slot[g], grp_len[g]) if G else (np.full(B, -1), np.zeros(B, dtype=np.int64))
+    member = in_range & (gs >= 0) & (gs < B) & (gl > 0) & (gl % int(page_size) == 0) & (gl <= pos) & (pos >= 0) & (pos < int(max_len))
+    return np.where(member, row_group, -1), np.where(member, gl, 0)
+
+
+def _prefix_tensors(prefix, B, dev, who):
+    """the checks of the three tensors that describe sharing; returns the launch arguments behind the paged ones"""
+    rg, gs, gl = (getattr(prefix, n, None) for n in ("row_group", "grp_slot", "grp_len"))
+    if any(not isinstance(t, torch.Tensor) for t in (rg, gs, gl)):
+        raise QpalError(f"{who}: prefix must carry the tensors row_group, grp_slot and grp_len (paging.SharedPrefix)")
+    for name, t in (("row_group", rg), ("grp_slot", gs), ("grp_len", gl)):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise QpalError(f"{who}: {name} must be a contiguous int32 vector, got {t.dtype} {list(t.shape)}")
+        if t.device != dev:
+            raise QpalError(f"{who}: {name} must be on the pools' device {dev}, got {t.device}")
+    G = gs.shape[0]
+    if rg.shape[0] != B:
+        raise QpalError(f"{who}: row_group must have shape [{B}], got {list(rg.shape)}")
+    if not 1 <= G <= MAX_GROUPS or gl.shape[0] != G:
+        raise QpalError(f"{who}: grp_slot and grp_len must both have shape [G] with 1 <= G <= {MAX_GROUPS}, got {list(gs.shape)} and "
+                        f"{list(gl.shape)}")
+    return (rg.data_ptr(), gs.data_ptr(), gl.data_ptr(), G), G
+
+
+def shared_prefix_workspace(B, G, nq, nkv, hd, max_len, device):
+    """The zero-filled workspace ``shared_prefix_decode_attention`` needs for up to B slots in up to G groups on a paged cache of
+    max_len = max_pages * page_size positions (same nq, nkv, hd).  It contains the plain launch's workspace; keep it across
+    launches and layers: both launches leave their tickets at zero."""
+    n = _native.lib().qpal_attn_prefix_ws_bytes(int(B), int(G), int(nq), int(nkv), int(hd), int(max_len))
+    if n <= 0:
+        raise QpalError(f"shared_prefix_workspace: no shared-prefix launch of shape B={B}, G={G}, nq={nq}, nkv={nkv}, hd={hd}, "
+                        f"max_len={max_len}")
+    return torch.zeros((n + 3) // 4, dtype=torch.float32, device=device)
+
+
+def shared_prefix_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, prefix, scale=None, out=None, ws=None):
+    """paged_decode_attention for slots that share the pages of a common prefix (``qpal_attn_rope_decode_batch_shared``, DESIGN.md
+    §26).  prefix: a paging.SharedPrefix (``cache.prefix``) — row_group int32 [B], grp_slot / grp_len int32 [G] on the pools'
+    device, read by the launches and never by the host.  A slot that reference_shared_rows() makes a member reads its group's first
+    grp_len positions through table row grp_slot, once per group, and the rest through its own row; every other slot, the appended
+    rows and the pools are bit for bit paged_decode_attention's.  Two launches on the current stream.  ws:
+    shared_prefix_workspace(B, G, ...), always needed."""
+    who = "shared_prefix_decode_attention"
+    if block_table.dim() != 2:
+        raise QpalError(f"{who}: block_table must have shape [B, max_pages >= 1], got {list(block_table.shape)}")
+    tensors, G = _prefix_tensors(prefix, block_table.shape[0], kpool.device, who)  # (first: these checks need no device)
+    B, nkv, max_len, hd, paged = _pools_2d(kpool, vpool, block_table, who)
+    return _decode(who, "qpal_attn_rope_decode_batch_shared", q, k, v, kpool, vpool, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd,
+                   paged + tensors, groups=G)
 
 
 def paged_prefill_attention(q, k, v, kpool, vpool, block_row, pos0, inv_freq, scale=None, out=None, ws=None):

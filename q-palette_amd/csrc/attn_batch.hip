@@ -27,6 +27,7 @@
 
 #include <type_traits>
 
+#include "attn_prefix.h"
 #include "kv8.h"
 #include "kv_paged.h"
 #include "qpal_common.h"
@@ -61,6 +62,11 @@ struct AttnBatchParams {
     const int *table;           // int32 [B][ld_table], device
     long ld_table;
     int num_pages, page_shift;
+    // SHARED only (qpal_attn_rope_decode_batch_shared, attn_prefix.h): the sharing of the launch, its B, and the
+    // merged prefix partials [B][nkv * REP][HD + 2] the prefix launch left in front of this one in the stream
+    SharedPrefixArgs sp;
+    int B;
+    const float *pre;
 };
 
 __device__ __forceinline__ void st_agent(float *p, float v) {
@@ -70,7 +76,10 @@ __device__ __forceinline__ float ld_agent(const float *p) {
     return __builtin_bit_cast(float, __hip_atomic_load(as_global(reinterpret_cast<const unsigned *>(p)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
-template <class CT, bool PAGED, int HD, int REP>
+// SHARED (PAGED only): a member of a group (shared_prefix_len) attends to [grp_len, pos] through its own table row — the chunk
+// formulas below applied to pos - start, so start = 0 is the plain launch — and every finishing path folds the row's prefix partial
+// in, as the chunk in front of the row's own, before the division.  An ordinary slot takes the plain launch's arithmetic.
+template <class CT, bool PAGED, int HD, int REP, bool SHARED = false>
 __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const AttnBatchParams<CT> p) {
     constexpr bool KV8 = kIsKv8<CT>;
     constexpr int NW = kBatchNW, NT = 64 * NW, HALF = HD / 2;
@@ -93,14 +102,21 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
     // the context that exists, cut evenly over the splits (chunks of a multiple of 64 positions, at least kBatchMinChunk, at most
     // the LDS capacity); chunks 0 .. neff-1 hold positions <= pos, the last of them the new one
     // (32-bit unsigned divisions: positions are below max_len < 2^30)
+    [[maybe_unused]] long start = 0;  // SHARED: the positions the prefix launch has served for this slot
+    if constexpr (SHARED) {
+        static_assert(PAGED, "groups share pages");
+        int g;
+        start = shared_prefix_len(p.sp, b, pos, p.B, p.page_shift, p.max_len, g);
+    }
+    const long rel = SHARED ? pos - start : pos;
     long cld = CL;
     if (p.nsplit > 1) {
-        cld = (long)((((unsigned)pos + (unsigned)p.nsplit) / (unsigned)p.nsplit + 63u) & ~63u);
+        cld = (long)((((unsigned)rel + (unsigned)p.nsplit) / (unsigned)p.nsplit + 63u) & ~63u);
         if (cld < kBatchMinChunk) cld = kBatchMinChunk;
         if (cld > CL) cld = CL;
     }
-    const long c0 = (long)split * cld;
-    const int neff = (int)((unsigned)pos / (unsigned)cld) + 1;
+    const long c0 = (SHARED ? start : 0) + (long)split * cld;
+    const int neff = (int)((unsigned)rel / (unsigned)cld) + 1;
     if (split >= neff) return;
     const bool owner = split == neff - 1;                    // this chunk holds the new position
     const long cend = pos < c0 + cld ? pos : c0 + cld;       // cached positions of the chunk: [c0, cend)
@@ -376,6 +392,15 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
         for (int w = 0; w < NW; w++) v += po[w * REP * HD + idx];
         const int h = idx / HD, d = idx - h * HD;
         if (owner) v += park[h] * vn[d];
+        if constexpr (SHARED) {
+            if (neff == 1 && start > 0) {  // the only chunk of a member: the prefix partial, then this one
+                const float *pr = p.pre + ((long)b * p.nkv * REP + kh * REP + h) * (HD + 2);
+                const float pm = pr[0], M = pm > mxf[h] ? pm : mxf[h];
+                const float f0 = __expf(pm - M), f1 = __expf(mxf[h] - M);
+                orow[idx] = __builtin_bit_cast(uint16_t, (_Float16)((pr[2 + d] * f0 + v * f1) / (pr[1] * f0 + sumf[h] * f1)));
+                continue;
+            }
+        }
         if (neff == 1) orow[idx] = __builtin_bit_cast(uint16_t, (_Float16)(v / sumf[h]));  // the only chunk
         else st_agent(wsp + h * (HD + 2) + 2 + d, v);
     }
@@ -412,6 +437,15 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
             M = m > M ? m : M;
         }
         float L = 0.f, o = 0.f;
+        if constexpr (SHARED) {
+            if (start > 0) {  // a member: the prefix partial is the chunk in front of the row's own
+                const float *pr = p.pre + ((long)b * p.nkv * REP + kh * REP + h) * (HD + 2);
+                const float pm = pr[0];
+                M = pm > M ? pm : M;
+                const float f = __expf(pm - M);
+                L = pr[1] * f, o = pr[2 + d] * f;
+            }
+        }
         for (int s0 = 0; s0 < neff; s0 += 16) {
             float v[16];
 #pragma unroll
@@ -439,6 +473,9 @@ size_t batch_lds_floats(int rep, int hd, long chunk) {
     const int nw = kBatchNW;
     return (size_t)rep * chunk + (size_t)rep * hd / 2 + hd / 2 + hd + (size_t)nw * rep * hd + 2 * (size_t)nw * rep + 3 * rep + 4;
 }
+
+template <class CT>
+constexpr int kKvFmt = kIsKv8<CT> ? 1 : 0;  // the kv_fmt of a cache element type
 
 struct BatchGeometry {
     int nsplit, chunk;
@@ -481,9 +518,9 @@ int batch_geometry(int B, int nq, int nkv, int hd, long max_len, BatchGeometry &
     return QPAL_OK;
 }
 
-template <class CT, bool PAGED, int HD, int REP>
+template <class CT, bool PAGED, int HD, int REP, bool SHARED = false>
 int launch_batch(const AttnBatchParams<CT> &p, int grid, size_t lds, void *stream) {
-    const auto kern = attn_rope_batch_kernel<CT, PAGED, HD, REP>;
+    const auto kern = attn_rope_batch_kernel<CT, PAGED, HD, REP, SHARED>;
     static bool attr_set[64] = {};  // one latch per instantiation and device
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
@@ -498,14 +535,29 @@ int launch_batch(const AttnBatchParams<CT> &p, int grid, size_t lds, void *strea
 
 // the entry points: the same checks, geometry and launch, the cache element type and the row addressing apart (PAGED: kcache /
 // vcache are the pools, `pg` the block table, max_len = max_pages * page_size)
-template <class CT, bool PAGED>
+// the workspace of the shared launches: the plain launch's in front, then the prefix phase's tickets, chunk partials and merged
+// partials (attn_prefix.h)
+size_t shared_ws_bytes(const BatchGeometry &g, const PrefixGeometry &x) {
+    return g.ws_bytes + (x.tickets + x.part + x.pre) * sizeof(float);
+}
+
+// sp: SHARED — the sharing of the launch; the prefix launch goes first, stream order is the only synchronisation between the two
+template <class CT, bool PAGED, bool SHARED = false>
 int attn_rope_decode_batch(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16,
                            long ld_out, const long *pos, const float *inv_freq, int B, int nq, int nkv, int hd, long max_len,
-                           float scale, void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0) {
+                           float scale, void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0,
+                           const SharedPrefixArgs *sp = nullptr) {
     if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
     BatchGeometry g;
     const int rc = batch_geometry(B, nq, nkv, hd, max_len, g);
     if (rc != QPAL_OK) return rc;
+    [[maybe_unused]] PrefixGeometry x{};
+    [[maybe_unused]] const size_t plain_ws = g.ws_bytes;
+    if constexpr (SHARED) {
+        if (sp->G < 1 || sp->G > kPxMaxGroups) return QPAL_E_SHAPE;
+        prefix_geometry(B, sp->G, nq, nkv, hd, max_len, x);
+        g.ws_bytes = shared_ws_bytes(g, x);  // (checked below as the plain launch's is)
+    }
     if (ld_qkv < (long)nq * hd || ld_out < (long)nq * hd) return QPAL_E_SHAPE;
     if ((reinterpret_cast<uintptr_t>(kcache) | reinterpret_cast<uintptr_t>(vcache)) & 15) return QPAL_E_ALIGN;
     if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
@@ -513,20 +565,33 @@ int attn_rope_decode_batch(const float *q, const float *k, const float *v, long 
         return QPAL_E_ALIGN;
     if (reinterpret_cast<uintptr_t>(out_f16) & 1) return QPAL_E_ALIGN;
     if (PAGED && (reinterpret_cast<uintptr_t>(pg->table) & 3)) return QPAL_E_ALIGN;
+    if constexpr (SHARED) {
+        if ((reinterpret_cast<uintptr_t>(sp->row_group) | reinterpret_cast<uintptr_t>(sp->grp_slot) | reinterpret_cast<uintptr_t>(sp->grp_len)) & 3)
+            return QPAL_E_ALIGN;
+    }
     if (g.ws_bytes) {
         if (!ws) return QPAL_E_NULL;
         if (ws_bytes < (long)g.ws_bytes) return QPAL_E_SHAPE;
         if (reinterpret_cast<uintptr_t>(ws) & 3) return QPAL_E_ALIGN;
     }
     float *wsf = static_cast<float *>(ws);
+    if constexpr (SHARED) g.ws_bytes = plain_ws;  // from here on: the part of the workspace the suffix launch owns
     AttnBatchParams<CT> p{q, k, v, ld_qkv, static_cast<CT *>(kcache), static_cast<CT *>(vcache),
                           static_cast<uint16_t *>(out_f16), ld_out, pos, inv_freq, nkv, max_len, scale,
                           g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr, g.ws_bytes ? wsf + (long)kBatchMax * nkv : nullptr,
                           g.nsplit, g.chunk};
     if constexpr (PAGED) p.table = pg->table, p.ld_table = pg->ld_table, p.num_pages = pg->num_pages, p.page_shift = shift;
     const int grid = B * nkv * g.nsplit, rep = nq / nkv;
+    if constexpr (SHARED) {
+        float *xf = wsf + plain_ws / sizeof(float);
+        p.sp = *sp, p.B = B, p.pre = xf + x.tickets + x.part;
+        const PrefixLaunch a{q, ld_qkv, kcache, vcache, pos, inv_freq, *sp, pg->table, pg->ld_table, pg->num_pages, shift, B, nkv,
+                             max_len, scale, reinterpret_cast<unsigned *>(xf), xf + x.tickets, xf + x.tickets + x.part, x.nsplit, x.ntile};
+        const int rc2 = launch_attn_prefix(a, kKvFmt<CT>, hd, rep, stream);
+        if (rc2 != QPAL_OK) return rc2;
+    }
 #define QPAL_BATCH(HD_, REP_) \
-    if (hd == HD_ && rep == REP_) return launch_batch<CT, PAGED, HD_, REP_>(p, grid, g.lds, stream);
+    if (hd == HD_ && rep == REP_) return launch_batch<CT, PAGED, HD_, REP_, SHARED>(p, grid, g.lds, stream);
     QPAL_BATCH(64, 1) QPAL_BATCH(64, 2) QPAL_BATCH(64, 4) QPAL_BATCH(64, 8)
     QPAL_BATCH(128, 1) QPAL_BATCH(128, 2) QPAL_BATCH(128, 4) QPAL_BATCH(128, 8)
     QPAL_BATCH(256, 1) QPAL_BATCH(256, 2) QPAL_BATCH(256, 4)
@@ -579,4 +644,32 @@ extern "C" int qpal_attn_rope_decode_batch_paged(const float *q, const float *k,
                                                      scale, ws, ws_bytes, stream, &pg, shift);
     return attn_rope_decode_batch<uint16_t, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd, max_len,
                                                   scale, ws, ws_bytes, stream, &pg, shift);
+}
+
+extern "C" long qpal_attn_prefix_ws_bytes(int B, int G, int nq, int nkv, int hd, long max_len) {
+    BatchGeometry g;
+    if (batch_geometry(B, nq, nkv, hd, max_len, g) != QPAL_OK || G < 1 || G > kPxMaxGroups) return 0;
+    PrefixGeometry x;
+    prefix_geometry(B, G, nq, nkv, hd, max_len, x);
+    return (long)shared_ws_bytes(g, x);
+}
+
+extern "C" int qpal_attn_rope_decode_batch_shared(const float *q, const float *k, const float *v, long ld_qkv, void *kpool, void *vpool,
+                                                  void *out_f16, long ld_out, const long *pos, const float *inv_freq,
+                                                  const int *block_table, long ld_table, int num_pages, int page_size, int max_pages,
+                                                  int kv_fmt, const int *row_group, const int *grp_slot, const int *grp_len, int G, int B,
+                                                  int nq, int nkv, int hd, float scale, void *ws, long ws_bytes, void *stream) {
+    if (!block_table || !row_group || !grp_slot || !grp_len) return QPAL_E_NULL;
+    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
+    const SharedPrefixArgs sp{row_group, grp_slot, grp_len, G};
+    int shift;
+    long max_len;
+    if (!q || !k || !v || !kpool || !vpool || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
+    const int rc = paged_shape(pg, kv_fmt, shift, max_len);
+    if (rc != QPAL_OK) return rc;
+    if (kv_fmt == 1)
+        return attn_rope_decode_batch<uint8_t, true, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd,
+                                                           max_len, scale, ws, ws_bytes, stream, &pg, shift, &sp);
+    return attn_rope_decode_batch<uint16_t, true, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd,
+                                                        max_len, scale, ws, ws_bytes, stream, &pg, shift, &sp);
 }

@@ -74,7 +74,8 @@ from . import hadamard as had
 from . import grammar as gram_mod
 from . import linear, logits, lora, ops, sampling
 from .attention import (attention_workspace, decode_attention, paged_decode_attention, paged_prefill_attention,
-                        paged_ragged_prefill_attention, prefill_attention, prefill_workspace, ragged_prefill_attention, ragged_workspace)
+                        paged_ragged_prefill_attention, prefill_attention, prefill_workspace, ragged_prefill_attention, ragged_workspace,
+                        shared_prefix_decode_attention, shared_prefix_workspace)
 from .linear import multi_gemv
 
 
@@ -304,7 +305,9 @@ class DecodeStep(_Rows):
     sampler.logits[b], for the rows that drew (pos[b] >= 0 — the positions are the launch's `active` vector; other slots keep theirs).
     block_table: int32 [B, max_pages] on the device — kcache / vcache are then the per-layer page pools [num_pages, nkv, page_size, hd]
     of a paged cache, context = max_pages * page_size, and the attention launch is paged_decode_attention (a batch of one as well:
-    the fused single-sequence kernel reads contiguous caches only).  The caller has reserved a page for every position the step, or
+    the fused single-sequence kernel reads contiguous caches only).  shared_prefix: paging.SharedPrefix (cache.prefix, with block_table=
+    cache.table) — the attention launch becomes shared_prefix_decode_attention, which reads a forked prefix once per group: one more
+    launch per layer, everything else in the step is untouched; without block_table: QpalError.  The caller has reserved a page for every position the step, or
     a run of replays of the captured step, will write: the step reads the table on the device and never allocates.
     adapters: a lora.LoraBank of B slots — row b runs with adapter bank.slot_adapter[b], read by the launches themselves: four more
     launches per layer.  At batch 1 the interleaved up|gate epilogue and down_proj's staged rotation are then off (they never put
@@ -320,8 +323,10 @@ class DecodeStep(_Rows):
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok, generic=False,
                  swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True, sampler=None, block_table=None,
-                 adapters=None, processor=None, grammar=None):
+                 adapters=None, processor=None, grammar=None, shared_prefix=None):
         B = tok.shape[0]
+        if shared_prefix is not None and block_table is None:
+            raise nat.QpalError("DecodeStep: shared_prefix needs a paged cache (block_table=cache.table)")
         self.batch1 = B == 1 and not generic
         super().__init__("DecodeStep", layers, embed, norm, lm_head, kcache, vcache, inv_freq, B, sampler, block_table, slots=B,
                          native_argmax=self.batch1 and native_lm_head, adapters=adapters, processor=processor, grammar=grammar)
@@ -347,7 +352,10 @@ class DecodeStep(_Rows):
         # the fused single-sequence attention kernel reads contiguous fp16 caches only: on float8_e4m3fn or paged caches the batch-1
         # step keeps its GEMV fusions and launches the batched attention at B = 1 (same launch count)
         self.attn_batch = not self.batch1 or kcache[0].dtype != torch.float16 or block_table is not None
-        if self.attn_batch:
+        self.shared_prefix = shared_prefix
+        if shared_prefix is not None:
+            self.attn_ws = shared_prefix_workspace(B, shared_prefix.G, self.nq, self.nkv, self.head_dim, self.context, dev)
+        elif self.attn_batch:
             self.attn_ws = attention_workspace(B, self.nq, self.nkv, self.head_dim, self.context, dev)
         else:
             # long caches: split-context attention (one workspace serves every layer: launches are stream-ordered)
@@ -360,8 +368,10 @@ class DecodeStep(_Rows):
         q|k|v, o and up|gate where the GEMV cannot rotate; - the SwiGLU rotation where down_proj's staging runs it); + the norm /
         lm_head / argmax launch, or the lm_head logits and the draw with a sampler, + the log-probability launch of a sampler with
         logprobs (the embedding row copy is a memcpy node); with adapters + 4 per layer, one per projection group; with a
-        processor + 2, observe and process; with a grammar + 2, mask and advance"""
+        processor + 2, observe and process; with a grammar + 2, mask and advance; with shared_prefix + 1 per layer, the prefix
+        phase in front of the attention launch"""
         per_layer = (5 if self.ug_il and self.ug_il[0][2] else 6) if self.rot_in_gemv else 9
+        per_layer += 1 if getattr(self, "shared_prefix", None) is not None else 0
         per_layer += 4 if getattr(self, "adapters", None) is not None else 0  # (arithmetic on the configuration: stand-ins may lack it)
         tail = 1 if self.sampler is None else (2 if self.sampler.logprob is None else 3)
         tail += 2 if getattr(self, "processor", None) is not None else 0
@@ -384,6 +394,9 @@ class DecodeStep(_Rows):
                                                      self.context, self.attn_scale, self.attn_ws.data_ptr() if self.attn_ws_bytes else None,
                                                      self.attn_ws_bytes, torch.cuda.current_stream(dev).cuda_stream)
             return nat.check(rc, "qpal_attn_rope_decode")
+        if self.shared_prefix is not None:
+            return shared_prefix_decode_attention(q, k, v, kc, vc, self.block_table, self.pos, self.inv_freq, self.shared_prefix,
+                                                  scale=self.attn_scale, out=out, ws=self.attn_ws)
         if self.block_table is None:
             attend, cache = decode_attention, (kc, vc)
         else:

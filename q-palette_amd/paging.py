@@ -5,6 +5,7 @@
     step = DecodeStep(layers, embed, norm, lm_head, cache.kpool, cache.vpool, inv_freq, tok, pos, out_tok, block_table=cache.table)
     cache.release(slot)                    # the slot's pages go back to the free list
     cache.fork(src, dst, n_positions)      # dst shares src's first n_positions (a shared prompt prefix)
+    step = DecodeStep(..., block_table=cache.table, shared_prefix=cache.prefix)   # the shared pages are read once per group
 
 A pool is ``[num_pages, nkv, page_size, hd]`` (k and v of every layer have one each); entry j of the table's row b is the page that
 holds positions ``j * page_size .. (j + 1) * page_size - 1`` of slot b in EVERY layer's pools, -1 where nothing is reserved (the
@@ -15,11 +16,50 @@ reach before it starts."""
 import torch
 
 from ._native import QpalError
-from .attention import PAGE_SIZES, kv_cache_bytes
+from .attention import MAX_GROUPS, PAGE_SIZES, kv_cache_bytes
+
+# The smallest prefix fork() makes a group of, in positions, and the fewest members a group needs before it is published to the
+# device.  DESIGN.md §26.5: the shared launch pair beats the plain paged launch by more than the plain launch's spread at (members,
+# length) = (32, 2048), (64, 2048), (32, 4096), (64, 4096) and loses or ties at 8 or 16 members and at 1024 positions; groups the
+# measurement does not favour stay with the plain arithmetic (the launch serves an unpublished slot exactly as the plain one does).
+MIN_SHARED_LEN = 2048
+MIN_SHARED_MEMBERS = 32
+
+
+class SharedPrefix:
+    """What the shared-prefix decode launch reads: row_group int32 [B] (the group of a slot, or -1), grp_slot int32
+    [G] (a live member whose table row addresses the group's shared pages), grp_len int32 [G] (the shared positions, a multiple of
+    page_size; 0: no such group).  The tensors keep their addresses: a captured step sees every later push()."""
+
+    def __init__(self, row_group, grp_slot, grp_len, flat=None):
+        self.row_group, self.grp_slot, self.grp_len = row_group, grp_slot, grp_len
+        self._flat = flat  # empty(): the three are views of one vector, so that push() is ONE copy
+
+    @property
+    def G(self):
+        return self.grp_slot.shape[0]
+
+    @classmethod
+    def empty(cls, B, G=MAX_GROUPS, device="cpu"):
+        flat = torch.tensor([-1] * (B + G) + [0] * G, dtype=torch.int32).to(device)
+        return cls(flat[:B], flat[B:B + G], flat[B + G:], flat)
+
+    def push(self, row_group, grp_slot, grp_len):
+        """the three host lists into the device tensors: one small copy"""
+        B, G = self.row_group.shape[0], self.G
+        new = torch.tensor(list(row_group) + list(grp_slot) + list(grp_len), dtype=torch.int32)
+        if self._flat is not None:
+            self._flat.copy_(new)
+        else:
+            for t, part in ((self.row_group, new[:B]), (self.grp_slot, new[B:B + G]), (self.grp_len, new[B + G:])):
+                t.copy_(part)
 
 
 class PagedKVCache:
-    def __init__(self, n_layers, num_pages, nkv, page_size, hd, B, max_pages, dtype=torch.float16, device="cpu"):
+    def __init__(self, n_layers, num_pages, nkv, page_size, hd, B, max_pages, dtype=torch.float16, device="cpu", groups=MAX_GROUPS,
+                 min_len=MIN_SHARED_LEN, min_members=MIN_SHARED_MEMBERS):
+        if not 1 <= int(groups) <= MAX_GROUPS:
+            raise QpalError(f"PagedKVCache: groups must lie in [1, {MAX_GROUPS}], got {groups}")
         if page_size not in PAGE_SIZES:
             raise QpalError(f"PagedKVCache: page_size must be one of {PAGE_SIZES}, got {page_size}")
         if min(n_layers, num_pages, nkv, hd, B, max_pages) < 1:
@@ -36,6 +76,13 @@ class PagedKVCache:
         self._shared = [0] * self.B                          # the prefix a forked slot took from its source
         self._refs = [0] * self.num_pages
         self._free = list(range(self.num_pages - 1, -1, -1))  # a stack: pop() hands out page 0 first
+        # shared prefixes: the groups fork() publishes for the shared-prefix decode launch
+        self.min_len = int(min_len)                          # the smallest prefix worth a group
+        self.min_members = max(int(min_members), 2)          # the fewest members of a group the device is told of
+        self.prefix = SharedPrefix.empty(self.B, int(groups), device)
+        self._group = [-1] * self.B                          # the group of every slot
+        self._members = [[] for _ in range(int(groups))]     # the members of every group, in joining order
+        self._glen = [0] * int(groups)
 
     # ------------------------------------------------------------------------------------------------------ figures
     @property
@@ -62,6 +109,55 @@ class PagedKVCache:
     def bytes(self):
         """bytes of ONE pool (k or v of one layer): kv_cache_bytes of a contiguous cache that holds as many positions"""
         return kv_cache_bytes(self.num_pages, self.nkv, self.page_size, self.hd, self.dtype)
+
+    def group_of(self, slot):
+        """the group whose shared pages `slot` reads once per group in the shared-prefix launch, or -1"""
+        return self._group[self._slot(slot)]
+
+    def members_of(self, group):
+        """the slots of `group` (a copy; empty: no such group)"""
+        return list(self._members[group])
+
+    def published(self, group):
+        """whether `prefix` names the group: it has at least min_members members"""
+        return len(self._members[group]) >= self.min_members
+
+    def _push_prefix(self):
+        pub = [self.published(g) for g in range(len(self._members))]
+        self.prefix.push([g if g >= 0 and pub[g] else -1 for g in self._group],
+                         [m[0] if ok else -1 for m, ok in zip(self._members, pub)], [n if ok else 0 for n, ok in zip(self._glen, pub)])
+
+    def _join(self, src, dst, n):
+        """fork's bookkeeping of groups: dst joins src's group where the fork shares at least that group's length, or the two
+        found a group of the whole pages below n; returns whether anything changed"""
+        shared = n // self.page_size * self.page_size
+        g = self._group[src]
+        if g >= 0:
+            if shared < self._glen[g]:
+                return False  # a shorter fork from a grouped slot: correct, just not deduplicated
+        else:
+            if shared < max(self.min_len, self.page_size):
+                return False
+            g = next((i for i, m in enumerate(self._members) if not m), -1)
+            if g < 0:
+                return False  # every group is taken: the fork stays ungrouped
+            self._members[g], self._glen[g], self._group[src] = [src], shared, g
+        self._members[g].append(dst)
+        self._group[dst] = g
+        return True
+
+    def _leave(self, slot):
+        """release's: the slot leaves its group; a group of fewer than two members dissolves; returns whether anything changed"""
+        g = self._group[slot]
+        if g < 0:
+            return False
+        self._members[g].remove(slot)  # (grp_slot is the first member left: a survivor)
+        self._group[slot] = -1
+        if len(self._members[g]) < 2:
+            for m in self._members[g]:
+                self._group[m] = -1
+            self._members[g], self._glen[g] = [], 0
+        return True
 
     # ---------------------------------------------------------------------------------------------------- allocator
     def _slot(self, slot):
@@ -101,10 +197,14 @@ class PagedKVCache:
         self._rows[slot], self._shared[slot] = [], 0
         if had:
             self._push_row(slot)
+        if self._leave(slot):
+            self._push_prefix()
 
     def fork(self, src, dst, n_positions):
         """`dst` (released) takes the first n_positions of `src`: references on src's pages that lie wholly below n_positions, and a
-        fresh page with a copy of the partial page, if any, in every layer.  No copy-on-write: both slots append at positions >=
+        fresh page with a copy of the partial page, if any, in every layer.  Whole shared pages of at least min_len positions make
+        the two a group (or dst joins src's group where the fork covers that group's length), which `prefix` names once it has
+        min_members members.  No copy-on-write: both slots append at positions >=
         n_positions only (`src` into its own partial page, `dst` into its copy), so a shared page is never written."""
         src, dst = self._slot(src), self._slot(dst)
         if src == dst or self._rows[dst]:
@@ -126,3 +226,5 @@ class PagedKVCache:
             pages = pages + [page]
         self._rows[dst], self._shared[dst] = pages, n
         self._push_row(dst)
+        if self._join(src, dst, n):
+            self._push_prefix()
