@@ -508,6 +508,27 @@ int qpal_sample(const float *logits_f32, long ld_logits, int rows, int vocab, co
 int qpal_token_logprob(const float *logits_f32, long ld_logits, int rows, int vocab, const long long *token, float *logprob,
                        float *lse, int *rank, const long long *active, void *stream);
 
+/* The n likeliest tokens of every row and their log-probabilities under the plain softmax of the row's raw logits — the
+ * "top_logprobs" of a completion API —, one launch (csrc/top_logprob.hip).  logits fp32 [rows][ld_logits],
+ * 1 <= rows <= 128, 1 <= vocab <= 2^30, ld_logits >= vocab, 1 <= n <= 64; top_id int32 [rows][n], top_logprob fp32 [rows][n]; lse
+ * fp32 [rows] and active int64 [rows] may each be NULL.  Alignment: 4 bytes, 8 for active.  The return codes of qpal_sample
+ * (QPAL_E_NULL / QPAL_E_SHAPE / QPAL_E_ALIGN).  All on the device and never read by the host (capturable); one launch, no
+ * workspace, no global atomics.  For row b:
+ *  1. Inactive rows.  active != NULL and active[b] < 0: nothing of row b is written.
+ *  2. Logit values.  l is the row's first vocab fp32 values, with NaN read as -inf.
+ *  3. Order and ids.  The tokens are ordered by l descending, comparing fp32 VALUES, so -0 and +0 tie.  Equal values are ordered
+ *     by ascending token id; NaN and -inf entries therefore tie with each other and order by id.  top_id[b][j] is the j-th token
+ *     of that order for j < min(n, vocab).  The remaining entries are id = -1, logprob = -inf.
+ *  4. Log-probabilities.  top_logprob[b][j] is the value qpal_token_logprob defines for token top_id[b][j] on this row, and
+ *     lse[b] is that kernel's lse.  Its special cases hold unchanged: no logit above -inf: every log-prob is -inf, lse is -inf,
+ *     ids are 0 .. n-1; +inf logits share the mass, -log(count) each, and every other entry is -inf; a token at -inf gets -inf.
+ *  5. Bitwise guarantees.  Sums run in a fixed order: two launches are bitwise equal.  top_logprob[b][j] and lse[b] are BITWISE
+ *     equal to what qpal_token_logprob returns for token = top_id[b][j] on the same row: the drawn token's entry in the list
+ *     carries exactly the sampler's logprob.
+ *  6. Greedy consequence.  top_id[b][0] equals qpal_sample's greedy token on every row, degenerate rows included.            */
+int qpal_top_logprob(const float *logits_f32, long ld_logits, int rows, int vocab, int n, int *top_id, float *top_logprob,
+                     float *lse, const long long *active, void *stream);
+
 /* SPECULATIVE decoding (csrc/spec.hip): the two ends of a step that feeds, per sequence, its pending token and up to
  * K guessed tokens as ONE segment of a ragged step (§18), draws at every row, and keeps the guesses that equal the draws.
  * Everything is on the device and never read by the host (a captured step is replayed while the state moves); no workspace, no

@@ -11,7 +11,12 @@ written, counts read = 12 bytes per logit.
 at 8 slots with drafts of 4 and 15 one-byte tokens (chains of dependent table reads), and GrammarBank.load of a 301-state automaton
 (upload, compile launch, the check's read) on a synthetic vocabulary of --vocab tokens.
 
+--top-logprobs N [N ...] adds qpal_top_logprob on the same logits, before any processor has touched them, between
+its two yardsticks: qpal_token_logprob (two passes over the row) below and qpal_sample with top_k = N, top_p = 0.9 (eight passes)
+above.  The three launches alternate for three rounds; the figures are the medians.
+
     python perf/sampling_kernels.py [--vocab 128256] [--k 4096] [--rows 1 8 64 128] [--iters 20] [--warmup 5] [--grammar]
+                                    [--top-logprobs 5 20 64]
 """
 import argparse
 import ctypes
@@ -99,6 +104,27 @@ def grammar_launches(table, dev, iters, warmup):
     return res
 
 
+def top_logprob_launches(smp, ctr, tok, ns, iters, warmup):
+    """qpal_top_logprob at every n of ns on smp.logits beside its yardsticks, three alternating rounds each: medians in us"""
+    rows, dev, out = smp.B, smp.device, []
+    lp = torch.zeros(rows, device=dev)
+    for n in ns:
+        ids, top = torch.zeros(rows, n, dtype=torch.int32, device=dev), torch.zeros(rows, n, device=dev)
+        smp.temperature.fill_(1.0); smp.top_k.fill_(n); smp.top_p.fill_(0.9)
+        launches = {"us_top_logprob": lambda: qp.top_logprobs(smp.logits, n, ids=ids, logprob=top, active=ctr),
+                    "us_token_logprob": lambda: qp.token_logprobs(smp.logits, tok, out=lp, active=ctr),
+                    "us_sample_topk_n_p0.9": lambda: qp.sample(smp.logits, smp, ctr, out=tok)}
+        rounds = {name: [] for name in launches}
+        for _ in range(3):
+            for name, fn in launches.items():
+                rounds[name].append(timed(fn, iters, warmup))
+        res = {"n": n, "passes": {"us_top_logprob": 4, "us_token_logprob": 2, "us_sample_topk_n_p0.9": 8}}
+        res.update({name: sorted(v)[1] for name, v in rounds.items()})
+        res["rounds"] = rounds
+        out.append(res)
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--vocab", type=int, default=128256)
@@ -106,6 +132,8 @@ def main(argv=None):
     ap.add_argument("--rows", type=int, nargs="+", default=[1, 8, 64, 128])
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--top-logprobs", type=int, nargs="+", default=[], metavar="N",
+                    help="also time qpal_top_logprob with these list lengths between qpal_token_logprob and qpal_sample(top_k = N, top_p = 0.9)")
     ap.add_argument("--grammar", action="store_true", help="also time the grammar launches (mask beside the processor, rows, advance, load)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -136,6 +164,8 @@ def main(argv=None):
                                 "t0.8_p0.95": (0.8, 0, 0.95), "t0.7_k50_p0.9": (0.7, 50, 0.9)}.items():
             smp.temperature.fill_(t); smp.top_k.fill_(k); smp.top_p.fill_(p)
             res["us_sample_" + name] = timed(lambda: qp.sample(smp.logits, smp, ctr, out=tok), args.iters, args.warmup)
+        if args.top_logprobs:
+            res["top_logprobs"] = top_logprob_launches(smp, ctr, tok, args.top_logprobs, args.iters, args.warmup)
         # the logit processor on these logits, in place; the stream yardstick reads as many bytes as it reads and writes
         slots = torch.arange(rows, dtype=torch.int32, device=dev)
         for name in ("neutral", "all_stages"):

@@ -26,7 +26,9 @@ Layout:
                    acceptance and the state update, all on the device; reference_spec_draft / reference_spec_accept: the contracts
   sampling.py      lm_head_logits (final norm + lm_head for up to 128 rows), sample / Sampler (temperature, top-k, top-p, seeded
                    draw; per-slot parameters on the device), reference_draw (the draw's contract in numpy fp64);
-                   token_logprobs (log softmax of a row at one token, csrc/logprob.hip) and its contract reference_logprob
+                   token_logprobs (log softmax of a row at one token, csrc/logprob.hip) and its contract reference_logprob;
+                   top_logprobs (the n likeliest tokens of a row and their log-probabilities, csrc/top_logprob.hip) and its
+                   contract reference_top_logprobs
   logits.py        logit processors between the lm_head and the draw: LogitProcessor (per-slot token mask, sparse bias, repetition /
                    presence / frequency penalties and token counts on the device), process / observe (csrc/logit_proc.hip) and the
                    contract reference_process (numpy fp32, bit for bit)
@@ -80,6 +82,7 @@ from . import paging  # noqa: F401
 from .paging import PagedKVCache, SharedPrefix  # noqa: F401
 from . import sampling  # noqa: F401
 from .sampling import Sampler, lm_head_logits, reference_draw, reference_logprob, sample, token_logprobs  # noqa: F401
+from .sampling import reference_top_logprobs, top_logprobs  # noqa: F401
 from . import logits  # noqa: F401
 from .logits import LogitProcessor, reference_process  # noqa: F401
 from . import grammar  # noqa: F401

@@ -15,7 +15,10 @@ own (70B: 8192).  `generic=True` runs a batch of one the way every larger batch 
 
 With `sampler=sampling.Sampler(B, vocab, device, ...)` the step ends in `qpal_lm_head_logits` + `qpal_sample` at every B instead of
 an argmax: out_tok[b] is drawn with slot b's temperature / top-k / top-p / seed and the counter pos[b] (DESIGN.md §14);
-sampler.logits holds the step's logits.
+sampler.logits holds the step's logits.  A sampler built with logprobs=True adds `qpal_token_logprob` on the drawn tokens
+(sampler.logprob), one built with top_logprobs=n `qpal_top_logprob` behind it (sampler.top_id / sampler.top_logprob
+[B, n]: the n likeliest tokens of every row that drew): one more launch each, in every step class below, and `Score(...,
+top_logprobs=n)` has the lists at every scored position.
 
 `Prefill` takes a prompt into ONE slot of the same caches: the batch-B layer with rows = consecutive positions of one sequence,
 in chunks of at most 128 rows, with `prefill_attention` (causal, rows appended to the slot's cache) in the attention's place.
@@ -262,7 +265,8 @@ class _Rows:
 
     def _sample_tail(self, h32, smp, ctr, out_tok, row_slot=None, fed=None, gslot=None):
         """final norm + lm_head of every row of h32 into smp.logits, then one draw per row with the counters ctr: two launches; with
-        smp.logprob a third, the log-probability of the tokens just drawn (rows with ctr < 0 drew nothing and keep theirs).  With a
+        smp.logprob a third, the log-probability of the tokens just drawn (rows with ctr < 0 drew nothing and keep theirs); with
+        smp.top_id one more behind it, the likeliest tokens of every row that drew and their log-probabilities.  With a
         processor (row_slot: the rows' slots) two launches in between: the tokens `fed` to the rows are counted where given, and the
         logits are processed in place — the draw and the log-probabilities are those of the processed logits.  With a grammar two
         more: the mask of every row's automaton state behind the processor, and behind the draw the advance of the states by the
@@ -280,6 +284,8 @@ class _Rows:
             gram_mod.grammar_advance(self.grammar, out_tok, active=ctr, slot0=gslot or 0)
         if smp.logprob is not None:
             sampling.token_logprobs(smp.logits, out_tok, out=smp.logprob, active=ctr)
+        if smp.top_id is not None:
+            sampling.top_logprobs(smp.logits, smp.top_id.shape[1], ids=smp.top_id, logprob=smp.top_logprob, active=ctr)
 
     def _argmax_tail(self, rows32, out_tok):
         """final norm + lm_head + argmax of the rows: one launch (ONE row) where the class found the kernel available, else torch ops"""
@@ -303,6 +309,8 @@ class DecodeStep(_Rows):
     becomes lm_head logits of all B rows + one draw per active row with the counter pos[b] (two launches); None: argmax.  A sampler
     built with logprobs=True adds a third launch: sampler.logprob[b] = the log-probability of out_tok[b] under the plain softmax of
     sampler.logits[b], for the rows that drew (pos[b] >= 0 — the positions are the launch's `active` vector; other slots keep theirs).
+    A sampler built with top_logprobs=n adds one more behind it: sampler.top_id[b] / sampler.top_logprob[b] = the n likeliest tokens
+    of sampler.logits[b] — the logits the draw saw — and their log-probabilities, for the same rows (sampling.top_logprobs).
     block_table: int32 [B, max_pages] on the device — kcache / vcache are then the per-layer page pools [num_pages, nkv, page_size, hd]
     of a paged cache, context = max_pages * page_size, and the attention launch is paged_decode_attention (a batch of one as well:
     the fused single-sequence kernel reads contiguous caches only).  shared_prefix: paging.SharedPrefix (cache.prefix, with block_table=
@@ -367,13 +375,15 @@ class DecodeStep(_Rows):
         """kernel launches of one step: per layer q|k|v, attention, o, up|gate, SwiGLU rotation, down (+ a rotation in front of
         q|k|v, o and up|gate where the GEMV cannot rotate; - the SwiGLU rotation where down_proj's staging runs it); + the norm /
         lm_head / argmax launch, or the lm_head logits and the draw with a sampler, + the log-probability launch of a sampler with
-        logprobs (the embedding row copy is a memcpy node); with adapters + 4 per layer, one per projection group; with a
+        logprobs, + the top-N launch of a sampler with top_logprobs (the embedding row copy is a memcpy node); with adapters + 4
+        per layer, one per projection group; with a
         processor + 2, observe and process; with a grammar + 2, mask and advance; with shared_prefix + 1 per layer, the prefix
         phase in front of the attention launch"""
         per_layer = (5 if self.ug_il and self.ug_il[0][2] else 6) if self.rot_in_gemv else 9
         per_layer += 1 if getattr(self, "shared_prefix", None) is not None else 0
         per_layer += 4 if getattr(self, "adapters", None) is not None else 0  # (arithmetic on the configuration: stand-ins may lack it)
         tail = 1 if self.sampler is None else (2 if self.sampler.logprob is None else 3)
+        tail += 1 if getattr(self.sampler, "top_id", None) is not None else 0
         tail += 2 if getattr(self, "processor", None) is not None else 0
         tail += 2 if getattr(self, "grammar", None) is not None else 0
         return per_layer * len(self.layers) + tail
@@ -444,7 +454,8 @@ class Prefill(_Rows):
     sampler: the sampling.Sampler of the DecodeStep whose caches this fills (one slot per sequence of the caches).  The token is then
     drawn with slot `slot`'s parameters and the counter of the last prompt row's position, pos0 + N - 1 (computed on the device):
     the counter a DecodeStep would have used had it fed that token.  sampler.logits[slot] holds the logits, and with a sampler
-    built with logprobs=True sampler.logprob[slot] the token's log-probability.
+    built with logprobs=True sampler.logprob[slot] the token's log-probability, with top_logprobs=n sampler.top_id[slot] /
+    sampler.top_logprob[slot] the n likeliest tokens of those logits (one more launch each).
 
     block_table: int32 [B, max_pages] — kcache / vcache are the per-layer page pools of a paged cache, the slot's row block_table[slot]
     addresses them (paged_prefill_attention), context = max_pages * page_size.  The caller has reserved pages for positions pos0 ..
@@ -547,10 +558,11 @@ class Score(Prefill):
     last row has no next token: its logits are computed, its row of the log-prob launch is inactive.  The slot is left as Prefill
     leaves it: a DecodeStep can continue at position pos0 + N.  The lm_head must suit qpal_lm_head_logits (a sampler's demands).
     block_table: as for Prefill (a paged cache; the caller reserves the slot's pages for pos0 .. pos0 + N - 1).  adapters: as for
-    Prefill."""
+    Prefill.  top_logprobs=n (1 .. 64): one `qpal_top_logprob` launch more per chunk; sc.top_id int32 / sc.top_logprob fp32 [N - 1, n]
+    are then the n likeliest tokens at every scored position and their log-probabilities (views of max_tokens x n buffers, like lp)."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, max_tokens=None, block_table=None,
-                 adapters=None):
+                 adapters=None, top_logprobs=0):
         self._check_lm_head("Score", embed, lm_head)
         super().__init__(layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=chunk, native_lm_head=False,
                          block_table=block_table, adapters=adapters)
@@ -563,6 +575,14 @@ class Score(Prefill):
         self._lp = torch.zeros(self.max_tokens, dtype=torch.float32, device=dev)
         self._rank = torch.zeros(self.max_tokens, dtype=torch.int32, device=dev)
         self.logits, self.rank = self._logits[:0], self._rank[:0]
+        self.top_n = int(top_logprobs or 0)
+        if not 0 <= self.top_n <= 64:
+            raise nat.QpalError(f"Score: top_logprobs must be in 0 .. 64, got {top_logprobs}")
+        self.top_id = self.top_logprob = None
+        if self.top_n:
+            self._top_id = torch.full((self.max_tokens, self.top_n), -1, dtype=torch.int32, device=dev)
+            self._top_logprob = torch.full((self.max_tokens, self.top_n), float("-inf"), dtype=torch.float32, device=dev)
+            self.top_id, self.top_logprob = self._top_id[:0], self._top_logprob[:0]
 
     def __call__(self, tokens, slot=0, pos0=0):
         N = self._begin(tokens, slot, pos0, least=2)
@@ -575,7 +595,12 @@ class Score(Prefill):
             self.logits = self._logits[:n]
             sampling.lm_head_logits(h32, self.norm.weight, self.norm.eps, self.lm_head, out=self.logits)
             sampling.token_logprobs(self.logits, self._targets[c:c + n], out=self._lp[c:c + n], rank=self._rank[c:c + n])
+            if self.top_n:  # (the row without a target is inactive here as well)
+                sampling.top_logprobs(self.logits, self.top_n, ids=self._top_id[c:c + n], logprob=self._top_logprob[c:c + n],
+                                      active=self._targets[c:c + n])
         self.rank = self._rank[:N - 1]
+        if self.top_n:
+            self.top_id, self.top_logprob = self._top_id[:N - 1], self._top_logprob[:N - 1]
         return self._lp[:N - 1]
 
     def nll(self, tokens, slot=0, pos0=0):
@@ -599,7 +624,8 @@ class RaggedStep(_Rows):
     sampler: the sampling.Sampler of the caches' slots; segment s draws with slot seq[s]'s parameters (gathered on the device into
     rs.draw, a Sampler of `segments` rows the step owns) and the counter of its last row's position, pos0[s] + rows of s - 1 —
     the draw Prefill or DecodeStep would have made.  None: argmax.  rs.draw.logits [segments, vocab] holds the logits, and with a
-    sampler built with logprobs=True rs.draw.logprob the drawn tokens' log-probabilities.
+    sampler built with logprobs=True rs.draw.logprob the drawn tokens' log-probabilities, with top_logprobs=n rs.draw.top_id /
+    rs.draw.top_logprob [segments, n] the n likeliest tokens per segment (an inactive segment keeps its list).
 
     block_table: int32 [B, max_pages] — a paged cache, as for DecodeStep; the caller has reserved the pages of every position the
     step writes.
@@ -629,9 +655,10 @@ class RaggedStep(_Rows):
         self._no_adapter = torch.full((self.rows,), -1, dtype=torch.int32, device=dev)
         self.seq = self.row0 = self.pos0 = None  # the descriptors of the call under way
         self.attn_ws = ragged_workspace(self.rows, self.segments, self.nq, self.nkv, self.head_dim, self.context, dev)
-        self._setup_tail(lm_head.shape[0], dev, sampler is not None and sampler.logprob is not None)
+        top_n = 0 if sampler is None or sampler.top_id is None else sampler.top_id.shape[1]
+        self._setup_tail(lm_head.shape[0], dev, sampler is not None and sampler.logprob is not None, top_n)
 
-    def _setup_tail(self, vocab, dev, logprobs):
+    def _setup_tail(self, vocab, dev, logprobs, top_n):
         """what the tail of the step owns: per SEGMENT its last row of the stream, that row's counter, a draw and a token"""
         S = self.segments
         self.out_tok = torch.zeros(S, dtype=torch.int64, device=dev)
@@ -639,7 +666,7 @@ class RaggedStep(_Rows):
         self._inactive = torch.full((S,), -1, dtype=torch.int64, device=dev)
         self.last32 = torch.zeros(S, self.h32.shape[1], dtype=torch.float32, device=dev)  # each segment's last row of the stream
         # the draw's per-segment parameters: greedy, or gathered from the sampler's slots seq[s] in every call
-        self.draw = sampling.Sampler(S, vocab, dev, temperature=0.0, logprobs=logprobs)
+        self.draw = sampling.Sampler(S, vocab, dev, temperature=0.0, logprobs=logprobs, top_logprobs=top_n)
 
     def _attention(self, i, q, k, v, out):
         kc, vc = self.kcache[i], self.vcache[i]
@@ -746,7 +773,10 @@ class SpeculativeStep(RaggedStep):
     rows: the step's rows, B <= rows <= 128 (default min(128, B * (draft + 1))); drafts are cut where the rows are full.  sampler:
     the sampling.Sampler of the caches' slots — row r draws with its slot's parameters (gathered into ss.draw, a Sampler of `rows`
     rows) and the counter of its position; None: greedy.  A sampler built with logprobs=True: the call returns (out_tok, n_out,
-    logprob fp32 [B, draft + 1]), the emitted tokens' log-probabilities, from one token_logprobs launch on the rows.
+    logprob fp32 [B, draft + 1]), the emitted tokens' log-probabilities, from one token_logprobs launch on the rows.  A sampler
+    built with top_logprobs=n: one top_logprobs launch on the rows next to it, gathered the same way into ss.out_top_id int32 /
+    ss.out_top_logprob fp32 [B, draft + 1, n] — entry (b, j), j < n_out[b], is the list of the row that emitted out_tok[b, j]; the
+    call's return tuple stays as it is.
     No cache rollback: the next step starts at the new pending position and rewrites the K / V rows a rejected draft left before
     anything reads them.  block_table: a paged cache as for DecodeStep; the caller has reserved the pages of min(limit, n_tok +
     draft) positions of every slot before the call.  adapters: as for RaggedStep (the rows of slot b run with slot b's adapter).
@@ -799,13 +829,15 @@ class SpeculativeStep(RaggedStep):
             self._obs_active = torch.zeros(B * (K + 1), dtype=i64, device=dev)
             self._lane1 = torch.arange(1, K + 2, dtype=i64, device=dev)
 
-    def _setup_tail(self, vocab, dev, logprobs):
+    def _setup_tail(self, vocab, dev, logprobs, top_n):
         """a draw at every ROW and up to draft + 1 tokens per slot: no last rows, no per-segment counters"""
         B, K = self.segments, self.draft_len
         self.drawn = torch.zeros(self.rows, dtype=torch.int64, device=dev)
         self.out_tok = torch.zeros(B, K + 1, dtype=torch.int64, device=dev)
-        self.draw = sampling.Sampler(self.rows, vocab, dev, temperature=0.0, logprobs=logprobs)  # greedy unless gathered
+        self.draw = sampling.Sampler(self.rows, vocab, dev, temperature=0.0, logprobs=logprobs, top_logprobs=top_n)  # greedy unless gathered
         self.out_logprob = torch.zeros(B, K + 1, dtype=torch.float32, device=dev) if logprobs else None
+        self.out_top_id = torch.full((B, K + 1, top_n), -1, dtype=torch.int32, device=dev) if top_n else None
+        self.out_top_logprob = torch.full((B, K + 1, top_n), float("-inf"), dtype=torch.float32, device=dev) if top_n else None
         self._lane = torch.arange(K + 1, dtype=torch.int64, device=dev)
 
     def hidden(self):
@@ -862,10 +894,16 @@ class SpeculativeStep(RaggedStep):
         if self.sampler is not None:
             self._gather_draw(self.row_slot.to(torch.int64).clamp(min=0))
         sampling.sample(self.draw.logits, self.draw, self.row_ctr, out=self.drawn)
+        if self.out_logprob is not None or self.out_top_id is not None:  # the rows that may emit slot b's tokens: row0[b] + 0 .. draft
+            rows = (self.row0[:-1].to(torch.int64)[:, None] + self._lane[None, :]).clamp(max=self.rows - 1).reshape(-1)
         if self.out_logprob is not None:
             sampling.token_logprobs(self.draw.logits, self.drawn, out=self.draw.logprob, active=self.row_ctr)
-            rows = (self.row0[:-1].to(torch.int64)[:, None] + self._lane[None, :]).clamp(max=self.rows - 1)
-            torch.index_select(self.draw.logprob, 0, rows.reshape(-1), out=self.out_logprob.view(-1))
+            torch.index_select(self.draw.logprob, 0, rows, out=self.out_logprob.view(-1))
+        if self.out_top_id is not None:
+            n = self.draw.top_id.shape[1]
+            sampling.top_logprobs(self.draw.logits, n, ids=self.draw.top_id, logprob=self.draw.top_logprob, active=self.row_ctr)
+            torch.index_select(self.draw.top_id, 0, rows, out=self.out_top_id.view(-1, n))
+            torch.index_select(self.draw.top_logprob, 0, rows, out=self.out_top_logprob.view(-1, n))
         spec.spec_accept(self.tokens, self.drawn, self.seq, self.row0, self.hist, self.n_tok, self.limit, self.eos, self.out_tok,
                          self.n_out, self.n_acc)
         if self.grammar is not None:

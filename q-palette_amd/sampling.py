@@ -13,6 +13,11 @@ temperature / top-k / top-p / seeded draw (``qpal_sample``, csrc/sample.hip), on
 ``Sampler(..., logprobs=True)`` makes that the third launch of the tail (``smp.logprob``); ``decoder.Score`` runs it on every row of
 a prompt.  ``reference_logprob`` is its contract in numpy fp64.
 
+    ids, lp = top_logprobs(smp.logits, 5)     # int32 / fp32 [B, 5]: the 5 likeliest tokens per row, one launch (``qpal_top_logprob``)
+
+``Sampler(..., top_logprobs=n)`` makes that one more launch of the tail (``smp.top_id``, ``smp.top_logprob``), ``decoder.Score(...,
+top_logprobs=n)`` runs it on every row; ``reference_top_logprobs`` is its contract.
+
 The draw is specified exactly (include/qpal.h); ``reference_draw`` restates it in numpy fp64 with its own Philox.
 It is the specification the tests hold the kernel to: CPU only, no torch.cuda, no library call.
 """
@@ -129,6 +134,19 @@ def reference_logprob(logits_row, token):
     return (lt - lse if lt > -np.inf else -np.inf), lse, rank
 
 
+def reference_top_logprobs(logits_row, n):
+    """The contract of qpal_top_logprob for one row, in fp64 on clean_logits(row): (ids int32 [n], logprob float64 [n], lse).  The
+    tokens by value descending (fp32 values: -0 and +0 tie; NaN is -inf), equal values by ascending id; entry j < min(n, vocab) is
+    the j-th of them with reference_logprob's value for it, the rest are id -1, logprob -inf."""
+    l = clean_logits(logits_row)
+    n = int(n)
+    order = np.argsort(-l.astype(np.float64), kind="stable")[:n]  # stable: equal values keep their ascending ids
+    ids, logprob = np.full(n, -1, dtype=np.int32), np.full(n, -np.inf, dtype=np.float64)
+    ids[:order.shape[0]] = order
+    logprob[:order.shape[0]] = [reference_logprob(l, t)[0] for t in order]
+    return ids, logprob, reference_logprob(l, 0)[1]
+
+
 # ---------------------------------------------------------------------------------------------------------------- GPU side
 
 def _torch():
@@ -239,15 +257,53 @@ def token_logprobs(logits, tokens, out=None, lse=None, rank=None, vocab=None, ac
     return out
 
 
+def top_logprobs(logits, n, ids=None, logprob=None, lse=None, vocab=None, active=None):
+    """(ids int32 [rows, n], logprob fp32 [rows, n]): the n <= 64 likeliest tokens of every row of logits fp32 [rows, >= vocab]
+    (contiguous rows; vocab defaults to the width) and their log-probabilities under the plain softmax of the row, likeliest first,
+    equal values by ascending id; entries past the vocabulary are id -1, logprob -inf.  Every value is bitwise what token_logprobs
+    gives for that token on the same row.  A row whose active[row] < 0 (active: an optional int64 [rows], a decode step's positions)
+    keeps what its entries held.  lse fp32 [rows], where given, receives the row's log-sum-exp.  ids / logprob: contiguous [rows, n]
+    tensors to write into.  Launches on the current stream (``qpal_top_logprob``, csrc/top_logprob.hip); no host read."""
+    torch = _torch()
+    from . import _native
+    who, QpalError = "top_logprobs", _native.QpalError
+    if logits.dtype != torch.float32 or not logits.is_cuda or logits.dim() != 2 or logits.stride(1) != 1:
+        raise QpalError(f"{who}: logits must be an fp32 device tensor [rows, vocab] with contiguous rows")
+    rows, dev, n = logits.shape[0], logits.device, int(n)
+    vocab = logits.shape[1] if vocab is None else int(vocab)
+    ld = logits.stride(0) if rows > 1 else logits.shape[1]
+    if not 1 <= rows <= 128 or not 1 <= vocab <= logits.shape[1] or ld < vocab:
+        raise QpalError(f"{who}: rows must be in 1 .. 128 and 1 <= vocab <= the row width, got {list(logits.shape)}, vocab {vocab}")
+    if not 1 <= n <= 64:
+        raise QpalError(f"{who}: n must be in 1 .. 64, got {n}")
+    if ids is None:
+        ids = torch.full((rows, n), -1, dtype=torch.int32, device=dev)
+    if logprob is None:
+        logprob = torch.full((rows, n), float("-inf"), dtype=torch.float32, device=dev)
+    for t, name, dtype in ((ids, "ids", torch.int32), (logprob, "logprob", torch.float32)):
+        if t.dtype != dtype or t.shape != (rows, n) or t.device != dev or not t.is_contiguous():
+            raise QpalError(f"{who}: {name} must be a contiguous {dtype} [{rows}, {n}] tensor on {dev}")
+    ptrs = [None if lse is None else _param(lse, "lse", torch.float32, rows, dev, who),
+            None if active is None else _param(active, "active", torch.int64, rows, dev, who)]
+    with torch.cuda.device(dev):
+        rc = _native.lib().qpal_top_logprob(logits.data_ptr(), ld, rows, vocab, n, ids.data_ptr(), logprob.data_ptr(), *ptrs,
+                                            torch.cuda.current_stream(dev).cuda_stream)
+    _native.check(rc, "qpal_top_logprob")
+    return ids, logprob
+
+
 class Sampler:
     """Per-slot sampling parameters of B sequences, on the device: temperature fp32, top_k int32, top_p fp32, seed int64, each [B],
     and the logits buffer fp32 [B, vocab] the step's lm_head writes.  Scalars broadcast; sequences of B values are taken per slot.
     temperature <= 0 or top_k == 1: greedy; top_k <= 0: no top-k; top_p >= 1 or <= 0: no top-p.  A captured step reads the tensors
     when it runs: ``set`` between replays changes the next draw.  logprobs=True: the sampler also owns logprob fp32 [B], and a step
     with this sampler writes the log-probability of each token it draws there (plain softmax of the logits, whatever the filter:
-    token_logprobs; one more launch); otherwise logprob is None."""
+    token_logprobs; one more launch); otherwise logprob is None.  top_logprobs=n (1 .. 64): the sampler also owns top_id int32 [B, n]
+    and top_logprob fp32 [B, n], and a step with this sampler writes the n likeliest tokens of each row that drew and their
+    log-probabilities there (top_logprobs, under the same plain softmax of the logits the draw saw; one more launch); 0 or unset:
+    both are None."""
 
-    def __init__(self, B, vocab, device, temperature=1.0, top_k=0, top_p=1.0, seed=0, logprobs=False):
+    def __init__(self, B, vocab, device, temperature=1.0, top_k=0, top_p=1.0, seed=0, logprobs=False, top_logprobs=0):
         torch = _torch()
         from ._native import QpalError
         if not 1 <= int(B) <= 128 or int(vocab) < 1:
@@ -264,6 +320,11 @@ class Sampler:
         self.top_p, self.seed = full(top_p, torch.float32), full(seed, torch.int64)
         self.logits = torch.zeros(self.B, self.vocab, dtype=torch.float32, device=self.device)
         self.logprob = torch.zeros(self.B, dtype=torch.float32, device=self.device) if logprobs else None
+        n = int(top_logprobs or 0)
+        if not 0 <= n <= 64:
+            raise QpalError(f"Sampler: top_logprobs must be in 0 .. 64, got {top_logprobs}")
+        self.top_id = torch.full((self.B, n), -1, dtype=torch.int32, device=self.device) if n else None
+        self.top_logprob = torch.full((self.B, n), float("-inf"), dtype=torch.float32, device=self.device) if n else None
 
     def set(self, slot, temperature=None, top_k=None, top_p=None, seed=None):
         """write one slot's parameters (those given)"""
@@ -281,4 +342,6 @@ class Sampler:
         s = slice(int(slot), int(slot) + 1)
         v.temperature, v.top_k, v.top_p, v.seed, v.logits = self.temperature[s], self.top_k[s], self.top_p[s], self.seed[s], self.logits[s]
         v.logprob = None if self.logprob is None else self.logprob[s]
+        v.top_id = None if self.top_id is None else self.top_id[s]
+        v.top_logprob = None if self.top_logprob is None else self.top_logprob[s]
         return v
