@@ -183,6 +183,11 @@ class _Rows:
                                 "contiguous 16-byte aligned lm_head")
 
     @staticmethod
+    def _has_argmax_kernel(embed, lm_head):
+        """qpal_lm_head_argmax serves these hidden widths and a 16-byte aligned lm_head; elsewhere `_argmax_tail` runs torch ops"""
+        return embed.shape[1] in (2048, 4096, 8192) and lm_head.data_ptr() % 16 == 0
+
+    @staticmethod
     def _check_sampler(sampler, B, embed, lm_head):
         if sampler is None:
             return None
@@ -305,8 +310,10 @@ class DecodeStep(_Rows):
     embed / lm_head fp16 [vocab, H]; norm: the final RMSNorm; kcache / vcache: per-layer fp16 or float8_e4m3fn [B, nkv, context, hd]; inv_freq fp32
     [hd / 2]; tok, pos, out_tok int64 [B] (pos[b] outside the cache: sequence b is inactive).  The caller owns the caches and
     tok / pos / out_tok and may write them between replays of a captured step.  swiglu_epilogue, k28_fusion, native_lm_head,
-    split_attention switch single fusions of the batch-1 step off (profiling).  sampler: a sampling.Sampler of B slots — the tail
-    becomes lm_head logits of all B rows + one draw per active row with the counter pos[b] (two launches); None: argmax.  A sampler
+    split_attention switch single fusions of the batch-1 step off (profiling).  qpal_lm_head_argmax serves the hidden widths
+    2048, 4096 and 8192: on any other width the batch-1 step ends in the torch tail every larger batch has, as Prefill does.
+    sampler: a sampling.Sampler of B slots — the tail becomes lm_head logits of all B rows + one draw per active row with the
+    counter pos[b] (two launches); None: argmax.  A sampler
     built with logprobs=True adds a third launch: sampler.logprob[b] = the log-probability of out_tok[b] under the plain softmax of
     sampler.logits[b], for the rows that drew (pos[b] >= 0 — the positions are the launch's `active` vector; other slots keep theirs).
     A sampler built with top_logprobs=n adds one more behind it: sampler.top_id[b] / sampler.top_logprob[b] = the n likeliest tokens
@@ -337,7 +344,8 @@ class DecodeStep(_Rows):
             raise nat.QpalError("DecodeStep: shared_prefix needs a paged cache (block_table=cache.table)")
         self.batch1 = B == 1 and not generic
         super().__init__("DecodeStep", layers, embed, norm, lm_head, kcache, vcache, inv_freq, B, sampler, block_table, slots=B,
-                         native_argmax=self.batch1 and native_lm_head, adapters=adapters, processor=processor, grammar=grammar)
+                         native_argmax=self.batch1 and native_lm_head and self._has_argmax_kernel(embed, lm_head), adapters=adapters,
+                         processor=processor, grammar=grammar)
         self._row_slot = None if processor is None and grammar is None else torch.arange(B, dtype=torch.int32, device=embed.device)  # row = slot
         if adapters is not None:
             self.row_adapter, swiglu_epilogue = adapters.slot_adapter, False  # row = slot
@@ -479,7 +487,7 @@ class Prefill(_Rows):
         self.chunk = int(chunk)
         dev, H = embed.device, embed.shape[1]
         super().__init__("Prefill", layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.chunk, sampler, block_table,
-                         native_argmax=native_lm_head and H in (2048, 4096, 8192) and lm_head.data_ptr() % 16 == 0, adapters=adapters,
+                         native_argmax=native_lm_head and self._has_argmax_kernel(embed, lm_head), adapters=adapters,
                          processor=processor, grammar=grammar)
         self._row_slot = None if processor is None and grammar is None else torch.zeros(1, dtype=torch.int32, device=dev)  # the call's slot
         self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
