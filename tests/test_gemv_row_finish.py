@@ -8,6 +8,10 @@ workgroups, batches 1, 2, 3 and 8, three jobs in one launch, launches of more th
 rotating kernels' SwiGLU finish.  Every output against the oracle's float64 GEMV under the project's bound
 |err| <= 1e-5 * sum |w x| (tests/test_gpu_parity.py), and bit-identical between two calls.
 
+The exact pass: every launch of the file runs a second time (`exact` in its dict) on exactly summable inputs — the codebook redrawn
+from the dyadic grid of gemv_reference.py, integer x, integer residuals — and must then EQUAL the float64 sum: no order of the
+finish's additions rounds, so the two-call equality holds for `accumulate` on shared rows too.
+
 The planner decides the runs, so every test reads the plan of its launches through qpal_plan_gemv and asserts the run lengths
 it is there for; test_census_of_run_lengths asserts that the file as a whole covers 1, 2, 3, 4, 5, 8, 15, 16 and a shared row.
 
@@ -23,16 +27,25 @@ import sys
 import numpy as np
 import pytest
 
+import gemv_reference as gx
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GEMV_RTOL_ABS = 1e-5  # times sum |w x|: the project's bound (tests/test_gpu_parity.py)
 TCQ, TCOMB = "tcq_6_none_0.9", "tcomb_6_7_0.5_none_0.9"
 Z, ACC, ACT = 1, 2, 4  # qpal_plan_gemv job flags: output declared zeroed, accumulate, SwiGLU epilogue
 
 
-def _launch(layers, k, n=1, mode="plain", runs=(), shared=None, rounds=False):
+def _launch(layers, k, n=1, mode="plain", runs=(), shared=None, rounds=False, exact=False):
     """One GEMV launch of the file: layers [(qstr, m, seed)], mode plain / zeroed / accumulate; what its plan must show: these run
-    lengths among its lead entries, a shared row (or none), more items than workgroups."""
-    return dict(layers=[list(l) for l in layers], k=k, n=n, mode=mode, runs=list(runs), shared=shared, rounds=rounds)
+    lengths among its lead entries, a shared row (or none), more items than workgroups.  exact: on exactly summable inputs."""
+    return dict(layers=[list(l) for l in layers], k=k, n=n, mode=mode, runs=list(runs), shared=shared, rounds=rounds, exact=exact)
+
+
+def _exact_twin(la):
+    return dict(la, exact=True)
+
+
+EXACT_RESIDUAL_MAX = 64  # |integer residual| of the exact pass's accumulate launches
 
 
 def _one(st, n=1):
@@ -62,6 +75,8 @@ FORCED = {
                   + [_launch([(TCQ, 64000, 180)], 128, runs=[1], shared=False, rounds=True),
                      _launch([(TCQ, 9600, 181)], 384, n=2, runs=[3], shared=False, rounds=True)]),
 }
+# every child runs its launches a second time on exact inputs (the same plans)
+FORCED = {name: (env, launches + [_exact_twin(la) for la in launches]) for name, (env, launches) in FORCED.items()}
 
 
 # ---------------------------------------------------------------------------------------------- the plan of a launch
@@ -124,10 +139,18 @@ def _child(name, plan_only, tmp_path):
 
 # ---------------------------------------------------------------------------------------------- running a launch
 def _infos(qp, la):
+    if la.get("exact"):  # the same codes, the codebook redrawn from the grid
+        return [gx.exact_info(la["k"], m, q, seed=seed, codebook_seed=13) for q, m, seed in la["layers"]]
     return [qp.mem_op.dummy_linear_info(la["k"], m, q, seed=seed, codebook_seed=13, device="cpu") for q, m, seed in la["layers"]]
 
 
 def _x_and_residuals(la):
+    if la.get("exact"):  # integer x, integer residuals; the budget is asserted before anything is launched
+        amax = gx.amax_for(la["k"])
+        gx.assert_budget(la["k"], xmax=amax, base=EXACT_RESIDUAL_MAX if la["mode"] == "accumulate" else 0.0)
+        x = gx.exact_x(la["n"], la["k"], seed=la["k"] * 8 + la["n"], amax=amax)
+        res = [gx.exact_base(la["n"], m, seed=seed, bmax=EXACT_RESIDUAL_MAX) for _, m, seed in la["layers"]]
+        return x, res
     rng = np.random.default_rng(la["k"] * 8 + la["n"])
     x = rng.standard_normal((la["n"], la["k"])).astype(np.float16)
     res = [rng.standard_normal((la["n"], m)).astype(np.float32) * 4.0 for _, m, _ in la["layers"]]
@@ -168,6 +191,13 @@ def _check(qp, oracle, la, results):
     onto a live fp32 value r: one more rounding of r + y — two where two workgroups add their halves, (r + a) + b — each at most
     2^-24 (|r| + sum |w x|)."""
     x, res = _x_and_residuals(la)
+    if la.get("exact"):
+        for (q, m, _), info, (y, y2), r in zip(la["layers"], _infos(qp, la), results, res):
+            want = gx.expected(_oracle_weight(oracle, q, info, m, la["k"]), x, base=r if la["mode"] == "accumulate" else None)
+            assert gx.same(y, want), (la, gx.describe_difference(y, want))
+            # nothing rounds, whatever the order: two calls agree on shared rows under accumulate as well
+            assert np.array_equal(y.view(np.uint32), y2.view(np.uint32)), (la, "two calls differ", gx.describe_difference(y2, y))
+        return
     for (q, m, _), info, (y, y2), r in zip(la["layers"], _infos(qp, la), results, res):
         # (two workgroups adding their halves of a shared row onto a LIVE value, (r + a) + b or (r + b) + a, round differently:
         # only there two calls may differ in the last bit — onto zeros, 0 + a + b, the order does not matter)
@@ -205,7 +235,8 @@ def oracle():
 
 def _in_process(qp, oracle, la):
     _check_plan(la, _plan_of(qp._native.lib(), la))
-    _check(qp, oracle, la, _run(qp, la))
+    for la in (la, _exact_twin(la)):
+        _check(qp, oracle, la, _run(qp, la))
 
 
 @pytest.mark.parametrize("la", ONE_ROW, ids=lambda la: f"k{la['k']}")
