@@ -50,10 +50,13 @@ from ._native import QpalError
 def attention_workspace(B, nq, nkv, hd, max_len, device):
     """The zero-filled workspace ``decode_attention`` needs for up to B sequences and caches of up to max_len positions (same nq,
     nkv, hd), or None where no launch of that shape needs one.  Keep it across launches: the kernel leaves it as it found it."""
-    n = _native.lib().qpal_attn_batch_ws_bytes(int(B), int(nq), int(nkv), int(hd), int(max_len))
-    if n <= 0:
-        return None
-    return torch.zeros((n + 3) // 4, dtype=torch.float32, device=device)
+    return _workspace("qpal_attn_batch_ws_bytes", device, B, nq, nkv, hd, max_len)
+
+
+def _workspace(sizer, device, *shape):
+    """the zero-filled workspace of the launches whose bytes `sizer` gives for `shape`, or None where none of them needs one"""
+    n = getattr(_native.lib(), sizer)(*(int(x) for x in shape))
+    return torch.zeros((n + 3) // 4, dtype=torch.float32, device=device) if n > 0 else None
 
 
 _CACHE_ENTRY = {torch.float16: "", torch.float8_e4m3fn: "_kv8"}  # cache dtype -> suffix of the C entry point
@@ -114,41 +117,23 @@ def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=Non
 def _decode(who, entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, paged, groups=None):
     """the checks and the launch the decode entry points share; paged: None, or the arguments that take max_len's place; groups: None,
     or the G of a shared-prefix launch (its workspace is shared_prefix_workspace's)"""
-    if q.dim() != 2 or q.shape[0] != B or q.shape[1] % hd:
-        raise QpalError(f"{who}: q must have shape [{B}, nq*{hd}], got {list(q.shape)}")
-    nq = q.shape[1] // hd
-    ld = _rows(q, "q", B, nq * hd, who)
-    for name, t in (("k", k), ("v", v)):
-        if _rows(t, name, B, nkv * hd, who) != ld and B > 1:
-            raise QpalError(f"{who}: q, k and v must share one row stride")
-    if pos.dtype != torch.int64 or pos.shape != (B,) or pos.device != kcache.device or not pos.is_contiguous():
-        raise QpalError(f"{who}: pos must be a contiguous int64 [{B}] tensor on {kcache.device}")
-    if inv_freq.dtype != torch.float32 or inv_freq.numel() != hd // 2 or inv_freq.device != kcache.device or not inv_freq.is_contiguous():
-        raise QpalError(f"{who}: inv_freq must be a contiguous fp32 [{hd // 2}] tensor on {kcache.device}")
-    if any(t.device != kcache.device for t in (q, k, v)):
-        raise QpalError(f"{who}: every tensor must be on the caches' device")
-    if out is None:
-        out = torch.empty(B, nq * hd, dtype=torch.float16, device=kcache.device)
-    elif out.dtype != torch.float16 or out.dim() != 2 or out.shape != (B, nq * hd) or out.stride(1) != 1 or out.device != kcache.device:
-        raise QpalError(f"{who}: out must be fp16 [{B}, {nq * hd}] with contiguous rows on {kcache.device}")
-    ld_out = out.stride(0) if B > 1 else nq * hd
+    def pos_check():
+        if pos.dtype != torch.int64 or pos.shape != (B,) or pos.device != kcache.device or not pos.is_contiguous():
+            raise QpalError(f"{who}: pos must be a contiguous int64 [{B}] tensor on {kcache.device}")
+
+    _, nq, ld, out, ld_out = _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos_check, B)
     lib = _native.lib()
     if groups is None:
         need, maker = lib.qpal_attn_batch_ws_bytes(B, nq, nkv, hd, max_len), "attention_workspace"
     else:
         need, maker = lib.qpal_attn_prefix_ws_bytes(B, groups, nq, nkv, hd, max_len), "shared_prefix_workspace"
-    if need > 0:
-        if ws is None:
-            raise QpalError(f"{who}: this shape needs a workspace ({maker}(...))")
-        if ws.device != kcache.device or ws.numel() * ws.element_size() < need or not ws.is_contiguous():
-            raise QpalError(f"{who}: ws must be a contiguous device buffer of >= {need} bytes on {kcache.device}")
+    ws_ptr, ws_bytes = _launch_ws(who, need, ws, kcache, maker)
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
     with torch.cuda.device(kcache.device):
         rc = getattr(lib, entry)(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
             pos.data_ptr(), inv_freq.data_ptr(), *((B, nq, nkv, hd, max_len) if paged is None else paged + (B, nq, nkv, hd)), scale,
-            ws.data_ptr() if need > 0 else None, ws.numel() * ws.element_size() if need > 0 else 0,
-            torch.cuda.current_stream(kcache.device).cuda_stream)
+            ws_ptr, ws_bytes, torch.cuda.current_stream(kcache.device).cuda_stream)
     _native.check(rc, entry)
     return out
 
@@ -157,10 +142,7 @@ def prefill_workspace(T, nq, nkv, hd, max_len, device):
     """The zero-filled workspace ``prefill_attention`` needs for chunks of up to T rows and a cache of up to max_len positions
     (same nq, nkv, hd), or None where no launch of that shape needs one.  Keep it across launches: the kernel leaves it as it
     found it."""
-    n = _native.lib().qpal_attn_prefill_ws_bytes(int(T), int(nq), int(nkv), int(hd), int(max_len))
-    if n <= 0:
-        return None
-    return torch.zeros((n + 3) // 4, dtype=torch.float32, device=device)
+    return _workspace("qpal_attn_prefill_ws_bytes", device, T, nq, nkv, hd, max_len)
 
 
 def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=None, ws=None):
@@ -183,18 +165,22 @@ def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=N
     return _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, None)
 
 
-def _prefill_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos0=None):
-    """the checks of q / k / v / inv_freq / out every prefill launch shares, and of the one-sequence launches' pos0 where one is
-    given; returns (T, nq, ld_qkv, out, ld_out)"""
-    if q.dim() != 2 or not 1 <= q.shape[0] <= 128 or q.shape[1] % hd:
+def _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos_check=None, B=None):
+    """the checks of q / k / v / inv_freq / out every attention launch shares — B: the rows of a decode launch, None: the 1 .. 128
+    rows of a prefill launch — with the launch's own position check, where it has one, in its place among them; returns (T, nq,
+    ld_qkv, out, ld_out)"""
+    if B is not None:
+        if q.dim() != 2 or q.shape[0] != B or q.shape[1] % hd:
+            raise QpalError(f"{who}: q must have shape [{B}, nq*{hd}], got {list(q.shape)}")
+    elif q.dim() != 2 or not 1 <= q.shape[0] <= 128 or q.shape[1] % hd:
         raise QpalError(f"{who}: q must have shape [T, nq*{hd}] with 1 <= T <= 128, got {list(q.shape)}")
     T, nq = q.shape[0], q.shape[1] // hd
     ld = _rows(q, "q", T, nq * hd, who)
     for name, t in (("k", k), ("v", v)):
         if _rows(t, name, T, nkv * hd, who) != ld and T > 1:
             raise QpalError(f"{who}: q, k and v must share one row stride")
-    if pos0 is not None and (pos0.dtype != torch.int64 or pos0.numel() != 1 or pos0.device != kcache.device):
-        raise QpalError(f"{who}: pos0 must be an int64 tensor of one element on {kcache.device}")
+    if pos_check is not None:
+        pos_check()
     if inv_freq.dtype != torch.float32 or inv_freq.numel() != hd // 2 or inv_freq.device != kcache.device or not inv_freq.is_contiguous():
         raise QpalError(f"{who}: inv_freq must be a contiguous fp32 [{hd // 2}] tensor on {kcache.device}")
     if any(t.device != kcache.device for t in (q, k, v)):
@@ -206,7 +192,7 @@ def _prefill_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos0=None):
     return T, nq, ld, out, out.stride(0) if T > 1 else nq * hd
 
 
-def _prefill_ws(who, need, ws, kcache, maker):
+def _launch_ws(who, need, ws, kcache, maker):
     """(pointer, bytes) of the workspace a launch that needs `need` bytes is given"""
     if need <= 0:
         return None, 0
@@ -219,9 +205,13 @@ def _prefill_ws(who, need, ws, kcache, maker):
 
 def _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, paged):
     """the checks and the launch both prefill entry points share; paged: None, or the arguments that take max_len's place"""
-    T, nq, ld, out, ld_out = _prefill_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos0)
+    def pos_check():
+        if pos0.dtype != torch.int64 or pos0.numel() != 1 or pos0.device != kcache.device:
+            raise QpalError(f"{who}: pos0 must be an int64 tensor of one element on {kcache.device}")
+
+    T, nq, ld, out, ld_out = _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos_check)
     lib = _native.lib()
-    ws_ptr, ws_bytes = _prefill_ws(who, lib.qpal_attn_prefill_ws_bytes(T, nq, nkv, hd, max_len), ws, kcache, "prefill_workspace")
+    ws_ptr, ws_bytes = _launch_ws(who, lib.qpal_attn_prefill_ws_bytes(T, nq, nkv, hd, max_len), ws, kcache, "prefill_workspace")
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
     with torch.cuda.device(kcache.device):
         rc = getattr(lib, entry)(
@@ -322,11 +312,11 @@ def shared_prefix_workspace(B, G, nq, nkv, hd, max_len, device):
     """The zero-filled workspace ``shared_prefix_decode_attention`` needs for up to B slots in up to G groups on a paged cache of
     max_len = max_pages * page_size positions (same nq, nkv, hd).  It contains the plain launch's workspace; keep it across
     launches and layers: both launches leave their tickets at zero."""
-    n = _native.lib().qpal_attn_prefix_ws_bytes(int(B), int(G), int(nq), int(nkv), int(hd), int(max_len))
-    if n <= 0:
+    ws = _workspace("qpal_attn_prefix_ws_bytes", device, B, G, nq, nkv, hd, max_len)
+    if ws is None:
         raise QpalError(f"shared_prefix_workspace: no shared-prefix launch of shape B={B}, G={G}, nq={nq}, nkv={nkv}, hd={hd}, "
                         f"max_len={max_len}")
-    return torch.zeros((n + 3) // 4, dtype=torch.float32, device=device)
+    return ws
 
 
 def shared_prefix_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, prefix, scale=None, out=None, ws=None):
@@ -366,10 +356,7 @@ def ragged_workspace(R, S, nq, nkv, hd, max_len, device):
     up to max_len positions (same nq, nkv, hd), or None where no launch of that shape needs one (max_len < 512).  Keep it across
     launches: every launch leaves its tickets at zero, and they sit at a fixed offset, so launches of fewer rows, fewer segments
     or a shorter cache may share it in any order.  It is laid out for ragged launches: a prefill_workspace does not stand in."""
-    n = _native.lib().qpal_attn_ragged_ws_bytes(int(R), int(S), int(nq), int(nkv), int(hd), int(max_len))
-    if n <= 0:
-        return None
-    return torch.zeros((n + 3) // 4, dtype=torch.float32, device=device)
+    return _workspace("qpal_attn_ragged_ws_bytes", device, R, S, nq, nkv, hd, max_len)
 
 
 def _segments(who, seq, row0, pos0, dev):
@@ -390,9 +377,9 @@ def _segments(who, seq, row0, pos0, dev):
 def _ragged(who, entry, q, k, v, kcache, vcache, seq, row0, pos0, S, inv_freq, scale, out, ws, B, nkv, max_len, hd, head, tail):
     """the checks (behind _segments, which gave S) and the launch both ragged entry points share; head / tail: the arguments in
     front of and behind (R, S, B, nq, nkv, hd)"""
-    R, nq, ld, out, ld_out = _prefill_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd)
+    R, nq, ld, out, ld_out = _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd)
     lib = _native.lib()
-    ws_ptr, ws_bytes = _prefill_ws(who, lib.qpal_attn_ragged_ws_bytes(R, S, nq, nkv, hd, max_len), ws, kcache, "ragged_workspace")
+    ws_ptr, ws_bytes = _launch_ws(who, lib.qpal_attn_ragged_ws_bytes(R, S, nq, nkv, hd, max_len), ws, kcache, "ragged_workspace")
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
     with torch.cuda.device(kcache.device):
         rc = getattr(lib, entry)(

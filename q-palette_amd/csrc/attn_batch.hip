@@ -27,16 +27,15 @@
 
 #include <type_traits>
 
+#include "attn_common.h"
 #include "attn_prefix.h"
 #include "kv8.h"
-#include "kv_paged.h"
-#include "qpal_common.h"
 
 namespace qpal {
 
 namespace {
 
-constexpr int kBatchMax = 128;        // the linears' fused batch
+constexpr int kBatchMax = kAttnMaxRows;
 constexpr long kBatchSplitFrom = 512; // caches shorter than this: one chunk per (sequence, kv head), no workspace
 constexpr long kBatchMinChunk = 128;  // a chunk holds at least this many positions (fewer: the merge costs more than it saves)
 constexpr int kBatchNW = 16;          // waves per workgroup
@@ -68,13 +67,6 @@ struct AttnBatchParams {
     int B;
     const float *pre;
 };
-
-__device__ __forceinline__ void st_agent(float *p, float v) {
-    __hip_atomic_store(as_global(reinterpret_cast<unsigned *>(p)), __builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float ld_agent(const float *p) {
-    return __builtin_bit_cast(float, __hip_atomic_load(as_global(reinterpret_cast<const unsigned *>(p)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
 
 // SHARED (PAGED only): a member of a group (shared_prefix_len) attends to [grp_len, pos] through its own table row — the chunk
 // formulas below applied to pos - start, so start = 0 is the plain launch — and every finishing path folds the row's prefix partial
@@ -411,14 +403,7 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
     }
     // ---- ticket: the partial stores are agent-scope (write-through); wait for them, then arrive with an agent-scope release /
     // acquire so that the last arriver sees every other chunk's partials
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned t = __hip_atomic_fetch_add(as_global(ticket), 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        *flag = t == (unsigned)neff - 1 ? 1u : 0u;
-    }
-    __syncthreads();
-    if (*flag == 0u) return;
+    if (!ticket_last<__ATOMIC_ACQ_REL>(ticket, (unsigned)neff, flag, tid)) return;
     // ---- last arriver of this (sequence, kv head): merge in chunk order (max / sum of every partial through LDS first, then the
     // out partials sixteen at a time: agent-scope loads are issued together, never one per iteration)
     const float *base = p.part + slot * REP * (HD + 2);
@@ -486,10 +471,9 @@ struct BatchGeometry {
 // most max_len positions needs (monotone in both): one workspace serves every smaller launch of the same heads.
 int batch_geometry(int B, int nq, int nkv, int hd, long max_len, BatchGeometry &g) {
     g = BatchGeometry{0, 0, 0, 0};
-    if (B < 1 || B > kBatchMax || nq < 1 || nkv < 1 || nq % nkv || (hd != 64 && hd != 128 && hd != 256)) return QPAL_E_SHAPE;
+    const int rc = attn_shape(B, nq, nkv, hd, max_len);
+    if (rc != QPAL_OK) return rc;
     const int rep = nq / nkv;
-    if ((rep != 1 && rep != 2 && rep != 4 && rep != 8) || rep * hd > 1024) return QPAL_E_SHAPE;
-    if (max_len < 4 || max_len % 4 || max_len >= (1L << 30)) return QPAL_E_SHAPE;
     const size_t budget = kBatchLdsMax / sizeof(float), fixed = batch_lds_floats(rep, hd, 0);
     const long cl_max = (long)((budget - fixed) / rep) / 64 * 64;  // the most positions one chunk's scores can hold
     if (cl_max < 64) return QPAL_E_SHAPE;
@@ -518,21 +502,6 @@ int batch_geometry(int B, int nq, int nkv, int hd, long max_len, BatchGeometry &
     return QPAL_OK;
 }
 
-template <class CT, bool PAGED, int HD, int REP, bool SHARED = false>
-int launch_batch(const AttnBatchParams<CT> &p, int grid, size_t lds, void *stream) {
-    const auto kern = attn_rope_batch_kernel<CT, PAGED, HD, REP, SHARED>;
-    static bool attr_set[64] = {};  // one latch per instantiation and device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
-    if (lds > 64 * 1024 && (dev < 0 || !attr_set[dev])) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBatchLdsMax);
-        if (e != hipSuccess) return (int)e;
-        if (dev >= 0) attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kBatchNW), lds, static_cast<hipStream_t>(stream), p);
-    return (int)hipGetLastError();
-}
-
 // the entry points: the same checks, geometry and launch, the cache element type and the row addressing apart (PAGED: kcache /
 // vcache are the pools, `pg` the block table, max_len = max_pages * page_size)
 // the workspace of the shared launches: the plain launch's in front, then the prefix phase's tickets, chunk partials and merged
@@ -558,22 +527,11 @@ int attn_rope_decode_batch(const float *q, const float *k, const float *v, long 
         prefix_geometry(B, sp->G, nq, nkv, hd, max_len, x);
         g.ws_bytes = shared_ws_bytes(g, x);  // (checked below as the plain launch's is)
     }
-    if (ld_qkv < (long)nq * hd || ld_out < (long)nq * hd) return QPAL_E_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(kcache) | reinterpret_cast<uintptr_t>(vcache)) & 15) return QPAL_E_ALIGN;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
-         reinterpret_cast<uintptr_t>(inv_freq) | reinterpret_cast<uintptr_t>(pos)) & 3)
-        return QPAL_E_ALIGN;
-    if (reinterpret_cast<uintptr_t>(out_f16) & 1) return QPAL_E_ALIGN;
-    if (PAGED && (reinterpret_cast<uintptr_t>(pg->table) & 3)) return QPAL_E_ALIGN;
-    if constexpr (SHARED) {
-        if ((reinterpret_cast<uintptr_t>(sp->row_group) | reinterpret_cast<uintptr_t>(sp->grp_slot) | reinterpret_cast<uintptr_t>(sp->grp_len)) & 3)
-            return QPAL_E_ALIGN;
-    }
-    if (g.ws_bytes) {
-        if (!ws) return QPAL_E_NULL;
-        if (ws_bytes < (long)g.ws_bytes) return QPAL_E_SHAPE;
-        if (reinterpret_cast<uintptr_t>(ws) & 3) return QPAL_E_ALIGN;
-    }
+    uintptr_t al4 = PAGED ? reinterpret_cast<uintptr_t>(pg->table) : 0;
+    if constexpr (SHARED)
+        al4 |= reinterpret_cast<uintptr_t>(sp->row_group) | reinterpret_cast<uintptr_t>(sp->grp_slot) | reinterpret_cast<uintptr_t>(sp->grp_len);
+    const int rca = attn_args(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos, inv_freq, nq, hd, g.ws_bytes, ws, ws_bytes, al4);
+    if (rca != QPAL_OK) return rca;
     float *wsf = static_cast<float *>(ws);
     if constexpr (SHARED) g.ws_bytes = plain_ws;  // from here on: the part of the workspace the suffix launch owns
     AttnBatchParams<CT> p{q, k, v, ld_qkv, static_cast<CT *>(kcache), static_cast<CT *>(vcache),
@@ -590,13 +548,10 @@ int attn_rope_decode_batch(const float *q, const float *k, const float *v, long 
         const int rc2 = launch_attn_prefix(a, kKvFmt<CT>, hd, rep, stream);
         if (rc2 != QPAL_OK) return rc2;
     }
-#define QPAL_BATCH(HD_, REP_) \
-    if (hd == HD_ && rep == REP_) return launch_batch<CT, PAGED, HD_, REP_, SHARED>(p, grid, g.lds, stream);
-    QPAL_BATCH(64, 1) QPAL_BATCH(64, 2) QPAL_BATCH(64, 4) QPAL_BATCH(64, 8)
-    QPAL_BATCH(128, 1) QPAL_BATCH(128, 2) QPAL_BATCH(128, 4) QPAL_BATCH(128, 8)
-    QPAL_BATCH(256, 1) QPAL_BATCH(256, 2) QPAL_BATCH(256, 4)
-#undef QPAL_BATCH
-    return QPAL_E_SHAPE;
+    return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
+        return launch_lds<attn_rope_batch_kernel<CT, PAGED, HD(), REP(), SHARED>>(dim3(grid), dim3(64 * kBatchNW), g.lds, (int)kBatchLdsMax,
+                                                                                   static_cast<hipStream_t>(stream), p);
+    });
 }
 
 }  // namespace
@@ -631,19 +586,12 @@ extern "C" int qpal_attn_rope_decode_batch_paged(const float *q, const float *k,
                                                  const int *block_table, long ld_table, int num_pages, int page_size, int max_pages,
                                                  int kv_fmt, int B, int nq, int nkv, int hd, float scale, void *ws, long ws_bytes,
                                                  void *stream) {
-    if (!block_table) return QPAL_E_NULL;
     const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
-    int shift;
-    long max_len;
-    // (the siblings' order: their null checks come first, so a null among q .. inv_freq wins over a paged shape error)
-    if (!q || !k || !v || !kpool || !vpool || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
-    const int rc = paged_shape(pg, kv_fmt, shift, max_len);
-    if (rc != QPAL_OK) return rc;
-    if (kv_fmt == 1)
-        return attn_rope_decode_batch<uint8_t, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd, max_len,
-                                                     scale, ws, ws_bytes, stream, &pg, shift);
-    return attn_rope_decode_batch<uint16_t, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd, max_len,
-                                                  scale, ws, ws_bytes, stream, &pg, shift);
+    const bool any_null = !block_table || !q || !k || !v || !kpool || !vpool || !out_f16 || !pos || !inv_freq;
+    return paged_entry(any_null, pg, kv_fmt, [&](auto ct, int shift, long max_len) {
+        return attn_rope_decode_batch<decltype(ct), true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd,
+                                                          max_len, scale, ws, ws_bytes, stream, &pg, shift);
+    });
 }
 
 extern "C" long qpal_attn_prefix_ws_bytes(int B, int G, int nq, int nkv, int hd, long max_len) {
@@ -659,17 +607,11 @@ extern "C" int qpal_attn_rope_decode_batch_shared(const float *q, const float *k
                                                   const int *block_table, long ld_table, int num_pages, int page_size, int max_pages,
                                                   int kv_fmt, const int *row_group, const int *grp_slot, const int *grp_len, int G, int B,
                                                   int nq, int nkv, int hd, float scale, void *ws, long ws_bytes, void *stream) {
-    if (!block_table || !row_group || !grp_slot || !grp_len) return QPAL_E_NULL;
     const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
     const SharedPrefixArgs sp{row_group, grp_slot, grp_len, G};
-    int shift;
-    long max_len;
-    if (!q || !k || !v || !kpool || !vpool || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
-    const int rc = paged_shape(pg, kv_fmt, shift, max_len);
-    if (rc != QPAL_OK) return rc;
-    if (kv_fmt == 1)
-        return attn_rope_decode_batch<uint8_t, true, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd,
-                                                           max_len, scale, ws, ws_bytes, stream, &pg, shift, &sp);
-    return attn_rope_decode_batch<uint16_t, true, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd,
-                                                        max_len, scale, ws, ws_bytes, stream, &pg, shift, &sp);
+    const bool any_null = !block_table || !row_group || !grp_slot || !grp_len || !q || !k || !v || !kpool || !vpool || !out_f16 || !pos || !inv_freq;
+    return paged_entry(any_null, pg, kv_fmt, [&](auto ct, int shift, long max_len) {
+        return attn_rope_decode_batch<decltype(ct), true, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv,
+                                                                hd, max_len, scale, ws, ws_bytes, stream, &pg, shift, &sp);
+    });
 }

@@ -7,15 +7,14 @@
 
 #include <type_traits>
 
+#include "attn_common.h"
 #include "kv8.h"
-#include "kv_paged.h"
-#include "qpal_common.h"
 
 namespace qpal {
 
 namespace {
 
-constexpr int kPfMaxT = 128;        // the linears' fused batch
+constexpr int kPfMaxT = kAttnMaxRows;
 constexpr int kPfKT = 32;           // keys per tile
 constexpr long kPfSplitFrom = 512;  // caches shorter than this: one chunk per (kv head, query tile), no workspace
 constexpr long kPfMinChunk = 128;   // a chunk holds at least this many keys
@@ -51,13 +50,6 @@ struct AttnRaggedParams : AttnPrefillParams<CT> {
     int S, B;
     long ld_table;
 };
-
-__device__ __forceinline__ void st_agent(float *p, float v) {
-    __hip_atomic_store(as_global(reinterpret_cast<unsigned *>(p)), __builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float ld_agent(const float *p) {
-    return __builtin_bit_cast(float, __hip_atomic_load(as_global(reinterpret_cast<const unsigned *>(p)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
 
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
@@ -390,14 +382,7 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
     // ---- ticket: the partial stores are agent-scope (write-through); wait for them, then arrive with an agent-scope release /
     // acquire so that the last arriver sees every other chunk's partials
     unsigned *ticket = p.tickets + kh * (RAGGED ? kPfRaggedTiles : kPfMaxTiles) + jg;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned t = __hip_atomic_fetch_add(as_global(ticket), 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        flag = t == (unsigned)neff - 1 ? 1u : 0u;
-    }
-    __syncthreads();
-    if (flag == 0u) return;
+    if (!ticket_last<__ATOMIC_ACQ_REL>(ticket, (unsigned)neff, &flag, tid)) return;
     // ---- last arriver of this (kv head, query tile): merge in chunk order
     const float *base = p.part + slot * R * (HD + 2);
     float *cf = reinterpret_cast<float *>(sm);  // [R][neff] weights exp(m_s - M), then [R] sums
@@ -438,15 +423,6 @@ struct PrefillGeometry {
     size_t ws_bytes;
 };
 
-// the shape rules every prefill launch shares (rows: T of a one-sequence launch, R of a ragged one)
-inline int prefill_shape(int rows, int nq, int nkv, int hd, long max_len) {
-    if (rows < 1 || rows > kPfMaxT || nq < 1 || nkv < 1 || nq % nkv || (hd != 64 && hd != 128 && hd != 256)) return QPAL_E_SHAPE;
-    const int rep = nq / nkv;
-    if ((rep != 1 && rep != 2 && rep != 4 && rep != 8) || rep * hd > 1024) return QPAL_E_SHAPE;
-    if (max_len < 4 || max_len % 4 || max_len >= (1L << 30)) return QPAL_E_SHAPE;
-    return QPAL_OK;
-}
-
 // chunks per query tile and the workspace of a launch of `ntile` query tiles per kv head with `tickets` ticket words.  ws_bytes
 // is an upper bound of what ANY launch with at most ntile tiles and at most max_len positions needs (monotone in both).
 inline void prefill_split(long ntile, long tickets, int nq, int nkv, int hd, long max_len, PrefillGeometry &g) {
@@ -463,25 +439,6 @@ inline void prefill_split(long ntile, long tickets, int nq, int nkv, int hd, lon
         const long slots = a < b ? a : b;
         g.ws_bytes = ((size_t)tickets + (size_t)slots * tq * rep * (hd + 2)) * sizeof(float);
     }
-}
-
-// the argument checks every prefill entry point shares, behind the null checks and the geometry
-inline int prefill_args(const void *q, const void *k, const void *v, long ld_qkv, const void *kcache, const void *vcache, const void *out_f16,
-                        long ld_out, const void *pos0, const void *inv_freq, int nq, int hd, const PrefillGeometry &g, const void *ws,
-                        long ws_bytes, const void *table) {
-    if (ld_qkv < (long)nq * hd || ld_out < (long)nq * hd) return QPAL_E_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(kcache) | reinterpret_cast<uintptr_t>(vcache)) & 15) return QPAL_E_ALIGN;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
-         reinterpret_cast<uintptr_t>(inv_freq) | reinterpret_cast<uintptr_t>(pos0)) & 3)
-        return QPAL_E_ALIGN;
-    if (reinterpret_cast<uintptr_t>(out_f16) & 1) return QPAL_E_ALIGN;
-    if (reinterpret_cast<uintptr_t>(table) & 3) return QPAL_E_ALIGN;
-    if (g.ws_bytes) {
-        if (!ws) return QPAL_E_NULL;
-        if (ws_bytes < (long)g.ws_bytes) return QPAL_E_SHAPE;
-        if (reinterpret_cast<uintptr_t>(ws) & 3) return QPAL_E_ALIGN;
-    }
-    return QPAL_OK;
 }
 
 }  // namespace

@@ -36,7 +36,7 @@ namespace {
 // max_len positions needs (monotone in both): one workspace serves every smaller launch of the same heads.
 int prefill_geometry(int T, int nq, int nkv, int hd, long max_len, PrefillGeometry &g) {
     g = PrefillGeometry{0, 0, 0};
-    const int rc = prefill_shape(T, nq, nkv, hd, max_len);
+    const int rc = attn_shape(T, nq, nkv, hd, max_len);
     if (rc != QPAL_OK) return rc;
     const int tq = 16 * pf_qs(nq / nkv);
     prefill_split((T + tq - 1) / tq, (long)nkv * kPfMaxTiles, nq, nkv, hd, max_len, g);
@@ -53,7 +53,8 @@ int attn_rope_prefill(const float *q, const float *k, const float *v, long ld_qk
     PrefillGeometry g;
     int rc = prefill_geometry(T, nq, nkv, hd, max_len, g);
     if (rc != QPAL_OK) return rc;
-    rc = prefill_args(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, nq, hd, g, ws, ws_bytes, PAGED ? pg->table : nullptr);
+    rc = attn_args(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, nq, hd, g.ws_bytes, ws, ws_bytes,
+                   PAGED ? reinterpret_cast<uintptr_t>(pg->table) : 0);
     if (rc != QPAL_OK) return rc;
     float *wsf = static_cast<float *>(ws);
     AttnPrefillParams<CT> p{q, k, v, ld_qkv, static_cast<CT *>(kcache), static_cast<CT *>(vcache),
@@ -62,17 +63,11 @@ int attn_rope_prefill(const float *q, const float *k, const float *v, long ld_qk
                             g.nsplit, g.ntile};
     if constexpr (PAGED) p.table = pg->table, p.num_pages = pg->num_pages, p.page_shift = shift;
     const int grid = nkv * g.ntile * g.nsplit, rep = nq / nkv;
-#define QPAL_PREFILL(HD_, REP_)                                                                                                    \
-    if (hd == HD_ && rep == REP_) {                                                                                                \
-        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, false, HD_, REP_>), dim3(grid), dim3(64 * REP_ * pf_qs(REP_)), 0,              \
-                           static_cast<hipStream_t>(stream), p);                                                                   \
-        return (int)hipGetLastError();                                                                                             \
-    }
-    QPAL_PREFILL(64, 1) QPAL_PREFILL(64, 2) QPAL_PREFILL(64, 4) QPAL_PREFILL(64, 8)
-    QPAL_PREFILL(128, 1) QPAL_PREFILL(128, 2) QPAL_PREFILL(128, 4) QPAL_PREFILL(128, 8)
-    QPAL_PREFILL(256, 1) QPAL_PREFILL(256, 2) QPAL_PREFILL(256, 4)
-#undef QPAL_PREFILL
-    return QPAL_E_SHAPE;
+    return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
+        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, false, HD(), REP()>), dim3(grid), dim3(64 * REP() * pf_qs(REP())), 0,
+                           static_cast<hipStream_t>(stream), p);
+        return (int)hipGetLastError();
+    });
 }
 
 }  // namespace
@@ -105,16 +100,10 @@ extern "C" int qpal_attn_rope_prefill_paged(const float *q, const float *k, cons
                                             void *out_f16, long ld_out, const long *pos0, const float *inv_freq, const int *block_row,
                                             int num_pages, int page_size, int max_pages, int kv_fmt, int T, int nq, int nkv, int hd,
                                             float scale, void *ws, long ws_bytes, void *stream) {
-    if (!block_row) return QPAL_E_NULL;
     const PageArgs pg{block_row, max_pages, num_pages, page_size, max_pages};
-    int shift;
-    long max_len;
-    if (!q || !k || !v || !kpool || !vpool || !out_f16 || !pos0 || !inv_freq) return QPAL_E_NULL;
-    const int rc = paged_shape(pg, kv_fmt, shift, max_len);
-    if (rc != QPAL_OK) return rc;
-    if (kv_fmt == 1)
-        return attn_rope_prefill<uint8_t, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, max_len,
-                                                scale, ws, ws_bytes, stream, &pg, shift);
-    return attn_rope_prefill<uint16_t, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, max_len, scale,
-                                             ws, ws_bytes, stream, &pg, shift);
+    const bool any_null = !block_row || !q || !k || !v || !kpool || !vpool || !out_f16 || !pos0 || !inv_freq;
+    return paged_entry(any_null, pg, kv_fmt, [&](auto ct, int shift, long max_len) {
+        return attn_rope_prefill<decltype(ct), true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, max_len,
+                                                     scale, ws, ws_bytes, stream, &pg, shift);
+    });
 }

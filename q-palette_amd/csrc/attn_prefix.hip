@@ -281,14 +281,7 @@ __global__ __launch_bounds__(256) void attn_prefix_kernel(const AttnPrefixParams
     // ---- ticket: the partial stores are agent-scope (write-through); wait for them, then arrive with an agent-scope release /
     // acquire so that the last arriver sees every other chunk's partials
     unsigned *ticket = p.tickets + (long)kh * p.ntile + jt;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned t = __hip_atomic_fetch_add(as_global(ticket), 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        flag = t == (unsigned)neff - 1 ? 1u : 0u;
-    }
-    __syncthreads();
-    if (flag == 0u) return;
+    if (!ticket_last<__ATOMIC_ACQ_REL>(ticket, (unsigned)neff, &flag, tid)) return;
     // ---- last arriver of this (kv head, tile): merge in chunk order
     // (agent-scope loads are issued in batches, never one per iteration: a round trip each would be the launch's longest part)
     float *cf = reinterpret_cast<float *>(sm);  // [R][neff]: the maxima, then in their place the weights exp(m_s - M); [R][neff] sums
@@ -355,16 +348,10 @@ template <class CT>
 int launch_prefix(const PrefixLaunch &a, int hd, int rep, void *stream) {
     const AttnPrefixParams<CT> p{a, static_cast<const CT *>(a.kpool), static_cast<const CT *>(a.vpool)};
     const int grid = a.nkv * a.ntile * a.nsplit;
-#define QPAL_PREFIX(HD_, REP_)                                                                                                \
-    if (hd == HD_ && rep == REP_) {                                                                                            \
-        hipLaunchKernelGGL((attn_prefix_kernel<CT, HD_, REP_>), dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), p); \
-        return (int)hipGetLastError();                                                                                         \
-    }
-    QPAL_PREFIX(64, 1) QPAL_PREFIX(64, 2) QPAL_PREFIX(64, 4) QPAL_PREFIX(64, 8)
-    QPAL_PREFIX(128, 1) QPAL_PREFIX(128, 2) QPAL_PREFIX(128, 4) QPAL_PREFIX(128, 8)
-    QPAL_PREFIX(256, 1) QPAL_PREFIX(256, 2) QPAL_PREFIX(256, 4)
-#undef QPAL_PREFIX
-    return QPAL_E_SHAPE;
+    return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
+        hipLaunchKernelGGL((attn_prefix_kernel<CT, HD(), REP()>), dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+        return (int)hipGetLastError();
+    });
 }
 
 }  // namespace

@@ -21,7 +21,7 @@ namespace {
 // rows; chunks and workspace by prefill_split with nkv * kPfRaggedTiles tickets.  ws_bytes is monotone in R, S and max_len.
 int ragged_geometry(int R, int S, int nq, int nkv, int hd, long max_len, PrefillGeometry &g) {
     g = PrefillGeometry{0, 0, 0};
-    const int rc = prefill_shape(R, nq, nkv, hd, max_len);
+    const int rc = attn_shape(R, nq, nkv, hd, max_len);
     if (rc != QPAL_OK) return rc;
     if (S < 1 || S > kPfMaxT) return QPAL_E_SHAPE;
     const int tq = 16 * pf_qs(nq / nkv);
@@ -38,7 +38,8 @@ int attn_rope_ragged(const float *q, const float *k, const float *v, long ld_qkv
     int rc = ragged_geometry(R, S, nq, nkv, hd, max_len, g);
     if (rc != QPAL_OK) return rc;
     if (B < 1) return QPAL_E_SHAPE;
-    rc = prefill_args(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, nq, hd, g, ws, ws_bytes, PAGED ? pg->table : nullptr);
+    rc = attn_args(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, nq, hd, g.ws_bytes, ws, ws_bytes,
+                   PAGED ? reinterpret_cast<uintptr_t>(pg->table) : 0);
     if (rc != QPAL_OK) return rc;
     if ((reinterpret_cast<uintptr_t>(seq) | reinterpret_cast<uintptr_t>(row0)) & 3) return QPAL_E_ALIGN;
     float *wsf = static_cast<float *>(ws);
@@ -50,17 +51,11 @@ int attn_rope_ragged(const float *q, const float *k, const float *v, long ld_qkv
     p.seq = seq, p.row0 = row0, p.S = S, p.B = B;
     if constexpr (PAGED) p.table = pg->table, p.num_pages = pg->num_pages, p.page_shift = shift, p.ld_table = pg->ld_table;
     const int grid = nkv * g.ntile * g.nsplit, rep = nq / nkv;
-#define QPAL_RAGGED(HD_, REP_)                                                                                                     \
-    if (hd == HD_ && rep == REP_) {                                                                                                \
-        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, true, HD_, REP_>), dim3(grid), dim3(64 * REP_ * pf_qs(REP_)), 0,               \
-                           static_cast<hipStream_t>(stream), p);                                                                   \
-        return (int)hipGetLastError();                                                                                             \
-    }
-    QPAL_RAGGED(64, 1) QPAL_RAGGED(64, 2) QPAL_RAGGED(64, 4) QPAL_RAGGED(64, 8)
-    QPAL_RAGGED(128, 1) QPAL_RAGGED(128, 2) QPAL_RAGGED(128, 4) QPAL_RAGGED(128, 8)
-    QPAL_RAGGED(256, 1) QPAL_RAGGED(256, 2) QPAL_RAGGED(256, 4)
-#undef QPAL_RAGGED
-    return QPAL_E_SHAPE;
+    return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
+        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, true, HD(), REP()>), dim3(grid), dim3(64 * REP() * pf_qs(REP())), 0,
+                           static_cast<hipStream_t>(stream), p);
+        return (int)hipGetLastError();
+    });
 }
 
 }  // namespace
@@ -81,11 +76,10 @@ extern "C" int qpal_attn_rope_prefill_ragged(const float *q, const float *k, con
                                              float scale, void *ws, long ws_bytes, void *stream) {
     if (!q || !k || !v || !kcache || !vcache || !out_f16 || !seq || !row0 || !pos0 || !inv_freq) return QPAL_E_NULL;
     if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
-    if (kv_fmt == 1)
-        return attn_rope_ragged<uint8_t, false>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B, nq, nkv,
-                                                hd, max_len, scale, ws, ws_bytes, stream);
-    return attn_rope_ragged<uint16_t, false>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B, nq, nkv, hd,
-                                             max_len, scale, ws, ws_bytes, stream);
+    return for_kv_fmt(kv_fmt, [&](auto ct) {
+        return attn_rope_ragged<decltype(ct), false>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B, nq,
+                                                     nkv, hd, max_len, scale, ws, ws_bytes, stream);
+    });
 }
 
 extern "C" int qpal_attn_rope_prefill_ragged_paged(const float *q, const float *k, const float *v, long ld_qkv, void *kpool, void *vpool,
@@ -93,16 +87,10 @@ extern "C" int qpal_attn_rope_prefill_ragged_paged(const float *q, const float *
                                                    const float *inv_freq, const int *block_table, long ld_table, int num_pages,
                                                    int page_size, int max_pages, int kv_fmt, int R, int S, int B, int nq, int nkv, int hd,
                                                    float scale, void *ws, long ws_bytes, void *stream) {
-    if (!block_table) return QPAL_E_NULL;
     const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
-    int shift;
-    long max_len;
-    if (!q || !k || !v || !kpool || !vpool || !out_f16 || !seq || !row0 || !pos0 || !inv_freq) return QPAL_E_NULL;
-    const int rc = paged_shape(pg, kv_fmt, shift, max_len);
-    if (rc != QPAL_OK) return rc;
-    if (kv_fmt == 1)
-        return attn_rope_ragged<uint8_t, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B, nq, nkv, hd,
-                                               max_len, scale, ws, ws_bytes, stream, &pg, shift);
-    return attn_rope_ragged<uint16_t, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B, nq, nkv, hd,
-                                            max_len, scale, ws, ws_bytes, stream, &pg, shift);
+    const bool any_null = !block_table || !q || !k || !v || !kpool || !vpool || !out_f16 || !seq || !row0 || !pos0 || !inv_freq;
+    return paged_entry(any_null, pg, kv_fmt, [&](auto ct, int shift, long max_len) {
+        return attn_rope_ragged<decltype(ct), true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B, nq, nkv,
+                                                    hd, max_len, scale, ws, ws_bytes, stream, &pg, shift);
+    });
 }

@@ -7,6 +7,7 @@
 // model/llama.py apply_rotary_pos_emb) -> q as fp16, k and v written into the static KV cache at `pos`.
 #include <hip/hip_runtime.h>
 
+#include "attn_common.h"
 #include "qpal_common.h"
 
 namespace qpal {
@@ -406,13 +407,6 @@ struct AttnSplitParams {
     int nsplit, chunk;  // chunk: positions per split (multiple of 64)
 };
 
-__device__ __forceinline__ void st_agent_f(float *p, float v) {
-    __hip_atomic_store(as_global(reinterpret_cast<unsigned *>(p)), __builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float ld_agent_f(const float *p) {
-    return __builtin_bit_cast(float, __hip_atomic_load(as_global(reinterpret_cast<const unsigned *>(p)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-
 template <int HD, int REP, int NW>
 __global__ __launch_bounds__(64 * NW) void attn_rope_split_kernel(const AttnSplitParams sp) {
     constexpr int NT = 64 * NW, HALF = HD / 2;
@@ -629,30 +623,23 @@ __global__ __launch_bounds__(64 * NW) void attn_rope_split_kernel(const AttnSpli
             const int h = idx / HD, d = idx - h * HD;
             if (owner) v += park[h] * vn[d];
             if (neff == 1) p.out[(long)(kh * REP) * HD + idx] = __builtin_bit_cast(uint16_t, (_Float16)(v / sumf[h]));  // the only chunk
-            else st_agent_f(wsp + h * (HD + 2) + 2 + d, v);
+            else st_agent(wsp + h * (HD + 2) + 2 + d, v);
         }
         if (neff == 1) return;  // no partials, no ticket
         if (tid < REP) {
-            st_agent_f(wsp + tid * (HD + 2), mxf[tid]);
-            st_agent_f(wsp + tid * (HD + 2) + 1, sumf[tid]);
+            st_agent(wsp + tid * (HD + 2), mxf[tid]);
+            st_agent(wsp + tid * (HD + 2) + 1, sumf[tid]);
         }
     }
     // ---- ticket: the stores above are write-through; wait for them, then arrive
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned t = __hip_atomic_fetch_add(as_global(ticket), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *flag = t == (unsigned)neff - 1 ? 1u : 0u;
-    }
-    __syncthreads();
-    if (*flag == 0u) return;
+    if (!ticket_last<__ATOMIC_RELAXED>(ticket, (unsigned)neff, flag, tid)) return;
     // ---- last arriver of this kv head: merge.  Agent-scope loads are ~1 us each: all of a stage's loads are issued
     // together (max / sum of every partial through LDS first, then the out partials eight at a time), never one per iteration.
     const float *base = sp.ws + (long)kh * sp.nsplit * REP * (HD + 2);
     float *ml = sh;  // [nsplit * REP][2]: the score buffer is free now
     for (int i = tid; i < neff * REP; i += NT) {
         const float *pp = base + (long)i * (HD + 2);
-        const float m = ld_agent_f(pp), l = ld_agent_f(pp + 1);
+        const float m = ld_agent(pp), l = ld_agent(pp + 1);
         ml[2 * i] = m;
         ml[2 * i + 1] = l;
     }
@@ -670,7 +657,7 @@ __global__ __launch_bounds__(64 * NW) void attn_rope_split_kernel(const AttnSpli
 #pragma unroll
             for (int u = 0; u < 16; u++) {
                 const int sx = s0 + u < neff ? s0 + u : neff - 1;
-                v[u] = ld_agent_f(base + ((long)sx * REP + h) * (HD + 2) + 2 + d);
+                v[u] = ld_agent(base + ((long)sx * REP + h) * (HD + 2) + 2 + d);
             }
 #pragma unroll
             for (int u = 0; u < 16; u++) {
@@ -779,8 +766,10 @@ __global__ __launch_bounds__(1024) void lm_head_argmax_kernel(const LmHeadParams
             const int vi = __builtin_bit_cast(int, red[16 + w]);
             if (v > b || (v == b && vi < bi)) b = v, bi = vi;
         }
-        __hip_atomic_store(as_global(reinterpret_cast<unsigned *>(p.ws + 2 * blockIdx.x)), __builtin_bit_cast(unsigned, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(as_global(reinterpret_cast<unsigned *>(p.ws + 2 * blockIdx.x + 1)), (unsigned)bi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        st_agent(p.ws + 2 * blockIdx.x, b);
+        st_agent(p.ws + 2 * blockIdx.x + 1, __builtin_bit_cast(float, bi));
+        // (thread 0 alone waits and arrives, with no barrier in front: not ticket_last's hand-over; the loads below stay spelled
+        // out too — through ld_agent the compiler orders the final reduction's instructions differently)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         unsigned *ticket = reinterpret_cast<unsigned *>(p.ws + 2 * gridDim.x);
         const unsigned t = __hip_atomic_fetch_add(as_global(ticket), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -831,19 +820,9 @@ extern "C" int qpal_attn_decode(const void *q_f16, const void *kcache_f16, const
     const size_t lds = sizeof(float) * ((size_t)max_len + 5 * (size_t)hd + 8);
     if (lds > 160 * 1024) return QPAL_E_SHAPE;  // ~40 k positions: longer contexts need the split-context form
     if ((reinterpret_cast<uintptr_t>(kcache_f16) | reinterpret_cast<uintptr_t>(vcache_f16)) & 15) return QPAL_E_ALIGN;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
-    if (lds > 64 * 1024 && (dev < 0 || !attr_set[dev])) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&attn_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        if (dev >= 0) attr_set[dev] = true;
-    }
     AttnParams p{static_cast<const uint16_t *>(q_f16), static_cast<const uint16_t *>(kcache_f16),
                  static_cast<const uint16_t *>(vcache_f16), static_cast<uint16_t *>(out_f16), pos, nq, nkv, hd, max_len, scale};
-    hipLaunchKernelGGL(attn_decode_kernel, dim3(nq), dim3(256), lds, static_cast<hipStream_t>(stream), p);
-    return (int)hipGetLastError();
+    return launch_lds<attn_decode_kernel>(dim3(nq), dim3(256), lds, 160 * 1024, static_cast<hipStream_t>(stream), p);
 }
 
 extern "C" int qpal_rope_kv(const float *q, const float *k, const float *v, void *q_out_f16, void *kcache_f16, void *vcache_f16,
@@ -886,20 +865,6 @@ extern "C" long qpal_attn_ws_bytes(int nq, int nkv, int hd, long max_len) {
     return (long)wsb;
 }
 
-template <class Kern, class Params>
-static int launch_attn(Kern kern, const Params &p, int grid, int threads, size_t lds, void *stream) {
-    static bool attr_set[64] = {};  // one latch per instantiation
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
-    if (lds > 64 * 1024 && (dev < 0 || !attr_set[dev])) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        if (dev >= 0) attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, static_cast<hipStream_t>(stream), p);
-    return (int)hipGetLastError();
-}
-
 extern "C" int qpal_attn_rope_decode(const float *q, const float *k, const float *v, void *kcache_f16, void *vcache_f16, void *out_f16,
                                      const long *pos, const float *inv_freq, int nq, int nkv, int hd, long max_len, float scale,
                                      void *ws, long ws_bytes, void *stream) {
@@ -916,24 +881,21 @@ extern "C" int qpal_attn_rope_decode(const float *q, const float *k, const float
     int ns, ch, nw;
     size_t slds, wsb;
     attn_split_geometry(nq, nkv, hd, max_len, ns, ch, nw, slds, wsb);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
     if (ws && ns >= 2) {  // split-context form
         if ((size_t)ws_bytes < wsb) return QPAL_E_SHAPE;
         if (reinterpret_cast<uintptr_t>(ws) & 3) return QPAL_E_ALIGN;
         AttnSplitParams sp{p, static_cast<float *>(ws), ns, ch};
         const int rep = nq / nkv, grid = nkv * ns;
-#define QPAL_SPLIT(HD_, REP_) \
-    if (hd == HD_ && rep == REP_) return launch_attn(attn_rope_split_kernel<HD_, REP_, 16>, sp, grid, 64 * nw, slds, stream);
-        QPAL_SPLIT(64, 1) QPAL_SPLIT(64, 2) QPAL_SPLIT(64, 4) QPAL_SPLIT(64, 8)
-        QPAL_SPLIT(128, 1) QPAL_SPLIT(128, 2) QPAL_SPLIT(128, 4) QPAL_SPLIT(128, 8)
-        QPAL_SPLIT(256, 1) QPAL_SPLIT(256, 2) QPAL_SPLIT(256, 4)
-#undef QPAL_SPLIT
-        return QPAL_E_SHAPE;
+        return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
+            return launch_lds<attn_rope_split_kernel<HD(), REP(), 16>>(dim3(grid), dim3(64 * nw), slds, 160 * 1024, s, sp);
+        });
     }
     const size_t lds = sizeof(float) * ((size_t)max_len + 2 * hd + 16 * (size_t)hd + 32);
     if (lds > 160 * 1024) return QPAL_E_SHAPE;  // ~38 k positions: give a workspace (qpal_attn_ws_bytes) for the split-context form
-    if (hd == 64) return launch_attn(attn_rope_decode_kernel<64>, p, nq, 1024, lds, stream);
-    if (hd == 128) return launch_attn(attn_rope_decode_kernel<128>, p, nq, 1024, lds, stream);
-    return launch_attn(attn_rope_decode_kernel<256>, p, nq, 1024, lds, stream);
+    if (hd == 64) return launch_lds<attn_rope_decode_kernel<64>>(dim3(nq), dim3(1024), lds, 160 * 1024, s, p);
+    if (hd == 128) return launch_lds<attn_rope_decode_kernel<128>>(dim3(nq), dim3(1024), lds, 160 * 1024, s, p);
+    return launch_lds<attn_rope_decode_kernel<256>>(dim3(nq), dim3(1024), lds, 160 * 1024, s, p);
 }
 
 // workspace of qpal_lm_head_argmax: one (max, index) pair per workgroup + the ticket

@@ -12,6 +12,7 @@
 //      (matmul_hadU_cuda); round_mid = 0 feeds t as an fp16 hi + lo pair, i.e. fp32-grade like
 //      matmul_hadU_head_cuda's float path.
 //   3. out = fp16( fp16(u) * post_scale [* sv] ).
+#include "launch.h"
 #include "qpal_common.h"
 #include "wht64.h"
 
@@ -631,18 +632,7 @@ int launch_hadamard(const HadParams &p, hipStream_t stream) {
     if (p.hd <= 4096) {  // <= 256 groups of 16: four waves do it
         hipLaunchKernelGGL((had_kernel<256>), dim3(grid), dim3(256), lds, stream, p);
     } else {
-        // > 64 KiB of dynamic LDS needs the opt-in, per DEVICE (function attributes belong to the device's code object);
-        // idempotent, races are harmless
-        static bool attr_set[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
-        if (dev < 0 || !attr_set[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&had_kernel<768>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return (int)e;
-            if (dev >= 0) attr_set[dev] = true;
-        }
-        hipLaunchKernelGGL((had_kernel<768>), dim3(grid), dim3(768), lds, stream, p);
+        return launch_lds<had_kernel<768>>(dim3(grid), dim3(768), lds, 160 * 1024, stream, p);
     }
     return (int)hipGetLastError();
 }

@@ -19,6 +19,7 @@
 //     (8g + s) ^ (g & 15), distinct modulo 16 over any 16 lanes with distinct g & 15;
 //   * the later passes (b0 >= 5): the 32 lanes of a ds_read_b32 / ds_write_b32 group read 32 consecutive elements of one
 //     aligned run of 32, which swz only permutes.
+#include "launch.h"
 #include "qpal_common.h"
 
 namespace qpal {
@@ -174,20 +175,7 @@ __global__ __launch_bounds__(NT) void had_f32_kernel(Params p) {
 
 template <int NT>
 static int launch(const Params &p, size_t lds, hipStream_t stream) {
-    if (lds > 64 * 1024) {
-        // > 64 KiB of dynamic LDS needs the opt-in, per DEVICE; idempotent, races are harmless
-        static bool attr_set[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
-        if (dev < 0 || !attr_set[dev]) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&had_f32_kernel<NT>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-            if (e != hipSuccess) return (int)e;
-            if (dev >= 0) attr_set[dev] = true;
-        }
-    }
-    hipLaunchKernelGGL((had_f32_kernel<NT>), dim3(p.rows * (p.n / p.hd)), dim3(NT), lds, stream, p);
-    return (int)hipGetLastError();
+    return launch_lds<had_f32_kernel<NT>>(dim3(p.rows * (p.n / p.hd)), dim3(NT), lds, kLdsBytes, stream, p);
 }
 
 }  // namespace hf32

@@ -18,6 +18,7 @@
 
 #include <type_traits>
 
+#include "launch.h"
 #include "qpal.h"
 
 namespace qpal {
@@ -186,20 +187,7 @@ extern "C" int qpal_hessian_accum(double *H, double *colsum, const void *X, long
     if ((reinterpret_cast<uintptr_t>(X) & 15) || (ld_x & 7)) return QPAL_E_ALIGN;  // 16-byte loads of every row
     if ((reinterpret_cast<uintptr_t>(H) | reinterpret_cast<uintptr_t>(colsum)) & 7) return QPAL_E_ALIGN;
     if (rows == 0) return 0;
-    if (kLdsBytes > 64 * 1024) {
-        // > 64 KiB of dynamic LDS needs the opt-in, per DEVICE; idempotent, races are harmless
-        static bool attr_set[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
-        if (dev < 0 || !attr_set[dev]) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&hessian_kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-            if (e != hipSuccess) return (int)e;
-            if (dev >= 0) attr_set[dev] = true;
-        }
-    }
     const int T = (n + kTile - 1) / kTile;
-    hipLaunchKernelGGL(hessian_kernel, dim3(T * (T + 1) / 2), dim3(256), kLdsBytes, static_cast<hipStream_t>(stream), H, colsum,
-                       static_cast<const uint16_t *>(X), ld_x, rows, n);
-    return (int)hipGetLastError();
+    return qpal::launch_lds<hessian_kernel>(dim3(T * (T + 1) / 2), dim3(256), kLdsBytes, kLdsBytes, static_cast<hipStream_t>(stream), H, colsum,
+                                            static_cast<const uint16_t *>(X), ld_x, rows, n);
 }

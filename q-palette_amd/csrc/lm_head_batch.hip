@@ -10,6 +10,7 @@
 // writer per logit, no workspace, no atomics.
 #include <hip/hip_runtime.h>
 
+#include "launch.h"
 #include "qpal_common.h"
 
 namespace qpal {
@@ -144,20 +145,6 @@ using namespace qpal;
 
 static size_t lm_logits_lds(int nbt) { return (size_t)nbt * 16 * (sizeof(float) + kLmStride * sizeof(uint16_t)); }
 
-template <class Kern>
-static int launch_lm_logits(Kern kern, const LmLogitsParams &p, int grid, size_t lds, void *stream) {
-    static bool attr_set[64] = {};  // one latch per instantiation and device (128 rows: 66 KiB of LDS)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
-    if (lds > 64 * 1024 && (dev < 0 || !attr_set[dev])) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        if (dev >= 0) attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), lds, static_cast<hipStream_t>(stream), p);
-    return (int)hipGetLastError();
-}
-
 extern "C" int qpal_lm_head_logits(const float *h_f32, long ld_h, const void *rms_w_f16, float rms_eps, const void *w_f16,
                                    float *logits_f32, long ld_logits, int rows, int vocab, int k, void *stream) {
     if (!h_f32 || !w_f16 || !logits_f32) return QPAL_E_NULL;
@@ -170,7 +157,11 @@ extern "C" int qpal_lm_head_logits(const float *h_f32, long ld_h, const void *rm
                      static_cast<const uint16_t *>(w_f16), logits_f32, ld_logits, rows, vocab, k};
     const int grid = (vocab + 255) / 256;
     switch ((rows + 15) / 16) {
-#define QPAL_LM_LOGITS(N_) case N_: return launch_lm_logits(lm_head_logits_kernel<N_>, p, grid, lm_logits_lds(N_), stream);
+    // (128 rows: 66 KiB of LDS)
+#define QPAL_LM_LOGITS(N_)                                                                                                  \
+    case N_:                                                                                                                \
+        return launch_lds<lm_head_logits_kernel<N_>>(dim3(grid), dim3(1024), lm_logits_lds(N_), (int)lm_logits_lds(N_), \
+                                                     static_cast<hipStream_t>(stream), p);
         QPAL_LM_LOGITS(1) QPAL_LM_LOGITS(2) QPAL_LM_LOGITS(3) QPAL_LM_LOGITS(4)
         QPAL_LM_LOGITS(5) QPAL_LM_LOGITS(6) QPAL_LM_LOGITS(7) QPAL_LM_LOGITS(8)
 #undef QPAL_LM_LOGITS

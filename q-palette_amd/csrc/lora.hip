@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch.h"
 #include "qpal.h"
 
 namespace qpal {
@@ -206,20 +207,7 @@ using namespace qpal::lora;
 
 template <int MODE, bool RMS>
 static int launch(const Params &p, dim3 grid, size_t lds, hipStream_t stream) {
-    if (lds > 64 * 1024) {
-        // > 64 KiB of dynamic LDS needs the opt-in, per DEVICE; idempotent, races are harmless
-        static bool attr_set[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
-        if (dev < 0 || !attr_set[dev]) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lora_kernel<MODE, RMS>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (kMaxK + kLdsTail) * 4);
-            if (e != hipSuccess) return (int)e;
-            if (dev >= 0) attr_set[dev] = true;
-        }
-    }
-    hipLaunchKernelGGL((lora_kernel<MODE, RMS>), grid, dim3(kThreads), lds, stream, p);
-    return (int)hipGetLastError();
+    return qpal::launch_lds<lora_kernel<MODE, RMS>>(grid, dim3(kThreads), lds, (kMaxK + kLdsTail) * 4, stream, p);
 }
 
 extern "C" int qpal_lora_apply(float *out, long ld_out, const void *in, int in_mode, float rms_eps, const void *rms_weight,

@@ -1,4 +1,5 @@
 // Instantiates the SIMT-format GEMV kernels for one batch width QPAL_NB.
+#include "launch.h"
 #include "lut_kernels_api.h"
 
 namespace qpal {
@@ -11,16 +12,9 @@ int QPAL_CAT(launch_simt_gemv_nb, QPAL_NB)(const SimtParams &p, int bits, int ve
     if (bits == B_ && vec == V_) {                                                                      \
         if constexpr (QPAL_NB == 1) {                                                                   \
             if (g.x_lds) {  /* dynamic LDS beside a static image: lift the 64 KiB default once per device */ \
-                auto kern = simt_gemv_kernel<B_, V_, 1, true>;                                          \
-                static bool latched[64] = {};                                                           \
-                int dev = 0;                                                                            \
-                if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;                 \
-                if (dev < 0 || !latched[dev]) {                                                         \
-                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                       160 * 1024 - SimtCodec<B_, V_>::LDS_DWORDS * 4); \
-                    if (e != hipSuccess) return (int)e;                                                 \
-                    if (dev >= 0) latched[dev] = true;                                                  \
-                }                                                                                       \
+                constexpr auto kern = simt_gemv_kernel<B_, V_, 1, true>;                                \
+                const int rc = lds_opt_in<kern>(160 * 1024 - SimtCodec<B_, V_>::LDS_DWORDS * 4);        \
+                if (rc != 0) return rc;                                                                 \
                 hipLaunchKernelGGL(kern, dim3(g.grid), dim3(g.threads), g.dyn_lds, stream, p, g.split);          \
                 return (int)hipGetLastError();                                                          \
             }                                                                                           \

@@ -480,6 +480,28 @@ def test_batch_one_kernels(dev, shape, ctx):
         _report("batch-1", family, w, f"{_id(shape)} ctx={ctx}")
 
 
+@pytest.mark.gpu
+def test_batch_one_kernel_opts_in_to_its_lds_at_every_head_size(dev):
+    """qpal_attn_rope_decode WITHOUT a workspace at 16384 positions: the one-workgroup-per-head kernel asks for 4 * (16384 + 18 hd +
+    32) bytes of dynamic LDS — 74 880 at hd 128, 70 272 at hd 64, both above the 64 KiB a kernel gets without the opt-in.  Both
+    head sizes in one process, in this order: the opt-in belongs to a kernel, and a latch the head sizes share refuses whichever
+    comes second."""
+    ctx = 16384
+    for shape in ((8, 1, 128), (8, 8, 64)):
+        nq, nkv, hd = shape
+        worst = {}
+        for i, pos in enumerate((16383, 8191)):
+            for family in ("census", "needle"):
+                prob = Problem(dev, shape, ctx, F16, family, pos, 1, 400 + i, needle_at=(pos, pos // 64 * 64)[i])
+                pos_t = torch.tensor([pos], dtype=torch.long, device=dev)
+                out = torch.full((1, nq * hd), float("nan"), dtype=F16, device=dev)
+                _attn_rope_decode(prob.q32[0], prob.k32[0], prob.v32[0], prob.kc, prob.vc, out, pos_t, prob.inv, shape, prob.scale, None)
+                torch.cuda.synchronize()  # (the launch returned QPAL_OK: check() raises on anything else)
+                worst[family] = max(worst.get(family, 0.0), prob.worst(out, 0.0))
+        for family, w in worst.items():
+            _report("batch-1", family, w, f"{_id(shape)} ctx={ctx} no workspace")
+
+
 # ---- prefill
 
 PF_T = [1, 15, 16, 17, 32, 33, 127, 128]
