@@ -491,6 +491,29 @@ int qpal_lm_head_logits(const float *h_f32, long ld_h, const void *rms_w_f16, fl
 int qpal_sample(const float *logits_f32, long ld_logits, int rows, int vocab, const float *temperature, const int *top_k,
                 const float *top_p, const long *seed, const long *ctr, long *token, void *stream);
 
+/* qpal_sample with three more truncation filters: min-p, top-a and typical-p (csrc/sample.hip), still one launch.
+ * min_p / top_a / typical_p fp32 [rows] on the device, never read by the host; each may be NULL, which turns that filter off for
+ * every row (all three NULL: the launch of qpal_sample).  Shapes, alignment (4 bytes for the three) and return codes are
+ * qpal_sample's, all decided on the host before any stream work.  Steps 1 - 4 of qpal_sample hold word for word: inactive rows,
+ * greedy rows, the top-k set K and the nucleus N.  Between step 4 and the race, for row b:
+ *  4a. The one distribution: w[i] = exp(z[i] - zmax) for i in N (zmax the maximum over K; it lies in N), S = sum over N of w, q[i] =
+ *      w[i] / S — the tempered distribution renormalised over N.  ALL THREE filters are judged on this one q and the kept set is
+ *      the intersection R = N ∩ A ∩ B ∩ C: there is no renormalisation between the three and no order among them (libraries that
+ *      chain the filters renormalise after each and so depend on their order; this entry does not).
+ *      min-p, on iff min_p[b] > 0 (values above 1 read as 1):  A = {i : q[i] >= min_p max q} = {i : w[i] >= min_p}.
+ *      top-a, on iff top_a[b] > 0:  B = {i : q[i] >= top_a (max q)^2} = {i : w[i] >= top_a / S}.
+ *      typical-p, on iff 0 < typical_p[b] < 1:  c = sum over N of q[i] (zmax - z[i]) (the entropy of q is c + ln S, so -ln q[i] - H =
+ *      (zmax - z[i]) - c), d[i] = |(zmax - z[i]) - c|, C = {i in N : d[i] <= delta}, delta the smallest value among the d's with
+ *      sum{q[j] : d[j] <= delta} >= typical_p; ties at delta are all kept (step 4's rule mirrored).
+ *      R empty (typical-p can exclude the likeliest token, which min-p keeps): R = the one token argmax l over N, lowest id on ties.
+ *      +inf logits share the mass equally and have d = 0; no logit above -inf: token 0; a NaN logit is never kept.
+ *  5. The race of qpal_sample, over R.
+ * A row on which none of the three is on takes steps 1 - 5 of qpal_sample: its token is bitwise the one qpal_sample returns.
+ * A draw depends on (seed, ctr, token index, the row's logits and parameters) and on nothing else; two launches are bitwise equal. */
+int qpal_sample_trunc(const float *logits_f32, long ld_logits, int rows, int vocab, const float *temperature, const int *top_k,
+                      const float *top_p, const float *min_p, const float *top_a, const float *typical_p,
+                      const long *seed, const long *ctr, long *token, void *stream);
+
 /* Log-probability of ONE token per row under the plain softmax of the row's raw logits (temperature 1, no top-k / top-p: what
  * "logprobs" means to a sampler's user and what a cross-entropy sums), one launch (csrc/logprob.hip).  logits fp32
  * [rows][ld_logits], 1 <= rows <= 128, 1 <= vocab <= 2^30, ld_logits >= vocab — the shapes and return codes of qpal_sample.  token int64

@@ -15,8 +15,16 @@ at 8 slots with drafts of 4 and 15 one-byte tokens (chains of dependent table re
 its two yardsticks: qpal_token_logprob (two passes over the row) below and qpal_sample with top_k = N, top_p = 0.9 (eight passes)
 above.  The three launches alternate for three rounds; the figures are the medians.
 
+--truncation times the draw alone and nothing else: qpal_sample on every row type of tests/test_sampling.py, and
+qpal_sample_trunc with neutral rows, min-p only (--min-p), top-a only (--top-a), typical-p only (--typical-p) and all three behind
+top-k 50 / top-p 0.9.  Every figure is us per launch from a captured graph of --iters launches, replayed --rounds times; the
+variants alternate within a round (A/B in one process), and median, least and largest round are kept.  --parent-lib PATH loads a
+second build of the library (the parent commit's) and times its qpal_sample in the same rounds.
+
     python perf/sampling_kernels.py [--vocab 128256] [--k 4096] [--rows 1 8 64 128] [--iters 20] [--warmup 5] [--grammar]
                                     [--top-logprobs 5 20 64]
+    python perf/sampling_kernels.py --truncation [--rows 1 8 128] [--min-p 0.05] [--top-a 0.2] [--typical-p 0.9] [--rounds 9]
+                                    [--parent-lib PATH]
 """
 import argparse
 import ctypes
@@ -125,6 +133,79 @@ def top_logprob_launches(smp, ctr, tok, ns, iters, warmup):
     return out
 
 
+# (temperature, top_k, top_p) by row type: tests/test_sampling.py::TYPES without the inactive row; top_k -1 stands for vocab + 10
+SAMPLE_TYPES = {"greedy": (0.0, 0, 1.0), "t0.6_k5": (0.6, 5, 1.0), "t1_no_filter": (1.0, 0, 1.0), "t0.8_p0.95": (0.8, 0, 0.95),
+                "t0.7_k50_p0.9": (0.7, 50, 0.9), "t0.9_k_above_vocab": (0.9, -1, 1.0)}
+
+
+def truncation_launches(args, dev):
+    """the measurement of DESIGN.md §30: graphs of args.iters launches each, replayed in alternation"""
+    lib = qp._native.lib()
+    parent = None
+    if args.parent_lib:
+        parent = ctypes.CDLL(args.parent_lib)
+        parent.qpal_sample.argtypes, parent.qpal_sample.restype = qp._native._SIGNATURES["qpal_sample"], ctypes.c_int
+    s = torch.cuda.Stream(dev)
+    out = {"what": "qpal_sample / qpal_sample_trunc alone, us per launch (graph replays of %d launches, %d alternating rounds)"
+                   % (args.iters, args.rounds), "vocab": args.vocab, "parent_lib": args.parent_lib, "rows": []}
+    gen = torch.Generator(device=dev).manual_seed(1)
+    for rows in args.rows:
+        logits = torch.randn(rows, args.vocab, device=dev, generator=gen) * 2.0
+        ctr = torch.arange(rows, dtype=torch.int64, device=dev)
+        variants = {}   # name -> (graph, passes over the row, the sampler that owns the parameter tensors)
+
+        def capture(name, passes, smp, entry):
+            tok = torch.zeros(rows, dtype=torch.int64, device=dev)
+            head = [logits.data_ptr(), logits.stride(0) if rows > 1 else args.vocab, rows, args.vocab, smp.temperature.data_ptr(),
+                    smp.top_k.data_ptr(), smp.top_p.data_ptr()]
+            tail = [smp.seed.data_ptr(), ctr.data_ptr(), tok.data_ptr(), s.cuda_stream]
+            trunc = [getattr(smp, n).data_ptr() for n in qp.sampling.TRUNCATION] if entry == "trunc" else []
+            fn = {"new": lib.qpal_sample, "parent": parent.qpal_sample if parent else None, "trunc": lib.qpal_sample_trunc}[entry]
+            with torch.cuda.stream(s):
+                for _ in range(args.warmup):
+                    qp._native.check(fn(*head, *trunc, *tail), name)
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, stream=s):
+                    for _ in range(args.iters):
+                        qp._native.check(fn(*head, *trunc, *tail), name)
+            variants[name] = (g, passes, (smp, tok))
+
+        for name, (t, k, p) in SAMPLE_TYPES.items():
+            k = args.vocab + 10 if k < 0 else k
+            passes = 1 + (3 if 1 < k < args.vocab and t > 0 else 0) + (4 if 0 < p < 1 and t > 0 else 0)
+            smp = qp.Sampler(rows, args.vocab, dev, temperature=t, top_k=k, top_p=p, seed=list(range(rows)), truncation=True)
+            capture("sample_" + name, passes, smp, "new")
+            if parent:
+                capture("parent_sample_" + name, passes, smp, "parent")
+            capture("trunc_neutral_" + name, passes, smp, "trunc")
+        for name, (t, k, p, mp, ta, ty, passes) in {
+                "trunc_min_p": (1.0, 0, 1.0, args.min_p, 0.0, 1.0, 2), "trunc_top_a": (1.0, 0, 1.0, 0.0, args.top_a, 1.0, 3),
+                "trunc_typical_p": (1.0, 0, 1.0, 0.0, 0.0, args.typical_p, 6),
+                "trunc_all_three_k50_p0.9": (0.7, 50, 0.9, args.min_p, args.top_a, args.typical_p, 12)}.items():
+            smp = qp.Sampler(rows, args.vocab, dev, temperature=t, top_k=k, top_p=p, min_p=mp, top_a=ta, typical_p=ty,
+                             seed=list(range(rows)), truncation=True)
+            capture(name, passes, smp, "trunc")
+        us = {name: [] for name in variants}
+        with torch.cuda.stream(s):
+            for _ in range(args.rounds):
+                for name, (g, _, _) in variants.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(s)
+                    g.replay()
+                    e1.record(s)
+                    e1.synchronize()
+                    us[name].append(e0.elapsed_time(e1) / args.iters * 1e3)
+        res = {"rows": rows, "launches": {}}
+        for name, v in us.items():
+            v = sorted(v)
+            res["launches"][name] = {"passes": variants[name][1], "us_median": v[len(v) // 2], "us_min": v[0], "us_max": v[-1]}
+        out["rows"].append(res)
+        del variants
+    print(json.dumps(out))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--vocab", type=int, default=128256)
@@ -135,10 +216,18 @@ def main(argv=None):
     ap.add_argument("--top-logprobs", type=int, nargs="+", default=[], metavar="N",
                     help="also time qpal_top_logprob with these list lengths between qpal_token_logprob and qpal_sample(top_k = N, top_p = 0.9)")
     ap.add_argument("--grammar", action="store_true", help="also time the grammar launches (mask beside the processor, rows, advance, load)")
+    ap.add_argument("--truncation", action="store_true", help="time qpal_sample and qpal_sample_trunc alone (DESIGN.md §30) and nothing else")
+    ap.add_argument("--min-p", type=float, default=0.05)
+    ap.add_argument("--top-a", type=float, default=0.2)
+    ap.add_argument("--typical-p", type=float, default=0.9)
+    ap.add_argument("--rounds", type=int, default=9, help="--truncation: alternating rounds of graph replays")
+    ap.add_argument("--parent-lib", default=None, help="--truncation: another build of libqpal_hip.so whose qpal_sample is timed beside this one's")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
     dev = torch.device("cuda", 0)
+    if args.truncation:
+        return truncation_launches(args, dev)
     gen = torch.Generator(device=dev).manual_seed(1)
     W = (torch.randn(args.vocab, args.k, device=dev, generator=gen) * 0.02).half()
     w_ln = torch.ones(args.k, dtype=torch.float16, device=dev)

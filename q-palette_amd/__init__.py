@@ -25,7 +25,8 @@ Layout:
   speculative.py   spec_draft / spec_accept (csrc/spec.hip): prompt-lookup drafts and the packing of a verify step, exact-match
                    acceptance and the state update, all on the device; reference_spec_draft / reference_spec_accept: the contracts
   sampling.py      lm_head_logits (final norm + lm_head for up to 128 rows), sample / Sampler (temperature, top-k, top-p, seeded
-                   draw; per-slot parameters on the device), reference_draw (the draw's contract in numpy fp64);
+                   draw; per-slot parameters on the device; with min_p / top_a / typical_p the truncating draw of csrc/sample.hip),
+                   reference_draw (the draw's contract in numpy fp64) and truncation_mask (the set the three filters keep);
                    token_logprobs (log softmax of a row at one token, csrc/logprob.hip) and its contract reference_logprob;
                    top_logprobs (the n likeliest tokens of a row and their log-probabilities, csrc/top_logprob.hip) and its
                    contract reference_top_logprobs
@@ -81,7 +82,7 @@ from .attention import paged_ragged_prefill_attention, ragged_prefill_attention,
 from . import paging  # noqa: F401
 from .paging import PagedKVCache, SharedPrefix  # noqa: F401
 from . import sampling  # noqa: F401
-from .sampling import Sampler, lm_head_logits, reference_draw, reference_logprob, sample, token_logprobs  # noqa: F401
+from .sampling import Sampler, lm_head_logits, reference_draw, reference_logprob, sample, token_logprobs, truncation_mask  # noqa: F401
 from .sampling import reference_top_logprobs, top_logprobs  # noqa: F401
 from . import logits  # noqa: F401
 from .logits import LogitProcessor, reference_process  # noqa: F401

@@ -86,6 +86,7 @@ _SIGNATURES = {
     "qpal_lm_head_ws_bytes": [_I],
     "qpal_lm_head_logits": [_P, ctypes.c_long, _P, _F, _P, _P, ctypes.c_long, _I, _I, _I, _P],
     "qpal_sample": [_P, ctypes.c_long, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "qpal_sample_trunc": [_P, ctypes.c_long, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "qpal_token_logprob": [_P, ctypes.c_long, _I, _I, _P, _P, _P, _P, _P, _P],
     "qpal_top_logprob": [_P, ctypes.c_long, _I, _I, _I, _P, _P, _P, _P, _P],
     "qpal_spec_draft": [_P, ctypes.c_long, _P, _P, _P, _P, _I, _I, _I, _I, _I, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P],

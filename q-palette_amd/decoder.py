@@ -15,7 +15,9 @@ own (70B: 8192).  `generic=True` runs a batch of one the way every larger batch 
 
 With `sampler=sampling.Sampler(B, vocab, device, ...)` the step ends in `qpal_lm_head_logits` + `qpal_sample` at every B instead of
 an argmax: out_tok[b] is drawn with slot b's temperature / top-k / top-p / seed and the counter pos[b] (DESIGN.md §14);
-sampler.logits holds the step's logits.  A sampler built with logprobs=True adds `qpal_token_logprob` on the drawn tokens
+sampler.logits holds the step's logits.  A sampler built with min_p / top_a / typical_p draws with `qpal_sample_trunc` in the same
+place, in every step class below (the same launch count; the speculative step stays lossless, a draw depends on
+(seed, ctr, logits, parameters) only).  A sampler built with logprobs=True adds `qpal_token_logprob` on the drawn tokens
 (sampler.logprob), one built with top_logprobs=n `qpal_top_logprob` behind it (sampler.top_id / sampler.top_logprob
 [B, n]: the n likeliest tokens of every row that drew): one more launch each, in every step class below, and `Score(...,
 top_logprobs=n)` has the lists at every scored position.
@@ -674,7 +676,7 @@ class RaggedStep(_Rows):
         self._inactive = torch.full((S,), -1, dtype=torch.int64, device=dev)
         self.last32 = torch.zeros(S, self.h32.shape[1], dtype=torch.float32, device=dev)  # each segment's last row of the stream
         # the draw's per-segment parameters: greedy, or gathered from the sampler's slots seq[s] in every call
-        self.draw = sampling.Sampler(S, vocab, dev, temperature=0.0, logprobs=logprobs, top_logprobs=top_n)
+        self.draw = sampling.Sampler(S, vocab, dev, temperature=0.0, logprobs=logprobs, top_logprobs=top_n, truncation=self._truncating())
 
     def _attention(self, i, q, k, v, out):
         kc, vc = self.kcache[i], self.vcache[i]
@@ -695,9 +697,13 @@ class RaggedStep(_Rows):
         held = (self._row_id >= row0[seg]) & (self._row_id < row0[seg + 1]) & (slot >= 0) & (slot < self.slots)
         torch.where(held, self.adapters.slot_adapter[slot.clamp(0, self.slots - 1).to(torch.int64)], self._no_adapter, out=self.row_adapter)
 
+    def _truncating(self):
+        """the sampler carries min_p / top_a / typical_p: self.draw does too, and the draw is qpal_sample_trunc"""
+        return self.sampler is not None and self.sampler.min_p is not None
+
     def _gather_draw(self, slot):
         """the sampler's parameters of the slots `slot` (int64, one per row of self.draw) into self.draw, on the device"""
-        for name in ("temperature", "top_k", "top_p", "seed"):
+        for name in ("temperature", "top_k", "top_p", "seed") + (sampling.TRUNCATION if self._truncating() else ()):
             torch.index_select(getattr(self.sampler, name), 0, slot, out=getattr(self.draw, name))
 
     def hidden(self):
@@ -842,7 +848,8 @@ class SpeculativeStep(RaggedStep):
         B, K = self.segments, self.draft_len
         self.drawn = torch.zeros(self.rows, dtype=torch.int64, device=dev)
         self.out_tok = torch.zeros(B, K + 1, dtype=torch.int64, device=dev)
-        self.draw = sampling.Sampler(self.rows, vocab, dev, temperature=0.0, logprobs=logprobs, top_logprobs=top_n)  # greedy unless gathered
+        self.draw = sampling.Sampler(self.rows, vocab, dev, temperature=0.0, logprobs=logprobs, top_logprobs=top_n,
+                                     truncation=self._truncating())  # greedy unless gathered
         self.out_logprob = torch.zeros(B, K + 1, dtype=torch.float32, device=dev) if logprobs else None
         self.out_top_id = torch.full((B, K + 1, top_n), -1, dtype=torch.int32, device=dev) if top_n else None
         self.out_top_logprob = torch.full((B, K + 1, top_n), float("-inf"), dtype=torch.float32, device=dev) if top_n else None

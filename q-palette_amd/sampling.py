@@ -18,6 +18,9 @@ a prompt.  ``reference_logprob`` is its contract in numpy fp64.
 ``Sampler(..., top_logprobs=n)`` makes that one more launch of the tail (``smp.top_id``, ``smp.top_logprob``), ``decoder.Score(...,
 top_logprobs=n)`` runs it on every row; ``reference_top_logprobs`` is its contract.
 
+``Sampler(..., min_p=0.05)`` (or top_a=, typical_p=, or truncation=True) adds the three truncation filters: the draw is then
+``qpal_sample_trunc``, still one launch; ``truncation_mask`` is the set it keeps.
+
 The draw is specified exactly (include/qpal.h); ``reference_draw`` restates it in numpy fp64 with its own Philox.
 It is the specification the tests hold the kernel to: CPU only, no torch.cuda, no library call.
 """
@@ -89,6 +92,46 @@ def nucleus_mask(p, kmask, top_p):
     return kmask & (p >= tau)
 
 
+def truncation_mask(l, T, nmask, min_p=0.0, top_a=0.0, typical_p=1.0, fallback=True, tol_d=0.0):
+    """step 4a (qpal_sample_trunc) on l (fp32 values, NaN already -inf) at temperature T > 0: R = N ∩ A ∩ B ∩ C for the
+    nucleus nmask, all three judged on the one q = the tempered distribution renormalised over N.  min_p > 0: A = {w >= min(min_p,
+    1)}, w = exp(z - zmax); top_a > 0: B = {w >= top_a / S}, S = sum of w over N; 0 < typical_p < 1: C = {d <= delta}, d = |(zmax -
+    z) - c|, c = sum of q (zmax - z), delta the smallest value among the d's with sum{q[j] : d[j] <= delta} >= typical_p (ties at
+    delta all kept).  An empty R is the one token argmax l over N, lowest id (fallback=False: the empty set, for tests that build
+    inner sets).  tol_d: C = {d <= delta + tol_d}, for tests that build inner (< 0) and outer (> 0) sets.  +inf logits share the
+    mass equally and have d = 0; no logit above -inf in N: N itself."""
+    nmask = np.asarray(nmask, dtype=bool)
+    min_p, top_a, typical_p = float(min_p), float(top_a), float(typical_p)
+    on_t = 0.0 < typical_p < 1.0
+    if not (min_p > 0.0 or top_a > 0.0 or on_t):
+        return nmask.copy()
+    z = np.where(nmask, l.astype(np.float64) / float(T), -np.inf)
+    zmax = z.max()
+    if zmax == -np.inf:
+        return nmask.copy()
+    with np.errstate(invalid="ignore"):
+        gap = np.where(z == zmax, 0.0, zmax - z)  # inf - inf: a copy of a +inf maximum is at gap 0
+    w = np.where(nmask, np.exp(-gap), 0.0)
+    S = w.sum()
+    keep = nmask.copy()
+    if min_p > 0.0:
+        keep &= w >= min(min_p, 1.0)
+    if top_a > 0.0:
+        keep &= w >= top_a / S
+    if on_t:
+        q = w / S
+        c = float((q[w > 0] * gap[w > 0]).sum())
+        d = np.abs(gap - c)
+        vals, inv = np.unique(d[nmask], return_inverse=True)  # ascending
+        cum = np.cumsum(np.bincount(inv, weights=q[nmask], minlength=vals.shape[0]))  # mass of {d <= vals[j]}
+        j = int(np.searchsorted(cum, typical_p, side="left"))
+        delta = vals[min(j, vals.shape[0] - 1)]
+        keep &= d <= delta + float(tol_d)
+    if fallback and not keep.any():
+        keep[int(np.argmax(np.where(nmask, l, -np.inf)))] = True
+    return keep
+
+
 def clean_logits(logits_row):
     """fp32 logits as the kernel sees them, NaN -> -inf (a NaN logit is never kept)"""
     l = np.asarray(logits_row, dtype=np.float32).copy()
@@ -96,8 +139,9 @@ def clean_logits(logits_row):
     return l
 
 
-def reference_draw(logits_row, temperature, top_k, top_p, seed, ctr):
-    """The contract of qpal_sample for one row, in fp64.  temperature / top_p are rounded to fp32 first (what the kernel is given).
+def reference_draw(logits_row, temperature, top_k, top_p, seed, ctr, min_p=0.0, top_a=0.0, typical_p=1.0):
+    """The contract of qpal_sample for one row, in fp64, and with min_p / top_a / typical_p that of qpal_sample_trunc (step 4a:
+    truncation_mask on the nucleus).  temperature / top_p and the three are rounded to fp32 first (what the kernel is given).
     ctr: an int -> the token (None for ctr < 0: the row is inactive), or an int array of non-negative counters -> tokens."""
     if np.ndim(ctr) == 0 and int(ctr) < 0:
         return None
@@ -109,6 +153,7 @@ def reference_draw(logits_row, temperature, top_k, top_p, seed, ctr):
         return tok if scalar else np.full(np.shape(ctr), tok, dtype=np.int64)
     kmask = topk_mask(l, top_k)
     kept = nucleus_mask(probabilities(l, T, kmask), kmask, P)
+    kept = truncation_mask(l, T, kept, float(np.float32(min_p)), float(np.float32(top_a)), float(np.float32(typical_p)))
     z = l.astype(np.float64) / T
     s = np.atleast_2d(race_scores(z, seed, ctr))
     s = np.where(kept[None, :] & (z[None, :] > -np.inf), s, -np.inf)
@@ -194,6 +239,9 @@ def lm_head_logits(h32, norm_weight, eps, lm_head, out=None):
     return out
 
 
+TRUNCATION = ("min_p", "top_a", "typical_p")  # the per-slot vectors of a truncating Sampler, in qpal_sample_trunc's order
+
+
 def _param(t, name, dtype, rows, dev, who):
     from ._native import QpalError
     if t.dtype != dtype or t.shape != (rows,) or t.device != dev or not t.is_contiguous():
@@ -204,7 +252,9 @@ def _param(t, name, dtype, rows, dev, who):
 def sample(logits, params, ctr, out=None, vocab=None):
     """token int64 [rows]: one draw per row of logits fp32 [rows, >= vocab] (contiguous rows; vocab defaults to the width) with
     params.temperature / top_k / top_p / seed ([rows] device tensors: a Sampler, or a view of one) and the counter ctr int64 [rows]
-    (the position; < 0: the row is inactive and out[row] keeps what it held).  Launches on the current stream; no host read."""
+    (the position; < 0: the row is inactive and out[row] keeps what it held).  params built with the truncation filters (min_p /
+    top_a / typical_p are tensors, not None): ``qpal_sample_trunc`` with them; otherwise ``qpal_sample``.  Launches on the current
+    stream; no host read."""
     torch = _torch()
     from . import _native
     who, QpalError = "sample", _native.QpalError
@@ -222,9 +272,16 @@ def sample(logits, params, ctr, out=None, vocab=None):
         out = torch.zeros(rows, dtype=torch.int64, device=dev)
     else:
         _param(out, "out", torch.int64, rows, dev, who)
+    if getattr(params, "min_p", None) is None:
+        with torch.cuda.device(dev):
+            rc = _native.lib().qpal_sample(logits.data_ptr(), ld, rows, vocab, *ptrs, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        _native.check(rc, "qpal_sample")
+        return out
+    trunc = [_param(getattr(params, name), name, torch.float32, rows, dev, who) for name in TRUNCATION]
     with torch.cuda.device(dev):
-        rc = _native.lib().qpal_sample(logits.data_ptr(), ld, rows, vocab, *ptrs, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    _native.check(rc, "qpal_sample")
+        rc = _native.lib().qpal_sample_trunc(logits.data_ptr(), ld, rows, vocab, *ptrs[:3], *trunc, *ptrs[3:], out.data_ptr(),
+                                             torch.cuda.current_stream(dev).cuda_stream)
+    _native.check(rc, "qpal_sample_trunc")
     return out
 
 
@@ -301,9 +358,12 @@ class Sampler:
     token_logprobs; one more launch); otherwise logprob is None.  top_logprobs=n (1 .. 64): the sampler also owns top_id int32 [B, n]
     and top_logprob fp32 [B, n], and a step with this sampler writes the n likeliest tokens of each row that drew and their
     log-probabilities there (top_logprobs, under the same plain softmax of the logits the draw saw; one more launch); 0 or unset:
-    both are None."""
+    both are None.  min_p / top_a / typical_p (min_p <= 0, top_a <= 0, typical_p <= 0 or >= 1: that filter off): given
+    a non-neutral value, or with truncation=True, the sampler also owns min_p / top_a / typical_p fp32 [B] and draws with
+    ``qpal_sample_trunc``; otherwise the three are None and every launch is the plain sampler's."""
 
-    def __init__(self, B, vocab, device, temperature=1.0, top_k=0, top_p=1.0, seed=0, logprobs=False, top_logprobs=0):
+    def __init__(self, B, vocab, device, temperature=1.0, top_k=0, top_p=1.0, seed=0, logprobs=False, top_logprobs=0, min_p=0.0,
+                 top_a=0.0, typical_p=1.0, truncation=False):
         torch = _torch()
         from ._native import QpalError
         if not 1 <= int(B) <= 128 or int(vocab) < 1:
@@ -325,13 +385,22 @@ class Sampler:
             raise QpalError(f"Sampler: top_logprobs must be in 0 .. 64, got {top_logprobs}")
         self.top_id = torch.full((self.B, n), -1, dtype=torch.int32, device=self.device) if n else None
         self.top_logprob = torch.full((self.B, n), float("-inf"), dtype=torch.float32, device=self.device) if n else None
+        given = [torch.as_tensor(v, dtype=torch.float32).reshape(-1) for v in (min_p, top_a, typical_p)]
+        neutral = bool((given[0] <= 0).all()) and bool((given[1] <= 0).all()) and bool(((given[2] <= 0) | (given[2] >= 1)).all())
+        if truncation or not neutral:
+            self.min_p, self.top_a, self.typical_p = (full(v, torch.float32) for v in given)
+        else:
+            self.min_p = self.top_a = self.typical_p = None
 
-    def set(self, slot, temperature=None, top_k=None, top_p=None, seed=None):
-        """write one slot's parameters (those given)"""
+    def set(self, slot, temperature=None, top_k=None, top_p=None, seed=None, min_p=None, top_a=None, typical_p=None):
+        """write one slot's parameters (those given); min_p / top_a / typical_p only on a sampler built with them"""
         from ._native import QpalError
         if not 0 <= int(slot) < self.B:
             raise QpalError(f"Sampler.set: slot {slot} outside 0 .. {self.B - 1}")
-        for t, v in ((self.temperature, temperature), (self.top_k, top_k), (self.top_p, top_p), (self.seed, seed)):
+        if self.min_p is None and not (min_p is None and top_a is None and typical_p is None):
+            raise QpalError("Sampler.set: min_p / top_a / typical_p need a sampler built with them (a non-neutral value, or truncation=True)")
+        for t, v in ((self.temperature, temperature), (self.top_k, top_k), (self.top_p, top_p), (self.seed, seed), (self.min_p, min_p),
+                     (self.top_a, top_a), (self.typical_p, typical_p)):
             if v is not None:
                 t[int(slot)] = v
 
@@ -344,4 +413,5 @@ class Sampler:
         v.logprob = None if self.logprob is None else self.logprob[s]
         v.top_id = None if self.top_id is None else self.top_id[s]
         v.top_logprob = None if self.top_logprob is None else self.top_logprob[s]
+        v.min_p, v.top_a, v.typical_p = (None if self.min_p is None else getattr(self, name)[s] for name in TRUNCATION)
         return v
