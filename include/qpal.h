@@ -463,6 +463,40 @@ int qpal_attn_rope_prefill_ragged_paged(const float *q, const float *k, const fl
                                         int kv_fmt, int R, int S, int B, int nq, int nkv, int hd,
                                         float scale, void *ws, long ws_bytes, void *stream);
 
+/* SLIDING-WINDOW attention: the three launches above — batched decode, one-sequence prefill, ragged prefill — with a
+ * lower edge.  window = W >= 1: the row at position p attends to keys lo(p) .. p, lo(p) = max(0, p - W + 1): W keys with its own
+ * (Hugging Face's sliding_window).  window = 0: no window, the launch IS the sibling's.  window < 0: QPAL_E_PARAM, behind the null
+ * checks and in front of everything else.  One entry point per family serves both element formats (kv_fmt 0 fp16, 1 e4m3fn) and
+ * both storages: block_table (block_row) == NULL — contiguous caches of max_len positions, the paged arguments are ignored; else
+ * the pools and the table of the paged sibling, max_len = max_pages * page_size, the max_len argument is ignored.
+ * The rotary embedding, the append of every new k / v row, the inactive-slot and *pos0 fit rules and the stored bytes are the
+ * siblings'.  Nothing outside the window is read: cache rows below lo(pos[b]) (decode) or below lo of the launch's / segment's FIRST
+ * row (prefill, ragged) may hold anything, NaN included, and block-table entries of pages that lie wholly below that floor may be
+ * -1 (PagedKVCache.trim).  window >= max_len: bit for bit the sibling, output and caches.
+ * Decode: the sibling's arithmetic on the keys [lo, pos] — chunks cut on pos - lo; grid and LDS are those of min(max_len, window
+ * rounded up to 4) positions, so a short window in a long cache takes one chunk and no merge.  Prefill / ragged: a query tile walks
+ * the keys from the multiple of 32 at or below lo(its first row), the mask is per row; the chunks are sized for the longest span a
+ * tile can have (window + rows of a tile + 30).  ws: the sibling's qpal_attn_*_ws_bytes of max_len always suffices (a windowed
+ * launch never needs more, often none).  Other checks and codes: the siblings'. */
+int qpal_attn_rope_decode_batch_window(const float *q, const float *k, const float *v, long ld_qkv,
+                                       void *kcache, void *vcache, void *out_f16, long ld_out,
+                                       const long *pos, const float *inv_freq, const int *block_table /* NULL: contiguous */,
+                                       long ld_table, int num_pages, int page_size, int max_pages, int kv_fmt,
+                                       int B, int nq, int nkv, int hd, long max_len, float scale, long window,
+                                       void *ws, long ws_bytes, void *stream);
+int qpal_attn_rope_prefill_window(const float *q, const float *k, const float *v, long ld_qkv,
+                                  void *kcache, void *vcache, void *out_f16, long ld_out,
+                                  const long *pos0, const float *inv_freq, const int *block_row /* NULL: contiguous */,
+                                  int num_pages, int page_size, int max_pages, int kv_fmt,
+                                  int T, int nq, int nkv, int hd, long max_len, float scale, long window,
+                                  void *ws, long ws_bytes, void *stream);
+int qpal_attn_rope_prefill_ragged_window(const float *q, const float *k, const float *v, long ld_qkv,
+                                         void *kcache, void *vcache, void *out_f16, long ld_out,
+                                         const int *seq, const int *row0, const long *pos0, const float *inv_freq,
+                                         const int *block_table /* NULL: contiguous */, long ld_table, int num_pages, int page_size,
+                                         int max_pages, int kv_fmt, int R, int S, int B, int nq, int nkv, int hd,
+                                         long max_len, float scale, long window, void *ws, long ws_bytes, void *stream);
+
 /* Final norm + fp16 lm_head for `rows` rows of the residual stream at once, on the matrix pipe (csrc/lm_head_batch.hip): the
  * logits a sampler needs, and the batch-B tail of a decode step.  h_f32 fp32 [rows][ld_h] (ld_h >= k, in elements), 1 <= rows <=
  * 128; k a multiple of 512, 512 <= k <= 8192; w_f16 the lm_head fp16 [vocab][k]; logits_f32 fp32 [rows][ld_logits], ld_logits >=

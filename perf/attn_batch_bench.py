@@ -17,8 +17,11 @@ their own each (max_len = P + 512; --context and --full are not used).  On ONE p
 paged launch, then the shared pair (qpalette_amd.shared_prefix_decode_attention), 10 + iters launches each.  Under
 `rocprofv3 --kernel-trace` perf/shared_prefix_trace.py turns the trace of this call into per-block medians.
 
+--window W (0: context / 4 of every row): behind the contiguous launch of a row, the same launch with window=W on the
+same caches and positions: "us_per_launch_events_window" next to "kv_rows_window" = sum_b min(pos[b] + 1, W), the rows it has to read.
+
     python perf/attn_batch_bench.py [--batch 8 64] [--context 1024 4096] [--iters 200] [--full] [--kv fp16 fp8] [--paged 16 64]
-                                    [--shared-prefix 4096 1024] [--repeats 5]
+                                    [--shared-prefix 4096 1024] [--repeats 5] [--window W]
 """
 import argparse
 import json
@@ -100,6 +103,7 @@ def main(argv=None):
     ap.add_argument("--shared-prefix", type=int, nargs="*", default=[], metavar="P",
                     help="with --paged PAGE: slots that share a P-position prefix, the plain launch against the shared pair")
     ap.add_argument("--repeats", type=int, default=5, help="--shared-prefix: timed blocks of each launch, in turn")
+    ap.add_argument("--window", type=int, default=None, metavar="W", help="also time the launch with this sliding window (0: context / 4)")
     args = ap.parse_args(argv)
     if args.shared_prefix and (len(args.paged) != 1 or any(P % args.paged[0] or P < args.paged[0] for P in args.shared_prefix)):
         raise SystemExit("--shared-prefix: with ONE --paged PAGE, prefixes that are multiples of it")
@@ -133,20 +137,29 @@ def main(argv=None):
                         launch = lambda: qp.paged_decode_attention(q, k, v, kp, vp, table, pos, inv_freq, out=out, ws=ws)  # noqa: E731
                     else:
                         launch = lambda: qp.decode_attention(q, k, v, kc, vc, pos, inv_freq, out=out, ws=ws)  # noqa: E731
-                    for _ in range(10):
-                        launch()
-                    torch.cuda.synchronize()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(args.iters):
-                        launch()
-                    e1.record()
-                    torch.cuda.synchronize()
-                    us = e0.elapsed_time(e1) * 1e3 / args.iters
+                    def timed(launch):
+                        for _ in range(10):
+                            launch()
+                        torch.cuda.synchronize()
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for _ in range(args.iters):
+                            launch()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        return e0.elapsed_time(e1) * 1e3 / args.iters
+
+                    us = timed(launch)
                     row = {"batch": B, "context": L, "kv": kv, "full": args.full, "kv_rows": kv_rows, "kv_MB": nbytes / 1e6,
                            "us_per_launch_events": us, "TBps_events": nbytes / (us * 1e-6) / 1e12,
                            "workspace_bytes": 0 if ws is None else ws.numel() * 4,
                            "cache_bytes": 2 * qp.attention.kv_cache_bytes(B, nkv, L, hd, kc.dtype)}
+                    if args.window is not None and not ps:
+                        W = args.window or L // 4
+                        rows_w = int(torch.clamp(pos_h + 1, max=W).sum())
+                        us_w = timed(lambda: qp.decode_attention(q, k, v, kc, vc, pos, inv_freq, out=out, ws=ws, window=W))
+                        row.update({"window": W, "kv_rows_window": rows_w, "kv_MB_window": rows_w * nkv * hd * 2 * kc.element_size() / 1e6,
+                                    "us_per_launch_events_window": us_w})
                     if args.paged:
                         row["paged"] = ps
                     if ps:

@@ -9,8 +9,11 @@ Event timing here; for the kernel time proper run it under `rocprofv3 --kernel-t
 qpalette_amd.paged_prefill_attention, once per page size ("us_paged"), and the contiguous launch a second time
 ("us_prefill_attention_again": the spread the paged times are read against).
 
+--window W: per row also the launch with window=W on the same cache ("us_window"; "keys_window": the keys its rows
+attend to, sum_t min(pos0 + t + 1, W), next to "keys": sum_t (pos0 + t + 1)), then the plain launch again ("us_prefill_attention_again").
+
     python perf/attn_prefill_bench.py [--T 128] [--pos0 0 1920 3968] [--context 4096] [--heads 32 8 128] [--iters 50] [--kv fp16|fp8]
-                                      [--paged 16 64]
+                                      [--paged 16 64] [--window W]
 """
 import argparse
 import json
@@ -33,6 +36,7 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--kv", default="fp16", choices=["fp16", "fp8"], help="KV-cache element format")
     ap.add_argument("--paged", type=int, nargs="*", default=[], metavar="PAGE_SIZE", help="also time paged launches of these page sizes")
+    ap.add_argument("--window", type=int, default=None, metavar="W", help="also time the launch with this sliding window")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
@@ -74,6 +78,12 @@ def main(argv=None):
         flop = 4 * nq * hd * sum(pos0 + t + 1 for t in range(T))
         rows.append({"T": T, "pos0": pos0, "kv": args.kv, "flop": flop, "us_prefill_attention": us, "tflops": flop / us * 1e-6,
                      "us_torch_sdpa_causal_mask": us_sdpa})
+        if args.window:
+            rows[-1].update({"window": args.window, "keys": sum(pos0 + t + 1 for t in range(T)),
+                             "keys_window": sum(min(pos0 + t + 1, args.window) for t in range(T)),
+                             "us_window": timed(lambda: qp.prefill_attention(q, k, v, kc, vc, pos_t, inv_freq, out=out, ws=ws, window=args.window))})
+            if not args.paged:
+                rows[-1]["us_prefill_attention_again"] = timed(lambda: qp.prefill_attention(q, k, v, kc, vc, pos_t, inv_freq, out=out, ws=ws))
         if args.paged:
             rows[-1]["us_paged"] = {}
             for ps in args.paged:

@@ -38,7 +38,7 @@ reference (what the format itself moves; not a gate).
 shared_prefix=...) —, the plain step again behind them, and how far the two steps' final hidden states lie apart.
 
     python perf/decode_llama_batch.py [--model 3_8b] [--batch 1 8 16 32 64] [--context 1024] [--tokens 64] [--inactive 0] [--sample]
-                                      [--process] [--grammar] [--kv fp16|fp8] [--paged PAGE_SIZE] [--shared-prefix P]
+                                      [--process] [--grammar] [--kv fp16|fp8] [--paged PAGE_SIZE] [--shared-prefix P] [--window W]
 """
 import argparse
 import json
@@ -102,6 +102,8 @@ def main(argv=None, quiet=False):
                     help="also time the step on a paged cache of this page size (pages in a seeded random order; DESIGN.md §17)")
     ap.add_argument("--shared-prefix", type=int, default=0, metavar="P",
                     help="with --paged: also time the step both ways on pools whose slots share a P-position prefix (DESIGN.md §26)")
+    ap.add_argument("--window", type=int, default=0, metavar="W",
+                    help="also time the step with this sliding window in every layer (DecodeStep(window=W), DESIGN.md §31)")
     args = ap.parse_args(argv)
     kv8 = args.kv == "fp8"
     if args.shared_prefix and (not args.paged or args.shared_prefix % args.paged or args.shared_prefix < args.paged
@@ -227,6 +229,13 @@ def main(argv=None, quiet=False):
             paged = {"page_size": ps, "ms_step": timed(pstep), "ms_step_contiguous_again": timed(kernel_step),
                      "pool_bytes": 2 * nlayers * qp.attention.kv_cache_bytes(pages, nkv, ps, head_dim, kc[0].dtype)}
             del pstep, kp, vp, table
+        windowed = None
+        if args.window:
+            # the same caches, tokens and positions with a window in every layer, then the plain step again (the spread)
+            wstep = qp.DecodeStep(layers, embed, norm, lm_head, kc, vc, inv_freq, tok, pos, out_tok, generic=True, window=args.window)
+            windowed = {"window": args.window, "ms_step": timed(wstep), "ms_step_plain_again": timed(kernel_step),
+                        "kv_rows_attended_first_step": int(torch.clamp(pos0[pos0 >= 0] + 1, max=args.window).sum())}
+            del wstep
         shared = None
         if args.shared_prefix:
             P, ps, mp = args.shared_prefix, args.paged, args.context // args.paged
@@ -319,6 +328,8 @@ def main(argv=None, quiet=False):
             res["sampled"] = sampled
         if paged is not None:
             res["paged"] = paged
+        if windowed is not None:
+            res["window"] = windowed
         if shared is not None:
             res["shared_prefix"] = shared
         del kc, vc, kc_ref, vc_ref, ref_cache, kernel_step

@@ -14,8 +14,10 @@ Layout:
                    paged_decode_attention / paged_prefill_attention: both on page pools behind a block table;
                    shared_prefix_decode_attention / shared_prefix_workspace: paged decode that reads a forked prefix once per group;
                    ragged_prefill_attention / paged_ragged_prefill_attention / ragged_workspace: up to 128 rows of SEVERAL
-                   sequences in one launch (segments described on the device)
-  paging.py        PagedKVCache: per-layer page pools, the block table and the host-side page allocator (reserve / release / fork);
+                   sequences in one launch (segments described on the device);
+                   window= on all of these but the shared-prefix launch: sliding-window attention; window_floor: its lower edge
+  paging.py        PagedKVCache: per-layer page pools, the block table and the host-side page allocator (reserve / release / fork /
+                   trim: the pages a sliding window has passed go back to the pool);
                    SharedPrefix (cache.prefix): the groups of slots that share a forked prefix, as the shared-prefix launch reads them
   decoder.py       DecodeStep: the whole-model decode step at batch B >= 1 on the kernels above (per-layer launch sequence,
                    scratch buffers, final norm + lm_head + argmax, launches per token); Prefill: a prompt into one cache slot;
@@ -79,6 +81,7 @@ from .attention import attention_workspace, decode_attention, prefill_attention,
 from .attention import paged_decode_attention, paged_prefill_attention  # noqa: F401
 from .attention import reference_shared_rows, shared_prefix_decode_attention, shared_prefix_workspace  # noqa: F401
 from .attention import paged_ragged_prefill_attention, ragged_prefill_attention, ragged_workspace  # noqa: F401
+from .attention import window_floor  # noqa: F401
 from . import paging  # noqa: F401
 from .paging import PagedKVCache, SharedPrefix  # noqa: F401
 from . import sampling  # noqa: F401

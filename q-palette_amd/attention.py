@@ -38,6 +38,13 @@ sequences in one launch — prompt chunks and decode tokens side by side — cut
     ws = ragged_workspace(128, S, nq, nkv, hd, max_len, device)
     out = ragged_prefill_attention(q, k, v, kcache, vcache, seq, row0, pos0, inv_freq, ws=ws)
     out = paged_ragged_prefill_attention(q, k, v, kpool, vpool, block_table, seq, row0, pos0, inv_freq, ws=ws)
+
+Sliding window (``qpal_attn_rope_decode_batch_window`` / ``_prefill_window`` / ``_prefill_ragged_window``): every launch
+above except the shared-prefix one takes ``window=W``: the row at position p attends to keys ``window_floor(p, W) .. p``, W keys
+with its own (Hugging Face's ``sliding_window``); ``None`` is no window.  Rotary embedding, append, the inactive and fit rules and
+the stored bytes do not change; nothing below the floor is read, so those rows may hold anything and a paged cache may give their
+pages back (``PagedKVCache.trim(slot, window_floor(pos, W))``).  ``W >= max_len`` is bit for bit the launch without a window.  The
+workspaces above serve the windowed launches as they are.
 """
 import math
 
@@ -45,6 +52,29 @@ import torch
 
 from . import _native
 from ._native import QpalError
+
+
+def _window(window, who):
+    """the window argument of a launch: None, or an int >= 1"""
+    if window is None:
+        return None
+    if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+        raise QpalError(f"{who}: window must be None or an int >= 1, got {window!r}")
+    return window
+
+
+def window_floor(pos, window):
+    """lo(pos) = max(0, pos - window + 1): the first key the row at position pos attends to under ``window`` (None: 0).  pos: an int,
+    a numpy array or a torch tensor; the result has its kind.  Inactive positions (pos < 0) give 0."""
+    w = _window(window, "window_floor")
+    if isinstance(pos, torch.Tensor):
+        return torch.zeros_like(pos) if w is None else (pos - (w - 1)).clamp(min=0)
+    if isinstance(pos, int):
+        return 0 if w is None else max(0, pos - w + 1)
+    import numpy as np
+
+    pos = np.asarray(pos)
+    return np.zeros_like(pos) if w is None else np.maximum(pos - (w - 1), 0)
 
 
 def attention_workspace(B, nq, nkv, hd, max_len, device):
@@ -97,7 +127,7 @@ def _rows(t, name, B, width, who):
     return t.stride(0) if B > 1 else width
 
 
-def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=None, ws=None):
+def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=None, ws=None, window=None):
     """q fp32 [B, nq*hd], k / v fp32 [B, nkv*hd] (rows may be strided: column slices of one q|k|v output with a common row
     stride); kcache / vcache [B, nkv, max_len, hd] contiguous, 16-byte aligned, updated in place at row pos[b]; pos int64
     [B] on the device; inv_freq fp32 [hd/2].  Returns out fp16 [B, nq*hd] (``out`` if given: rows of an inactive sequence keep
@@ -106,17 +136,30 @@ def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=Non
     The caches' dtype selects the kernel: torch.float16 -> qpal_attn_rope_decode_batch; torch.float8_e4m3fn ->
     qpal_attn_rope_decode_batch_kv8 (the new row is stored as h.float().clamp(-448, 448).to(torch.float8_e4m3fn) of the fp16 row h
     and attended to at that value).  Caches of two different dtypes, or of any other dtype, raise QpalError before the library is
-    reached.  One attention_workspace serves both formats."""
+    reached.  One attention_workspace serves both formats.
+
+    window=W (an int >= 1): sequence b attends to positions window_floor(pos[b], W) .. pos[b] only (qpal_attn_rope_decode_batch_window);
+    cache rows below that floor are not read and may hold anything.  The attention_workspace of max_len serves it."""
+    window = _window(window, "decode_attention")
     if kcache.dim() != 4 or kcache.shape != vcache.shape:
         raise QpalError("decode_attention: kcache / vcache must both have shape [B, nkv, max_len, hd]")
     B, nkv, max_len, hd = kcache.shape
     entry = "qpal_attn_rope_decode_batch" + _cache_entry(kcache, vcache, "decode_attention")
-    return _decode("decode_attention", entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, None)
+    return _decode("decode_attention", entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, None,
+                   window=window)
 
 
-def _decode(who, entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, paged, groups=None):
+def _window_args(paged, empty, kcache, rows, max_len, scale, window):
+    """the arguments of a _window entry point between inv_freq and ws: the paged arguments (`empty`: their stand-in for a contiguous
+    cache, a null table), kv_fmt, the rows' shape, max_len (paged: ignored), scale, window"""
+    head = empty + (_KV_FMT[kcache.dtype],) if paged is None else paged
+    return head + rows + (max_len if paged is None else 0, scale, window)
+
+
+def _decode(who, entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, paged, groups=None, window=None):
     """the checks and the launch the decode entry points share; paged: None, or the arguments that take max_len's place; groups: None,
-    or the G of a shared-prefix launch (its workspace is shared_prefix_workspace's)"""
+    or the G of a shared-prefix launch (its workspace is shared_prefix_workspace's); window: None, or the W of the _window entry
+    point, which then takes `entry`'s place"""
     def pos_check():
         if pos.dtype != torch.int64 or pos.shape != (B,) or pos.device != kcache.device or not pos.is_contiguous():
             raise QpalError(f"{who}: pos must be a contiguous int64 [{B}] tensor on {kcache.device}")
@@ -129,10 +172,14 @@ def _decode(who, entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, 
         need, maker = lib.qpal_attn_prefix_ws_bytes(B, groups, nq, nkv, hd, max_len), "shared_prefix_workspace"
     ws_ptr, ws_bytes = _launch_ws(who, need, ws, kcache, maker)
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
+    if window is None:
+        shape = ((B, nq, nkv, hd, max_len) if paged is None else paged + (B, nq, nkv, hd)) + (scale,)
+    else:
+        entry, shape = "qpal_attn_rope_decode_batch_window", _window_args(paged, (None, 0, 0, 0, 0), kcache, (B, nq, nkv, hd), max_len, scale, window)
     with torch.cuda.device(kcache.device):
         rc = getattr(lib, entry)(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
-            pos.data_ptr(), inv_freq.data_ptr(), *((B, nq, nkv, hd, max_len) if paged is None else paged + (B, nq, nkv, hd)), scale,
+            pos.data_ptr(), inv_freq.data_ptr(), *shape,
             ws_ptr, ws_bytes, torch.cuda.current_stream(kcache.device).cuda_stream)
     _native.check(rc, entry)
     return out
@@ -145,7 +192,7 @@ def prefill_workspace(T, nq, nkv, hd, max_len, device):
     return _workspace("qpal_attn_prefill_ws_bytes", device, T, nq, nkv, hd, max_len)
 
 
-def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=None, ws=None):
+def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=None, ws=None, window=None):
     """q fp32 [T, nq*hd], k / v fp32 [T, nkv*hd], 1 <= T <= 128: row t is the token at position pos0 + t (rows may be strided:
     column slices of one q|k|v output with a common row stride); kcache / vcache [nkv, max_len, hd] of ONE sequence,
     contiguous, 16-byte aligned (``kcache[b]`` of the batched layout), updated in place at rows pos0 .. pos0 + T - 1; pos0 int64
@@ -156,13 +203,18 @@ def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=N
     The caches' dtype selects the kernel: torch.float16 -> qpal_attn_rope_prefill; torch.float8_e4m3fn -> qpal_attn_rope_prefill_kv8
     (new rows are stored as h.float().clamp(-448, 448).to(torch.float8_e4m3fn) of the fp16 rows h and attended to at that value: the
     cache ends up byte for byte as decode_attention would have filled it token by token).  Caches of two different dtypes, or of any
-    other dtype, raise QpalError before the library is reached.  One prefill_workspace serves both formats."""
+    other dtype, raise QpalError before the library is reached.  One prefill_workspace serves both formats.
+
+    window=W (an int >= 1): row t attends to positions window_floor(pos0 + t, W) .. pos0 + t only (qpal_attn_rope_prefill_window); the
+    cache ends up byte for byte as without a window, rows below window_floor(pos0, W) are not read and may hold anything.  The
+    prefill_workspace of max_len serves it."""
     who = "prefill_attention"
+    window = _window(window, who)
     if kcache.dim() != 3 or kcache.shape != vcache.shape:
         raise QpalError(f"{who}: kcache / vcache must both have shape [nkv, max_len, hd]")
     nkv, max_len, hd = kcache.shape
     entry = "qpal_attn_rope_prefill" + _cache_entry(kcache, vcache, who)
-    return _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, None)
+    return _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, None, window=window)
 
 
 def _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos_check=None, B=None):
@@ -203,8 +255,9 @@ def _launch_ws(who, need, ws, kcache, maker):
     return ws.data_ptr(), ws.numel() * ws.element_size()
 
 
-def _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, paged):
-    """the checks and the launch both prefill entry points share; paged: None, or the arguments that take max_len's place"""
+def _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, paged, window=None):
+    """the checks and the launch both prefill entry points share; paged: None, or the arguments that take max_len's place; window:
+    None, or the W of the _window entry point, which then takes `entry`'s place"""
     def pos_check():
         if pos0.dtype != torch.int64 or pos0.numel() != 1 or pos0.device != kcache.device:
             raise QpalError(f"{who}: pos0 must be an int64 tensor of one element on {kcache.device}")
@@ -213,10 +266,14 @@ def _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws
     lib = _native.lib()
     ws_ptr, ws_bytes = _launch_ws(who, lib.qpal_attn_prefill_ws_bytes(T, nq, nkv, hd, max_len), ws, kcache, "prefill_workspace")
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
+    if window is None:
+        shape = ((T, nq, nkv, hd, max_len) if paged is None else paged + (T, nq, nkv, hd)) + (scale,)
+    else:
+        entry, shape = "qpal_attn_rope_prefill_window", _window_args(paged, (None, 0, 0, 0), kcache, (T, nq, nkv, hd), max_len, scale, window)
     with torch.cuda.device(kcache.device):
         rc = getattr(lib, entry)(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
-            pos0.data_ptr(), inv_freq.data_ptr(), *((T, nq, nkv, hd, max_len) if paged is None else paged + (T, nq, nkv, hd)), scale,
+            pos0.data_ptr(), inv_freq.data_ptr(), *shape,
             ws_ptr, ws_bytes, torch.cuda.current_stream(kcache.device).cuda_stream)
     _native.check(rc, entry)
     return out
@@ -257,17 +314,21 @@ def _pools_2d(kpool, vpool, block_table, who):
     return B, nkv, max_pages * page_size, hd, (block_table.data_ptr(), ld_table, num_pages, page_size, max_pages, _KV_FMT[kpool.dtype])
 
 
-def paged_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, scale=None, out=None, ws=None):
+def paged_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, scale=None, out=None, ws=None, window=None):
     """decode_attention on a paged cache: kpool / vpool [num_pages, nkv, page_size, hd] (fp16 or float8_e4m3fn, contiguous, 16-byte
     aligned, page_size in {16, 32, 64, 128, 256}), block_table int32 [B, max_pages] on the device with contiguous rows (a row
     stride >= max_pages): entry j of row b is the page of positions j * page_size .. of sequence b.  Everything else, and every
     rule, is decode_attention's with max_len = max_pages * page_size (ws: attention_workspace of that max_len); the result is bit
     for bit that launch's on the gathered cache.  Only entries that cover positions 0 .. pos[b] are read.  An entry in use outside
-    [0, num_pages) (an unreserved -1): reads go to page 0, the new row is dropped, that sequence's out row is unspecified."""
+    [0, num_pages) (an unreserved -1): reads go to page 0, the new row is dropped, that sequence's out row is unspecified.
+
+    window=W: decode_attention's window; only entries that cover window_floor(pos[b], W) .. pos[b] are read, so the entries of pages
+    wholly below the floor may be -1 (PagedKVCache.trim)."""
     who = "paged_decode_attention"
+    window = _window(window, who)
     B, nkv, max_len, hd, paged = _pools_2d(kpool, vpool, block_table, who)
     return _decode(who, "qpal_attn_rope_decode_batch_paged", q, k, v, kpool, vpool, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd,
-                   paged)
+                   paged, window=window)
 
 
 MAX_GROUPS = 16  # groups of one shared-prefix launch
@@ -319,14 +380,18 @@ def shared_prefix_workspace(B, G, nq, nkv, hd, max_len, device):
     return ws
 
 
-def shared_prefix_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, prefix, scale=None, out=None, ws=None):
+def shared_prefix_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, prefix, scale=None, out=None, ws=None,
+                                   window=None):
     """paged_decode_attention for slots that share the pages of a common prefix (``qpal_attn_rope_decode_batch_shared``, DESIGN.md
     §26).  prefix: a paging.SharedPrefix (``cache.prefix``) — row_group int32 [B], grp_slot / grp_len int32 [G] on the pools'
     device, read by the launches and never by the host.  A slot that reference_shared_rows() makes a member reads its group's first
     grp_len positions through table row grp_slot, once per group, and the rest through its own row; every other slot, the appended
     rows and the pools are bit for bit paged_decode_attention's.  Two launches on the current stream.  ws:
-    shared_prefix_workspace(B, G, ...), always needed."""
+    shared_prefix_workspace(B, G, ...), always needed.  window: anything but None raises QpalError — the shared-prefix launches have
+    no window."""
     who = "shared_prefix_decode_attention"
+    if window is not None:
+        raise QpalError(f"{who}: no sliding window in the shared-prefix launches (window must be None)")
     if block_table.dim() != 2:
         raise QpalError(f"{who}: block_table must have shape [B, max_pages >= 1], got {list(block_table.shape)}")
     tensors, G = _prefix_tensors(prefix, block_table.shape[0], kpool.device, who)  # (first: these checks need no device)
@@ -335,20 +400,22 @@ def shared_prefix_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_
                    paged + tensors, groups=G)
 
 
-def paged_prefill_attention(q, k, v, kpool, vpool, block_row, pos0, inv_freq, scale=None, out=None, ws=None):
+def paged_prefill_attention(q, k, v, kpool, vpool, block_row, pos0, inv_freq, scale=None, out=None, ws=None, window=None):
     """prefill_attention on a paged cache: the pools of paged_decode_attention and block_row int32 [max_pages], the block-table row
     of the ONE sequence (``block_table[b]``).  Every rule is prefill_attention's with max_len = max_pages * page_size (ws:
     prefill_workspace of that max_len); bit for bit that launch's result on the gathered cache, and the pools end up byte for byte
     as paged_decode_attention would have filled them token by token.  Only entries that cover positions 0 .. pos0 + T - 1 are read;
-    the guard on entries outside [0, num_pages) is paged_decode_attention's."""
+    the guard on entries outside [0, num_pages) is paged_decode_attention's.  window=W: prefill_attention's window; entries of pages
+    wholly below window_floor(pos0, W) may be -1."""
     who = "paged_prefill_attention"
+    window = _window(window, who)
     num_pages, nkv, page_size, hd = _pools(kpool, vpool, block_row, who)
     if block_row.dim() != 1 or block_row.shape[0] < 1:
         raise QpalError(f"{who}: block_row must have shape [max_pages >= 1], got {list(block_row.shape)}")
     max_pages = block_row.shape[0]
     paged = (block_row.data_ptr(), num_pages, page_size, max_pages, _KV_FMT[kpool.dtype])
     return _prefill(who, "qpal_attn_rope_prefill_paged", q, k, v, kpool, vpool, pos0, inv_freq, scale, out, ws, nkv,
-                    max_pages * page_size, hd, paged)
+                    max_pages * page_size, hd, paged, window=window)
 
 
 def ragged_workspace(R, S, nq, nkv, hd, max_len, device):
@@ -374,23 +441,30 @@ def _segments(who, seq, row0, pos0, dev):
     return S
 
 
-def _ragged(who, entry, q, k, v, kcache, vcache, seq, row0, pos0, S, inv_freq, scale, out, ws, B, nkv, max_len, hd, head, tail):
+def _ragged(who, entry, q, k, v, kcache, vcache, seq, row0, pos0, S, inv_freq, scale, out, ws, B, nkv, max_len, hd, head, tail,
+            window=None):
     """the checks (behind _segments, which gave S) and the launch both ragged entry points share; head / tail: the arguments in
-    front of and behind (R, S, B, nq, nkv, hd)"""
+    front of and behind (R, S, B, nq, nkv, hd); window: None, or the W of the _window entry point, which then takes `entry`'s place
+    (tail empty: a paged launch, head its paged arguments)"""
     R, nq, ld, out, ld_out = _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd)
     lib = _native.lib()
     ws_ptr, ws_bytes = _launch_ws(who, lib.qpal_attn_ragged_ws_bytes(R, S, nq, nkv, hd, max_len), ws, kcache, "ragged_workspace")
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
+    if window is None:
+        shape = tuple(head) + (R, S, B, nq, nkv, hd) + tuple(tail) + (scale,)
+    else:
+        entry = "qpal_attn_rope_prefill_ragged_window"
+        shape = _window_args(head if not tail else None, (None, 0, 0, 0, 0), kcache, (R, S, B, nq, nkv, hd), max_len, scale, window)
     with torch.cuda.device(kcache.device):
         rc = getattr(lib, entry)(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
-            seq.data_ptr(), row0.data_ptr(), pos0.data_ptr(), inv_freq.data_ptr(), *head, R, S, B, nq, nkv, hd, *tail, scale,
+            seq.data_ptr(), row0.data_ptr(), pos0.data_ptr(), inv_freq.data_ptr(), *shape,
             ws_ptr, ws_bytes, torch.cuda.current_stream(kcache.device).cuda_stream)
     _native.check(rc, entry)
     return out
 
 
-def ragged_prefill_attention(q, k, v, kcache, vcache, seq, row0, pos0, inv_freq, scale=None, out=None, ws=None):
+def ragged_prefill_attention(q, k, v, kcache, vcache, seq, row0, pos0, inv_freq, scale=None, out=None, ws=None, window=None):
     """prefill_attention for rows of SEVERAL sequences in one launch (``qpal_attn_rope_prefill_ragged``).  q fp32 [R,
     nq*hd], k / v fp32 [R, nkv*hd], 1 <= R <= 128 (strided rows as for prefill_attention); kcache / vcache [B, nkv, max_len, hd],
     fp16 or float8_e4m3fn, contiguous, 16-byte aligned.  The rows are cut into S <= 128 segments described ON THE DEVICE (never read
@@ -401,25 +475,32 @@ def ragged_prefill_attention(q, k, v, kcache, vcache, seq, row0, pos0, inv_freq,
 
     A segment with no rows, row0[s + 1] > R, seq[s] outside [0, B), pos0[s] < 0 or pos0[s] + rows > max_len is inactive: no cache
     byte and no out byte is written for it; out rows of no active segment keep what they held.  Two active segments naming one
-    sequence: the caller's error, that sequence's result is unspecified.  ws: ragged_workspace(R, S, ...)."""
+    sequence: the caller's error, that sequence's result is unspecified.  ws: ragged_workspace(R, S, ...).
+
+    window=W: per segment prefill_attention's window (qpal_attn_rope_prefill_ragged_window): bit for bit the one-sequence windowed
+    launch wherever the unwindowed pair is; rows below window_floor(pos0[s], W) of a segment's sequence are not read."""
     who = "ragged_prefill_attention"
+    window = _window(window, who)
     if kcache.dim() != 4 or kcache.shape != vcache.shape:
         raise QpalError(f"{who}: kcache / vcache must both have shape [B, nkv, max_len, hd]")
     B, nkv, max_len, hd = kcache.shape
     S = _segments(who, seq, row0, pos0, kcache.device)  # (first: these checks need no device)
     _cache_entry(kcache, vcache, who)
     return _ragged(who, "qpal_attn_rope_prefill_ragged", q, k, v, kcache, vcache, seq, row0, pos0, S, inv_freq, scale, out, ws, B,
-                   nkv, max_len, hd, (_KV_FMT[kcache.dtype],), (max_len,))
+                   nkv, max_len, hd, (_KV_FMT[kcache.dtype],), (max_len,), window=window)
 
 
-def paged_ragged_prefill_attention(q, k, v, kpool, vpool, block_table, seq, row0, pos0, inv_freq, scale=None, out=None, ws=None):
+def paged_ragged_prefill_attention(q, k, v, kpool, vpool, block_table, seq, row0, pos0, inv_freq, scale=None, out=None, ws=None,
+                                   window=None):
     """ragged_prefill_attention on a paged cache (``qpal_attn_rope_prefill_ragged_paged``): the pools and the block table int32 [B,
     max_pages] of paged_decode_attention; segment s uses row seq[s] of the table.  Every rule is ragged_prefill_attention's with
     max_len = max_pages * page_size (ws: ragged_workspace of that max_len); bit for bit that launch's result on the gathered cache.
     Only entries that cover positions 0 .. pos0[s] + rows - 1 of an active segment are read; the guard on entries outside [0,
-    num_pages) is paged_decode_attention's."""
+    num_pages) is paged_decode_attention's.  window=W: ragged_prefill_attention's window; entries of pages wholly below a segment's
+    window_floor(pos0[s], W) may be -1."""
     who = "paged_ragged_prefill_attention"
+    window = _window(window, who)
     S = _segments(who, seq, row0, pos0, kpool.device)
     B, nkv, max_len, hd, head = _pools_2d(kpool, vpool, block_table, who)
     return _ragged(who, "qpal_attn_rope_prefill_ragged_paged", q, k, v, kpool, vpool, seq, row0, pos0, S, inv_freq, scale, out, ws, B,
-                   nkv, max_len, hd, head, ())
+                   nkv, max_len, hd, head, (), window=window)

@@ -66,12 +66,21 @@ struct AttnBatchParams {
     SharedPrefixArgs sp;
     int B;
     const float *pre;
+    // WIN only (qpal_attn_rope_decode_batch_window): sequence b attends to [max(0, pos[b] - window + 1), pos[b]]
+    long window;
 };
 
 // SHARED (PAGED only): a member of a group (shared_prefix_len) attends to [grp_len, pos] through its own table row — the chunk
 // formulas below applied to pos - start, so start = 0 is the plain launch — and every finishing path folds the row's prefix partial
 // in, as the chunk in front of the row's own, before the division.  An ordinary slot takes the plain launch's arithmetic.
-template <class CT, bool PAGED, int HD, int REP, bool SHARED = false>
+//
+// WIN (sliding window): start = lo(pos) = max(0, pos - window + 1) in the same place, with no partial in front:
+// the plain launch's arithmetic on the keys [lo, pos].  lo is arbitrary (SHARED's starts are page-aligned): every row address
+// below is c0 + t with t relative to the chunk, the LDS scores are indexed by t alone, and the paged lookups take (c0 + t) >>
+// page_shift per lane (scores) or per wave (values), so nothing depends on c0's alignment.  No row and no table entry below lo
+// is read: the clamp of the rows past the chunk goes to c0 >= lo.  The host sizes nsplit and the LDS chunk for min(max_len,
+// window rounded up to 4) positions, which rel = pos - lo never reaches.
+template <class CT, bool PAGED, int HD, int REP, bool SHARED = false, bool WIN = false>
 __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const AttnBatchParams<CT> p) {
     constexpr bool KV8 = kIsKv8<CT>;
     constexpr int NW = kBatchNW, NT = 64 * NW, HALF = HD / 2;
@@ -94,20 +103,22 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
     // the context that exists, cut evenly over the splits (chunks of a multiple of 64 positions, at least kBatchMinChunk, at most
     // the LDS capacity); chunks 0 .. neff-1 hold positions <= pos, the last of them the new one
     // (32-bit unsigned divisions: positions are below max_len < 2^30)
-    [[maybe_unused]] long start = 0;  // SHARED: the positions the prefix launch has served for this slot
+    [[maybe_unused]] long start = 0;  // SHARED: the positions the prefix launch has served for this slot; WIN: lo(pos)
+    static_assert(!(SHARED && WIN), "no window in the shared-prefix launches");
     if constexpr (SHARED) {
         static_assert(PAGED, "groups share pages");
         int g;
         start = shared_prefix_len(p.sp, b, pos, p.B, p.page_shift, p.max_len, g);
     }
-    const long rel = SHARED ? pos - start : pos;
+    if constexpr (WIN) start = pos >= p.window ? pos - p.window + 1 : 0;
+    const long rel = (SHARED || WIN) ? pos - start : pos;
     long cld = CL;
     if (p.nsplit > 1) {
         cld = (long)((((unsigned)rel + (unsigned)p.nsplit) / (unsigned)p.nsplit + 63u) & ~63u);
         if (cld < kBatchMinChunk) cld = kBatchMinChunk;
         if (cld > CL) cld = CL;
     }
-    const long c0 = (SHARED ? start : 0) + (long)split * cld;
+    const long c0 = ((SHARED || WIN) ? start : 0) + (long)split * cld;
     const int neff = (int)((unsigned)rel / (unsigned)cld) + 1;
     if (split >= neff) return;
     const bool owner = split == neff - 1;                    // this chunk holds the new position
@@ -462,6 +473,11 @@ size_t batch_lds_floats(int rep, int hd, long chunk) {
 template <class CT>
 constexpr int kKvFmt = kIsKv8<CT> ? 1 : 0;  // the kv_fmt of a cache element type
 
+// the positions a windowed launch is sized for: min(max_len, window rounded up to 4) (max_len is a multiple of 4, at least 4)
+long window_positions(long window, long max_len) {
+    return window >= max_len ? max_len : (window + 3) / 4 * 4;
+}
+
 struct BatchGeometry {
     int nsplit, chunk;
     size_t lds, ws_bytes;
@@ -511,14 +527,22 @@ size_t shared_ws_bytes(const BatchGeometry &g, const PrefixGeometry &x) {
 }
 
 // sp: SHARED — the sharing of the launch; the prefix launch goes first, stream order is the only synchronisation between the two
-template <class CT, bool PAGED, bool SHARED = false>
+// window: WIN — the geometry is that of min(max_len, window rounded up to 4) positions (a short window in a long cache takes no
+// split and no merge floor); its workspace is never larger than the plain launch's of max_len
+template <class CT, bool PAGED, bool SHARED = false, bool WIN = false>
 int attn_rope_decode_batch(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16,
                            long ld_out, const long *pos, const float *inv_freq, int B, int nq, int nkv, int hd, long max_len,
                            float scale, void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0,
-                           const SharedPrefixArgs *sp = nullptr) {
+                           const SharedPrefixArgs *sp = nullptr, long window = 0) {
     if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
     BatchGeometry g;
-    const int rc = batch_geometry(B, nq, nkv, hd, max_len, g);
+    long geo_len = max_len;
+    if constexpr (WIN) {
+        const int rcs = attn_shape(B, nq, nkv, hd, max_len);
+        if (rcs != QPAL_OK) return rcs;
+        geo_len = window_positions(window, max_len);
+    }
+    const int rc = batch_geometry(B, nq, nkv, hd, geo_len, g);
     if (rc != QPAL_OK) return rc;
     [[maybe_unused]] PrefixGeometry x{};
     [[maybe_unused]] const size_t plain_ws = g.ws_bytes;
@@ -539,6 +563,7 @@ int attn_rope_decode_batch(const float *q, const float *k, const float *v, long 
                           g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr, g.ws_bytes ? wsf + (long)kBatchMax * nkv : nullptr,
                           g.nsplit, g.chunk};
     if constexpr (PAGED) p.table = pg->table, p.ld_table = pg->ld_table, p.num_pages = pg->num_pages, p.page_shift = shift;
+    if constexpr (WIN) p.window = window;
     const int grid = B * nkv * g.nsplit, rep = nq / nkv;
     if constexpr (SHARED) {
         float *xf = wsf + plain_ws / sizeof(float);
@@ -549,7 +574,7 @@ int attn_rope_decode_batch(const float *q, const float *k, const float *v, long 
         if (rc2 != QPAL_OK) return rc2;
     }
     return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
-        return launch_lds<attn_rope_batch_kernel<CT, PAGED, HD(), REP(), SHARED>>(dim3(grid), dim3(64 * kBatchNW), g.lds, (int)kBatchLdsMax,
+        return launch_lds<attn_rope_batch_kernel<CT, PAGED, HD(), REP(), SHARED, WIN>>(dim3(grid), dim3(64 * kBatchNW), g.lds, (int)kBatchLdsMax,
                                                                                    static_cast<hipStream_t>(stream), p);
     });
 }
@@ -591,6 +616,32 @@ extern "C" int qpal_attn_rope_decode_batch_paged(const float *q, const float *k,
     return paged_entry(any_null, pg, kv_fmt, [&](auto ct, int shift, long max_len) {
         return attn_rope_decode_batch<decltype(ct), true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd,
                                                           max_len, scale, ws, ws_bytes, stream, &pg, shift);
+    });
+}
+
+extern "C" int qpal_attn_rope_decode_batch_window(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache,
+                                                  void *out_f16, long ld_out, const long *pos, const float *inv_freq,
+                                                  const int *block_table, long ld_table, int num_pages, int page_size, int max_pages,
+                                                  int kv_fmt, int B, int nq, int nkv, int hd, long max_len, float scale, long window,
+                                                  void *ws, long ws_bytes, void *stream) {
+    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
+    if (window < 0) return QPAL_E_PARAM;
+    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
+    auto launch = [&](auto ct, auto paged, auto win, long len, const PageArgs *pg, int shift) {
+        return attn_rope_decode_batch<decltype(ct), paged(), false, win()>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos, inv_freq, B, nq,
+                                                                          nkv, hd, len, scale, ws, ws_bytes, stream, pg, shift, nullptr,
+                                                                          window);
+    };
+    using T = std::true_type;
+    using F = std::false_type;
+    if (!block_table) {  // contiguous caches [B][nkv][max_len][hd]
+        return for_kv_fmt(kv_fmt, [&](auto ct) {
+            return window ? launch(ct, F{}, T{}, max_len, nullptr, 0) : launch(ct, F{}, F{}, max_len, nullptr, 0);
+        });
+    }
+    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
+    return paged_entry(false, pg, kv_fmt, [&](auto ct, int shift, long len) {
+        return window ? launch(ct, T{}, T{}, len, &pg, shift) : launch(ct, T{}, F{}, len, &pg, shift);
     });
 }
 

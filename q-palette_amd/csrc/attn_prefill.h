@@ -40,6 +40,8 @@ struct AttnPrefillParams {
     // PAGED only: kcache / vcache are the pools [num_pages][nkv][1 << page_shift][HD], max_len = max_pages << page_shift
     const int *table;           // int32 [max_pages] of this sequence, device
     int num_pages, page_shift;
+    // WIN only (the _window entry points): the row at position n attends to [max(0, n - window + 1), n]
+    long window;
 };
 
 // RAGGED: T = the rows R of q / k / v / out, pos0 = int64 [S], kcache / vcache = [B][nkv][max_len][HD] (PAGED: table = int32
@@ -87,7 +89,15 @@ __device__ __forceinline__ u32x4 rope_chunk(const float *src, int ch, long pos, 
 }
 
 // RAGGED: the launch serves rows of several sequences (attn_ragged.hip)
-template <class CT, bool PAGED, bool RAGGED, int HD, int REP>
+//
+// WIN (sliding window): the keys of a query tile are [kmin, kend) with kmin = lo(pos0 + t0), lo(n) = max(0, n -
+// window + 1), and the chunk formulas run on kend - (kmin & ~31): a chunk still starts on a multiple of 32, so a 16-key half of a
+// tile still lies in one page.  fetch() hands out zeros for n < kmin without touching the cache or a page (those rows may hold
+// NaN, their pages may be gone: 0 * NaN in the second product would leak), the mask admits lo(qpos) <= n <= qpos per ROW, and a
+// row with no admitted key in a tile or a whole chunk keeps m = -3e38, l = 0, O = 0, which the running rescale (alpha = 0 once a
+// key arrives) and the merge (weight exp(-3e38 - M) = 0) meet today behind the diagonal.  window >= 1: a tile's own new rows lie
+// at or above kmin, so they are fetched, and stored, as without a window.
+template <class CT, bool PAGED, bool RAGGED, int HD, int REP, bool WIN = false>
 __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
     const std::conditional_t<RAGGED, AttnRaggedParams<CT>, AttnPrefillParams<CT>> p) {
     constexpr bool KV8 = kIsKv8<CT>;
@@ -159,19 +169,28 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
     uint16_t *const orows = RAGGED ? p.out + (long)row_base * p.ld_out : p.out;
     const int t0 = j * TQ, tend = t0 + TQ < T ? t0 + TQ : T;  // query rows of the tile: [t0, tend)
     const unsigned kend = (unsigned)pos0 + (unsigned)tend;    // its keys: [0, kend)  (positions are below 2^30)
-    unsigned cld = (kend + 31u) & ~31u;
+    [[maybe_unused]] unsigned kmin = 0u;  // WIN: the first key any row of the tile admits
+    if constexpr (WIN) {
+        const long first = (long)pos0 + t0 - p.window + 1;
+        kmin = first > 0 ? (unsigned)first : 0u;
+    }
+    const unsigned kbase = WIN ? kmin & ~31u : 0u;  // the chunks cut [kbase, kend)
+    const unsigned span = kend - kbase;
+    unsigned cld = (span + 31u) & ~31u;
     if (p.nsplit > 1) {
-        cld = ((kend + (unsigned)p.nsplit - 1u) / (unsigned)p.nsplit + 31u) & ~31u;
+        cld = ((span + (unsigned)p.nsplit - 1u) / (unsigned)p.nsplit + 31u) & ~31u;
         if (cld < (unsigned)kPfMinChunk) cld = (unsigned)kPfMinChunk;
     }
-    const int neff = (int)((kend + cld - 1u) / cld);  // chunks that hold keys: the same in every workgroup of the tile
+    const int neff = (int)((span + cld - 1u) / cld);  // chunks that hold keys: the same in every workgroup of the tile
     if (split >= neff) return;
-    const pos_t c0 = (pos_t)split * cld;
+    const pos_t c0 = (WIN ? (pos_t)kbase : (pos_t)0) + (pos_t)split * cld;
     const pos_t c1 = c0 + cld < kend ? (pos_t)(c0 + cld) : (pos_t)kend;
     const int hh = wave % REP, qsub = wave / REP;
     const int head = kh * REP + hh;
     const int trow = t0 + qsub * 16 + mi;  // this lane's query row (a column of S^T)
     const pos_t qpos = pos0 + trow;
+    [[maybe_unused]] pos_t qlo = 0;  // WIN: lo(qpos)
+    if constexpr (WIN) qlo = (long)qpos >= p.window ? (pos_t)((long)qpos - p.window + 1) : (pos_t)0;
     long kvoff;
     if constexpr (PAGED) kvoff = 0;
     else if constexpr (RAGGED) kvoff = ((long)sq * p.nkv + kh) * p.max_len * HD;
@@ -235,7 +254,7 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
             const int isv = idx / (kPfKT * CPR), rr = (idx / CPR) % kPfKT, ch = idx % CPR;
             const pos_t n = kt0 + rr;
             KR val{};
-            if (n < c1) {
+            if (n < c1 && (!WIN || n >= (pos_t)kmin)) {
                 [[maybe_unused]] bool st_ok = true;  // (PAGED: a new row behind an entry outside the pool is not stored)
                 if (n < pos0) {
                     val = *(gptr<const KR>)((isv ? Vc : Kc) + row_off(n, rr, st_ok) + 8 * ch);
@@ -321,6 +340,7 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
                 for (int r = 0; r < 4; r++) {
                     const pos_t n = kt0 - kPfKT + 16 * kt + 4 * mq + r;
                     ok[4 * kt + r] = n <= qpos;  // causal (keys past the tile's last row lie past every row of it)
+                    if constexpr (WIN) ok[4 * kt + r] = n <= qpos && n >= qlo;  // and the row's own lower edge
                     sv[4 * kt + r] = s[kt][r] * p.scale;
                     if (ok[4 * kt + r]) mx = fmaxf(mx, sv[4 * kt + r]);
                 }
@@ -439,6 +459,13 @@ inline void prefill_split(long ntile, long tickets, int nq, int nkv, int hd, lon
         const long slots = a < b ? a : b;
         g.ws_bytes = ((size_t)tickets + (size_t)slots * tq * rep * (hd + 2)) * sizeof(float);
     }
+}
+
+// the positions a windowed launch is sized for: the longest span [kmin & ~31, kend) a query tile can have — window - 1 keys below
+// the tile's first row, its 16 pf_qs(rep) rows, 31 keys down to the multiple of 32 — or max_len where that is shorter
+inline long prefill_window_positions(long window, int rep, long max_len) {
+    const long span = window + 16 * pf_qs(rep) + 30;
+    return window >= max_len || span >= max_len ? max_len : span;
 }
 
 }  // namespace

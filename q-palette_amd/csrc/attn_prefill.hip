@@ -34,24 +34,27 @@ namespace {
 
 // Launch geometry from (T, heads, max_len) only.  ws_bytes is an upper bound of what ANY launch with at most T rows and at most
 // max_len positions needs (monotone in both): one workspace serves every smaller launch of the same heads.
-int prefill_geometry(int T, int nq, int nkv, int hd, long max_len, PrefillGeometry &g) {
+// window > 0: the chunks are sized for the longest span a query tile can have (prefill_window_positions) instead of max_len — never
+// more chunks, never a larger workspace
+int prefill_geometry(int T, int nq, int nkv, int hd, long max_len, PrefillGeometry &g, long window = 0) {
     g = PrefillGeometry{0, 0, 0};
     const int rc = attn_shape(T, nq, nkv, hd, max_len);
     if (rc != QPAL_OK) return rc;
     const int tq = 16 * pf_qs(nq / nkv);
-    prefill_split((T + tq - 1) / tq, (long)nkv * kPfMaxTiles, nq, nkv, hd, max_len, g);
+    prefill_split((T + tq - 1) / tq, (long)nkv * kPfMaxTiles, nq, nkv, hd,
+                  window > 0 ? prefill_window_positions(window, nq / nkv, max_len) : max_len, g);
     return QPAL_OK;
 }
 
 // the entry points: the same checks, geometry and launch, the cache element type and the row addressing apart (PAGED: kcache /
 // vcache are the pools, `pg` the sequence's block-table row, max_len = max_pages * page_size)
-template <class CT, bool PAGED>
+template <class CT, bool PAGED, bool WIN = false>
 int attn_rope_prefill(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16,
                       long ld_out, const long *pos0, const float *inv_freq, int T, int nq, int nkv, int hd, long max_len, float scale,
-                      void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0) {
+                      void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0, long window = 0) {
     if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos0 || !inv_freq) return QPAL_E_NULL;
     PrefillGeometry g;
-    int rc = prefill_geometry(T, nq, nkv, hd, max_len, g);
+    int rc = prefill_geometry(T, nq, nkv, hd, max_len, g, WIN ? window : 0);
     if (rc != QPAL_OK) return rc;
     rc = attn_args(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, nq, hd, g.ws_bytes, ws, ws_bytes,
                    PAGED ? reinterpret_cast<uintptr_t>(pg->table) : 0);
@@ -62,9 +65,10 @@ int attn_rope_prefill(const float *q, const float *k, const float *v, long ld_qk
                             g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr, g.ws_bytes ? wsf + (long)nkv * kPfMaxTiles : nullptr,
                             g.nsplit, g.ntile};
     if constexpr (PAGED) p.table = pg->table, p.num_pages = pg->num_pages, p.page_shift = shift;
+    if constexpr (WIN) p.window = window;
     const int grid = nkv * g.ntile * g.nsplit, rep = nq / nkv;
     return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
-        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, false, HD(), REP()>), dim3(grid), dim3(64 * REP() * pf_qs(REP())), 0,
+        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, false, HD(), REP(), WIN>), dim3(grid), dim3(64 * REP() * pf_qs(REP())), 0,
                            static_cast<hipStream_t>(stream), p);
         return (int)hipGetLastError();
     });
@@ -105,5 +109,29 @@ extern "C" int qpal_attn_rope_prefill_paged(const float *q, const float *k, cons
     return paged_entry(any_null, pg, kv_fmt, [&](auto ct, int shift, long max_len) {
         return attn_rope_prefill<decltype(ct), true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, max_len,
                                                      scale, ws, ws_bytes, stream, &pg, shift);
+    });
+}
+
+extern "C" int qpal_attn_rope_prefill_window(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache,
+                                             void *out_f16, long ld_out, const long *pos0, const float *inv_freq, const int *block_row,
+                                             int num_pages, int page_size, int max_pages, int kv_fmt, int T, int nq, int nkv, int hd,
+                                             long max_len, float scale, long window, void *ws, long ws_bytes, void *stream) {
+    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos0 || !inv_freq) return QPAL_E_NULL;
+    if (window < 0) return QPAL_E_PARAM;
+    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
+    auto launch = [&](auto ct, auto paged, auto win, long len, const PageArgs *pg, int shift) {
+        return attn_rope_prefill<decltype(ct), paged(), win()>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd,
+                                                              len, scale, ws, ws_bytes, stream, pg, shift, window);
+    };
+    using Y = std::true_type;
+    using N = std::false_type;
+    if (!block_row) {  // a contiguous cache [nkv][max_len][hd]
+        return for_kv_fmt(kv_fmt, [&](auto ct) {
+            return window ? launch(ct, N{}, Y{}, max_len, nullptr, 0) : launch(ct, N{}, N{}, max_len, nullptr, 0);
+        });
+    }
+    const PageArgs pg{block_row, max_pages, num_pages, page_size, max_pages};
+    return paged_entry(false, pg, kv_fmt, [&](auto ct, int shift, long len) {
+        return window ? launch(ct, Y{}, Y{}, len, &pg, shift) : launch(ct, Y{}, N{}, len, &pg, shift);
     });
 }

@@ -19,23 +19,26 @@ namespace {
 
 // Launch geometry from (R, S, heads, max_len) only: ntile bounds the sum over segments of ceil(T_s / TQ) for segments that share R
 // rows; chunks and workspace by prefill_split with nkv * kPfRaggedTiles tickets.  ws_bytes is monotone in R, S and max_len.
-int ragged_geometry(int R, int S, int nq, int nkv, int hd, long max_len, PrefillGeometry &g) {
+// window > 0: the chunks are sized for the longest span a query tile can have (prefill_window_positions) instead of max_len.
+int ragged_geometry(int R, int S, int nq, int nkv, int hd, long max_len, PrefillGeometry &g, long window = 0) {
     g = PrefillGeometry{0, 0, 0};
     const int rc = attn_shape(R, nq, nkv, hd, max_len);
     if (rc != QPAL_OK) return rc;
     if (S < 1 || S > kPfMaxT) return QPAL_E_SHAPE;
     const int tq = 16 * pf_qs(nq / nkv);
     const long bound = ((long)R + (long)S * (tq - 1)) / tq, ntile = bound < R ? bound : R;
-    prefill_split(ntile, (long)nkv * kPfRaggedTiles, nq, nkv, hd, max_len, g);
+    prefill_split(ntile, (long)nkv * kPfRaggedTiles, nq, nkv, hd,
+                  window > 0 ? prefill_window_positions(window, nq / nkv, max_len) : max_len, g);
     return QPAL_OK;
 }
 
-template <class CT, bool PAGED>
+template <class CT, bool PAGED, bool WIN = false>
 int attn_rope_ragged(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16, long ld_out,
                      const int *seq, const int *row0, const long *pos0, const float *inv_freq, int R, int S, int B, int nq, int nkv, int hd,
-                     long max_len, float scale, void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0) {
+                     long max_len, float scale, void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0,
+                     long window = 0) {
     PrefillGeometry g;
-    int rc = ragged_geometry(R, S, nq, nkv, hd, max_len, g);
+    int rc = ragged_geometry(R, S, nq, nkv, hd, max_len, g, WIN ? window : 0);
     if (rc != QPAL_OK) return rc;
     if (B < 1) return QPAL_E_SHAPE;
     rc = attn_args(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, nq, hd, g.ws_bytes, ws, ws_bytes,
@@ -50,9 +53,10 @@ int attn_rope_ragged(const float *q, const float *k, const float *v, long ld_qkv
         g.ws_bytes ? wsf + (long)nkv * kPfRaggedTiles : nullptr, g.nsplit, g.ntile};
     p.seq = seq, p.row0 = row0, p.S = S, p.B = B;
     if constexpr (PAGED) p.table = pg->table, p.num_pages = pg->num_pages, p.page_shift = shift, p.ld_table = pg->ld_table;
+    if constexpr (WIN) p.window = window;
     const int grid = nkv * g.ntile * g.nsplit, rep = nq / nkv;
     return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
-        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, true, HD(), REP()>), dim3(grid), dim3(64 * REP() * pf_qs(REP())), 0,
+        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, true, HD(), REP(), WIN>), dim3(grid), dim3(64 * REP() * pf_qs(REP())), 0,
                            static_cast<hipStream_t>(stream), p);
         return (int)hipGetLastError();
     });
@@ -92,5 +96,30 @@ extern "C" int qpal_attn_rope_prefill_ragged_paged(const float *q, const float *
     return paged_entry(any_null, pg, kv_fmt, [&](auto ct, int shift, long max_len) {
         return attn_rope_ragged<decltype(ct), true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B, nq, nkv,
                                                     hd, max_len, scale, ws, ws_bytes, stream, &pg, shift);
+    });
+}
+
+extern "C" int qpal_attn_rope_prefill_ragged_window(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache,
+                                                    void *out_f16, long ld_out, const int *seq, const int *row0, const long *pos0,
+                                                    const float *inv_freq, const int *block_table, long ld_table, int num_pages,
+                                                    int page_size, int max_pages, int kv_fmt, int R, int S, int B, int nq, int nkv, int hd,
+                                                    long max_len, float scale, long window, void *ws, long ws_bytes, void *stream) {
+    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !seq || !row0 || !pos0 || !inv_freq) return QPAL_E_NULL;
+    if (window < 0) return QPAL_E_PARAM;
+    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
+    auto launch = [&](auto ct, auto paged, auto win, long len, const PageArgs *pg, int shift) {
+        return attn_rope_ragged<decltype(ct), paged(), win()>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B,
+                                                             nq, nkv, hd, len, scale, ws, ws_bytes, stream, pg, shift, window);
+    };
+    using Y = std::true_type;
+    using N = std::false_type;
+    if (!block_table) {  // contiguous caches [B][nkv][max_len][hd]
+        return for_kv_fmt(kv_fmt, [&](auto ct) {
+            return window ? launch(ct, N{}, Y{}, max_len, nullptr, 0) : launch(ct, N{}, N{}, max_len, nullptr, 0);
+        });
+    }
+    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
+    return paged_entry(false, pg, kv_fmt, [&](auto ct, int shift, long len) {
+        return window ? launch(ct, Y{}, Y{}, len, &pg, shift) : launch(ct, Y{}, N{}, len, &pg, shift);
     });
 }

@@ -6,6 +6,7 @@
     cache.release(slot)                    # the slot's pages go back to the free list
     cache.fork(src, dst, n_positions)      # dst shares src's first n_positions (a shared prompt prefix)
     step = DecodeStep(..., block_table=cache.table, shared_prefix=cache.prefix)   # the shared pages are read once per group
+    cache.trim(slot, window_floor(pos, W)) # sliding window: pages wholly below the floor go back to the pool
 
 A pool is ``[num_pages, nkv, page_size, hd]`` (k and v of every layer have one each); entry j of the table's row b is the page that
 holds positions ``j * page_size .. (j + 1) * page_size - 1`` of slot b in EVERY layer's pools, -1 where nothing is reserved (the
@@ -72,7 +73,8 @@ class PagedKVCache:
                       for _ in range(self.n_layers)]
         self.kpool, self.vpool = mk(), mk()
         self.table = torch.full((self.B, self.max_pages), -1, dtype=torch.int32, device=device)
-        self._rows = [[] for _ in range(self.B)]             # the pages of every slot, in position order
+        self._rows = [[] for _ in range(self.B)]             # the pages of every slot, in position order (-1: trimmed)
+        self._trimmed = [0] * self.B                         # positions below this have lost their pages (a multiple of page_size)
         self._shared = [0] * self.B                          # the prefix a forked slot took from its source
         self._refs = [0] * self.num_pages
         self._free = list(range(self.num_pages - 1, -1, -1))  # a stack: pop() hands out page 0 first
@@ -95,11 +97,19 @@ class PagedKVCache:
         return len(self._free)
 
     def pages_of(self, slot):
-        """the pages of `slot` in position order (a copy)"""
+        """the pages of `slot` in position order (a copy; -1 where trim() has taken the page)"""
         return list(self._rows[self._slot(slot)])
 
     def refcount(self, page):
         return self._refs[page]
+
+    def trimmed_upto(self, slot):
+        """positions of `slot` below this have no page any more (trim); 0 for a slot that was never trimmed"""
+        return self._trimmed[self._slot(slot)]
+
+    def pages_held(self, slot):
+        """the pages `slot` holds a reference on: its reserved pages without the trimmed ones"""
+        return sum(1 for page in self._rows[self._slot(slot)] if page >= 0)
 
     def shared_upto(self, slot):
         """the shared positions of a forked slot: its first shared_upto positions are the source's prefix (whole pages shared, the
@@ -190,13 +200,39 @@ class PagedKVCache:
         """drops the slot's references; a page nobody else holds goes back to the free list; the row goes back to -1"""
         slot = self._slot(slot)
         for page in reversed(self._rows[slot]):
+            if page < 0:
+                continue  # (trimmed: the reference went with trim())
             self._refs[page] -= 1
             if self._refs[page] == 0:
                 self._free.append(page)
         had = bool(self._rows[slot])
-        self._rows[slot], self._shared[slot] = [], 0
+        self._rows[slot], self._shared[slot], self._trimmed[slot] = [], 0, 0
         if had:
             self._push_row(slot)
+        if self._leave(slot):
+            self._push_prefix()
+
+    def trim(self, slot, below):
+        """`slot` will never again read a position < below (a sliding window has passed them: below = window_floor(pos, W) of the
+        LARGEST window of any layer; a model with one unwindowed layer never trims).  Pages that lie wholly below `below` lose this
+        slot's reference — a page nobody else holds goes back to the free list — and their table entries become -1, which the
+        windowed launches never dereference.  The slot keeps its length: reserve() still counts positions from 0 and never backs
+        a trimmed position again.  A trimmed slot leaves its shared-prefix group (the group's launch would read the pages), and
+        fork() from it raises.  A call with a smaller `below` than an earlier one does nothing.  Host code and one small copy of
+        the table row, as reserve(): between replays of a captured step, never inside one."""
+        slot = self._slot(slot)
+        rows = self._rows[slot]
+        first, n = self._trimmed[slot] // self.page_size, min(max(int(below), 0) // self.page_size, len(rows))
+        if n <= first:
+            return
+        for j in range(first, n):
+            page = rows[j]
+            self._refs[page] -= 1
+            if self._refs[page] == 0:
+                self._free.append(page)
+            rows[j] = -1
+        self._trimmed[slot] = n * self.page_size
+        self._push_row(slot)
         if self._leave(slot):
             self._push_prefix()
 
@@ -212,6 +248,8 @@ class PagedKVCache:
         n = int(n_positions)
         if not 0 <= n <= len(self._rows[src]) * self.page_size:
             raise QpalError(f"PagedKVCache.fork: slot {src} has no {n} reserved positions")
+        if n > 0 and self._trimmed[src] > 0:
+            raise QpalError(f"PagedKVCache.fork: slot {src} has been trimmed below position {self._trimmed[src]}: its prefix is gone")
         full, part = divmod(n, self.page_size)
         if part and not self._free:
             raise QpalError("PagedKVCache.fork: no free page for the copy of the partial page")
