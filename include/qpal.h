@@ -497,6 +497,42 @@ int qpal_attn_rope_prefill_ragged_window(const float *q, const float *k, const f
                                          int max_pages, int kv_fmt, int R, int S, int B, int nq, int nkv, int hd,
                                          long max_len, float scale, long window, void *ws, long ws_bytes, void *stream);
 
+/* SCORE MODIFIERS: the three _window launches above with a logit soft cap (Gemma-2's attn_logit_softcapping) and
+ * per-head sinks (gpt-oss); the argument lists are the _window ones plus softcap and sinks behind window.  For a row with scaled
+ * scores s_j = scale * q.k_j over its admitted keys (causal, and windowed if window > 0):
+ *   softcap = c > 0: s_j <- c * tanh(s_j / c), behind scale and in front of the maximum, the mask and everything else, the new
+ *     position's own score included.  softcap = 0: no cap.  softcap < 0, NaN or inf: QPAL_E_PARAM (beside window < 0: behind the
+ *     null checks, in front of everything else).
+ *   sinks: fp32 [nq] on the device, 4-byte aligned (QPAL_E_ALIGN), read at every launch; NULL: none.  Head h's row becomes
+ *     out = sum_j e^(s_j - M) v_j / (sum_j e^(s_j - M) + e^(sinks[h] - M)),  M = max(max_j s_j, sinks[h]):
+ *     one more logit in the denominator and nowhere else (Hugging Face: concatenate a column, softmax, drop the column).  The sink
+ *     is not soft-capped and has no value row; it enters once per row, where the row is finished (behind the chunk merge of a split
+ *     launch, behind the last tile of a prefill row).  A sink far above every score drives the row to 0, without inf or NaN;
+ *     sinks[h] = -inf is bit for bit the launch without sinks.
+ * softcap == 0 && sinks == NULL: the call IS the _window entry point's.  Otherwise one instantiation per (format, storage, hd, rep)
+ * built on the windowed kernel body serves every combination; window = 0 runs it with window = max_len.  The rotary embedding,
+ * the append and the stored bytes, the inactive-slot and *pos0 fit rules, both formats, paging, the window rules and the
+ * workspaces (qpal_attn_*_ws_bytes) are the _window launches'. */
+int qpal_attn_rope_decode_batch_score(const float *q, const float *k, const float *v, long ld_qkv,
+                                      void *kcache, void *vcache, void *out_f16, long ld_out,
+                                      const long *pos, const float *inv_freq, const int *block_table /* NULL: contiguous */,
+                                      long ld_table, int num_pages, int page_size, int max_pages, int kv_fmt,
+                                      int B, int nq, int nkv, int hd, long max_len, float scale, long window,
+                                      float softcap, const float *sinks, void *ws, long ws_bytes, void *stream);
+int qpal_attn_rope_prefill_score(const float *q, const float *k, const float *v, long ld_qkv,
+                                 void *kcache, void *vcache, void *out_f16, long ld_out,
+                                 const long *pos0, const float *inv_freq, const int *block_row /* NULL: contiguous */,
+                                 int num_pages, int page_size, int max_pages, int kv_fmt,
+                                 int T, int nq, int nkv, int hd, long max_len, float scale, long window,
+                                 float softcap, const float *sinks, void *ws, long ws_bytes, void *stream);
+int qpal_attn_rope_prefill_ragged_score(const float *q, const float *k, const float *v, long ld_qkv,
+                                        void *kcache, void *vcache, void *out_f16, long ld_out,
+                                        const int *seq, const int *row0, const long *pos0, const float *inv_freq,
+                                        const int *block_table /* NULL: contiguous */, long ld_table, int num_pages, int page_size,
+                                        int max_pages, int kv_fmt, int R, int S, int B, int nq, int nkv, int hd,
+                                        long max_len, float scale, long window, float softcap, const float *sinks,
+                                        void *ws, long ws_bytes, void *stream);
+
 /* Final norm + fp16 lm_head for `rows` rows of the residual stream at once, on the matrix pipe (csrc/lm_head_batch.hip): the
  * logits a sampler needs, and the batch-B tail of a decode step.  h_f32 fp32 [rows][ld_h] (ld_h >= k, in elements), 1 <= rows <=
  * 128; k a multiple of 512, 512 <= k <= 8192; w_f16 the lm_head fp16 [vocab][k]; logits_f32 fp32 [rows][ld_logits], ld_logits >=

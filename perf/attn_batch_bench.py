@@ -20,7 +20,12 @@ paged launch, then the shared pair (qpalette_amd.shared_prefix_decode_attention,
 --window W (0: context / 4 of every row): behind the contiguous launch of a row, the same launch with window=W on the
 same caches and positions: "us_per_launch_events_window" next to "kv_rows_window" = sum_b min(pos[b] + 1, W), the rows it has to read.
 
-    python perf/attn_batch_bench.py [--batch 8 64] [--context 1024 4096] [--iters 200] [--full] [--kv fp16 fp8] [--paged 16 64]
+--softcap CAP / --sinks: behind the contiguous launch of a row, the same launch with softcap=CAP
+("us_per_launch_events_cap"), with sinks of N(0, 1) per head ("..._sinks") and with both ("..._cap_sinks"), then the plain launch
+again ("us_per_launch_events_again": the spread the three are read against).  Under `rocprofv3 --kernel-trace --stats` the plain and
+the modified launches are two kernel names (attn_rope_batch_kernel<..., false, false> and <..., true, true>).
+
+    python perf/attn_batch_bench.py [--softcap CAP] [--sinks] [--batch 8 64] [--context 1024 4096] [--iters 200] [--full] [--kv fp16 fp8] [--paged 16 64]
                                     [--shared-prefix 4096 1024] [--repeats 5] [--window W]
 """
 import argparse
@@ -104,6 +109,8 @@ def main(argv=None):
                     help="with --paged PAGE: slots that share a P-position prefix, the plain launch against the shared pair")
     ap.add_argument("--repeats", type=int, default=5, help="--shared-prefix: timed blocks of each launch, in turn")
     ap.add_argument("--window", type=int, default=None, metavar="W", help="also time the launch with this sliding window (0: context / 4)")
+    ap.add_argument("--softcap", type=float, default=None, metavar="CAP", help="also time the launch with this logit soft cap")
+    ap.add_argument("--sinks", action="store_true", help="also time the launch with per-head sinks")
     args = ap.parse_args(argv)
     if args.shared_prefix and (len(args.paged) != 1 or any(P % args.paged[0] or P < args.paged[0] for P in args.shared_prefix)):
         raise SystemExit("--shared-prefix: with ONE --paged PAGE, prefixes that are multiples of it")
@@ -160,6 +167,14 @@ def main(argv=None):
                         us_w = timed(lambda: qp.decode_attention(q, k, v, kc, vc, pos, inv_freq, out=out, ws=ws, window=W))
                         row.update({"window": W, "kv_rows_window": rows_w, "kv_MB_window": rows_w * nkv * hd * 2 * kc.element_size() / 1e6,
                                     "us_per_launch_events_window": us_w})
+                    if (args.softcap is not None or args.sinks) and not ps:
+                        sinks = torch.randn(nq, generator=torch.Generator().manual_seed(9)).to(dev) if args.sinks else None
+                        mods = ([("cap", dict(softcap=args.softcap))] if args.softcap is not None else []) + ([("sinks", dict(sinks=sinks))] if args.sinks else [])
+                        if len(mods) == 2:
+                            mods.append(("cap_sinks", dict(softcap=args.softcap, sinks=sinks)))
+                        for name, kw in mods:
+                            row["us_per_launch_events_" + name] = timed(lambda: qp.decode_attention(q, k, v, kc, vc, pos, inv_freq, out=out, ws=ws, **kw))
+                        row["us_per_launch_events_again"] = timed(launch)
                     if args.paged:
                         row["paged"] = ps
                     if ps:

@@ -12,7 +12,10 @@ qpalette_amd.paged_prefill_attention, once per page size ("us_paged"), and the c
 --window W: per row also the launch with window=W on the same cache ("us_window"; "keys_window": the keys its rows
 attend to, sum_t min(pos0 + t + 1, W), next to "keys": sum_t (pos0 + t + 1)), then the plain launch again ("us_prefill_attention_again").
 
-    python perf/attn_prefill_bench.py [--T 128] [--pos0 0 1920 3968] [--context 4096] [--heads 32 8 128] [--iters 50] [--kv fp16|fp8]
+--softcap CAP / --sinks: per row also the launch with softcap=CAP ("us_cap"), with sinks of N(0, 1) per head
+("us_sinks") and with both ("us_cap_sinks"), then the plain launch again ("us_prefill_attention_again").
+
+    python perf/attn_prefill_bench.py [--softcap CAP] [--sinks] [--T 128] [--pos0 0 1920 3968] [--context 4096] [--heads 32 8 128] [--iters 50] [--kv fp16|fp8]
                                       [--paged 16 64] [--window W]
 """
 import argparse
@@ -37,6 +40,8 @@ def main(argv=None):
     ap.add_argument("--kv", default="fp16", choices=["fp16", "fp8"], help="KV-cache element format")
     ap.add_argument("--paged", type=int, nargs="*", default=[], metavar="PAGE_SIZE", help="also time paged launches of these page sizes")
     ap.add_argument("--window", type=int, default=None, metavar="W", help="also time the launch with this sliding window")
+    ap.add_argument("--softcap", type=float, default=None, metavar="CAP", help="also time the launch with this logit soft cap")
+    ap.add_argument("--sinks", action="store_true", help="also time the launch with per-head sinks")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
@@ -78,6 +83,15 @@ def main(argv=None):
         flop = 4 * nq * hd * sum(pos0 + t + 1 for t in range(T))
         rows.append({"T": T, "pos0": pos0, "kv": args.kv, "flop": flop, "us_prefill_attention": us, "tflops": flop / us * 1e-6,
                      "us_torch_sdpa_causal_mask": us_sdpa})
+        if args.softcap is not None or args.sinks:
+            sinks = torch.randn(nq, generator=torch.Generator().manual_seed(9)).to(dev) if args.sinks else None
+            mods = ([("cap", dict(softcap=args.softcap))] if args.softcap is not None else []) + ([("sinks", dict(sinks=sinks))] if args.sinks else [])
+            if len(mods) == 2:
+                mods.append(("cap_sinks", dict(softcap=args.softcap, sinks=sinks)))
+            for name, kw in mods:
+                rows[-1]["us_" + name] = timed(lambda: qp.prefill_attention(q, k, v, kc, vc, pos_t, inv_freq, out=out, ws=ws, **kw))
+            if not args.paged and not args.window:
+                rows[-1]["us_prefill_attention_again"] = timed(lambda: qp.prefill_attention(q, k, v, kc, vc, pos_t, inv_freq, out=out, ws=ws))
         if args.window:
             rows[-1].update({"window": args.window, "keys": sum(pos0 + t + 1 for t in range(T)),
                              "keys_window": sum(min(pos0 + t + 1, args.window) for t in range(T)),

@@ -39,6 +39,7 @@ shared_prefix=...) —, the plain step again behind them, and h
 
     python perf/decode_llama_batch.py [--model 3_8b] [--batch 1 8 16 32 64] [--context 1024] [--tokens 64] [--inactive 0] [--sample]
                                       [--process] [--grammar] [--kv fp16|fp8] [--paged PAGE_SIZE] [--shared-prefix P] [--window W]
+                                      [--softcap CAP] [--sinks]
 """
 import argparse
 import json
@@ -104,6 +105,9 @@ def main(argv=None, quiet=False):
                     help="with --paged: also time the step both ways on pools whose slots share a P-position prefix (DESIGN.md §26)")
     ap.add_argument("--window", type=int, default=0, metavar="W",
                     help="also time the step with this sliding window in every layer (DecodeStep(window=W), DESIGN.md §31)")
+    ap.add_argument("--softcap", type=float, default=None, metavar="CAP",
+                    help="also time the step with this logit soft cap in every layer (DecodeStep(softcap=CAP), DESIGN.md §32)")
+    ap.add_argument("--sinks", action="store_true", help="also time the step with per-head sinks in every layer (DecodeStep(sinks=...))")
     args = ap.parse_args(argv)
     kv8 = args.kv == "fp8"
     if args.shared_prefix and (not args.paged or args.shared_prefix % args.paged or args.shared_prefix < args.paged
@@ -236,6 +240,13 @@ def main(argv=None, quiet=False):
             windowed = {"window": args.window, "ms_step": timed(wstep), "ms_step_plain_again": timed(kernel_step),
                         "kv_rows_attended_first_step": int(torch.clamp(pos0[pos0 >= 0] + 1, max=args.window).sum())}
             del wstep
+        scored = None
+        if args.softcap is not None or args.sinks:
+            # the same caches, tokens and positions with the score modifiers in every layer, then the plain step again (the spread)
+            sinks = torch.randn(nlayers, cfg.num_attention_heads, generator=torch.Generator().manual_seed(9)).to(embed.device) if args.sinks else None
+            sstep = qp.DecodeStep(layers, embed, norm, lm_head, kc, vc, inv_freq, tok, pos, out_tok, generic=True, softcap=args.softcap, sinks=sinks)
+            scored = {"softcap": args.softcap, "sinks": bool(args.sinks), "ms_step": timed(sstep), "ms_step_plain_again": timed(kernel_step)}
+            del sstep
         shared = None
         if args.shared_prefix:
             P, ps, mp = args.shared_prefix, args.paged, args.context // args.paged
@@ -330,6 +341,8 @@ def main(argv=None, quiet=False):
             res["paged"] = paged
         if windowed is not None:
             res["window"] = windowed
+        if scored is not None:
+            res["score_mods"] = scored
         if shared is not None:
             res["shared_prefix"] = shared
         del kc, vc, kc_ref, vc_ref, ref_cache, kernel_step

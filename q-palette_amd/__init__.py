@@ -16,6 +16,7 @@ Layout:
                    ragged_prefill_attention / paged_ragged_prefill_attention / ragged_workspace: up to 128 rows of SEVERAL
                    sequences in one launch (segments described on the device);
                    window= on all of these but the shared-prefix launch: sliding-window attention; window_floor: its lower edge
+                   softcap= / sinks= on the same launches: the logit soft cap and per-head sinks
   paging.py        PagedKVCache: per-layer page pools, the block table and the host-side page allocator (reserve / release / fork /
                    trim: the pages a sliding window has passed go back to the pool);
                    SharedPrefix (cache.prefix): the groups of slots that share a forked prefix, as the shared-prefix launch reads them

@@ -88,6 +88,13 @@ _SIGNATURES = {
                                       _I, _I, _I, _I, ctypes.c_long, _F, ctypes.c_long, _P, ctypes.c_long, _P],
     "qpal_attn_rope_prefill_ragged_window": [_P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _P, _P, _P, _P, ctypes.c_long, _I,
                                              _I, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.c_long, _F, ctypes.c_long, _P, ctypes.c_long, _P],
+    "qpal_attn_rope_decode_batch_score": [_P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _I, _I, _I, _I,
+                                          _I, _I, _I, _I, ctypes.c_long, _F, ctypes.c_long, _F, _P, _P, ctypes.c_long, _P],
+    "qpal_attn_rope_prefill_score": [_P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _P, _P, _I, _I, _I, _I,
+                                     _I, _I, _I, _I, ctypes.c_long, _F, ctypes.c_long, _F, _P, _P, ctypes.c_long, _P],
+    "qpal_attn_rope_prefill_ragged_score": [_P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _P, _P, _P, _P, ctypes.c_long, _I,
+                                            _I, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.c_long, _F, ctypes.c_long, _F, _P, _P, ctypes.c_long,
+                                            _P],
     "qpal_lm_head_argmax": [_P, _P, _F, _P, _P, _P, _P, ctypes.c_long, _I, _I, _P],
     "qpal_lm_head_ws_bytes": [_I],
     "qpal_lm_head_logits": [_P, ctypes.c_long, _P, _F, _P, _P, ctypes.c_long, _I, _I, _I, _P],

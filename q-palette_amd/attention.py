@@ -45,6 +45,13 @@ with its own (Hugging Face's ``sliding_window``); ``None`` is no window.  Rotary
 the stored bytes do not change; nothing below the floor is read, so those rows may hold anything and a paged cache may give their
 pages back (``PagedKVCache.trim(slot, window_floor(pos, W))``).  ``W >= max_len`` is bit for bit the launch without a window.  The
 workspaces above serve the windowed launches as they are.
+
+Score modifiers (``qpal_attn_rope_decode_batch_score`` / ``_prefill_score`` / ``_prefill_ragged_score``): the same
+launches take ``softcap=c`` (a finite float > 0: every scaled score s becomes c * tanh(s / c) in front of the mask and the softmax,
+Gemma-2's ``attn_logit_softcapping``) and ``sinks=t`` (fp32 [nq] on the cache's device: one learned logit per query head that joins
+the softmax denominator and nothing else, gpt-oss's sinks; read on the device at every launch).  ``None`` for both is the launch
+as it was, bit for bit; ``sinks`` of -inf is bit for bit the launch without sinks.  With or without ``window``; not on the
+shared-prefix launch.  Nothing else changes: stored bytes, rules and workspaces are the plain launches'.
 """
 import math
 
@@ -61,6 +68,32 @@ def _window(window, who):
     if isinstance(window, bool) or not isinstance(window, int) or window < 1:
         raise QpalError(f"{who}: window must be None or an int >= 1, got {window!r}")
     return window
+
+
+def _score_mods(softcap, sinks, who):
+    """the softcap / sinks arguments of a launch: (None, None), or (softcap as a float or None, sinks or None); the tensor's shape
+    and device are checked by _score_args, where nq is known"""
+    if softcap is not None:
+        if isinstance(softcap, bool) or not isinstance(softcap, (int, float)) or not math.isfinite(softcap) or not softcap > 0:
+            raise QpalError(f"{who}: softcap must be None or a finite float > 0, got {softcap!r}")
+        softcap = float(softcap)
+        if not math.isfinite(torch.tensor(softcap, dtype=torch.float32).item()):
+            raise QpalError(f"{who}: softcap must be finite in fp32, got {softcap!r}")
+    if sinks is not None and not isinstance(sinks, torch.Tensor):
+        raise QpalError(f"{who}: sinks must be None or an fp32 [nq] tensor, got {type(sinks).__name__}")
+    return softcap, sinks
+
+
+def _score_args(who, mods, nq, dev):
+    """the two arguments of a _score entry point behind window: softcap (0: none) and the sinks' address (None: none)"""
+    softcap, sinks = mods
+    if sinks is not None:
+        if sinks.dtype != torch.float32 or sinks.shape != (nq,) or sinks.device != dev or not sinks.is_contiguous():
+            raise QpalError(f"{who}: sinks must be a contiguous float32 [{nq}] tensor on {dev}, got {sinks.dtype} "
+                            f"{list(sinks.shape)} on {sinks.device}")
+        if sinks.data_ptr() % 4:
+            raise QpalError(f"{who}: sinks must be 4-byte aligned")
+    return (0.0 if softcap is None else softcap, None if sinks is None else sinks.data_ptr())
 
 
 def window_floor(pos, window):
@@ -127,7 +160,7 @@ def _rows(t, name, B, width, who):
     return t.stride(0) if B > 1 else width
 
 
-def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=None, ws=None, window=None):
+def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=None, ws=None, window=None, softcap=None, sinks=None):
     """q fp32 [B, nq*hd], k / v fp32 [B, nkv*hd] (rows may be strided: column slices of one q|k|v output with a common row
     stride); kcache / vcache [B, nkv, max_len, hd] contiguous, 16-byte aligned, updated in place at row pos[b]; pos int64
     [B] on the device; inv_freq fp32 [hd/2].  Returns out fp16 [B, nq*hd] (``out`` if given: rows of an inactive sequence keep
@@ -139,14 +172,17 @@ def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=Non
     reached.  One attention_workspace serves both formats.
 
     window=W (an int >= 1): sequence b attends to positions window_floor(pos[b], W) .. pos[b] only (qpal_attn_rope_decode_batch_window);
-    cache rows below that floor are not read and may hold anything.  The attention_workspace of max_len serves it."""
-    window = _window(window, "decode_attention")
+    cache rows below that floor are not read and may hold anything.  The attention_workspace of max_len serves it.
+
+    softcap=c / sinks=t (the module's "Score modifiers", qpal_attn_rope_decode_batch_score): the capped scores, the new position's
+    included, and one sink logit per query head in the denominator; the stored rows and the workspace do not change."""
+    window, mods = _window(window, "decode_attention"), _score_mods(softcap, sinks, "decode_attention")
     if kcache.dim() != 4 or kcache.shape != vcache.shape:
         raise QpalError("decode_attention: kcache / vcache must both have shape [B, nkv, max_len, hd]")
     B, nkv, max_len, hd = kcache.shape
     entry = "qpal_attn_rope_decode_batch" + _cache_entry(kcache, vcache, "decode_attention")
     return _decode("decode_attention", entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, None,
-                   window=window)
+                   window=window, mods=mods)
 
 
 def _window_args(paged, empty, kcache, rows, max_len, scale, window):
@@ -156,15 +192,17 @@ def _window_args(paged, empty, kcache, rows, max_len, scale, window):
     return head + rows + (max_len if paged is None else 0, scale, window)
 
 
-def _decode(who, entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, paged, groups=None, window=None):
+def _decode(who, entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, paged, groups=None, window=None,
+            mods=(None, None)):
     """the checks and the launch the decode entry points share; paged: None, or the arguments that take max_len's place; groups: None,
     or the G of a shared-prefix launch (its workspace is shared_prefix_workspace's); window: None, or the W of the _window entry
-    point, which then takes `entry`'s place"""
+    point, which then takes `entry`'s place; mods: (softcap, sinks) — with either, the _score entry point takes it"""
     def pos_check():
         if pos.dtype != torch.int64 or pos.shape != (B,) or pos.device != kcache.device or not pos.is_contiguous():
             raise QpalError(f"{who}: pos must be a contiguous int64 [{B}] tensor on {kcache.device}")
 
     _, nq, ld, out, ld_out = _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos_check, B)
+    score = None if mods[0] is None and mods[1] is None else _score_args(who, mods, nq, kcache.device)  # (before the library)
     lib = _native.lib()
     if groups is None:
         need, maker = lib.qpal_attn_batch_ws_bytes(B, nq, nkv, hd, max_len), "attention_workspace"
@@ -172,7 +210,11 @@ def _decode(who, entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, 
         need, maker = lib.qpal_attn_prefix_ws_bytes(B, groups, nq, nkv, hd, max_len), "shared_prefix_workspace"
     ws_ptr, ws_bytes = _launch_ws(who, need, ws, kcache, maker)
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    if window is None:
+    if score is not None:
+        entry = "qpal_attn_rope_decode_batch_score"
+        shape = (_window_args(paged, (None, 0, 0, 0, 0), kcache, (B, nq, nkv, hd), max_len, scale, window or 0)
+                 + score)
+    elif window is None:
         shape = ((B, nq, nkv, hd, max_len) if paged is None else paged + (B, nq, nkv, hd)) + (scale,)
     else:
         entry, shape = "qpal_attn_rope_decode_batch_window", _window_args(paged, (None, 0, 0, 0, 0), kcache, (B, nq, nkv, hd), max_len, scale, window)
@@ -192,7 +234,7 @@ def prefill_workspace(T, nq, nkv, hd, max_len, device):
     return _workspace("qpal_attn_prefill_ws_bytes", device, T, nq, nkv, hd, max_len)
 
 
-def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=None, ws=None, window=None):
+def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=None, ws=None, window=None, softcap=None, sinks=None):
     """q fp32 [T, nq*hd], k / v fp32 [T, nkv*hd], 1 <= T <= 128: row t is the token at position pos0 + t (rows may be strided:
     column slices of one q|k|v output with a common row stride); kcache / vcache [nkv, max_len, hd] of ONE sequence,
     contiguous, 16-byte aligned (``kcache[b]`` of the batched layout), updated in place at rows pos0 .. pos0 + T - 1; pos0 int64
@@ -207,14 +249,18 @@ def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=N
 
     window=W (an int >= 1): row t attends to positions window_floor(pos0 + t, W) .. pos0 + t only (qpal_attn_rope_prefill_window); the
     cache ends up byte for byte as without a window, rows below window_floor(pos0, W) are not read and may hold anything.  The
-    prefill_workspace of max_len serves it."""
+    prefill_workspace of max_len serves it.
+
+    softcap=c / sinks=t (the module's "Score modifiers", qpal_attn_rope_prefill_score): every row's scores capped, one sink logit
+    per query head in every row's denominator; the cache ends up byte for byte as without them."""
     who = "prefill_attention"
-    window = _window(window, who)
+    window, mods = _window(window, who), _score_mods(softcap, sinks, who)
     if kcache.dim() != 3 or kcache.shape != vcache.shape:
         raise QpalError(f"{who}: kcache / vcache must both have shape [nkv, max_len, hd]")
     nkv, max_len, hd = kcache.shape
     entry = "qpal_attn_rope_prefill" + _cache_entry(kcache, vcache, who)
-    return _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, None, window=window)
+    return _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, None, window=window,
+                    mods=mods)
 
 
 def _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos_check=None, B=None):
@@ -255,18 +301,25 @@ def _launch_ws(who, need, ws, kcache, maker):
     return ws.data_ptr(), ws.numel() * ws.element_size()
 
 
-def _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, paged, window=None):
+def _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, paged, window=None,
+             mods=(None, None)):
     """the checks and the launch both prefill entry points share; paged: None, or the arguments that take max_len's place; window:
-    None, or the W of the _window entry point, which then takes `entry`'s place"""
+    None, or the W of the _window entry point, which then takes `entry`'s place; mods: (softcap, sinks) — with either, the _score
+    entry point takes it"""
     def pos_check():
         if pos0.dtype != torch.int64 or pos0.numel() != 1 or pos0.device != kcache.device:
             raise QpalError(f"{who}: pos0 must be an int64 tensor of one element on {kcache.device}")
 
     T, nq, ld, out, ld_out = _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos_check)
+    score = None if mods[0] is None and mods[1] is None else _score_args(who, mods, nq, kcache.device)  # (before the library)
     lib = _native.lib()
     ws_ptr, ws_bytes = _launch_ws(who, lib.qpal_attn_prefill_ws_bytes(T, nq, nkv, hd, max_len), ws, kcache, "prefill_workspace")
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    if window is None:
+    if score is not None:
+        entry = "qpal_attn_rope_prefill_score"
+        shape = (_window_args(paged, (None, 0, 0, 0), kcache, (T, nq, nkv, hd), max_len, scale, window or 0)
+                 + score)
+    elif window is None:
         shape = ((T, nq, nkv, hd, max_len) if paged is None else paged + (T, nq, nkv, hd)) + (scale,)
     else:
         entry, shape = "qpal_attn_rope_prefill_window", _window_args(paged, (None, 0, 0, 0), kcache, (T, nq, nkv, hd), max_len, scale, window)
@@ -314,7 +367,8 @@ def _pools_2d(kpool, vpool, block_table, who):
     return B, nkv, max_pages * page_size, hd, (block_table.data_ptr(), ld_table, num_pages, page_size, max_pages, _KV_FMT[kpool.dtype])
 
 
-def paged_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, scale=None, out=None, ws=None, window=None):
+def paged_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, scale=None, out=None, ws=None, window=None, softcap=None,
+                           sinks=None):
     """decode_attention on a paged cache: kpool / vpool [num_pages, nkv, page_size, hd] (fp16 or float8_e4m3fn, contiguous, 16-byte
     aligned, page_size in {16, 32, 64, 128, 256}), block_table int32 [B, max_pages] on the device with contiguous rows (a row
     stride >= max_pages): entry j of row b is the page of positions j * page_size .. of sequence b.  Everything else, and every
@@ -323,12 +377,12 @@ def paged_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, sc
     [0, num_pages) (an unreserved -1): reads go to page 0, the new row is dropped, that sequence's out row is unspecified.
 
     window=W: decode_attention's window; only entries that cover window_floor(pos[b], W) .. pos[b] are read, so the entries of pages
-    wholly below the floor may be -1 (PagedKVCache.trim)."""
+    wholly below the floor may be -1 (PagedKVCache.trim).  softcap / sinks: decode_attention's."""
     who = "paged_decode_attention"
-    window = _window(window, who)
+    window, mods = _window(window, who), _score_mods(softcap, sinks, who)
     B, nkv, max_len, hd, paged = _pools_2d(kpool, vpool, block_table, who)
     return _decode(who, "qpal_attn_rope_decode_batch_paged", q, k, v, kpool, vpool, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd,
-                   paged, window=window)
+                   paged, window=window, mods=mods)
 
 
 MAX_GROUPS = 16  # groups of one shared-prefix launch
@@ -381,17 +435,19 @@ def shared_prefix_workspace(B, G, nq, nkv, hd, max_len, device):
 
 
 def shared_prefix_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, prefix, scale=None, out=None, ws=None,
-                                   window=None):
+                                   window=None, softcap=None, sinks=None):
     """paged_decode_attention for slots that share the pages of a common prefix (``qpal_attn_rope_decode_batch_shared``, DESIGN.md
     §26).  prefix: a paging.SharedPrefix (``cache.prefix``) — row_group int32 [B], grp_slot / grp_len int32 [G] on the pools'
     device, read by the launches and never by the host.  A slot that reference_shared_rows() makes a member reads its group's first
     grp_len positions through table row grp_slot, once per group, and the rest through its own row; every other slot, the appended
     rows and the pools are bit for bit paged_decode_attention's.  Two launches on the current stream.  ws:
     shared_prefix_workspace(B, G, ...), always needed.  window: anything but None raises QpalError — the shared-prefix launches have
-    no window."""
+    no window.  softcap / sinks: the same — no score modifiers there either."""
     who = "shared_prefix_decode_attention"
     if window is not None:
         raise QpalError(f"{who}: no sliding window in the shared-prefix launches (window must be None)")
+    if softcap is not None or sinks is not None:
+        raise QpalError(f"{who}: no soft cap and no sinks in the shared-prefix launches (softcap and sinks must be None)")
     if block_table.dim() != 2:
         raise QpalError(f"{who}: block_table must have shape [B, max_pages >= 1], got {list(block_table.shape)}")
     tensors, G = _prefix_tensors(prefix, block_table.shape[0], kpool.device, who)  # (first: these checks need no device)
@@ -400,22 +456,23 @@ def shared_prefix_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_
                    paged + tensors, groups=G)
 
 
-def paged_prefill_attention(q, k, v, kpool, vpool, block_row, pos0, inv_freq, scale=None, out=None, ws=None, window=None):
+def paged_prefill_attention(q, k, v, kpool, vpool, block_row, pos0, inv_freq, scale=None, out=None, ws=None, window=None, softcap=None,
+                            sinks=None):
     """prefill_attention on a paged cache: the pools of paged_decode_attention and block_row int32 [max_pages], the block-table row
     of the ONE sequence (``block_table[b]``).  Every rule is prefill_attention's with max_len = max_pages * page_size (ws:
     prefill_workspace of that max_len); bit for bit that launch's result on the gathered cache, and the pools end up byte for byte
     as paged_decode_attention would have filled them token by token.  Only entries that cover positions 0 .. pos0 + T - 1 are read;
     the guard on entries outside [0, num_pages) is paged_decode_attention's.  window=W: prefill_attention's window; entries of pages
-    wholly below window_floor(pos0, W) may be -1."""
+    wholly below window_floor(pos0, W) may be -1.  softcap / sinks: prefill_attention's."""
     who = "paged_prefill_attention"
-    window = _window(window, who)
+    window, mods = _window(window, who), _score_mods(softcap, sinks, who)
     num_pages, nkv, page_size, hd = _pools(kpool, vpool, block_row, who)
     if block_row.dim() != 1 or block_row.shape[0] < 1:
         raise QpalError(f"{who}: block_row must have shape [max_pages >= 1], got {list(block_row.shape)}")
     max_pages = block_row.shape[0]
     paged = (block_row.data_ptr(), num_pages, page_size, max_pages, _KV_FMT[kpool.dtype])
     return _prefill(who, "qpal_attn_rope_prefill_paged", q, k, v, kpool, vpool, pos0, inv_freq, scale, out, ws, nkv,
-                    max_pages * page_size, hd, paged, window=window)
+                    max_pages * page_size, hd, paged, window=window, mods=mods)
 
 
 def ragged_workspace(R, S, nq, nkv, hd, max_len, device):
@@ -442,15 +499,20 @@ def _segments(who, seq, row0, pos0, dev):
 
 
 def _ragged(who, entry, q, k, v, kcache, vcache, seq, row0, pos0, S, inv_freq, scale, out, ws, B, nkv, max_len, hd, head, tail,
-            window=None):
+            window=None, mods=(None, None)):
     """the checks (behind _segments, which gave S) and the launch both ragged entry points share; head / tail: the arguments in
     front of and behind (R, S, B, nq, nkv, hd); window: None, or the W of the _window entry point, which then takes `entry`'s place
-    (tail empty: a paged launch, head its paged arguments)"""
+    (tail empty: a paged launch, head its paged arguments); mods: (softcap, sinks) — with either, the _score entry point takes it"""
     R, nq, ld, out, ld_out = _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd)
+    score = None if mods[0] is None and mods[1] is None else _score_args(who, mods, nq, kcache.device)  # (before the library)
     lib = _native.lib()
     ws_ptr, ws_bytes = _launch_ws(who, lib.qpal_attn_ragged_ws_bytes(R, S, nq, nkv, hd, max_len), ws, kcache, "ragged_workspace")
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    if window is None:
+    if score is not None:
+        entry = "qpal_attn_rope_prefill_ragged_score"
+        shape = (_window_args(head if not tail else None, (None, 0, 0, 0, 0), kcache, (R, S, B, nq, nkv, hd), max_len, scale, window or 0)
+                 + score)
+    elif window is None:
         shape = tuple(head) + (R, S, B, nq, nkv, hd) + tuple(tail) + (scale,)
     else:
         entry = "qpal_attn_rope_prefill_ragged_window"
@@ -464,7 +526,8 @@ def _ragged(who, entry, q, k, v, kcache, vcache, seq, row0, pos0, S, inv_freq, s
     return out
 
 
-def ragged_prefill_attention(q, k, v, kcache, vcache, seq, row0, pos0, inv_freq, scale=None, out=None, ws=None, window=None):
+def ragged_prefill_attention(q, k, v, kcache, vcache, seq, row0, pos0, inv_freq, scale=None, out=None, ws=None, window=None,
+                             softcap=None, sinks=None):
     """prefill_attention for rows of SEVERAL sequences in one launch (``qpal_attn_rope_prefill_ragged``).  q fp32 [R,
     nq*hd], k / v fp32 [R, nkv*hd], 1 <= R <= 128 (strided rows as for prefill_attention); kcache / vcache [B, nkv, max_len, hd],
     fp16 or float8_e4m3fn, contiguous, 16-byte aligned.  The rows are cut into S <= 128 segments described ON THE DEVICE (never read
@@ -478,29 +541,31 @@ def ragged_prefill_attention(q, k, v, kcache, vcache, seq, row0, pos0, inv_freq,
     sequence: the caller's error, that sequence's result is unspecified.  ws: ragged_workspace(R, S, ...).
 
     window=W: per segment prefill_attention's window (qpal_attn_rope_prefill_ragged_window): bit for bit the one-sequence windowed
-    launch wherever the unwindowed pair is; rows below window_floor(pos0[s], W) of a segment's sequence are not read."""
+    launch wherever the unwindowed pair is; rows below window_floor(pos0[s], W) of a segment's sequence are not read.
+
+    softcap=c / sinks=t (qpal_attn_rope_prefill_ragged_score): per segment prefill_attention's, bit for bit that launch's."""
     who = "ragged_prefill_attention"
-    window = _window(window, who)
+    window, mods = _window(window, who), _score_mods(softcap, sinks, who)
     if kcache.dim() != 4 or kcache.shape != vcache.shape:
         raise QpalError(f"{who}: kcache / vcache must both have shape [B, nkv, max_len, hd]")
     B, nkv, max_len, hd = kcache.shape
     S = _segments(who, seq, row0, pos0, kcache.device)  # (first: these checks need no device)
     _cache_entry(kcache, vcache, who)
     return _ragged(who, "qpal_attn_rope_prefill_ragged", q, k, v, kcache, vcache, seq, row0, pos0, S, inv_freq, scale, out, ws, B,
-                   nkv, max_len, hd, (_KV_FMT[kcache.dtype],), (max_len,), window=window)
+                   nkv, max_len, hd, (_KV_FMT[kcache.dtype],), (max_len,), window=window, mods=mods)
 
 
 def paged_ragged_prefill_attention(q, k, v, kpool, vpool, block_table, seq, row0, pos0, inv_freq, scale=None, out=None, ws=None,
-                                   window=None):
+                                   window=None, softcap=None, sinks=None):
     """ragged_prefill_attention on a paged cache (``qpal_attn_rope_prefill_ragged_paged``): the pools and the block table int32 [B,
     max_pages] of paged_decode_attention; segment s uses row seq[s] of the table.  Every rule is ragged_prefill_attention's with
     max_len = max_pages * page_size (ws: ragged_workspace of that max_len); bit for bit that launch's result on the gathered cache.
     Only entries that cover positions 0 .. pos0[s] + rows - 1 of an active segment are read; the guard on entries outside [0,
     num_pages) is paged_decode_attention's.  window=W: ragged_prefill_attention's window; entries of pages wholly below a segment's
-    window_floor(pos0[s], W) may be -1."""
+    window_floor(pos0[s], W) may be -1.  softcap / sinks: ragged_prefill_attention's."""
     who = "paged_ragged_prefill_attention"
-    window = _window(window, who)
+    window, mods = _window(window, who), _score_mods(softcap, sinks, who)
     S = _segments(who, seq, row0, pos0, kpool.device)
     B, nkv, max_len, hd, head = _pools_2d(kpool, vpool, block_table, who)
     return _ragged(who, "qpal_attn_rope_prefill_ragged_paged", q, k, v, kpool, vpool, seq, row0, pos0, S, inv_freq, scale, out, ws, B,
-                   nkv, max_len, hd, head, (), window=window)
+                   nkv, max_len, hd, head, (), window=window, mods=mods)

@@ -68,6 +68,10 @@ struct AttnBatchParams {
     const float *pre;
     // WIN only (qpal_attn_rope_decode_batch_window): sequence b attends to [max(0, pos[b] - window + 1), pos[b]]
     long window;
+    // SC only (qpal_attn_rope_decode_batch_score): softcap 0 — no cap, else every score is softcap * tanh(score /
+    // softcap) (inv_softcap = 1 / softcap); sinks null — none, else fp32 [nq], one logit per query head in the row's denominator
+    float softcap, inv_softcap;
+    const float *sinks;
 };
 
 // SHARED (PAGED only): a member of a group (shared_prefix_len) attends to [grp_len, pos] through its own table row — the chunk
@@ -80,7 +84,13 @@ struct AttnBatchParams {
 // page_shift per lane (scores) or per wave (values), so nothing depends on c0's alignment.  No row and no table entry below lo
 // is read: the clamp of the rows past the chunk goes to c0 >= lo.  The host sizes nsplit and the LDS chunk for min(max_len,
 // window rounded up to 4) positions, which rel = pos - lo never reaches.
-template <class CT, bool PAGED, int HD, int REP, bool SHARED = false, bool WIN = false>
+//
+// SC (score modifiers; built on the WIN body, window = max_len where the launch has none): the soft cap at the two
+// places a score is scaled, in front of the maximum; the sink of head h once per row, where the row is finished — the only
+// chunk's division or the last arriver's merge — as one more term exp(sink - M) of the denominator with M = max(row maximum,
+// sink).  The partials in the workspace stay (m, l, O) of the keys alone.  Both are wave-uniform runtime tests (softcap == 0,
+// sinks == nullptr); a sink of -inf gives M = the row's maximum, a rescale of exp(0) = 1 and a term of 0: the bits without sinks.
+template <class CT, bool PAGED, int HD, int REP, bool SHARED = false, bool WIN = false, bool SC = false>
 __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const AttnBatchParams<CT> p) {
     constexpr bool KV8 = kIsKv8<CT>;
     constexpr int NW = kBatchNW, NT = 64 * NW, HALF = HD / 2;
@@ -105,6 +115,7 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
     // (32-bit unsigned divisions: positions are below max_len < 2^30)
     [[maybe_unused]] long start = 0;  // SHARED: the positions the prefix launch has served for this slot; WIN: lo(pos)
     static_assert(!(SHARED && WIN), "no window in the shared-prefix launches");
+    static_assert(!SC || WIN, "the score modifiers are built on the windowed body");
     if constexpr (SHARED) {
         static_assert(PAGED, "groups share pages");
         int g;
@@ -261,7 +272,10 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
                         if (4 * mq + r < REP) {
-                            const float a = d[r] * p.scale;
+                            float a = d[r] * p.scale;
+                            if constexpr (SC) {
+                                if (p.softcap != 0.f) a = soft_cap(a, p.softcap, p.inv_softcap);
+                            }
                             sc[(4 * mq + r) * CL + t] = a;
                             mx4[r] = a > mx4[r] ? a : mx4[r];
                         }
@@ -297,7 +311,11 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
             a = fdot2(kn.z, qv.z, a);
             a = fdot2(kn.w, qv.w, a);
             a = group_sum<LPR>(a);
-            if (lane == 0) park[h] = a * p.scale;
+            a *= p.scale;
+            if constexpr (SC) {
+                if (p.softcap != 0.f) a = soft_cap(a, p.softcap, p.inv_softcap);
+            }
+            if (lane == 0) park[h] = a;
         }
     }
 #pragma unroll
@@ -404,6 +422,14 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
                 continue;
             }
         }
+        if constexpr (SC) {
+            if (neff == 1 && p.sinks) {  // the only chunk: the sink joins the denominator here
+                const float sk = p.sinks[kh * REP + h], M = sk > mxf[h] ? sk : mxf[h];
+                const float f = __expf(mxf[h] - M);
+                orow[idx] = __builtin_bit_cast(uint16_t, (_Float16)((v * f) / (sumf[h] * f + __expf(sk - M))));
+                continue;
+            }
+        }
         if (neff == 1) orow[idx] = __builtin_bit_cast(uint16_t, (_Float16)(v / sumf[h]));  // the only chunk
         else st_agent(wsp + h * (HD + 2) + 2 + d, v);
     }
@@ -432,6 +458,14 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
             const float m = ml[2 * (s * REP + h)];
             M = m > M ? m : M;
         }
+        [[maybe_unused]] float es = 0.f;  // SC: the sink's term of the denominator, once per row
+        if constexpr (SC) {
+            if (p.sinks) {
+                const float sk = p.sinks[kh * REP + h];
+                M = sk > M ? sk : M;
+                es = __expf(sk - M);
+            }
+        }
         float L = 0.f, o = 0.f;
         if constexpr (SHARED) {
             if (start > 0) {  // a member: the prefix partial is the chunk in front of the row's own
@@ -459,6 +493,7 @@ __global__ __launch_bounds__(64 * kBatchNW) void attn_rope_batch_kernel(const At
                 }
             }
         }
+        if constexpr (SC) L += es;
         orow[idx] = __builtin_bit_cast(uint16_t, (_Float16)(o / L));
     }
     if (tid == 0) __hip_atomic_store(as_global(ticket), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -529,17 +564,21 @@ size_t shared_ws_bytes(const BatchGeometry &g, const PrefixGeometry &x) {
 // sp: SHARED — the sharing of the launch; the prefix launch goes first, stream order is the only synchronisation between the two
 // window: WIN — the geometry is that of min(max_len, window rounded up to 4) positions (a short window in a long cache takes no
 // split and no merge floor); its workspace is never larger than the plain launch's of max_len
-template <class CT, bool PAGED, bool SHARED = false, bool WIN = false>
+// mods: SC — the soft cap and the sinks; a launch without a window runs the windowed body with window = max_len
+template <class CT, bool PAGED, bool SHARED = false, bool WIN = false, bool SC = false>
 int attn_rope_decode_batch(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16,
                            long ld_out, const long *pos, const float *inv_freq, int B, int nq, int nkv, int hd, long max_len,
                            float scale, void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0,
-                           const SharedPrefixArgs *sp = nullptr, long window = 0) {
+                           const SharedPrefixArgs *sp = nullptr, long window = 0, const ScoreMods *mods = nullptr) {
     if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
     BatchGeometry g;
     long geo_len = max_len;
     if constexpr (WIN) {
         const int rcs = attn_shape(B, nq, nkv, hd, max_len);
         if (rcs != QPAL_OK) return rcs;
+        if constexpr (SC) {
+            if (window == 0) window = max_len;
+        }
         geo_len = window_positions(window, max_len);
     }
     const int rc = batch_geometry(B, nq, nkv, hd, geo_len, g);
@@ -552,6 +591,7 @@ int attn_rope_decode_batch(const float *q, const float *k, const float *v, long 
         g.ws_bytes = shared_ws_bytes(g, x);  // (checked below as the plain launch's is)
     }
     uintptr_t al4 = PAGED ? reinterpret_cast<uintptr_t>(pg->table) : 0;
+    if constexpr (SC) al4 |= reinterpret_cast<uintptr_t>(mods->sinks);
     if constexpr (SHARED)
         al4 |= reinterpret_cast<uintptr_t>(sp->row_group) | reinterpret_cast<uintptr_t>(sp->grp_slot) | reinterpret_cast<uintptr_t>(sp->grp_len);
     const int rca = attn_args(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos, inv_freq, nq, hd, g.ws_bytes, ws, ws_bytes, al4);
@@ -564,6 +604,7 @@ int attn_rope_decode_batch(const float *q, const float *k, const float *v, long 
                           g.nsplit, g.chunk};
     if constexpr (PAGED) p.table = pg->table, p.ld_table = pg->ld_table, p.num_pages = pg->num_pages, p.page_shift = shift;
     if constexpr (WIN) p.window = window;
+    if constexpr (SC) p.softcap = mods->softcap, p.inv_softcap = mods->softcap != 0.f ? 1.f / mods->softcap : 0.f, p.sinks = mods->sinks;
     const int grid = B * nkv * g.nsplit, rep = nq / nkv;
     if constexpr (SHARED) {
         float *xf = wsf + plain_ws / sizeof(float);
@@ -574,7 +615,7 @@ int attn_rope_decode_batch(const float *q, const float *k, const float *v, long 
         if (rc2 != QPAL_OK) return rc2;
     }
     return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
-        return launch_lds<attn_rope_batch_kernel<CT, PAGED, HD(), REP(), SHARED, WIN>>(dim3(grid), dim3(64 * kBatchNW), g.lds, (int)kBatchLdsMax,
+        return launch_lds<attn_rope_batch_kernel<CT, PAGED, HD(), REP(), SHARED, WIN, SC>>(dim3(grid), dim3(64 * kBatchNW), g.lds, (int)kBatchLdsMax,
                                                                                    static_cast<hipStream_t>(stream), p);
     });
 }
@@ -643,6 +684,30 @@ extern "C" int qpal_attn_rope_decode_batch_window(const float *q, const float *k
     return paged_entry(false, pg, kv_fmt, [&](auto ct, int shift, long len) {
         return window ? launch(ct, T{}, T{}, len, &pg, shift) : launch(ct, T{}, F{}, len, &pg, shift);
     });
+}
+
+extern "C" int qpal_attn_rope_decode_batch_score(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache,
+                                                 void *out_f16, long ld_out, const long *pos, const float *inv_freq,
+                                                 const int *block_table, long ld_table, int num_pages, int page_size, int max_pages,
+                                                 int kv_fmt, int B, int nq, int nkv, int hd, long max_len, float scale, long window,
+                                                 float softcap, const float *sinks, void *ws, long ws_bytes, void *stream) {
+    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
+    if (window < 0 || !score_mods_ok(softcap)) return QPAL_E_PARAM;
+    if (softcap == 0.f && !sinks)
+        return qpal_attn_rope_decode_batch_window(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos, inv_freq, block_table, ld_table,
+                                                  num_pages, page_size, max_pages, kv_fmt, B, nq, nkv, hd, max_len, scale, window, ws,
+                                                  ws_bytes, stream);
+    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
+    const ScoreMods mods{softcap, sinks};
+    auto launch = [&](auto ct, auto paged, long len, const PageArgs *pg, int shift) {
+        return attn_rope_decode_batch<decltype(ct), paged(), false, true, true>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos, inv_freq,
+                                                                               B, nq, nkv, hd, len, scale, ws, ws_bytes, stream, pg, shift,
+                                                                               nullptr, window, &mods);
+    };
+    if (!block_table)  // contiguous caches [B][nkv][max_len][hd]
+        return for_kv_fmt(kv_fmt, [&](auto ct) { return launch(ct, std::false_type{}, max_len, nullptr, 0); });
+    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
+    return paged_entry(false, pg, kv_fmt, [&](auto ct, int shift, long len) { return launch(ct, std::true_type{}, len, &pg, shift); });
 }
 
 extern "C" long qpal_attn_prefix_ws_bytes(int B, int G, int nq, int nkv, int hd, long max_len) {

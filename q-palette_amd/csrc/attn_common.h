@@ -75,6 +75,25 @@ int paged_entry(bool any_null, const PageArgs &pg, int kv_fmt, F &&f) {
     return for_kv_fmt(kv_fmt, [&](auto ct) { return f(ct, shift, max_len); });
 }
 
+// the score modifiers of the _score entry points: softcap 0 — none; sinks null — none, else fp32 [nq] on the device
+struct ScoreMods {
+    float softcap;
+    const float *sinks;
+};
+
+// softcap as an argument: 0 or a finite value above it (anything else is QPAL_E_PARAM)
+inline bool score_mods_ok(float softcap) {
+    return softcap >= 0.f && softcap <= 3.0e38f;
+}
+
+// cap * tanh(s / cap) in fp32 with tanh(x) = 1 - 2 / (exp(2 x) + 1): one v_exp_f32 and one v_rcp_f32, no branch.  x is clamped to
+// +-15, where the form has long reached +-1 in fp32 (tanh(15) = 1 - 2e-13), so exp never overflows; the absolute error of the
+// tanh is a few 2^-24 (the rounding of exp(2 x) + 1 and of the subtraction from 1), of the result a few cap * 2^-24.
+__device__ __forceinline__ float soft_cap(float s, float cap, float inv_cap) {
+    const float x = fminf(fmaxf(s * inv_cap, -15.f), 15.f);
+    return cap * (1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * x) + 1.f));
+}
+
 // partials that cross workgroups go out and come in at agent scope: the L2s of the XCDs are not coherent with each other
 __device__ __forceinline__ void st_agent(float *p, float v) {
     __hip_atomic_store(as_global(reinterpret_cast<unsigned *>(p)), __builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -42,6 +42,10 @@ struct AttnPrefillParams {
     int num_pages, page_shift;
     // WIN only (the _window entry points): the row at position n attends to [max(0, n - window + 1), n]
     long window;
+    // SC only (the _score entry points): softcap 0 — no cap, else every score is softcap * tanh(score / softcap)
+    // (inv_softcap = 1 / softcap); sinks null — none, else fp32 [nq], one logit per query head in the row's denominator
+    float softcap, inv_softcap;
+    const float *sinks;
 };
 
 // RAGGED: T = the rows R of q / k / v / out, pos0 = int64 [S], kcache / vcache = [B][nkv][max_len][HD] (PAGED: table = int32
@@ -97,10 +101,17 @@ __device__ __forceinline__ u32x4 rope_chunk(const float *src, int ch, long pos, 
 // row with no admitted key in a tile or a whole chunk keeps m = -3e38, l = 0, O = 0, which the running rescale (alpha = 0 once a
 // key arrives) and the merge (weight exp(-3e38 - M) = 0) meet today behind the diagonal.  window >= 1: a tile's own new rows lie
 // at or above kmin, so they are fetched, and stored, as without a window.
-template <class CT, bool PAGED, bool RAGGED, int HD, int REP, bool WIN = false>
+//
+// SC (score modifiers; built on the WIN body, window = max_len where the launch has none): the soft cap where sv =
+// s * scale is formed, in front of the mask and the maximum; the sink of the row's head once per row — behind the last tile of a
+// one-chunk row, or in the last arriver's merge — as one more term exp(sink - M) of the denominator, M = max(row maximum, sink).
+// The running (m, l, O) and the partials in the workspace stay those of the keys alone.  Both are wave-uniform runtime tests; a
+// sink of -inf leaves M, a rescale of exp(0) = 1 and a term of 0: the bits without sinks.
+template <class CT, bool PAGED, bool RAGGED, int HD, int REP, bool WIN = false, bool SC = false>
 __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
     const std::conditional_t<RAGGED, AttnRaggedParams<CT>, AttnPrefillParams<CT>> p) {
     constexpr bool KV8 = kIsKv8<CT>;
+    static_assert(!SC || WIN, "the score modifiers are built on the windowed body");
     using KR = std::conditional_t<KV8, u32x2, u32x4>;  // eight elements of a cache row as prefetched
     constexpr int QS = pf_qs(REP), NW = REP * QS, NT = 64 * NW, TQ = 16 * QS, R = 16 * NW;
     constexpr int HALF = HD / 2, KC = HD / 32, DT = HD / 16, CPR = HD / 8;
@@ -342,8 +353,19 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
                     ok[4 * kt + r] = n <= qpos;  // causal (keys past the tile's last row lie past every row of it)
                     if constexpr (WIN) ok[4 * kt + r] = n <= qpos && n >= qlo;  // and the row's own lower edge
                     sv[4 * kt + r] = s[kt][r] * p.scale;
-                    if (ok[4 * kt + r]) mx = fmaxf(mx, sv[4 * kt + r]);
+                    if constexpr (!SC) {
+                        if (ok[4 * kt + r]) mx = fmaxf(mx, sv[4 * kt + r]);
+                    }
                 }
+            if constexpr (SC) {  // the cap on the tile's eight scores behind ONE wave-uniform test, then the maximum in the same order
+                if (p.softcap != 0.f) {
+    #pragma unroll
+                    for (int e = 0; e < 8; e++) sv[e] = soft_cap(sv[e], p.softcap, p.inv_softcap);
+                }
+    #pragma unroll
+                for (int e = 0; e < 8; e++)
+                    if (ok[e]) mx = fmaxf(mx, sv[e]);
+            }
             mx = fmaxf(mx, lane_xor<16>(mx));
             mx = fmaxf(mx, lane_xor<32>(mx));
             const float m_new = fmaxf(m_run, mx);
@@ -381,11 +403,23 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
     if (neff == 1) {  // the only chunk
         if (trow < T) {
             uint16_t *orow = orows + (long)trow * p.ld_out + (long)head * HD;
-            const float inv = 1.f / l_run;
+            float inv = 1.f / l_run;
+            [[maybe_unused]] float f = 1.f;  // SC: the rescale of the keys' sums to the maximum that includes the sink
+            if constexpr (SC) {
+                if (p.sinks) {  // the row is finished here: the sink joins the denominator
+                    const float sk = p.sinks[head], M = fmaxf(m_run, sk);
+                    f = __expf(m_run - M);
+                    inv = 1.f / (l_run * f + __expf(sk - M));
+                }
+            }
 #pragma unroll
             for (int dt = 0; dt < DT; dt++)
 #pragma unroll
-                for (int r = 0; r < 4; r++) orow[16 * dt + 4 * mq + r] = __builtin_bit_cast(uint16_t, (_Float16)(oacc[dt][r] * inv));
+                for (int r = 0; r < 4; r++) {
+                    float o = oacc[dt][r];
+                    if constexpr (SC) o *= f;
+                    orow[16 * dt + 4 * mq + r] = __builtin_bit_cast(uint16_t, (_Float16)(o * inv));
+                }
         }
         return;
     }
@@ -410,6 +444,13 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
         float M = -3.0e38f;
         for (int sx = 0; sx < neff; sx++) M = fmaxf(M, ld_agent(base + ((long)sx * R + tid) * (HD + 2)));
         float L = 0.f;
+        if constexpr (SC) {
+            if (p.sinks) {  // once per row, in front of the chunks' terms
+                const float sk = p.sinks[kh * REP + (tid >> 4) % REP];
+                M = fmaxf(M, sk);
+                L = __expf(sk - M);
+            }
+        }
         for (int sx = 0; sx < neff; sx++) {
             const float *pp = base + ((long)sx * R + tid) * (HD + 2);
             const float f = __expf(ld_agent(pp) - M);

@@ -48,16 +48,21 @@ int prefill_geometry(int T, int nq, int nkv, int hd, long max_len, PrefillGeomet
 
 // the entry points: the same checks, geometry and launch, the cache element type and the row addressing apart (PAGED: kcache /
 // vcache are the pools, `pg` the sequence's block-table row, max_len = max_pages * page_size)
-template <class CT, bool PAGED, bool WIN = false>
+// mods: SC — the soft cap and the sinks; a launch without a window runs the windowed body with window = max_len
+template <class CT, bool PAGED, bool WIN = false, bool SC = false>
 int attn_rope_prefill(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16,
                       long ld_out, const long *pos0, const float *inv_freq, int T, int nq, int nkv, int hd, long max_len, float scale,
-                      void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0, long window = 0) {
+                      void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0, long window = 0,
+                      const ScoreMods *mods = nullptr) {
     if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos0 || !inv_freq) return QPAL_E_NULL;
+    if constexpr (SC) {
+        if (window == 0) window = max_len;
+    }
     PrefillGeometry g;
     int rc = prefill_geometry(T, nq, nkv, hd, max_len, g, WIN ? window : 0);
     if (rc != QPAL_OK) return rc;
     rc = attn_args(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, nq, hd, g.ws_bytes, ws, ws_bytes,
-                   PAGED ? reinterpret_cast<uintptr_t>(pg->table) : 0);
+                   (PAGED ? reinterpret_cast<uintptr_t>(pg->table) : 0) | (SC ? reinterpret_cast<uintptr_t>(mods->sinks) : 0));
     if (rc != QPAL_OK) return rc;
     float *wsf = static_cast<float *>(ws);
     AttnPrefillParams<CT> p{q, k, v, ld_qkv, static_cast<CT *>(kcache), static_cast<CT *>(vcache),
@@ -66,9 +71,10 @@ int attn_rope_prefill(const float *q, const float *k, const float *v, long ld_qk
                             g.nsplit, g.ntile};
     if constexpr (PAGED) p.table = pg->table, p.num_pages = pg->num_pages, p.page_shift = shift;
     if constexpr (WIN) p.window = window;
+    if constexpr (SC) p.softcap = mods->softcap, p.inv_softcap = mods->softcap != 0.f ? 1.f / mods->softcap : 0.f, p.sinks = mods->sinks;
     const int grid = nkv * g.ntile * g.nsplit, rep = nq / nkv;
     return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
-        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, false, HD(), REP(), WIN>), dim3(grid), dim3(64 * REP() * pf_qs(REP())), 0,
+        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, false, HD(), REP(), WIN, SC>), dim3(grid), dim3(64 * REP() * pf_qs(REP())), 0,
                            static_cast<hipStream_t>(stream), p);
         return (int)hipGetLastError();
     });
@@ -134,4 +140,26 @@ extern "C" int qpal_attn_rope_prefill_window(const float *q, const float *k, con
     return paged_entry(false, pg, kv_fmt, [&](auto ct, int shift, long len) {
         return window ? launch(ct, Y{}, Y{}, len, &pg, shift) : launch(ct, Y{}, N{}, len, &pg, shift);
     });
+}
+
+extern "C" int qpal_attn_rope_prefill_score(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache,
+                                            void *out_f16, long ld_out, const long *pos0, const float *inv_freq, const int *block_row,
+                                            int num_pages, int page_size, int max_pages, int kv_fmt, int T, int nq, int nkv, int hd,
+                                            long max_len, float scale, long window, float softcap, const float *sinks, void *ws,
+                                            long ws_bytes, void *stream) {
+    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos0 || !inv_freq) return QPAL_E_NULL;
+    if (window < 0 || !score_mods_ok(softcap)) return QPAL_E_PARAM;
+    if (softcap == 0.f && !sinks)
+        return qpal_attn_rope_prefill_window(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, block_row, num_pages,
+                                             page_size, max_pages, kv_fmt, T, nq, nkv, hd, max_len, scale, window, ws, ws_bytes, stream);
+    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
+    const ScoreMods mods{softcap, sinks};
+    auto launch = [&](auto ct, auto paged, long len, const PageArgs *pg, int shift) {
+        return attn_rope_prefill<decltype(ct), paged(), true, true>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, T, nq,
+                                                                   nkv, hd, len, scale, ws, ws_bytes, stream, pg, shift, window, &mods);
+    };
+    if (!block_row)  // a contiguous cache [nkv][max_len][hd]
+        return for_kv_fmt(kv_fmt, [&](auto ct) { return launch(ct, std::false_type{}, max_len, nullptr, 0); });
+    const PageArgs pg{block_row, max_pages, num_pages, page_size, max_pages};
+    return paged_entry(false, pg, kv_fmt, [&](auto ct, int shift, long len) { return launch(ct, std::true_type{}, len, &pg, shift); });
 }

@@ -32,17 +32,21 @@ int ragged_geometry(int R, int S, int nq, int nkv, int hd, long max_len, Prefill
     return QPAL_OK;
 }
 
-template <class CT, bool PAGED, bool WIN = false>
+// mods: SC — the soft cap and the sinks; a launch without a window runs the windowed body with window = max_len
+template <class CT, bool PAGED, bool WIN = false, bool SC = false>
 int attn_rope_ragged(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16, long ld_out,
                      const int *seq, const int *row0, const long *pos0, const float *inv_freq, int R, int S, int B, int nq, int nkv, int hd,
                      long max_len, float scale, void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0,
-                     long window = 0) {
+                     long window = 0, const ScoreMods *mods = nullptr) {
+    if constexpr (SC) {
+        if (window == 0) window = max_len;
+    }
     PrefillGeometry g;
     int rc = ragged_geometry(R, S, nq, nkv, hd, max_len, g, WIN ? window : 0);
     if (rc != QPAL_OK) return rc;
     if (B < 1) return QPAL_E_SHAPE;
     rc = attn_args(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, nq, hd, g.ws_bytes, ws, ws_bytes,
-                   PAGED ? reinterpret_cast<uintptr_t>(pg->table) : 0);
+                   (PAGED ? reinterpret_cast<uintptr_t>(pg->table) : 0) | (SC ? reinterpret_cast<uintptr_t>(mods->sinks) : 0));
     if (rc != QPAL_OK) return rc;
     if ((reinterpret_cast<uintptr_t>(seq) | reinterpret_cast<uintptr_t>(row0)) & 3) return QPAL_E_ALIGN;
     float *wsf = static_cast<float *>(ws);
@@ -54,9 +58,10 @@ int attn_rope_ragged(const float *q, const float *k, const float *v, long ld_qkv
     p.seq = seq, p.row0 = row0, p.S = S, p.B = B;
     if constexpr (PAGED) p.table = pg->table, p.num_pages = pg->num_pages, p.page_shift = shift, p.ld_table = pg->ld_table;
     if constexpr (WIN) p.window = window;
+    if constexpr (SC) p.softcap = mods->softcap, p.inv_softcap = mods->softcap != 0.f ? 1.f / mods->softcap : 0.f, p.sinks = mods->sinks;
     const int grid = nkv * g.ntile * g.nsplit, rep = nq / nkv;
     return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
-        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, true, HD(), REP(), WIN>), dim3(grid), dim3(64 * REP() * pf_qs(REP())), 0,
+        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, true, HD(), REP(), WIN, SC>), dim3(grid), dim3(64 * REP() * pf_qs(REP())), 0,
                            static_cast<hipStream_t>(stream), p);
         return (int)hipGetLastError();
     });
@@ -122,4 +127,29 @@ extern "C" int qpal_attn_rope_prefill_ragged_window(const float *q, const float 
     return paged_entry(false, pg, kv_fmt, [&](auto ct, int shift, long len) {
         return window ? launch(ct, Y{}, Y{}, len, &pg, shift) : launch(ct, Y{}, N{}, len, &pg, shift);
     });
+}
+
+extern "C" int qpal_attn_rope_prefill_ragged_score(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache,
+                                                   void *out_f16, long ld_out, const int *seq, const int *row0, const long *pos0,
+                                                   const float *inv_freq, const int *block_table, long ld_table, int num_pages,
+                                                   int page_size, int max_pages, int kv_fmt, int R, int S, int B, int nq, int nkv, int hd,
+                                                   long max_len, float scale, long window, float softcap, const float *sinks, void *ws,
+                                                   long ws_bytes, void *stream) {
+    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !seq || !row0 || !pos0 || !inv_freq) return QPAL_E_NULL;
+    if (window < 0 || !score_mods_ok(softcap)) return QPAL_E_PARAM;
+    if (softcap == 0.f && !sinks)
+        return qpal_attn_rope_prefill_ragged_window(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, seq, row0, pos0, inv_freq, block_table,
+                                                    ld_table, num_pages, page_size, max_pages, kv_fmt, R, S, B, nq, nkv, hd, max_len, scale,
+                                                    window, ws, ws_bytes, stream);
+    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
+    const ScoreMods mods{softcap, sinks};
+    auto launch = [&](auto ct, auto paged, long len, const PageArgs *pg, int shift) {
+        return attn_rope_ragged<decltype(ct), paged(), true, true>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, seq, row0, pos0, inv_freq, R,
+                                                                  S, B, nq, nkv, hd, len, scale, ws, ws_bytes, stream, pg, shift, window,
+                                                                  &mods);
+    };
+    if (!block_table)  // contiguous caches [B][nkv][max_len][hd]
+        return for_kv_fmt(kv_fmt, [&](auto ct) { return launch(ct, std::false_type{}, max_len, nullptr, 0); });
+    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
+    return paged_entry(false, pg, kv_fmt, [&](auto ct, int shift, long len) { return launch(ct, std::true_type{}, len, &pg, shift); });
 }

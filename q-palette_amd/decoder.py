@@ -77,6 +77,14 @@ included.  A batch-1 DecodeStep with a window launches the batched attention at 
 window), and `shared_prefix=` together with a window raises QpalError.  The steps never give pages back: on a paged cache the
 caller calls `cache.trim(slot, window_floor(pos, W))` with the LARGEST window of any layer between steps (not at all if one layer
 has none).
+
+All five also take `softcap=`, `sinks=` and `attn_scale=`.  softcap: None, a finite float > 0 or one entry per layer —
+every attention score s of that layer becomes softcap * tanh(s / softcap) (Gemma-2's attn_logit_softcapping).  sinks: None or an
+fp32 [n_layers, nq] tensor on the device — layer i's launch reads row i, one logit per query head that joins the softmax
+denominator only (gpt-oss); the launches read it on the device, so a captured step follows values changed in place between replays.
+attn_scale: None (1 / sqrt(head_dim)) or the factor on q.k (Gemma-2 27B's query_pre_attn_scalar).  Nothing else in a step changes, the
+launch count included; a batch-1 DecodeStep with a cap or sinks launches the batched attention at B = 1, and `shared_prefix=`
+together with either raises QpalError.
 """
 import math
 
@@ -86,6 +94,7 @@ from . import _native as nat
 from . import hadamard as had
 from . import grammar as gram_mod
 from . import linear, logits, lora, ops, sampling
+from .attention import _score_mods as _check_score_mods
 from .attention import _window as _check_one_window
 from .attention import (attention_workspace, decode_attention, paged_decode_attention, paged_prefill_attention,
                         paged_ragged_prefill_attention, prefill_attention, prefill_workspace, ragged_prefill_attention, ragged_workspace,
@@ -135,14 +144,18 @@ class _Rows:
     _launches_per = None  # "<class>: launches are per <what>" where a step has no launches per token
 
     def __init__(self, who, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows, sampler, block_table, slots=None,
-                 logits_tail=False, native_argmax=False, adapters=None, processor=None, grammar=None, window=None):
+                 logits_tail=False, native_argmax=False, adapters=None, processor=None, grammar=None, window=None, softcap=None,
+                 sinks=None, attn_scale=None):
         """window: None, an int or one entry per layer — the sliding window of every layer's attention launch (self.window[i]);
+        softcap: None, a float or one entry per layer (self.softcap[i]); sinks: None or fp32 [n_layers, nq] (layer i: row i);
+        attn_scale: None (1 / sqrt(head_dim)) or the scale of every layer's scores;
         slots: the sequences of the caches where the caller fixes them (DecodeStep's B), else read off the caches or the table;
         logits_tail: the tail is qpal_lm_head_logits without a sampler too; native_argmax: `_argmax_tail` is the one-launch kernel;
         adapters: a lora.LoraBank of these layers and slots, or None; processor: a logits.LogitProcessor of these slots, or None;
         grammar: a grammar.GrammarBank of these slots, or None"""
         self.block_table = block_table
         self.window = self._check_window(who, window, len(layers))
+        self.softcap, self.sinks = self._check_score(who, softcap, sinks, layers, embed.device)
         self.slots = self._check_table(who, kcache, block_table, slots)
         self.adapters = self._check_adapters(who, adapters, self.slots, layers, embed)
         # the adapter of every row, looked up on the device before the layers run (DecodeStep: the bank's own vector, row = slot)
@@ -160,6 +173,10 @@ class _Rows:
         # paged: the pools' third dimension is the page size
         self.context = kcache[0].shape[2] * (1 if block_table is None else block_table.shape[1])
         self.eps, self.attn_scale = layers[0].input_layernorm.eps, 1.0 / math.sqrt(att.head_dim)
+        if attn_scale is not None:
+            if isinstance(attn_scale, bool) or not isinstance(attn_scale, (int, float)) or not math.isfinite(attn_scale):
+                raise nat.QpalError(f"{who}: attn_scale must be None or a finite float, got {attn_scale!r}")
+            self.attn_scale = float(attn_scale)
         hk, self.hidden_K = had.get_hadK(H)
         self.hidden_hadT = None if hk is None else hk.T.contiguous().half().to(dev)
         self.h32 = torch.zeros(rows, H, dtype=torch.float32, device=dev)
@@ -179,6 +196,26 @@ class _Rows:
         if not isinstance(window, (list, tuple)) or len(window) != n_layers:
             raise nat.QpalError(f"{who}: window must be None, an int >= 1 or one entry per layer ({n_layers}), got {window!r}")
         return [_check_one_window(w, who) for w in window]
+
+    @staticmethod
+    def _check_score(who, softcap, sinks, layers, dev):
+        """softcap= and sinks= of a step class: one cap (None or a float > 0) per layer, and sinks (None or fp32 [n_layers, nq])"""
+        n_layers, nq = len(layers), layers[0].self_attn.num_heads
+        if softcap is None or isinstance(softcap, (int, float)):
+            caps = [_check_score_mods(softcap, None, who)[0]] * n_layers
+        elif isinstance(softcap, (list, tuple)) and len(softcap) == n_layers:
+            caps = [_check_score_mods(c, None, who)[0] for c in softcap]
+        else:
+            raise nat.QpalError(f"{who}: softcap must be None, a float > 0 or one entry per layer ({n_layers}), got {softcap!r}")
+        if sinks is not None:
+            if (not isinstance(sinks, torch.Tensor) or sinks.dtype != torch.float32 or sinks.shape != (n_layers, nq)
+                    or sinks.device != dev or not sinks.is_contiguous()):
+                raise nat.QpalError(f"{who}: sinks must be None or a contiguous float32 [{n_layers}, {nq}] tensor on {dev}")
+        return caps, sinks
+
+    def _score(self, i):
+        """the window= / softcap= / sinks= of layer i's attention launch"""
+        return {"window": self.window[i], "softcap": self.softcap[i], "sinks": None if self.sinks is None else self.sinks[i]}
 
     @staticmethod
     def _check_table(who, kcache, block_table, B=None):
@@ -349,6 +386,8 @@ class DecodeStep(_Rows):
     window: None, an int W >= 1 or one entry per layer — sequence b attends to positions max(0, pos[b] - W + 1) .. pos[b] in the
     layers that have one (decode_attention's window=); with one anywhere a batch of one launches the batched attention too, and
     shared_prefix with a window is a QpalError.  The step never trims: PagedKVCache.trim between replays is the caller's.
+    softcap / sinks / attn_scale: the module's last paragraph (decode_attention's softcap= and sinks=, layer i reading sinks[i]);
+    with either modifier a batch of one launches the batched attention, and shared_prefix with either is a QpalError.
     adapters: a lora.LoraBank of B slots — row b runs with adapter bank.slot_adapter[b], read by the launches themselves: four more
     launches per layer.  At batch 1 the interleaved up|gate epilogue and down_proj's staged rotation are then off (they never put
     up | gate into memory: the swiglu_epilogue=False step); RMSNorm and the rotation stay inside the GEMV staging.
@@ -363,16 +402,19 @@ class DecodeStep(_Rows):
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok, generic=False,
                  swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True, sampler=None, block_table=None,
-                 adapters=None, processor=None, grammar=None, shared_prefix=None, window=None):
+                 adapters=None, processor=None, grammar=None, shared_prefix=None, window=None, softcap=None, sinks=None,
+                 attn_scale=None):
         B = tok.shape[0]
         if shared_prefix is not None and block_table is None:
             raise nat.QpalError("DecodeStep: shared_prefix needs a paged cache (block_table=cache.table)")
         if shared_prefix is not None and any(w is not None for w in self._check_window("DecodeStep", window, len(layers))):
             raise nat.QpalError("DecodeStep: no sliding window in the shared-prefix launches (shared_prefix with window)")
+        if shared_prefix is not None and (softcap is not None or sinks is not None):
+            raise nat.QpalError("DecodeStep: no soft cap and no sinks in the shared-prefix launches (shared_prefix with softcap / sinks)")
         self.batch1 = B == 1 and not generic
         super().__init__("DecodeStep", layers, embed, norm, lm_head, kcache, vcache, inv_freq, B, sampler, block_table, slots=B,
                          native_argmax=self.batch1 and native_lm_head and self._has_argmax_kernel(embed, lm_head), adapters=adapters,
-                         processor=processor, grammar=grammar, window=window)
+                         processor=processor, grammar=grammar, window=window, softcap=softcap, sinks=sinks, attn_scale=attn_scale)
         self._row_slot = None if processor is None and grammar is None else torch.arange(B, dtype=torch.int32, device=embed.device)  # row = slot
         if adapters is not None:
             self.row_adapter, swiglu_epilogue = adapters.slot_adapter, False  # row = slot
@@ -394,9 +436,10 @@ class DecodeStep(_Rows):
                                    k28_fusion and k28_in_gemv(m)))
         # the fused single-sequence attention kernel reads contiguous fp16 caches only: on float8_e4m3fn or paged caches the batch-1
         # step keeps its GEMV fusions and launches the batched attention at B = 1 (same launch count); it has no
-        # window either: a step with a window in any layer does the same
+        # window either, no soft cap and no sinks: a step with one of them in any layer does the same
         self.attn_batch = (not self.batch1 or kcache[0].dtype != torch.float16 or block_table is not None
-                           or any(w is not None for w in self.window))
+                           or any(w is not None for w in self.window) or any(c is not None for c in self.softcap)
+                           or self.sinks is not None)
         self.shared_prefix = shared_prefix
         if shared_prefix is not None:
             self.attn_ws = shared_prefix_workspace(B, shared_prefix.G, self.nq, self.nkv, self.head_dim, self.context, dev)
@@ -448,7 +491,7 @@ class DecodeStep(_Rows):
             attend, cache = decode_attention, (kc, vc)
         else:
             attend, cache = paged_decode_attention, (kc, vc, self.block_table)
-        attend(q, k, v, *cache, self.pos, self.inv_freq, scale=self.attn_scale, out=out, ws=self.attn_ws, window=self.window[i])
+        attend(q, k, v, *cache, self.pos, self.inv_freq, scale=self.attn_scale, out=out, ws=self.attn_ws, **self._score(i))
 
     def _mlp(self, i, h32, ug32):
         if not self.ug_il:
@@ -508,19 +551,20 @@ class Prefill(_Rows):
     masked with the slot's state as it stands (bank.set / reset put it at the start) and the drawn token advances it.
 
     window: as for DecodeStep (prefill_attention's window=): the row at position p attends to positions max(0, p - W + 1) .. p; the
-    caches end up byte for byte as without a window."""
+    caches end up byte for byte as without a window.  softcap / sinks / attn_scale: as for DecodeStep (prefill_attention's)."""
 
     _launches_per = "Prefill: launches are per chunk"
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, native_lm_head=True, sampler=None,
-                 block_table=None, adapters=None, processor=None, grammar=None, window=None):
+                 block_table=None, adapters=None, processor=None, grammar=None, window=None, softcap=None, sinks=None,
+                 attn_scale=None):
         if not 1 <= int(chunk) <= 128:
             raise nat.QpalError(f"Prefill: chunk must be in 1 .. 128, got {chunk}")
         self.chunk = int(chunk)
         dev, H = embed.device, embed.shape[1]
         super().__init__("Prefill", layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.chunk, sampler, block_table,
                          native_argmax=native_lm_head and self._has_argmax_kernel(embed, lm_head), adapters=adapters,
-                         processor=processor, grammar=grammar, window=window)
+                         processor=processor, grammar=grammar, window=window, softcap=softcap, sinks=sinks, attn_scale=attn_scale)
         self._row_slot = None if processor is None and grammar is None else torch.zeros(1, dtype=torch.int32, device=dev)  # the call's slot
         self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
         self.out_tok = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -535,7 +579,7 @@ class Prefill(_Rows):
             attend, cache = prefill_attention, (kc[self.slot], vc[self.slot])
         else:
             attend, cache = paged_prefill_attention, (kc, vc, self.block_table[self.slot])
-        attend(q, k, v, *cache, self.pos, self.inv_freq, scale=self.attn_scale, out=out, ws=self.attn_ws, window=self.window[i])
+        attend(q, k, v, *cache, self.pos, self.inv_freq, scale=self.attn_scale, out=out, ws=self.attn_ws, **self._score(i))
 
     def hidden(self):
         """fp16 [1, H]: the final norm of the last prompt row"""
@@ -600,13 +644,14 @@ class Score(Prefill):
     block_table: as for Prefill (a paged cache; the caller reserves the slot's pages for pos0 .. pos0 + N - 1).  adapters: as for
     Prefill.  top_logprobs=n (1 .. 64): one `qpal_top_logprob` launch more per chunk; sc.top_id int32 / sc.top_logprob fp32 [N - 1, n]
     are then the n likeliest tokens at every scored position and their log-probabilities (views of max_tokens x n buffers, like lp).
-    window: as for Prefill — the log-probabilities are those of the model with that sliding window."""
+    window, softcap, sinks, attn_scale: as for Prefill — the log-probabilities are those of the model with that attention."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, max_tokens=None, block_table=None,
-                 adapters=None, top_logprobs=0, window=None):
+                 adapters=None, top_logprobs=0, window=None, softcap=None, sinks=None, attn_scale=None):
         self._check_lm_head("Score", embed, lm_head)
         super().__init__(layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=chunk, native_lm_head=False,
-                         block_table=block_table, adapters=adapters, window=window)
+                         block_table=block_table, adapters=adapters, window=window, softcap=softcap, sinks=sinks,
+                         attn_scale=attn_scale)
         self.max_tokens = self.context if max_tokens is None else int(max_tokens)
         if self.max_tokens < 2:
             raise nat.QpalError(f"Score: max_tokens must be at least 2, got {max_tokens}")
@@ -676,12 +721,13 @@ class RaggedStep(_Rows):
 
     processor: not on a RaggedStep (QpalError): a prompt chunk's rows would have to be counted row by row; SpeculativeStep has one.
     grammar: not on a RaggedStep either (QpalError); DecodeStep, Prefill and SpeculativeStep take one.
-    window: as for DecodeStep (ragged_prefill_attention's window=), per segment what Prefill does with it."""
+    window: as for DecodeStep (ragged_prefill_attention's window=), per segment what Prefill does with it.
+    softcap / sinks / attn_scale: as for DecodeStep."""
 
     _launches_per = "RaggedStep: launches are per step"
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=128, segments=16, sampler=None, block_table=None,
-                 adapters=None, processor=None, grammar=None, window=None):
+                 adapters=None, processor=None, grammar=None, window=None, softcap=None, sinks=None, attn_scale=None):
         who = type(self).__name__
         if processor is not None and not isinstance(self, SpeculativeStep):
             raise nat.QpalError("RaggedStep: no processor on a ragged step (DecodeStep, Prefill and SpeculativeStep take one)")
@@ -691,7 +737,8 @@ class RaggedStep(_Rows):
             raise nat.QpalError(f"{who}: rows and segments must be in 1 .. 128, got {rows}, {segments}")
         self.rows, self.segments = int(rows), int(segments)
         super().__init__(who, layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.rows, sampler, block_table, logits_tail=True,
-                         adapters=adapters, processor=processor, grammar=grammar, window=window)
+                         adapters=adapters, processor=processor, grammar=grammar, window=window, softcap=softcap, sinks=sinks,
+                         attn_scale=attn_scale)
         dev = embed.device
         self._row_id = torch.arange(self.rows, dtype=torch.int32, device=dev)
         self._no_adapter = torch.full((self.rows,), -1, dtype=torch.int32, device=dev)
@@ -717,7 +764,7 @@ class RaggedStep(_Rows):
         else:
             attend, cache = paged_ragged_prefill_attention, (kc, vc, self.block_table)
         attend(q, k, v, *cache, self.seq, self.row0, self.pos0, self.inv_freq, scale=self.attn_scale, out=out, ws=self.attn_ws,
-               window=self.window[i])
+               **self._score(i))
 
     def _map_rows(self, seq, row0):
         """with a bank: self.row_adapter[r] = the adapter of the slot whose segment holds row r, -1 for rows of no segment or of a
@@ -845,10 +892,11 @@ class SpeculativeStep(RaggedStep):
     decoding would have had: the stream is the sequential one.  `begin` puts the slot's state at the start; `release` leaves it
     alone.  Give `begin` the table's eos as `eos`, so that the slot stops where its text ends.
 
-    window: as for RaggedStep; the stream is then token for token the windowed DecodeStep's."""
+    window, softcap, sinks, attn_scale: as for RaggedStep; the stream is then token for token that DecodeStep's."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, draft=4, gram=(2, 4), rows=None, sampler=None,
-                 block_table=None, history=None, adapters=None, processor=None, grammar=None, window=None):
+                 block_table=None, history=None, adapters=None, processor=None, grammar=None, window=None, softcap=None, sinks=None,
+                 attn_scale=None):
         B, K = self._check_table("SpeculativeStep", kcache, block_table), int(draft)
         if not 0 <= K <= 15 or len(gram) != 2 or not 1 <= int(gram[0]) <= int(gram[1]) <= 8:
             raise nat.QpalError(f"SpeculativeStep: draft must be in 0 .. 15 and 1 <= gram[0] <= gram[1] <= 8, got {draft}, {gram}")
@@ -857,7 +905,8 @@ class SpeculativeStep(RaggedStep):
             raise nat.QpalError(f"SpeculativeStep: rows must be in B = {B} .. 128, got {rows}")
         self.draft_len, self.gram = K, (int(gram[0]), int(gram[1]))
         super().__init__(layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=rows, segments=B, sampler=sampler,
-                         block_table=block_table, adapters=adapters, processor=processor, grammar=grammar, window=window)
+                         block_table=block_table, adapters=adapters, processor=processor, grammar=grammar, window=window,
+                         softcap=softcap, sinks=sinks, attn_scale=attn_scale)
         dev = embed.device
         self._row_state = None if grammar is None else torch.full((rows,), -1, dtype=torch.int32, device=dev)
         self.history = self.context if history is None else int(history)
