@@ -755,6 +755,84 @@ int qpal_grammar_advance(const unsigned short *trans, const unsigned char *accep
                          const int *tok_off, const unsigned char *tok_bytes, int vocab, int total_bytes, int eos, const int *gram,
                          int *state, int slots, const long *tokens, int width, const int *n, const long *active, void *stream);
 
+/* STOP CONDITIONS (csrc/stop.hip): stop strings, stop token ids, token budgets and the context limit of every slot,
+ * judged on the device by one launch at the end of a step.  A STOP SET of S states (1 .. 65535; state 0 is the start) is the
+ * byte-level Aho-Corasick automaton of 1 .. 64 byte strings in dense form, failure links resolved:
+ *   trans uint16 [S][256]      the state byte c leads to from state s; a value >= S is read as 0
+ *   out_len uint16 [S]         the length of the LONGEST string that ends at state s (suffix links closed), 0: none
+ * The vocabulary is the grammar block's: tok_off int32 [vocab + 1], tok_bytes uint8 [total_bytes]; a token outside [0, vocab), or
+ * whose offsets do not lie in 0 <= tok_off[t] <= tok_off[t + 1] <= total_bytes, has no bytes.
+ * A bank (qpal_stop_bank, a HOST struct read before the call returns; every pointer is device memory the host never reads):
+ *   trans uint16 [sets][max_states][256], out_len uint16 [sets][max_states], n_states int32 [sets]       sets 1 .. 256
+ *   set_id int32 [slots]       the slot's stop set; it HAS one when set_id lies in [0, sets) and n_states[set_id] in [1, max_states]
+ *   ac_state int32 [slots]     the automaton state; a value outside [0, S) is read as 0
+ *   stop_ids int32 [slots][id_slots], n_ids int32 [slots]     the first n_ids (clamped to 0 .. id_slots; id_slots 1 .. 16) are the ids
+ *   max_tokens int32 [slots]   0: no bound          min_tokens int32 [slots]
+ *   n_gen int32 [slots]        tokens generated     gen_bytes int64 [slots]      bytes generated
+ *   out int64 [slots][cap]     the generated tokens (cap >= 1); a token past cap is counted, not recorded
+ *   reason int32 [slots]       0 running, 1 stop id, 2 stop string, 3 max_tokens, 4 context
+ *   text_len int64 [slots]     the bytes of the generated text that belong to the answer
+ *   hit int32 [slots]          the automaton state at the match (reason 2)
+ *   end_pos int64 [slots]      the position the slot had reached when it finished
+ *
+ * JUDGING one generated token t of slot b whose next position (the one t would be fed at) is q:
+ *  1. n_gen += 1; out[b][n_gen - 1] = t if n_gen <= cap.
+ *  2. exempt = n_gen < min_tokens.
+ *  3. Not exempt and t equals one of the slot's stop ids: reason 1, text_len = gen_bytes; t's bytes are not walked.
+ *  4. Else t's bytes are walked through trans from ac_state, gen_bytes += 1 per byte (a slot without a set: gen_bytes += the number
+ *     of bytes, no walk, ac_state untouched).  At the FIRST byte whose new state s has out_len[s] > 0, in a token that is not exempt:
+ *     reason 2, text_len = gen_bytes - out_len[s], hit = s, the rest of the token is not walked.  ac_state = the last state reached.
+ *  5. Still running, max_tokens > 0 and n_gen >= max_tokens: reason 3, text_len = gen_bytes.
+ *  6. Still running and q >= max_len: reason 4, text_len = gen_bytes.
+ * A slot that finishes gets reason[b] and end_pos[b] = q; reason, text_len, hit and end_pos are written then and only then.
+ *
+ * qpal_stop_advance, 1 <= slots <= 128, max_len >= 1 (cache positions), tokens int64 [slots][width]:
+ *   DECODE mode (n_out == NULL, width == 1, tok / pos int64 [slots]): slot b is judged iff 0 <= pos[b] < max_len, with q = pos[b] + 1.
+ *     Finished: pos[b] = -1 (tok[b] keeps its value).  Goes on: tok[b] = tokens[b], pos[b] += 1.  A skipped slot keeps every word.
+ *   SPECULATIVE mode (n_out int32 [slots] read and written; n_tok / limit int64 [slots]: qpal_spec_accept's, as the accept left
+ *     them; 1 <= width <= 16): with m = n_out[b] clamped to 0 .. width, tokens[b][0 .. m) are judged in order, token j with q =
+ *     n_tok[b] - m + j.  At the first j that finishes the slot: n_out[b] = j + 1, n_tok[b] = n_tok[b] - m + j + 1, limit[b] =
+ *     n_tok[b] (the slot is inactive from then on).  m == 0: the slot is skipped.  tok / pos are ignored.
+ * One wave per slot: the wave fetches the tokens, their offsets and bytes and the stop ids, one lane walks.  No workspace, no
+ * atomics, one writer per word: two launches on equal state leave equal bits, equal to stop.reference_stop_advance.
+ *
+ * qpal_stop_mask: in place on logits fp32 [rows][ld_logits] (1 <= rows <= 128, ld_logits >= vocab), the min_tokens mask in front of
+ * the draw.  Row r with b = row_slot[r] is the j-th row of its slot's segment, j = r - row0[b] (row0 int32 [slots + 1]:
+ * qpal_spec_draft's) or j = 0 with row0 == NULL (a decode step).  It is SKIPPED when ctr[r] < 0 (int64 [rows]), b is outside
+ * [0, slots), or (row0 != NULL) row0[b] < 0 or j outside 0 .. 15.  Else, while n_gen[b] + j < min_tokens[b], l[id] = -inf for each of
+ * the slot's stop ids in [0, vocab); nothing else is written and the logits are not read.  One workgroup.
+ *
+ * Both read their state on the device, never synchronise: capturable.  Codes, all decided on the host before any stream work: a
+ * null pointer (the bank's fields included; row0 may be NULL; of n_out / n_tok / limit and tok / pos the mode's own must be there)
+ * QPAL_E_NULL; slots, rows, width, sets, max_states, id_slots, cap, vocab, total_bytes, max_len or a stride outside the ranges above
+ * QPAL_E_SHAPE; decode mode with width != 1 QPAL_E_PARAM; uint16 arrays 2-byte, fp32 / int32 arrays 4-byte, int64 arrays 8-byte
+ * aligned, else QPAL_E_ALIGN. */
+typedef struct qpal_stop_bank {
+    const unsigned short *trans;
+    const unsigned short *out_len;
+    const int *n_states;
+    const int *set_id;
+    int *ac_state;
+    const int *stop_ids;
+    const int *n_ids;
+    const int *max_tokens;
+    const int *min_tokens;
+    int *n_gen;
+    long *gen_bytes;
+    long *out;
+    int *reason;
+    long *text_len;
+    int *hit;
+    long *end_pos;
+    int sets, max_states, id_slots, cap;
+} qpal_stop_bank;
+int qpal_stop_advance(const qpal_stop_bank *bank, const int *tok_off, const unsigned char *tok_bytes, int vocab, int total_bytes,
+                      int slots, const long *tokens, int width, int *n_out, long *n_tok, long *limit, long *tok, long *pos,
+                      long max_len, void *stream);
+int qpal_stop_mask(float *logits_f32, long ld_logits, int rows, int vocab, const int *row_slot, const long *ctr, const int *row0,
+                   const int *stop_ids, int id_slots, const int *n_ids, const int *min_tokens, const int *n_gen, int slots,
+                   void *stream);
+
 /* PROXY HESSIAN of a linear layer's inputs (csrc/hessian.hip):  H += X^T X  and  colsum += 1^T X  in one launch.
  *   X       fp16 [rows, n] row-major, row stride ld_x >= n elements (a column slice of a wider buffer is passed as it lies);
  *           base 16-byte aligned, ld_x a multiple of 8

@@ -28,6 +28,11 @@ next to the same step without one, in the same call.
 pattern on a synthetic vocabulary (perf/sampling_kernels.py's) — mask + advance, two more launches — next to the same step without
 one, in the same call.
 
+--stop (with --sample) also times each sampled step with a stop.StopBank: a stop set of eight strings, eos as the stop
+id and no budget in every slot, `qpal_stop_advance` as the step's last launch — the step then moves tok / pos itself, so its replays
+run with NOTHING between them — next to the same step followed by the `tok.copy_(out_tok); pos += 1` this driver issues between
+replays today, timed before and behind it in the same call.  Both figures and their difference go to profiles/stop.json.
+
 --kv fp8 keeps the caches as torch.float8_e4m3fn.  The torch-glue reference then keeps fp16 caches of its own that
 hold e4m3 values only: `BatchKV.update` stores a new row through the round trip clamp(-448, 448) -> float8_e4m3fn -> half and the
 step attends to the round-tripped cache, as the kernels do.  The check also reports how far the fp16-cache step lies from that
@@ -38,7 +43,7 @@ reference (what the format itself moves; not a gate).
 shared_prefix=...) —, the plain step again behind them, and how far the two steps' final hidden states lie apart.
 
     python perf/decode_llama_batch.py [--model 3_8b] [--batch 1 8 16 32 64] [--context 1024] [--tokens 64] [--inactive 0] [--sample]
-                                      [--process] [--grammar] [--kv fp16|fp8] [--paged PAGE_SIZE] [--shared-prefix P] [--window W]
+                                      [--process] [--grammar] [--stop] [--kv fp16|fp8] [--paged PAGE_SIZE] [--shared-prefix P] [--window W]
                                       [--softcap CAP] [--sinks]
 """
 import argparse
@@ -98,6 +103,8 @@ def main(argv=None, quiet=False):
     ap.add_argument("--sample", action="store_true", help="also time the step with a sampler (0.6 / top-k 5 and 0.8 / top-p 0.95)")
     ap.add_argument("--process", action="store_true", help="with --sample: also time the sampled step with a logit processor")
     ap.add_argument("--grammar", action="store_true", help="with --sample: also time the sampled step with a grammar in every slot")
+    ap.add_argument("--stop", action="store_true",
+                    help="with --sample: also time the sampled step with a stop bank that ends it, against the step + the host's feed")
     ap.add_argument("--kv", default="fp16", choices=["fp16", "fp8"], help="KV-cache element format (fp8: OCP e4m3fn, no scales)")
     ap.add_argument("--paged", type=int, default=0, metavar="PAGE_SIZE",
                     help="also time the step on a paged cache of this page size (pages in a seeded random order; DESIGN.md §17)")
@@ -117,6 +124,8 @@ def main(argv=None, quiet=False):
         raise SystemExit("needs a GPU")
     if args.grammar and not args.sample:
         raise SystemExit("--grammar: the grammar masks a sampler's logits, add --sample")
+    if args.stop and not args.sample:
+        raise SystemExit("--stop: timed next to the sampled step, add --sample")
     if args.process and not args.sample:
         raise SystemExit("--process: the processor works on a sampler's logits, add --sample")
     if args.context % 4 or args.context < args.tokens + 16:
@@ -329,6 +338,29 @@ def main(argv=None, quiet=False):
                                         "grammar_launches_per_token": [sstep.launches_per_token, gstep.launches_per_token],
                                         "grammar_slots_alive_at_the_end": int((bank.state >= 0).sum())})
                     del gstep, bank
+                if args.stop:
+                    # strings over the vocabulary's bytes that end in a byte no token has: every token is walked, none matches
+                    from sampling_kernels import synthetic_table
+                    bank = qp.StopBank(B, synthetic_table(args.vocab), dev, sets=1, max_states=64, cap=512)
+                    bank.load(0, [b"ab01\n", b"12.-\n", b"xx  \n", b"0.5 \n", b"a-b \n\n", b"\n\n", b"</answer>", b"###"])
+                    for b in range(B):
+                        bank.set(b, stop=0)
+                        bank.reset(b)
+                    tstep = qp.DecodeStep(layers, embed, norm, lm_head, kc, vc, inv_freq, tok, pos, out_tok, generic=True, sampler=smp,
+                                          stop=bank)
+
+                    def rewind(i):
+                        """the step feeds itself: only the first replay is told where to start (the eager run and the capture moved on)"""
+                        if i == 0:
+                            pos.copy_(pos0)
+
+                    ms_t, ms_again = timed(tstep, rewind), timed(sstep)
+                    sampled[-1].update({"ms_step_stop": ms_t, "ms_step_again_behind_stop": ms_again,
+                                        "ms_stop_minus_plain_with_host_feed": ms_t - 0.5 * (ms + ms_again),
+                                        "stop_launches_per_token": [sstep.launches_per_token, tstep.launches_per_token],
+                                        "stop_slots_running_at_the_end": int((bank.reason == 0).sum()),
+                                        "stop_tokens_judged_per_slot": bank.n_gen.tolist()})
+                    del tstep, bank
                 del sstep, smp
         res = {"batch": B, "active": nact, "ms_step": ms_step, "tokens_per_s": nact / ms_step * 1e3,
                "ms_linears_only": ms_lin, "ms_torch_glue": ms_torch,
@@ -353,6 +385,14 @@ def main(argv=None, quiet=False):
     out = {"what": "decode step at batch B: quantized projections + batched attention (one launch per layer) + rotations",
            "model": args.model, "layers": nlayers, "quantizer": args.qdict or args.quantizer, "context": args.context,
            "tokens": args.tokens, "inactive": args.inactive, "batches": results}
+    if args.stop:
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        with open(os.path.join(root, "profiles", "stop.json"), "w") as f:
+            json.dump({"what": "DecodeStep(stop=bank), whose last launch judges the token and moves tok / pos, against the same sampled "
+                               "step followed by the host's tok.copy_(out_tok); pos += 1 (DESIGN.md §33), one MI355X, one call",
+                       "command": "python perf/decode_llama_batch.py " + " ".join(sys.argv[1:] if argv is None else argv),
+                       "result": out}, f, indent=1)
+            f.write("\n")
     if not quiet:
         print(json.dumps(out))
     return out

@@ -40,6 +40,10 @@ Layout:
                    GrammarBank (the automata, their per-state token bitmasks and the slots' states on the device), grammar_rows /
                    grammar_mask / grammar_advance (csrc/grammar.hip) and the contracts reference_allow / _step / _rows / _mask /
                    _advance (numpy, bit for bit)
+  stop.py          stop conditions on the device: compile_stops (byte strings -> a dense byte-level Aho-Corasick automaton), StopBank
+                   (the stop sets and per slot the stop ids, budgets, automaton state and generation record), stop_advance /
+                   stop_mask (csrc/stop.hip: the launch that ends a step and the min_tokens mask) and the contracts
+                   reference_stop_advance / reference_stop_mask (numpy, bit for bit)
   packers.py       pack_trellis / pack_qweight / pack_qweight_{sq,vq}_simt on the C-ABI's host-side encoders
   quantize.py      TCQ quantiser: tail-biting Viterbi encoder (csrc/tcq_viterbi.hip) + LDLQ -> QTIPLinearTCQ
                    VQ / SQ quantiser: nearest-codeword LDLQ encoder (csrc/vq_encode.hip) -> VQLinearPack{TensorCore,SIMT}
@@ -92,6 +96,8 @@ from . import logits  # noqa: F401
 from .logits import LogitProcessor, reference_process  # noqa: F401
 from . import grammar  # noqa: F401
 from .grammar import ByteDFA, GrammarBank, TokenTable, compile_regex, grammar_advance, grammar_mask, grammar_rows  # noqa: F401
+from . import stop  # noqa: F401
+from .stop import StopBank, StopSet, compile_stops, reference_stop_advance, reference_stop_mask, stop_advance, stop_mask  # noqa: F401
 from . import decoder  # noqa: F401
 from .decoder import DecodeStep, Prefill, RaggedStep, Score, SpeculativeStep, perplexity  # noqa: F401
 from . import speculative  # noqa: F401

@@ -32,6 +32,13 @@ class LutJob(ctypes.Structure):
                 ("x_rms_eps", _F), ("x_rms_w", _P), ("accumulate", _I), ("act_out", _P), ("x_hadk", _P), ("x_K", _I), ("act_su", _P)]
 
 
+class StopBankStruct(ctypes.Structure):
+    """qpal_stop_bank (include/qpal.h)"""
+    _fields_ = [(n, _P) for n in ("trans", "out_len", "n_states", "set_id", "ac_state", "stop_ids", "n_ids", "max_tokens", "min_tokens",
+                                  "n_gen", "gen_bytes", "out", "reason", "text_len", "hit", "end_pos")] + [
+        (n, _I) for n in ("sets", "max_states", "id_slots", "cap")]
+
+
 PEER_WS_BYTES_PER_SLOT = 256
 IPC_HANDLE_BYTES = 64
 
@@ -111,6 +118,8 @@ _SIGNATURES = {
     "qpal_grammar_rows": [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P],
     "qpal_grammar_mask": [_P, ctypes.c_long, _I, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, ctypes.c_long, _P],
     "qpal_grammar_advance": [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P],
+    "qpal_stop_advance": [ctypes.POINTER(StopBankStruct), _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, ctypes.c_long, _P],
+    "qpal_stop_mask": [_P, ctypes.c_long, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P],
     "qpal_peer_gather": [_P, ctypes.c_long, _I, ctypes.POINTER(_P), ctypes.POINTER(_P), _I, _I, _P],
     "qpal_peer_alloc": [ctypes.POINTER(_P), ctypes.c_long, _I],
     "qpal_peer_free": [_P],

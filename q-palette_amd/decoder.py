@@ -70,6 +70,13 @@ drawn tokens advance that state (`qpal_grammar_advance`): two more launches, thr
 state their guessed tokens lead to (`qpal_grammar_rows`).  No host read in a step; bank.set / reset between replays of a captured
 step change the next draw.
 
+`DecodeStep` and `SpeculativeStep` take `stop=`, a stop.StopBank of the caches' slots: stop strings, stop token ids,
+max_tokens / min_tokens and the context limit are judged on the device by the step itself (`qpal_stop_advance`, one more launch).  A
+DecodeStep then moves tok / pos itself — `for _ in range(n): graph.replay()` generates with no host work — and a slot that is done
+gets pos = -1 and falls out of the replays that follow; a SpeculativeStep cuts its emitted run at the token that finishes the slot.
+With a bank built with min_tokens=True (needs a sampler) one more launch in front of the draw keeps the stop ids from being drawn
+before a slot's min_tokens (`qpal_stop_mask`).  bank.result(slot) reads the record after the run.
+
 All five take `window=`: None, an int W >= 1, or one entry (None or an int) per layer — sliding-window attention,
 the row at position p attends to positions max(0, p - W + 1) .. p in the layers that have a window (Mistral: every layer; Gemma-2,
 gpt-oss: every other one).  Each layer's attention launch passes its own value; nothing else in a step changes, the launch count
@@ -94,6 +101,7 @@ from . import _native as nat
 from . import hadamard as had
 from . import grammar as gram_mod
 from . import linear, logits, lora, ops, sampling
+from . import stop as stop_mod
 from .attention import _score_mods as _check_score_mods
 from .attention import _window as _check_one_window
 from .attention import (attention_workspace, decode_attention, paged_decode_attention, paged_prefill_attention,
@@ -145,14 +153,14 @@ class _Rows:
 
     def __init__(self, who, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows, sampler, block_table, slots=None,
                  logits_tail=False, native_argmax=False, adapters=None, processor=None, grammar=None, window=None, softcap=None,
-                 sinks=None, attn_scale=None):
+                 sinks=None, attn_scale=None, stop=None):
         """window: None, an int or one entry per layer — the sliding window of every layer's attention launch (self.window[i]);
         softcap: None, a float or one entry per layer (self.softcap[i]); sinks: None or fp32 [n_layers, nq] (layer i: row i);
         attn_scale: None (1 / sqrt(head_dim)) or the scale of every layer's scores;
         slots: the sequences of the caches where the caller fixes them (DecodeStep's B), else read off the caches or the table;
         logits_tail: the tail is qpal_lm_head_logits without a sampler too; native_argmax: `_argmax_tail` is the one-launch kernel;
         adapters: a lora.LoraBank of these layers and slots, or None; processor: a logits.LogitProcessor of these slots, or None;
-        grammar: a grammar.GrammarBank of these slots, or None"""
+        grammar: a grammar.GrammarBank of these slots, or None; stop: a stop.StopBank of these slots, or None"""
         self.block_table = block_table
         self.window = self._check_window(who, window, len(layers))
         self.softcap, self.sinks = self._check_score(who, softcap, sinks, layers, embed.device)
@@ -165,6 +173,7 @@ class _Rows:
             self._check_lm_head(who, embed, lm_head)
         self.processor = self._check_processor(who, processor, self.slots, embed, lm_head, sampler is not None or logits_tail)
         self.grammar = self._check_grammar(who, grammar, self.slots, embed, lm_head, sampler is not None)
+        self.stop = self._check_stop(who, stop, self.slots, embed, lm_head, sampler is not None)
         att, mlp = layers[0].self_attn, layers[0].mlp
         H, dev = att.hidden_size, embed.device
         self.layers, self.embed, self.norm, self.lm_head, self.inv_freq = layers, embed, norm, lm_head, inv_freq
@@ -276,6 +285,17 @@ class _Rows:
             raise nat.QpalError(f"{who}: grammar must be a GrammarBank of {B} slots of {lm_head.shape[0]} tokens on {embed.device}")
         return bank
 
+    @staticmethod
+    def _check_stop(who, bank, B, embed, lm_head, sampled):
+        if bank is None:
+            return None
+        if not isinstance(bank, stop_mod.StopBank) or bank.B != B or bank.vocab != lm_head.shape[0] or bank.device != embed.device:
+            raise nat.QpalError(f"{who}: stop must be a StopBank of {B} slots of {lm_head.shape[0]} tokens on {embed.device}")
+        if bank.min_tokens_mask and not sampled:
+            raise nat.QpalError(f"{who}: the min_tokens mask works on the logits of a sampler's tail: give the step a sampler "
+                                "(greedy: temperature 0) or build the bank without min_tokens=True")
+        return bank
+
     @property
     def launches_per_token(self):
         raise nat.QpalError(f"{self._launches_per} (9 per layer), not per token")
@@ -334,7 +354,8 @@ class _Rows:
         processor (row_slot: the rows' slots) two launches in between: the tokens `fed` to the rows are counted where given, and the
         logits are processed in place — the draw and the log-probabilities are those of the processed logits.  With a grammar two
         more: the mask of every row's automaton state behind the processor, and behind the draw the advance of the states by the
-        drawn tokens (gslot None: row = slot, all of them; an int: the one row is that slot's)"""
+        drawn tokens (gslot None: row = slot, all of them; an int: the one row is that slot's).  With a stop bank built with min_tokens
+        one more in front of the draw: the stop ids of the slots that are below their min_tokens become -inf"""
         sampling.lm_head_logits(h32, self.norm.weight, self.norm.eps, self.lm_head, out=smp.logits)
         if self.processor is not None:
             if fed is not None:
@@ -343,6 +364,8 @@ class _Rows:
         if self.grammar is not None:
             state = self.grammar.state if gslot is None else self.grammar.state[gslot:gslot + 1]
             gram_mod.grammar_mask(smp.logits, self.grammar, row_slot, ctr, row_state=state)
+        if self.stop is not None and self.stop.min_tokens_mask:
+            stop_mod.stop_mask(smp.logits, self.stop, row_slot, ctr)
         sampling.sample(smp.logits, smp, ctr, out=out_tok)
         if self.grammar is not None:
             gram_mod.grammar_advance(self.grammar, out_tok, active=ctr, slot0=gslot or 0)
@@ -398,12 +421,19 @@ class DecodeStep(_Rows):
     grammar: a grammar.GrammarBank of B slots (needs a sampler; greedy is temperature 0).  Behind the processor every active row of
     a slot with a grammar is masked with the tokens its automaton state allows (bank.state[b], read by the launch), and behind the
     draw out_tok[b] advances that state, with the positions as the active vector: two more launches.  sampler.logits and
-    sampler.logprob are then the MASKED logits and the log-probabilities under them.  The grammar sees generated tokens only."""
+    sampler.logprob are then the MASKED logits and the log-probabilities under them.  The grammar sees generated tokens only.
+    stop: a stop.StopBank of B slots.  The LAST launch of the step judges out_tok[b] of every slot with pos[b] inside
+    the cache against the slot's stop ids, stop strings, max_tokens and the context, records it in the bank, and moves the step's own
+    inputs: a slot that goes on gets tok[b] = out_tok[b], pos[b] += 1, a slot that is done pos[b] = -1 — it is inactive in every
+    launch of the replays that follow, and its cache rows past bank.end_pos[b] are never written.  It runs behind the draw, the
+    log-probability launches and the grammar's advance, which read pos as their active vector.  Works with the argmax tail and with
+    a sampler: one more launch.  A bank built with min_tokens=True (needs a sampler) adds the mask launch behind the processor and
+    the grammar mask, in front of the draw: two more."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok, generic=False,
                  swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True, sampler=None, block_table=None,
                  adapters=None, processor=None, grammar=None, shared_prefix=None, window=None, softcap=None, sinks=None,
-                 attn_scale=None):
+                 attn_scale=None, stop=None):
         B = tok.shape[0]
         if shared_prefix is not None and block_table is None:
             raise nat.QpalError("DecodeStep: shared_prefix needs a paged cache (block_table=cache.table)")
@@ -414,8 +444,10 @@ class DecodeStep(_Rows):
         self.batch1 = B == 1 and not generic
         super().__init__("DecodeStep", layers, embed, norm, lm_head, kcache, vcache, inv_freq, B, sampler, block_table, slots=B,
                          native_argmax=self.batch1 and native_lm_head and self._has_argmax_kernel(embed, lm_head), adapters=adapters,
-                         processor=processor, grammar=grammar, window=window, softcap=softcap, sinks=sinks, attn_scale=attn_scale)
-        self._row_slot = None if processor is None and grammar is None else torch.arange(B, dtype=torch.int32, device=embed.device)  # row = slot
+                         processor=processor, grammar=grammar, window=window, softcap=softcap, sinks=sinks, attn_scale=attn_scale,
+                         stop=stop)
+        masked = processor is not None or grammar is not None or (stop is not None and stop.min_tokens_mask)
+        self._row_slot = torch.arange(B, dtype=torch.int32, device=embed.device) if masked else None  # row = slot
         if adapters is not None:
             self.row_adapter, swiglu_epilogue = adapters.slot_adapter, False  # row = slot
         if self.batch1 and not fusable(layers):
@@ -458,7 +490,8 @@ class DecodeStep(_Rows):
         logprobs, + the top-N launch of a sampler with top_logprobs (the embedding row copy is a memcpy node); with adapters + 4
         per layer, one per projection group; with a
         processor + 2, observe and process; with a grammar + 2, mask and advance; with shared_prefix + 1 per layer, the prefix
-        phase in front of the attention launch"""
+        phase in front of the attention launch; with stop + 1, the stop launch that ends the step, + 2 with a bank built with
+        min_tokens=True, whose mask launch sits in front of the draw"""
         per_layer = (5 if self.ug_il and self.ug_il[0][2] else 6) if self.rot_in_gemv else 9
         per_layer += 1 if getattr(self, "shared_prefix", None) is not None else 0
         per_layer += 4 if getattr(self, "adapters", None) is not None else 0  # (arithmetic on the configuration: stand-ins may lack it)
@@ -466,6 +499,8 @@ class DecodeStep(_Rows):
         tail += 1 if getattr(self.sampler, "top_id", None) is not None else 0
         tail += 2 if getattr(self, "processor", None) is not None else 0
         tail += 2 if getattr(self, "grammar", None) is not None else 0
+        stop = getattr(self, "stop", None)
+        tail += 0 if stop is None else (2 if stop.min_tokens_mask else 1)
         return per_layer * len(self.layers) + tail
 
     def _gemv(self, proj, x, su, scale, rms=None, **kw):
@@ -517,6 +552,8 @@ class DecodeStep(_Rows):
             self._sample_tail(self.h32, self.sampler, self.pos, self.out_tok, row_slot=self._row_slot, fed=self.tok)
         else:
             self._argmax_tail(self.h32, self.out_tok)
+        if self.stop is not None:  # the last launch: everything in front of it has read pos as its active vector
+            stop_mod.stop_advance(self.stop, self.out_tok, self.context, tok=self.tok, pos=self.pos)
 
 
 class Prefill(_Rows):
@@ -721,14 +758,17 @@ class RaggedStep(_Rows):
 
     processor: not on a RaggedStep (QpalError): a prompt chunk's rows would have to be counted row by row; SpeculativeStep has one.
     grammar: not on a RaggedStep either (QpalError); DecodeStep, Prefill and SpeculativeStep take one.
+    stop: not on a RaggedStep (a prompt chunk generates nothing to judge); DecodeStep and SpeculativeStep take one.
     window: as for DecodeStep (ragged_prefill_attention's window=), per segment what Prefill does with it.
     softcap / sinks / attn_scale: as for DecodeStep."""
 
     _launches_per = "RaggedStep: launches are per step"
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=128, segments=16, sampler=None, block_table=None,
-                 adapters=None, processor=None, grammar=None, window=None, softcap=None, sinks=None, attn_scale=None):
+                 adapters=None, processor=None, grammar=None, window=None, softcap=None, sinks=None, attn_scale=None, stop=None):
         who = type(self).__name__
+        if stop is not None and not isinstance(self, SpeculativeStep):
+            raise nat.QpalError("RaggedStep: no stop bank on a ragged step (DecodeStep and SpeculativeStep take one)")
         if processor is not None and not isinstance(self, SpeculativeStep):
             raise nat.QpalError("RaggedStep: no processor on a ragged step (DecodeStep, Prefill and SpeculativeStep take one)")
         if grammar is not None and not isinstance(self, SpeculativeStep):
@@ -738,7 +778,7 @@ class RaggedStep(_Rows):
         self.rows, self.segments = int(rows), int(segments)
         super().__init__(who, layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.rows, sampler, block_table, logits_tail=True,
                          adapters=adapters, processor=processor, grammar=grammar, window=window, softcap=softcap, sinks=sinks,
-                         attn_scale=attn_scale)
+                         attn_scale=attn_scale, stop=stop)
         dev = embed.device
         self._row_id = torch.arange(self.rows, dtype=torch.int32, device=dev)
         self._no_adapter = torch.full((self.rows,), -1, dtype=torch.int32, device=dev)
@@ -892,11 +932,19 @@ class SpeculativeStep(RaggedStep):
     decoding would have had: the stream is the sequential one.  `begin` puts the slot's state at the start; `release` leaves it
     alone.  Give `begin` the table's eos as `eos`, so that the slot stops where its text ends.
 
+    stop: a stop.StopBank of the caches' slots.  Directly behind the accept the emitted run out_tok[b, :n_out[b]] is
+    judged token by token; at the first token that finishes the slot n_out, n_tok and limit are cut there (the slot has no rows from
+    then on), so the grammar's advance and the processor's observe see the cut run: one more launch.  The verdict depends on the
+    emitted bytes only, so stream, reason and text_len are those of DecodeStep(stop=).  `begin` resets the slot's record; the stop ids
+    live in the bank, so `begin`'s own eos can stay -1 (a slot that the accept's eos or limit ends first keeps reason 0).  A bank
+    built with min_tokens=True (needs a sampler) adds the mask launch in front of the draw: row j of a segment is masked as the
+    j-th token from now — the mask depends on the accepted prefix in front of the row only, the stream stays the sequential one.
+
     window, softcap, sinks, attn_scale: as for RaggedStep; the stream is then token for token that DecodeStep's."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, draft=4, gram=(2, 4), rows=None, sampler=None,
                  block_table=None, history=None, adapters=None, processor=None, grammar=None, window=None, softcap=None, sinks=None,
-                 attn_scale=None):
+                 attn_scale=None, stop=None):
         B, K = self._check_table("SpeculativeStep", kcache, block_table), int(draft)
         if not 0 <= K <= 15 or len(gram) != 2 or not 1 <= int(gram[0]) <= int(gram[1]) <= 8:
             raise nat.QpalError(f"SpeculativeStep: draft must be in 0 .. 15 and 1 <= gram[0] <= gram[1] <= 8, got {draft}, {gram}")
@@ -906,7 +954,7 @@ class SpeculativeStep(RaggedStep):
         self.draft_len, self.gram = K, (int(gram[0]), int(gram[1]))
         super().__init__(layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=rows, segments=B, sampler=sampler,
                          block_table=block_table, adapters=adapters, processor=processor, grammar=grammar, window=window,
-                         softcap=softcap, sinks=sinks, attn_scale=attn_scale)
+                         softcap=softcap, sinks=sinks, attn_scale=attn_scale, stop=stop)
         dev = embed.device
         self._row_state = None if grammar is None else torch.full((rows,), -1, dtype=torch.int32, device=dev)
         self.history = self.context if history is None else int(history)
@@ -966,6 +1014,8 @@ class SpeculativeStep(RaggedStep):
                 self.processor.count_tokens(slot, toks)
         if self.grammar is not None:
             self.grammar.reset(slot)
+        if self.stop is not None:
+            self.stop.reset(slot)
 
     def release(self, slot):
         """the slot has no sequence: no rows in the steps that follow"""
@@ -990,6 +1040,8 @@ class SpeculativeStep(RaggedStep):
             logits.process(self.draw.logits, self.processor, self.row_slot, self.row_ctr, tokens=self.tokens, row0=self.row0)
         if self.grammar is not None:
             gram_mod.grammar_mask(self.draw.logits, self.grammar, self.row_slot, self.row_ctr, row_state=self._row_state)
+        if self.stop is not None and self.stop.min_tokens_mask:
+            stop_mod.stop_mask(self.draw.logits, self.stop, self.row_slot, self.row_ctr, row0=self.row0)
         if self.sampler is not None:
             self._gather_draw(self.row_slot.to(torch.int64).clamp(min=0))
         sampling.sample(self.draw.logits, self.draw, self.row_ctr, out=self.drawn)
@@ -1005,6 +1057,8 @@ class SpeculativeStep(RaggedStep):
             torch.index_select(self.draw.top_logprob, 0, rows, out=self.out_top_logprob.view(-1, n))
         spec.spec_accept(self.tokens, self.drawn, self.seq, self.row0, self.hist, self.n_tok, self.limit, self.eos, self.out_tok,
                          self.n_out, self.n_acc)
+        if self.stop is not None:  # cuts n_out / n_tok / limit where a slot finishes inside its run: what follows sees the cut
+            stop_mod.stop_advance(self.stop, self.out_tok, self.context, n_out=self.n_out, n_tok=self.n_tok, limit=self.limit)
         if self.grammar is not None:
             gram_mod.grammar_advance(self.grammar, self.out_tok, n=self.n_out)
         if self.processor is not None:
