@@ -879,6 +879,36 @@ int qpal_lora_apply(float *out_f32, long ld_out, const void *in, int in_mode, fl
                     const void *B, const int *blk_off, const int *blk_m, int P, const int *row_adapter, int rows, int k, int R, int N,
                     void *stream);
 
+/* BLOCK GLUE of Qwen- and Gemma-shaped layers (csrc/block_glue.hip; blocks.py restates each rule in numpy float64).
+ * Four launches on fp32 rows that lie in memory between the existing launches of a step.  Each is ONE launch on `stream`, reads
+ * nothing on the host and never synchronises (capturable); rows == 0 is success with nothing launched; rows up to 65535.  Codes are
+ * decided before any stream work: a null pointer QPAL_E_NULL, a size outside the limits QPAL_E_SHAPE, a bad eps / cap / pairing or
+ * an overlap QPAL_E_PARAM, a misaligned pointer or stride QPAL_E_ALIGN.
+ *
+ * qpal_qkv_prep: in place on q [rows][nq * hd], k and v [rows][nkv * hd], fp32 views with ONE row stride ld (elements, >= nq * hd) —
+ *   the views every attention entry point takes, in whatever order they lie in the caller's buffer; 4-byte aligned, disjoint.
+ *   bias   fp32 [(nq + 2 nkv) hd] in q | k | v order, or NULL:  x += b  on q, k and v (one fp32 add: equal to the host's fp32 x + b)
+ *   q_norm_w, k_norm_w  fp32 [hd] each, both or neither (one alone: QPAL_E_PARAM).  BEHIND the bias every head of q and of k becomes
+ *          x * rsqrt(mean_hd(x^2) + eps) * w  in fp32 ((x * inv) * w, the sum of squares over the head's hd elements); v is not
+ *          normed; a head of zeros stays zero.  w is the EFFECTIVE weight (Gemma's 1 + w is the caller's).  eps <= 0, NaN or inf
+ *          with weights given: QPAL_E_PARAM
+ *   hd in {64, 128, 256}, nq and nkv 1 .. 1024, else QPAL_E_SHAPE.  Neither bias nor weights: success, nothing is launched.
+ *   Columns of the caller's buffer outside the three views are never read or written.
+ * qpal_norm_add:  h[r] += y[r] * rsqrt(mean_n(y[r]^2) + eps) * w  in fp32 ((y * inv) * w, then one add), the sandwich post-norm and
+ *   the residual add.  n a multiple of 4, 4 .. 16384; w fp32 [n], the effective weight; h, y, w 16-byte aligned, ld_h and ld_y
+ *   multiples of 4 and >= n; h must not overlap y (QPAL_E_PARAM); eps as above.
+ * qpal_glu_gelu_tanh:  act[r][j] = gelu_tanh(ug[r][inter + j]) * ug[r][j]  for j < inter — ug is the up | gate row pair —,
+ *   gelu_tanh(g) = 0.5 g (1 + tanh(0.7978845608 (g + 0.044715 g^3))), the tanh in the clamped exp / rcp form of the attention
+ *   soft cap (absolute error <= 4 * 2^-24).  inter a multiple of 4 up to 2^24, ld_act >= inter, ld_ug >= 2 inter; act and ug 16-byte
+ *   aligned, strides multiples of 4; act must not overlap ug.
+ * qpal_logit_cap:  l <- cap * tanh(l / cap)  in place on logits [rows][ld >= vocab] (columns past vocab are left alone), the same
+ *   tanh form: absolute error <= 5 * 2^-24 * cap + 2^-24 |result|.  cap <= 0, NaN or inf: QPAL_E_PARAM.  4-byte aligned. */
+int qpal_qkv_prep(float *q, float *k, float *v, long ld, int rows, int nq, int nkv, int hd, const float *bias, const float *q_norm_w,
+                  const float *k_norm_w, float eps, void *stream);
+int qpal_norm_add(float *h, long ld_h, const float *y, long ld_y, const float *w, float eps, int rows, int n, void *stream);
+int qpal_glu_gelu_tanh(float *act, long ld_act, const float *ug, long ld_ug, int rows, int inter, void *stream);
+int qpal_logit_cap(float *logits, long ld, int rows, int vocab, float cap, void *stream);
+
 /* The launch planner of the fused GEMV entry points, on its own (host code, no GPU call; what tests and tools inspect).
  * A launch of njobs jobs — rows[j] supertile rows (m / 32) of steps1[j] + steps2[j] steps (a step = 128 columns; steps2 = 0: one
  * stream) — is cut into workgroup-sized pieces: a GROUP of G = 1 << lg_g workgroups (`waves` = 16 or 8 waves each) owns rg

@@ -45,6 +45,11 @@ shared_prefix=...) —, the plain step again behind them, and h
     python perf/decode_llama_batch.py [--model 3_8b] [--batch 1 8 16 32 64] [--context 1024] [--tokens 64] [--inactive 0] [--sample]
                                       [--process] [--grammar] [--stop] [--kv fp16|fp8] [--paged PAGE_SIZE] [--shared-prefix P] [--window W]
                                       [--softcap CAP] [--sinks]
+                                      [--qkv-bias] [--qk-norm] [--geglu] [--post-norms] [--logit-cap CAP]
+
+--qkv-bias / --qk-norm / --geglu / --post-norms / --logit-cap time the step with each block variant of DESIGN.md §34 on the random
+model (random bias, norm weights 1 + 0.3 N(0, 1)), each on its own, all given ones together, and the plain step again: "blocks" in
+the result, with every step's launches_per_token.
 """
 import argparse
 import json
@@ -115,6 +120,14 @@ def main(argv=None, quiet=False):
     ap.add_argument("--softcap", type=float, default=None, metavar="CAP",
                     help="also time the step with this logit soft cap in every layer (DecodeStep(softcap=CAP), DESIGN.md §32)")
     ap.add_argument("--sinks", action="store_true", help="also time the step with per-head sinks in every layer (DecodeStep(sinks=...))")
+    # the block variants: each one given is timed on its own next to the plain step, then all given ones together
+    ap.add_argument("--qkv-bias", action="store_true", help="also time the step with a random q|k|v bias (DecodeStep(qkv_bias=...))")
+    ap.add_argument("--qk-norm", action="store_true", help="also time the step with per-head QK-norm (DecodeStep(qk_norm=...))")
+    ap.add_argument("--geglu", action="store_true", help="also time the step with mlp_act='gelu_tanh'")
+    ap.add_argument("--post-norms", action="store_true", help="also time the step with sandwich post-norms (DecodeStep(post_norms=...))")
+    ap.add_argument("--logit-cap", type=float, default=None, metavar="CAP",
+                    help="also time the step with this final-logit soft cap (DecodeStep(logit_cap=CAP); it launches behind a sampler's "
+                         "lm_head only: the step is timed with a greedy sampler, against the plain step with that sampler)")
     args = ap.parse_args(argv)
     kv8 = args.kv == "fp8"
     if args.shared_prefix and (not args.paged or args.shared_prefix % args.paged or args.shared_prefix < args.paged
@@ -256,6 +269,30 @@ def main(argv=None, quiet=False):
             sstep = qp.DecodeStep(layers, embed, norm, lm_head, kc, vc, inv_freq, tok, pos, out_tok, generic=True, softcap=args.softcap, sinks=sinks)
             scored = {"softcap": args.softcap, "sinks": bool(args.sinks), "ms_step": timed(sstep), "ms_step_plain_again": timed(kernel_step)}
             del sstep
+        blocks = None
+        bg = torch.Generator().manual_seed(11)
+        variants = {}
+        if args.qkv_bias:
+            variants["qkv_bias"] = dict(qkv_bias=torch.randn(nlayers, H + 2 * nkv * head_dim, generator=bg).to(dev))
+        if args.qk_norm:
+            variants["qk_norm"] = dict(qk_norm=(1e-6, (1.0 + 0.3 * torch.randn(nlayers, 2, head_dim, generator=bg)).to(dev)))
+        if args.geglu:
+            variants["geglu"] = dict(mlp_act="gelu_tanh")
+        if args.post_norms:
+            variants["post_norms"] = dict(post_norms=(1e-6, (1.0 + 0.3 * torch.randn(nlayers, 2, H, generator=bg)).to(dev)))
+        if args.logit_cap is not None:
+            variants["logit_cap"] = dict(logit_cap=args.logit_cap, sampler=qp.Sampler(B, args.vocab, dev, temperature=0.0))
+        if variants:
+            # the same caches, tokens and positions with each variant, then the plain step again (the spread)
+            def variant_step(kw):
+                st = qp.DecodeStep(layers, embed, norm, lm_head, kc, vc, inv_freq, tok, pos, out_tok, generic=True, **kw)
+                return {"ms_step": timed(st), "launches_per_token": st.launches_per_token}
+            blocks = {name: variant_step(kw) for name, kw in variants.items()}
+            if "logit_cap" in variants:
+                blocks["sampler_alone"] = variant_step(dict(sampler=variants["logit_cap"]["sampler"]))
+            if len(variants) > 1:
+                blocks["all"] = variant_step({k: v for kw in variants.values() for k, v in kw.items()})
+            blocks["plain_again"] = {"ms_step": timed(kernel_step), "launches_per_token": kernel_step.launches_per_token}
         shared = None
         if args.shared_prefix:
             P, ps, mp = args.shared_prefix, args.paged, args.context // args.paged
@@ -375,6 +412,8 @@ def main(argv=None, quiet=False):
             res["window"] = windowed
         if scored is not None:
             res["score_mods"] = scored
+        if blocks is not None:
+            res["blocks"] = blocks
         if shared is not None:
             res["shared_prefix"] = shared
         del kc, vc, kc_ref, vc_ref, ref_cache, kernel_step
@@ -390,6 +429,14 @@ def main(argv=None, quiet=False):
         with open(os.path.join(root, "profiles", "stop.json"), "w") as f:
             json.dump({"what": "DecodeStep(stop=bank), whose last launch judges the token and moves tok / pos, against the same sampled "
                                "step followed by the host's tok.copy_(out_tok); pos += 1 (DESIGN.md §33), one MI355X, one call",
+                       "command": "python perf/decode_llama_batch.py " + " ".join(sys.argv[1:] if argv is None else argv),
+                       "result": out}, f, indent=1)
+            f.write("\n")
+    if args.qkv_bias or args.qk_norm or args.geglu or args.post_norms or args.logit_cap is not None:
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        with open(os.path.join(root, "profiles", "blocks.json"), "w") as f:
+            json.dump({"what": "DecodeStep with the block variants of DESIGN.md §34, each on its own, all together, and the plain step "
+                               "again, one MI355X, one call",
                        "command": "python perf/decode_llama_batch.py " + " ".join(sys.argv[1:] if argv is None else argv),
                        "result": out}, f, indent=1)
             f.write("\n")

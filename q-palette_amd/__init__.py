@@ -44,6 +44,10 @@ Layout:
                    (the stop sets and per slot the stop ids, budgets, automaton state and generation record), stop_advance /
                    stop_mask (csrc/stop.hip: the launch that ends a step and the min_tokens mask) and the contracts
                    reference_stop_advance / reference_stop_mask (numpy, bit for bit)
+  blocks.py        the glue of Qwen- and Gemma-shaped blocks (csrc/block_glue.hip): qkv_prep (q | k | v bias and per-head QK-norm in
+                   front of every attention launch), norm_add (sandwich post-norm + residual add), glu_gelu_tanh (GeGLU), logit_cap
+                   (final-logit soft cap) and their float64 contracts reference_*; the step classes take them as qkv_bias= /
+                   qk_norm= / post_norms= / mlp_act= / logit_cap=
   packers.py       pack_trellis / pack_qweight / pack_qweight_{sq,vq}_simt on the C-ABI's host-side encoders
   quantize.py      TCQ quantiser: tail-biting Viterbi encoder (csrc/tcq_viterbi.hip) + LDLQ -> QTIPLinearTCQ
                    VQ / SQ quantiser: nearest-codeword LDLQ encoder (csrc/vq_encode.hip) -> VQLinearPack{TensorCore,SIMT}
@@ -98,6 +102,7 @@ from . import grammar  # noqa: F401
 from .grammar import ByteDFA, GrammarBank, TokenTable, compile_regex, grammar_advance, grammar_mask, grammar_rows  # noqa: F401
 from . import stop  # noqa: F401
 from .stop import StopBank, StopSet, compile_stops, reference_stop_advance, reference_stop_mask, stop_advance, stop_mask  # noqa: F401
+from . import blocks  # noqa: F401
 from . import decoder  # noqa: F401
 from .decoder import DecodeStep, Prefill, RaggedStep, Score, SpeculativeStep, perplexity  # noqa: F401
 from . import speculative  # noqa: F401

@@ -133,6 +133,10 @@ _SIGNATURES = {
     "qpal_vq_encode": [_P, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P],
     "qpal_hessian_accum": [_P, _P, _P, ctypes.c_long, _I, _I, _P],
     "qpal_lora_apply": [_P, ctypes.c_long, _P, _I, _F, _P, _P, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, _P, _I, _I, _I, _I, _P],
+    "qpal_qkv_prep": [_P, _P, _P, ctypes.c_long, _I, _I, _I, _I, _P, _P, _P, _F, _P],
+    "qpal_norm_add": [_P, ctypes.c_long, _P, ctypes.c_long, _P, _F, _I, _I, _P],
+    "qpal_glu_gelu_tanh": [_P, ctypes.c_long, _P, ctypes.c_long, _I, _I, _P],
+    "qpal_logit_cap": [_P, ctypes.c_long, _I, _I, _F, _P],
 }
 
 HESSIAN_TILE = 128  # QPAL_HESSIAN_TILE

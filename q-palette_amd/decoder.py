@@ -92,6 +92,26 @@ denominator only (gpt-oss); the launches read it on the device, so a captured st
 attn_scale: None (1 / sqrt(head_dim)) or the factor on q.k (Gemma-2 27B's query_pre_attn_scalar).  Nothing else in a step changes, the
 launch count included; a batch-1 DecodeStep with a cap or sinks launches the batched attention at B = 1, and `shared_prefix=`
 together with either raises QpalError.
+
+All five take the block variants of Qwen2 / 2.5 / 3 and Gemma-2 / 3 shaped layers (blocks.py, csrc/block_glue.hip).  Every
+tensor is contiguous fp32 on the step's device, checked in the constructor, and layer i's launch gets the VIEW of row i: values
+written in place between replays of a captured step are followed.
+  qkv_bias: None or [n_layers, (nq + 2 nkv) hd], q | k | v order — added to the projections (Qwen2).
+  qk_norm: None or (eps, [n_layers, 2, hd]) — per-head RMSNorm of q (row 0) and k (row 1) behind the bias, in front of the rotary
+    embedding (Qwen3, Gemma-3).  The EFFECTIVE weight: a Gemma caller passes 1 + w.  One `qpal_qkv_prep` launch per layer serves both,
+    between the q|k|v launch (and its adapter's) and the attention launch, which itself is untouched.
+  mlp_act: "silu" or "gelu_tanh" (GeGLU) — `qpal_glu_gelu_tanh` writes gelu_tanh(gate) * up as fp32 rows, which the rotation in front
+    of down_proj and the adapter's "down" update read: one more launch per layer.
+  post_norms: None or (eps, [n_layers, 2, H]) — Gemma's sandwich norms: row 0 norms the attention sublayer's output, row 1 the MLP's
+    (effective weights again).  o_proj and down_proj (and their adapter updates) then write a scratch row instead of adding into the
+    stream, and `qpal_norm_add` folds RMSNorm(scratch) * w into it: two more launches per layer.  The modules'
+    `post_attention_layernorm` keeps its Llama meaning throughout, the norm in FRONT of the MLP — Gemma calls that one
+    `pre_feedforward_layernorm`; Gemma's own `post_attention_layernorm` is post_norms row 0, its `post_feedforward_layernorm` row 1.
+  logit_cap: None or a float > 0 — the final logits become cap * tanh(l / cap) (`qpal_logit_cap`), one launch directly behind the
+    lm_head of a sampler's tail, of Score and of SpeculativeStep, in front of the processor, grammar and stop masks; an argmax tail
+    needs none (the cap is monotone).
+  inv_freq may be fp32 [n_layers, hd / 2]: layer i rotates with row i (Gemma-3's local and global layers have different bases).
+With every one of them at its default a step launches exactly what it launched without them.
 """
 import math
 
@@ -100,7 +120,7 @@ import torch
 from . import _native as nat
 from . import hadamard as had
 from . import grammar as gram_mod
-from . import linear, logits, lora, ops, sampling
+from . import blocks, linear, logits, lora, ops, sampling
 from . import stop as stop_mod
 from .attention import _score_mods as _check_score_mods
 from .attention import _window as _check_one_window
@@ -153,8 +173,10 @@ class _Rows:
 
     def __init__(self, who, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows, sampler, block_table, slots=None,
                  logits_tail=False, native_argmax=False, adapters=None, processor=None, grammar=None, window=None, softcap=None,
-                 sinks=None, attn_scale=None, stop=None):
-        """window: None, an int or one entry per layer — the sliding window of every layer's attention launch (self.window[i]);
+                 sinks=None, attn_scale=None, stop=None,
+                 qkv_bias=None, qk_norm=None, mlp_act="silu", post_norms=None, logit_cap=None):
+        """qkv_bias, qk_norm, mlp_act, post_norms, logit_cap: the block variants (the module's last paragraph; `_check_block`);
+        window: None, an int or one entry per layer — the sliding window of every layer's attention launch (self.window[i]);
         softcap: None, a float or one entry per layer (self.softcap[i]); sinks: None or fp32 [n_layers, nq] (layer i: row i);
         attn_scale: None (1 / sqrt(head_dim)) or the scale of every layer's scores;
         slots: the sequences of the caches where the caller fixes them (DecodeStep's B), else read off the caches or the table;
@@ -174,6 +196,7 @@ class _Rows:
         self.processor = self._check_processor(who, processor, self.slots, embed, lm_head, sampler is not None or logits_tail)
         self.grammar = self._check_grammar(who, grammar, self.slots, embed, lm_head, sampler is not None)
         self.stop = self._check_stop(who, stop, self.slots, embed, lm_head, sampler is not None)
+        self._check_block(who, layers, embed.device, inv_freq, qkv_bias, qk_norm, mlp_act, post_norms, logit_cap)
         att, mlp = layers[0].self_attn, layers[0].mlp
         H, dev = att.hidden_size, embed.device
         self.layers, self.embed, self.norm, self.lm_head, self.inv_freq = layers, embed, norm, lm_head, inv_freq
@@ -192,6 +215,9 @@ class _Rows:
         self.a16 = torch.zeros(rows, H, dtype=torch.float16, device=dev)
         self.qkv32 = torch.zeros(rows, H + 2 * att.kv_out, dtype=torch.float32, device=dev)
         self.ug32 = torch.zeros(rows, 2 * mlp.intermediate_size, dtype=torch.float32, device=dev)
+        # a sublayer's output in front of its post-norm, and GeGLU's activation: only where a step has them
+        self.y32 = None if post_norms is None else torch.zeros(rows, H, dtype=torch.float32, device=dev)
+        self.act32 = None if not self.gelu else torch.zeros(rows, mlp.intermediate_size, dtype=torch.float32, device=dev)
         self.lm_ws = None
         if native_argmax:
             self.lm_ws_bytes = nat.lib().qpal_lm_head_ws_bytes(lm_head.shape[0])
@@ -225,6 +251,72 @@ class _Rows:
     def _score(self, i):
         """the window= / softcap= / sinks= of layer i's attention launch"""
         return {"window": self.window[i], "softcap": self.softcap[i], "sinks": None if self.sinks is None else self.sinks[i]}
+
+    def _check_block(self, who, layers, dev, inv_freq, qkv_bias, qk_norm, mlp_act, post_norms, logit_cap):
+        """the block variants of a step class: sets self.qkv_bias (None or fp32 [n_layers, (nq + 2 nkv) hd]),
+        self.qk_norm / self.post_norms (None or (eps, fp32 [n_layers, 2, hd | H])), self.gelu, self.logit_cap (None or a float) and
+        self.rope_per_layer (inv_freq is fp32 [n_layers, hd / 2]: layer i rotates with row i)"""
+        att = layers[0].self_attn
+        L, nq, nkv, hd, H = len(layers), att.num_heads, att.num_key_value_heads, att.head_dim, att.hidden_size
+
+        def rows(name, t, shape):
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != dev
+                    or not t.is_contiguous()):
+                raise nat.QpalError(f"{who}: {name} must be a contiguous float32 {list(shape)} tensor on {dev}")
+            return t
+
+        def normed(name, arg, width):
+            if arg is None:
+                return None
+            if not isinstance(arg, (tuple, list)) or len(arg) != 2:
+                raise nat.QpalError(f"{who}: {name} must be None or (eps, float32 [{L}, 2, {width}])")
+            eps, w = arg
+            if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not math.isfinite(eps) or eps <= 0:
+                raise nat.QpalError(f"{who}: {name}: eps must be a finite float > 0, got {eps!r}")
+            return float(eps), rows(name, w, (L, 2, width))
+
+        self.qkv_bias = None if qkv_bias is None else rows("qkv_bias", qkv_bias, (L, (nq + 2 * nkv) * hd))
+        self.qk_norm, self.post_norms = normed("qk_norm", qk_norm, hd), normed("post_norms", post_norms, H)
+        if (self.qkv_bias is not None or self.qk_norm is not None) and hd not in (64, 128, 256):
+            raise nat.QpalError(f"{who}: qkv_bias / qk_norm need a head_dim of 64, 128 or 256, got {hd}")
+        if self.post_norms is not None and (H % 4 or H > 16384):
+            raise nat.QpalError(f"{who}: post_norms need a hidden width that is a multiple of 4 up to 16384, got {H}")
+        if mlp_act not in ("silu", "gelu_tanh"):
+            raise nat.QpalError(f"{who}: mlp_act must be 'silu' or 'gelu_tanh', got {mlp_act!r}")
+        self.gelu = mlp_act == "gelu_tanh"
+        if self.gelu and layers[0].mlp.intermediate_size % 4:
+            raise nat.QpalError(f"{who}: mlp_act='gelu_tanh' needs an intermediate size that is a multiple of 4")
+        if logit_cap is not None and (isinstance(logit_cap, bool) or not isinstance(logit_cap, (int, float))
+                                      or not math.isfinite(logit_cap) or logit_cap <= 0):
+            raise nat.QpalError(f"{who}: logit_cap must be None or a finite float > 0, got {logit_cap!r}")
+        self.logit_cap = None if logit_cap is None else float(logit_cap)
+        self.rope_per_layer = isinstance(inv_freq, torch.Tensor) and inv_freq.dim() == 2
+        if self.rope_per_layer:
+            rows("a per-layer inv_freq", inv_freq, (L, hd // 2))
+
+    def _inv_freq(self, i):
+        """the rotary table of layer i's attention launch: the one table, or row i of a per-layer one (a view)"""
+        return self.inv_freq[i] if self.rope_per_layer else self.inv_freq
+
+    def _prep(self, i, q, k, v):
+        """bias and per-head QK-norm of layer i on the q | k | v rows, in place, in front of the attention launch (one launch)"""
+        if self.qkv_bias is None and self.qk_norm is None:
+            return
+        eps, w = (0.0, None) if self.qk_norm is None else self.qk_norm
+        blocks.qkv_prep(q, k, v, self.nq, self.nkv, self.head_dim, bias=None if self.qkv_bias is None else self.qkv_bias[i],
+                        q_norm_w=None if w is None else w[i, 0], k_norm_w=None if w is None else w[i, 1], eps=eps)
+
+    def _cap_logits(self, lg):
+        """the final-logit soft cap, directly behind the lm_head (one launch): in front of the processor, grammar and stop masks"""
+        if self.logit_cap is not None:
+            blocks.logit_cap(lg, self.logit_cap)
+
+    def _block_launches(self):
+        """(per layer, tail) launches the block variants add (arithmetic on the configuration: stand-ins may lack the attributes)"""
+        per_layer = 1 if getattr(self, "qkv_bias", None) is not None or getattr(self, "qk_norm", None) is not None else 0
+        per_layer += 2 if getattr(self, "post_norms", None) is not None else 0
+        per_layer += 1 if getattr(self, "gelu", False) else 0
+        return per_layer, 1 if getattr(self, "logit_cap", None) is not None and self.sampler is not None else 0
 
     @staticmethod
     def _check_table(who, kcache, block_table, B=None):
@@ -322,19 +414,39 @@ class _Rows:
         self._gemv(proj, h32, att.SU_qkv, att.scale, rms=rms, wscales=wsc, outs=list(qkv32.split([l.out_features for l in proj], dim=1)))
         self._lora(i, "qkv", h32, qkv32, had.IN_F32, rms)
         parts = dict(zip([b[0] for b in blocks], qkv32.split([b[1] for b in blocks], dim=1)))
+        self._prep(i, parts["q"], parts["k"], parts["v"])  # behind the adapter's update, as the modules add their bias and norm
         self._attention(i, parts["q"], parts["k"], parts["v"], a16)
-        self._gemv([att.o_proj], a16, att.SU_o, att.scale, wscales=[att.Wscale_o], outs=[h32], accumulate=True)
-        self._lora(i, "o", a16, h32, had.IN_F16)  # before up|gate reads the stream
+        y32 = self._sub_out(h32)
+        self._gemv([att.o_proj], a16, att.SU_o, att.scale, wscales=[att.Wscale_o], outs=[y32], accumulate=y32 is h32)
+        self._lora(i, "o", a16, y32, had.IN_F16)  # before up|gate reads the stream
+        self._post_norm(i, 0, h32, y32)
         self._mlp(i, h32, ug32)
+
+    def _sub_out(self, h32):
+        """where a sublayer's last projection writes: ADDED into the stream, or with post_norms overwritten into the rows of the
+        scratch that `_post_norm` then folds into the stream"""
+        return h32 if self.post_norms is None else self.y32[:h32.shape[0]]
+
+    def _post_norm(self, i, which, h32, y32):
+        """with post_norms: h32 += RMSNorm(y32) * w[i, which] (0: behind the attention sublayer and its adapter, 1: behind the MLP's)"""
+        if self.post_norms is not None:
+            eps, w = self.post_norms
+            blocks.norm_add(h32, y32, w[i, which], eps)
 
     def _mlp(self, i, h32, ug32):
         mlp, rms = self.layers[i].mlp, (self.eps, self.layers[i].post_attention_layernorm.weight)
         ugl, ugw = ug_layout(mlp)
         self._gemv(ugl, h32, mlp.SU_ug, mlp.scale, rms=rms, wscales=ugw, outs=list(ug32.split([l.out_features for l in ugl], dim=1)))
         self._lora(i, "ug", h32, ug32, had.IN_F32, rms)
-        x = had.rotate(ug32, in_mode=had.IN_SWIGLU_F32, hadK=mlp.had_left_dp_T, K=mlp.inter_K, su=mlp.SU_dp, post_scale=1.0 / mlp.scale)
-        multi_gemv([mlp.down_proj], x, outs=[h32], wscales=[mlp.Wscale_dp], oscale=mlp.scale, accumulate=True)
-        self._lora(i, "down", ug32, h32, had.IN_SWIGLU_F32)  # reads up | gate with their own update in
+        if self.gelu:  # GeGLU: the activation in fp32 rows of its own, which the rotation and the adapter read as they are
+            act, act_mode = blocks.glu_gelu_tanh(ug32, out=self.act32[:ug32.shape[0]]), had.IN_F32
+        else:
+            act, act_mode = ug32, had.IN_SWIGLU_F32
+        x = had.rotate(act, in_mode=act_mode, hadK=mlp.had_left_dp_T, K=mlp.inter_K, su=mlp.SU_dp, post_scale=1.0 / mlp.scale)
+        y32 = self._sub_out(h32)
+        multi_gemv([mlp.down_proj], x, outs=[y32], wscales=[mlp.Wscale_dp], oscale=mlp.scale, accumulate=y32 is h32)
+        self._lora(i, "down", act, y32, act_mode)  # reads up | gate with their own update in
+        self._post_norm(i, 1, h32, y32)
 
     def _run_layers(self, tokens, n=None):
         """the embedding rows of `tokens` through every layer, in the row buffers or (n: a short chunk) their first n rows; returns
@@ -357,6 +469,7 @@ class _Rows:
         drawn tokens (gslot None: row = slot, all of them; an int: the one row is that slot's).  With a stop bank built with min_tokens
         one more in front of the draw: the stop ids of the slots that are below their min_tokens become -inf"""
         sampling.lm_head_logits(h32, self.norm.weight, self.norm.eps, self.lm_head, out=smp.logits)
+        self._cap_logits(smp.logits)
         if self.processor is not None:
             if fed is not None:
                 logits.observe(self.processor, fed, row_slot, active=ctr)
@@ -376,6 +489,7 @@ class _Rows:
 
     def _argmax_tail(self, rows32, out_tok):
         """final norm + lm_head + argmax of the rows: one launch (ONE row) where the class found the kernel available, else torch ops"""
+        # (logit_cap needs nothing here: cap * tanh(l / cap) is monotone, the argmax of the capped logits is that of the plain ones)
         if self.lm_ws is None:
             out_tok.copy_((self.norm(rows32.half()) @ self.lm_head.T).argmax(-1))
             return
@@ -428,12 +542,20 @@ class DecodeStep(_Rows):
     launch of the replays that follow, and its cache rows past bank.end_pos[b] are never written.  It runs behind the draw, the
     log-probability launches and the grammar's advance, which read pos as their active vector.  Works with the argmax tail and with
     a sampler: one more launch.  A bank built with min_tokens=True (needs a sampler) adds the mask launch behind the processor and
-    the grammar mask, in front of the draw: two more."""
+    the grammar mask, in front of the draw: two more.
+    qkv_bias / qk_norm / mlp_act / post_norms / logit_cap, a per-layer inv_freq: the module's last paragraph.  At batch 1
+    mlp_act="gelu_tanh" switches the interleaved up|gate epilogue and down_proj's staged rotation off, the way adapters do (both are
+    built on silu(gate) * up in fp16); RMSNorm and the rotation stay inside the GEMV staging of q|k|v and up|gate, and qkv_prep works in
+    front of the fused single-sequence attention kernel as in front of every other.  layers[i].post_attention_layernorm is the norm
+    in FRONT of the MLP (Gemma: pre_feedforward_layernorm).
+    Gemma's embedding scale needs no argument: embed and lm_head are separate.  Gemma multiplies the embedding row by fp16(sqrt(H)) and
+    rounds to the activation dtype, so the caller passes embed = fp16(table * fp16(sqrt(H))) and lm_head = the unscaled table."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, tok, pos, out_tok, generic=False,
                  swiglu_epilogue=True, k28_fusion=True, native_lm_head=True, split_attention=True, sampler=None, block_table=None,
                  adapters=None, processor=None, grammar=None, shared_prefix=None, window=None, softcap=None, sinks=None,
-                 attn_scale=None, stop=None):
+                 attn_scale=None, stop=None,
+                 qkv_bias=None, qk_norm=None, mlp_act="silu", post_norms=None, logit_cap=None):
         B = tok.shape[0]
         if shared_prefix is not None and block_table is None:
             raise nat.QpalError("DecodeStep: shared_prefix needs a paged cache (block_table=cache.table)")
@@ -445,11 +567,14 @@ class DecodeStep(_Rows):
         super().__init__("DecodeStep", layers, embed, norm, lm_head, kcache, vcache, inv_freq, B, sampler, block_table, slots=B,
                          native_argmax=self.batch1 and native_lm_head and self._has_argmax_kernel(embed, lm_head), adapters=adapters,
                          processor=processor, grammar=grammar, window=window, softcap=softcap, sinks=sinks, attn_scale=attn_scale,
-                         stop=stop)
+                         stop=stop,
+                         qkv_bias=qkv_bias, qk_norm=qk_norm, mlp_act=mlp_act, post_norms=post_norms, logit_cap=logit_cap)
         masked = processor is not None or grammar is not None or (stop is not None and stop.min_tokens_mask)
         self._row_slot = torch.arange(B, dtype=torch.int32, device=embed.device) if masked else None  # row = slot
         if adapters is not None:
             self.row_adapter, swiglu_epilogue = adapters.slot_adapter, False  # row = slot
+        if self.gelu:
+            swiglu_epilogue = False  # the interleaved epilogue is silu(gate) * up: GeGLU runs the plain up|gate launch, as adapters do
         if self.batch1 and not fusable(layers):
             raise nat.QpalError("DecodeStep: these layers have no batch-1 step (fusable(layers))")
         self.tok, self.pos, self.out_tok = tok, pos, out_tok
@@ -491,8 +616,12 @@ class DecodeStep(_Rows):
         per layer, one per projection group; with a
         processor + 2, observe and process; with a grammar + 2, mask and advance; with shared_prefix + 1 per layer, the prefix
         phase in front of the attention launch; with stop + 1, the stop launch that ends the step, + 2 with a bank built with
-        min_tokens=True, whose mask launch sits in front of the draw"""
+        min_tokens=True, whose mask launch sits in front of the draw; with qkv_bias or qk_norm (one launch for both) + 1 per layer,
+        with post_norms + 2 per layer, with mlp_act="gelu_tanh" + 1 per layer (the activation; the rotation behind it is the SwiGLU
+        rotation's launch), with logit_cap + 1 behind a sampler's lm_head (an argmax tail needs none)"""
         per_layer = (5 if self.ug_il and self.ug_il[0][2] else 6) if self.rot_in_gemv else 9
+        block_layer, block_tail = _Rows._block_launches(self)
+        per_layer += block_layer
         per_layer += 1 if getattr(self, "shared_prefix", None) is not None else 0
         per_layer += 4 if getattr(self, "adapters", None) is not None else 0  # (arithmetic on the configuration: stand-ins may lack it)
         tail = 1 if self.sampler is None else (2 if self.sampler.logprob is None else 3)
@@ -501,7 +630,7 @@ class DecodeStep(_Rows):
         tail += 2 if getattr(self, "grammar", None) is not None else 0
         stop = getattr(self, "stop", None)
         tail += 0 if stop is None else (2 if stop.min_tokens_mask else 1)
-        return per_layer * len(self.layers) + tail
+        return per_layer * len(self.layers) + tail + block_tail
 
     def _gemv(self, proj, x, su, scale, rms=None, **kw):
         """batch 1, k in {2048, 4096}: RMSNorm + rotation inside the GEMV launch; else (70B: 8192, every batch > 1) the launch pair"""
@@ -515,18 +644,18 @@ class DecodeStep(_Rows):
             dev = out.device
             with torch.cuda.device(dev):
                 rc = nat.lib().qpal_attn_rope_decode(q.data_ptr(), k.data_ptr(), v.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
-                                                     self.pos.data_ptr(), self.inv_freq.data_ptr(), self.nq, self.nkv, self.head_dim,
+                                                     self.pos.data_ptr(), self._inv_freq(i).data_ptr(), self.nq, self.nkv, self.head_dim,
                                                      self.context, self.attn_scale, self.attn_ws.data_ptr() if self.attn_ws_bytes else None,
                                                      self.attn_ws_bytes, torch.cuda.current_stream(dev).cuda_stream)
             return nat.check(rc, "qpal_attn_rope_decode")
         if self.shared_prefix is not None:
-            return shared_prefix_decode_attention(q, k, v, kc, vc, self.block_table, self.pos, self.inv_freq, self.shared_prefix,
+            return shared_prefix_decode_attention(q, k, v, kc, vc, self.block_table, self.pos, self._inv_freq(i), self.shared_prefix,
                                                   scale=self.attn_scale, out=out, ws=self.attn_ws)
         if self.block_table is None:
             attend, cache = decode_attention, (kc, vc)
         else:
             attend, cache = paged_decode_attention, (kc, vc, self.block_table)
-        attend(q, k, v, *cache, self.pos, self.inv_freq, scale=self.attn_scale, out=out, ws=self.attn_ws, **self._score(i))
+        attend(q, k, v, *cache, self.pos, self._inv_freq(i), scale=self.attn_scale, out=out, ws=self.attn_ws, **self._score(i))
 
     def _mlp(self, i, h32, ug32):
         if not self.ug_il:
@@ -540,7 +669,9 @@ class DecodeStep(_Rows):
             x, x_rot = self.act16, (None, 1.0 / mlp.scale, mlp.had_left_dp_T, mlp.inter_K)
         else:
             x, x_rot = had.rotate(self.act16, hadK=mlp.had_left_dp_T, K=mlp.inter_K, su=mlp.SU_dp, post_scale=1.0 / mlp.scale), None
-        multi_gemv([mlp.down_proj], x, outs=[h32], wscales=[mlp.Wscale_dp], oscale=mlp.scale, x_rot=x_rot, accumulate=True)
+        y32 = self._sub_out(h32)
+        multi_gemv([mlp.down_proj], x, outs=[y32], wscales=[mlp.Wscale_dp], oscale=mlp.scale, x_rot=x_rot, accumulate=y32 is h32)
+        self._post_norm(i, 1, h32, y32)
 
     def hidden(self):
         """fp16 [B, H]: the final norm of the residual stream the last step left (a torch op: for checks, not part of the step)"""
@@ -594,14 +725,16 @@ class Prefill(_Rows):
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, native_lm_head=True, sampler=None,
                  block_table=None, adapters=None, processor=None, grammar=None, window=None, softcap=None, sinks=None,
-                 attn_scale=None):
+                 attn_scale=None,
+                 qkv_bias=None, qk_norm=None, mlp_act="silu", post_norms=None, logit_cap=None):
         if not 1 <= int(chunk) <= 128:
             raise nat.QpalError(f"Prefill: chunk must be in 1 .. 128, got {chunk}")
         self.chunk = int(chunk)
         dev, H = embed.device, embed.shape[1]
         super().__init__("Prefill", layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.chunk, sampler, block_table,
                          native_argmax=native_lm_head and self._has_argmax_kernel(embed, lm_head), adapters=adapters,
-                         processor=processor, grammar=grammar, window=window, softcap=softcap, sinks=sinks, attn_scale=attn_scale)
+                         processor=processor, grammar=grammar, window=window, softcap=softcap, sinks=sinks, attn_scale=attn_scale,
+                         qkv_bias=qkv_bias, qk_norm=qk_norm, mlp_act=mlp_act, post_norms=post_norms, logit_cap=logit_cap)
         self._row_slot = None if processor is None and grammar is None else torch.zeros(1, dtype=torch.int32, device=dev)  # the call's slot
         self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
         self.out_tok = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -616,7 +749,7 @@ class Prefill(_Rows):
             attend, cache = prefill_attention, (kc[self.slot], vc[self.slot])
         else:
             attend, cache = paged_prefill_attention, (kc, vc, self.block_table[self.slot])
-        attend(q, k, v, *cache, self.pos, self.inv_freq, scale=self.attn_scale, out=out, ws=self.attn_ws, **self._score(i))
+        attend(q, k, v, *cache, self.pos, self._inv_freq(i), scale=self.attn_scale, out=out, ws=self.attn_ws, **self._score(i))
 
     def hidden(self):
         """fp16 [1, H]: the final norm of the last prompt row"""
@@ -684,11 +817,13 @@ class Score(Prefill):
     window, softcap, sinks, attn_scale: as for Prefill — the log-probabilities are those of the model with that attention."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, max_tokens=None, block_table=None,
-                 adapters=None, top_logprobs=0, window=None, softcap=None, sinks=None, attn_scale=None):
+                 adapters=None, top_logprobs=0, window=None, softcap=None, sinks=None, attn_scale=None,
+                 qkv_bias=None, qk_norm=None, mlp_act="silu", post_norms=None, logit_cap=None):
         self._check_lm_head("Score", embed, lm_head)
         super().__init__(layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=chunk, native_lm_head=False,
                          block_table=block_table, adapters=adapters, window=window, softcap=softcap, sinks=sinks,
-                         attn_scale=attn_scale)
+                         attn_scale=attn_scale,
+                         qkv_bias=qkv_bias, qk_norm=qk_norm, mlp_act=mlp_act, post_norms=post_norms, logit_cap=logit_cap)
         self.max_tokens = self.context if max_tokens is None else int(max_tokens)
         if self.max_tokens < 2:
             raise nat.QpalError(f"Score: max_tokens must be at least 2, got {max_tokens}")
@@ -717,6 +852,7 @@ class Score(Prefill):
             n = h32.shape[0]
             self.logits = self._logits[:n]
             sampling.lm_head_logits(h32, self.norm.weight, self.norm.eps, self.lm_head, out=self.logits)
+            self._cap_logits(self.logits)
             sampling.token_logprobs(self.logits, self._targets[c:c + n], out=self._lp[c:c + n], rank=self._rank[c:c + n])
             if self.top_n:  # (the row without a target is inactive here as well)
                 sampling.top_logprobs(self.logits, self.top_n, ids=self._top_id[c:c + n], logprob=self._top_logprob[c:c + n],
@@ -765,7 +901,8 @@ class RaggedStep(_Rows):
     _launches_per = "RaggedStep: launches are per step"
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=128, segments=16, sampler=None, block_table=None,
-                 adapters=None, processor=None, grammar=None, window=None, softcap=None, sinks=None, attn_scale=None, stop=None):
+                 adapters=None, processor=None, grammar=None, window=None, softcap=None, sinks=None, attn_scale=None, stop=None,
+                 qkv_bias=None, qk_norm=None, mlp_act="silu", post_norms=None, logit_cap=None):
         who = type(self).__name__
         if stop is not None and not isinstance(self, SpeculativeStep):
             raise nat.QpalError("RaggedStep: no stop bank on a ragged step (DecodeStep and SpeculativeStep take one)")
@@ -778,7 +915,8 @@ class RaggedStep(_Rows):
         self.rows, self.segments = int(rows), int(segments)
         super().__init__(who, layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.rows, sampler, block_table, logits_tail=True,
                          adapters=adapters, processor=processor, grammar=grammar, window=window, softcap=softcap, sinks=sinks,
-                         attn_scale=attn_scale, stop=stop)
+                         attn_scale=attn_scale, stop=stop,
+                         qkv_bias=qkv_bias, qk_norm=qk_norm, mlp_act=mlp_act, post_norms=post_norms, logit_cap=logit_cap)
         dev = embed.device
         self._row_id = torch.arange(self.rows, dtype=torch.int32, device=dev)
         self._no_adapter = torch.full((self.rows,), -1, dtype=torch.int32, device=dev)
@@ -803,7 +941,7 @@ class RaggedStep(_Rows):
             attend, cache = ragged_prefill_attention, (kc, vc)
         else:
             attend, cache = paged_ragged_prefill_attention, (kc, vc, self.block_table)
-        attend(q, k, v, *cache, self.seq, self.row0, self.pos0, self.inv_freq, scale=self.attn_scale, out=out, ws=self.attn_ws,
+        attend(q, k, v, *cache, self.seq, self.row0, self.pos0, self._inv_freq(i), scale=self.attn_scale, out=out, ws=self.attn_ws,
                **self._score(i))
 
     def _map_rows(self, seq, row0):
@@ -944,7 +1082,8 @@ class SpeculativeStep(RaggedStep):
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, draft=4, gram=(2, 4), rows=None, sampler=None,
                  block_table=None, history=None, adapters=None, processor=None, grammar=None, window=None, softcap=None, sinks=None,
-                 attn_scale=None, stop=None):
+                 attn_scale=None, stop=None,
+                 qkv_bias=None, qk_norm=None, mlp_act="silu", post_norms=None, logit_cap=None):
         B, K = self._check_table("SpeculativeStep", kcache, block_table), int(draft)
         if not 0 <= K <= 15 or len(gram) != 2 or not 1 <= int(gram[0]) <= int(gram[1]) <= 8:
             raise nat.QpalError(f"SpeculativeStep: draft must be in 0 .. 15 and 1 <= gram[0] <= gram[1] <= 8, got {draft}, {gram}")
@@ -954,7 +1093,8 @@ class SpeculativeStep(RaggedStep):
         self.draft_len, self.gram = K, (int(gram[0]), int(gram[1]))
         super().__init__(layers, embed, norm, lm_head, kcache, vcache, inv_freq, rows=rows, segments=B, sampler=sampler,
                          block_table=block_table, adapters=adapters, processor=processor, grammar=grammar, window=window,
-                         softcap=softcap, sinks=sinks, attn_scale=attn_scale, stop=stop)
+                         softcap=softcap, sinks=sinks, attn_scale=attn_scale, stop=stop,
+                         qkv_bias=qkv_bias, qk_norm=qk_norm, mlp_act=mlp_act, post_norms=post_norms, logit_cap=logit_cap)
         dev = embed.device
         self._row_state = None if grammar is None else torch.full((rows,), -1, dtype=torch.int32, device=dev)
         self.history = self.context if history is None else int(history)
@@ -1036,6 +1176,7 @@ class SpeculativeStep(RaggedStep):
         self._map_rows(self.seq, self.row0)
         self._run_layers(tokens)
         sampling.lm_head_logits(self.h32, self.norm.weight, self.norm.eps, self.lm_head, out=self.draw.logits)
+        self._cap_logits(self.draw.logits)
         if self.processor is not None:
             logits.process(self.draw.logits, self.processor, self.row_slot, self.row_ctr, tokens=self.tokens, row0=self.row0)
         if self.grammar is not None:
