@@ -909,6 +909,57 @@ int qpal_norm_add(float *h, long ld_h, const float *y, long ld_y, const float *w
 int qpal_glu_gelu_tanh(float *act, long ld_act, const float *ug, long ld_ug, int rows, int inter, void *stream);
 int qpal_logit_cap(float *logits, long ld, int rows, int vocab, float cap, void *stream);
 
+/* MIXTURE-OF-EXPERTS layers (csrc/moe_route.hip, csrc/moe_gemv.hip; moe.py restates each rule in numpy float64).
+ * n <= 128 rows, E <= 256 experts, 1 <= top_k <= min(8, E): P = n * top_k routed pairs (r, j), pair id r * top_k + j.  Every entry
+ * point is ONE launch on `stream`, reads nothing on the host, uses no memory beyond its arguments and never synchronises
+ * (capturable).  Codes are decided before any stream work.
+ *
+ * qpal_moe_max_groups: the largest number of groups (below) any routing of the shape can give, exactly; 0 for a shape outside the
+ *   limits.  It sizes the group table and the grid of qpal_moe_gemv.  qpal_moe_route_ws_bytes: bytes of one buffer that holds the
+ *   ticket (first, 16 bytes) and every output of qpal_moe_route, as moe.moe_workspace lays them out.
+ * qpal_moe_route: per row  x = h * rsqrt(mean(h^2) + eps) * rms_w  (fp32; rms_w fp16 [H] or NULL),  logits = router_w x + bias
+ *   (router_w fp16 [E][H], 16-byte aligned; fp32 accumulation in ONE order for every expert: equal router rows give equal logits;
+ *   bias fp32 [E] or NULL),  p = softmax over all E.  The top_k largest logits are chosen, ties to the lower expert id;
+ *   sel [n][top_k] lists them in ascending expert id; gate [n][top_k] = p[sel], divided by their sum when renorm.  Rows with
+ *   active[r] < 0 (int64 [n]; NULL: all active) choose nothing: sel -1, gate 0.  The layout: the pairs with sel >= 0 sorted by
+ *   (expert, pair id) — order [P] the pair at each sorted position, inv [P] the position of each pair or -1, x_index [P] =
+ *   order / top_k, the source row (order and x_index: -1 behind the routed pairs) — and every expert's run cut into GROUPS of at
+ *   most 8 consecutive positions: group_expert, group_first, group_count [max_groups] in sorted order (-1, 0, 0 behind the last),
+ *   ngroups [1].  H a multiple of 8 up to 8192, ld_h >= H, max_groups >= qpal_moe_max_groups.  ticket: one zeroed 32-bit word
+ *   of device memory the launch leaves zero again (the last workgroup to arrive builds the layout).
+ * qpal_moe_gemv: for every group g < min(*ngroups, max_groups) with 0 <= group_expert[g] < E (others do no work), projection j < nproj
+ *   (1 or 2, one k) and row < proj[j].m:
+ *     out[group_first[g] + b][proj[j].out_col + row] = (W x[xi(g, b)])[row] * wscale[row] * oscale,   b < group_count[g] <= 8
+ *   with W the TCQ matrix of expert e = group_expert[g] — its stream(s) at ((const void *const *)proj[j].c1)[e] (and .c2 for a
+ *   column-split matrix: kv2 = kv + 1, columns [k / 2, k)), its fp16 Wscale [m] at .wscale[e] (table NULL: none) — and
+ *   xi(g, b) = x_index[group_first[g] + b], or the position itself when x_index is NULL; an index outside [0, x_rows) reads zeros.
+ *   x fp16 [x_rows][ldx], 8-byte aligned, ldx % 4 == 0; out fp32 [out_rows][ldo]; a group that reaches past out_rows does no work;
+ *   rows of `out` no group names are not written.  The tables are uint64 [E] in device memory.  S = 9 with kv (kv2) in 2 .. 8,
+ *   one codebook tlut [512][2] fp16 for the launch; any other codec: QPAL_E_PARAM.  m % 32, k % 32 (k % 64 when split), as
+ *   qpal_tcq_gemv.  fp32 accumulation whose order depends on the shapes alone: a row's result is bitwise independent of the rows
+ *   that share its group.
+ * qpal_moe_combine:  out[r][c] (+)= sum_j gate[r][j] * y[inv[r][j]][c],  j ascending, every product rounded to fp32, the sum built
+ *   in j order and then added (accumulate = 1) or stored (0: rows without pairs become zeros).  y fp32 [P][ld_y].                */
+typedef struct qpal_moe_proj {
+    const void *c1;      /* device table uint64 [E]: stream 1 of every expert                 */
+    const void *c2;      /* ... stream 2 (column-split matrices), or NULL                     */
+    const void *wscale;  /* ... fp16 [m] output-row scales, or NULL                           */
+    int m;               /* output rows of the projection                                     */
+    int kv, kv2;         /* trellis dwords per lane of stream 1 / stream 2 (0: single stream) */
+    int out_col;         /* first column of this projection inside a row of `out`             */
+} qpal_moe_proj;
+int qpal_moe_max_groups(int n, int E, int top_k);
+long qpal_moe_route_ws_bytes(int n, int E, int top_k);
+int qpal_moe_route(const float *h_f32, long ld_h, const void *rms_w_f16, float rms_eps, const void *router_w_f16,
+                   const float *router_bias, const long long *active, int n, int H, int E, int top_k, int renorm, int *sel,
+                   float *gate, int *order, int *inv, int *x_index, int *group_expert, int *group_first, int *group_count,
+                   int *ngroups, int max_groups, unsigned *ticket, void *stream);
+int qpal_moe_gemv(float *out, long ldo, int out_rows, const qpal_moe_proj *proj, int nproj, const void *x_f16, long ldx, int x_rows,
+                  const int *x_index, const int *group_expert, const int *group_first, const int *group_count, const int *ngroups,
+                  int max_groups, int E, int k, const void *tlut, int S, float oscale, void *stream);
+int qpal_moe_combine(float *out_f32, long ld_out, const float *y_f32, long ld_y, const float *gate, const int *inv, int n, int top_k,
+                     int H, int P, int accumulate, void *stream);
+
 /* The launch planner of the fused GEMV entry points, on its own (host code, no GPU call; what tests and tools inspect).
  * A launch of njobs jobs — rows[j] supertile rows (m / 32) of steps1[j] + steps2[j] steps (a step = 128 columns; steps2 = 0: one
  * stream) — is cut into workgroup-sized pieces: a GROUP of G = 1 << lg_g workgroups (`waves` = 16 or 8 waves each) owns rg

@@ -92,6 +92,34 @@ def e4m3_round_trip(x):
     return x.float().clamp(-448.0, 448.0).to(torch.float8_e4m3fn).half()
 
 
+def sparse_layers(layers, E, top_k, inter, qstr, dev, seed=5):
+    """the model's layers with every MLP replaced by a MoEMLP of E random experts of intermediate width `inter` (the attention
+    modules and norms are the dense model's own): random packed weights of quantizer `qstr`, one codebook, one SU per rotation"""
+    import math
+    H = layers[0].self_attn.hidden_size
+    g = torch.Generator().manual_seed(seed)
+
+    def wrapped(k, m, s, su):
+        il = qp.IncoherentLinear(k, m, k, m, use_linear=False)
+        il.linear = qp.make_linear_from_info(qstr, qp.mem_op.dummy_linear_info(k, m, qstr, seed=s, codebook_seed=777))
+        il.SU.data.copy_(su)
+        il.Wscale.data.fill_(1.0 / math.sqrt(k))
+        il.rot_info = "skip_r"
+        il.apply_rot_info()
+        return il.to(dev)
+
+    out = torch.nn.ModuleList()
+    for i, l in enumerate(layers):
+        su_h, su_i = ((torch.randint(0, 2, (n,), generator=g) * 2 - 1).half() for n in (H, inter))
+        experts = [(wrapped(H, inter, 3 * (i * E + e), su_h), wrapped(H, inter, 3 * (i * E + e) + 1, su_h),
+                    wrapped(inter, H, 3 * (i * E + e) + 2, su_i)) for e in range(E)]
+        layer = torch.nn.Module()
+        layer.self_attn, layer.input_layernorm, layer.post_attention_layernorm = l.self_attn, l.input_layernorm, l.post_attention_layernorm
+        layer.mlp = qp.MoEMLP.from_experts((torch.randn(E, H, generator=g) * 4 / math.sqrt(H)).half().to(dev), experts, top_k)
+        out.append(layer)
+    return out
+
+
 def main(argv=None, quiet=False):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="3_8b", choices=sorted(qp.mem_op.LAYER_INFO))
@@ -128,6 +156,9 @@ def main(argv=None, quiet=False):
     ap.add_argument("--logit-cap", type=float, default=None, metavar="CAP",
                     help="also time the step with this final-logit soft cap (DecodeStep(logit_cap=CAP); it launches behind a sampler's "
                          "lm_head only: the step is timed with a greedy sampler, against the plain step with that sampler)")
+    ap.add_argument("--moe", type=int, nargs=3, default=None, metavar=("E", "TOP_K", "I"),
+                    help="also time the step on the same model with every MLP a MoEMLP of E random experts of intermediate width I, "
+                         "TOP_K of them per token (DESIGN.md §35; --quantizer must be a tcq_* / tcomb_*_0.5 string with KV <= 8)")
     args = ap.parse_args(argv)
     kv8 = args.kv == "fp8"
     if args.shared_prefix and (not args.paged or args.shared_prefix % args.paged or args.shared_prefix < args.paged
@@ -149,6 +180,7 @@ def main(argv=None, quiet=False):
     m = build_model(args.model, args.quantizer, args.qdict, args.layers, args.vocab, dev)
     cfg, layers, embed, lm_head, norm, inv_freq = m.cfg, m.layers, m.embed, m.lm_head, m.norm, m.inv_freq
     H, I, nkv, head_dim, nlayers = cfg.hidden_size, cfg.intermediate_size, cfg.num_key_value_heads, cfg.head_dim, len(layers)
+    moe_layers = sparse_layers(layers, *args.moe, args.quantizer, dev) if args.moe else None
 
     def run_batch(B):
         nact = B - args.inactive
@@ -293,6 +325,13 @@ def main(argv=None, quiet=False):
             if len(variants) > 1:
                 blocks["all"] = variant_step({k: v for kw in variants.values() for k, v in kw.items()})
             blocks["plain_again"] = {"ms_step": timed(kernel_step), "launches_per_token": kernel_step.launches_per_token}
+        moe = None
+        if moe_layers is not None:  # the same attention, caches, tokens and positions with sparse MLPs, then the dense step again
+            mstep = qp.DecodeStep(moe_layers, embed, norm, lm_head, kc, vc, inv_freq, tok, pos, out_tok, generic=True)
+            moe = {"experts": args.moe[0], "top_k": args.moe[1], "expert_intermediate": args.moe[2], "ms_step": timed(mstep),
+                   "launches_per_token": mstep.launches_per_token, "ms_step_dense_again": timed(kernel_step),
+                   "launches_per_token_dense": kernel_step.launches_per_token}
+            del mstep
         shared = None
         if args.shared_prefix:
             P, ps, mp = args.shared_prefix, args.paged, args.context // args.paged
@@ -416,6 +455,8 @@ def main(argv=None, quiet=False):
             res["blocks"] = blocks
         if shared is not None:
             res["shared_prefix"] = shared
+        if moe is not None:
+            res["moe"] = moe
         del kc, vc, kc_ref, vc_ref, ref_cache, kernel_step
         torch.cuda.empty_cache()
         return res

@@ -48,6 +48,9 @@ Layout:
                    front of every attention launch), norm_add (sandwich post-norm + residual add), glu_gelu_tanh (GeGLU), logit_cap
                    (final-logit soft cap) and their float64 contracts reference_*; the step classes take them as qkv_bias= /
                    qk_norm= / post_norms= / mlp_act= / logit_cap=
+  moe.py           mixture-of-experts MLPs (csrc/moe_route.hip, csrc/moe_gemv.hip): route (RMSNorm, router, softmax, top-k and the
+                   expert-sorted layout in one launch), moe_gemv (the routed fused decode + GEMV: experts through device pointer
+                   tables), combine, MoEMLP / quantize_experts and the contracts reference_route / _layout / _moe_mlp (numpy float64)
   packers.py       pack_trellis / pack_qweight / pack_qweight_{sq,vq}_simt on the C-ABI's host-side encoders
   quantize.py      TCQ quantiser: tail-biting Viterbi encoder (csrc/tcq_viterbi.hip) + LDLQ -> QTIPLinearTCQ
                    VQ / SQ quantiser: nearest-codeword LDLQ encoder (csrc/vq_encode.hip) -> VQLinearPack{TensorCore,SIMT}
@@ -103,6 +106,8 @@ from .grammar import ByteDFA, GrammarBank, TokenTable, compile_regex, grammar_ad
 from . import stop  # noqa: F401
 from .stop import StopBank, StopSet, compile_stops, reference_stop_advance, reference_stop_mask, stop_advance, stop_mask  # noqa: F401
 from . import blocks  # noqa: F401
+from . import moe  # noqa: F401
+from .moe import MoEMLP, quantize_experts, reference_layout, reference_moe_mlp, reference_route  # noqa: F401
 from . import decoder  # noqa: F401
 from .decoder import DecodeStep, Prefill, RaggedStep, Score, SpeculativeStep, perplexity  # noqa: F401
 from . import speculative  # noqa: F401

@@ -39,6 +39,11 @@ class StopBankStruct(ctypes.Structure):
         (n, _I) for n in ("sets", "max_states", "id_slots", "cap")]
 
 
+class MoeProj(ctypes.Structure):
+    """qpal_moe_proj (include/qpal.h)"""
+    _fields_ = [("c1", _P), ("c2", _P), ("wscale", _P), ("m", _I), ("kv", _I), ("kv2", _I), ("out_col", _I)]
+
+
 PEER_WS_BYTES_PER_SLOT = 256
 IPC_HANDLE_BYTES = 64
 
@@ -137,6 +142,12 @@ _SIGNATURES = {
     "qpal_norm_add": [_P, ctypes.c_long, _P, ctypes.c_long, _P, _F, _I, _I, _P],
     "qpal_glu_gelu_tanh": [_P, ctypes.c_long, _P, ctypes.c_long, _I, _I, _P],
     "qpal_logit_cap": [_P, ctypes.c_long, _I, _I, _F, _P],
+    "qpal_moe_max_groups": [_I, _I, _I],
+    "qpal_moe_route_ws_bytes": [_I, _I, _I],
+    "qpal_moe_route": [_P, ctypes.c_long, _P, _F, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
+    "qpal_moe_gemv": [_P, ctypes.c_long, _I, ctypes.POINTER(MoeProj), _I, _P, ctypes.c_long, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I,
+                      _F, _P],
+    "qpal_moe_combine": [_P, ctypes.c_long, _P, ctypes.c_long, _P, _P, _I, _I, _I, _I, _I, _P],
 }
 
 HESSIAN_TILE = 128  # QPAL_HESSIAN_TILE
@@ -177,6 +188,7 @@ def lib():
         l.qpal_attn_ragged_ws_bytes.restype = ctypes.c_long
         l.qpal_lm_head_ws_bytes.restype = ctypes.c_long
         l.qpal_tcq_viterbi_ws_bytes.restype = ctypes.c_long
+        l.qpal_moe_route_ws_bytes.restype = ctypes.c_long
         _lib = l
     return _lib
 

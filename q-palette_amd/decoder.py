@@ -128,6 +128,7 @@ from .attention import (attention_workspace, decode_attention, paged_decode_atte
                         paged_ragged_prefill_attention, prefill_attention, prefill_workspace, ragged_prefill_attention, ragged_workspace,
                         shared_prefix_decode_attention, shared_prefix_workspace)
 from .linear import multi_gemv
+from .moe import MoEMLP
 
 
 def ug_layout(mlp):
@@ -146,7 +147,9 @@ def fusable(layers):
     """True if the batch-1 step can run on `layers`: tensor-core-order projections, and codecs with a multi-job launch where the
     GEMV staging is to rotate the hidden width."""
     rot_in_gemv = ops.can_fuse_rotation(1, layers[0].self_attn.hidden_size)
-    return all(all(_tc(p) for p in l.self_attn._qkv_layout()[0] + ug_layout(l.mlp)[0] + [l.self_attn.o_proj, l.mlp.down_proj])
+    def mlp_proj(m):  # (a sparse layer's experts run the routed launches of moe.py at every batch)
+        return [] if isinstance(m, MoEMLP) else ug_layout(m)[0] + [m.down_proj]
+    return all(all(_tc(p) for p in l.self_attn._qkv_layout()[0] + mlp_proj(l.mlp) + [l.self_attn.o_proj])
                and (not rot_in_gemv or (linear.rotation_fusable(l.self_attn._qkv_layout()[0], 1)
                                         and linear.rotation_fusable([l.self_attn.o_proj], 1)))
                for l in layers)
@@ -184,6 +187,9 @@ class _Rows:
         adapters: a lora.LoraBank of these layers and slots, or None; processor: a logits.LogitProcessor of these slots, or None;
         grammar: a grammar.GrammarBank of these slots, or None; stop: a stop.StopBank of these slots, or None"""
         self.block_table = block_table
+        self.moe = [isinstance(l.mlp, MoEMLP) for l in layers]
+        if any(self.moe) and adapters is not None:
+            raise nat.QpalError(f"{who}: adapters= on a model with MoE layers is not built (no adapters on experts)")
         self.window = self._check_window(who, window, len(layers))
         self.softcap, self.sinks = self._check_score(who, softcap, sinks, layers, embed.device)
         self.slots = self._check_table(who, kcache, block_table, slots)
@@ -197,8 +203,17 @@ class _Rows:
         self.grammar = self._check_grammar(who, grammar, self.slots, embed, lm_head, sampler is not None)
         self.stop = self._check_stop(who, stop, self.slots, embed, lm_head, sampler is not None)
         self._check_block(who, layers, embed.device, inv_freq, qkv_bias, qk_norm, mlp_act, post_norms, logit_cap)
-        att, mlp = layers[0].self_attn, layers[0].mlp
+        att = layers[0].self_attn
         H, dev = att.hidden_size, embed.device
+        # an MoE layer is one whose .mlp is a MoEMLP (self.moe; dense and sparse layers may mix): its buffers are its own, sized here
+        if any(self.moe) and self.gelu:
+            raise nat.QpalError(f"{who}: mlp_act=\"gelu_tanh\" on MoE layers is not built (the routed SwiGLU rotation is silu only)")
+        # the step's OWN workspaces, one per shape of sparse layer (launches are stream-ordered): they live as long as the step
+        self.moe_ws = {}
+        for l, sparse in zip(layers, self.moe):
+            if sparse and l.mlp.shape_key() not in self.moe_ws:
+                self.moe_ws[l.mlp.shape_key()] = l.mlp.new_workspace(rows)
+        dense_inter = max([l.mlp.intermediate_size for l, sparse in zip(layers, self.moe) if not sparse], default=0)
         self.layers, self.embed, self.norm, self.lm_head, self.inv_freq = layers, embed, norm, lm_head, inv_freq
         self.kcache, self.vcache = kcache, vcache
         self.nq, self.nkv, self.head_dim = att.num_heads, att.num_key_value_heads, att.head_dim
@@ -214,10 +229,10 @@ class _Rows:
         self.h32 = torch.zeros(rows, H, dtype=torch.float32, device=dev)
         self.a16 = torch.zeros(rows, H, dtype=torch.float16, device=dev)
         self.qkv32 = torch.zeros(rows, H + 2 * att.kv_out, dtype=torch.float32, device=dev)
-        self.ug32 = torch.zeros(rows, 2 * mlp.intermediate_size, dtype=torch.float32, device=dev)
+        self.ug32 = torch.zeros(rows, 2 * dense_inter, dtype=torch.float32, device=dev)
         # a sublayer's output in front of its post-norm, and GeGLU's activation: only where a step has them
         self.y32 = None if post_norms is None else torch.zeros(rows, H, dtype=torch.float32, device=dev)
-        self.act32 = None if not self.gelu else torch.zeros(rows, mlp.intermediate_size, dtype=torch.float32, device=dev)
+        self.act32 = None if not self.gelu else torch.zeros(rows, dense_inter, dtype=torch.float32, device=dev)
         self.lm_ws = None
         if native_argmax:
             self.lm_ws_bytes = nat.lib().qpal_lm_head_ws_bytes(lm_head.shape[0])
@@ -433,7 +448,22 @@ class _Rows:
             eps, w = self.post_norms
             blocks.norm_add(h32, y32, w[i, which], eps)
 
+    def _moe_active(self):
+        """the row-activity vector of the routed launches (int64, negative: the row chooses no expert) where a class holds one on
+        the device, else None"""
+        return None
+
+    def _moe(self, i, h32):
+        """a sparse layer on the rows of h32: the six launches of moe.MoEMLP.run (rotation with the norm, route, routed up | gate,
+        SwiGLU rotation of the sorted rows, routed down, combine into the stream or the post-norm scratch)"""
+        mlp, rms = self.layers[i].mlp, (self.eps, self.layers[i].post_attention_layernorm.weight)
+        y32 = self._sub_out(h32)
+        mlp.run(h32, rms, y32, y32 is h32, active=self._moe_active(), ws=self.moe_ws[mlp.shape_key()])
+        self._post_norm(i, 1, h32, y32)
+
     def _mlp(self, i, h32, ug32):
+        if self.moe[i]:
+            return self._moe(i, h32)
         mlp, rms = self.layers[i].mlp, (self.eps, self.layers[i].post_attention_layernorm.weight)
         ugl, ugw = ug_layout(mlp)
         self._gemv(ugl, h32, mlp.SU_ug, mlp.scale, rms=rms, wscales=ugw, outs=list(ug32.split([l.out_features for l in ugl], dim=1)))
@@ -578,14 +608,17 @@ class DecodeStep(_Rows):
         if self.batch1 and not fusable(layers):
             raise nat.QpalError("DecodeStep: these layers have no batch-1 step (fusable(layers))")
         self.tok, self.pos, self.out_tok = tok, pos, out_tok
-        mlp, dev = layers[0].mlp, embed.device
+        dev = embed.device
         self.rot_in_gemv = self.batch1 and ops.can_fuse_rotation(1, self.h32.shape[1])  # k in {2048, 4096}: the GEMV staging rotates x
         self.ug_il = None
         if self.rot_in_gemv and swiglu_epilogue:
             # up | gate as ONE layer with interleaved supertile rows: the launch's epilogue writes fp16 silu(gate) * up itself
-            self.act16 = torch.zeros(1, mlp.intermediate_size, dtype=torch.float16, device=dev)
+            self.act16 = torch.zeros(1, self.ug32.shape[1] // 2, dtype=torch.float16, device=dev)
             self.ug_il = []
             for m in (l.mlp for l in layers):
+                if isinstance(m, MoEMLP):
+                    self.ug_il.append(None)  # (a sparse layer: _moe)
+                    continue
                 il = linear.interleave_up_gate(m.ug_proj, None) if m.merge_ug else linear.interleave_up_gate(m.up_proj, m.gate_proj)
                 linear.share_codebooks([il, m.down_proj] + ug_layout(m)[0])
                 inter = m.intermediate_size
@@ -619,7 +652,9 @@ class DecodeStep(_Rows):
         min_tokens=True, whose mask launch sits in front of the draw; with qkv_bias or qk_norm (one launch for both) + 1 per layer,
         with post_norms + 2 per layer, with mlp_act="gelu_tanh" + 1 per layer (the activation; the rotation behind it is the SwiGLU
         rotation's launch), with logit_cap + 1 behind a sampler's lm_head (an argmax tail needs none)"""
-        per_layer = (5 if self.ug_il and self.ug_il[0][2] else 6) if self.rot_in_gemv else 9
+        dense_il = [e for e in (self.ug_il or []) if e is not None]
+        mlp_dense = (2 if dense_il and dense_il[0][2] else 3) if self.rot_in_gemv else 4
+        per_layer = (3 if self.rot_in_gemv else 5) + mlp_dense
         block_layer, block_tail = _Rows._block_launches(self)
         per_layer += block_layer
         per_layer += 1 if getattr(self, "shared_prefix", None) is not None else 0
@@ -630,7 +665,8 @@ class DecodeStep(_Rows):
         tail += 2 if getattr(self, "grammar", None) is not None else 0
         stop = getattr(self, "stop", None)
         tail += 0 if stop is None else (2 if stop.min_tokens_mask else 1)
-        return per_layer * len(self.layers) + tail + block_tail
+        n_moe = sum(getattr(self, "moe", ()))  # a sparse layer: the six routed launches in place of the dense MLP's
+        return per_layer * len(self.layers) + (6 - mlp_dense) * n_moe + tail + block_tail
 
     def _gemv(self, proj, x, su, scale, rms=None, **kw):
         """batch 1, k in {2048, 4096}: RMSNorm + rotation inside the GEMV launch; else (70B: 8192, every batch > 1) the launch pair"""
@@ -657,8 +693,11 @@ class DecodeStep(_Rows):
             attend, cache = paged_decode_attention, (kc, vc, self.block_table)
         attend(q, k, v, *cache, self.pos, self._inv_freq(i), scale=self.attn_scale, out=out, ws=self.attn_ws, **self._score(i))
 
+    def _moe_active(self):
+        return self.pos  # an idle slot (pos < 0) routes nothing
+
     def _mlp(self, i, h32, ug32):
-        if not self.ug_il:
+        if not self.ug_il or self.ug_il[i] is None:
             return super()._mlp(i, h32, ug32)
         mlp, rms = self.layers[i].mlp, (self.eps, self.layers[i].post_attention_layernorm.weight)
         il, il_w, fuse28 = self.ug_il[i]
@@ -1114,6 +1153,9 @@ class SpeculativeStep(RaggedStep):
             self._obs_slot = torch.arange(B, dtype=i32, device=dev).repeat_interleave(K + 1).contiguous()
             self._obs_active = torch.zeros(B * (K + 1), dtype=i64, device=dev)
             self._lane1 = torch.arange(1, K + 2, dtype=i64, device=dev)
+
+    def _moe_active(self):
+        return self.row_ctr  # rows no slot holds (-1) route nothing
 
     def _setup_tail(self, vocab, dev, logprobs, top_n):
         """a draw at every ROW and up to draft + 1 tokens per slot: no last rows, no per-segment counters"""
