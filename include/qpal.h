@@ -960,6 +960,53 @@ int qpal_moe_gemv(float *out, long ldo, int out_rows, const qpal_moe_proj *proj,
 int qpal_moe_combine(float *out_f32, long ld_out, const float *y_f32, long ld_y, const float *gate, const int *inv, int n, int top_k,
                      int H, int P, int accumulate, void *stream);
 
+/* THE SECOND ROUTER AND SHARED EXPERTS (csrc/moe_route.hip; moe.reference_route_ex restates each step in float64).
+ * qpal_moe_route_ex is qpal_moe_route's argument list (renorm moves into the struct) plus a qpal_moe_router.  Per row:
+ *   1. x̂ and logits are exactly as in qpal_moe_route.  The existing router_bias still adds to the logits.
+ *   2. score = softmax(logits) over all E (QPAL_MOE_SOFTMAX), or 1 / (1 + exp(-logits)) (QPAL_MOE_SIGMOID).
+ *   3. key = score + select_bias (fp32 [E] or NULL).  The bias decides who is chosen and never enters a gate.  (An expert whose
+ *      logit is -inf — the kernel's image of a NaN logit too — has key -inf whatever its bias: chosen only when nothing else is left.)
+ *   4. With n_group > 1: experts g S .. g S + S - 1, S = E / n_group, form group g.  Its score is the largest key in it
+ *      (QPAL_MOE_GROUP_MAX) or the sum of its two largest (QPAL_MOE_GROUP_TOP2).  The topk_group groups with the largest score
+ *      are allowed, ties to the lower group id.  An expert outside them is never chosen.  (The Hugging Face code fills masked
+ *      keys with 0.0, which differs only when an allowed key is negative.)
+ *   5. The chosen set is the top_k largest keys among the allowed experts, ties to the lower expert id.  sel lists it in
+ *      ascending expert id.
+ *   6. gate = score[sel], not key.  It is divided by its sum over the chosen in ascending-id order when renorm, then multiplied
+ *      by routed_scale.
+ *   7. shared_gate_out[r] = sigmoid(x̂[r] . shared_gate) (fp16 [H], 16-byte aligned), or exactly 1.0 without shared_gate.  The
+ *      dot product runs through the logits' own chain and tree.  shared_gate_out NULL (allowed without shared_gate): not written.
+ *   8. Rows with active[r] < 0 get sel -1, gate 0 and shared_gate_out 0.
+ *   The layout arrays, the ticket and every limit are qpal_moe_route's.  Equal router rows (and equal biases) give bitwise equal
+ *   keys.  QPAL_E_SHAPE unless E % n_group == 0, 1 <= topk_group <= n_group, topk_group * S >= top_k and (TOP2) S >= 2;
+ *   QPAL_E_PARAM for an unknown scoring / group_score or a routed_scale that is not finite and > 0; QPAL_E_NULL for a NULL
+ *   router, or a shared_gate without shared_gate_out.
+ * qpal_moe_combine_shared is qpal_moe_combine plus the shared expert's rows ys fp32 [n][ld_ys] and their gates sgate fp32 [n]:
+ *   the routed sum is built as qpal_moe_combine builds it; then t = fp32(sgate[r] * ys[r][c]), one rounding; the row's term is
+ *   acc + t, or t alone where the row has no routed pair; the term is added to out or stored.  A row with sgate[r] == 0 exactly
+ *   gets no shared term at all, not even 0 * ys: what ys holds for an inactive row never reaches the stream.                    */
+#define QPAL_MOE_SOFTMAX 0
+#define QPAL_MOE_SIGMOID 1
+#define QPAL_MOE_GROUP_MAX 0
+#define QPAL_MOE_GROUP_TOP2 1
+typedef struct qpal_moe_router {
+    int scoring;                 /* QPAL_MOE_SOFTMAX / QPAL_MOE_SIGMOID                             */
+    int n_group, topk_group;     /* 1, 1: no group limit                                            */
+    int group_score;             /* QPAL_MOE_GROUP_MAX / QPAL_MOE_GROUP_TOP2                        */
+    int renorm;                  /* gates divided by their sum over the chosen                      */
+    float routed_scale;          /* finite, > 0                                                     */
+    const float *select_bias;    /* fp32 [E] added to the scores for the selection only, or NULL    */
+    const void *shared_gate_f16; /* fp16 [H] weight of the shared expert's per-row gate, or NULL    */
+    float *shared_gate_out;      /* fp32 [n], or NULL (nothing written)                             */
+} qpal_moe_router;
+int qpal_moe_route_ex(const float *h_f32, long ld_h, const void *rms_w_f16, float rms_eps, const void *router_w_f16,
+                      const float *router_bias, const long long *active, int n, int H, int E, int top_k, int *sel, float *gate,
+                      int *order, int *inv, int *x_index, int *group_expert, int *group_first, int *group_count, int *ngroups,
+                      int max_groups, unsigned *ticket, const qpal_moe_router *router, void *stream);
+int qpal_moe_combine_shared(float *out_f32, long ld_out, const float *y_f32, long ld_y, const float *gate, const int *inv,
+                            const float *ys_f32, long ld_ys, const float *sgate, int n, int top_k, int H, int P, int accumulate,
+                            void *stream);
+
 /* The launch planner of the fused GEMV entry points, on its own (host code, no GPU call; what tests and tools inspect).
  * A launch of njobs jobs — rows[j] supertile rows (m / 32) of steps1[j] + steps2[j] steps (a step = 128 columns; steps2 = 0: one
  * stream) — is cut into workgroup-sized pieces: a GROUP of G = 1 << lg_g workgroups (`waves` = 16 or 8 waves each) owns rg

@@ -92,9 +92,11 @@ def e4m3_round_trip(x):
     return x.float().clamp(-448.0, 448.0).to(torch.float8_e4m3fn).half()
 
 
-def sparse_layers(layers, E, top_k, inter, qstr, dev, seed=5):
+def sparse_layers(layers, E, top_k, inter, qstr, dev, seed=5, router="mixtral", shared_inter=0):
     """the model's layers with every MLP replaced by a MoEMLP of E random experts of intermediate width `inter` (the attention
-    modules and norms are the dense model's own): random packed weights of quantizer `qstr`, one codebook, one SU per rotation"""
+    modules and norms are the dense model's own): random packed weights of quantizer `qstr`, one codebook, one SU per rotation.
+    router: a moe.router_preset name (random select bias / shared gate where the family has one); shared_inter: the width of a
+    shared expert with sign vectors of its own (0: none)"""
     import math
     H = layers[0].self_attn.hidden_size
     g = torch.Generator().manual_seed(seed)
@@ -115,13 +117,34 @@ def sparse_layers(layers, E, top_k, inter, qstr, dev, seed=5):
                     wrapped(inter, H, 3 * (i * E + e) + 2, su_i)) for e in range(E)]
         layer = torch.nn.Module()
         layer.self_attn, layer.input_layernorm, layer.post_attention_layernorm = l.self_attn, l.input_layernorm, l.post_attention_layernorm
-        layer.mlp = qp.MoEMLP.from_experts((torch.randn(E, H, generator=g) * 4 / math.sqrt(H)).half().to(dev), experts, top_k)
+        kw = qp.moe.router_preset(router, E, top_k)
+        if router == "deepseek_v3":
+            kw["select_bias"] = (0.1 * torch.randn(E, generator=g)).to(dev)
+        if shared_inter:
+            su_s, su_d = ((torch.randint(0, 2, (n,), generator=g) * 2 - 1).half() for n in (H, shared_inter))
+            s0 = 3 * (len(layers) * E + i)
+            up, gt, dn = wrapped(H, shared_inter, s0, su_s), wrapped(H, shared_inter, s0 + 1, su_s), wrapped(shared_inter, H, s0 + 2, su_d)
+            mlp = qp.IncoherentMLP(H, shared_inter, "silu")
+            mlp.up_proj, mlp.gate_proj, mlp.down_proj = up.linear, gt.linear, dn.linear
+            mlp = mlp.to(dev)
+            mlp.SU_ug.data.copy_(up.SU), mlp.SU_dp.data.copy_(dn.SU)
+            mlp.Wscale_ug.data.copy_(torch.cat([up.Wscale, gt.Wscale])), mlp.Wscale_dp.data.copy_(dn.Wscale)
+            mlp.scale = up.scale
+            kw["shared"] = mlp
+            if router == "qwen2":
+                kw["shared_gate"] = (torch.randn(H, generator=g) / math.sqrt(H)).half().to(dev)
+        amp = 1.0 if router == "deepseek_v3" else 4.0   # (4 / sqrt(H) saturates a sigmoid)
+        layer.mlp = qp.MoEMLP.from_experts((torch.randn(E, H, generator=g) * amp / math.sqrt(H)).half().to(dev), experts, top_k, **kw)
         out.append(layer)
     return out
 
 
 def main(argv=None, quiet=False):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--moe-router", default="mixtral", choices=qp.moe.ROUTER_PRESETS,
+                    help="with --moe: the router of the sparse layers (moe.router_preset; DESIGN.md §36)")
+    ap.add_argument("--moe-shared", type=int, default=0, metavar="IS",
+                    help="with --moe: a shared expert of intermediate width IS in every sparse layer (gated for qwen2)")
     ap.add_argument("--model", default="3_8b", choices=sorted(qp.mem_op.LAYER_INFO))
     ap.add_argument("--quantizer", default="tcomb_6_7_0.5_none_0.9")
     ap.add_argument("--qdict", default=None, help="perf/qdicts/<name>.json (figure1c, figure1d) instead of --quantizer")
@@ -180,7 +203,8 @@ def main(argv=None, quiet=False):
     m = build_model(args.model, args.quantizer, args.qdict, args.layers, args.vocab, dev)
     cfg, layers, embed, lm_head, norm, inv_freq = m.cfg, m.layers, m.embed, m.lm_head, m.norm, m.inv_freq
     H, I, nkv, head_dim, nlayers = cfg.hidden_size, cfg.intermediate_size, cfg.num_key_value_heads, cfg.head_dim, len(layers)
-    moe_layers = sparse_layers(layers, *args.moe, args.quantizer, dev) if args.moe else None
+    moe_layers = (sparse_layers(layers, *args.moe, args.quantizer, dev, router=args.moe_router, shared_inter=args.moe_shared)
+                  if args.moe else None)
 
     def run_batch(B):
         nact = B - args.inactive
@@ -328,7 +352,8 @@ def main(argv=None, quiet=False):
         moe = None
         if moe_layers is not None:  # the same attention, caches, tokens and positions with sparse MLPs, then the dense step again
             mstep = qp.DecodeStep(moe_layers, embed, norm, lm_head, kc, vc, inv_freq, tok, pos, out_tok, generic=True)
-            moe = {"experts": args.moe[0], "top_k": args.moe[1], "expert_intermediate": args.moe[2], "ms_step": timed(mstep),
+            moe = {"experts": args.moe[0], "top_k": args.moe[1], "expert_intermediate": args.moe[2], "router": args.moe_router,
+                   "shared_intermediate": args.moe_shared, "ms_step": timed(mstep),
                    "launches_per_token": mstep.launches_per_token, "ms_step_dense_again": timed(kernel_step),
                    "launches_per_token_dense": kernel_step.launches_per_token}
             del mstep

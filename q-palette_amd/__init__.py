@@ -108,6 +108,7 @@ from .stop import StopBank, StopSet, compile_stops, reference_stop_advance, refe
 from . import blocks  # noqa: F401
 from . import moe  # noqa: F401
 from .moe import MoEMLP, quantize_experts, reference_layout, reference_moe_mlp, reference_route  # noqa: F401
+from .moe import Router, reference_combine_shared, reference_moe_mlp_ex, reference_route_ex  # noqa: F401
 from . import decoder  # noqa: F401
 from .decoder import DecodeStep, Prefill, RaggedStep, Score, SpeculativeStep, perplexity  # noqa: F401
 from . import speculative  # noqa: F401

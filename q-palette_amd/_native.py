@@ -44,6 +44,12 @@ class MoeProj(ctypes.Structure):
     _fields_ = [("c1", _P), ("c2", _P), ("wscale", _P), ("m", _I), ("kv", _I), ("kv2", _I), ("out_col", _I)]
 
 
+class MoeRouter(ctypes.Structure):
+    """qpal_moe_router (include/qpal.h)"""
+    _fields_ = [("scoring", _I), ("n_group", _I), ("topk_group", _I), ("group_score", _I), ("renorm", _I), ("routed_scale", _F),
+                ("select_bias", _P), ("shared_gate", _P), ("shared_gate_out", _P)]
+
+
 PEER_WS_BYTES_PER_SLOT = 256
 IPC_HANDLE_BYTES = 64
 
@@ -148,6 +154,9 @@ _SIGNATURES = {
     "qpal_moe_gemv": [_P, ctypes.c_long, _I, ctypes.POINTER(MoeProj), _I, _P, ctypes.c_long, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I,
                       _F, _P],
     "qpal_moe_combine": [_P, ctypes.c_long, _P, ctypes.c_long, _P, _P, _I, _I, _I, _I, _I, _P],
+    "qpal_moe_route_ex": [_P, ctypes.c_long, _P, _F, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P,
+                          ctypes.POINTER(MoeRouter), _P],
+    "qpal_moe_combine_shared": [_P, ctypes.c_long, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _I, _I, _I, _I, _I, _P],
 }
 
 HESSIAN_TILE = 128  # QPAL_HESSIAN_TILE

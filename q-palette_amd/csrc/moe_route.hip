@@ -1,6 +1,8 @@
 // Mixture-of-experts routing for the step classes: qpal_moe_route — RMSNorm of the fp32 stream rows, router
 // logits, softmax, top-k, gate weights and the expert-sorted layout of the routed pairs, one launch — and qpal_moe_combine, the
-// gate-weighted sum of the experts' outputs back into the stream.
+// gate-weighted sum of the experts' outputs back into the stream.  qpal_moe_route_ex is the same kernel with the second
+// router (sigmoid or softmax scores, a selection-only bias, group-limited top-k, a routed scale, a per-row shared-expert gate) in
+// wave 0's selection, and qpal_moe_combine_shared the same combine with a shared expert's rows folded in.
 //
 // Route: one workgroup (16 waves) per row.  Every expert's logit is accumulated in the same order of operations (a lane's chain over its
 // columns, then the wave's fixed tree), so two identical router rows give bitwise equal logits and the tie rule (lower expert id)
@@ -33,6 +35,7 @@ struct MoeRouteParams {
     float *gate;
     int *order, *inv, *x_index, *group_expert, *group_first, *group_count, *ngroups;
     unsigned *ticket;
+    qpal_moe_router rt;  // (read by moe_route_kernel<true> only)
 };
 
 __device__ __forceinline__ void st_agent_i(int *p, int v) {
@@ -42,12 +45,42 @@ __device__ __forceinline__ int ld_agent_i(const int *p) {
     return (int)__hip_atomic_load(as_global(reinterpret_cast<const unsigned *>(p)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// `rounds` rounds of arg-max over the values a wave holds as v[j] of id lane + 64 j (ids whose `valid` bit j is clear never
+// compete): the largest wins, ties to the lower id.  -> the bits j of this lane's winners.  The order of moe_route_kernel's own
+// top-k rounds.
+__device__ __forceinline__ unsigned route_rounds(const float (&v)[4], unsigned valid, int rounds, int lane) {
+    unsigned chosen = 0u;
+    for (int t = 0; t < rounds; t++) {
+        float b = kNegInf;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int e = lane + 64 * j;
+            if (((valid & ~chosen) >> j) & 1u)
+                if (v[j] > b || (v[j] == b && e < bi)) b = v[j], bi = e;
+        }
+#pragma unroll
+        for (int sh = 32; sh >= 1; sh >>= 1) {
+            const float ob = __shfl_xor(b, sh, 64);
+            const int oi = __shfl_xor(bi, sh, 64);
+            if (ob > b || (ob == b && oi < bi)) b = ob, bi = oi;
+        }
+        if (bi != 0x7fffffff && (bi & 63) == lane) chosen |= 1u << (bi >> 6);
+    }
+    return chosen;
+}
+
+// EX = false: qpal_moe_route.  EX = true: qpal_moe_route_ex — the shared gate's weight row is one more "expert" of the logit loop,
+// and wave 0 selects by the contract of reference_route_ex.
+template <bool EX>
 __global__ __launch_bounds__(kRouteThreads) void moe_route_kernel(const MoeRouteParams p) {
     __shared__ __attribute__((aligned(16))) float xh[kMoeMaxH];
-    __shared__ float logit[kMoeMaxExperts];
+    __shared__ float logit[kMoeMaxExperts + 1];  // (EX: entry E is the shared gate's dot product)
     __shared__ float red[kRouteThreads / 64];
     __shared__ int sel_s[kMoeMaxTopK];
     __shared__ float prob_s[kMoeMaxTopK];
+    __shared__ float key_s[EX ? kMoeMaxExperts : 1];
+    __shared__ unsigned char gallow_s[EX ? kMoeMaxExperts : 1];
     __shared__ unsigned flag;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = blockIdx.x;
@@ -77,7 +110,8 @@ __global__ __launch_bounds__(kRouteThreads) void moe_route_kernel(const MoeRoute
         // ---- logits: wave w takes experts w, w + 16, ..., kRouteBatch of them at a time (one memory round trip for the batch);
         // lane l the 8-column pieces l, l + 64, ... (H % 8 == 0).  Every expert: the same chain of FMAs per lane, the same tree.
         const int npiece = p.H >> 3;
-        for (int e0 = wave; e0 < p.E; e0 += kRouteWaves * kRouteBatch) {
+        const int ET = p.E + (EX && p.rt.shared_gate_f16 ? 1 : 0);
+        for (int e0 = wave; e0 < ET; e0 += kRouteWaves * kRouteBatch) {
             float a[kRouteBatch];
 #pragma unroll
             for (int u = 0; u < kRouteBatch; u++) a[u] = 0.f;
@@ -86,7 +120,9 @@ __global__ __launch_bounds__(kRouteThreads) void moe_route_kernel(const MoeRoute
 #pragma unroll
                 for (int u = 0; u < kRouteBatch; u++) {
                     const int e = e0 + u * kRouteWaves;
-                    wv[u] = *reinterpret_cast<const u32x4 *>(p.router_w + (long)(e < p.E ? e : e0) * p.H + 8 * c);  // (past E: a re-read, unused)
+                    const int er = e < ET ? e : e0;  // (past the end: a re-read, unused)
+                    const uint16_t *wr = EX && er == p.E ? static_cast<const uint16_t *>(p.rt.shared_gate_f16) : p.router_w + (long)er * p.H;
+                    wv[u] = *reinterpret_cast<const u32x4 *>(wr + 8 * c);
                 }
                 const float4 x0 = *reinterpret_cast<const float4 *>(xh + 8 * c);
                 const float4 x1 = *reinterpret_cast<const float4 *>(xh + 8 * c + 4);
@@ -108,6 +144,8 @@ __global__ __launch_bounds__(kRouteThreads) void moe_route_kernel(const MoeRoute
                 if (e < p.E) {  // (wave-uniform)
                     if (p.router_bias) v += p.router_bias[e];
                     if (lane == 0) logit[e] = v == v ? v : kNegInf;  // (a NaN logit is never chosen)
+                } else if (EX && e == p.E && ET > p.E) {
+                    if (lane == 0) logit[e] = v;
                 }
             }
         }
@@ -123,30 +161,117 @@ __global__ __launch_bounds__(kRouteThreads) void moe_route_kernel(const MoeRoute
                 v[j] = e < p.E ? logit[e] : kNegInf;
                 mx = fmaxf(mx, v[j]);
             }
-            mx = wave_max(mx);
-            float ex[4], sum = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                ex[j] = lane + 64 * j < p.E ? expf(v[j] - mx) : 0.f;
-                sum += ex[j];
-            }
-            sum = wave_sum(sum);
             unsigned chosen = 0u;
-            for (int t = 0; t < p.top_k; t++) {
-                float b = kNegInf;
-                int bi = 0x7fffffff;
+            float score[4];  // (EX: the gate of a chosen expert; else ex[j] / sum below)
+            float ex[4], sum = 0.f;
+            if (!EX || p.rt.scoring == QPAL_MOE_SOFTMAX) {
+                mx = wave_max(mx);
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    ex[j] = lane + 64 * j < p.E ? expf(v[j] - mx) : 0.f;
+                    sum += ex[j];
+                }
+                sum = wave_sum(sum);
+            }
+            if constexpr (!EX) {
+                for (int t = 0; t < p.top_k; t++) {
+                    float b = kNegInf;
+                    int bi = 0x7fffffff;
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const int e = lane + 64 * j;
+                        if (e < p.E && !((chosen >> j) & 1u) && (v[j] > b || (v[j] == b && e < bi))) b = v[j], bi = e;
+                    }
+#pragma unroll
+                    for (int sh = 32; sh >= 1; sh >>= 1) {
+                        const float ob = __shfl_xor(b, sh, 64);
+                        const int oi = __shfl_xor(bi, sh, 64);
+                        if (ob > b || (ob == b && oi < bi)) b = ob, bi = oi;
+                    }
+                    if ((bi & 63) == lane && bi < p.E) chosen |= 1u << (bi >> 6);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; j++) score[j] = ex[j] / sum;
+            } else {
+                // ---- scores and keys: key = score + select_bias decides who is chosen, the score alone becomes the gate
+                float key[4];
+                unsigned allowed = 0u;
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const int e = lane + 64 * j;
-                    if (e < p.E && !((chosen >> j) & 1u) && (v[j] > b || (v[j] == b && e < bi))) b = v[j], bi = e;
+                    score[j] = p.rt.scoring == QPAL_MOE_SOFTMAX ? ex[j] / sum : 1.0f / (1.0f + expf(-v[j]));
+                    key[j] = kNegInf;
+                    if (e < p.E) {
+                        key[j] = v[j] == kNegInf ? kNegInf : (p.rt.select_bias ? score[j] + p.rt.select_bias[e] : score[j]);
+                        if (!(key[j] == key[j])) key[j] = kNegInf;  // (a NaN key is never preferred)
+                        allowed |= 1u << j;
+                    }
                 }
+                if (p.rt.n_group > 1) {
+                    // ---- group scores: group g = experts g S .. g S + S - 1, its score in register g >> 6 of lane g & 63
+                    const int G = p.rt.n_group, S = p.E / G;
+                    const bool top2 = p.rt.group_score == QPAL_MOE_GROUP_TOP2;
+                    float gs[4] = {kNegInf, kNegInf, kNegInf, kNegInf};
+                    if (S <= G) {  // short groups: lane g walks its own members (S steps)
 #pragma unroll
-                for (int sh = 32; sh >= 1; sh >>= 1) {
-                    const float ob = __shfl_xor(b, sh, 64);
-                    const int oi = __shfl_xor(bi, sh, 64);
-                    if (ob > b || (ob == b && oi < bi)) b = ob, bi = oi;
+                        for (int j = 0; j < 4; j++) key_s[lane + 64 * j] = key[j];
+                        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                        for (int j = 0; j < 4; j++) {
+                            const int g = lane + 64 * j;
+                            if (g < G) {
+                                float m1 = kNegInf, m2 = kNegInf;
+                                for (int i = 0; i < S; i++) {
+                                    const float k = key_s[g * S + i];
+                                    m2 = fmaxf(m2, fminf(m1, k));
+                                    m1 = fmaxf(m1, k);
+                                }
+                                gs[j] = top2 ? m1 + m2 : m1;
+                            }
+                        }
+                    } else {  // few groups: one wave reduction each (G steps); a lane's members of g are at most its four registers
+                        for (int g = 0; g < G; g++) {
+                            float m1 = kNegInf, m2 = kNegInf;
+#pragma unroll
+                            for (int j = 0; j < 4; j++) {
+                                const int e = lane + 64 * j;
+                                if (e >= g * S && e < g * S + S) {
+                                    m2 = fmaxf(m2, fminf(m1, key[j]));
+                                    m1 = fmaxf(m1, key[j]);
+                                }
+                            }
+#pragma unroll
+                            for (int sh = 32; sh >= 1; sh >>= 1) {  // (the two sets are disjoint: equal keys count twice)
+                                const float o1 = __shfl_xor(m1, sh, 64), o2 = __shfl_xor(m2, sh, 64);
+                                m2 = fmaxf(fminf(m1, o1), fmaxf(m2, o2));
+                                m1 = fmaxf(m1, o1);
+                            }
+                            const float sc = top2 ? m1 + m2 : m1;
+#pragma unroll
+                            for (int j = 0; j < 4; j++)
+                                if (g == lane + 64 * j) gs[j] = sc;
+                        }
+                    }
+                    // ---- the topk_group best groups (ties to the lower group id), then the mask of their experts
+                    unsigned gvalid = 0u;
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        if (lane + 64 * j < G) gvalid |= 1u << j;
+                        if (!(gs[j] == gs[j])) gs[j] = kNegInf;
+                    }
+                    const unsigned gsel = route_rounds(gs, gvalid, p.rt.topk_group, lane);
+#pragma unroll
+                    for (int j = 0; j < 4; j++) gallow_s[lane + 64 * j] = (unsigned char)((gsel >> j) & 1u);
+                    __builtin_amdgcn_wave_barrier();
+                    unsigned in_group = 0u;
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const int e = lane + 64 * j;
+                        if (e < p.E && gallow_s[e / S]) in_group |= 1u << j;
+                    }
+                    allowed &= in_group;
                 }
-                if ((bi & 63) == lane && bi < p.E) chosen |= 1u << (bi >> 6);
+                chosen = route_rounds(key, allowed, p.top_k, lane);
             }
             // ascending expert id: the position of a chosen expert is the number of chosen ones below it
             int below = 0;
@@ -156,7 +281,7 @@ __global__ __launch_bounds__(kRouteThreads) void moe_route_kernel(const MoeRoute
                 if ((chosen >> j) & 1u) {
                     const int pos = below + __popcll(m & ((1ull << lane) - 1ull));
                     sel_s[pos] = lane + 64 * j;
-                    prob_s[pos] = ex[j] / sum;
+                    prob_s[pos] = score[j];
                 }
                 below += __popcll(m);
             }
@@ -173,10 +298,14 @@ __global__ __launch_bounds__(kRouteThreads) void moe_route_kernel(const MoeRoute
                     for (int j = 0; j < p.top_k; j++) den += prob_s[j];
                     g = g / den;
                 }
+                if constexpr (EX) g = g * p.rt.routed_scale;
             }
             st_agent_i(p.sel + r * p.top_k + lane, s);
             p.gate[r * p.top_k + lane] = g;
         }
+        if constexpr (EX)
+            if (lane == 0 && p.rt.shared_gate_out)  // sigmoid(x̂ · shared_gate), 1 without a gate, 0 on an inactive row
+                p.rt.shared_gate_out[r] = !live ? 0.f : (p.rt.shared_gate_f16 ? 1.0f / (1.0f + expf(-logit[p.E])) : 1.0f);
     }
     if (!ticket_last<__ATOMIC_ACQ_REL>(p.ticket, (unsigned)p.n, &flag, tid)) return;
 
@@ -260,9 +389,14 @@ struct MoeCombineParams {
     const float *gate;
     const int *inv;
     int n, top_k, H, P, accumulate;
+    const float *ys;  // (moe_combine_kernel<true> only: the shared expert's rows and their gates)
+    long ld_ys;
+    const float *sgate;
 };
 
-// out[r][c] (+)= sum_j gate[r][j] * y[inv[r][j]][c], j ascending: each product rounded to fp32, added in j order
+// out[r][c] (+)= sum_j gate[r][j] * y[inv[r][j]][c], j ascending: each product rounded to fp32, added in j order.  SHARED: then
+// + fp32(sgate[r] * ys[r][c]) behind the routed sum (alone where the row has no routed pair); a row with sgate[r] == 0 reads no ys
+template <bool SHARED>
 __global__ __launch_bounds__(256) void moe_combine_kernel(const MoeCombineParams p) {
 #pragma clang fp contract(off)  // (a product and the add behind it stay two roundings: the contract's order)
     const int r = blockIdx.y;
@@ -276,6 +410,9 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(const MoeCombineParams
             if ((unsigned)s < (unsigned)p.P) src[j] = s, g[j] = p.gate[r * p.top_k + j];
         }
     }
+    float sg = 0.f;
+    if constexpr (SHARED) sg = p.sgate[r];
+    const bool shared = SHARED && sg != 0.f;  // (an inactive row's gate is exactly 0: whatever ys holds stays out of the stream)
     for (int c = blockIdx.x * 256 + threadIdx.x; c < p.H; c += gridDim.x * 256) {
         float *o = p.out + (long)r * p.ld_out + c;
         float acc = 0.f;
@@ -287,6 +424,11 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(const MoeCombineParams
                 acc = any ? acc + t : t;
                 any = true;
             }
+        if (shared) {
+            const float t = sg * p.ys[(long)r * p.ld_ys + c];
+            acc = any ? acc + t : t;
+            any = true;
+        }
         if (p.accumulate) {
             if (any) *o = *o + acc;
         } else {
@@ -325,10 +467,11 @@ extern "C" long qpal_moe_route_ws_bytes(int n, int E, int top_k) {
     return 16 + 4L * (5L * n * top_k + 3L * mg + 1);
 }
 
-extern "C" int qpal_moe_route(const float *h_f32, long ld_h, const void *rms_w_f16, float rms_eps, const void *router_w_f16,
+static int moe_route_launch(const float *h_f32, long ld_h, const void *rms_w_f16, float rms_eps, const void *router_w_f16,
                               const float *router_bias, const long long *active, int n, int H, int E, int top_k, int renorm,
                               int *sel, float *gate, int *order, int *inv, int *x_index, int *group_expert, int *group_first,
-                              int *group_count, int *ngroups, int max_groups, unsigned *ticket, void *stream) {
+                              int *group_count, int *ngroups, int max_groups, unsigned *ticket, const qpal_moe_router *router,
+                              void *stream) {
     if (!h_f32 || !router_w_f16 || !sel || !gate || !order || !inv || !x_index || !group_expert || !group_first || !group_count ||
         !ngroups || !ticket)
         return QPAL_E_NULL;
@@ -342,22 +485,77 @@ extern "C" int qpal_moe_route(const float *h_f32, long ld_h, const void *rms_w_f
          reinterpret_cast<uintptr_t>(group_count) | reinterpret_cast<uintptr_t>(ngroups) | reinterpret_cast<uintptr_t>(ticket)) & 3)
         return QPAL_E_ALIGN;
     if (reinterpret_cast<uintptr_t>(active) & 7) return QPAL_E_ALIGN;
+    qpal_moe_router rt{};
+    if (router) {
+        rt = *router;
+        if (rt.scoring != QPAL_MOE_SOFTMAX && rt.scoring != QPAL_MOE_SIGMOID) return QPAL_E_PARAM;
+        if (rt.group_score != QPAL_MOE_GROUP_MAX && rt.group_score != QPAL_MOE_GROUP_TOP2) return QPAL_E_PARAM;
+        if (!(rt.routed_scale > 0.f) || !(rt.routed_scale < __builtin_inff())) return QPAL_E_PARAM;
+        if (rt.n_group < 1 || E % rt.n_group || rt.topk_group < 1 || rt.topk_group > rt.n_group) return QPAL_E_SHAPE;
+        const int S = E / rt.n_group;
+        if ((long)rt.topk_group * S < top_k || (rt.group_score == QPAL_MOE_GROUP_TOP2 && S < 2)) return QPAL_E_SHAPE;
+        if (rt.shared_gate_f16 && !rt.shared_gate_out) return QPAL_E_NULL;
+        if ((reinterpret_cast<uintptr_t>(rt.shared_gate_f16) & 15) ||
+            ((reinterpret_cast<uintptr_t>(rt.select_bias) | reinterpret_cast<uintptr_t>(rt.shared_gate_out)) & 3))
+            return QPAL_E_ALIGN;
+    }
     MoeRouteParams p{h_f32, ld_h, static_cast<const uint16_t *>(rms_w_f16), rms_eps, static_cast<const uint16_t *>(router_w_f16),
                      router_bias, active, n, H, E, top_k, renorm ? 1 : 0, max_groups, sel, gate, order, inv, x_index, group_expert,
-                     group_first, group_count, ngroups, ticket};
-    hipLaunchKernelGGL(moe_route_kernel, dim3(n), dim3(kRouteThreads), 0, static_cast<hipStream_t>(stream), p);
+                     group_first, group_count, ngroups, ticket, rt};
+    if (router)
+        hipLaunchKernelGGL(moe_route_kernel<true>, dim3(n), dim3(kRouteThreads), 0, static_cast<hipStream_t>(stream), p);
+    else
+        hipLaunchKernelGGL(moe_route_kernel<false>, dim3(n), dim3(kRouteThreads), 0, static_cast<hipStream_t>(stream), p);
+    return (int)hipGetLastError();
+}
+
+extern "C" int qpal_moe_route(const float *h_f32, long ld_h, const void *rms_w_f16, float rms_eps, const void *router_w_f16,
+                              const float *router_bias, const long long *active, int n, int H, int E, int top_k, int renorm,
+                              int *sel, float *gate, int *order, int *inv, int *x_index, int *group_expert, int *group_first,
+                              int *group_count, int *ngroups, int max_groups, unsigned *ticket, void *stream) {
+    return moe_route_launch(h_f32, ld_h, rms_w_f16, rms_eps, router_w_f16, router_bias, active, n, H, E, top_k, renorm, sel, gate, order,
+                            inv, x_index, group_expert, group_first, group_count, ngroups, max_groups, ticket, nullptr, stream);
+}
+
+extern "C" int qpal_moe_route_ex(const float *h_f32, long ld_h, const void *rms_w_f16, float rms_eps, const void *router_w_f16,
+                                 const float *router_bias, const long long *active, int n, int H, int E, int top_k, int *sel, float *gate,
+                                 int *order, int *inv, int *x_index, int *group_expert, int *group_first, int *group_count, int *ngroups,
+                                 int max_groups, unsigned *ticket, const qpal_moe_router *router, void *stream) {
+    if (!router) return QPAL_E_NULL;
+    return moe_route_launch(h_f32, ld_h, rms_w_f16, rms_eps, router_w_f16, router_bias, active, n, H, E, top_k, router->renorm, sel, gate,
+                            order, inv, x_index, group_expert, group_first, group_count, ngroups, max_groups, ticket, router, stream);
+}
+
+static int moe_combine_launch(float *out_f32, long ld_out, const float *y_f32, long ld_y, const float *gate, const int *inv, int n,
+                              int top_k, int H, int P, int accumulate, bool shared, const float *ys_f32, long ld_ys, const float *sgate,
+                              void *stream) {
+    if (!out_f32 || !y_f32 || !gate || !inv) return QPAL_E_NULL;
+    if (shared) {
+        if (!ys_f32 || !sgate) return QPAL_E_NULL;
+        if (ld_ys < H) return QPAL_E_SHAPE;
+        if ((reinterpret_cast<uintptr_t>(ys_f32) | reinterpret_cast<uintptr_t>(sgate)) & 3) return QPAL_E_ALIGN;
+    }
+    if (n < 1 || n > kMoeMaxRows || top_k < 1 || top_k > kMoeMaxTopK || H < 1 || P < 1 || ld_out < H || ld_y < H) return QPAL_E_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(out_f32) | reinterpret_cast<uintptr_t>(y_f32) | reinterpret_cast<uintptr_t>(gate) |
+         reinterpret_cast<uintptr_t>(inv)) & 3)
+        return QPAL_E_ALIGN;
+    MoeCombineParams p{out_f32, ld_out, y_f32, ld_y, gate, inv, n, top_k, H, P, accumulate ? 1 : 0, ys_f32, ld_ys, sgate};
+    const int gx = (H + 255) / 256;
+    const dim3 grid(gx < 32 ? gx : 32, n);
+    if (shared)
+        hipLaunchKernelGGL(moe_combine_kernel<true>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    else
+        hipLaunchKernelGGL(moe_combine_kernel<false>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
     return (int)hipGetLastError();
 }
 
 extern "C" int qpal_moe_combine(float *out_f32, long ld_out, const float *y_f32, long ld_y, const float *gate, const int *inv, int n,
                                 int top_k, int H, int P, int accumulate, void *stream) {
-    if (!out_f32 || !y_f32 || !gate || !inv) return QPAL_E_NULL;
-    if (n < 1 || n > kMoeMaxRows || top_k < 1 || top_k > kMoeMaxTopK || H < 1 || P < 1 || ld_out < H || ld_y < H) return QPAL_E_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(out_f32) | reinterpret_cast<uintptr_t>(y_f32) | reinterpret_cast<uintptr_t>(gate) |
-         reinterpret_cast<uintptr_t>(inv)) & 3)
-        return QPAL_E_ALIGN;
-    MoeCombineParams p{out_f32, ld_out, y_f32, ld_y, gate, inv, n, top_k, H, P, accumulate ? 1 : 0};
-    const int gx = (H + 255) / 256;
-    hipLaunchKernelGGL(moe_combine_kernel, dim3(gx < 32 ? gx : 32, n), dim3(256), 0, static_cast<hipStream_t>(stream), p);
-    return (int)hipGetLastError();
+    return moe_combine_launch(out_f32, ld_out, y_f32, ld_y, gate, inv, n, top_k, H, P, accumulate, false, nullptr, 0, nullptr, stream);
+}
+
+extern "C" int qpal_moe_combine_shared(float *out_f32, long ld_out, const float *y_f32, long ld_y, const float *gate, const int *inv,
+                                       const float *ys_f32, long ld_ys, const float *sgate, int n, int top_k, int H, int P,
+                                       int accumulate, void *stream) {
+    return moe_combine_launch(out_f32, ld_out, y_f32, ld_y, gate, inv, n, top_k, H, P, accumulate, true, ys_f32, ld_ys, sgate, stream);
 }

@@ -455,7 +455,8 @@ class _Rows:
 
     def _moe(self, i, h32):
         """a sparse layer on the rows of h32: the six launches of moe.MoEMLP.run (rotation with the norm, route, routed up | gate,
-        SwiGLU rotation of the sorted rows, routed down, combine into the stream or the post-norm scratch)"""
+        SwiGLU rotation of the sorted rows, routed down, combine into the stream or the post-norm scratch); a layer of the second
+        router routes through qpal_moe_route_ex and runs its shared expert in front of the one combine"""
         mlp, rms = self.layers[i].mlp, (self.eps, self.layers[i].post_attention_layernorm.weight)
         y32 = self._sub_out(h32)
         mlp.run(h32, rms, y32, y32 is h32, active=self._moe_active(), ws=self.moe_ws[mlp.shape_key()])
@@ -665,8 +666,9 @@ class DecodeStep(_Rows):
         tail += 2 if getattr(self, "grammar", None) is not None else 0
         stop = getattr(self, "stop", None)
         tail += 0 if stop is None else (2 if stop.min_tokens_mask else 1)
-        n_moe = sum(getattr(self, "moe", ()))  # a sparse layer: the six routed launches in place of the dense MLP's
-        return per_layer * len(self.layers) + (6 - mlp_dense) * n_moe + tail + block_tail
+        # a sparse layer: its routed launches (six; more with a shared expert: MoEMLP.launches) in place of the dense MLP's
+        sparse = sum(l.mlp.launches(self.h32.shape[0]) - mlp_dense for l, s in zip(self.layers, getattr(self, "moe", ())) if s)
+        return per_layer * len(self.layers) + sparse + tail + block_tail
 
     def _gemv(self, proj, x, su, scale, rms=None, **kw):
         """batch 1, k in {2048, 4096}: RMSNorm + rotation inside the GEMV launch; else (70B: 8192, every batch > 1) the launch pair"""
