@@ -960,6 +960,27 @@ int qpal_moe_gemv(float *out, long ldo, int out_rows, const qpal_moe_proj *proj,
 int qpal_moe_combine(float *out_f32, long ld_out, const float *y_f32, long ld_y, const float *gate, const int *inv, int n, int top_k,
                      int H, int P, int accumulate, void *stream);
 
+/* THE ROUTED SKINNY GEMM (csrc/moe_gemm.hip).  qpal_moe_gemm has qpal_moe_gemv's arguments, contract, limits and
+ * codes, plus max_run in 1 .. 128 (outside: QPAL_E_SHAPE) — and reads the same group table by CHUNKS: one pass over an expert's
+ * weights serves a whole chunk, where qpal_moe_gemv makes one per entry.
+ *   An entry g < min(*ngroups, max_groups) is VALID when 0 <= group_expert[g] < E, 1 <= group_count[g] <= 8, group_first[g] >= 0 and
+ *   group_first[g] + group_count[g] <= out_rows; an invalid entry belongs to no chunk and does no work.  A valid entry g + 1 FOLLOWS
+ *   a valid entry g when group_expert[g + 1] == group_expert[g] and group_first[g + 1] == group_first[g] + group_count[g].  A
+ *   SEQUENCE is a maximal run of entries each following the one before.  Its chunks are cut from its start: an entry joins the
+ *   chunk in front of it while that chunk stays within max_run rows, else it opens the next chunk (an entry is never divided: with
+ *   max_run below an entry's count the entry is a chunk of its own).  A table built by qpal_moe_route with max_run >= n gives
+ *   exactly one chunk per expert in use; a caller's table gives whatever the rule yields.
+ *   For every chunk (expert e, positions first .. first + rows - 1), projection j and row:
+ *     out[first + b][proj[j].out_col + row] = (W_e x[xi(first + b)])[row] * wscale_e[row] * oscale,   b < rows
+ *   with xi(pos) = x_index[pos], or pos when x_index is NULL; an index outside [0, x_rows) reads zeros.  Rows of `out` no chunk
+ *   names are not written.  x_rows * ldx * 2 < 2^31 (QPAL_E_SHAPE).  fp32 accumulation in the order of the columns, whatever the
+ *   table holds: a row's result is bitwise independent of the rows that share its chunk, of n and of max_run; there is no split
+ *   of K and no atomic.  (Its bits are not qpal_moe_gemv's: that kernel sums K in parts.)  One launch, no host read, no memory
+ *   beyond the arguments, never synchronises (capturable).                                                                        */
+int qpal_moe_gemm(float *out, long ldo, int out_rows, const qpal_moe_proj *proj, int nproj, const void *x_f16, long ldx, int x_rows,
+                  const int *x_index, const int *group_expert, const int *group_first, const int *group_count, const int *ngroups,
+                  int max_groups, int E, int k, const void *tlut, int S, float oscale, int max_run, void *stream);
+
 /* THE SECOND ROUTER AND SHARED EXPERTS (csrc/moe_route.hip; moe.reference_route_ex restates each step in float64).
  * qpal_moe_route_ex is qpal_moe_route's argument list (renorm moves into the struct) plus a qpal_moe_router.  Per row:
  *   1. x̂ and logits are exactly as in qpal_moe_route.  The existing router_bias still adds to the logits.

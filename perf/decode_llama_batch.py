@@ -143,6 +143,8 @@ def main(argv=None, quiet=False):
     ap = argparse.ArgumentParser()
     ap.add_argument("--moe-router", default="mixtral", choices=qp.moe.ROUTER_PRESETS,
                     help="with --moe: the router of the sparse layers (moe.router_preset; DESIGN.md §36)")
+    ap.add_argument("--moe-wide", action="store_true",
+                    help="with --moe: also time the step with MoEMLP.wide = True (moe_gemm), and once more with it off")
     ap.add_argument("--moe-shared", type=int, default=0, metavar="IS",
                     help="with --moe: a shared expert of intermediate width IS in every sparse layer (gated for qwen2)")
     ap.add_argument("--model", default="3_8b", choices=sorted(qp.mem_op.LAYER_INFO))
@@ -357,6 +359,14 @@ def main(argv=None, quiet=False):
                    "launches_per_token": mstep.launches_per_token, "ms_step_dense_again": timed(kernel_step),
                    "launches_per_token_dense": kernel_step.launches_per_token}
             del mstep
+            if args.moe_wide:   # the same layers with the routed launches as moe_gemm, then as they were
+                sparse = [l.mlp for l in moe_layers if isinstance(l.mlp, qp.MoEMLP)]
+                for wide, key in ((True, "ms_step_wide"), (False, "ms_step_again")):
+                    for mlp in sparse:
+                        mlp.wide = wide
+                    wstep = qp.DecodeStep(moe_layers, embed, norm, lm_head, kc, vc, inv_freq, tok, pos, out_tok, generic=True)
+                    moe[key] = timed(wstep)
+                    del wstep
         shared = None
         if args.shared_prefix:
             P, ps, mp = args.shared_prefix, args.paged, args.context // args.paged

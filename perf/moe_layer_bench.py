@@ -2,11 +2,12 @@
 intermediate width top_k * I at the same codec, which reads the same weight bytes at batch 1.
 
     python perf/moe_layer_bench.py [--shape mixtral | qwen3-30b-a3b] [--batch 1 8] [--no-dense] [--quantizer tcq_6_none_0.9]
-                                   [--moe-router mixtral | qwen2 | deepseek_v2 | deepseek_v3] [--moe-shared IS] [--route]
+                                   [--moe-router mixtral | qwen2 | deepseek_v2 | deepseek_v3] [--moe-shared IS] [--route] [--wide]
 
 --moe-router sets the router's fields (moe.router_preset), --moe-shared IS adds a shared expert of intermediate width
 IS (gated for qwen2): the layer is then timed with it, without it, and next to a separate IncoherentMLP of width IS.  --route times
-qpal_moe_route_ex against qpal_moe_route at the same shapes in the same call, and nothing else.
+qpal_moe_route_ex against qpal_moe_route at the same shapes in the same call, and nothing else.  --wide times the same layer, built
+once, with wide off (moe_gemv) and on (moe_gemm): two captured graphs replayed alternately, and nothing else.
 
 Random packed experts, one codebook.  Prints one JSON line per measurement: median (min, max) microseconds of 30 replays, the experts
 the routing read and the routed bytes per second over the whole layer.  For per-kernel times run it alone under a kernel trace:
@@ -56,6 +57,29 @@ def timed(fn, iters=30):
     return ts[len(ts) // 2], ts[0], ts[-1]
 
 
+def timed_pair(fa, fb, iters=30):
+    """two graphs replayed alternately: (median, min, max) microseconds of each"""
+    graphs = []
+    for fn in (fa, fb):
+        fn()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fn()
+        graphs.append(g)
+    ts = ([], [])
+    for i in range(iters + 5):
+        for g, t in zip(graphs, ts):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            g.replay()
+            b.record()
+            torch.cuda.synchronize()
+            if i >= 5:
+                t.append(a.elapsed_time(b) * 1e3)
+    return [(sorted(t)[len(t) // 2], min(t), max(t)) for t in ts]
+
+
 def dense_mlp(H, Id, q, seed=0):
     cfg = types.SimpleNamespace(hidden_size=H, intermediate_size=Id, hidden_act="silu")
 
@@ -102,6 +126,7 @@ def main(argv=None):
     ap.add_argument("--moe-router", default="mixtral", choices=qp.moe.ROUTER_PRESETS)
     ap.add_argument("--moe-shared", type=int, default=0, metavar="IS")
     ap.add_argument("--route", action="store_true")
+    ap.add_argument("--wide", action="store_true")
     args = ap.parse_args(argv)
     if args.route:
         return route_bench()
@@ -117,6 +142,22 @@ def main(argv=None):
         shared = dense_mlp(H, args.moe_shared, q, seed=1000) if args.moe_shared else None
         layer = qp.MoEMLP.from_experts(router_w, experts, K, shared=shared, **rkw)
         bare = qp.MoEMLP.from_experts(router_w, experts, K, **{k: v for k, v in rkw.items() if k != "shared_gate"}) if shared is not None else None
+        for B in args.batch if args.wide else ():
+            h, w = torch.randn(B, H, device="cuda"), torch.ones(H, dtype=torch.float16, device="cuda")
+            out, ws = torch.zeros_like(h), layer.workspace(B)
+
+            def run(wide):
+                layer.wide = wide
+                layer.run(h, (1e-5, w), out, False, ws=ws)
+            (n_med, n_lo, n_hi), (w_med, w_lo, w_hi) = timed_pair(lambda: run(False), lambda: run(True))
+            layer.wide = False
+            print(json.dumps(dict(shape=name, B=B, quantizer=q, ngroups=int(ws.ngroups[0]), experts_read=len(set(ws.sel.cpu().numpy().ravel().tolist())),
+                                  auto=qp.moe.wide_rule(B, E, K), narrow_us=n_med, narrow_us_min=n_lo, narrow_us_max=n_hi, wide_us=w_med,
+                                  wide_us_min=w_lo, wide_us_max=w_hi)), flush=True)
+        if args.wide:
+            del layer, experts, bare, shared
+            torch.cuda.empty_cache()
+            continue
         for B in args.batch:
             h, w = torch.randn(B, H, device="cuda"), torch.ones(H, dtype=torch.float16, device="cuda")
             out, ws = torch.zeros_like(h), layer.workspace(B)

@@ -50,7 +50,8 @@ Layout:
                    qk_norm= / post_norms= / mlp_act= / logit_cap=
   moe.py           mixture-of-experts MLPs (csrc/moe_route.hip, csrc/moe_gemv.hip): route (RMSNorm, router, softmax, top-k and the
                    expert-sorted layout in one launch), moe_gemv (the routed fused decode + GEMV: experts through device pointer
-                   tables), combine, MoEMLP / quantize_experts and the contracts reference_route / _layout / _moe_mlp (numpy float64)
+                   tables), moe_gemm (csrc/moe_gemm.hip: an expert's run of up to 128 rows in one pass over its weights;
+                   MoEMLP(wide=)), combine, MoEMLP / quantize_experts and the contracts reference_route / _layout / _moe_mlp (numpy float64)
   packers.py       pack_trellis / pack_qweight / pack_qweight_{sq,vq}_simt on the C-ABI's host-side encoders
   quantize.py      TCQ quantiser: tail-biting Viterbi encoder (csrc/tcq_viterbi.hip) + LDLQ -> QTIPLinearTCQ
                    VQ / SQ quantiser: nearest-codeword LDLQ encoder (csrc/vq_encode.hip) -> VQLinearPack{TensorCore,SIMT}

@@ -16,7 +16,11 @@ theirs; tests/test_moe_contract.py checks the restatement, tests/test_moe.py hol
 The second router and shared experts: a layer built with scoring=, select_bias=, n_group=, topk_group=,
 group_score=, routed_scale=, shared= or shared_gate= routes through qpal_moe_route_ex (reference_route_ex), runs its shared expert
 (an IncoherentMLP) on the same normed rows with the dense MLP's launches into ws.ys32, and folds it in with the one combine
-launch (qpal_moe_combine_shared, reference_combine_shared).  A layer built without them launches exactly the six above."""
+launch (qpal_moe_combine_shared, reference_combine_shared).  A layer built without them launches exactly the six above.
+
+The routed skinny GEMM: MoEMLP(wide=True | "auto") makes the two routed launches moe_gemm (qpal_moe_gemm,
+csrc/moe_gemm.hip), which reads the same group table by chunks of up to 128 rows of one expert — one pass over an expert's weights
+per chunk where moe_gemv makes one per 8 rows."""
 import collections
 import ctypes
 import math
@@ -425,6 +429,13 @@ def route(h32, rms, router_w, router_bias, top_k, renorm, ws, active=None, route
     return ws
 
 
+def wide_rule(n, E, top_k):
+    """MoEMLP(wide="auto"): the routed launches are moe_gemm when the mean run of an expert exceeds one table entry of 8 rows —
+    below that moe_gemv already makes one pass per expert in use and the wide kernel has no pass to save.  A function of the
+    shape alone: nothing is read on the host.  (DESIGN.md §37.6 holds the measured table the rule is to be set from.)"""
+    return n * top_k > GROUP_ROWS * E
+
+
 class Projection:
     """One projection kind of a layer's experts as qpal_moe_gemv takes it: device tables of the experts' stream (and second
     stream, Wscale) pointers.  Keeps the tensors it points at alive."""
@@ -455,23 +466,37 @@ def moe_gemv(out, projs, x16, tlut, group_expert, group_first, group_count, ngro
     objects of one k): out[group_first[g] + b][out_col + row] = (W_e x16[xi])[row] * wscale_e[row] * oscale for b < group_count[g],
     e = group_expert[g], xi = x_index[group_first[g] + b] (or the position itself).  out fp32 [P, ldo]; out_cols: the first
     column of each projection (default: one behind the other)."""
+    return _routed(out, projs, x16, tlut, group_expert, group_first, group_count, ngroups, x_index, oscale, out_cols, None)
+
+
+def moe_gemm(out, projs, x16, tlut, group_expert, group_first, group_count, ngroups, x_index=None, oscale=1.0, out_cols=None,
+             max_run=128):
+    """qpal_moe_gemm: moe_gemv's arguments, checks and outputs, one pass over an expert's weights per CHUNK — a run
+    of consecutive table entries of one expert with contiguous positions, cut from its start into at most max_run (1 .. 128) rows —
+    instead of one per entry.  A row's bits depend on the shapes alone: not on its chunk, not on max_run."""
+    return _routed(out, projs, x16, tlut, group_expert, group_first, group_count, ngroups, x_index, oscale, out_cols, int(max_run))
+
+
+def _routed(out, projs, x16, tlut, group_expert, group_first, group_count, ngroups, x_index, oscale, out_cols, max_run):
+    """the checks, the struct cache and the launch of moe_gemv (max_run None) and moe_gemm"""
+    who = "moe_gemv" if max_run is None else "moe_gemm"
     if out.dtype != torch.float32 or not out.is_cuda or out.dim() != 2 or out.stride(1) != 1:
-        raise nat.QpalError("moe_gemv: out must be fp32 CUDA rows")
+        raise nat.QpalError(f"{who}: out must be fp32 CUDA rows")
     if x16.dtype != torch.float16 or not x16.is_cuda or x16.dim() != 2 or x16.stride(1) != 1:
-        raise nat.QpalError("moe_gemv: x must be fp16 CUDA rows")
+        raise nat.QpalError(f"{who}: x must be fp16 CUDA rows")
     for t, name in ((group_expert, "group_expert"), (group_first, "group_first"), (group_count, "group_count"), (ngroups, "ngroups"),
                     (x_index, "x_index")):
         _want(t, name, torch.int32)
     if not 1 <= len(projs) <= 2 or any(p.k != x16.shape[1] or p.E != projs[0].E for p in projs):
-        raise nat.QpalError("moe_gemv: one or two projections of x's width and one expert count")
+        raise nat.QpalError(f"{who}: one or two projections of x's width and one expert count")
     for p in projs:
         if p.tlut_bits != 9 or not 2 <= p.kv <= 8 or (p.kv2 and not p.kv2 <= 8):
-            raise nat.QpalError(f"moe_gemv: the routed kernel decodes tcq_* and tcomb_* layers with codebooks of 512 pairs (S = 9) and KV 2..8 "
+            raise nat.QpalError(f"{who}: the routed kernel decodes tcq_* and tcomb_* layers with codebooks of 512 pairs (S = 9) and KV 2..8 "
                                 f"(S = 9); got S = {p.tlut_bits}, KV = {(p.kv, p.kv2) if p.kv2 else p.kv}")
     if x_index is not None and x_index.numel() < out.shape[0]:
-        raise nat.QpalError("moe_gemv: x_index must have an entry for every row of out")
+        raise nat.QpalError(f"{who}: x_index must have an entry for every row of out")
     if not (len(group_expert) == len(group_first) == len(group_count)):
-        raise nat.QpalError("moe_gemv: the three columns of the group table differ in length")
+        raise nat.QpalError(f"{who}: the three columns of the group table differ in length")
     if out_cols is None:
         out_cols = [sum(p.m for p in projs[:i]) for i in range(len(projs))]
     key = (tuple(id(p) for p in projs[1:]), tuple(out_cols))
@@ -480,11 +505,14 @@ def moe_gemv(out, projs, x16, tlut, group_expert, group_first, group_count, ngro
         cache[key] = (nat.MoeProj * len(projs))(*[p.struct(c) for p, c in zip(projs, out_cols)])
     arr = cache[key]
     _want(tlut, "tlut", torch.float16)
+    args = (out.data_ptr(), out.stride(0), out.shape[0], arr, len(projs), x16.data_ptr(), x16.stride(0), x16.shape[0], _ptr(x_index),
+            group_expert.data_ptr(), group_first.data_ptr(), group_count.data_ptr(), ngroups.data_ptr(), len(group_expert), projs[0].E,
+            x16.shape[1], tlut.data_ptr(), projs[0].tlut_bits, float(oscale))
     with torch.cuda.device_of(out):
-        nat.check(nat.lib().qpal_moe_gemv(out.data_ptr(), out.stride(0), out.shape[0], arr, len(projs), x16.data_ptr(), x16.stride(0),
-                                          x16.shape[0], _ptr(x_index), group_expert.data_ptr(), group_first.data_ptr(),
-                                          group_count.data_ptr(), ngroups.data_ptr(), len(group_expert), projs[0].E, x16.shape[1],
-                                          tlut.data_ptr(), projs[0].tlut_bits, float(oscale), _stream(out)), "qpal_moe_gemv")
+        if max_run is None:
+            nat.check(nat.lib().qpal_moe_gemv(*args, _stream(out)), "qpal_moe_gemv")
+        else:
+            nat.check(nat.lib().qpal_moe_gemm(*args, max_run, _stream(out)), "qpal_moe_gemm")
     return out
 
 
@@ -546,11 +574,16 @@ class MoEMLP(nn.Module):
     scoring, select_bias, n_group, topk_group, group_score, routed_scale: the fields of the second router (Router); shared: an
     IncoherentMLP of the layer's hidden width and any intermediate width, in tensor-core-order codecs with a silu activation (it
     carries its own SUs and scale); shared_gate: fp16 [H], the weight of its per-row sigmoid gate (None: the shared expert counts
-    in full).  With every one of them at its default the layer is the first router's, launch for launch."""
+    in full).  With every one of them at its default the layer is the first router's, launch for launch.
+
+    wide (also an attribute): which kernel the two routed launches are.  False: moe_gemv, one pass over an expert's
+    weights per 8 routed rows.  True: moe_gemm with max_run = n, one pass per expert in use.  "auto": moe_gemm where
+    wide_rule(n, E, top_k) holds.  The launch count and the workspaces are the same."""
 
     def __init__(self, router_w, experts, top_k, renorm=True, router_bias=None, scoring="softmax", select_bias=None, n_group=1,
-                 topk_group=1, group_score="max", routed_scale=1.0, shared=None, shared_gate=None):
+                 topk_group=1, group_score="max", routed_scale=1.0, shared=None, shared_gate=None, wide=False):
         super().__init__()
+        self.wide = wide
         E = len(experts)
         if router_w.dim() != 2 or router_w.shape[0] != E:
             raise nat.QpalError(f"MoEMLP: router_w must be [E = {E}, H], got {tuple(router_w.shape)}")
@@ -644,7 +677,7 @@ class MoEMLP(nn.Module):
         """experts: a list of (up, gate, down) IncoherentLinear triples (quantize_experts builds one).  Checks what the launches
         assume — one quantizer string per projection kind, ONE SU for all up and gate, ONE for all down, left-only rotation, one
         scale, one codebook — builds the pointer tables and keeps the modules alive.  **router: scoring=, select_bias=, n_group=,
-        topk_group=, group_score=, routed_scale=, shared=, shared_gate= (the class's)."""
+        topk_group=, group_score=, routed_scale=, shared=, shared_gate=, wide= (the class's)."""
         return MoEMLP(router_w, [tuple(t) for t in experts], top_k, renorm=renorm, router_bias=router_bias, **router)
 
     @property
@@ -684,10 +717,17 @@ class MoEMLP(nn.Module):
                    in_mode=had.IN_F32, out=ws.x16)
         route(h32, rms, self.router_w, self.router_bias, self.top_k, self.renorm, ws, active=active, router=self.router)
         table = (ws.group_expert, ws.group_first, ws.group_count, ws.ngroups)
-        moe_gemv(ws.ug32, [self.p_up, self.p_gate], ws.x16, self.tlut, *table, x_index=ws.x_index, oscale=self.scale)
+        if self.wide not in (False, True, "auto"):
+            raise nat.QpalError(f"MoEMLP: wide must be False, True or \"auto\", got {self.wide!r}")
+        if self.wide is True or (self.wide == "auto" and wide_rule(n, self.num_experts, self.top_k)):
+            def routed(*a, **kw):   # one pass over an expert's weights per expert in use (a run is at most n rows)
+                return moe_gemm(*a, max_run=n, **kw)
+        else:
+            routed = moe_gemv
+        routed(ws.ug32, [self.p_up, self.p_gate], ws.x16, self.tlut, *table, x_index=ws.x_index, oscale=self.scale)
         had.rotate(ws.ug32, in_mode=had.IN_SWIGLU_F32, hadK=self.had_left_dp_T, K=self.inter_K, su=self.SU_dp,
                    post_scale=1.0 / self.scale, out=ws.act16)
-        moe_gemv(ws.y32, [self.p_down], ws.act16, self.tlut, *table, oscale=self.scale)
+        routed(ws.y32, [self.p_down], ws.act16, self.tlut, *table, oscale=self.scale)
         if self.shared is None:
             return combine(out, ws.y32, ws.gate, ws.inv, accumulate=accumulate)
         # the shared expert on the same normed rows, every row (an inactive row's result stays out: its gate is 0): the dense MLP's
