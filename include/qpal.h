@@ -543,6 +543,35 @@ int qpal_attn_rope_prefill_ragged_score(const float *q, const float *k, const fl
 int qpal_lm_head_logits(const float *h_f32, long ld_h, const void *rms_w_f16, float rms_eps, const void *w_f16, float *logits_f32,
                         long ld_logits, int rows, int vocab, int k, void *stream);
 
+/* Final norm + an 8-bit lm_head, logits and / or the greedy token of every row in one launch (csrc/lm_head_w8.hip).
+ * The table: row v of a [vocab, k] table is w_e4m3[v][:] in OCP e4m3fn, one byte per element with no NaN codes, plus scale_f32[v]
+ * in fp32, finite and > 0; its value is scale[v] * e4m3(w8[v][j]).  The argument list is qpal_lm_head_logits's with w_e4m3 and
+ * scale_f32 [vocab] in place of w_f16; logits_f32 may be NULL; token int64 [rows] or NULL; active int64 [rows] or NULL; ws /
+ * ws_bytes the workspace: qpal_lm_head_w8_ws_bytes(rows, vocab) bytes of device memory, 8-byte aligned, ZERO before the first
+ * launch; the launch leaves the workspace as it found it (it is read and written only where token is given).  Row and width
+ * limits are unchanged: rows 1 .. 128, k a multiple of 512 with 512 <= k <= 8192.
+ *   x is exactly the fp16 kernel's staged x: the two-rounding RMSNorm, rms_w == NULL for weight 1, eps <= 0 for no norm.
+ *   logits[b][v] = fp32(acc[b][v]) * scale[v], where acc is the fp32 accumulation of f16(e4m3 w) * x.  The conversion to fp16 is
+ *     exact, because every e4m3 value is an fp16 value.  One fp32 rounding comes from the scale.  Columns vocab .. ld_logits are
+ *     left as they were.
+ *   token[b] is the argmax of that row's logits, the lowest index on ties (-0 = +0).  It is computed in the same launch.  It is
+ *     written only where active == NULL or active[b] >= 0.
+ *   Either output pointer may be NULL, but not both: that is QPAL_E_NULL.
+ *   There is one writer per logit.  The cross-workgroup hand-over of the argmax is an integer maximum over an order-preserving
+ *   key and a ticket: it is order-independent, two launches are bitwise equal.
+ * All argument errors are return codes decided before any stream work: a null h, w, scale, both outputs, or ws with a token
+ * QPAL_E_NULL; rows, vocab, k, ld_h < k, ld_logits < vocab or a short workspace QPAL_E_SHAPE; alignment (QPAL_E_ALIGN): w and h
+ * 16 bytes, ld_h % 4 == 0 when rows > 1, scale and logits 4, rms_w, token, active and ws 8.  The launch is capturable. */
+long qpal_lm_head_w8_ws_bytes(int rows, int vocab);
+int qpal_lm_head_w8(const float *h_f32, long ld_h, const void *rms_w_f16, float rms_eps, const void *w_e4m3, const float *scale_f32,
+                    float *logits_f32, long ld_logits, long *token /* [rows] or NULL */, const long *active /* [rows] or NULL */,
+                    void *ws, long ws_bytes, int rows, int vocab, int k, void *stream);
+/* The embedding rows of such a table, one elementwise launch: out_f32[r][j] = scale[t] * float(e4m3 w8[t][j]) with t = tokens[r]
+ * (int64), one fp32 rounding; a t outside [0, vocab) writes a row of zeros.  rows 1 .. 128, k a multiple of 16, ld_out >= k
+ * (columns k .. ld_out are left as they were).  Alignment: w and out 16 bytes, ld_out % 4 == 0 when rows > 1, scale 4, tokens 8. */
+int qpal_embed_rows_w8(const void *w_e4m3, const float *scale_f32, const long *tokens, float *out_f32, long ld_out, int rows,
+                       int vocab, int k, void *stream);
+
 /* The next token of `rows` sequences (1 .. 128) from their logits fp32 [rows][ld_logits] (ld_logits >= vocab), one launch
  * (csrc/sample.hip).  temperature / top_p fp32 [rows], top_k int32 [rows], seed / ctr int64 [rows], token int64 [rows]: all on the
  * device and never read by the host (a captured launch can be replayed while the caller rewrites them); nothing is allocated.

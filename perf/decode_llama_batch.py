@@ -50,6 +50,10 @@ shared_prefix=...) —, the plain step again behind them, and h
 --qkv-bias / --qk-norm / --geglu / --post-norms / --logit-cap time the step with each block variant of DESIGN.md §34 on the random
 model (random bias, norm weights 1 + 0.3 N(0, 1)), each on its own, all given ones together, and the plain step again: "blocks" in
 the result, with every step's launches_per_token.
+
+--vocab-w8 times the step with both vocabulary tables in 8 bits (sampling.quantize_table of embed and lm_head): greedy
+(one tail launch, tokens only) and with a greedy sampler (8-bit logits + draw), between timings of the fp16 step with that sampler
+and behind them the plain step again, in the same call: "vocab_w8" in the result.
 """
 import argparse
 import json
@@ -181,6 +185,9 @@ def main(argv=None, quiet=False):
     ap.add_argument("--logit-cap", type=float, default=None, metavar="CAP",
                     help="also time the step with this final-logit soft cap (DecodeStep(logit_cap=CAP); it launches behind a sampler's "
                          "lm_head only: the step is timed with a greedy sampler, against the plain step with that sampler)")
+    ap.add_argument("--vocab-w8", action="store_true",
+                    help="also time the step with embed = lm_head's 8-bit twins (sampling.Table8, DESIGN.md §38): greedy and with a greedy "
+                         "sampler, beside the fp16 step with that sampler and the plain step again")
     ap.add_argument("--moe", type=int, nargs=3, default=None, metavar=("E", "TOP_K", "I"),
                     help="also time the step on the same model with every MLP a MoEMLP of E random experts of intermediate width I, "
                          "TOP_K of them per token (DESIGN.md §35; --quantizer must be a tcq_* / tcomb_*_0.5 string with KV <= 8)")
@@ -351,6 +358,23 @@ def main(argv=None, quiet=False):
             if len(variants) > 1:
                 blocks["all"] = variant_step({k: v for kw in variants.values() for k, v in kw.items()})
             blocks["plain_again"] = {"ms_step": timed(kernel_step), "launches_per_token": kernel_step.launches_per_token}
+        vocab8 = None
+        if args.vocab_w8:
+            # the same layers, caches, tokens and positions with both tables in 8 bits; the greedy 8-bit step ends in ONE launch
+            # (tokens only), the sampled one in the 8-bit logits + a draw; the fp16 steps before and behind them (the spread)
+            e8, l8 = qp.sampling.quantize_table(embed), qp.sampling.quantize_table(lm_head)
+            smp = qp.Sampler(B, args.vocab, dev, temperature=0.0)
+            s16 = qp.DecodeStep(layers, embed, norm, lm_head, kc, vc, inv_freq, tok, pos, out_tok, generic=True, sampler=smp)
+            g8 = qp.DecodeStep(layers, e8, norm, l8, kc, vc, inv_freq, tok, pos, out_tok, generic=True)
+            s8 = qp.DecodeStep(layers, e8, norm, l8, kc, vc, inv_freq, tok, pos, out_tok, generic=True, sampler=smp)
+            vocab8 = {"ms_step_fp16_sampler": timed(s16), "ms_step_w8_greedy": timed(g8), "ms_step_w8_sampler": timed(s8),
+                      "ms_step_fp16_sampler_again": timed(s16), "ms_step_w8_greedy_again": timed(g8),
+                      "ms_step_fp16_greedy_again": timed(kernel_step),
+                      "launches_per_token": {"fp16_greedy": kernel_step.launches_per_token, "fp16_sampler": s16.launches_per_token,
+                                             "w8_greedy": g8.launches_per_token, "w8_sampler": s8.launches_per_token},
+                      "table_bytes": {"fp16": 2 * embed.numel() + 2 * lm_head.numel(),
+                                      "w8": sum(t.w8.numel() + 4 * t.scale.numel() for t in (e8, l8))}}
+            del s16, g8, s8, smp, e8, l8
         moe = None
         if moe_layers is not None:  # the same attention, caches, tokens and positions with sparse MLPs, then the dense step again
             mstep = qp.DecodeStep(moe_layers, embed, norm, lm_head, kc, vc, inv_freq, tok, pos, out_tok, generic=True)
@@ -492,6 +516,8 @@ def main(argv=None, quiet=False):
             res["shared_prefix"] = shared
         if moe is not None:
             res["moe"] = moe
+        if vocab8 is not None:
+            res["vocab_w8"] = vocab8
         del kc, vc, kc_ref, vc_ref, ref_cache, kernel_step
         torch.cuda.empty_cache()
         return res

@@ -21,6 +21,11 @@ top-k 50 / top-p 0.9.  Every figure is us per launch from a captured graph of --
 variants alternate within a round (A/B in one process), and median, least and largest round are kept.  --parent-lib PATH loads a
 second build of the library (the parent commit's) and times its qpal_sample in the same rounds.
 
+--lm-head-w8 times the 8-bit lm_head and nothing else: qpal_lm_head_w8 writing logits, tokens only and both, beside
+qpal_lm_head_logits on the fp16 table, that launch plus a greedy qpal_sample, and qpal_calib_stream_read over either table's bytes;
+the launches alternate within --rounds rounds; median, least and largest round are kept.
+
+    python perf/sampling_kernels.py --lm-head-w8 [--rows 1 8 64 128] [--rounds 9]
     python perf/sampling_kernels.py [--vocab 128256] [--k 4096] [--rows 1 8 64 128] [--iters 20] [--warmup 5] [--grammar]
                                     [--top-logprobs 5 20 64]
     python perf/sampling_kernels.py --truncation [--rows 1 8 128] [--min-p 0.05] [--top-a 0.2] [--typical-p 0.9] [--rounds 9]
@@ -206,6 +211,54 @@ def truncation_launches(args, dev):
     return out
 
 
+def lm_head_w8_launches(args, dev):
+    """the measurement of DESIGN.md §38: qpal_lm_head_w8 (logits; tokens only; both) beside qpal_lm_head_logits on the fp16 twin,
+    logits + greedy qpal_sample, and qpal_calib_stream_read over the 8-bit and the fp16 table's bytes; the launches alternate
+    within a round, args.rounds rounds of args.iters launches each: median, least and largest round in us per launch"""
+    lib, stream = qp._native.lib(), torch.cuda.current_stream(dev).cuda_stream
+    gen = torch.Generator(device=dev).manual_seed(1)
+    W = (torch.randn(args.vocab, args.k, device=dev, generator=gen) * 0.02).half()
+    table = qp.sampling.quantize_table(W)
+    w_ln = torch.ones(args.k, dtype=torch.float16, device=dev)
+    sink = torch.zeros(4096, dtype=torch.uint8, device=dev)
+
+    def stream_read(t):
+        srcs, nbytes = (ctypes.c_void_p * 1)(t.data_ptr()), (ctypes.c_long * 1)(t.numel() * t.element_size())
+        return lambda: qp._native.check(lib.qpal_calib_stream_read(srcs, nbytes, 1, sink.data_ptr(), 2048, stream), "stream")
+
+    out = {"what": "qpal_lm_head_w8 beside qpal_lm_head_logits, us per launch (events, %d alternating rounds of %d launches)"
+                   % (args.rounds, args.iters), "vocab": args.vocab, "k": args.k, "table8_bytes": table.w8.numel(), "rows": []}
+    for rows in args.rows:
+        h = torch.randn(rows, args.k, device=dev, generator=gen)
+        ctr = torch.arange(rows, dtype=torch.int64, device=dev)
+        tok = torch.zeros(rows, dtype=torch.int64, device=dev)
+        smp = qp.Sampler(rows, args.vocab, dev, temperature=0.0)
+        ws = qp.sampling.lm_head_w8_workspace(rows, args.vocab, dev)
+
+        def fp16_tail():
+            qp.lm_head_logits(h, w_ln, 1e-5, W, out=smp.logits)
+            qp.sample(smp.logits, smp, ctr, out=tok)
+
+        launches = {"fp16_logits": lambda: qp.lm_head_logits(h, w_ln, 1e-5, W, out=smp.logits),
+                    "w8_logits": lambda: qp.lm_head_logits(h, w_ln, 1e-5, table, out=smp.logits),
+                    "w8_tokens_only": lambda: qp.sampling.lm_head_argmax(h, w_ln, 1e-5, table, tok, ws=ws),
+                    "w8_logits_and_tokens": lambda: qp.sampling.lm_head_argmax(h, w_ln, 1e-5, table, tok, ws=ws, out=smp.logits),
+                    "fp16_logits_then_greedy_sample": fp16_tail,
+                    "stream_read_table8_bytes": stream_read(table.w8), "stream_read_fp16_bytes": stream_read(W)}
+        us = {name: [] for name in launches}
+        for _ in range(args.rounds):
+            for name, fn in launches.items():
+                us[name].append(timed(fn, args.iters, args.warmup))
+        res = {"rows": rows, "launches": {}}
+        for name, v in us.items():
+            v = sorted(v)
+            res["launches"][name] = {"us_median": v[len(v) // 2], "us_min": v[0], "us_max": v[-1]}
+        out["rows"].append(res)
+        del smp
+    print(json.dumps(out))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--vocab", type=int, default=128256)
@@ -217,6 +270,7 @@ def main(argv=None):
                     help="also time qpal_top_logprob with these list lengths between qpal_token_logprob and qpal_sample(top_k = N, top_p = 0.9)")
     ap.add_argument("--grammar", action="store_true", help="also time the grammar launches (mask beside the processor, rows, advance, load)")
     ap.add_argument("--truncation", action="store_true", help="time qpal_sample and qpal_sample_trunc alone (DESIGN.md §30) and nothing else")
+    ap.add_argument("--lm-head-w8", action="store_true", help="time qpal_lm_head_w8 beside the fp16 kernel (DESIGN.md §38) and nothing else")
     ap.add_argument("--min-p", type=float, default=0.05)
     ap.add_argument("--top-a", type=float, default=0.2)
     ap.add_argument("--typical-p", type=float, default=0.9)
@@ -228,6 +282,8 @@ def main(argv=None):
     dev = torch.device("cuda", 0)
     if args.truncation:
         return truncation_launches(args, dev)
+    if args.lm_head_w8:
+        return lm_head_w8_launches(args, dev)
     gen = torch.Generator(device=dev).manual_seed(1)
     W = (torch.randn(args.vocab, args.k, device=dev, generator=gen) * 0.02).half()
     w_ln = torch.ones(args.k, dtype=torch.float16, device=dev)

@@ -116,6 +116,9 @@ _SIGNATURES = {
     "qpal_lm_head_argmax": [_P, _P, _F, _P, _P, _P, _P, ctypes.c_long, _I, _I, _P],
     "qpal_lm_head_ws_bytes": [_I],
     "qpal_lm_head_logits": [_P, ctypes.c_long, _P, _F, _P, _P, ctypes.c_long, _I, _I, _I, _P],
+    "qpal_lm_head_w8": [_P, ctypes.c_long, _P, _F, _P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _I, _I, _I, _P],
+    "qpal_lm_head_w8_ws_bytes": [_I, _I],
+    "qpal_embed_rows_w8": [_P, _P, _P, _P, ctypes.c_long, _I, _I, _I, _P],
     "qpal_sample": [_P, ctypes.c_long, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "qpal_sample_trunc": [_P, ctypes.c_long, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "qpal_token_logprob": [_P, ctypes.c_long, _I, _I, _P, _P, _P, _P, _P, _P],
@@ -198,6 +201,8 @@ def lib():
         l.qpal_attn_prefix_ws_bytes.restype = ctypes.c_long
         l.qpal_attn_ragged_ws_bytes.restype = ctypes.c_long
         l.qpal_lm_head_ws_bytes.restype = ctypes.c_long
+        if hasattr(l, "qpal_lm_head_w8_ws_bytes"):
+            l.qpal_lm_head_w8_ws_bytes.restype = ctypes.c_long
         l.qpal_tcq_viterbi_ws_bytes.restype = ctypes.c_long
         l.qpal_moe_route_ws_bytes.restype = ctypes.c_long
         _lib = l

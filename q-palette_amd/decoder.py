@@ -234,6 +234,13 @@ class _Rows:
         self.y32 = None if post_norms is None else torch.zeros(rows, H, dtype=torch.float32, device=dev)
         self.act32 = None if not self.gelu else torch.zeros(rows, dense_inter, dtype=torch.float32, device=dev)
         self.lm_ws = None
+        # an 8-bit lm_head (sampling.Table8): every tail is qpal_lm_head_w8, its argmax workspace the step's own
+        self.w8_ws = None
+        if isinstance(lm_head, sampling.Table8):
+            self._check_lm_head(who, embed, lm_head)
+            self.w8_ws = sampling.lm_head_w8_workspace(128, lm_head.shape[0], dev)  # (a tail has up to 128 rows or segments)
+        if isinstance(embed, sampling.Table8) and (H % 16 or rows > 128):
+            raise nat.QpalError(f"{who}: a Table8 embed needs a hidden width that is a multiple of 16 and at most 128 rows")
         if native_argmax:
             self.lm_ws_bytes = nat.lib().qpal_lm_head_ws_bytes(lm_head.shape[0])
             self.lm_ws = torch.zeros(self.lm_ws_bytes // 4, dtype=torch.float32, device=dev)
@@ -353,6 +360,11 @@ class _Rows:
     @staticmethod
     def _check_lm_head(who, embed, lm_head):
         H = embed.shape[1]
+        if isinstance(lm_head, sampling.Table8):  # (aligned and contiguous by construction)
+            if H % 512 or H > 8192 or lm_head.shape[1] != H:
+                raise nat.QpalError(f"{who}: qpal_lm_head_w8 needs a hidden width that is a multiple of 512 up to 8192 and a Table8 "
+                                    f"of that width, got {H} and {list(lm_head.shape)}")
+            return
         if H % 512 or H > 8192 or lm_head.data_ptr() % 16 or not lm_head.is_contiguous():
             raise nat.QpalError(f"{who}: qpal_lm_head_logits needs a hidden width that is a multiple of 512 up to 8192 and a "
                                 "contiguous 16-byte aligned lm_head")
@@ -360,6 +372,8 @@ class _Rows:
     @staticmethod
     def _has_argmax_kernel(embed, lm_head):
         """qpal_lm_head_argmax serves these hidden widths and a 16-byte aligned lm_head; elsewhere `_argmax_tail` runs torch ops"""
+        if isinstance(lm_head, sampling.Table8):
+            return False  # (its argmax is qpal_lm_head_w8's own, at every batch and width: `_argmax_tail`)
         return embed.shape[1] in (2048, 4096, 8192) and lm_head.data_ptr() % 16 == 0
 
     @staticmethod
@@ -485,7 +499,10 @@ class _Rows:
         bufs = (self.h32, self.a16, self.qkv32, self.ug32)
         if n is not None:
             bufs = tuple(t[:n] for t in bufs)
-        bufs[0].copy_(self.embed[tokens])
+        if isinstance(self.embed, sampling.Table8):
+            sampling.embed_rows(self.embed, tokens, bufs[0])  # one launch: scale[t] * e4m3 row, into the stream
+        else:
+            bufs[0].copy_(self.embed[tokens])
         for i in range(len(self.layers)):
             self._layer(i, *bufs)
         return bufs[0]
@@ -518,9 +535,24 @@ class _Rows:
         if smp.top_id is not None:
             sampling.top_logprobs(smp.logits, smp.top_id.shape[1], ids=smp.top_id, logprob=smp.top_logprob, active=ctr)
 
-    def _argmax_tail(self, rows32, out_tok):
-        """final norm + lm_head + argmax of the rows: one launch (ONE row) where the class found the kernel available, else torch ops"""
+    def _greedy_w8(self):
+        """a Table8 lm_head under a logits tail whose draw is the plain argmax of the logits as the lm_head leaves them: no sampler,
+        cap, processor, grammar or min_tokens mask.  The tail is then `_logits_argmax_tail`, one launch."""
+        return (self.w8_ws is not None and self.sampler is None and self.logit_cap is None and self.processor is None
+                and self.grammar is None and (self.stop is None or not self.stop.min_tokens_mask))
+
+    def _logits_argmax_tail(self, rows32, lg, ctr, out_tok):
+        """`_greedy_w8`'s tail: final norm + 8-bit lm_head of the rows into lg AND the argmax of every row with ctr >= 0 into out_tok,
+        in qpal_lm_head_w8's one launch — the token qpal_sample's greedy draw takes from those logits (lowest index on ties)"""
+        sampling.lm_head_argmax(rows32, self.norm.weight, self.norm.eps, self.lm_head, out_tok, active=ctr, ws=self.w8_ws, out=lg)
+
+    def _argmax_tail(self, rows32, out_tok, active=None):
+        """final norm + lm_head + argmax of the rows: one launch (ONE row) where the class found the kernel available, else torch ops;
+        a Table8 lm_head: one launch at every batch and width, no logit written; rows with active[row] < 0 then keep their token"""
         # (logit_cap needs nothing here: cap * tanh(l / cap) is monotone, the argmax of the capped logits is that of the plain ones)
+        if self.w8_ws is not None:
+            sampling.lm_head_argmax(rows32, self.norm.weight, self.norm.eps, self.lm_head, out_tok, active=active, ws=self.w8_ws)
+            return
         if self.lm_ws is None:
             out_tok.copy_((self.norm(rows32.half()) @ self.lm_head.T).argmax(-1))
             return
@@ -534,7 +566,9 @@ class _Rows:
 
 class DecodeStep(_Rows):
     """layers: modules with self_attn (IncoherentSdpaAttention), mlp (IncoherentMLP), input_layernorm, post_attention_layernorm;
-    embed / lm_head fp16 [vocab, H]; norm: the final RMSNorm; kcache / vcache: per-layer fp16 or float8_e4m3fn [B, nkv, context, hd]; inv_freq fp32
+    embed / lm_head fp16 [vocab, H], or a sampling.Table8 for either or both (8-bit rows with per-row scales, DESIGN.md §38: the gather is
+    qpal_embed_rows_w8, every tail qpal_lm_head_w8 — with a sampler its logits, without one the tokens alone at every B, in the
+    lm_head's own launch, idle slots keeping theirs); norm: the final RMSNorm; kcache / vcache: per-layer fp16 or float8_e4m3fn [B, nkv, context, hd]; inv_freq fp32
     [hd / 2]; tok, pos, out_tok int64 [B] (pos[b] outside the cache: sequence b is inactive).  The caller owns the caches and
     tok / pos / out_tok and may write them between replays of a captured step.  swiglu_epilogue, k28_fusion, native_lm_head,
     split_attention switch single fusions of the batch-1 step off (profiling).  qpal_lm_head_argmax serves the hidden widths
@@ -646,7 +680,8 @@ class DecodeStep(_Rows):
         """kernel launches of one step: per layer q|k|v, attention, o, up|gate, SwiGLU rotation, down (+ a rotation in front of
         q|k|v, o and up|gate where the GEMV cannot rotate; - the SwiGLU rotation where down_proj's staging runs it); + the norm /
         lm_head / argmax launch, or the lm_head logits and the draw with a sampler, + the log-probability launch of a sampler with
-        logprobs, + the top-N launch of a sampler with top_logprobs (the embedding row copy is a memcpy node); with adapters + 4
+        logprobs, + the top-N launch of a sampler with top_logprobs (the embedding row copy of an fp16 table is a memcpy node and
+        not counted; the gather from a Table8 embed is a launch, qpal_embed_rows_w8: + 1); with adapters + 4
         per layer, one per projection group; with a
         processor + 2, observe and process; with a grammar + 2, mask and advance; with shared_prefix + 1 per layer, the prefix
         phase in front of the attention launch; with stop + 1, the stop launch that ends the step, + 2 with a bank built with
@@ -661,6 +696,7 @@ class DecodeStep(_Rows):
         per_layer += 1 if getattr(self, "shared_prefix", None) is not None else 0
         per_layer += 4 if getattr(self, "adapters", None) is not None else 0  # (arithmetic on the configuration: stand-ins may lack it)
         tail = 1 if self.sampler is None else (2 if self.sampler.logprob is None else 3)
+        tail += 1 if isinstance(getattr(self, "embed", None), sampling.Table8) else 0  # the gather is a launch: qpal_embed_rows_w8
         tail += 1 if getattr(self.sampler, "top_id", None) is not None else 0
         tail += 2 if getattr(self, "processor", None) is not None else 0
         tail += 2 if getattr(self, "grammar", None) is not None else 0
@@ -723,7 +759,7 @@ class DecodeStep(_Rows):
         if self.sampler is not None:
             self._sample_tail(self.h32, self.sampler, self.pos, self.out_tok, row_slot=self._row_slot, fed=self.tok)
         else:
-            self._argmax_tail(self.h32, self.out_tok)
+            self._argmax_tail(self.h32, self.out_tok, active=self.pos)
         if self.stop is not None:  # the last launch: everything in front of it has read pos as its active vector
             stop_mod.stop_advance(self.stop, self.out_tok, self.context, tok=self.tok, pos=self.pos)
 
@@ -851,7 +887,9 @@ class Score(Prefill):
     The logits live in ONE fp32 [chunk, vocab] buffer (sc.logits: the last chunk's n rows); lp and sc.rank are views of buffers of
     max_tokens entries (default: the caches' context) that the next call overwrites.  No host synchronisation inside the call.  The
     last row has no next token: its logits are computed, its row of the log-prob launch is inactive.  The slot is left as Prefill
-    leaves it: a DecodeStep can continue at position pos0 + N.  The lm_head must suit qpal_lm_head_logits (a sampler's demands).
+    leaves it: a DecodeStep can continue at position pos0 + N.  The lm_head must suit qpal_lm_head_logits (a sampler's demands), or
+    be a sampling.Table8: the logits launch is then qpal_lm_head_w8, the log-prob launch behind it as it is (two launches: the 8-bit
+    kernel has no log-sum-exp output); a Table8 embed gathers with qpal_embed_rows_w8.
     block_table: as for Prefill (a paged cache; the caller reserves the slot's pages for pos0 .. pos0 + N - 1).  adapters: as for
     Prefill.  top_logprobs=n (1 .. 64): one `qpal_top_logprob` launch more per chunk; sc.top_id int32 / sc.top_logprob fp32 [N - 1, n]
     are then the n likeliest tokens at every scored position and their log-probabilities (views of max_tokens x n buffers, like lp).
@@ -926,6 +964,8 @@ class RaggedStep(_Rows):
     the draw Prefill or DecodeStep would have made.  None: argmax.  rs.draw.logits [segments, vocab] holds the logits, and with a
     sampler built with logprobs=True rs.draw.logprob the drawn tokens' log-probabilities, with top_logprobs=n rs.draw.top_id /
     rs.draw.top_logprob [segments, n] the n likeliest tokens per segment (an inactive segment keeps its list).
+    embed / lm_head: fp16 tables or sampling.Table8.  With a Table8 lm_head and no sampler (nor a logit_cap) the tail
+    is ONE launch, qpal_lm_head_w8 writing rs.draw.logits and out_tok together; else its logits and the draw's launches.
 
     block_table: int32 [B, max_pages] — a paged cache, as for DecodeStep; the caller has reserved the pages of every position the
     step writes.
@@ -1062,7 +1102,10 @@ class RaggedStep(_Rows):
         torch.index_select(self.h32, 0, (end.to(torch.int64) - 1).clamp(0, self.rows - 1), out=self.last32)
         if self.sampler is not None:
             self._gather_draw(seq.to(torch.int64).clamp(0, self.slots - 1))
-        self._sample_tail(self.last32, self.draw, self.ctr, self.out_tok)
+        if self._greedy_w8():
+            self._logits_argmax_tail(self.last32, self.draw.logits, self.ctr, self.out_tok)
+        else:
+            self._sample_tail(self.last32, self.draw, self.ctr, self.out_tok)
         return self.out_tok
 
 
@@ -1085,7 +1128,8 @@ class SpeculativeStep(RaggedStep):
 
     rows: the step's rows, B <= rows <= 128 (default min(128, B * (draft + 1))); drafts are cut where the rows are full.  sampler:
     the sampling.Sampler of the caches' slots — row r draws with its slot's parameters (gathered into ss.draw, a Sampler of `rows`
-    rows) and the counter of its position; None: greedy.  A sampler built with logprobs=True: the call returns (out_tok, n_out,
+    rows) and the counter of its position; None: greedy (with a sampling.Table8 lm_head and no logit_cap, processor, grammar or
+    min_tokens mask then ONE launch, qpal_lm_head_w8 writing every row's logits and draw).  A sampler built with logprobs=True: the call returns (out_tok, n_out,
     logprob fp32 [B, draft + 1]), the emitted tokens' log-probabilities, from one token_logprobs launch on the rows.  A sampler
     built with top_logprobs=n: one top_logprobs launch on the rows next to it, gathered the same way into ss.out_top_id int32 /
     ss.out_top_logprob fp32 [B, draft + 1, n] — entry (b, j), j < n_out[b], is the list of the row that emitted out_tok[b, j]; the
@@ -1219,6 +1263,9 @@ class SpeculativeStep(RaggedStep):
         tokens = self.tokens if ext_draft is None else torch.clamp(self.tokens, max=self.embed.shape[0] - 1, out=self._gather)
         self._map_rows(self.seq, self.row0)
         self._run_layers(tokens)
+        if self._greedy_w8():  # (no sampler: no log-probabilities or lists either) every row's logits and draw in one launch
+            self._logits_argmax_tail(self.h32, self.draw.logits, self.row_ctr, self.drawn)
+            return self._accept()
         sampling.lm_head_logits(self.h32, self.norm.weight, self.norm.eps, self.lm_head, out=self.draw.logits)
         self._cap_logits(self.draw.logits)
         if self.processor is not None:
@@ -1240,6 +1287,11 @@ class SpeculativeStep(RaggedStep):
             sampling.top_logprobs(self.draw.logits, n, ids=self.draw.top_id, logprob=self.draw.top_logprob, active=self.row_ctr)
             torch.index_select(self.draw.top_id, 0, rows, out=self.out_top_id.view(-1, n))
             torch.index_select(self.draw.top_logprob, 0, rows, out=self.out_top_logprob.view(-1, n))
+        return self._accept()
+
+    def _accept(self):
+        """behind the rows' draws: the accept, and what follows it (stop, grammar, processor); the call's return value"""
+        from . import speculative as spec
         spec.spec_accept(self.tokens, self.drawn, self.seq, self.row0, self.hist, self.n_tok, self.limit, self.eos, self.out_tok,
                          self.n_out, self.n_acc)
         if self.stop is not None:  # cuts n_out / n_tok / limit where a slot finishes inside its run: what follows sees the cut

@@ -21,6 +21,10 @@ top_logprobs=n)`` runs it on every row; ``reference_top_logprobs`` is its contra
 ``Sampler(..., min_p=0.05)`` (or top_a=, typical_p=, or truncation=True) adds the three truncation filters: the draw is then
 ``qpal_sample_trunc``, still one launch; ``truncation_mask`` is the set it keeps.
 
+``Table8(w8, scale)`` / ``quantize_table(t)``: an 8-bit vocabulary table (e4m3 rows, one fp32 scale per row).
+``lm_head_logits`` takes one in place of the fp16 lm_head (``qpal_lm_head_w8``, csrc/lm_head_w8.hip), ``lm_head_argmax`` is the fused
+greedy tail on it (tokens, and logits where wanted, in that one launch), ``embed_rows`` the gather (``qpal_embed_rows_w8``).
+
 The draw is specified exactly (include/qpal.h); ``reference_draw`` restates it in numpy fp64 with its own Philox.
 It is the specification the tests hold the kernel to: CPU only, no torch.cuda, no library call.
 """
@@ -199,15 +203,158 @@ def _torch():
     return torch
 
 
+class Table8:
+    """An 8-bit vocabulary table: row v of a [vocab, k] table is w8[v] in OCP e4m3fn (torch.float8_e4m3fn, one byte
+    per element, no NaN codes) and scale[v] in fp32, its value scale[v] * e4m3(w8[v][j]).  w8: contiguous float8_e4m3fn [vocab, k],
+    16-byte aligned; scale: contiguous fp32 [vocab] on the same device, finite and > 0.  A step class takes one as lm_head= and / or
+    embed= (one object serves both for tied weights) and asks it what it asks a tensor: shape, device, dtype (that of w8)."""
+
+    def __init__(self, w8, scale):
+        torch = _torch()
+        from ._native import QpalError
+        if not isinstance(w8, torch.Tensor) or w8.dtype != torch.float8_e4m3fn or w8.dim() != 2 or not w8.is_contiguous():
+            raise QpalError("Table8: w8 must be a contiguous torch.float8_e4m3fn [vocab, k] tensor (dtype)")
+        if w8.data_ptr() % 16:
+            raise QpalError("Table8: w8 must be 16-byte aligned (misaligned)")
+        if (not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or scale.shape != (w8.shape[0],)
+                or not scale.is_contiguous() or scale.device != w8.device):
+            raise QpalError(f"Table8: scale must be a contiguous fp32 [{w8.shape[0]}] tensor on {w8.device} (one scale per row: length)")
+        if not bool((torch.isfinite(scale) & (scale > 0)).all()):
+            raise QpalError("Table8: every scale must be finite and > 0")
+        self.w8, self.scale = w8, scale
+
+    shape = property(lambda self: self.w8.shape)
+    device = property(lambda self: self.w8.device)
+    dtype = property(lambda self: self.w8.dtype)
+
+    def dequantize(self):
+        """float32 [vocab, k]: scale[:, None] * w8.float()"""
+        return self.scale[:, None] * self.w8.float()
+
+
+def quantize_table(t):
+    """Table8 of an fp16 (or fp32) [vocab, k] table: scale[v] = max|t[v]| / 448 (a zero row: 1), w8 = (t / scale) clamped to +-448
+    and cast as the KV cache casts.  torch ops: not on the hot path."""
+    torch = _torch()
+    t32 = t.float()
+    amax = t32.abs().amax(dim=1)
+    scale = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+    w8 = (t32 / scale[:, None]).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+    return Table8(w8.contiguous(), scale.contiguous())
+
+
+def embed_rows(table, tokens, out):
+    """out fp32 [rows, >= k columns] (contiguous rows, 16-byte aligned) <- the rows tokens int64 [rows] of a Table8:
+    scale[t] * float(w8[t]), one fp32 rounding; a token outside [0, vocab) gives a row of zeros; columns past k are left alone.
+    1 <= rows <= 128, k a multiple of 16.  One launch on the current stream (``qpal_embed_rows_w8``)."""
+    torch = _torch()
+    from . import _native
+    who, QpalError = "embed_rows", _native.QpalError
+    if not isinstance(table, Table8):
+        raise QpalError(f"{who}: table must be a Table8")
+    vocab, k = table.shape
+    dev = table.device
+    if tokens.dtype != torch.int64 or tokens.dim() != 1 or not tokens.is_contiguous() or tokens.device != dev:
+        raise QpalError(f"{who}: tokens must be a contiguous int64 [rows] tensor on {dev}")
+    rows = tokens.shape[0]
+    if not 1 <= rows <= 128 or k % 16:
+        raise QpalError(f"{who}: rows must be in 1 .. 128 and k a multiple of 16, got {rows} rows of {k}")
+    if (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != rows or out.shape[1] < k or out.stride(1) != 1
+            or out.device != dev or out.data_ptr() % 16 or (rows > 1 and (out.stride(0) < k or out.stride(0) % 4))):
+        raise QpalError(f"{who}: out must be a 16-byte aligned fp32 [{rows}, >= {k}] tensor with contiguous rows on {dev}")
+    ld = out.stride(0) if rows > 1 else out.shape[1]
+    with torch.cuda.device(dev):
+        rc = _native.lib().qpal_embed_rows_w8(table.w8.data_ptr(), table.scale.data_ptr(), tokens.data_ptr(), out.data_ptr(), ld,
+                                              rows, vocab, k, torch.cuda.current_stream(dev).cuda_stream)
+    _native.check(rc, "qpal_embed_rows_w8")
+    return out
+
+
+def lm_head_w8_workspace(rows, vocab, device):
+    """the zeroed workspace of lm_head_argmax for up to `rows` rows: the launch leaves it zero (a step owns one for its lifetime)"""
+    torch = _torch()
+    from . import _native
+    return torch.zeros(_native.lib().qpal_lm_head_w8_ws_bytes(int(rows), int(vocab)) // 8, dtype=torch.int64, device=device)
+
+
+def _lm_head_w8(who, h32, norm_weight, eps, table, out, out_tok, active, ws):
+    """the one launch behind lm_head_logits (a Table8) and lm_head_argmax: logits into out and / or tokens into out_tok"""
+    torch = _torch()
+    from . import _native
+    QpalError = _native.QpalError
+    if not isinstance(table, Table8):
+        raise QpalError(f"{who}: the table must be a Table8 (dtype float8_e4m3fn with per-row scales)")
+    if h32.dtype != torch.float32 or not h32.is_cuda or h32.dim() != 2 or h32.stride(1) != 1:
+        raise QpalError(f"{who}: h32 must be an fp32 device tensor [rows, k] with contiguous rows")
+    rows, k = h32.shape
+    dev = h32.device
+    if not 1 <= rows <= 128 or k % 512 or not 512 <= k <= 8192:
+        raise QpalError(f"{who}: rows must be in 1 .. 128 and k a multiple of 512 up to 8192, got {list(h32.shape)}")
+    if table.shape[1] != k or table.device != dev:
+        raise QpalError(f"{who}: the table must be [vocab, {k}] on {dev}, got {list(table.shape)} on {table.device}")
+    vocab = table.shape[0]
+    ld_h = h32.stride(0) if rows > 1 else k
+    if h32.data_ptr() % 16 or ld_h % 4:
+        raise QpalError(f"{who}: h32 must be 16-byte aligned, its row stride a multiple of 4")
+    w = None
+    eps = float(eps) if eps > 0 else 0.0
+    if norm_weight is not None and eps > 0:
+        w = norm_weight
+        if w.dtype != torch.float16 or w.shape != (k,) or not w.is_contiguous() or w.device != dev or w.data_ptr() % 8:
+            raise QpalError(f"{who}: norm_weight must be a contiguous 8-byte aligned fp16 [{k}] tensor on {dev}")
+    if out is None and out_tok is None:
+        raise QpalError(f"{who}: both outputs are None: give out, out_tok or both")
+    ld_out = 0
+    if out is not None:
+        if (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != rows or out.shape[1] < vocab or out.stride(1) != 1
+                or out.device != dev or (rows > 1 and out.stride(0) < vocab)):
+            raise QpalError(f"{who}: out must be fp32 [{rows}, >= {vocab}] with contiguous rows on {dev}")
+        ld_out = out.stride(0) if rows > 1 else out.shape[1]
+    ws_bytes = 0
+    if out_tok is not None:
+        _param(out_tok, "out_tok", torch.int64, rows, dev, who)
+        if active is not None:
+            _param(active, "active", torch.int64, rows, dev, who)
+        need = _native.lib().qpal_lm_head_w8_ws_bytes(rows, vocab)
+        if ws is None:
+            ws = lm_head_w8_workspace(rows, vocab, dev)
+        ws_bytes = ws.numel() * ws.element_size()
+        if ws.device != dev or not ws.is_contiguous() or ws_bytes < need or ws.data_ptr() % 8:
+            raise QpalError(f"{who}: ws must be a contiguous 8-byte aligned workspace of >= {need} bytes on {dev} (short workspace: "
+                            f"{ws_bytes})")
+    with torch.cuda.device(dev):
+        rc = _native.lib().qpal_lm_head_w8(h32.data_ptr(), ld_h, w.data_ptr() if w is not None else None, eps, table.w8.data_ptr(),
+                                           table.scale.data_ptr(), out.data_ptr() if out is not None else None, ld_out,
+                                           out_tok.data_ptr() if out_tok is not None else None,
+                                           active.data_ptr() if out_tok is not None and active is not None else None,
+                                           ws.data_ptr() if out_tok is not None else None, ws_bytes, rows, vocab, k,
+                                           torch.cuda.current_stream(dev).cuda_stream)
+    _native.check(rc, "qpal_lm_head_w8")
+
+
+def lm_head_argmax(h32, norm_weight, eps, table8, out_tok, active=None, ws=None, out=None):
+    """The fused greedy tail on a Table8: out_tok int64 [rows] <- the argmax of every row's logits (lm_head_logits's on that table),
+    the lowest index on ties, in the lm_head's own launch (``qpal_lm_head_w8``); rows with active[row] < 0 (active: an optional
+    int64 [rows]) keep their token.  out: fp32 [rows, >= vocab] receives the logits as well, else no logit is written.  ws: a
+    workspace from lm_head_w8_workspace (None: one is allocated; a captured step passes its own).  Returns out_tok."""
+    _lm_head_w8("lm_head_argmax", h32, norm_weight, eps, table8, out, out_tok, active, ws)
+    return out_tok
+
+
 def lm_head_logits(h32, norm_weight, eps, lm_head, out=None):
     """logits fp32 [rows, vocab] = lm_head @ fp16(fp16(RMSNorm(h32)) * norm_weight) per row; norm_weight None: weight 1, as in the
     other norm entry points; eps <= 0: no norm at all, x = fp16(h32), and norm_weight is ignored.
     h32 fp32 [rows, k] (rows may be strided), 1 <= rows <= 128, k a multiple of 512 up to 8192; lm_head fp16 [vocab, k] contiguous,
-    16-byte aligned; out: fp32 [rows, >= vocab columns] with contiguous rows (columns past vocab are left alone).  Launches on the
-    current stream."""
+    16-byte aligned, or a Table8 (``qpal_lm_head_w8``: the same x against the 8-bit rows, the row scale on the fp32 sums); out: fp32
+    [rows, >= vocab columns] with contiguous rows (columns past vocab are left alone).  Launches on the current stream."""
     torch = _torch()
     from . import _native
     who, QpalError = "lm_head_logits", _native.QpalError
+    if isinstance(lm_head, Table8):
+        if out is None and h32.dim() == 2:
+            out = torch.empty(h32.shape[0], lm_head.shape[0], dtype=torch.float32, device=h32.device)
+        _lm_head_w8(who, h32, norm_weight, eps, lm_head, out, None, None, None)
+        return out
     if h32.dtype != torch.float32 or not h32.is_cuda or h32.dim() != 2 or h32.stride(1) != 1:
         raise QpalError(f"{who}: h32 must be an fp32 device tensor [rows, k] with contiguous rows")
     rows, k = h32.shape
