@@ -1010,6 +1010,25 @@ int qpal_moe_gemm(float *out, long ldo, int out_rows, const qpal_moe_proj *proj,
                   const int *x_index, const int *group_expert, const int *group_first, const int *group_count, const int *ngroups,
                   int max_groups, int E, int k, const void *tlut, int S, float oscale, int max_run, void *stream);
 
+/* THE WIDE DEQUANT GEMM (csrc/tcq_gemm_wide.hip): 129 <= n <= 256 batch rows in ONE pass over the packed weights
+ * (the entry points above make one pass per 128 rows).  njobs in 1 .. 4 jobs that share x (q | k | v, up | gate), one codec for
+ * the launch: S = 9, KV1 in 2 .. 8; KV2 = 0: single-stream layers; KV2 in 2 .. 8: column-split (combt) layers, columns [0, k/2) from
+ * c1 at KV1, [k/2, k) from c2 at KV2.  For job j, b < n and row < m:
+ *   out[b][row] (+)= (sum_c W[row][c] x[b][c]) * wscale[row] * oscale
+ * with qpal_tcq_gemv_multi's meaning of the job fields it honours: out / ldo, c1 / c2, x (fp16 [n][k], ALREADY rotated, the same
+ * pointer in every job), tlut, m, k (the same in every job), wscale, oscale, accumulate.  out_zeroed is ignored: where the launch
+ * splits K over workgroups (a function of the shapes alone) it clears rows 0 .. n - 1 of a non-accumulating output itself, with a
+ * kernel in front of the GEMM (no memset node: capturable), and adds the partial sums with fp32 atomics — such an output is
+ * reproducible to rounding, not to the bit; an accumulating job's atomics land on the live output.  Rows >= n of out are never
+ * written.  No rotation, RMSNorm, activation or per-job codec: x_had, x_su, x_f32, x_rms_eps, x_rms_w, act_out, act_su, x_hadk,
+ * x_K, kv and kv2 must be zero (QPAL_E_PARAM).
+ * Codes, decided before any device access: jobs NULL: QPAL_E_NULL; njobs outside 1 .. 4, n outside 129 .. 256, k not a multiple
+ * of 128 (two streams: 256), n * k * 2 >= 2^31, m % 32 != 0 (a supertile row is 32 output rows; m % 16 != 0 included), jobs of
+ * different k, 0 < ldo < m: QPAL_E_SHAPE; S != 9 or a KV outside 2 .. 8: QPAL_E_PARAM; a NULL out / c1 / x / tlut (c2 with KV2):
+ * QPAL_E_NULL; x not 16-byte, wscale not 2-byte, the others not 4-byte aligned: QPAL_E_ALIGN.  What it refuses runs as passes of
+ * qpal_tcq_gemv_multi over at most 128 rows each (qpalette_amd.linear.wide_gemm does that).  Never synchronises.              */
+int qpal_tcq_gemm_wide(const qpal_tcq_job *jobs, int njobs, int n, int S, int KV1, int KV2, void *stream);
+
 /* THE SECOND ROUTER AND SHARED EXPERTS (csrc/moe_route.hip; moe.reference_route_ex restates each step in float64).
  * qpal_moe_route_ex is qpal_moe_route's argument list (renorm moves into the struct) plus a qpal_moe_router.  Per row:
  *   1. x̂ and logits are exactly as in qpal_moe_route.  The existing router_bias still adds to the logits.

@@ -42,6 +42,8 @@ def main(argv=None, quiet=False):
     ap.add_argument("--prompt", type=int, nargs="+", default=[128], help="one prompt length or a list")
     ap.add_argument("--context", type=int, default=4096, help="static KV-cache length")
     ap.add_argument("--chunk", type=int, default=128)
+    ap.add_argument("--wide", type=int, default=None, metavar="R",
+                    help="also time Prefill(wide=R), 129 .. 256: chunks of R rows in one weight pass (DESIGN.md §39), same call")
     ap.add_argument("--slots", type=int, default=1, help="sequences the caches hold (B of a DecodeStep over them)")
     ap.add_argument("--slot", type=int, default=0, help="the slot the prompt goes into; the last slot, if another, is inactive")
     ap.add_argument("--vocab", type=int, default=128256)
@@ -96,6 +98,7 @@ def main(argv=None, quiet=False):
     kc = [(torch.randn(B, nkv, ctx, head_dim, device=dev, generator=cg) * 0.5).half() for _ in range(nlayers)]
     vc = [(torch.randn(B, nkv, ctx, head_dim, device=dev, generator=cg) * 0.5).half() for _ in range(nlayers)]
     pf = qp.Prefill(layers, embed, norm, lm_head, kc, vc, inv_freq, chunk=args.chunk)
+    pfw = None if args.wide is None else qp.Prefill(layers, embed, norm, lm_head, kc, vc, inv_freq, wide=args.wide)
     ref = StaticKV(nlayers, nkv, head_dim, ctx, dev)       # the torch-glue path's cache
     one = StaticKV(nlayers, nkv, head_dim, ctx, dev)       # the token-by-token paths' cache
     tok1 = torch.zeros(1, dtype=torch.long, device=dev)
@@ -172,6 +175,12 @@ def main(argv=None, quiet=False):
                 pos1.fill_(j)
             ms_pf = time_graph(lambda: pf(tokens, slot=slot, pos0=0), args.iters, dev)
             note(N, "prefill ms", ms_pf)
+            if pfw is not None:  # the same prompt into the same slot, in chunks of --wide rows
+                res["next_token_wide"] = int(pfw(tokens, slot=slot, pos0=0))
+                res["wide_vs_chunk_max_abs_diff_final_norm"] = float((pfw.hidden().float() - got_h).abs().max())
+                ms_w = time_graph(lambda: pfw(tokens, slot=slot, pos0=0), args.iters, dev)
+                note(N, "wide prefill ms", ms_w)
+                res.update({"wide": args.wide, "ms_prefill_wide": ms_w, "prompt_tokens_per_s_prefill_wide": N / ms_w * 1e3})
             ms_tbt = time_graph(fast1, N, dev, feed) * N
             note(N, "token by token ms", ms_tbt)
             ms_glue = time_graph(lambda: glue(tokens, pos), args.iters, dev)

@@ -86,6 +86,7 @@ from .linear import (  # noqa: F401
     make_linear_from_info,
     multi_gemv,
     share_codebooks,
+    wide_gemm,
 )
 from . import quantize  # noqa: F401
 from . import quantize_layer  # noqa: F401

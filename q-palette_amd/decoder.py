@@ -239,7 +239,7 @@ class _Rows:
         if isinstance(lm_head, sampling.Table8):
             self._check_lm_head(who, embed, lm_head)
             self.w8_ws = sampling.lm_head_w8_workspace(128, lm_head.shape[0], dev)  # (a tail has up to 128 rows or segments)
-        if isinstance(embed, sampling.Table8) and (H % 16 or rows > 128):
+        if isinstance(embed, sampling.Table8) and (H % 16 or (rows > 128 and who != "Prefill")):
             raise nat.QpalError(f"{who}: a Table8 embed needs a hidden width that is a multiple of 16 and at most 128 rows")
         if native_argmax:
             self.lm_ws_bytes = nat.lib().qpal_lm_head_ws_bytes(lm_head.shape[0])
@@ -426,7 +426,11 @@ class _Rows:
         launch"""
         xr = had.rotate(x, hadK=self.hidden_hadT, K=self.hidden_K, su=su, post_scale=1.0 / scale, rms=rms,
                         in_mode=had.IN_F32 if x.dtype == torch.float32 else had.IN_F16)
-        return multi_gemv(proj, xr, oscale=scale, **kw)
+        return self._gemm(proj, xr, oscale=scale, **kw)
+
+    def _gemm(self, layers, x, **kw):
+        """multi_gemv of one projection group on the rotated rows x (Prefill(wide=): a chunk above 128 rows takes linear.wide_gemm)"""
+        return multi_gemv(layers, x, **kw)
 
     def _lora(self, i, group, x, out, in_mode, rms=None):
         """with a bank: the low-rank update of one projection group of layer i on the rows of x, added to out (one launch)"""
@@ -489,7 +493,7 @@ class _Rows:
             act, act_mode = ug32, had.IN_SWIGLU_F32
         x = had.rotate(act, in_mode=act_mode, hadK=mlp.had_left_dp_T, K=mlp.inter_K, su=mlp.SU_dp, post_scale=1.0 / mlp.scale)
         y32 = self._sub_out(h32)
-        multi_gemv([mlp.down_proj], x, outs=[y32], wscales=[mlp.Wscale_dp], oscale=mlp.scale, accumulate=y32 is h32)
+        self._gemm([mlp.down_proj], x, outs=[y32], wscales=[mlp.Wscale_dp], oscale=mlp.scale, accumulate=y32 is h32)
         self._lora(i, "down", act, y32, act_mode)  # reads up | gate with their own update in
         self._post_norm(i, 1, h32, y32)
 
@@ -500,7 +504,8 @@ class _Rows:
         if n is not None:
             bufs = tuple(t[:n] for t in bufs)
         if isinstance(self.embed, sampling.Table8):
-            sampling.embed_rows(self.embed, tokens, bufs[0])  # one launch: scale[t] * e4m3 row, into the stream
+            for r in range(0, bufs[0].shape[0], 128):  # one launch per 128 rows: scale[t] * e4m3 row, into the stream
+                sampling.embed_rows(self.embed, tokens[r:r + 128], bufs[0][r:r + 128])
         else:
             bufs[0].copy_(self.embed[tokens])
         for i in range(len(self.layers)):
@@ -766,7 +771,7 @@ class DecodeStep(_Rows):
 
 class Prefill(_Rows):
     """A prompt into ONE slot of the caches a DecodeStep is built on (per-layer fp16 or float8_e4m3fn [B, nkv, context, hd]): chunks of at most
-    `chunk` <= 128 rows, each through DecodeStep's batch-B layer with rows = consecutive positions and `prefill_attention` on
+    `chunk` <= 128 rows (wide=R, 129 .. 256: of at most R rows, last paragraph), each through DecodeStep's batch-B layer with rows = consecutive positions and `prefill_attention` on
     kcache[i][slot] / vcache[i][slot] (rotary embedding at pos0 + row, rows appended, causal); final norm, lm_head and argmax for
     the LAST row only.  Other slots are not touched.  The position lives on the device and the chunk loop advances it there: no
     host synchronisation inside the call.
@@ -796,19 +801,32 @@ class Prefill(_Rows):
     masked with the slot's state as it stands (bank.set / reset put it at the start) and the drawn token advances it.
 
     window: as for DecodeStep (prefill_attention's window=): the row at position p attends to positions max(0, p - W + 1) .. p; the
-    caches end up byte for byte as without a window.  softcap / sinks / attn_scale: as for DecodeStep (prefill_attention's)."""
+    caches end up byte for byte as without a window.  softcap / sinks / attn_scale: as for DecodeStep (prefill_attention's).
+
+    wide: None, or an int R in 129 .. 256: the prompt goes in chunks of R rows, and a chunk of 129 rows or more makes
+    ONE pass over every projection's weights (linear.wide_gemm: qpal_tcq_gemm_wide where the layer's format has it, else two passes
+    of the 128-row launch) and two attention launches of at most 128 rows; a last chunk of 128 rows or fewer takes the existing
+    launches.  Not with adapters= or MoE layers (QpalError).  Split-K atomics round differently from the 128-row passes: caches and
+    logits agree with chunk=128 to rounding, not to the bit."""
 
     _launches_per = "Prefill: launches are per chunk"
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, native_lm_head=True, sampler=None,
                  block_table=None, adapters=None, processor=None, grammar=None, window=None, softcap=None, sinks=None,
                  attn_scale=None,
-                 qkv_bias=None, qk_norm=None, mlp_act="silu", post_norms=None, logit_cap=None):
+                 qkv_bias=None, qk_norm=None, mlp_act="silu", post_norms=None, logit_cap=None, wide=None):
         if not 1 <= int(chunk) <= 128:
             raise nat.QpalError(f"Prefill: chunk must be in 1 .. 128, got {chunk}")
         self.chunk = int(chunk)
+        if wide is not None:
+            if isinstance(wide, bool) or not isinstance(wide, int) or not ops.WIDE_MIN_BATCH <= wide <= ops.WIDE_MAX_BATCH:
+                raise nat.QpalError(f"Prefill: wide must be None or an int in {ops.WIDE_MIN_BATCH} .. {ops.WIDE_MAX_BATCH}, got {wide!r}")
+            if adapters is not None or any(isinstance(l.mlp, MoEMLP) for l in layers):
+                raise nat.QpalError("Prefill: wide= with adapters= or MoE layers is not built")
+        self.wide = wide
+        self.rows = self.chunk if wide is None else wide  # rows of a full chunk
         dev, H = embed.device, embed.shape[1]
-        super().__init__("Prefill", layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.chunk, sampler, block_table,
+        super().__init__("Prefill", layers, embed, norm, lm_head, kcache, vcache, inv_freq, self.rows, sampler, block_table,
                          native_argmax=native_lm_head and self._has_argmax_kernel(embed, lm_head), adapters=adapters,
                          processor=processor, grammar=grammar, window=window, softcap=softcap, sinks=sinks, attn_scale=attn_scale,
                          qkv_bias=qkv_bias, qk_norm=qk_norm, mlp_act=mlp_act, post_norms=post_norms, logit_cap=logit_cap)
@@ -818,7 +836,13 @@ class Prefill(_Rows):
         self.ctr = torch.zeros(1, dtype=torch.int64, device=dev)  # with a sampler: the last prompt row's position
         self.last32 = torch.zeros(1, H, dtype=torch.float32, device=dev)  # the last prompt row of the residual stream
         self.slot = 0
-        self.attn_ws = prefill_workspace(self.chunk, self.nq, self.nkv, self.head_dim, self.context, dev)
+        self.pos2 = torch.zeros(1, dtype=torch.int64, device=dev)  # wide: the position of a chunk's row 128
+        self.attn_ws = prefill_workspace(min(self.rows, 128), self.nq, self.nkv, self.head_dim, self.context, dev)
+
+    def _gemm(self, layers, x, **kw):
+        if x.shape[0] <= 128:
+            return multi_gemv(layers, x, **kw)
+        return linear.wide_gemm(layers, x, **kw)
 
     def _attention(self, i, q, k, v, out):
         kc, vc = self.kcache[i], self.vcache[i]
@@ -826,7 +850,10 @@ class Prefill(_Rows):
             attend, cache = prefill_attention, (kc[self.slot], vc[self.slot])
         else:
             attend, cache = paged_prefill_attention, (kc, vc, self.block_table[self.slot])
-        attend(q, k, v, *cache, self.pos, self._inv_freq(i), scale=self.attn_scale, out=out, ws=self.attn_ws, **self._score(i))
+        # (a wide chunk: two launches of at most 128 rows, the second from the device scalar pos + 128 behind the rows of the first)
+        for r, pos in ((0, self.pos), (128, self.pos2))[:1 if q.shape[0] <= 128 else 2]:
+            attend(q[r:r + 128], k[r:r + 128], v[r:r + 128], *cache, pos, self._inv_freq(i), scale=self.attn_scale, out=out[r:r + 128],
+                   ws=self.attn_ws, **self._score(i))
 
     def hidden(self):
         """fp16 [1, H]: the final norm of the last prompt row"""
@@ -855,8 +882,10 @@ class Prefill(_Rows):
 
     def _chunks(self, tokens, N):
         """runs the layers chunk by chunk; yields (c, h32) after chunk tokens[c : c + n], h32 its n rows of the residual stream"""
-        for c in range(0, N, self.chunk):
-            n = min(self.chunk, N - c)
+        for c in range(0, N, self.rows):
+            n = min(self.rows, N - c)
+            if n > 128:
+                torch.add(self.pos, 128, out=self.pos2)
             h32 = self._run_layers(tokens[c:c + n], n)
             if self.processor is not None and self.processor.count_prompt:
                 logits.observe(self.processor, tokens[c:c + n], self.slot)

@@ -235,7 +235,56 @@ def multi_gemv(layers, x, outs=None, outs_zeroed=False, prezero=None, wscales=No
     return results
 
 
+def _wide_jobs(grp):
+    """(jobs, S, KV1, KV2) of ops.tcq_gemm_wide for layers of one codec key, or None where qpal_tcq_gemm_wide refuses them (its
+    checks, restated: S = 9, KV 2..8, m % 32 == 0, whole 128-column steps in every stream)"""
+    first = grp[0]
+    kind, k = _codec_key(first)[0], first.in_features
+    if kind not in ("tcq", "tcombt") or first.tlut_bits != 9 or any(l.out_features % 32 for l in grp):
+        return None
+    kvs = (first.KV, 0) if kind == "tcq" else tuple(first.KV)
+    if not all(kv == 0 or 2 <= kv <= 8 for kv in kvs) or k % (128 if kind == "tcq" else 256):
+        return None
+    # Measured slower than two 128-row passes (DESIGN.md §39.6: the down projection of Llama-8B): ONE layer whose K the launch
+    # cuts 16 ways or more.  (The launch's own plan, restated: wide_split.)
+    nblk, T, lsk = sum(-(-l.out_features // 256) for l in grp), k // 128, 0
+    while (nblk << lsk) < 192 and (T >> (lsk + 1)) >= 4 and lsk < 5:
+        lsk += 1
+    if len(grp) == 1 and lsk >= 4:
+        return None
+    if kind == "tcq":
+        return [(l.trellis, None, l.tlut, l.out_features) for l in grp], 9, kvs[0], 0
+    return [(l.trellis1, l.trellis2, l.tlut, l.out_features) for l in grp], 9, kvs[0], kvs[1]
+
+
+def wide_gemm(layers, x, outs, wscales=None, oscale=1.0, accumulate=False):
+    """outs[i] (+)= layers[i](x) * wscales[i] * oscale for 129 .. 256 rows of one ALREADY rotated fp16 input x [n, k]: layers of one
+    codec the wide kernel serves (tcq_* / tcomb_*_0.5 at tlut_bits 9) go out as ONE pass over their weights per group of up to 4
+    (qpal_tcq_gemm_wide); every other layer runs multi_gemv on row slices of at most 128 into the same outs.
+    outs: fp32 [n, m_i] tensors (row stride >= m_i).  Returns outs."""
+    from .. import ops
+
+    x2 = x.reshape(-1, layers[0].in_features)
+    n = x2.shape[0]
+    if not ops.WIDE_MIN_BATCH <= n <= ops.WIDE_MAX_BATCH:
+        raise RuntimeError(f"wide_gemm: {n} rows; the wide launch serves {ops.WIDE_MIN_BATCH} .. {ops.WIDE_MAX_BATCH}")
+    for idxs in launch_groups(layers):
+        for a in range(0, len(idxs), 4):
+            sub = idxs[a:a + 4]
+            grp = [layers[i] for i in sub]
+            o = [outs[i] for i in sub]
+            ws = [wscales[i] for i in sub] if wscales is not None else None
+            wide = _wide_jobs(grp)
+            if wide is not None:
+                jobs, S, kv1, kv2 = wide
+                ops.tcq_gemm_wide(jobs, x2, S, kv1, kv2, outs=o, wscales=ws, oscale=oscale, accumulate=accumulate)
+            else:
+                for r in range(0, n, 128):
+                    multi_gemv(grp, x2[r:r + 128], outs=[t[r:r + 128] for t in o], wscales=ws, oscale=oscale, accumulate=accumulate)
+    return outs
+
+
 from .incoherent_linear import IncoherentLinear, IncoherentMLP, IncoherentSdpaAttention, make_linear  # noqa: E402
 
-__all__ = ["rotation_fusable", "IncoherentLinear", "IncoherentMLP", "IncoherentSdpaAttention", "make_linear", "multi_gemv", "launch_groups", "share_codebooks","QTIPLinearTCQ", "CombLinearTCQ", "CombtLinearTCQ", "VQLinearPackTensorCore", "VQLinearPackSIMT",
+__all__ = ["rotation_fusable", "IncoherentLinear", "IncoherentMLP", "IncoherentSdpaAttention", "make_linear", "multi_gemv", "wide_gemm", "launch_groups", "share_codebooks","QTIPLinearTCQ", "CombLinearTCQ", "CombtLinearTCQ", "VQLinearPackTensorCore", "VQLinearPackSIMT",
            "linear_class_for", "make_linear_from_info"]

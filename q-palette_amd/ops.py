@@ -403,6 +403,45 @@ def tcq_gemv_multi(streams, x, S, KV1, KV2=0, split=0, outs=None, outs_zeroed=Fa
                        accumulate=accumulate, act_outs=act_outs, act_su=act_su)
 
 
+WIDE_MIN_BATCH, WIDE_MAX_BATCH = 129, 256  # qpal_tcq_gemm_wide: one pass over the weights for 129 .. 256 rows
+
+
+def tcq_gemm_wide(jobs, x, S, KV1, KV2=0, outs=None, wscales=None, oscale=1.0, accumulate=False):
+    """Up to 4 TCQ layers of one codec on 129 .. 256 rows of one ALREADY rotated input in ONE pass over the weights (C-ABI
+    qpal_tcq_gemm_wide).  jobs: list of (c1, c2_or_None, tlut, m); KV2 != 0: column-split (combt) layers.  x: fp16 [n, k].
+    outs: fp32 [n, m_j] tensors to write into (row stride >= m_j), else fresh ones; wscales / oscale: out = acc * wscales[j][row]
+    * oscale; accumulate: outs[j] += ...  Returns the outputs."""
+    n, k = x.shape
+    _chk(WIDE_MIN_BATCH <= n <= WIDE_MAX_BATCH, f"batch size must be in {WIDE_MIN_BATCH}..{WIDE_MAX_BATCH}")
+    _chk(x.dtype == torch.float16, "x must be fp16 (already rotated)")
+    _chk(outs is not None or not accumulate, "accumulate needs outs")
+    xh = _dev(x, "x")
+    ms = [j[3] for j in jobs]
+    if outs is None:
+        outs = _fresh_outs(ms, n, x.device)
+    cjobs = (nat.TcqJob * len(jobs))()
+    keep = [xh]
+    for j, (c1, c2, tlut, m) in enumerate(jobs):
+        c1, tl = _dev(c1, "compressed1"), _dev(tlut, "codebook")
+        _chk(tl.dtype == torch.float16 and tl.numel() == 2 << S, f"codebook must be fp16 with {2 << S} elements")
+        if KV2:
+            c2 = _dev(c2, "compressed2")
+            _tcq_stream_ok(c1, m, k // 2, KV1, "compressed1")
+            _tcq_stream_ok(c2, m, k // 2, KV2, "compressed2")
+        else:
+            c2 = None
+            _tcq_stream_ok(c1, m, k, KV1, "compressed")
+        out = _out_arg(outs, j, n, m, x.device)
+        cjobs[j] = nat.TcqJob(out=out.data_ptr(), c1=c1.data_ptr(), c2=c2.data_ptr() if c2 is not None else None, x=xh.data_ptr(),
+                              tlut=tl.data_ptr(), m=m, k=k, wscale=_wscale_arg(wscales, j, m), oscale=float(oscale), ldo=_ldo(out, n, m),
+                              accumulate=1 if accumulate else 0)
+        keep += [c1, c2, tl]
+    with torch.cuda.device_of(x):
+        rc = nat.lib().qpal_tcq_gemm_wide(cjobs, len(jobs), n, S, KV1, KV2, _stream(x))
+    nat.check(rc, "qpal_tcq_gemm_wide")
+    return list(outs)
+
+
 def lut_tc_gemv_multi(layers, x, bits, vec, outs=None, outs_zeroed=False, prezero=None, wscales=None, oscale=1.0,
                       x_rot=None, x_rms=None, accumulate=False, act_outs=None, act_su=None):
     """Several VQ/SQ (tensor-core packing) GEMVs of one codec and one input in ONE launch.
