@@ -463,6 +463,44 @@ int qpal_attn_rope_prefill_ragged_paged(const float *q, const float *k, const fl
                                         int kv_fmt, int R, int S, int B, int nq, int nkv, int hd,
                                         float scale, void *ws, long ws_bytes, void *stream);
 
+/* TREE-MASKED ragged prefill: the two ragged launches above with two more DEVICE tensors over the R rows, depth int32
+ * [R] and anc uint32 [R]: bit j of anc[row0[s] + t] says that row j of the same segment is an ancestor of row t, or row t itself.
+ * Per segment s of T_s <= 32 rows (a longer segment is inactive in this launch; every other activity rule, the guards, tickets,
+ * workspace layout and the split over the context are the ragged launch's), with d_t = clamp(depth, 0, t) and a_t = (anc & ((2u <<
+ * t) - 1)) | (1u << t) — no value in the two tensors leads outside the segment or leaves a row without a key:
+ *   row t is rotated at POSITION pos0[s] + d_t, query and key alike; its K / V row is stored at cache SLOT pos0[s] + t;
+ *   row t attends to every cache key below pos0[s] and to the in-segment keys whose bit is set in a_t.
+ * A chain (depth[t] = t, anc[t] = all bits 0 .. t) is bit for bit qpal_attn_rope_prefill_ragged[_paged], out and caches.  Cache row
+ * pos0 + t is bit for bit what the one-sequence launch writes for that k / v row at position pos0 + d_t.  Checks and codes are the
+ * ragged launches'; depth / anc: null QPAL_E_NULL, 4-byte aligned else QPAL_E_ALIGN.  Not combined with a window or score modifiers. */
+int qpal_attn_rope_prefill_ragged_tree(const float *q, const float *k, const float *v, long ld_qkv,
+                                       void *kcache, void *vcache, void *out_f16, long ld_out,
+                                       const int *seq, const int *row0, const long *pos0, const int *depth, const unsigned *anc,
+                                       const float *inv_freq, int kv_fmt /* 0 fp16, 1 e4m3fn */, int R, int S, int B, int nq, int nkv,
+                                       int hd, long max_len, float scale, void *ws, long ws_bytes, void *stream);
+int qpal_attn_rope_prefill_ragged_tree_paged(const float *q, const float *k, const float *v, long ld_qkv,
+                                             void *kpool, void *vpool, void *out_f16, long ld_out,
+                                             const int *seq, const int *row0, const long *pos0, const int *depth, const unsigned *anc,
+                                             const float *inv_freq, const int *block_table, long ld_table, int num_pages, int page_size,
+                                             int max_pages, int kv_fmt, int R, int S, int B, int nq, int nkv, int hd,
+                                             float scale, void *ws, long ws_bytes, void *stream);
+
+/* qpal_kv_compact (csrc/kv_compact.hip): behind qpal_spec_tree_accept the accepted node of depth k sits at cache
+ * slot pos0[b] + path[b][k], rotated for position pos0[b] + k.  ONE launch copies, for every slot b of B (1 .. 128), every kv head and
+ * every layer, the K and V rows from slot pos0[b] + path[b][k] to slot pos0[b] + k, k = 1 .. n_acc[b], where path[b][k] != k; a
+ * thread owns one 16-byte column of a row for all the slot's moves and loads every source before it stores any (a destination may be
+ * another move's source: path (0, 2, 3, 5) reads slot 2 for k = 1 and writes it for k = 2).  kptrs / vptrs: DEVICE
+ * arrays of `layers` device pointers, the layers' caches [B][nkv][max_len][hd] (block_table NULL; ld_table .. max_pages ignored) or
+ * pools with the block table int32 [B][ld_table] of the paged launches (max_len is then max_pages * page_size); kv_fmt 0 fp16, 1
+ * e4m3fn (a byte copy).  pos0 int64 [B], path int32 [B][16], n_acc int32 [B] are the tree draft's and accept's tensors: the host
+ * reads nothing.  Skipped, never an error: n_acc outside 0 .. 15, pos0 outside [0, max_len), path[k] outside (k, 32), a slot at or
+ * past max_len, a table entry outside [0, num_pages).  Every other cache byte keeps its value.  Codes: a null pointer QPAL_E_NULL
+ * (block_table may be NULL); layers outside 1 .. 65535, B outside 1 .. 128, nkv < 1, hd not 64 / 128 / 256, kv_fmt not 0 / 1, a bad
+ * paged shape or max_len: QPAL_E_SHAPE; kptrs / vptrs / pos0 8-byte, the int32 arrays 4-byte aligned, else QPAL_E_ALIGN. */
+int qpal_kv_compact(void *const *kptrs, void *const *vptrs, int layers, const long *pos0, const int *path, const int *n_acc,
+                    const int *block_table, long ld_table, int num_pages, int page_size, int max_pages, int kv_fmt, int B, int nkv,
+                    int hd, long max_len, void *stream);
+
 /* SLIDING-WINDOW attention: the three launches above — batched decode, one-sequence prefill, ragged prefill — with a
  * lower edge.  window = W >= 1: the row at position p attends to keys lo(p) .. p, lo(p) = max(0, p - W + 1): W keys with its own
  * (Hugging Face's sliding_window).  window = 0: no window, the launch IS the sibling's.  window < 0: QPAL_E_PARAM, behind the null
@@ -689,6 +727,36 @@ int qpal_spec_draft(const int *hist, long ld_hist, const long *n_tok, const long
                     int *row_slot, long *row_ctr, int *n_draft, void *stream);
 int qpal_spec_accept(const long *tokens, const long *drawn, const int *seq, const int *row0, int *hist, long ld_hist, long *n_tok,
                      long *limit, const long *eos, int B, int K, int R, long *out_tok, int *n_out, int *n_acc, void *stream);
+
+/* DRAFT TREES (csrc/spec.hip): the two ends of a step whose segments are trees.  State, activity rule and codes are
+ * the pair's above.  A segment's rows are the pending token (row 0, the root) and up to N <= 31 NODES, numbered 1 .. n in the
+ * caller's order.
+ *
+ * qpal_spec_tree_draft.  ext_tok != NULL: ext_tok int32 [B][N], ext_par int32 [B][N], ext_n int32 [B]; node i has token ext_tok[b][i -
+ * 1] and parent ext_par[b][i - 1] in [0, i) (0: the pending token), depth(i) = depth(parent) + 1, depth(0) = 0.  With n = n_tok[b]
+ * and d_max = max(0, min(15, limit - n - 1)) the list is nodes 1 .. min(ext_n[b], N) and ends in front of the first node with a
+ * token outside [0, 2^30), a parent outside [0, i), a depth above d_max, or a cache slot n - 1 + i >= max_len (a prefix of a
+ * topologically ordered list is a tree).  ext_tok == NULL: the chain of qpal_spec_draft's prompt lookup with K = min(N, 15) is the
+ * tree (parent(i) = i - 1).  Packing is qpal_spec_draft's: every active slot keeps its root row, nodes are handed out in slot order
+ * until R is full — slot b keeps clamp(R - (active slots) - (nodes of the slots before it), 0, its nodes), a prefix.  Outputs: those
+ * of qpal_spec_draft with row_ctr = pos0 + depth (a row's POSITION, qpal_sample's ctr), plus depth int32 [R] and anc uint32 [R], the
+ * two tensors of qpal_attn_rope_prefill_ragged_tree (anc: the row's own bit and those of its root path; unused rows: 0).  One launch
+ * with ext_tok, the search launch in front of it without.  Codes: as qpal_spec_draft, N outside 0 .. 31 QPAL_E_SHAPE; ext_tok given
+ * without ext_par or ext_n QPAL_E_NULL.
+ *
+ * qpal_spec_tree_accept takes drawn int64 [R] and tokens / seq / row0 / depth / anc as the draft call wrote them.  A segment counts
+ * iff seq[b] == b, it has T in 1 .. 32 rows inside [0, R] and 1 <= n_tok[b] < limit[b].  From cur = the root row: emit drawn[cur],
+ * then step to the LOWEST-indexed child of cur (a row j > cur with depth[j] == depth[cur] + 1 and bit cur of anc[j]) whose token
+ * equals it; stop where there is none, or at depth 15.  The cuts at limit and eos, the hist / n_tok / limit update, n_out and n_acc (=
+ * the depth reached, before the cuts) are qpal_spec_accept's; out_tok is int64 [B][16].  path int32 [B][16]: path[b][k] = the segment-
+ * local row of the accepted node of depth k (path[b][0] = 0), -1 for k > n_acc[b].  On a chain it is bit for bit qpal_spec_accept
+ * with K = 15. */
+int qpal_spec_tree_draft(const int *hist, long ld_hist, const long *n_tok, const long *limit, const int *ext_tok, const int *ext_par,
+                         const int *ext_n, int B, int N, int gmin, int gmax, int R, long max_len, long *tokens, int *seq, int *row0,
+                         long *pos0, int *row_slot, long *row_ctr, int *n_draft, int *depth, unsigned *anc, void *stream);
+int qpal_spec_tree_accept(const long *tokens, const long *drawn, const int *seq, const int *row0, const int *depth, const unsigned *anc,
+                          int *hist, long ld_hist, long *n_tok, long *limit, const long *eos, int B, int R, long *out_tok, int *n_out,
+                          int *n_acc, int *path, void *stream);
 
 /* LOGIT PROCESSORS (csrc/logit_proc.hip): token masks, a sparse logit bias and repetition / presence / frequency
  * penalties, applied to the logits between qpal_lm_head_logits and qpal_sample.  State of slot b of `slots` (1 .. 128), all on the

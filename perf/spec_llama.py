@@ -15,6 +15,12 @@ those with draft M replaced by another token — exactly M drafts are accepted (
 The state is put back in front of every replay, so every replay is the same step.
 
     python perf/spec_llama.py [--model 3_8b] [--batch 1 4 8] [--draft 2 4 7] [--accept M] [--context 1024] [--replays 32] [--out F]
+
+--tree N [N ...] --width W [W ...] --right J [J ...]: the TREE step, SpeculativeStep(tree=N), against the chain step of the same row
+count min(128, B (N + 1)) in the same call.  A sequential pre-run yields each slot's next tokens; the tree has N // W levels (at most
+15) of W siblings under the previous level's sibling J, and sibling J (1-based; 0: none) carries the pre-run's token of its level.
+The chain step is fed the pre-run's tokens themselves (every draft accepted).  --repeats times, alternating: chain, tree, chain, ...;
+per step the list of ms per replay, and n_out / n_acc of the last replay.
 """
 import argparse
 import json
@@ -27,6 +33,40 @@ import torch
 
 import qpalette_amd as qp
 from decode_llama import build_model, time_graph
+
+
+def tree_against_chain(args, m, kc, vc, hist, B, N, W, J, n0, dev, ms_decode):
+    """one (B, N, W, J) of --tree: the chain step and the tree step at the same row count, timed alternately"""
+    K = min(15, N)
+    D, R = min(15, N // W), min(128, B * (N + 1))
+    model = (m.layers, m.embed, m.norm, m.lm_head, kc, vc, m.inv_freq)
+    chain, tree = qp.SpeculativeStep(*model, draft=K, rows=R), qp.SpeculativeStep(*model, tree=N, rows=R)
+    for ss in (chain, tree):
+        for b in range(B):
+            ss.begin(b, hist[b].tolist())
+    start = tree.n_tok.clone()
+    for _ in range(K):  # the sequential pre-run (a random model repeats nothing: prompt lookup proposes nothing, one token per step)
+        tree()
+    nxt = tree.hist[:, n0:n0 + K].to(torch.int64).contiguous()
+    ext_n = torch.full((B,), K, dtype=torch.int32, device=dev)
+    tok, par = torch.zeros(B, N, dtype=torch.int32, device=dev), torch.zeros(B, N, dtype=torch.int32, device=dev)
+    for l in range(D):  # level l: W siblings under the previous level's sibling J (none right: the first)
+        for w in range(W):
+            tok[:, l * W + w] = nxt[:, l] if w == J - 1 else (nxt[:, l] + 1 + w) % args.vocab
+            par[:, l * W + w] = 0 if l == 0 else (l - 1) * W + max(J, 1)
+    tree_n = torch.full((B,), D * W, dtype=torch.int32, device=dev)
+    steps = {"chain": (chain, lambda: chain(nxt, ext_n)), "tree": (tree, lambda: tree(ext_tok=tok, ext_par=par, ext_n=tree_n))}
+    ms = {"chain": [], "tree": []}
+    for _ in range(args.repeats):
+        for name, (ss, fn) in steps.items():
+            ss.n_tok.copy_(start)
+            ms[name].append(time_graph(fn, args.replays, dev, lambda i, ss=ss: ss.n_tok.copy_(start)))
+    res = {"batch": B, "tree": N, "width": W, "right": J, "levels": D, "rows": R, "ms_chain": ms["chain"], "ms_tree": ms["tree"],
+           "ms_decode": ms_decode, "tree_over_chain": min(ms["tree"]) / min(ms["chain"]),
+           "chain_spread": (max(ms["chain"]) - min(ms["chain"])) / min(ms["chain"])}
+    for name, (ss, _) in steps.items():
+        res[f"n_out_{name}"], res[f"n_acc_{name}"] = ss.n_out.double().mean().item(), ss.n_acc.double().mean().item()
+    return res
 
 
 def main(argv=None, quiet=False):
@@ -43,6 +83,10 @@ def main(argv=None, quiet=False):
     ap.add_argument("--context", type=int, default=1024)
     ap.add_argument("--replays", type=int, default=32)
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--tree", type=int, nargs="+", default=None, metavar="N", help="time the tree step of N nodes per slot against the chain step")
+    ap.add_argument("--width", type=int, nargs="+", default=[2], help="--tree: siblings per level")
+    ap.add_argument("--right", type=int, nargs="+", default=[1], help="--tree: the sibling (1-based) that carries the sequential token; 0: none")
+    ap.add_argument("--repeats", type=int, default=3, help="--tree: alternating repeats of (chain, tree)")
     ap.add_argument("--out", default=None, help="also write the JSON result to this file")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -69,7 +113,11 @@ def main(argv=None, quiet=False):
             ds = qp.DecodeStep(m.layers, m.embed, m.norm, m.lm_head, kc, vc, m.inv_freq, tok, pos, out_tok, generic=True)
             ms_generic = time_graph(ds, args.replays, dev)
             del ds
-        for K in args.draft:
+        for N, W, J in ((N, W, J) for N in args.tree or [] for W in args.width for J in args.right if J <= W):
+            results.append(tree_against_chain(args, m, kc, vc, hist, B, N, W, J, n0, dev, ms_decode))
+            if not quiet:
+                print(json.dumps(results[-1]), file=sys.stderr, flush=True)
+        for K in ([] if args.tree else args.draft):
             ss = qp.SpeculativeStep(m.layers, m.embed, m.norm, m.lm_head, kc, vc, m.inv_freq, draft=K)
             for b in range(B):
                 ss.begin(b, hist[b].tolist())

@@ -17,6 +17,8 @@ Layout:
                    sequences in one launch (segments described on the device);
                    window= on all of these but the shared-prefix launch: sliding-window attention; window_floor: its lower edge
                    softcap= / sinks= on the same launches: the logit soft cap and per-head sinks
+                   tree= on both ragged launches (draft trees: a row attends to its root path) and kv_compact (csrc/kv_compact.hip:
+                   the accepted path's K / V rows moved to consecutive slots in every layer, one launch): DESIGN.md §40
   paging.py        PagedKVCache: per-layer page pools, the block table and the host-side page allocator (reserve / release / fork /
                    trim: the pages a sliding window has passed go back to the pool);
                    SharedPrefix (cache.prefix): the groups of slots that share a forked prefix, as the shared-prefix launch reads them
@@ -25,8 +27,10 @@ Layout:
                    Score: the log-probability of every next token of a sequence, nll and perplexity;
                    RaggedStep: prompt chunks and decode tokens of several slots in ONE 128-row step;
                    SpeculativeStep: the pending token + guessed tokens of every slot in one step, several tokens out per slot
+                   (tree=N: draft trees of up to N nodes per slot)
   speculative.py   spec_draft / spec_accept (csrc/spec.hip): prompt-lookup drafts and the packing of a verify step, exact-match
                    acceptance and the state update, all on the device; reference_spec_draft / reference_spec_accept: the contracts
+                   spec_tree_draft / spec_tree_accept, reference_spec_tree_draft / reference_spec_tree_accept: the same for draft trees
   sampling.py      lm_head_logits (final norm + lm_head for up to 128 rows), sample / Sampler (temperature, top-k, top-p, seeded
                    draw; per-slot parameters on the device; with min_p / top_a / typical_p the truncating draw of csrc/sample.hip),
                    reference_draw (the draw's contract in numpy fp64) and truncation_mask (the set the three filters keep);
@@ -115,6 +119,8 @@ from . import decoder  # noqa: F401
 from .decoder import DecodeStep, Prefill, RaggedStep, Score, SpeculativeStep, perplexity  # noqa: F401
 from . import speculative  # noqa: F401
 from .speculative import reference_spec_accept, reference_spec_draft, spec_accept, spec_draft  # noqa: F401
+from .speculative import reference_spec_tree_accept, reference_spec_tree_draft, spec_tree_accept, spec_tree_draft  # noqa: F401
+from .attention import kv_compact, kv_pointer_table  # noqa: F401
 from .quantize_layer import incoherent_preprocess, layer_file_path, load_hessian, quantize_linear  # noqa: F401
 from . import calibrate  # noqa: F401
 from .calibrate import (  # noqa: F401

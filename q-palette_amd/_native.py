@@ -125,6 +125,14 @@ _SIGNATURES = {
     "qpal_top_logprob": [_P, ctypes.c_long, _I, _I, _I, _P, _P, _P, _P, _P],
     "qpal_spec_draft": [_P, ctypes.c_long, _P, _P, _P, _P, _I, _I, _I, _I, _I, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P],
     "qpal_spec_accept": [_P, _P, _P, _P, _P, ctypes.c_long, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "qpal_spec_tree_draft": [_P, ctypes.c_long, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                             _P],
+    "qpal_spec_tree_accept": [_P, _P, _P, _P, _P, _P, _P, ctypes.c_long, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
+    "qpal_attn_rope_prefill_ragged_tree": [_P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I,
+                                           _I, _I, _I, ctypes.c_long, _F, _P, ctypes.c_long, _P],
+    "qpal_attn_rope_prefill_ragged_tree_paged": [_P, _P, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _P, _P, _P, _P, _P, _P,
+                                                 ctypes.c_long, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, ctypes.c_long, _P],
+    "qpal_kv_compact": [_P, _P, _I, _P, _P, _P, _P, ctypes.c_long, _I, _I, _I, _I, _I, _I, _I, ctypes.c_long, _P],
     "qpal_logit_process": [_P, ctypes.c_long, _P, ctypes.c_long, _I, _I, _P, _P, _I, _P, ctypes.c_long, _P, _P, _P, _P, ctypes.c_long, _P,
                            _P, _P, _P, _I, _P, _P, _P],
     "qpal_logit_observe": [_P, ctypes.c_long, _I, _I, _P, _I, _P, _P, _I, _P],

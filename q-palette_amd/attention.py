@@ -499,11 +499,23 @@ def _segments(who, seq, row0, pos0, dev):
 
 
 def _ragged(who, entry, q, k, v, kcache, vcache, seq, row0, pos0, S, inv_freq, scale, out, ws, B, nkv, max_len, hd, head, tail,
-            window=None, mods=(None, None)):
+            window=None, mods=(None, None), tree=None):
     """the checks (behind _segments, which gave S) and the launch both ragged entry points share; head / tail: the arguments in
     front of and behind (R, S, B, nq, nkv, hd); window: None, or the W of the _window entry point, which then takes `entry`'s place
-    (tail empty: a paged launch, head its paged arguments); mods: (softcap, sinks) — with either, the _score entry point takes it"""
+    (tail empty: a paged launch, head its paged arguments); mods: (softcap, sinks) — with either, the _score entry point takes it;
+    tree: None, or (depth, anc) — the _tree entry points, not with a window or score modifiers"""
     R, nq, ld, out, ld_out = _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd)
+    rows = ()
+    if tree is not None:
+        if len(tree) != 2:
+            raise QpalError(f"{who}: tree must be the pair (depth, anc)")
+        if window is not None or mods[0] is not None or mods[1] is not None:
+            raise NotImplementedError(f"{who}: tree= is not combined with window=, softcap= or sinks=")
+        for name, t in zip(("depth", "anc"), tree):
+            if t.dtype != torch.int32 or t.shape != (R,) or not t.is_contiguous() or t.device != kcache.device:
+                raise QpalError(f"{who}: tree {name} must be a contiguous int32 [{R}] tensor on {kcache.device}")
+        entry = entry.replace("_ragged", "_ragged_tree")
+        rows = (tree[0].data_ptr(), tree[1].data_ptr())
     score = None if mods[0] is None and mods[1] is None else _score_args(who, mods, nq, kcache.device)  # (before the library)
     lib = _native.lib()
     ws_ptr, ws_bytes = _launch_ws(who, lib.qpal_attn_ragged_ws_bytes(R, S, nq, nkv, hd, max_len), ws, kcache, "ragged_workspace")
@@ -520,14 +532,14 @@ def _ragged(who, entry, q, k, v, kcache, vcache, seq, row0, pos0, S, inv_freq, s
     with torch.cuda.device(kcache.device):
         rc = getattr(lib, entry)(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
-            seq.data_ptr(), row0.data_ptr(), pos0.data_ptr(), inv_freq.data_ptr(), *shape,
+            seq.data_ptr(), row0.data_ptr(), pos0.data_ptr(), *rows, inv_freq.data_ptr(), *shape,
             ws_ptr, ws_bytes, torch.cuda.current_stream(kcache.device).cuda_stream)
     _native.check(rc, entry)
     return out
 
 
 def ragged_prefill_attention(q, k, v, kcache, vcache, seq, row0, pos0, inv_freq, scale=None, out=None, ws=None, window=None,
-                             softcap=None, sinks=None):
+                             softcap=None, sinks=None, tree=None):
     """prefill_attention for rows of SEVERAL sequences in one launch (``qpal_attn_rope_prefill_ragged``).  q fp32 [R,
     nq*hd], k / v fp32 [R, nkv*hd], 1 <= R <= 128 (strided rows as for prefill_attention); kcache / vcache [B, nkv, max_len, hd],
     fp16 or float8_e4m3fn, contiguous, 16-byte aligned.  The rows are cut into S <= 128 segments described ON THE DEVICE (never read
@@ -543,7 +555,13 @@ def ragged_prefill_attention(q, k, v, kcache, vcache, seq, row0, pos0, inv_freq,
     window=W: per segment prefill_attention's window (qpal_attn_rope_prefill_ragged_window): bit for bit the one-sequence windowed
     launch wherever the unwindowed pair is; rows below window_floor(pos0[s], W) of a segment's sequence are not read.
 
-    softcap=c / sinks=t (qpal_attn_rope_prefill_ragged_score): per segment prefill_attention's, bit for bit that launch's."""
+    softcap=c / sinks=t (qpal_attn_rope_prefill_ragged_score): per segment prefill_attention's, bit for bit that launch's.
+
+    tree=(depth, anc), int32 [R] each (qpal_attn_rope_prefill_ragged_tree): every segment is a draft tree of at most 32
+    rows (a longer one is inactive).  Row t is rotated at position pos0[s] + clamp(depth, 0, t), stored at cache slot pos0[s] + t, and
+    attends to the cache below pos0[s] and to the rows of its segment whose bit is set in its anc word (its own always is; bits
+    above t are ignored).  depth[t] = t with anc[t] = all bits 0 .. t is bit for bit the launch without tree=.  Not with window=,
+    softcap= or sinks= (NotImplementedError)."""
     who = "ragged_prefill_attention"
     window, mods = _window(window, who), _score_mods(softcap, sinks, who)
     if kcache.dim() != 4 or kcache.shape != vcache.shape:
@@ -552,20 +570,53 @@ def ragged_prefill_attention(q, k, v, kcache, vcache, seq, row0, pos0, inv_freq,
     S = _segments(who, seq, row0, pos0, kcache.device)  # (first: these checks need no device)
     _cache_entry(kcache, vcache, who)
     return _ragged(who, "qpal_attn_rope_prefill_ragged", q, k, v, kcache, vcache, seq, row0, pos0, S, inv_freq, scale, out, ws, B,
-                   nkv, max_len, hd, (_KV_FMT[kcache.dtype],), (max_len,), window=window, mods=mods)
+                   nkv, max_len, hd, (_KV_FMT[kcache.dtype],), (max_len,), window=window, mods=mods, tree=tree)
 
 
 def paged_ragged_prefill_attention(q, k, v, kpool, vpool, block_table, seq, row0, pos0, inv_freq, scale=None, out=None, ws=None,
-                                   window=None, softcap=None, sinks=None):
+                                   window=None, softcap=None, sinks=None, tree=None):
     """ragged_prefill_attention on a paged cache (``qpal_attn_rope_prefill_ragged_paged``): the pools and the block table int32 [B,
     max_pages] of paged_decode_attention; segment s uses row seq[s] of the table.  Every rule is ragged_prefill_attention's with
     max_len = max_pages * page_size (ws: ragged_workspace of that max_len); bit for bit that launch's result on the gathered cache.
     Only entries that cover positions 0 .. pos0[s] + rows - 1 of an active segment are read; the guard on entries outside [0,
     num_pages) is paged_decode_attention's.  window=W: ragged_prefill_attention's window; entries of pages wholly below a segment's
-    window_floor(pos0[s], W) may be -1.  softcap / sinks: ragged_prefill_attention's."""
+    window_floor(pos0[s], W) may be -1.  softcap / sinks / tree: ragged_prefill_attention's (qpal_attn_rope_prefill_ragged_tree_paged)."""
     who = "paged_ragged_prefill_attention"
     window, mods = _window(window, who), _score_mods(softcap, sinks, who)
     S = _segments(who, seq, row0, pos0, kpool.device)
     B, nkv, max_len, hd, head = _pools_2d(kpool, vpool, block_table, who)
     return _ragged(who, "qpal_attn_rope_prefill_ragged_paged", q, k, v, kpool, vpool, seq, row0, pos0, S, inv_freq, scale, out, ws, B,
-                   nkv, max_len, hd, head, (), window=window, mods=mods)
+                   nkv, max_len, hd, head, (), window=window, mods=mods, tree=tree)
+
+
+def kv_pointer_table(caches):
+    """int64 [L] on the device: the data pointers of the L layers' K (or V) caches or pools — kv_compact's kptrs / vptrs, built once"""
+    return torch.tensor([c.data_ptr() for c in caches], dtype=torch.int64, device=caches[0].device)
+
+
+def kv_compact(kptrs, vptrs, kcache, pos0, path, n_acc, block_table=None):
+    """Behind speculative.spec_tree_accept (``qpal_kv_compact``): in EVERY layer's caches, for every slot b and kv
+    head, the K and V rows at cache slots pos0[b] + path[b, k] move to slots pos0[b] + k, k = 1 .. n_acc[b] — the accepted root path
+    becomes the consecutive run sequential decoding would have written.  kptrs / vptrs: kv_pointer_table of the layers' caches
+    (all shaped and typed as `kcache`, one of them: [B, nkv, max_len, hd], or a pool with block_table int32 [B, max_pages]); pos0 int64
+    [B], path int32 [B, 16], n_acc int32 [B] as the draft and the accept wrote them.  One launch on the current stream for all
+    layers; the host reads nothing."""
+    who = "kv_compact"
+    dev = kcache.device
+    if block_table is None:
+        if kcache.dim() != 4:
+            raise QpalError(f"{who}: kcache must have shape [B, nkv, max_len, hd]")
+        B, nkv, max_len, hd = kcache.shape
+        _cache_entry(kcache, kcache, who)
+        paged = (None, 0, 0, 0, 0, _KV_FMT[kcache.dtype])
+    else:
+        B, nkv, max_len, hd, paged = _pools_2d(kcache, kcache, block_table, who)
+    L = kptrs.shape[0]
+    for name, t, dtype, shape in (("kptrs", kptrs, torch.int64, (L,)), ("vptrs", vptrs, torch.int64, (L,)), ("pos0", pos0, torch.int64, (B,)),
+                                  ("path", path, torch.int32, (B, 16)), ("n_acc", n_acc, torch.int32, (B,))):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise QpalError(f"{who}: {name} must be a contiguous {dtype} {list(shape)} tensor on {dev}")
+    with torch.cuda.device(dev):
+        rc = _native.lib().qpal_kv_compact(kptrs.data_ptr(), vptrs.data_ptr(), L, pos0.data_ptr(), path.data_ptr(), n_acc.data_ptr(),
+                                           *paged, B, nkv, hd, max_len, torch.cuda.current_stream(dev).cuda_stream)
+    _native.check(rc, "qpal_kv_compact")

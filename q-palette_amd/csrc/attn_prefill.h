@@ -55,6 +55,10 @@ struct AttnRaggedParams : AttnPrefillParams<CT> {
     const int *seq, *row0;  // int32 [S], [S + 1], device
     int S, B;
     long ld_table;
+    // TREE only (the _tree entry points): int32 / uint32 [R], device — a row's depth below its segment's first row
+    // and the bit set of its ancestors among the segment's rows, itself included
+    const int *depth;
+    const unsigned *anc;
 };
 
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
@@ -107,11 +111,21 @@ __device__ __forceinline__ u32x4 rope_chunk(const float *src, int ch, long pos, 
 // one-chunk row, or in the last arriver's merge — as one more term exp(sink - M) of the denominator, M = max(row maximum, sink).
 // The running (m, l, O) and the partials in the workspace stay those of the keys alone.  Both are wave-uniform runtime tests; a
 // sink of -inf leaves M, a rescale of exp(0) = 1 and a term of 0: the bits without sinks.
-template <class CT, bool PAGED, bool RAGGED, int HD, int REP, bool WIN = false, bool SC = false>
+//
+// TREE (draft trees; RAGGED only, not with WIN / SC): a segment of T <= 32 rows is a tree whose row t has depth d_t
+// = clamp(depth, 0, t) and ancestor set a_t = (anc & ((2u << t) - 1)) | (1u << t).  Row t is rotated — query and key — at POSITION
+// pos0 + d_t, its K / V row is stored at SLOT pos0 + t, and it attends to the cache below pos0 and to the in-segment keys of a_t.
+// The mask is one 64-bit word per lane (a_t of the lane's query row, one bit up; bit 0: the cache) and one shift per key; the
+// clamped depths of the segment wait in LDS for the fetches.
+// Ancestors have lower indices, so keys past a tile's last row still lie past every row of it: chunks, tickets and merge are
+// untouched.  A chain (d_t = t, a_t = all bits 0 .. t) admits n <= qpos and rotates at n: the bits of the launch without TREE.
+template <class CT, bool PAGED, bool RAGGED, int HD, int REP, bool WIN = false, bool SC = false, bool TREE = false>
 __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
     const std::conditional_t<RAGGED, AttnRaggedParams<CT>, AttnPrefillParams<CT>> p) {
     constexpr bool KV8 = kIsKv8<CT>;
     static_assert(!SC || WIN, "the score modifiers are built on the windowed body");
+    static_assert(!TREE || (RAGGED && !WIN), "draft trees are segments of a ragged launch without a window");
+    constexpr int kTreeRows = 32;  // TREE: a segment's rows, the bits of an ancestor word
     using KR = std::conditional_t<KV8, u32x2, u32x4>;  // eight elements of a cache row as prefetched
     constexpr int QS = pf_qs(REP), NW = REP * QS, NT = 64 * NW, TQ = 16 * QS, R = 16 * NW;
     constexpr int HALF = HD / 2, KC = HD / 32, DT = HD / 16, CPR = HD / 8;
@@ -151,7 +165,8 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
             if (tid < p.S) {
                 const int r0 = p.row0[tid], r1 = p.row0[tid + 1], b = p.seq[tid];
                 const long ps = p.pos0[tid];
-                if (r0 >= 0 && r1 > r0 && r1 <= p.T && (unsigned)b < (unsigned)p.B && ps >= 0 && ps <= p.max_len - (r1 - r0))
+                if (r0 >= 0 && r1 > r0 && r1 <= p.T && (unsigned)b < (unsigned)p.B && ps >= 0 && ps <= p.max_len - (r1 - r0) &&
+                    (!TREE || r1 - r0 <= kTreeRows))
                     n = (r1 - r0 + TQ - 1) / TQ;
             }
             seg_tiles[tid] = n;
@@ -200,6 +215,23 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
     const int head = kh * REP + hh;
     const int trow = t0 + qsub * 16 + mi;  // this lane's query row (a column of S^T)
     const pos_t qpos = pos0 + trow;
+    // TREE: the in-segment keys this lane's query row admits, and the segment's clamped depths
+    // (as a 64-bit word one bit up: bit 0 stands for every cache key, bit 1 + j for row j, bit 33 for the keys past the word)
+    [[maybe_unused]] unsigned long long amask = 1ull;
+    [[maybe_unused]] int key_rel = 0;  // the lane's first key of a tile at kt0 = 0, counted from pos0 (per lane: pos0 stays out of the loop)
+    [[maybe_unused]] __shared__ int seg_depth[TREE ? kTreeRows : 1];
+    if constexpr (TREE) {
+        key_rel = 4 * mq - kPfKT - (int)pos0;
+        // (rows >= T of the tile take row T - 1's word, by a minimum: a `trow < T` test here would keep its lane mask alive in two
+        // SGPRs until the output store, which the paged hd 256 instantiations cannot spare)
+        const int tr = trow < T - 1 ? trow : T - 1;
+        amask = ((unsigned long long)((p.anc[row_base + tr] & ((2u << tr) - 1u)) | (1u << tr)) << 1) | 1ull;
+        if (tid < kTreeRows) {
+            const int d = tid < T ? p.depth[row_base + tid] : 0;
+            seg_depth[tid] = d < 0 ? 0 : (d > tid ? tid : d);
+        }
+        __syncthreads();
+    }
     [[maybe_unused]] pos_t qlo = 0;  // WIN: lo(qpos)
     if constexpr (WIN) qlo = (long)qpos >= p.window ? (pos_t)((long)qpos - p.window + 1) : (pos_t)0;
     long kvoff;
@@ -240,7 +272,7 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
         uint16_t r1 = 0, r2 = 0;
         if (t < T) {
             const float *src = qrows + (long)t * p.ld_qkv + (long)head * HD;
-            const float ang = (float)(pos0 + t) * p.inv_freq[i];
+            const float ang = (float)(pos0 + (TREE ? seg_depth[t] : t)) * p.inv_freq[i];
             const _Float16 c = (_Float16)cosf(ang), s = (_Float16)sinf(ang);
             const _Float16 x1 = (_Float16)src[i], x2 = (_Float16)src[i + HALF];
             const _Float16 o1 = x1 * c + (-x2) * s, o2 = x2 * c + x1 * s;
@@ -280,7 +312,7 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
                         h16 = u32x4{(uint32_t)h[0] | (uint32_t)h[1] << 16, (uint32_t)h[2] | (uint32_t)h[3] << 16,
                                     (uint32_t)h[4] | (uint32_t)h[5] << 16, (uint32_t)h[6] | (uint32_t)h[7] << 16};
                     } else {
-                        h16 = rope_chunk<HD>(krows + (long)tn * p.ld_qkv + (long)kh * HD, ch, n, p.inv_freq);
+                        h16 = rope_chunk<HD>(krows + (long)tn * p.ld_qkv + (long)kh * HD, ch, TREE ? pos0 + seg_depth[tn] : n, p.inv_freq);
                     }
                     val = e4m3_pack8(h16);  // quantised once: these bytes reach the cache and, converted back, the LDS image
                     {
@@ -297,7 +329,7 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
                         val = u32x4{(uint32_t)h[0] | (uint32_t)h[1] << 16, (uint32_t)h[2] | (uint32_t)h[3] << 16,
                                     (uint32_t)h[4] | (uint32_t)h[5] << 16, (uint32_t)h[6] | (uint32_t)h[7] << 16};
                     } else {
-                        val = rope_chunk<HD>(krows + (long)tn * p.ld_qkv + (long)kh * HD, ch, n, p.inv_freq);
+                        val = rope_chunk<HD>(krows + (long)tn * p.ld_qkv + (long)kh * HD, ch, TREE ? pos0 + seg_depth[tn] : n, p.inv_freq);
                     }
                     {
                         const long noff = row_off(n, rr, st_ok);
@@ -352,6 +384,10 @@ __global__ __launch_bounds__(64 * REP * pf_qs(REP)) void attn_prefill_kernel(
                     const pos_t n = kt0 - kPfKT + 16 * kt + 4 * mq + r;
                     ok[4 * kt + r] = n <= qpos;  // causal (keys past the tile's last row lie past every row of it)
                     if constexpr (WIN) ok[4 * kt + r] = n <= qpos && n >= qlo;  // and the row's own lower edge
+                    if constexpr (TREE) {  // the cache, and the row's root path: ONE shift of the lane's word by the key's index
+                        const int rel = (int)kt0 + 16 * kt + r + key_rel;  // n - pos0, clamped to [-1, 32]: a tile's keys may reach 62 past pos0
+                        ok[4 * kt + r] = ((amask >> ((rel < -1 ? -1 : (rel > kTreeRows ? kTreeRows : rel)) + 1)) & 1ull) != 0ull;
+                    }
                     sv[4 * kt + r] = s[kt][r] * p.scale;
                     if constexpr (!SC) {
                         if (ok[4 * kt + r]) mx = fmaxf(mx, sv[4 * kt + r]);

@@ -32,12 +32,18 @@ int ragged_geometry(int R, int S, int nq, int nkv, int hd, long max_len, Prefill
     return QPAL_OK;
 }
 
+// the two per-row tensors of a TREE launch
+struct TreeArgs {
+    const int *depth;
+    const unsigned *anc;
+};
+
 // mods: SC — the soft cap and the sinks; a launch without a window runs the windowed body with window = max_len
-template <class CT, bool PAGED, bool WIN = false, bool SC = false>
+template <class CT, bool PAGED, bool WIN = false, bool SC = false, bool TREE = false>
 int attn_rope_ragged(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16, long ld_out,
                      const int *seq, const int *row0, const long *pos0, const float *inv_freq, int R, int S, int B, int nq, int nkv, int hd,
                      long max_len, float scale, void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0,
-                     long window = 0, const ScoreMods *mods = nullptr) {
+                     long window = 0, const ScoreMods *mods = nullptr, const TreeArgs *tree = nullptr) {
     if constexpr (SC) {
         if (window == 0) window = max_len;
     }
@@ -49,6 +55,9 @@ int attn_rope_ragged(const float *q, const float *k, const float *v, long ld_qkv
                    (PAGED ? reinterpret_cast<uintptr_t>(pg->table) : 0) | (SC ? reinterpret_cast<uintptr_t>(mods->sinks) : 0));
     if (rc != QPAL_OK) return rc;
     if ((reinterpret_cast<uintptr_t>(seq) | reinterpret_cast<uintptr_t>(row0)) & 3) return QPAL_E_ALIGN;
+    if constexpr (TREE) {
+        if ((reinterpret_cast<uintptr_t>(tree->depth) | reinterpret_cast<uintptr_t>(tree->anc)) & 3) return QPAL_E_ALIGN;
+    }
     float *wsf = static_cast<float *>(ws);
     AttnRaggedParams<CT> p{};
     static_cast<AttnPrefillParams<CT> &>(p) = AttnPrefillParams<CT>{
@@ -59,9 +68,10 @@ int attn_rope_ragged(const float *q, const float *k, const float *v, long ld_qkv
     if constexpr (PAGED) p.table = pg->table, p.num_pages = pg->num_pages, p.page_shift = shift, p.ld_table = pg->ld_table;
     if constexpr (WIN) p.window = window;
     if constexpr (SC) p.softcap = mods->softcap, p.inv_softcap = mods->softcap != 0.f ? 1.f / mods->softcap : 0.f, p.sinks = mods->sinks;
+    if constexpr (TREE) p.depth = tree->depth, p.anc = tree->anc;
     const int grid = nkv * g.ntile * g.nsplit, rep = nq / nkv;
     return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
-        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, true, HD(), REP(), WIN, SC>), dim3(grid), dim3(64 * REP() * pf_qs(REP())), 0,
+        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, true, HD(), REP(), WIN, SC, TREE>), dim3(grid), dim3(64 * REP() * pf_qs(REP())), 0,
                            static_cast<hipStream_t>(stream), p);
         return (int)hipGetLastError();
     });
@@ -101,6 +111,39 @@ extern "C" int qpal_attn_rope_prefill_ragged_paged(const float *q, const float *
     return paged_entry(any_null, pg, kv_fmt, [&](auto ct, int shift, long max_len) {
         return attn_rope_ragged<decltype(ct), true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B, nq, nkv,
                                                     hd, max_len, scale, ws, ws_bytes, stream, &pg, shift);
+    });
+}
+
+// Draft trees: the two launches above with depth int32 [R] and anc uint32 [R] behind pos0
+extern "C" int qpal_attn_rope_prefill_ragged_tree(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache,
+                                                  void *out_f16, long ld_out, const int *seq, const int *row0, const long *pos0,
+                                                  const int *depth, const unsigned *anc, const float *inv_freq, int kv_fmt, int R, int S,
+                                                  int B, int nq, int nkv, int hd, long max_len, float scale, void *ws, long ws_bytes,
+                                                  void *stream) {
+    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !seq || !row0 || !pos0 || !depth || !anc || !inv_freq) return QPAL_E_NULL;
+    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
+    const TreeArgs tree{depth, anc};
+    return for_kv_fmt(kv_fmt, [&](auto ct) {
+        return attn_rope_ragged<decltype(ct), false, false, false, true>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, seq, row0, pos0,
+                                                                         inv_freq, R, S, B, nq, nkv, hd, max_len, scale, ws, ws_bytes, stream,
+                                                                         nullptr, 0, 0, nullptr, &tree);
+    });
+}
+
+extern "C" int qpal_attn_rope_prefill_ragged_tree_paged(const float *q, const float *k, const float *v, long ld_qkv, void *kpool,
+                                                        void *vpool, void *out_f16, long ld_out, const int *seq, const int *row0,
+                                                        const long *pos0, const int *depth, const unsigned *anc, const float *inv_freq,
+                                                        const int *block_table, long ld_table, int num_pages, int page_size, int max_pages,
+                                                        int kv_fmt, int R, int S, int B, int nq, int nkv, int hd, float scale, void *ws,
+                                                        long ws_bytes, void *stream) {
+    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
+    const bool any_null =
+        !block_table || !q || !k || !v || !kpool || !vpool || !out_f16 || !seq || !row0 || !pos0 || !depth || !anc || !inv_freq;
+    const TreeArgs tree{depth, anc};
+    return paged_entry(any_null, pg, kv_fmt, [&](auto ct, int shift, long max_len) {
+        return attn_rope_ragged<decltype(ct), true, false, false, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, seq, row0, pos0,
+                                                                        inv_freq, R, S, B, nq, nkv, hd, max_len, scale, ws, ws_bytes, stream,
+                                                                        &pg, shift, 0, nullptr, &tree);
     });
 }
 

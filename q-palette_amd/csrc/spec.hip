@@ -234,6 +234,175 @@ __global__ __launch_bounds__(kSpecMaxSlots) void spec_accept_kernel(const SpecAc
     p.n_acc[b] = m;
 }
 
+// ---- draft TREES: qpal_spec_tree_draft / qpal_spec_tree_accept.  A segment's rows are the pending token (row 0)
+// and up to N <= 31 nodes in the caller's order, node i with a parent in [0, i); a row carries its depth and the bit set of its
+// root path, which is all the verify launch and the accept need of the tree.
+//   spec_search_kernel      unchanged, with K = min(N, 15): without ext_tok the chain of the prompt lookup is the tree
+//   spec_tree_pack_kernel   one workgroup, one thread per slot: the slot's node list is validated serially (<= 31 nodes, the depths
+//                           in LDS), then spec_pack_kernel's scans and cut, and every output array
+//   spec_tree_accept_kernel one workgroup, one thread per slot: the walk from the root over <= 15 levels of <= 31 rows
+constexpr int kSpecMaxNodes = 31, kSpecTreeRows = kSpecMaxNodes + 1;
+
+struct SpecTreeDraftParams {
+    SpecDraftParams d;  // K = min(N, 15); ext_draft unused
+    const int *ext_tok, *ext_par;
+    int N;
+    int *depth;
+    unsigned *anc;
+};
+
+__global__ __launch_bounds__(kSpecMaxSlots) void spec_tree_pack_kernel(const SpecTreeDraftParams q) {
+    __shared__ int sc_act[kSpecMaxSlots], sc_d[kSpecMaxSlots];
+    __shared__ unsigned char dep[kSpecMaxSlots][kSpecTreeRows];  // [slot][row]: the depth of a valid node (row 0: the root)
+    const SpecDraftParams &p = q.d;
+    const int t = threadIdx.x, B = p.B, R = p.R;
+    long n = 0;
+    bool act = false;
+    int d = 0;
+    long src = 0;
+    const int *etok = nullptr, *epar = nullptr;
+    if (t < B) {
+        n = p.n_tok[t];
+        act = spec_active(n, p.limit[t], p.max_len, p.ld_hist);
+        if (q.ext_tok) {
+            etok = q.ext_tok + (long)t * q.N, epar = q.ext_par + (long)t * q.N;
+            if (act) {
+                long dm = p.limit[t] - n - 1;
+                const int d_max = (int)(dm < 0 ? 0 : (dm > kSpecMaxDraft ? kSpecMaxDraft : dm));
+                int en = p.ext_n[t];
+                en = en < 0 ? 0 : (en > q.N ? q.N : en);
+                dep[t][0] = 0;
+                // the list ends at the first node with a token outside [0, 2^30), a parent outside [0, i), a depth above d_max or a
+                // slot n - 1 + i at or past max_len; a prefix of a topologically ordered list is a tree
+                while (d < en) {
+                    const int i = d + 1, tok = etok[d], par = epar[d];
+                    if (tok < 0 || tok >= (1 << 30) || par < 0 || par >= i || n - 1 + i >= p.max_len) break;
+                    const int dd = dep[t][par] + 1;
+                    if (dd > d_max) break;
+                    dep[t][i] = (unsigned char)dd;
+                    d = i;
+                }
+            }
+        } else {
+            d = act ? p.n_draft[t] : 0;
+            d = d < 0 ? 0 : (d > p.K ? p.K : d);
+            src = p.pos0[t];
+            if (src < 1 || src >= n) d = 0;  // what the search launch left, held to the history: no read past hist[n - 1]
+            else if (n - src < d) d = (int)(n - src);
+        }
+    }
+    sc_act[t] = act ? 1 : 0;
+    sc_d[t] = d;
+    __syncthreads();
+#pragma unroll 1
+    for (int off = 1; off < kSpecMaxSlots; off <<= 1) {  // inclusive scans of both counts
+        const int a = t >= off ? sc_act[t - off] : 0, dd = t >= off ? sc_d[t - off] : 0;
+        __syncthreads();
+        sc_act[t] += a;
+        sc_d[t] += dd;
+        __syncthreads();
+    }
+    // nodes are handed out in slot order from what the root rows leave of R: slot b keeps clamp(E - (nodes before it), 0, d)
+    const int E = R - sc_act[kSpecMaxSlots - 1];  // >= 0: R >= B
+    const int a_before = sc_act[t] - (act ? 1 : 0), d_before = sc_d[t] - d;
+    const int given_before = d_before < E ? d_before : E;
+    int given = E - d_before;
+    given = given < 0 ? 0 : (given > d ? d : given);
+    const int r0 = a_before + given_before;
+    const int d_all = sc_d[kSpecMaxSlots - 1];
+    const int total = sc_act[kSpecMaxSlots - 1] + (d_all < E ? d_all : E);
+    if (t < B) {
+        const int rows = act ? 1 + given : 0;
+        if (t == 0) p.row0[0] = 0;
+        p.row0[t + 1] = r0 + rows;
+        p.seq[t] = act ? t : -1;
+        p.pos0[t] = n - 1;
+        p.n_draft[t] = given;
+        if (act) {
+            const int *h = p.hist + (long)t * p.ld_hist;
+            for (int i = 0; i < rows; i++) {
+                int di = i;                          // the chain: depth i, every row in front of it an ancestor
+                unsigned a = (2u << i) - 1u;
+                long tok = i == 0 ? (long)h[n - 1] : 0;
+                if (q.ext_tok) {
+                    di = dep[t][i];
+                    a = 1u << i;
+                    for (int j = i; j > 0;) {  // at most 15 parents
+                        j = epar[j - 1];
+                        a |= 1u << j;
+                    }
+                    if (i > 0) tok = etok[i - 1];
+                } else if (i > 0) {
+                    tok = h[src + i - 1];
+                }
+                p.tokens[r0 + i] = tok;
+                p.row_slot[r0 + i] = t;
+                p.row_ctr[r0 + i] = n - 1 + di;
+                q.depth[r0 + i] = di;
+                q.anc[r0 + i] = a;
+            }
+        }
+    }
+    for (int r = total + t; r < R; r += kSpecMaxSlots) {
+        p.tokens[r] = 0;
+        p.row_slot[r] = -1;
+        p.row_ctr[r] = -1;
+        q.depth[r] = 0;
+        q.anc[r] = 0u;
+    }
+}
+
+struct SpecTreeAcceptParams {
+    SpecAcceptParams a;  // K = 15: out_tok is [B][16]
+    const int *depth;
+    const unsigned *anc;
+    int *path;
+};
+
+__global__ __launch_bounds__(kSpecMaxSlots) void spec_tree_accept_kernel(const SpecTreeAcceptParams q) {
+    const SpecAcceptParams &p = q.a;
+    const int b = threadIdx.x;
+    if (b >= p.B) return;
+    const int r = p.row0[b], T = p.row0[b + 1] - r;
+    const long n = p.n_tok[b], lim = p.limit[b];
+    int m = 0, cnt = 0;
+    int *path = q.path + b * (kSpecMaxDraft + 1);
+    path[0] = 0;
+    // an active segment: the tree draft's (seq[b] = b, 1 .. 32 rows inside R) on a slot that can still grow
+    if (p.seq[b] == b && T >= 1 && T <= kSpecTreeRows && r >= 0 && r + T <= p.R && n >= 1 && n < lim) {
+        // from the root: the draw of the current row, then its lowest-indexed child that carries that token
+        for (int cur = 0; m < kSpecMaxDraft;) {
+            const long tok = p.drawn[r + cur];
+            const int dc = q.depth[r + cur];
+            int nxt = -1;
+            for (int j = cur + 1; j < T && nxt < 0; j++)
+                if (q.depth[r + j] == dc + 1 && ((q.anc[r + j] >> cur) & 1u) && p.tokens[r + j] == tok) nxt = j;
+            if (nxt < 0) break;
+            cur = nxt;
+            path[++m] = cur;
+        }
+        cnt = m + 1;
+        if (lim - n < cnt) cnt = (int)(lim - n);
+        const long stop = p.eos[b];
+        bool hit = false;
+        int *h = p.hist + (long)b * p.ld_hist;
+        for (int i = 0; i < cnt; i++) {
+            const long tok = p.drawn[r + path[i]];
+            p.out_tok[(long)b * (kSpecMaxDraft + 1) + i] = tok;
+            if (n + i < p.ld_hist) h[n + i] = (int)tok;
+            if (stop >= 0 && tok == stop) {
+                cnt = i + 1;
+                hit = true;
+            }
+        }
+        p.n_tok[b] = n + cnt;
+        if (hit) p.limit[b] = n + cnt;
+    }
+    for (int i = m + 1; i <= kSpecMaxDraft; i++) path[i] = -1;
+    p.n_out[b] = cnt;
+    p.n_acc[b] = m;
+}
+
 }  // namespace qpal
 
 using namespace qpal;
@@ -271,5 +440,44 @@ extern "C" int qpal_spec_accept(const long *tokens, const long *drawn, const int
         return QPAL_E_ALIGN;
     SpecAcceptParams p{tokens, drawn, seq, row0, hist, ld_hist, n_tok, limit, eos, B, K, R, out_tok, n_out, n_acc};
     hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(kSpecMaxSlots), 0, static_cast<hipStream_t>(stream), p);
+    return (int)hipGetLastError();
+}
+
+extern "C" int qpal_spec_tree_draft(const int *hist, long ld_hist, const long *n_tok, const long *limit, const int *ext_tok,
+                                    const int *ext_par, const int *ext_n, int B, int N, int gmin, int gmax, int R, long max_len,
+                                    long *tokens, int *seq, int *row0, long *pos0, int *row_slot, long *row_ctr, int *n_draft,
+                                    int *depth, unsigned *anc, void *stream) {
+    if (!hist || !n_tok || !limit || !tokens || !seq || !row0 || !pos0 || !row_slot || !row_ctr || !n_draft || !depth || !anc)
+        return QPAL_E_NULL;
+    if (ext_tok && (!ext_par || !ext_n)) return QPAL_E_NULL;
+    if (B < 1 || B > kSpecMaxSlots || N < 0 || N > kSpecMaxNodes || gmin < 1 || gmax > kSpecMaxGram || gmin > gmax || R < B || R > 128 ||
+        max_len < 1 || ld_hist < 1 || ld_hist > 0x7fffffffl)
+        return QPAL_E_SHAPE;
+    if (misaligned(hist, 4) || misaligned(n_tok, 8) || misaligned(limit, 8) || misaligned(ext_tok, 4) || misaligned(ext_par, 4) ||
+        misaligned(ext_n, 4) || misaligned(tokens, 8) || misaligned(seq, 4) || misaligned(row0, 4) || misaligned(pos0, 8) ||
+        misaligned(row_slot, 4) || misaligned(row_ctr, 8) || misaligned(n_draft, 4) || misaligned(depth, 4) || misaligned(anc, 4))
+        return QPAL_E_ALIGN;
+    const int K = N < kSpecMaxDraft ? N : kSpecMaxDraft;
+    SpecTreeDraftParams p{{hist, ld_hist, n_tok, limit, nullptr, ext_n, B, K, gmin, gmax, R, max_len, tokens, seq, row0, pos0, row_slot,
+                           row_ctr, n_draft},
+                          ext_tok, ext_par, N, depth, anc};
+    if (!ext_tok) hipLaunchKernelGGL(spec_search_kernel, dim3(B), dim3(kSpecSearchThreads), 0, static_cast<hipStream_t>(stream), p.d);
+    hipLaunchKernelGGL(spec_tree_pack_kernel, dim3(1), dim3(kSpecMaxSlots), 0, static_cast<hipStream_t>(stream), p);
+    return (int)hipGetLastError();
+}
+
+extern "C" int qpal_spec_tree_accept(const long *tokens, const long *drawn, const int *seq, const int *row0, const int *depth,
+                                     const unsigned *anc, int *hist, long ld_hist, long *n_tok, long *limit, const long *eos, int B, int R,
+                                     long *out_tok, int *n_out, int *n_acc, int *path, void *stream) {
+    if (!tokens || !drawn || !seq || !row0 || !depth || !anc || !hist || !n_tok || !limit || !eos || !out_tok || !n_out || !n_acc || !path)
+        return QPAL_E_NULL;
+    if (B < 1 || B > kSpecMaxSlots || R < B || R > 128 || ld_hist < 1 || ld_hist > 0x7fffffffl) return QPAL_E_SHAPE;
+    if (misaligned(tokens, 8) || misaligned(drawn, 8) || misaligned(seq, 4) || misaligned(row0, 4) || misaligned(depth, 4) ||
+        misaligned(anc, 4) || misaligned(hist, 4) || misaligned(n_tok, 8) || misaligned(limit, 8) || misaligned(eos, 8) ||
+        misaligned(out_tok, 8) || misaligned(n_out, 4) || misaligned(n_acc, 4) || misaligned(path, 4))
+        return QPAL_E_ALIGN;
+    SpecTreeAcceptParams p{{tokens, drawn, seq, row0, hist, ld_hist, n_tok, limit, eos, B, kSpecMaxDraft, R, out_tok, n_out, n_acc},
+                           depth, anc, path};
+    hipLaunchKernelGGL(spec_tree_accept_kernel, dim3(1), dim3(kSpecMaxSlots), 0, static_cast<hipStream_t>(stream), p);
     return (int)hipGetLastError();
 }

@@ -124,7 +124,7 @@ from . import blocks, linear, logits, lora, ops, sampling
 from . import stop as stop_mod
 from .attention import _score_mods as _check_score_mods
 from .attention import _window as _check_one_window
-from .attention import (attention_workspace, decode_attention, paged_decode_attention, paged_prefill_attention,
+from .attention import (attention_workspace, decode_attention, kv_compact, kv_pointer_table, paged_decode_attention, paged_prefill_attention,
                         paged_ragged_prefill_attention, prefill_attention, prefill_workspace, ragged_prefill_attention, ragged_workspace,
                         shared_prefix_decode_attention, shared_prefix_workspace)
 from .linear import multi_gemv
@@ -1192,16 +1192,40 @@ class SpeculativeStep(RaggedStep):
     built with min_tokens=True (needs a sampler) adds the mask launch in front of the draw: row j of a segment is masked as the
     j-th token from now — the mask depends on the accepted prefix in front of the row only, the stream stays the sequential one.
 
-    window, softcap, sinks, attn_scale: as for RaggedStep; the stream is then token for token that DecodeStep's."""
+    window, softcap, sinks, attn_scale: as for RaggedStep; the stream is then token for token that DecodeStep's.
+
+    tree=N (0 .. 31): every slot's segment is a draft TREE of up to N nodes, and the step emits the longest root path
+    whose tokens equal the draws.  `draft` must be left at its default (paths go as deep as 15, out_tok is [B, 16]); rows defaults to
+    min(128, B (N + 1)).  ss(ext_tok=, ext_par=, ext_n=): the caller's trees, int32 [B, N] / [B, N] / [B] on the device — node i (1 ..
+    ext_n[b]) has token ext_tok[b, i - 1] and parent ext_par[b, i - 1] in [0, i), 0 the pending token; without them the tree is the
+    prompt-lookup chain.  Behind the accept, ONE kv_compact launch moves the accepted path's K / V rows to consecutive cache slots in
+    every layer, so there is still no rollback; ss.path int32 [B, 16] holds the accepted rows.  A paged caller reserves pos + N + 1
+    rows.  adapters, stop (without min_tokens) and MoE layers work unchanged; window, softcap, sinks, processor, grammar and a
+    sampler with logprobs / top_logprobs raise NotImplementedError together with tree=."""
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, draft=4, gram=(2, 4), rows=None, sampler=None,
                  block_table=None, history=None, adapters=None, processor=None, grammar=None, window=None, softcap=None, sinks=None,
                  attn_scale=None, stop=None,
-                 qkv_bias=None, qk_norm=None, mlp_act="silu", post_norms=None, logit_cap=None):
+                 qkv_bias=None, qk_norm=None, mlp_act="silu", post_norms=None, logit_cap=None, tree=None):
         B, K = self._check_table("SpeculativeStep", kcache, block_table), int(draft)
+        self.tree = None if tree is None else int(tree)
+        if tree is not None:  # draft trees (DESIGN.md §40): up to `tree` nodes per slot, paths of up to 15, out_tok [B, 16]
+            if not 0 <= self.tree <= 31:
+                raise nat.QpalError(f"SpeculativeStep: tree must be in 0 .. 31 nodes, got {tree}")
+            if K != 4:
+                raise nat.QpalError(f"SpeculativeStep: draft= has no meaning with tree= (paths go as deep as 15), got draft={draft}")
+            unbuilt = [name for name, given in (("window", window), ("softcap", softcap), ("sinks", sinks), ("processor", processor),
+                                                ("grammar", grammar)) if given is not None]
+            if sampler is not None and (sampler.logprob is not None or sampler.top_id is not None):
+                unbuilt.append("a sampler with logprobs / top_logprobs")
+            if stop is not None and stop.min_tokens_mask:
+                unbuilt.append("a stop bank with min_tokens")
+            if unbuilt:
+                raise NotImplementedError(f"SpeculativeStep: tree= is not built together with {', '.join(unbuilt)}")
+            K = 15
         if not 0 <= K <= 15 or len(gram) != 2 or not 1 <= int(gram[0]) <= int(gram[1]) <= 8:
             raise nat.QpalError(f"SpeculativeStep: draft must be in 0 .. 15 and 1 <= gram[0] <= gram[1] <= 8, got {draft}, {gram}")
-        rows = min(128, B * (K + 1)) if rows is None else int(rows)
+        rows = min(128, B * ((K if tree is None else self.tree) + 1)) if rows is None else int(rows)
         if not 1 <= B <= rows <= 128:
             raise nat.QpalError(f"SpeculativeStep: rows must be in B = {B} .. 128, got {rows}")
         self.draft_len, self.gram = K, (int(gram[0]), int(gram[1]))
@@ -1224,6 +1248,10 @@ class SpeculativeStep(RaggedStep):
         self.row_slot, self.row_ctr = torch.full((rows,), -1, dtype=i32, device=dev), torch.full((rows,), -1, dtype=i64, device=dev)
         self.n_draft, self.n_out, self.n_acc = (torch.zeros(B, dtype=i32, device=dev) for _ in range(3))
         self._gather = torch.zeros(rows, dtype=i64, device=dev)  # the rows' embedding indices when the caller drafts
+        if self.tree is not None:  # the rows' depths and root paths, the accepted path, and the layers' caches for the compaction
+            self.depth, self.anc = torch.zeros(rows, dtype=i32, device=dev), torch.zeros(rows, dtype=i32, device=dev)
+            self.path = torch.full((B, 16), -1, dtype=i32, device=dev)
+            self._kptrs, self._vptrs = kv_pointer_table(self.kcache), kv_pointer_table(self.vcache)
         if processor is not None:  # the observe launch behind the accept: entry (b, i) of out_tok counts for slot b iff i < n_out[b]
             self._obs_slot = torch.arange(B, dtype=i32, device=dev).repeat_interleave(K + 1).contiguous()
             self._obs_active = torch.zeros(B * (K + 1), dtype=i64, device=dev)
@@ -1231,6 +1259,17 @@ class SpeculativeStep(RaggedStep):
 
     def _moe_active(self):
         return self.row_ctr  # rows no slot holds (-1) route nothing
+
+    def _attention(self, i, q, k, v, out):
+        if self.tree is None:
+            return super()._attention(i, q, k, v, out)
+        kc, vc = self.kcache[i], self.vcache[i]
+        if self.block_table is None:
+            attend, cache = ragged_prefill_attention, (kc, vc)
+        else:
+            attend, cache = paged_ragged_prefill_attention, (kc, vc, self.block_table)
+        attend(q, k, v, *cache, self.seq, self.row0, self.pos0, self._inv_freq(i), scale=self.attn_scale, out=out, ws=self.attn_ws,
+               tree=(self.depth, self.anc))
 
     def _setup_tail(self, vocab, dev, logprobs, top_n):
         """a draw at every ROW and up to draft + 1 tokens per slot: no last rows, no per-segment counters"""
@@ -1280,12 +1319,22 @@ class SpeculativeStep(RaggedStep):
             raise nat.QpalError(f"SpeculativeStep.release: slot {slot} outside the caches' {self.slots} sequences")
         self.n_tok[int(slot)], self.limit[int(slot)], self.eos[int(slot)] = 0, 0, -1
 
-    def __call__(self, ext_draft=None, ext_n=None):
+    def __call__(self, ext_draft=None, ext_n=None, ext_tok=None, ext_par=None):
         from . import speculative as spec
-        if ext_draft is None and ext_n is not None:
-            raise nat.QpalError("SpeculativeStep: ext_n without ext_draft")
-        spec.spec_draft(self.hist, self.n_tok, self.limit, self.draft_len, self.gram, self.context, self.tokens, self.seq, self.row0,
-                        self.pos0, self.row_slot, self.row_ctr, self.n_draft, ext_draft=ext_draft, ext_n=ext_n)
+        if self.tree is not None:
+            if ext_draft is not None or (ext_tok is None) != (ext_par is None) or (ext_tok is None) != (ext_n is None):
+                raise nat.QpalError("SpeculativeStep: a tree step takes ext_tok, ext_par and ext_n together, or none of them")
+            spec.spec_tree_draft(self.hist, self.n_tok, self.limit, self.tree, self.gram, self.context, self.tokens, self.seq, self.row0,
+                                 self.pos0, self.row_slot, self.row_ctr, self.n_draft, self.depth, self.anc, ext_tok=ext_tok,
+                                 ext_par=ext_par, ext_n=ext_n)
+            ext_draft = ext_tok
+        else:
+            if ext_tok is not None or ext_par is not None:
+                raise nat.QpalError("SpeculativeStep: ext_tok / ext_par need a step built with tree=")
+            if ext_draft is None and ext_n is not None:
+                raise nat.QpalError("SpeculativeStep: ext_n without ext_draft")
+            spec.spec_draft(self.hist, self.n_tok, self.limit, self.draft_len, self.gram, self.context, self.tokens, self.seq, self.row0,
+                            self.pos0, self.row_slot, self.row_ctr, self.n_draft, ext_draft=ext_draft, ext_n=ext_n)
         if self.grammar is not None:
             gram_mod.grammar_rows(self.grammar, self.tokens, self.row0, self._row_state)
         # a caller's draft may be no token of the model: it can equal no draw, so any valid row of the embedding stands in for it
@@ -1321,8 +1370,13 @@ class SpeculativeStep(RaggedStep):
     def _accept(self):
         """behind the rows' draws: the accept, and what follows it (stop, grammar, processor); the call's return value"""
         from . import speculative as spec
-        spec.spec_accept(self.tokens, self.drawn, self.seq, self.row0, self.hist, self.n_tok, self.limit, self.eos, self.out_tok,
-                         self.n_out, self.n_acc)
+        if self.tree is not None:  # the accepted root path, then its K / V rows moved to consecutive slots in every layer
+            spec.spec_tree_accept(self.tokens, self.drawn, self.seq, self.row0, self.depth, self.anc, self.hist, self.n_tok, self.limit,
+                                  self.eos, self.out_tok, self.n_out, self.n_acc, self.path)
+            kv_compact(self._kptrs, self._vptrs, self.kcache[0], self.pos0, self.path, self.n_acc, block_table=self.block_table)
+        else:
+            spec.spec_accept(self.tokens, self.drawn, self.seq, self.row0, self.hist, self.n_tok, self.limit, self.eos, self.out_tok,
+                             self.n_out, self.n_acc)
         if self.stop is not None:  # cuts n_out / n_tok / limit where a slot finishes inside its run: what follows sees the cut
             stop_mod.stop_advance(self.stop, self.out_tok, self.context, n_out=self.n_out, n_tok=self.n_tok, limit=self.limit)
         if self.grammar is not None:

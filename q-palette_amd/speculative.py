@@ -111,6 +111,95 @@ def reference_spec_accept(tokens, drawn, seq, row0, hist, n_tok, limit, eos, K, 
     return dict(hist=hist, n_tok=n_tok, limit=limit, out_tok=out, n_out=n_out, n_acc=n_acc)
 
 
+MAX_NODES = 31
+
+
+def reference_spec_tree_draft(hist, n_tok, limit, N, gmin, gmax, R, max_len, ext_tok=None, ext_par=None, ext_n=None):
+    """The contract of qpal_spec_tree_draft.  ext_tok / ext_par int [B, N] and ext_n int [B], or None: the chain of
+    the prompt lookup.  Returns reference_spec_draft's dict with row_ctr = pos0 + depth, plus depth int32 [R] and anc uint32 [R]."""
+    hist = np.asarray(hist)
+    B, ld = hist.shape
+    if not (1 <= B <= MAX_SLOTS and 0 <= N <= MAX_NODES and 1 <= gmin <= gmax <= MAX_GRAM and B <= R <= MAX_ROWS and max_len >= 1):
+        raise ValueError("reference_spec_tree_draft: B, N, gram, R or max_len outside the contract")
+    n_tok, limit = [int(v) for v in n_tok], [int(v) for v in limit]
+    act = [_active(n_tok[b], limit[b], max_len, ld) for b in range(B)]
+    trees = []  # per slot: [(token, parent, depth)] of nodes 1 ..
+    for b in range(B):
+        nodes, n = [], n_tok[b]
+        if act[b] and ext_tok is not None:
+            d_max, depth = max(0, min(MAX_DRAFT, limit[b] - n - 1)), [0]
+            for i in range(1, max(0, min(int(ext_n[b]), N)) + 1):
+                tok, par = int(ext_tok[b][i - 1]), int(ext_par[b][i - 1])
+                if not 0 <= tok < 2 ** 30 or not 0 <= par < i or depth[par] + 1 > d_max or n - 1 + i >= max_len:
+                    break
+                depth.append(depth[par] + 1)
+                nodes.append((tok, par, depth[i]))
+        elif act[b]:
+            d_max = max(0, min(N, MAX_DRAFT, limit[b] - n - 1, max_len - n))
+            at = lookup(hist[b, :n], gmin, gmax) if d_max > 0 else None
+            if at is not None:
+                nodes = [(int(t), i, i + 1) for i, t in enumerate(hist[b, at:min(at + d_max, n)])]
+        trees.append(nodes)
+    out = dict(tokens=np.zeros(R, np.int64), seq=np.full(B, -1, np.int32), row0=np.zeros(B + 1, np.int32), pos0=np.zeros(B, np.int64),
+               row_slot=np.full(R, -1, np.int32), row_ctr=np.full(R, -1, np.int64), n_draft=np.zeros(B, np.int32),
+               depth=np.zeros(R, np.int32), anc=np.zeros(R, np.uint32))
+    at = 0
+    for b in range(B):
+        out["pos0"][b] = n_tok[b] - 1
+        if act[b]:
+            nodes = trees[b][:max(0, R - at - 1 - sum(act[b + 1:]))]  # every active slot keeps its root row; cut where R is full
+            rows = [(int(hist[b, n_tok[b] - 1]), 0, 0)] + nodes
+            for i, (tok, par, d) in enumerate(rows):
+                a, j = 1 << i, i
+                while j > 0:
+                    j = rows[j][1]
+                    a |= 1 << j
+                out["tokens"][at + i], out["depth"][at + i], out["anc"][at + i] = tok, d, a
+                out["row_slot"][at + i], out["row_ctr"][at + i] = b, n_tok[b] - 1 + d
+            out["seq"][b], out["n_draft"][b] = b, len(nodes)
+            at += len(rows)
+        out["row0"][b + 1] = at
+    return out
+
+
+def reference_spec_tree_accept(tokens, drawn, seq, row0, depth, anc, hist, n_tok, limit, eos, out_tok=None):
+    """The contract of qpal_spec_tree_accept.  Returns reference_spec_accept's dict (out_tok int64 [B, 16]) plus path int32 [B, 16]."""
+    tokens, drawn = np.asarray(tokens, np.int64), np.asarray(drawn, np.int64)
+    hist = np.array(hist, dtype=np.int32)
+    B, ld = hist.shape
+    R, W = tokens.shape[0], MAX_DRAFT + 1
+    n_tok, limit = np.array(n_tok, dtype=np.int64), np.array(limit, dtype=np.int64)
+    out = np.zeros((B, W), np.int64) if out_tok is None else np.array(out_tok, dtype=np.int64)
+    n_out, n_acc, path = np.zeros(B, np.int32), np.zeros(B, np.int32), np.full((B, W), -1, np.int32)
+    path[:, 0] = 0
+    for b in range(B):
+        r, T = int(row0[b]), int(row0[b + 1]) - int(row0[b])
+        n, lim = int(n_tok[b]), int(limit[b])
+        if not (int(seq[b]) == b and 1 <= T <= MAX_NODES + 1 and r >= 0 and r + T <= R and 1 <= n < lim):
+            continue
+        walk = [0]
+        while len(walk) <= MAX_DRAFT:
+            cur = walk[-1]
+            kids = [j for j in range(cur + 1, T) if int(depth[r + j]) == int(depth[r + cur]) + 1 and (int(anc[r + j]) >> cur) & 1
+                    and tokens[r + j] == drawn[r + cur]]
+            if not kids:
+                break
+            walk.append(kids[0])
+        path[b, :len(walk)] = walk
+        emitted = [int(drawn[r + j]) for j in walk][:lim - n]
+        stop = int(eos[b])
+        if stop >= 0 and stop in emitted:
+            emitted = emitted[:emitted.index(stop) + 1]
+            limit[b] = n + len(emitted)
+        for i, t in enumerate(emitted):
+            out[b, i] = t
+            if n + i < ld:
+                hist[b, n + i] = t
+        n_tok[b] = n + len(emitted)
+        n_out[b], n_acc[b] = len(emitted), len(walk) - 1
+    return dict(hist=hist, n_tok=n_tok, limit=limit, out_tok=out, n_out=n_out, n_acc=n_acc, path=path)
+
+
 # ---------------------------------------------------------------------------------------------------------------- GPU side
 
 def _torch():
@@ -197,3 +286,63 @@ def spec_accept(tokens, drawn, seq, row0, hist, n_tok, limit, eos, out_tok, n_ou
         rc = _native.lib().qpal_spec_accept(*ins, hist.data_ptr(), hist.shape[1], *st, eos_p, B, K, R, *outs,
                                             torch.cuda.current_stream(dev).cuda_stream)
     _native.check(rc, "qpal_spec_accept")
+
+
+def spec_tree_draft(hist, n_tok, limit, N, gram, max_len, tokens, seq, row0, pos0, row_slot, row_ctr, n_draft, depth, anc,
+                    ext_tok=None, ext_par=None, ext_n=None):
+    """spec_draft for draft TREES (the contract: include/qpal.h, reference_spec_tree_draft).  N: the nodes per slot,
+    0 .. 31.  Written: spec_draft's tensors (row_ctr = pos0 + depth) plus depth int32 [R] and anc int32 [R] (the 32 bits of the
+    contract's uint32) — the tree= of ragged_prefill_attention.  ext_tok / ext_par int32 [B, N] with ext_n int32 [B]: the caller's
+    trees; without them the chain of the prompt lookup.  Device tensors the host never reads; one or two launches."""
+    torch = _torch()
+    from . import _native
+    who, QpalError = "spec_tree_draft", _native.QpalError
+    B, dev, st = _state(who, hist, n_tok, limit)
+    N, (gmin, gmax), max_len = int(N), (int(gram[0]), int(gram[1])), int(max_len)
+    if not 0 <= N <= MAX_NODES or not 1 <= gmin <= gmax <= MAX_GRAM or max_len < 1:
+        raise QpalError(f"{who}: N must be in 0 .. {MAX_NODES}, 1 <= gmin <= gmax <= {MAX_GRAM} and max_len >= 1, got {N}, {gram}, {max_len}")
+    if tokens.dim() != 1 or not B <= tokens.shape[0] <= MAX_ROWS:
+        raise QpalError(f"{who}: tokens must be int64 [R] with {B} <= R <= {MAX_ROWS}")
+    R = tokens.shape[0]
+    outs = [_arr(tokens, "tokens", torch.int64, (R,), dev, who), _arr(seq, "seq", torch.int32, (B,), dev, who),
+            _arr(row0, "row0", torch.int32, (B + 1,), dev, who), _arr(pos0, "pos0", torch.int64, (B,), dev, who),
+            _arr(row_slot, "row_slot", torch.int32, (R,), dev, who), _arr(row_ctr, "row_ctr", torch.int64, (R,), dev, who),
+            _arr(n_draft, "n_draft", torch.int32, (B,), dev, who), _arr(depth, "depth", torch.int32, (R,), dev, who),
+            _arr(anc, "anc", torch.int32, (R,), dev, who)]
+    ext = [None, None, None]
+    if ext_tok is not None:
+        if ext_par is None or ext_n is None:
+            raise QpalError(f"{who}: ext_tok needs ext_par and ext_n")
+        ext = [_arr(ext_tok, "ext_tok", torch.int32, (B, N), dev, who), _arr(ext_par, "ext_par", torch.int32, (B, N), dev, who),
+               _arr(ext_n, "ext_n", torch.int32, (B,), dev, who)]
+    if not hist.is_cuda:
+        raise QpalError(f"{who}: the state must live on a GPU, got {dev}")
+    with torch.cuda.device(dev):
+        rc = _native.lib().qpal_spec_tree_draft(hist.data_ptr(), hist.shape[1], *st, *ext, B, N, gmin, gmax, R, max_len, *outs,
+                                                torch.cuda.current_stream(dev).cuda_stream)
+    _native.check(rc, "qpal_spec_tree_draft")
+
+
+def spec_tree_accept(tokens, drawn, seq, row0, depth, anc, hist, n_tok, limit, eos, out_tok, n_out, n_acc, path):
+    """spec_accept on a tree (the contract: include/qpal.h, reference_spec_tree_accept): the longest root path whose tokens equal the
+    draws.  tokens / seq / row0 / depth / anc as spec_tree_draft wrote them; out_tok int64 [B, 16]; path int32 [B, 16], the accepted
+    rows by depth — kv_compact's argument.  One launch on the current stream; the host reads nothing."""
+    torch = _torch()
+    from . import _native
+    who, QpalError = "spec_tree_accept", _native.QpalError
+    B, dev, st = _state(who, hist, n_tok, limit)
+    if tokens.dim() != 1 or not B <= tokens.shape[0] <= MAX_ROWS:
+        raise QpalError(f"{who}: tokens must be int64 [R] with {B} <= R <= {MAX_ROWS}")
+    R, W = tokens.shape[0], MAX_DRAFT + 1
+    ins = [_arr(tokens, "tokens", torch.int64, (R,), dev, who), _arr(drawn, "drawn", torch.int64, (R,), dev, who),
+           _arr(seq, "seq", torch.int32, (B,), dev, who), _arr(row0, "row0", torch.int32, (B + 1,), dev, who),
+           _arr(depth, "depth", torch.int32, (R,), dev, who), _arr(anc, "anc", torch.int32, (R,), dev, who)]
+    eos_p = _arr(eos, "eos", torch.int64, (B,), dev, who)
+    outs = [_arr(out_tok, "out_tok", torch.int64, (B, W), dev, who), _arr(n_out, "n_out", torch.int32, (B,), dev, who),
+            _arr(n_acc, "n_acc", torch.int32, (B,), dev, who), _arr(path, "path", torch.int32, (B, W), dev, who)]
+    if not hist.is_cuda:
+        raise QpalError(f"{who}: the state must live on a GPU, got {dev}")
+    with torch.cuda.device(dev):
+        rc = _native.lib().qpal_spec_tree_accept(*ins, hist.data_ptr(), hist.shape[1], *st, eos_p, B, R, *outs,
+                                                 torch.cuda.current_stream(dev).cuda_stream)
+    _native.check(rc, "qpal_spec_tree_accept")
