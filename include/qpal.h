@@ -571,6 +571,38 @@ int qpal_attn_rope_prefill_ragged_score(const float *q, const float *k, const fl
                                         long max_len, float scale, long window, float softcap, const float *sinks,
                                         void *ws, long ws_bytes, void *stream);
 
+/* WIDE prompt prefill attention of ONE sequence (csrc/attn_prefill_wide.hip): qpal_attn_rope_prefill's contract for
+ * 129 <= T <= 256 new tokens, as TWO launches on `stream`.  The first rotates the T rows of q and k once (qpal_rope_kv's
+ * arithmetic, bit for bit), writes the rotated q as fp16 into a scratch [T][nq * hd] inside ws and appends k and (fp16) v to cache
+ * rows *pos0 .. *pos0 + T - 1: fp16 caches as they are, e4m3 caches by the store rule of the _kv8 entry points — the bytes two
+ * 128-row launches of qpal_attn_rope_prefill_window(window = 0) leave for the same q | k | v, and no other cache byte.  The second
+ * is the causal attention of row t over positions 0 .. *pos0 + t; it reads EVERY key, the new rows included, from the cache
+ * (stream order between the two launches orders the accesses), so a new row takes part at its stored, dequantised value.
+ * One entry point serves both element formats (kv_fmt 0 fp16, 1 e4m3fn) and both storages, as qpal_attn_rope_prefill_window
+ * does: block_row == NULL — contiguous caches [nkv][max_len][hd], the paged arguments are ignored; else the pools and the table
+ * row of qpal_attn_rope_prefill_paged, max_len = max_pages * page_size, the max_len argument is ignored (a used entry outside
+ * [0, num_pages): loads read page 0, the row's stores are dropped).  q / k / v / out / pos0 / inv_freq, the (nq, nkv) rule, page
+ * sizes and alignment rules are qpal_attn_rope_prefill_window's; hd in {64, 128} (hd 256: QPAL_E_SHAPE — run two 128-row
+ * launches); T outside 129 .. 256: QPAL_E_SHAPE.  *pos0 < 0 or *pos0 + T > max_len: neither launch writes anything (no cache
+ * byte, no out byte, no scratch byte).  pos0 and the table are never read by the host; both launches are graph-capturable and
+ * two runs are bitwise equal (partials merged in chunk order by the last arriver, no float atomics).
+ * Every argument error is a return code in front of any stream work: no pointer is dereferenced on the host.  Codes: a null q /
+ * k / v / cache / out / pos0 / inv_freq QPAL_E_NULL; kv_fmt, the paged shape, T, nq / nkv / hd, max_len, ld_qkv or ld_out below
+ * nq * hd: QPAL_E_SHAPE; a misaligned pointer (caches 16, q / k / v / inv_freq / pos0 / table 4, out 2, ws 16 bytes): QPAL_E_ALIGN;
+ * ws NULL: QPAL_E_NULL; ws_bytes below qpal_attn_prefill_wide_ws_bytes(T, ...): QPAL_E_SHAPE.
+ * ws: qpal_attn_prefill_wide_ws_bytes(T, nq, nkv, hd, max_len) bytes of device memory (never 0 for an accepted shape; 0 for a
+ * refused one), 16-byte aligned, zero-filled ONCE, kept across launches: tickets, split-context partials, the q scratch.  A
+ * launch leaves it as it found it, the scratch apart.  The size is monotone in T and max_len and never below
+ * qpal_attn_prefill_ws_bytes(128, ...) of the same heads and max_len, whose ticket words it shares: one workspace serves every
+ * layer, every narrower wide chunk and the 128-row launches of a prompt's last chunk, in both formats and both storages. */
+long qpal_attn_prefill_wide_ws_bytes(int T, int nq, int nkv, int hd, long max_len);
+int qpal_attn_rope_prefill_wide(const float *q, const float *k, const float *v, long ld_qkv,
+                                void *kcache, void *vcache, void *out_f16, long ld_out,
+                                const long *pos0, const float *inv_freq, const int *block_row /* NULL: contiguous */,
+                                int num_pages, int page_size, int max_pages, int kv_fmt,
+                                int T, int nq, int nkv, int hd, long max_len, float scale,
+                                void *ws, long ws_bytes, void *stream);
+
 /* Final norm + fp16 lm_head for `rows` rows of the residual stream at once, on the matrix pipe (csrc/lm_head_batch.hip): the
  * logits a sampler needs, and the batch-B tail of a decode step.  h_f32 fp32 [rows][ld_h] (ld_h >= k, in elements), 1 <= rows <=
  * 128; k a multiple of 512, 512 <= k <= 8192; w_f16 the lm_head fp16 [vocab][k]; logits_f32 fp32 [rows][ld_logits], ld_logits >=

@@ -15,7 +15,11 @@ attend to, sum_t min(pos0 + t + 1, W), next to "keys": sum_t (pos0 + t + 1)), th
 --softcap CAP / --sinks: per row also the launch with softcap=CAP ("us_cap"), with sinks of N(0, 1) per head
 ("us_sinks") and with both ("us_cap_sinks"), then the plain launch again ("us_prefill_attention_again").
 
-    python perf/attn_prefill_bench.py [--softcap CAP] [--sinks] [--T 128] [--pos0 0 1920 3968] [--context 4096] [--heads 32 8 128] [--iters 50] [--kv fp16|fp8]
+--wide: T = 256 rows through the wide launch (qpal_attn_rope_prefill_wide) against two 128-row launches of the
+existing entry on the same q | k | v and cache, alternated call by call, one event pair per call, the median of --iters (>= 30)
+calls each ("us_wide", "us_two_launches", "ratio" = two / wide); the outputs are compared first ("max_abs_diff").
+
+    python perf/attn_prefill_bench.py [--wide] [--softcap CAP] [--sinks] [--T 128] [--pos0 0 1920 3968] [--context 4096] [--heads 32 8 128] [--iters 50] [--kv fp16|fp8]
                                       [--paged 16 64] [--window W]
 """
 import argparse
@@ -42,7 +46,10 @@ def main(argv=None):
     ap.add_argument("--window", type=int, default=None, metavar="W", help="also time the launch with this sliding window")
     ap.add_argument("--softcap", type=float, default=None, metavar="CAP", help="also time the launch with this logit soft cap")
     ap.add_argument("--sinks", action="store_true", help="also time the launch with per-head sinks")
+    ap.add_argument("--wide", action="store_true", help="T = 256 through the wide launch against two 128-row launches, alternated")
     args = ap.parse_args(argv)
+    if args.wide:
+        args.T = 256
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
     dev = torch.device("cuda", 0)
@@ -69,6 +76,43 @@ def main(argv=None):
         e1.record()
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / args.iters * 1e3  # us
+
+    def wide_rows():
+        """the wide pair of launches and two 128-row launches, alternated; median of one event pair per call"""
+        res, out2, iters = [], torch.empty_like(out), max(args.iters, 30)
+        for pos0 in args.pos0:
+            pos_t, pos2 = (torch.tensor([p], dtype=torch.long, device=dev) for p in (pos0, pos0 + 128))
+
+            def wide():
+                qp.prefill_attention(q, k, v, kc, vc, pos_t, inv_freq, out=out, ws=ws)
+
+            def two():
+                qp.prefill_attention(q[:128], k[:128], v[:128], kc, vc, pos_t, inv_freq, out=out2[:128], ws=ws)
+                qp.prefill_attention(q[128:], k[128:], v[128:], kc, vc, pos2, inv_freq, out=out2[128:], ws=ws)
+
+            for _ in range(5):
+                wide(), two()
+            torch.cuda.synchronize()
+            diff = float((out.float() - out2.float()).abs().max())
+            us = {wide: [], two: []}
+            for _ in range(iters):
+                for fn in (wide, two):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us[fn].append(e0.elapsed_time(e1) * 1e3)
+            mw, mt = (sorted(us[fn])[iters // 2] for fn in (wide, two))
+            flop = 4 * nq * hd * sum(pos0 + t + 1 for t in range(T))
+            res.append({"T": T, "pos0": pos0, "kv": args.kv, "flop": flop, "us_wide": mw, "us_two_launches": mt, "ratio": mt / mw,
+                        "tflops_wide": flop / mw * 1e-6, "tflops_two_launches": flop / mt * 1e-6, "max_abs_diff": diff})
+        return res
+
+    if args.wide:
+        print(json.dumps({"what": "wide prefill attention (rope-and-append + attention launch) vs two 128-row launches, alternated, "
+                                  "median of event-timed calls", "heads": args.heads, "context": L, "rows": wide_rows()}))
+        return
 
     rows = []
     for pos0 in args.pos0:

@@ -44,6 +44,8 @@ def main(argv=None, quiet=False):
     ap.add_argument("--chunk", type=int, default=128)
     ap.add_argument("--wide", type=int, default=None, metavar="R",
                     help="also time Prefill(wide=R), 129 .. 256: chunks of R rows in one weight pass (DESIGN.md §39), same call")
+    ap.add_argument("--wide-attention", action="store_true",
+                    help="with --wide: also time Prefill(wide=R, wide_attention=True), one attention call per wide chunk (DESIGN.md §41)")
     ap.add_argument("--slots", type=int, default=1, help="sequences the caches hold (B of a DecodeStep over them)")
     ap.add_argument("--slot", type=int, default=0, help="the slot the prompt goes into; the last slot, if another, is inactive")
     ap.add_argument("--vocab", type=int, default=128256)
@@ -99,6 +101,8 @@ def main(argv=None, quiet=False):
     vc = [(torch.randn(B, nkv, ctx, head_dim, device=dev, generator=cg) * 0.5).half() for _ in range(nlayers)]
     pf = qp.Prefill(layers, embed, norm, lm_head, kc, vc, inv_freq, chunk=args.chunk)
     pfw = None if args.wide is None else qp.Prefill(layers, embed, norm, lm_head, kc, vc, inv_freq, wide=args.wide)
+    pfwa = None if pfw is None or not args.wide_attention else qp.Prefill(layers, embed, norm, lm_head, kc, vc, inv_freq, wide=args.wide,
+                                                                          wide_attention=True)
     ref = StaticKV(nlayers, nkv, head_dim, ctx, dev)       # the torch-glue path's cache
     one = StaticKV(nlayers, nkv, head_dim, ctx, dev)       # the token-by-token paths' cache
     tok1 = torch.zeros(1, dtype=torch.long, device=dev)
@@ -181,6 +185,12 @@ def main(argv=None, quiet=False):
                 ms_w = time_graph(lambda: pfw(tokens, slot=slot, pos0=0), args.iters, dev)
                 note(N, "wide prefill ms", ms_w)
                 res.update({"wide": args.wide, "ms_prefill_wide": ms_w, "prompt_tokens_per_s_prefill_wide": N / ms_w * 1e3})
+            if pfwa is not None:
+                res["next_token_wide_attention"] = int(pfwa(tokens, slot=slot, pos0=0))
+                res["wide_attention_vs_chunk_max_abs_diff_final_norm"] = float((pfwa.hidden().float() - got_h).abs().max())
+                ms_wa = time_graph(lambda: pfwa(tokens, slot=slot, pos0=0), args.iters, dev)
+                note(N, "wide-attention prefill ms", ms_wa)
+                res.update({"ms_prefill_wide_attention": ms_wa, "prompt_tokens_per_s_prefill_wide_attention": N / ms_wa * 1e3})
             ms_tbt = time_graph(fast1, N, dev, feed) * N
             note(N, "token by token ms", ms_tbt)
             ms_glue = time_graph(lambda: glue(tokens, pos), args.iters, dev)

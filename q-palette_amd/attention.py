@@ -230,12 +230,18 @@ def _decode(who, entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, 
 def prefill_workspace(T, nq, nkv, hd, max_len, device):
     """The zero-filled workspace ``prefill_attention`` needs for chunks of up to T rows and a cache of up to max_len positions
     (same nq, nkv, hd), or None where no launch of that shape needs one.  Keep it across launches: the kernel leaves it as it
-    found it."""
+    found it.  T in 129 .. 256 (the wide launch): qpal_attn_prefill_wide_ws_bytes — that workspace also serves the
+    launches of 128 rows or fewer; hd 256 has no wide launch (QpalError)."""
+    if int(T) > 128:
+        ws = _workspace("qpal_attn_prefill_wide_ws_bytes", device, T, nq, nkv, hd, max_len)
+        if ws is None:
+            raise QpalError(f"prefill_workspace: no wide prefill launch of shape T={T}, nq={nq}, nkv={nkv}, hd={hd}, max_len={max_len}")
+        return ws
     return _workspace("qpal_attn_prefill_ws_bytes", device, T, nq, nkv, hd, max_len)
 
 
 def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=None, ws=None, window=None, softcap=None, sinks=None):
-    """q fp32 [T, nq*hd], k / v fp32 [T, nkv*hd], 1 <= T <= 128: row t is the token at position pos0 + t (rows may be strided:
+    """q fp32 [T, nq*hd], k / v fp32 [T, nkv*hd], 1 <= T <= 256 (above 128: the last paragraph): row t is the token at position pos0 + t (rows may be strided:
     column slices of one q|k|v output with a common row stride); kcache / vcache [nkv, max_len, hd] of ONE sequence,
     contiguous, 16-byte aligned (``kcache[b]`` of the batched layout), updated in place at rows pos0 .. pos0 + T - 1; pos0 int64
     [1] on the device; inv_freq fp32 [hd/2].  Returns out fp16 [T, nq*hd] (``out`` if given): row t attends to positions 0 ..
@@ -263,15 +269,15 @@ def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=N
                     mods=mods)
 
 
-def _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos_check=None, B=None):
+def _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos_check=None, B=None, max_rows=128):
     """the checks of q / k / v / inv_freq / out every attention launch shares — B: the rows of a decode launch, None: the 1 .. 128
-    rows of a prefill launch — with the launch's own position check, where it has one, in its place among them; returns (T, nq,
-    ld_qkv, out, ld_out)"""
+    rows of a prefill launch (max_rows: 256 for the one-sequence callers) — with the launch's own position check, where it has one,
+    in its place among them; returns (T, nq, ld_qkv, out, ld_out)"""
     if B is not None:
         if q.dim() != 2 or q.shape[0] != B or q.shape[1] % hd:
             raise QpalError(f"{who}: q must have shape [{B}, nq*{hd}], got {list(q.shape)}")
-    elif q.dim() != 2 or not 1 <= q.shape[0] <= 128 or q.shape[1] % hd:
-        raise QpalError(f"{who}: q must have shape [T, nq*{hd}] with 1 <= T <= 128, got {list(q.shape)}")
+    elif q.dim() != 2 or not 1 <= q.shape[0] <= max_rows or q.shape[1] % hd:
+        raise QpalError(f"{who}: q must have shape [T, nq*{hd}] with 1 <= T <= {max_rows}, got {list(q.shape)}")
     T, nq = q.shape[0], q.shape[1] // hd
     ld = _rows(q, "q", T, nq * hd, who)
     for name, t in (("k", k), ("v", v)):
@@ -310,12 +316,19 @@ def _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws
         if pos0.dtype != torch.int64 or pos0.numel() != 1 or pos0.device != kcache.device:
             raise QpalError(f"{who}: pos0 must be an int64 tensor of one element on {kcache.device}")
 
-    T, nq, ld, out, ld_out = _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos_check)
+    T, nq, ld, out, ld_out = _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos_check, max_rows=256)
+    wide = T > 128
+    if wide and not (window is None and mods[0] is None and mods[1] is None):
+        raise QpalError(f"{who}: a launch of {T} > 128 rows takes no window, softcap or sinks")
     score = None if mods[0] is None and mods[1] is None else _score_args(who, mods, nq, kcache.device)  # (before the library)
     lib = _native.lib()
-    ws_ptr, ws_bytes = _launch_ws(who, lib.qpal_attn_prefill_ws_bytes(T, nq, nkv, hd, max_len), ws, kcache, "prefill_workspace")
+    sizer = lib.qpal_attn_prefill_wide_ws_bytes if wide else lib.qpal_attn_prefill_ws_bytes
+    ws_ptr, ws_bytes = _launch_ws(who, sizer(T, nq, nkv, hd, max_len), ws, kcache, "prefill_workspace")
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    if score is not None:
+    if wide:  # (a shape without a wide launch, hd 256: no workspace above, QPAL_E_SHAPE here)
+        entry = "qpal_attn_rope_prefill_wide"
+        shape = _window_args(paged, (None, 0, 0, 0), kcache, (T, nq, nkv, hd), max_len, scale, 0)[:-1]
+    elif score is not None:
         entry = "qpal_attn_rope_prefill_score"
         shape = (_window_args(paged, (None, 0, 0, 0), kcache, (T, nq, nkv, hd), max_len, scale, window or 0)
                  + score)
@@ -463,7 +476,8 @@ def paged_prefill_attention(q, k, v, kpool, vpool, block_row, pos0, inv_freq, sc
     prefill_workspace of that max_len); bit for bit that launch's result on the gathered cache, and the pools end up byte for byte
     as paged_decode_attention would have filled them token by token.  Only entries that cover positions 0 .. pos0 + T - 1 are read;
     the guard on entries outside [0, num_pages) is paged_decode_attention's.  window=W: prefill_attention's window; entries of pages
-    wholly below window_floor(pos0, W) may be -1.  softcap / sinks: prefill_attention's."""
+    wholly below window_floor(pos0, W) may be -1.  softcap / sinks: prefill_attention's.  129 <= T <= 256: prefill_attention's wide
+    launch on the pools."""
     who = "paged_prefill_attention"
     window, mods = _window(window, who), _score_mods(softcap, sinks, who)
     num_pages, nkv, page_size, hd = _pools(kpool, vpool, block_row, who)

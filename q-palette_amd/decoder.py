@@ -807,14 +807,18 @@ class Prefill(_Rows):
     ONE pass over every projection's weights (linear.wide_gemm: qpal_tcq_gemm_wide where the layer's format has it, else two passes
     of the 128-row launch) and two attention launches of at most 128 rows; a last chunk of 128 rows or fewer takes the existing
     launches.  Not with adapters= or MoE layers (QpalError).  Split-K atomics round differently from the 128-row passes: caches and
-    logits agree with chunk=128 to rounding, not to the bit."""
+    logits agree with chunk=128 to rounding, not to the bit.
+
+    wide_attention: False, or True with wide=: a chunk of 129 rows or more makes ONE prefill_attention call (the wide
+    launch) in every layer without a window, soft cap or sinks; such layers, and head_dim 256, keep the two launches.  The caches
+    end up byte for byte as with False, the attention output agrees to rounding."""
 
     _launches_per = "Prefill: launches are per chunk"
 
     def __init__(self, layers, embed, norm, lm_head, kcache, vcache, inv_freq, chunk=128, native_lm_head=True, sampler=None,
                  block_table=None, adapters=None, processor=None, grammar=None, window=None, softcap=None, sinks=None,
                  attn_scale=None,
-                 qkv_bias=None, qk_norm=None, mlp_act="silu", post_norms=None, logit_cap=None, wide=None):
+                 qkv_bias=None, qk_norm=None, mlp_act="silu", post_norms=None, logit_cap=None, wide=None, wide_attention=False):
         if not 1 <= int(chunk) <= 128:
             raise nat.QpalError(f"Prefill: chunk must be in 1 .. 128, got {chunk}")
         self.chunk = int(chunk)
@@ -823,6 +827,8 @@ class Prefill(_Rows):
                 raise nat.QpalError(f"Prefill: wide must be None or an int in {ops.WIDE_MIN_BATCH} .. {ops.WIDE_MAX_BATCH}, got {wide!r}")
             if adapters is not None or any(isinstance(l.mlp, MoEMLP) for l in layers):
                 raise nat.QpalError("Prefill: wide= with adapters= or MoE layers is not built")
+        if not isinstance(wide_attention, bool) or (wide_attention and wide is None):
+            raise nat.QpalError(f"Prefill: wide_attention must be False, or True together with wide=, got {wide_attention!r}")
         self.wide = wide
         self.rows = self.chunk if wide is None else wide  # rows of a full chunk
         dev, H = embed.device, embed.shape[1]
@@ -837,7 +843,9 @@ class Prefill(_Rows):
         self.last32 = torch.zeros(1, H, dtype=torch.float32, device=dev)  # the last prompt row of the residual stream
         self.slot = 0
         self.pos2 = torch.zeros(1, dtype=torch.int64, device=dev)  # wide: the position of a chunk's row 128
-        self.attn_ws = prefill_workspace(min(self.rows, 128), self.nq, self.nkv, self.head_dim, self.context, dev)
+        self.wide_attention = wide_attention and self.head_dim != 256  # (head_dim 256 has no wide launch: two launches)
+        self.attn_ws = prefill_workspace(self.rows if self.wide_attention else min(self.rows, 128), self.nq, self.nkv, self.head_dim,
+                                         self.context, dev)
 
     def _gemm(self, layers, x, **kw):
         if x.shape[0] <= 128:
@@ -850,10 +858,14 @@ class Prefill(_Rows):
             attend, cache = prefill_attention, (kc[self.slot], vc[self.slot])
         else:
             attend, cache = paged_prefill_attention, (kc, vc, self.block_table[self.slot])
+        mods = self._score(i)
+        if q.shape[0] > 128 and self.wide_attention and all(m is None for m in mods.values()):  # ONE wide launch
+            attend(q, k, v, *cache, self.pos, self._inv_freq(i), scale=self.attn_scale, out=out, ws=self.attn_ws)
+            return
         # (a wide chunk: two launches of at most 128 rows, the second from the device scalar pos + 128 behind the rows of the first)
         for r, pos in ((0, self.pos), (128, self.pos2))[:1 if q.shape[0] <= 128 else 2]:
             attend(q[r:r + 128], k[r:r + 128], v[r:r + 128], *cache, pos, self._inv_freq(i), scale=self.attn_scale, out=out[r:r + 128],
-                   ws=self.attn_ws, **self._score(i))
+                   ws=self.attn_ws, **mods)
 
     def hidden(self):
         """fp16 [1, H]: the final norm of the last prompt row"""
