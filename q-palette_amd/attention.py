@@ -54,6 +54,7 @@ as it was, bit for bit; ``sinks`` of -inf is bit for bit the launch without sink
 shared-prefix launch.  Nothing else changes: stored bytes, rules and workspaces are the plain launches'.
 """
 import math
+from typing import NamedTuple as _NamedTuple
 
 import torch
 
@@ -180,48 +181,84 @@ def decode_attention(q, k, v, kcache, vcache, pos, inv_freq, scale=None, out=Non
     if kcache.dim() != 4 or kcache.shape != vcache.shape:
         raise QpalError("decode_attention: kcache / vcache must both have shape [B, nkv, max_len, hd]")
     B, nkv, max_len, hd = kcache.shape
-    entry = "qpal_attn_rope_decode_batch" + _cache_entry(kcache, vcache, "decode_attention")
-    return _decode("decode_attention", entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, None,
-                   window=window, mods=mods)
+    _cache_entry(kcache, vcache, "decode_attention")
+    return _launch("decode_attention", _decode_family("decode_attention", pos, B, kcache.device), q, k, v, kcache, vcache, inv_freq, scale,
+                   out, ws, nkv, max_len, hd, None, window=window, mods=mods)
 
 
-def _window_args(paged, empty, kcache, rows, max_len, scale, window):
-    """the arguments of a _window entry point between inv_freq and ws: the paged arguments (`empty`: their stand-in for a contiguous
-    cache, a null table), kv_fmt, the rows' shape, max_len (paged: ignored), scale, window"""
-    head = empty + (_KV_FMT[kcache.dtype],) if paged is None else paged
-    return head + rows + (max_len if paged is None else 0, scale, window)
+class _Family(_NamedTuple):
+    """what tells the launches of one family — decode, one-sequence prefill, ragged prefill — from the others' for _launch"""
+    stem: str                  # the common name of its entry points
+    sizer: str                 # the C function that sizes its workspace, called with (rows, *sized, nq, nkv, hd, max_len) ...
+    maker: str                 # ... and the Python function that makes it, for the error text
+    front: tuple               # the position and segment tensors whose addresses go in front of inv_freq
+    dims: tuple = ()           # the dimensions of a launch between its rows and nq
+    sized: tuple = ()          # the dimensions the sizer takes there
+    pos_check: object = None   # _qkv_rows' pos_check, B and max_rows
+    B: object = None
+    max_rows: int = 128
+    paged: str = "_paged"      # the suffix of the plain entry point on a paged cache
+    kv_fmt_arg: bool = False   # the plain entry point on contiguous caches takes kv_fmt (else its name says the format)
+    no_table: tuple = (None, 0, 0, 0, 0)  # contiguous caches at a _window / _score / _wide entry point: the paged arguments' stand-in
 
 
-def _decode(who, entry, q, k, v, kcache, vcache, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd, paged, groups=None, window=None,
-            mods=(None, None)):
-    """the checks and the launch the decode entry points share; paged: None, or the arguments that take max_len's place; groups: None,
-    or the G of a shared-prefix launch (its workspace is shared_prefix_workspace's); window: None, or the W of the _window entry
-    point, which then takes `entry`'s place; mods: (softcap, sinks) — with either, the _score entry point takes it"""
+def _decode_family(who, pos, B, dev, groups=None):
+    """groups: None, or the G of a shared-prefix launch (its entry point and workspace are the _shared ones)"""
     def pos_check():
-        if pos.dtype != torch.int64 or pos.shape != (B,) or pos.device != kcache.device or not pos.is_contiguous():
-            raise QpalError(f"{who}: pos must be a contiguous int64 [{B}] tensor on {kcache.device}")
+        if pos.dtype != torch.int64 or pos.shape != (B,) or pos.device != dev or not pos.is_contiguous():
+            raise QpalError(f"{who}: pos must be a contiguous int64 [{B}] tensor on {dev}")
 
-    _, nq, ld, out, ld_out = _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos_check, B)
+    fam = _Family("qpal_attn_rope_decode_batch", "qpal_attn_batch_ws_bytes", "attention_workspace", (pos,), pos_check=pos_check, B=B)
+    if groups is None:
+        return fam
+    return fam._replace(sizer="qpal_attn_prefix_ws_bytes", maker="shared_prefix_workspace", sized=(groups,), paged="_shared")
+
+
+def _launch(who, fam, q, k, v, kcache, vcache, inv_freq, scale, out, ws, nkv, max_len, hd, paged, window=None, mods=(None, None),
+            tree=None):
+    """the checks and the launch every entry point of every family shares.  paged: None, or the arguments that take max_len's place
+    (a shared-prefix launch: with its three tensors and G).  The C entry point: fam.stem's plain one (_kv8, _paged or _shared by the
+    cache); _window with window = W; _score with mods = (softcap, sinks) where either is given; _wide above 128 rows, which takes
+    neither; tree: None, or (depth, anc) — the _tree entry points, not with a window or score modifiers"""
+    rows, nq, ld, out, ld_out = _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, fam.pos_check, fam.B, fam.max_rows)
+    plain = window is None and mods[0] is None and mods[1] is None
+    stem, sizer, front, wide = fam.stem, fam.sizer, fam.front, rows > 128
+    if wide:
+        if not plain:
+            raise QpalError(f"{who}: a launch of {rows} > 128 rows takes no window, softcap or sinks")
+        sizer = "qpal_attn_prefill_wide_ws_bytes"  # (only the one-sequence prefill family takes more than 128 rows)
+    if tree is not None:
+        if len(tree) != 2:
+            raise QpalError(f"{who}: tree must be the pair (depth, anc)")
+        if not plain:
+            raise NotImplementedError(f"{who}: tree= is not combined with window=, softcap= or sinks=")
+        for name, t in zip(("depth", "anc"), tree):
+            if t.dtype != torch.int32 or t.shape != (rows,) or not t.is_contiguous() or t.device != kcache.device:
+                raise QpalError(f"{who}: tree {name} must be a contiguous int32 [{rows}] tensor on {kcache.device}")
+        stem, front = stem + "_tree", front + tuple(tree)
     score = None if mods[0] is None and mods[1] is None else _score_args(who, mods, nq, kcache.device)  # (before the library)
     lib = _native.lib()
-    if groups is None:
-        need, maker = lib.qpal_attn_batch_ws_bytes(B, nq, nkv, hd, max_len), "attention_workspace"
-    else:
-        need, maker = lib.qpal_attn_prefix_ws_bytes(B, groups, nq, nkv, hd, max_len), "shared_prefix_workspace"
-    ws_ptr, ws_bytes = _launch_ws(who, need, ws, kcache, maker)
+    ws_ptr, ws_bytes = _launch_ws(who, getattr(lib, sizer)(rows, *fam.sized, nq, nkv, hd, max_len), ws, kcache, fam.maker)
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    if score is not None:
-        entry = "qpal_attn_rope_decode_batch_score"
-        shape = (_window_args(paged, (None, 0, 0, 0, 0), kcache, (B, nq, nkv, hd), max_len, scale, window or 0)
-                 + score)
-    elif window is None:
-        shape = ((B, nq, nkv, hd, max_len) if paged is None else paged + (B, nq, nkv, hd)) + (scale,)
+    dims = (rows,) + fam.dims + (nq, nkv, hd)
+    if wide or not plain:  # the paged arguments or their stand-in, kv_fmt, the dimensions, max_len (paged: ignored), scale
+        shape = (fam.no_table + (_KV_FMT[kcache.dtype],) if paged is None else paged) + dims + (max_len if paged is None else 0, scale)
+        if wide:  # (a shape without a wide launch, hd 256: no workspace above, QPAL_E_SHAPE here)
+            entry = stem + "_wide"
+        elif score is not None:
+            entry, shape = stem + "_score", shape + (window or 0,) + score
+        else:
+            entry, shape = stem + "_window", shape + (window,)
+    elif paged is not None:
+        entry, shape = stem + fam.paged, paged + dims + (scale,)
+    elif fam.kv_fmt_arg:
+        entry, shape = stem, (_KV_FMT[kcache.dtype],) + dims + (max_len, scale)
     else:
-        entry, shape = "qpal_attn_rope_decode_batch_window", _window_args(paged, (None, 0, 0, 0, 0), kcache, (B, nq, nkv, hd), max_len, scale, window)
+        entry, shape = stem + _CACHE_ENTRY[kcache.dtype], dims + (max_len, scale)
     with torch.cuda.device(kcache.device):
         rc = getattr(lib, entry)(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
-            pos.data_ptr(), inv_freq.data_ptr(), *shape,
+            *(t.data_ptr() for t in front), inv_freq.data_ptr(), *shape,
             ws_ptr, ws_bytes, torch.cuda.current_stream(kcache.device).cuda_stream)
     _native.check(rc, entry)
     return out
@@ -264,9 +301,9 @@ def prefill_attention(q, k, v, kcache, vcache, pos0, inv_freq, scale=None, out=N
     if kcache.dim() != 3 or kcache.shape != vcache.shape:
         raise QpalError(f"{who}: kcache / vcache must both have shape [nkv, max_len, hd]")
     nkv, max_len, hd = kcache.shape
-    entry = "qpal_attn_rope_prefill" + _cache_entry(kcache, vcache, who)
-    return _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, None, window=window,
-                    mods=mods)
+    _cache_entry(kcache, vcache, who)
+    return _launch(who, _prefill_family(who, pos0, kcache.device), q, k, v, kcache, vcache, inv_freq, scale, out, ws, nkv, max_len, hd,
+                   None, window=window, mods=mods)
 
 
 def _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos_check=None, B=None, max_rows=128):
@@ -307,42 +344,13 @@ def _launch_ws(who, need, ws, kcache, maker):
     return ws.data_ptr(), ws.numel() * ws.element_size()
 
 
-def _prefill(who, entry, q, k, v, kcache, vcache, pos0, inv_freq, scale, out, ws, nkv, max_len, hd, paged, window=None,
-             mods=(None, None)):
-    """the checks and the launch both prefill entry points share; paged: None, or the arguments that take max_len's place; window:
-    None, or the W of the _window entry point, which then takes `entry`'s place; mods: (softcap, sinks) — with either, the _score
-    entry point takes it"""
+def _prefill_family(who, pos0, dev):
     def pos_check():
-        if pos0.dtype != torch.int64 or pos0.numel() != 1 or pos0.device != kcache.device:
-            raise QpalError(f"{who}: pos0 must be an int64 tensor of one element on {kcache.device}")
+        if pos0.dtype != torch.int64 or pos0.numel() != 1 or pos0.device != dev:
+            raise QpalError(f"{who}: pos0 must be an int64 tensor of one element on {dev}")
 
-    T, nq, ld, out, ld_out = _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd, pos_check, max_rows=256)
-    wide = T > 128
-    if wide and not (window is None and mods[0] is None and mods[1] is None):
-        raise QpalError(f"{who}: a launch of {T} > 128 rows takes no window, softcap or sinks")
-    score = None if mods[0] is None and mods[1] is None else _score_args(who, mods, nq, kcache.device)  # (before the library)
-    lib = _native.lib()
-    sizer = lib.qpal_attn_prefill_wide_ws_bytes if wide else lib.qpal_attn_prefill_ws_bytes
-    ws_ptr, ws_bytes = _launch_ws(who, sizer(T, nq, nkv, hd, max_len), ws, kcache, "prefill_workspace")
-    scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    if wide:  # (a shape without a wide launch, hd 256: no workspace above, QPAL_E_SHAPE here)
-        entry = "qpal_attn_rope_prefill_wide"
-        shape = _window_args(paged, (None, 0, 0, 0), kcache, (T, nq, nkv, hd), max_len, scale, 0)[:-1]
-    elif score is not None:
-        entry = "qpal_attn_rope_prefill_score"
-        shape = (_window_args(paged, (None, 0, 0, 0), kcache, (T, nq, nkv, hd), max_len, scale, window or 0)
-                 + score)
-    elif window is None:
-        shape = ((T, nq, nkv, hd, max_len) if paged is None else paged + (T, nq, nkv, hd)) + (scale,)
-    else:
-        entry, shape = "qpal_attn_rope_prefill_window", _window_args(paged, (None, 0, 0, 0), kcache, (T, nq, nkv, hd), max_len, scale, window)
-    with torch.cuda.device(kcache.device):
-        rc = getattr(lib, entry)(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
-            pos0.data_ptr(), inv_freq.data_ptr(), *shape,
-            ws_ptr, ws_bytes, torch.cuda.current_stream(kcache.device).cuda_stream)
-    _native.check(rc, entry)
-    return out
+    return _Family("qpal_attn_rope_prefill", "qpal_attn_prefill_ws_bytes", "prefill_workspace", (pos0,), pos_check=pos_check, max_rows=256,
+                   no_table=(None, 0, 0, 0))
 
 
 PAGE_SIZES = (16, 32, 64, 128, 256)
@@ -394,7 +402,7 @@ def paged_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_freq, sc
     who = "paged_decode_attention"
     window, mods = _window(window, who), _score_mods(softcap, sinks, who)
     B, nkv, max_len, hd, paged = _pools_2d(kpool, vpool, block_table, who)
-    return _decode(who, "qpal_attn_rope_decode_batch_paged", q, k, v, kpool, vpool, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd,
+    return _launch(who, _decode_family(who, pos, B, kpool.device), q, k, v, kpool, vpool, inv_freq, scale, out, ws, nkv, max_len, hd,
                    paged, window=window, mods=mods)
 
 
@@ -465,8 +473,8 @@ def shared_prefix_decode_attention(q, k, v, kpool, vpool, block_table, pos, inv_
         raise QpalError(f"{who}: block_table must have shape [B, max_pages >= 1], got {list(block_table.shape)}")
     tensors, G = _prefix_tensors(prefix, block_table.shape[0], kpool.device, who)  # (first: these checks need no device)
     B, nkv, max_len, hd, paged = _pools_2d(kpool, vpool, block_table, who)
-    return _decode(who, "qpal_attn_rope_decode_batch_shared", q, k, v, kpool, vpool, pos, inv_freq, scale, out, ws, B, nkv, max_len, hd,
-                   paged + tensors, groups=G)
+    return _launch(who, _decode_family(who, pos, B, kpool.device, groups=G), q, k, v, kpool, vpool, inv_freq, scale, out, ws, nkv,
+                   max_len, hd, paged + tensors)
 
 
 def paged_prefill_attention(q, k, v, kpool, vpool, block_row, pos0, inv_freq, scale=None, out=None, ws=None, window=None, softcap=None,
@@ -485,8 +493,8 @@ def paged_prefill_attention(q, k, v, kpool, vpool, block_row, pos0, inv_freq, sc
         raise QpalError(f"{who}: block_row must have shape [max_pages >= 1], got {list(block_row.shape)}")
     max_pages = block_row.shape[0]
     paged = (block_row.data_ptr(), num_pages, page_size, max_pages, _KV_FMT[kpool.dtype])
-    return _prefill(who, "qpal_attn_rope_prefill_paged", q, k, v, kpool, vpool, pos0, inv_freq, scale, out, ws, nkv,
-                    max_pages * page_size, hd, paged, window=window, mods=mods)
+    return _launch(who, _prefill_family(who, pos0, kpool.device), q, k, v, kpool, vpool, inv_freq, scale, out, ws, nkv,
+                   max_pages * page_size, hd, paged, window=window, mods=mods)
 
 
 def ragged_workspace(R, S, nq, nkv, hd, max_len, device):
@@ -512,44 +520,10 @@ def _segments(who, seq, row0, pos0, dev):
     return S
 
 
-def _ragged(who, entry, q, k, v, kcache, vcache, seq, row0, pos0, S, inv_freq, scale, out, ws, B, nkv, max_len, hd, head, tail,
-            window=None, mods=(None, None), tree=None):
-    """the checks (behind _segments, which gave S) and the launch both ragged entry points share; head / tail: the arguments in
-    front of and behind (R, S, B, nq, nkv, hd); window: None, or the W of the _window entry point, which then takes `entry`'s place
-    (tail empty: a paged launch, head its paged arguments); mods: (softcap, sinks) — with either, the _score entry point takes it;
-    tree: None, or (depth, anc) — the _tree entry points, not with a window or score modifiers"""
-    R, nq, ld, out, ld_out = _qkv_rows(who, q, k, v, kcache, inv_freq, out, nkv, hd)
-    rows = ()
-    if tree is not None:
-        if len(tree) != 2:
-            raise QpalError(f"{who}: tree must be the pair (depth, anc)")
-        if window is not None or mods[0] is not None or mods[1] is not None:
-            raise NotImplementedError(f"{who}: tree= is not combined with window=, softcap= or sinks=")
-        for name, t in zip(("depth", "anc"), tree):
-            if t.dtype != torch.int32 or t.shape != (R,) or not t.is_contiguous() or t.device != kcache.device:
-                raise QpalError(f"{who}: tree {name} must be a contiguous int32 [{R}] tensor on {kcache.device}")
-        entry = entry.replace("_ragged", "_ragged_tree")
-        rows = (tree[0].data_ptr(), tree[1].data_ptr())
-    score = None if mods[0] is None and mods[1] is None else _score_args(who, mods, nq, kcache.device)  # (before the library)
-    lib = _native.lib()
-    ws_ptr, ws_bytes = _launch_ws(who, lib.qpal_attn_ragged_ws_bytes(R, S, nq, nkv, hd, max_len), ws, kcache, "ragged_workspace")
-    scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    if score is not None:
-        entry = "qpal_attn_rope_prefill_ragged_score"
-        shape = (_window_args(head if not tail else None, (None, 0, 0, 0, 0), kcache, (R, S, B, nq, nkv, hd), max_len, scale, window or 0)
-                 + score)
-    elif window is None:
-        shape = tuple(head) + (R, S, B, nq, nkv, hd) + tuple(tail) + (scale,)
-    else:
-        entry = "qpal_attn_rope_prefill_ragged_window"
-        shape = _window_args(head if not tail else None, (None, 0, 0, 0, 0), kcache, (R, S, B, nq, nkv, hd), max_len, scale, window)
-    with torch.cuda.device(kcache.device):
-        rc = getattr(lib, entry)(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), ld_out,
-            seq.data_ptr(), row0.data_ptr(), pos0.data_ptr(), *rows, inv_freq.data_ptr(), *shape,
-            ws_ptr, ws_bytes, torch.cuda.current_stream(kcache.device).cuda_stream)
-    _native.check(rc, entry)
-    return out
+def _ragged_family(seq, row0, pos0, S, B):
+    """behind _segments, which gave S"""
+    return _Family("qpal_attn_rope_prefill_ragged", "qpal_attn_ragged_ws_bytes", "ragged_workspace", (seq, row0, pos0), dims=(S, B),
+                   sized=(S,), kv_fmt_arg=True)
 
 
 def ragged_prefill_attention(q, k, v, kcache, vcache, seq, row0, pos0, inv_freq, scale=None, out=None, ws=None, window=None,
@@ -583,8 +557,8 @@ def ragged_prefill_attention(q, k, v, kcache, vcache, seq, row0, pos0, inv_freq,
     B, nkv, max_len, hd = kcache.shape
     S = _segments(who, seq, row0, pos0, kcache.device)  # (first: these checks need no device)
     _cache_entry(kcache, vcache, who)
-    return _ragged(who, "qpal_attn_rope_prefill_ragged", q, k, v, kcache, vcache, seq, row0, pos0, S, inv_freq, scale, out, ws, B,
-                   nkv, max_len, hd, (_KV_FMT[kcache.dtype],), (max_len,), window=window, mods=mods, tree=tree)
+    return _launch(who, _ragged_family(seq, row0, pos0, S, B), q, k, v, kcache, vcache, inv_freq, scale, out, ws, nkv, max_len, hd, None,
+                   window=window, mods=mods, tree=tree)
 
 
 def paged_ragged_prefill_attention(q, k, v, kpool, vpool, block_table, seq, row0, pos0, inv_freq, scale=None, out=None, ws=None,
@@ -598,9 +572,9 @@ def paged_ragged_prefill_attention(q, k, v, kpool, vpool, block_table, seq, row0
     who = "paged_ragged_prefill_attention"
     window, mods = _window(window, who), _score_mods(softcap, sinks, who)
     S = _segments(who, seq, row0, pos0, kpool.device)
-    B, nkv, max_len, hd, head = _pools_2d(kpool, vpool, block_table, who)
-    return _ragged(who, "qpal_attn_rope_prefill_ragged_paged", q, k, v, kpool, vpool, seq, row0, pos0, S, inv_freq, scale, out, ws, B,
-                   nkv, max_len, hd, head, (), window=window, mods=mods, tree=tree)
+    B, nkv, max_len, hd, paged = _pools_2d(kpool, vpool, block_table, who)
+    return _launch(who, _ragged_family(seq, row0, pos0, S, B), q, k, v, kpool, vpool, inv_freq, scale, out, ws, nkv, max_len, hd, paged,
+                   window=window, mods=mods, tree=tree)
 
 
 def kv_pointer_table(caches):

@@ -505,9 +505,6 @@ size_t batch_lds_floats(int rep, int hd, long chunk) {
     return (size_t)rep * chunk + (size_t)rep * hd / 2 + hd / 2 + hd + (size_t)nw * rep * hd + 2 * (size_t)nw * rep + 3 * rep + 4;
 }
 
-template <class CT>
-constexpr int kKvFmt = kIsKv8<CT> ? 1 : 0;  // the kv_fmt of a cache element type
-
 // the positions a windowed launch is sized for: min(max_len, window rounded up to 4) (max_len is a multiple of 4, at least 4)
 long window_positions(long window, long max_len) {
     return window >= max_len ? max_len : (window + 3) / 4 * 4;
@@ -553,72 +550,75 @@ int batch_geometry(int B, int nq, int nkv, int hd, long max_len, BatchGeometry &
     return QPAL_OK;
 }
 
-// the entry points: the same checks, geometry and launch, the cache element type and the row addressing apart (PAGED: kcache /
-// vcache are the pools, `pg` the block table, max_len = max_pages * page_size)
 // the workspace of the shared launches: the plain launch's in front, then the prefix phase's tickets, chunk partials and merged
 // partials (attn_prefix.h)
 size_t shared_ws_bytes(const BatchGeometry &g, const PrefixGeometry &x) {
     return g.ws_bytes + (x.tickets + x.part + x.pre) * sizeof(float);
 }
 
-// sp: SHARED — the sharing of the launch; the prefix launch goes first, stream order is the only synchronisation between the two
-// window: WIN — the geometry is that of min(max_len, window rounded up to 4) positions (a short window in a long cache takes no
-// split and no merge floor); its workspace is never larger than the plain launch's of max_len
-// mods: SC — the soft cap and the sinks; a launch without a window runs the windowed body with window = max_len
-template <class CT, bool PAGED, bool SHARED = false, bool WIN = false, bool SC = false>
-int attn_rope_decode_batch(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16,
-                           long ld_out, const long *pos, const float *inv_freq, int B, int nq, int nkv, int hd, long max_len,
-                           float scale, void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0,
-                           const SharedPrefixArgs *sp = nullptr, long window = 0, const ScoreMods *mods = nullptr) {
-    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
-    BatchGeometry g;
-    long geo_len = max_len;
-    if constexpr (WIN) {
-        const int rcs = attn_shape(B, nq, nkv, hd, max_len);
-        if (rcs != QPAL_OK) return rcs;
-        if constexpr (SC) {
-            if (window == 0) window = max_len;
+// The decode family of attn_launch: the same checks, geometry and launch for every entry point below, the cache element type and
+// the row addressing apart (PAGED: kcache / vcache are the pools, v.pg the block table, max_len = max_pages * page_size).
+// SHARED: sp is the sharing of the launch; the prefix launch goes first, stream order is the only synchronisation between the two
+// WIN: the geometry is that of min(max_len, window rounded up to 4) positions (a short window in a long cache takes no split and
+// no merge floor); its workspace is never larger than the plain launch's of max_len
+// SC: the soft cap and the sinks; a launch without a window runs the windowed body with window = max_len
+template <bool SHARED>
+struct DecodeBatch {
+    static constexpr bool kContig = !SHARED, kMods = !SHARED;  // groups share pages; no window in the shared-prefix launches
+    SharedPrefixArgs sp;                                       // SHARED only
+
+    bool any_null() const { return SHARED && (!sp.row_group || !sp.grp_slot || !sp.grp_len); }
+
+    template <class CT, bool PAGED, bool WIN, bool SC>
+    int launch(const AttnCall &c, const AttnVariant &v, int shift, long max_len) const {
+        const int B = c.rows;
+        BatchGeometry g;
+        long window = v.window, geo_len = max_len;
+        if constexpr (WIN) {
+            const int rcs = attn_shape(B, c.nq, c.nkv, c.hd, max_len);
+            if (rcs != QPAL_OK) return rcs;
+            if (SC && window == 0) window = max_len;
+            geo_len = window_positions(window, max_len);
         }
-        geo_len = window_positions(window, max_len);
+        const int rc = batch_geometry(B, c.nq, c.nkv, c.hd, geo_len, g);
+        if (rc != QPAL_OK) return rc;
+        [[maybe_unused]] PrefixGeometry x{};
+        const size_t plain_ws = g.ws_bytes;  // the part of the workspace the suffix launch owns
+        size_t need_ws = plain_ws;
+        uintptr_t al4 = 0;
+        if constexpr (SHARED) {
+            if (sp.G < 1 || sp.G > kPxMaxGroups) return QPAL_E_SHAPE;
+            prefix_geometry(B, sp.G, c.nq, c.nkv, c.hd, max_len, x);
+            need_ws = shared_ws_bytes(g, x);
+            al4 = reinterpret_cast<uintptr_t>(sp.row_group) | reinterpret_cast<uintptr_t>(sp.grp_slot) | reinterpret_cast<uintptr_t>(sp.grp_len);
+        }
+        const int rca = attn_args(c, v, need_ws, al4);
+        if (rca != QPAL_OK) return rca;
+        float *wsf = static_cast<float *>(c.ws);
+        AttnBatchParams<CT> p{c.q, c.k, c.v, c.ld_qkv, static_cast<CT *>(c.kcache), static_cast<CT *>(c.vcache),
+                              static_cast<uint16_t *>(c.out_f16), c.ld_out, c.pos, c.inv_freq, c.nkv, max_len, c.scale,
+                              plain_ws ? reinterpret_cast<unsigned *>(wsf) : nullptr, plain_ws ? wsf + (long)kBatchMax * c.nkv : nullptr,
+                              g.nsplit, g.chunk};
+        if constexpr (PAGED) p.table = v.pg.table, p.ld_table = v.pg.ld_table, p.num_pages = v.pg.num_pages, p.page_shift = shift;
+        if constexpr (WIN) p.window = window;
+        if constexpr (SC)
+            p.softcap = v.mods.softcap, p.inv_softcap = v.mods.softcap != 0.f ? 1.f / v.mods.softcap : 0.f, p.sinks = v.mods.sinks;
+        const int grid = B * c.nkv * g.nsplit, rep = c.nq / c.nkv;  // (nkv >= 1: the geometry has passed)
+        if constexpr (SHARED) {
+            float *xf = wsf + plain_ws / sizeof(float);
+            p.sp = sp, p.B = B, p.pre = xf + x.tickets + x.part;
+            const PrefixLaunch a{c.q, c.ld_qkv, c.kcache, c.vcache, c.pos, c.inv_freq, sp, v.pg.table, v.pg.ld_table, v.pg.num_pages, shift,
+                                 B, c.nkv, max_len, c.scale, reinterpret_cast<unsigned *>(xf), xf + x.tickets, xf + x.tickets + x.part,
+                                 x.nsplit, x.ntile};
+            const int rc2 = launch_attn_prefix(a, v.kv_fmt, c.hd, rep, c.stream);
+            if (rc2 != QPAL_OK) return rc2;
+        }
+        return for_hd_rep(c.hd, rep, [&](auto HD, auto REP) {
+            return launch_lds<attn_rope_batch_kernel<CT, PAGED, HD(), REP(), SHARED, WIN, SC>>(
+                dim3(grid), dim3(64 * kBatchNW), g.lds, (int)kBatchLdsMax, static_cast<hipStream_t>(c.stream), p);
+        });
     }
-    const int rc = batch_geometry(B, nq, nkv, hd, geo_len, g);
-    if (rc != QPAL_OK) return rc;
-    [[maybe_unused]] PrefixGeometry x{};
-    [[maybe_unused]] const size_t plain_ws = g.ws_bytes;
-    if constexpr (SHARED) {
-        if (sp->G < 1 || sp->G > kPxMaxGroups) return QPAL_E_SHAPE;
-        prefix_geometry(B, sp->G, nq, nkv, hd, max_len, x);
-        g.ws_bytes = shared_ws_bytes(g, x);  // (checked below as the plain launch's is)
-    }
-    uintptr_t al4 = PAGED ? reinterpret_cast<uintptr_t>(pg->table) : 0;
-    if constexpr (SC) al4 |= reinterpret_cast<uintptr_t>(mods->sinks);
-    if constexpr (SHARED)
-        al4 |= reinterpret_cast<uintptr_t>(sp->row_group) | reinterpret_cast<uintptr_t>(sp->grp_slot) | reinterpret_cast<uintptr_t>(sp->grp_len);
-    const int rca = attn_args(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos, inv_freq, nq, hd, g.ws_bytes, ws, ws_bytes, al4);
-    if (rca != QPAL_OK) return rca;
-    float *wsf = static_cast<float *>(ws);
-    if constexpr (SHARED) g.ws_bytes = plain_ws;  // from here on: the part of the workspace the suffix launch owns
-    AttnBatchParams<CT> p{q, k, v, ld_qkv, static_cast<CT *>(kcache), static_cast<CT *>(vcache),
-                          static_cast<uint16_t *>(out_f16), ld_out, pos, inv_freq, nkv, max_len, scale,
-                          g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr, g.ws_bytes ? wsf + (long)kBatchMax * nkv : nullptr,
-                          g.nsplit, g.chunk};
-    if constexpr (PAGED) p.table = pg->table, p.ld_table = pg->ld_table, p.num_pages = pg->num_pages, p.page_shift = shift;
-    if constexpr (WIN) p.window = window;
-    if constexpr (SC) p.softcap = mods->softcap, p.inv_softcap = mods->softcap != 0.f ? 1.f / mods->softcap : 0.f, p.sinks = mods->sinks;
-    const int grid = B * nkv * g.nsplit, rep = nq / nkv;
-    if constexpr (SHARED) {
-        float *xf = wsf + plain_ws / sizeof(float);
-        p.sp = *sp, p.B = B, p.pre = xf + x.tickets + x.part;
-        const PrefixLaunch a{q, ld_qkv, kcache, vcache, pos, inv_freq, *sp, pg->table, pg->ld_table, pg->num_pages, shift, B, nkv,
-                             max_len, scale, reinterpret_cast<unsigned *>(xf), xf + x.tickets, xf + x.tickets + x.part, x.nsplit, x.ntile};
-        const int rc2 = launch_attn_prefix(a, kKvFmt<CT>, hd, rep, stream);
-        if (rc2 != QPAL_OK) return rc2;
-    }
-    return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
-        return launch_lds<attn_rope_batch_kernel<CT, PAGED, HD(), REP(), SHARED, WIN, SC>>(dim3(grid), dim3(64 * kBatchNW), g.lds, (int)kBatchLdsMax,
-                                                                                   static_cast<hipStream_t>(stream), p);
-    });
-}
+};
 
 }  // namespace
 
@@ -635,16 +635,16 @@ extern "C" long qpal_attn_batch_ws_bytes(int B, int nq, int nkv, int hd, long ma
 extern "C" int qpal_attn_rope_decode_batch(const float *q, const float *k, const float *v, long ld_qkv, void *kcache_f16, void *vcache_f16,
                                            void *out_f16, long ld_out, const long *pos, const float *inv_freq, int B, int nq, int nkv,
                                            int hd, long max_len, float scale, void *ws, long ws_bytes, void *stream) {
-    return attn_rope_decode_batch<uint16_t, false>(q, k, v, ld_qkv, kcache_f16, vcache_f16, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd,
-                                            max_len, scale, ws, ws_bytes, stream);
+    return attn_launch({q, k, v, ld_qkv, kcache_f16, vcache_f16, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.kv_fmt = 0, .max_len = max_len}, DecodeBatch<false>{});
 }
 
 extern "C" int qpal_attn_rope_decode_batch_kv8(const float *q, const float *k, const float *v, long ld_qkv, void *kcache_e4m3,
                                                void *vcache_e4m3, void *out_f16, long ld_out, const long *pos, const float *inv_freq,
                                                int B, int nq, int nkv, int hd, long max_len, float scale, void *ws, long ws_bytes,
                                                void *stream) {
-    return attn_rope_decode_batch<uint8_t, false>(q, k, v, ld_qkv, kcache_e4m3, vcache_e4m3, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd,
-                                           max_len, scale, ws, ws_bytes, stream);
+    return attn_launch({q, k, v, ld_qkv, kcache_e4m3, vcache_e4m3, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.kv_fmt = 1, .max_len = max_len}, DecodeBatch<false>{});
 }
 
 extern "C" int qpal_attn_rope_decode_batch_paged(const float *q, const float *k, const float *v, long ld_qkv, void *kpool, void *vpool,
@@ -652,12 +652,9 @@ extern "C" int qpal_attn_rope_decode_batch_paged(const float *q, const float *k,
                                                  const int *block_table, long ld_table, int num_pages, int page_size, int max_pages,
                                                  int kv_fmt, int B, int nq, int nkv, int hd, float scale, void *ws, long ws_bytes,
                                                  void *stream) {
-    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
-    const bool any_null = !block_table || !q || !k || !v || !kpool || !vpool || !out_f16 || !pos || !inv_freq;
-    return paged_entry(any_null, pg, kv_fmt, [&](auto ct, int shift, long max_len) {
-        return attn_rope_decode_batch<decltype(ct), true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd,
-                                                          max_len, scale, ws, ws_bytes, stream, &pg, shift);
-    });
+    return attn_launch({q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.pg = {block_table, ld_table, num_pages, page_size, max_pages}, .need_table = true, .kv_fmt = kv_fmt},
+                       DecodeBatch<false>{});
 }
 
 extern "C" int qpal_attn_rope_decode_batch_window(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache,
@@ -665,25 +662,9 @@ extern "C" int qpal_attn_rope_decode_batch_window(const float *q, const float *k
                                                   const int *block_table, long ld_table, int num_pages, int page_size, int max_pages,
                                                   int kv_fmt, int B, int nq, int nkv, int hd, long max_len, float scale, long window,
                                                   void *ws, long ws_bytes, void *stream) {
-    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
-    if (window < 0) return QPAL_E_PARAM;
-    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
-    auto launch = [&](auto ct, auto paged, auto win, long len, const PageArgs *pg, int shift) {
-        return attn_rope_decode_batch<decltype(ct), paged(), false, win()>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos, inv_freq, B, nq,
-                                                                          nkv, hd, len, scale, ws, ws_bytes, stream, pg, shift, nullptr,
-                                                                          window);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    if (!block_table) {  // contiguous caches [B][nkv][max_len][hd]
-        return for_kv_fmt(kv_fmt, [&](auto ct) {
-            return window ? launch(ct, F{}, T{}, max_len, nullptr, 0) : launch(ct, F{}, F{}, max_len, nullptr, 0);
-        });
-    }
-    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
-    return paged_entry(false, pg, kv_fmt, [&](auto ct, int shift, long len) {
-        return window ? launch(ct, T{}, T{}, len, &pg, shift) : launch(ct, T{}, F{}, len, &pg, shift);
-    });
+    return attn_launch({q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.pg = {block_table, ld_table, num_pages, page_size, max_pages}, .kv_fmt = kv_fmt, .max_len = max_len, .window = window},
+                       DecodeBatch<false>{});
 }
 
 extern "C" int qpal_attn_rope_decode_batch_score(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache,
@@ -691,23 +672,10 @@ extern "C" int qpal_attn_rope_decode_batch_score(const float *q, const float *k,
                                                  const int *block_table, long ld_table, int num_pages, int page_size, int max_pages,
                                                  int kv_fmt, int B, int nq, int nkv, int hd, long max_len, float scale, long window,
                                                  float softcap, const float *sinks, void *ws, long ws_bytes, void *stream) {
-    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos || !inv_freq) return QPAL_E_NULL;
-    if (window < 0 || !score_mods_ok(softcap)) return QPAL_E_PARAM;
-    if (softcap == 0.f && !sinks)
-        return qpal_attn_rope_decode_batch_window(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos, inv_freq, block_table, ld_table,
-                                                  num_pages, page_size, max_pages, kv_fmt, B, nq, nkv, hd, max_len, scale, window, ws,
-                                                  ws_bytes, stream);
-    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
-    const ScoreMods mods{softcap, sinks};
-    auto launch = [&](auto ct, auto paged, long len, const PageArgs *pg, int shift) {
-        return attn_rope_decode_batch<decltype(ct), paged(), false, true, true>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos, inv_freq,
-                                                                               B, nq, nkv, hd, len, scale, ws, ws_bytes, stream, pg, shift,
-                                                                               nullptr, window, &mods);
-    };
-    if (!block_table)  // contiguous caches [B][nkv][max_len][hd]
-        return for_kv_fmt(kv_fmt, [&](auto ct) { return launch(ct, std::false_type{}, max_len, nullptr, 0); });
-    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
-    return paged_entry(false, pg, kv_fmt, [&](auto ct, int shift, long len) { return launch(ct, std::true_type{}, len, &pg, shift); });
+    return attn_launch({q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.pg = {block_table, ld_table, num_pages, page_size, max_pages}, .kv_fmt = kv_fmt, .max_len = max_len, .window = window,
+                        .mods = {softcap, sinks}},
+                       DecodeBatch<false>{});
 }
 
 extern "C" long qpal_attn_prefix_ws_bytes(int B, int G, int nq, int nkv, int hd, long max_len) {
@@ -723,11 +691,7 @@ extern "C" int qpal_attn_rope_decode_batch_shared(const float *q, const float *k
                                                   const int *block_table, long ld_table, int num_pages, int page_size, int max_pages,
                                                   int kv_fmt, const int *row_group, const int *grp_slot, const int *grp_len, int G, int B,
                                                   int nq, int nkv, int hd, float scale, void *ws, long ws_bytes, void *stream) {
-    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
-    const SharedPrefixArgs sp{row_group, grp_slot, grp_len, G};
-    const bool any_null = !block_table || !row_group || !grp_slot || !grp_len || !q || !k || !v || !kpool || !vpool || !out_f16 || !pos || !inv_freq;
-    return paged_entry(any_null, pg, kv_fmt, [&](auto ct, int shift, long max_len) {
-        return attn_rope_decode_batch<decltype(ct), true, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv,
-                                                                hd, max_len, scale, ws, ws_bytes, stream, &pg, shift, &sp);
-    });
+    return attn_launch({q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos, inv_freq, B, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.pg = {block_table, ld_table, num_pages, page_size, max_pages}, .need_table = true, .kv_fmt = kv_fmt},
+                       DecodeBatch<true>{{row_group, grp_slot, grp_len, G}});
 }

@@ -1,6 +1,7 @@
-// What the attention launches share (decoder_glue.hip's split-context kernel, attn_batch.hip, attn_prefill.h with attn_prefill.hip
-// and attn_ragged.hip, attn_prefix.hip): the supported head shapes, the shape rule and the argument checks of the entry points,
-// the preamble of the paged ones, and the agent-scope partial / ticket hand-over of the kernels that split a context.
+// What the attention launches share (decoder_glue.hip's split-context kernel, attn_batch.hip, attn_prefill.h with attn_prefill.hip,
+// attn_ragged.hip and attn_prefill_wide.hip, attn_prefix.hip): the supported head shapes and the shape rule; the call and variant
+// descriptors of the rope-append-attention entry points with their one preamble, variant dispatch (attn_launch) and argument
+// checks (attn_args); the soft cap; and the agent-scope partial / ticket hand-over of the kernels that split a context.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,38 +44,6 @@ inline int attn_shape(int rows, int nq, int nkv, int hd, long max_len) {
     return QPAL_OK;
 }
 
-// the argument checks those entry points share, behind the null checks and the geometry (need_ws: the workspace bytes of the
-// launch; al4: every further pointer that must be 4-byte aligned, OR-ed — the block table, the shared launch's descriptors)
-inline int attn_args(const void *q, const void *k, const void *v, long ld_qkv, const void *kcache, const void *vcache, const void *out_f16,
-                     long ld_out, const void *pos, const void *inv_freq, int nq, int hd, size_t need_ws, const void *ws, long ws_bytes,
-                     uintptr_t al4) {
-    if (ld_qkv < (long)nq * hd || ld_out < (long)nq * hd) return QPAL_E_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(kcache) | reinterpret_cast<uintptr_t>(vcache)) & 15) return QPAL_E_ALIGN;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
-         reinterpret_cast<uintptr_t>(inv_freq) | reinterpret_cast<uintptr_t>(pos)) & 3)
-        return QPAL_E_ALIGN;
-    if (reinterpret_cast<uintptr_t>(out_f16) & 1) return QPAL_E_ALIGN;
-    if (al4 & 3) return QPAL_E_ALIGN;
-    if (need_ws) {
-        if (!ws) return QPAL_E_NULL;
-        if (ws_bytes < (long)need_ws) return QPAL_E_SHAPE;
-        if (reinterpret_cast<uintptr_t>(ws) & 3) return QPAL_E_ALIGN;
-    }
-    return QPAL_OK;
-}
-
-// the preamble of a paged entry point: the null checks (any_null: the table first, then the siblings' pointers, so a null among
-// q .. inv_freq wins over a paged shape error), the paged shape, then f(CT{}, shift, max_len) with the cache element type
-template <class F>
-int paged_entry(bool any_null, const PageArgs &pg, int kv_fmt, F &&f) {
-    if (any_null) return QPAL_E_NULL;
-    int shift;
-    long max_len;
-    const int rc = paged_shape(pg, kv_fmt, shift, max_len);
-    if (rc != QPAL_OK) return rc;
-    return for_kv_fmt(kv_fmt, [&](auto ct) { return f(ct, shift, max_len); });
-}
-
 // the score modifiers of the _score entry points: softcap 0 — none; sinks null — none, else fp32 [nq] on the device
 struct ScoreMods {
     float softcap;
@@ -84,6 +53,87 @@ struct ScoreMods {
 // softcap as an argument: 0 or a finite value above it (anything else is QPAL_E_PARAM)
 inline bool score_mods_ok(float softcap) {
     return softcap >= 0.f && softcap <= 3.0e38f;
+}
+
+// ---- the entry points: every launching extern "C" function fills an AttnCall and an AttnVariant, names its family
+// and returns attn_launch's result
+
+// what every entry point receives (pos: pos [B] of a decode launch, pos0 of a prefill, pos0 [S] of a ragged one; rows: B, T or R)
+struct AttnCall {
+    const float *q, *k, *v;
+    long ld_qkv;
+    void *kcache, *vcache, *out_f16;
+    long ld_out;
+    const long *pos;
+    const float *inv_freq;
+    int rows, nq, nkv, hd;
+    float scale;
+    void *ws;
+    long ws_bytes;
+    void *stream;
+};
+
+// the cache of a call and the variant of the launch, as far as the entry point's prototype can say them
+struct AttnVariant {
+    PageArgs pg{};            // table null: contiguous caches
+    bool need_table = false;  // the _paged / _shared entry points: a null table is QPAL_E_NULL, not a contiguous cache
+    int kv_fmt = 0;
+    long max_len = 0;         // of contiguous caches; a paged launch's is max_pages * page_size
+    long window = 0;          // 0: none
+    ScoreMods mods{0.f, nullptr};
+};
+
+// the argument checks the launches share, behind attn_launch's and the geometry (need_ws: the workspace bytes of the launch; al4:
+// the family's own pointers that must be 4-byte aligned, OR-ed — the block table and the sinks are taken from v)
+inline int attn_args(const AttnCall &c, const AttnVariant &v, size_t need_ws, uintptr_t al4 = 0) {
+    auto at = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
+    if (c.ld_qkv < (long)c.nq * c.hd || c.ld_out < (long)c.nq * c.hd) return QPAL_E_SHAPE;
+    if ((at(c.kcache) | at(c.vcache)) & 15) return QPAL_E_ALIGN;
+    if ((at(c.q) | at(c.k) | at(c.v) | at(c.inv_freq) | at(c.pos)) & 3) return QPAL_E_ALIGN;
+    if (at(c.out_f16) & 1) return QPAL_E_ALIGN;
+    if ((al4 | at(v.pg.table) | at(v.mods.sinks)) & 3) return QPAL_E_ALIGN;
+    if (need_ws) {
+        if (!c.ws) return QPAL_E_NULL;
+        if (c.ws_bytes < (long)need_ws) return QPAL_E_SHAPE;
+        if (at(c.ws) & 3) return QPAL_E_ALIGN;
+    }
+    return QPAL_OK;
+}
+
+// THE preamble and variant dispatch of the entry points, in the order of the codes: a null pointer (the call's, the family's
+// own, the table where the entry point needs one) QPAL_E_NULL; window < 0 or a bad softcap QPAL_E_PARAM; kv_fmt and the paged
+// shape QPAL_E_SHAPE; then fam.launch<CT, PAGED, WIN, SC>(call, variant, log2(page_size), max_len) with the cache element type of
+// kv_fmt, PAGED for a table, SC for a softcap or sinks (on the windowed body: WIN), WIN for a window.  A family says what it has kernels
+// for — kContig: contiguous caches, kMods: windows and score modifiers — and nothing else of it is instantiated.
+template <class Family>
+int attn_launch(const AttnCall &c, const AttnVariant &v, const Family &fam) {
+    const bool paged = v.pg.table != nullptr;
+    if (!c.q || !c.k || !c.v || !c.kcache || !c.vcache || !c.out_f16 || !c.pos || !c.inv_freq || fam.any_null()) return QPAL_E_NULL;
+    if ((v.need_table || !Family::kContig) && !paged) return QPAL_E_NULL;
+    if (v.window < 0 || !score_mods_ok(v.mods.softcap)) return QPAL_E_PARAM;
+    if (v.kv_fmt != 0 && v.kv_fmt != 1) return QPAL_E_SHAPE;
+    int shift = 0;
+    long max_len = v.max_len;
+    if (paged) {
+        const int rc = paged_shape(v.pg, v.kv_fmt, shift, max_len);
+        if (rc != QPAL_OK) return rc;
+    }
+    const bool sc = v.mods.softcap != 0.f || v.mods.sinks, win = sc || v.window != 0;
+    auto variant = [&](auto ct, auto pg) {
+        using CT = decltype(ct);
+        constexpr bool PAGED = decltype(pg)::value;
+        if constexpr (Family::kMods) {
+            if (sc) return fam.template launch<CT, PAGED, true, true>(c, v, shift, max_len);
+            if (win) return fam.template launch<CT, PAGED, true, false>(c, v, shift, max_len);
+        }
+        return fam.template launch<CT, PAGED, false, false>(c, v, shift, max_len);
+    };
+    return for_kv_fmt(v.kv_fmt, [&](auto ct) {
+        if constexpr (Family::kContig) {
+            if (!paged) return variant(ct, std::false_type{});
+        }
+        return variant(ct, std::true_type{});
+    });
 }
 
 // cap * tanh(s / cap) in fp32 with tanh(x) = 1 - 2 / (exp(2 x) + 1): one v_exp_f32 and one v_rcp_f32, no branch.  x is clamped to

@@ -46,39 +46,41 @@ int prefill_geometry(int T, int nq, int nkv, int hd, long max_len, PrefillGeomet
     return QPAL_OK;
 }
 
-// the entry points: the same checks, geometry and launch, the cache element type and the row addressing apart (PAGED: kcache /
-// vcache are the pools, `pg` the sequence's block-table row, max_len = max_pages * page_size)
-// mods: SC — the soft cap and the sinks; a launch without a window runs the windowed body with window = max_len
-template <class CT, bool PAGED, bool WIN = false, bool SC = false>
-int attn_rope_prefill(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16,
-                      long ld_out, const long *pos0, const float *inv_freq, int T, int nq, int nkv, int hd, long max_len, float scale,
-                      void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0, long window = 0,
-                      const ScoreMods *mods = nullptr) {
-    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos0 || !inv_freq) return QPAL_E_NULL;
-    if constexpr (SC) {
-        if (window == 0) window = max_len;
+// The one-sequence prefill family of attn_launch: the same checks, geometry and launch for every entry point below, the cache
+// element type and the row addressing apart (PAGED: kcache / vcache are the pools, v.pg the sequence's block-table row, max_len =
+// max_pages * page_size)
+// SC: the soft cap and the sinks; a launch without a window runs the windowed body with window = max_len
+struct Prefill {
+    static constexpr bool kContig = true, kMods = true;
+
+    bool any_null() const { return false; }
+
+    template <class CT, bool PAGED, bool WIN, bool SC>
+    int launch(const AttnCall &c, const AttnVariant &v, int shift, long max_len) const {
+        const int T = c.rows;
+        const long window = SC && v.window == 0 ? max_len : v.window;
+        PrefillGeometry g;
+        int rc = prefill_geometry(T, c.nq, c.nkv, c.hd, max_len, g, WIN ? window : 0);
+        if (rc != QPAL_OK) return rc;
+        rc = attn_args(c, v, g.ws_bytes);
+        if (rc != QPAL_OK) return rc;
+        float *wsf = static_cast<float *>(c.ws);
+        AttnPrefillParams<CT> p{c.q, c.k, c.v, c.ld_qkv, static_cast<CT *>(c.kcache), static_cast<CT *>(c.vcache),
+                                static_cast<uint16_t *>(c.out_f16), c.ld_out, c.pos, c.inv_freq, T, c.nkv, max_len, c.scale,
+                                g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr,
+                                g.ws_bytes ? wsf + (long)c.nkv * kPfMaxTiles : nullptr, g.nsplit, g.ntile};
+        if constexpr (PAGED) p.table = v.pg.table, p.num_pages = v.pg.num_pages, p.page_shift = shift;
+        if constexpr (WIN) p.window = window;
+        if constexpr (SC)
+            p.softcap = v.mods.softcap, p.inv_softcap = v.mods.softcap != 0.f ? 1.f / v.mods.softcap : 0.f, p.sinks = v.mods.sinks;
+        const int grid = c.nkv * g.ntile * g.nsplit;
+        return for_hd_rep(c.hd, c.nq / c.nkv, [&](auto HD, auto REP) {
+            hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, false, HD(), REP(), WIN, SC>), dim3(grid), dim3(64 * REP() * pf_qs(REP())), 0,
+                               static_cast<hipStream_t>(c.stream), p);
+            return (int)hipGetLastError();
+        });
     }
-    PrefillGeometry g;
-    int rc = prefill_geometry(T, nq, nkv, hd, max_len, g, WIN ? window : 0);
-    if (rc != QPAL_OK) return rc;
-    rc = attn_args(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, nq, hd, g.ws_bytes, ws, ws_bytes,
-                   (PAGED ? reinterpret_cast<uintptr_t>(pg->table) : 0) | (SC ? reinterpret_cast<uintptr_t>(mods->sinks) : 0));
-    if (rc != QPAL_OK) return rc;
-    float *wsf = static_cast<float *>(ws);
-    AttnPrefillParams<CT> p{q, k, v, ld_qkv, static_cast<CT *>(kcache), static_cast<CT *>(vcache),
-                            static_cast<uint16_t *>(out_f16), ld_out, pos0, inv_freq, T, nkv, max_len, scale,
-                            g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr, g.ws_bytes ? wsf + (long)nkv * kPfMaxTiles : nullptr,
-                            g.nsplit, g.ntile};
-    if constexpr (PAGED) p.table = pg->table, p.num_pages = pg->num_pages, p.page_shift = shift;
-    if constexpr (WIN) p.window = window;
-    if constexpr (SC) p.softcap = mods->softcap, p.inv_softcap = mods->softcap != 0.f ? 1.f / mods->softcap : 0.f, p.sinks = mods->sinks;
-    const int grid = nkv * g.ntile * g.nsplit, rep = nq / nkv;
-    return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
-        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, false, HD(), REP(), WIN, SC>), dim3(grid), dim3(64 * REP() * pf_qs(REP())), 0,
-                           static_cast<hipStream_t>(stream), p);
-        return (int)hipGetLastError();
-    });
-}
+};
 
 }  // namespace
 
@@ -95,51 +97,32 @@ extern "C" long qpal_attn_prefill_ws_bytes(int T, int nq, int nkv, int hd, long 
 extern "C" int qpal_attn_rope_prefill(const float *q, const float *k, const float *v, long ld_qkv, void *kcache_f16, void *vcache_f16,
                                       void *out_f16, long ld_out, const long *pos0, const float *inv_freq, int T, int nq, int nkv,
                                       int hd, long max_len, float scale, void *ws, long ws_bytes, void *stream) {
-    return attn_rope_prefill<uint16_t, false>(q, k, v, ld_qkv, kcache_f16, vcache_f16, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, max_len,
-                                       scale, ws, ws_bytes, stream);
+    return attn_launch({q, k, v, ld_qkv, kcache_f16, vcache_f16, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.kv_fmt = 0, .max_len = max_len}, Prefill{});
 }
 
 extern "C" int qpal_attn_rope_prefill_kv8(const float *q, const float *k, const float *v, long ld_qkv, void *kcache_e4m3,
                                           void *vcache_e4m3, void *out_f16, long ld_out, const long *pos0, const float *inv_freq, int T,
                                           int nq, int nkv, int hd, long max_len, float scale, void *ws, long ws_bytes, void *stream) {
-    return attn_rope_prefill<uint8_t, false>(q, k, v, ld_qkv, kcache_e4m3, vcache_e4m3, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, max_len,
-                                      scale, ws, ws_bytes, stream);
+    return attn_launch({q, k, v, ld_qkv, kcache_e4m3, vcache_e4m3, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.kv_fmt = 1, .max_len = max_len}, Prefill{});
 }
 
 extern "C" int qpal_attn_rope_prefill_paged(const float *q, const float *k, const float *v, long ld_qkv, void *kpool, void *vpool,
                                             void *out_f16, long ld_out, const long *pos0, const float *inv_freq, const int *block_row,
                                             int num_pages, int page_size, int max_pages, int kv_fmt, int T, int nq, int nkv, int hd,
                                             float scale, void *ws, long ws_bytes, void *stream) {
-    const PageArgs pg{block_row, max_pages, num_pages, page_size, max_pages};
-    const bool any_null = !block_row || !q || !k || !v || !kpool || !vpool || !out_f16 || !pos0 || !inv_freq;
-    return paged_entry(any_null, pg, kv_fmt, [&](auto ct, int shift, long max_len) {
-        return attn_rope_prefill<decltype(ct), true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, max_len,
-                                                     scale, ws, ws_bytes, stream, &pg, shift);
-    });
+    return attn_launch({q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.pg = {block_row, max_pages, num_pages, page_size, max_pages}, .need_table = true, .kv_fmt = kv_fmt}, Prefill{});
 }
 
 extern "C" int qpal_attn_rope_prefill_window(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache,
                                              void *out_f16, long ld_out, const long *pos0, const float *inv_freq, const int *block_row,
                                              int num_pages, int page_size, int max_pages, int kv_fmt, int T, int nq, int nkv, int hd,
                                              long max_len, float scale, long window, void *ws, long ws_bytes, void *stream) {
-    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos0 || !inv_freq) return QPAL_E_NULL;
-    if (window < 0) return QPAL_E_PARAM;
-    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
-    auto launch = [&](auto ct, auto paged, auto win, long len, const PageArgs *pg, int shift) {
-        return attn_rope_prefill<decltype(ct), paged(), win()>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd,
-                                                              len, scale, ws, ws_bytes, stream, pg, shift, window);
-    };
-    using Y = std::true_type;
-    using N = std::false_type;
-    if (!block_row) {  // a contiguous cache [nkv][max_len][hd]
-        return for_kv_fmt(kv_fmt, [&](auto ct) {
-            return window ? launch(ct, N{}, Y{}, max_len, nullptr, 0) : launch(ct, N{}, N{}, max_len, nullptr, 0);
-        });
-    }
-    const PageArgs pg{block_row, max_pages, num_pages, page_size, max_pages};
-    return paged_entry(false, pg, kv_fmt, [&](auto ct, int shift, long len) {
-        return window ? launch(ct, Y{}, Y{}, len, &pg, shift) : launch(ct, Y{}, N{}, len, &pg, shift);
-    });
+    return attn_launch({q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.pg = {block_row, max_pages, num_pages, page_size, max_pages}, .kv_fmt = kv_fmt, .max_len = max_len, .window = window},
+                       Prefill{});
 }
 
 extern "C" int qpal_attn_rope_prefill_score(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache,
@@ -147,19 +130,8 @@ extern "C" int qpal_attn_rope_prefill_score(const float *q, const float *k, cons
                                             int num_pages, int page_size, int max_pages, int kv_fmt, int T, int nq, int nkv, int hd,
                                             long max_len, float scale, long window, float softcap, const float *sinks, void *ws,
                                             long ws_bytes, void *stream) {
-    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos0 || !inv_freq) return QPAL_E_NULL;
-    if (window < 0 || !score_mods_ok(softcap)) return QPAL_E_PARAM;
-    if (softcap == 0.f && !sinks)
-        return qpal_attn_rope_prefill_window(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, block_row, num_pages,
-                                             page_size, max_pages, kv_fmt, T, nq, nkv, hd, max_len, scale, window, ws, ws_bytes, stream);
-    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
-    const ScoreMods mods{softcap, sinks};
-    auto launch = [&](auto ct, auto paged, long len, const PageArgs *pg, int shift) {
-        return attn_rope_prefill<decltype(ct), paged(), true, true>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, T, nq,
-                                                                   nkv, hd, len, scale, ws, ws_bytes, stream, pg, shift, window, &mods);
-    };
-    if (!block_row)  // a contiguous cache [nkv][max_len][hd]
-        return for_kv_fmt(kv_fmt, [&](auto ct) { return launch(ct, std::false_type{}, max_len, nullptr, 0); });
-    const PageArgs pg{block_row, max_pages, num_pages, page_size, max_pages};
-    return paged_entry(false, pg, kv_fmt, [&](auto ct, int shift, long len) { return launch(ct, std::true_type{}, len, &pg, shift); });
+    return attn_launch({q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.pg = {block_row, max_pages, num_pages, page_size, max_pages}, .kv_fmt = kv_fmt, .max_len = max_len, .window = window,
+                        .mods = {softcap, sinks}},
+                       Prefill{});
 }

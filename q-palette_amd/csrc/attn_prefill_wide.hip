@@ -383,6 +383,42 @@ int wide_geometry(int T, int nq, int nkv, int hd, long max_len, WideGeometry &g)
     return QPAL_OK;
 }
 
+// the wide family of attn_launch: no windows and no score modifiers; both launches on c.stream
+struct PrefillWide {
+    static constexpr bool kContig = true, kMods = false;
+
+    bool any_null() const { return false; }
+
+    template <class CT, bool PAGED, bool, bool>
+    int launch(const AttnCall &c, const AttnVariant &v, int shift, long max_len) const {
+        const int T = c.rows, nq = c.nq, nkv = c.nkv;
+        WideGeometry g;
+        int rc = wide_geometry(T, nq, nkv, c.hd, max_len, g);
+        if (rc != QPAL_OK) return rc;
+        rc = attn_args(c, v, g.ws_bytes);
+        if (rc != QPAL_OK) return rc;
+        if (reinterpret_cast<uintptr_t>(c.ws) & 15) return QPAL_E_ALIGN;  // the q scratch is read 16 bytes at a time
+        unsigned char *wsb = static_cast<unsigned char *>(c.ws);
+        uint16_t *qs = reinterpret_cast<uint16_t *>(wsb + g.qs_off);
+        const int grid = nkv * g.ntile * g.nsplit, rope_grid = (T * (nq + 2 * nkv) * (c.hd / 8) + 255) / 256;
+        AttnPrefillParams<CT> p{c.q, c.k, c.v, c.ld_qkv, static_cast<CT *>(c.kcache), static_cast<CT *>(c.vcache),
+                                static_cast<uint16_t *>(c.out_f16), c.ld_out, c.pos, c.inv_freq, T, nkv, max_len, c.scale,
+                                reinterpret_cast<unsigned *>(wsb), reinterpret_cast<float *>(wsb + g.part_off), g.nsplit, g.ntile};
+        p.table = v.pg.table, p.num_pages = v.pg.num_pages, p.page_shift = shift;
+        return for_hd_rep(c.hd, nq / nkv, [&](auto HD, auto REP) {
+            if constexpr (HD() == 256) {
+                return (int)QPAL_E_SHAPE;
+            } else {
+                hipLaunchKernelGGL((rope_append_wide_kernel<CT, PAGED, HD()>), dim3(rope_grid), dim3(256), 0,
+                                   static_cast<hipStream_t>(c.stream), p, qs, nq);
+                hipLaunchKernelGGL((attn_prefill_wide_kernel<CT, PAGED, HD(), REP()>), dim3(grid), dim3(64 * REP() * pw_qs(REP())), 0,
+                                   static_cast<hipStream_t>(c.stream), p, static_cast<const uint16_t *>(qs), nq);
+                return (int)hipGetLastError();
+            }
+        });
+    }
+};
+
 }  // namespace
 
 }  // namespace qpal
@@ -399,43 +435,6 @@ extern "C" int qpal_attn_rope_prefill_wide(const float *q, const float *k, const
                                            void *out_f16, long ld_out, const long *pos0, const float *inv_freq, const int *block_row,
                                            int num_pages, int page_size, int max_pages, int kv_fmt, int T, int nq, int nkv, int hd,
                                            long max_len, float scale, void *ws, long ws_bytes, void *stream) {
-    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !pos0 || !inv_freq) return QPAL_E_NULL;
-    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
-    int shift = 0;
-    if (block_row) {
-        const PageArgs pg{block_row, max_pages, num_pages, page_size, max_pages};
-        const int rc = paged_shape(pg, kv_fmt, shift, max_len);
-        if (rc != QPAL_OK) return rc;
-    }
-    WideGeometry g;
-    int rc = wide_geometry(T, nq, nkv, hd, max_len, g);
-    if (rc != QPAL_OK) return rc;
-    rc = attn_args(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, nq, hd, g.ws_bytes, ws, ws_bytes,
-                   reinterpret_cast<uintptr_t>(block_row));
-    if (rc != QPAL_OK) return rc;
-    if (reinterpret_cast<uintptr_t>(ws) & 15) return QPAL_E_ALIGN;  // the q scratch is read 16 bytes at a time
-    unsigned char *wsb = static_cast<unsigned char *>(ws);
-    uint16_t *qs = reinterpret_cast<uint16_t *>(wsb + g.qs_off);
-    const int rep = nq / nkv, grid = nkv * g.ntile * g.nsplit;
-    const int rope_grid = (T * (nq + 2 * nkv) * (hd / 8) + 255) / 256;
-    auto launch = [&](auto ct, auto paged) {
-        using CT = decltype(ct);
-        constexpr bool PAGED = decltype(paged)::value;
-        AttnPrefillParams<CT> p{q, k, v, ld_qkv, static_cast<CT *>(kcache), static_cast<CT *>(vcache), static_cast<uint16_t *>(out_f16),
-                                ld_out, pos0, inv_freq, T, nkv, max_len, scale, reinterpret_cast<unsigned *>(wsb),
-                                reinterpret_cast<float *>(wsb + g.part_off), g.nsplit, g.ntile};
-        p.table = block_row, p.num_pages = num_pages, p.page_shift = shift;
-        return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
-            if constexpr (HD() == 256) {
-                return (int)QPAL_E_SHAPE;
-            } else {
-                hipLaunchKernelGGL((rope_append_wide_kernel<CT, PAGED, HD()>), dim3(rope_grid), dim3(256), 0,
-                                   static_cast<hipStream_t>(stream), p, qs, nq);
-                hipLaunchKernelGGL((attn_prefill_wide_kernel<CT, PAGED, HD(), REP()>), dim3(grid), dim3(64 * REP() * pw_qs(REP())), 0,
-                                   static_cast<hipStream_t>(stream), p, static_cast<const uint16_t *>(qs), nq);
-                return (int)hipGetLastError();
-            }
-        });
-    };
-    return for_kv_fmt(kv_fmt, [&](auto ct) { return block_row ? launch(ct, std::true_type{}) : launch(ct, std::false_type{}); });
+    return attn_launch({q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, T, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.pg = {block_row, max_pages, num_pages, page_size, max_pages}, .kv_fmt = kv_fmt, .max_len = max_len}, PrefillWide{});
 }

@@ -38,44 +38,51 @@ struct TreeArgs {
     const unsigned *anc;
 };
 
-// mods: SC — the soft cap and the sinks; a launch without a window runs the windowed body with window = max_len
-template <class CT, bool PAGED, bool WIN = false, bool SC = false, bool TREE = false>
-int attn_rope_ragged(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache, void *out_f16, long ld_out,
-                     const int *seq, const int *row0, const long *pos0, const float *inv_freq, int R, int S, int B, int nq, int nkv, int hd,
-                     long max_len, float scale, void *ws, long ws_bytes, void *stream, const PageArgs *pg = nullptr, int shift = 0,
-                     long window = 0, const ScoreMods *mods = nullptr, const TreeArgs *tree = nullptr) {
-    if constexpr (SC) {
-        if (window == 0) window = max_len;
+// The ragged family of attn_launch (c.rows = R, c.pos = pos0 [S]); TREE: the _tree entry points, without windows or score modifiers
+// SC: the soft cap and the sinks; a launch without a window runs the windowed body with window = max_len
+template <bool TREE>
+struct Ragged {
+    static constexpr bool kContig = true, kMods = !TREE;
+    const int *seq, *row0;
+    int S, B;
+    TreeArgs tree;  // TREE only
+
+    bool any_null() const { return !seq || !row0 || (TREE && (!tree.depth || !tree.anc)); }
+
+    template <class CT, bool PAGED, bool WIN, bool SC>
+    int launch(const AttnCall &c, const AttnVariant &v, int shift, long max_len) const {
+        const int R = c.rows;
+        const long window = SC && v.window == 0 ? max_len : v.window;
+        PrefillGeometry g;
+        int rc = ragged_geometry(R, S, c.nq, c.nkv, c.hd, max_len, g, WIN ? window : 0);
+        if (rc != QPAL_OK) return rc;
+        if (B < 1) return QPAL_E_SHAPE;
+        rc = attn_args(c, v, g.ws_bytes);
+        if (rc != QPAL_OK) return rc;
+        if ((reinterpret_cast<uintptr_t>(seq) | reinterpret_cast<uintptr_t>(row0)) & 3) return QPAL_E_ALIGN;
+        if constexpr (TREE) {
+            if ((reinterpret_cast<uintptr_t>(tree.depth) | reinterpret_cast<uintptr_t>(tree.anc)) & 3) return QPAL_E_ALIGN;
+        }
+        float *wsf = static_cast<float *>(c.ws);
+        AttnRaggedParams<CT> p{};
+        static_cast<AttnPrefillParams<CT> &>(p) = AttnPrefillParams<CT>{
+            c.q, c.k, c.v, c.ld_qkv, static_cast<CT *>(c.kcache), static_cast<CT *>(c.vcache), static_cast<uint16_t *>(c.out_f16), c.ld_out,
+            c.pos, c.inv_freq, R, c.nkv, max_len, c.scale, g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr,
+            g.ws_bytes ? wsf + (long)c.nkv * kPfRaggedTiles : nullptr, g.nsplit, g.ntile};
+        p.seq = seq, p.row0 = row0, p.S = S, p.B = B;
+        if constexpr (PAGED) p.table = v.pg.table, p.num_pages = v.pg.num_pages, p.page_shift = shift, p.ld_table = v.pg.ld_table;
+        if constexpr (WIN) p.window = window;
+        if constexpr (SC)
+            p.softcap = v.mods.softcap, p.inv_softcap = v.mods.softcap != 0.f ? 1.f / v.mods.softcap : 0.f, p.sinks = v.mods.sinks;
+        if constexpr (TREE) p.depth = tree.depth, p.anc = tree.anc;
+        const int grid = c.nkv * g.ntile * g.nsplit;
+        return for_hd_rep(c.hd, c.nq / c.nkv, [&](auto HD, auto REP) {
+            hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, true, HD(), REP(), WIN, SC, TREE>), dim3(grid), dim3(64 * REP() * pf_qs(REP())),
+                               0, static_cast<hipStream_t>(c.stream), p);
+            return (int)hipGetLastError();
+        });
     }
-    PrefillGeometry g;
-    int rc = ragged_geometry(R, S, nq, nkv, hd, max_len, g, WIN ? window : 0);
-    if (rc != QPAL_OK) return rc;
-    if (B < 1) return QPAL_E_SHAPE;
-    rc = attn_args(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, nq, hd, g.ws_bytes, ws, ws_bytes,
-                   (PAGED ? reinterpret_cast<uintptr_t>(pg->table) : 0) | (SC ? reinterpret_cast<uintptr_t>(mods->sinks) : 0));
-    if (rc != QPAL_OK) return rc;
-    if ((reinterpret_cast<uintptr_t>(seq) | reinterpret_cast<uintptr_t>(row0)) & 3) return QPAL_E_ALIGN;
-    if constexpr (TREE) {
-        if ((reinterpret_cast<uintptr_t>(tree->depth) | reinterpret_cast<uintptr_t>(tree->anc)) & 3) return QPAL_E_ALIGN;
-    }
-    float *wsf = static_cast<float *>(ws);
-    AttnRaggedParams<CT> p{};
-    static_cast<AttnPrefillParams<CT> &>(p) = AttnPrefillParams<CT>{
-        q, k, v, ld_qkv, static_cast<CT *>(kcache), static_cast<CT *>(vcache), static_cast<uint16_t *>(out_f16), ld_out, pos0, inv_freq,
-        R, nkv, max_len, scale, g.ws_bytes ? reinterpret_cast<unsigned *>(wsf) : nullptr,
-        g.ws_bytes ? wsf + (long)nkv * kPfRaggedTiles : nullptr, g.nsplit, g.ntile};
-    p.seq = seq, p.row0 = row0, p.S = S, p.B = B;
-    if constexpr (PAGED) p.table = pg->table, p.num_pages = pg->num_pages, p.page_shift = shift, p.ld_table = pg->ld_table;
-    if constexpr (WIN) p.window = window;
-    if constexpr (SC) p.softcap = mods->softcap, p.inv_softcap = mods->softcap != 0.f ? 1.f / mods->softcap : 0.f, p.sinks = mods->sinks;
-    if constexpr (TREE) p.depth = tree->depth, p.anc = tree->anc;
-    const int grid = nkv * g.ntile * g.nsplit, rep = nq / nkv;
-    return for_hd_rep(hd, rep, [&](auto HD, auto REP) {
-        hipLaunchKernelGGL((attn_prefill_kernel<CT, PAGED, true, HD(), REP(), WIN, SC, TREE>), dim3(grid), dim3(64 * REP() * pf_qs(REP())), 0,
-                           static_cast<hipStream_t>(stream), p);
-        return (int)hipGetLastError();
-    });
-}
+};
 
 }  // namespace
 
@@ -93,12 +100,8 @@ extern "C" int qpal_attn_rope_prefill_ragged(const float *q, const float *k, con
                                              void *out_f16, long ld_out, const int *seq, const int *row0, const long *pos0,
                                              const float *inv_freq, int kv_fmt, int R, int S, int B, int nq, int nkv, int hd, long max_len,
                                              float scale, void *ws, long ws_bytes, void *stream) {
-    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !seq || !row0 || !pos0 || !inv_freq) return QPAL_E_NULL;
-    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
-    return for_kv_fmt(kv_fmt, [&](auto ct) {
-        return attn_rope_ragged<decltype(ct), false>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B, nq,
-                                                     nkv, hd, max_len, scale, ws, ws_bytes, stream);
-    });
+    return attn_launch({q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, R, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.kv_fmt = kv_fmt, .max_len = max_len}, Ragged<false>{seq, row0, S, B});
 }
 
 extern "C" int qpal_attn_rope_prefill_ragged_paged(const float *q, const float *k, const float *v, long ld_qkv, void *kpool, void *vpool,
@@ -106,12 +109,9 @@ extern "C" int qpal_attn_rope_prefill_ragged_paged(const float *q, const float *
                                                    const float *inv_freq, const int *block_table, long ld_table, int num_pages,
                                                    int page_size, int max_pages, int kv_fmt, int R, int S, int B, int nq, int nkv, int hd,
                                                    float scale, void *ws, long ws_bytes, void *stream) {
-    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
-    const bool any_null = !block_table || !q || !k || !v || !kpool || !vpool || !out_f16 || !seq || !row0 || !pos0 || !inv_freq;
-    return paged_entry(any_null, pg, kv_fmt, [&](auto ct, int shift, long max_len) {
-        return attn_rope_ragged<decltype(ct), true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B, nq, nkv,
-                                                    hd, max_len, scale, ws, ws_bytes, stream, &pg, shift);
-    });
+    return attn_launch({q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos0, inv_freq, R, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.pg = {block_table, ld_table, num_pages, page_size, max_pages}, .need_table = true, .kv_fmt = kv_fmt},
+                       Ragged<false>{seq, row0, S, B});
 }
 
 // Draft trees: the two launches above with depth int32 [R] and anc uint32 [R] behind pos0
@@ -120,14 +120,8 @@ extern "C" int qpal_attn_rope_prefill_ragged_tree(const float *q, const float *k
                                                   const int *depth, const unsigned *anc, const float *inv_freq, int kv_fmt, int R, int S,
                                                   int B, int nq, int nkv, int hd, long max_len, float scale, void *ws, long ws_bytes,
                                                   void *stream) {
-    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !seq || !row0 || !pos0 || !depth || !anc || !inv_freq) return QPAL_E_NULL;
-    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
-    const TreeArgs tree{depth, anc};
-    return for_kv_fmt(kv_fmt, [&](auto ct) {
-        return attn_rope_ragged<decltype(ct), false, false, false, true>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, seq, row0, pos0,
-                                                                         inv_freq, R, S, B, nq, nkv, hd, max_len, scale, ws, ws_bytes, stream,
-                                                                         nullptr, 0, 0, nullptr, &tree);
-    });
+    return attn_launch({q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, R, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.kv_fmt = kv_fmt, .max_len = max_len}, Ragged<true>{seq, row0, S, B, {depth, anc}});
 }
 
 extern "C" int qpal_attn_rope_prefill_ragged_tree_paged(const float *q, const float *k, const float *v, long ld_qkv, void *kpool,
@@ -136,15 +130,9 @@ extern "C" int qpal_attn_rope_prefill_ragged_tree_paged(const float *q, const fl
                                                         const int *block_table, long ld_table, int num_pages, int page_size, int max_pages,
                                                         int kv_fmt, int R, int S, int B, int nq, int nkv, int hd, float scale, void *ws,
                                                         long ws_bytes, void *stream) {
-    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
-    const bool any_null =
-        !block_table || !q || !k || !v || !kpool || !vpool || !out_f16 || !seq || !row0 || !pos0 || !depth || !anc || !inv_freq;
-    const TreeArgs tree{depth, anc};
-    return paged_entry(any_null, pg, kv_fmt, [&](auto ct, int shift, long max_len) {
-        return attn_rope_ragged<decltype(ct), true, false, false, true>(q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, seq, row0, pos0,
-                                                                        inv_freq, R, S, B, nq, nkv, hd, max_len, scale, ws, ws_bytes, stream,
-                                                                        &pg, shift, 0, nullptr, &tree);
-    });
+    return attn_launch({q, k, v, ld_qkv, kpool, vpool, out_f16, ld_out, pos0, inv_freq, R, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.pg = {block_table, ld_table, num_pages, page_size, max_pages}, .need_table = true, .kv_fmt = kv_fmt},
+                       Ragged<true>{seq, row0, S, B, {depth, anc}});
 }
 
 extern "C" int qpal_attn_rope_prefill_ragged_window(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache,
@@ -152,24 +140,9 @@ extern "C" int qpal_attn_rope_prefill_ragged_window(const float *q, const float 
                                                     const float *inv_freq, const int *block_table, long ld_table, int num_pages,
                                                     int page_size, int max_pages, int kv_fmt, int R, int S, int B, int nq, int nkv, int hd,
                                                     long max_len, float scale, long window, void *ws, long ws_bytes, void *stream) {
-    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !seq || !row0 || !pos0 || !inv_freq) return QPAL_E_NULL;
-    if (window < 0) return QPAL_E_PARAM;
-    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
-    auto launch = [&](auto ct, auto paged, auto win, long len, const PageArgs *pg, int shift) {
-        return attn_rope_ragged<decltype(ct), paged(), win()>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, seq, row0, pos0, inv_freq, R, S, B,
-                                                             nq, nkv, hd, len, scale, ws, ws_bytes, stream, pg, shift, window);
-    };
-    using Y = std::true_type;
-    using N = std::false_type;
-    if (!block_table) {  // contiguous caches [B][nkv][max_len][hd]
-        return for_kv_fmt(kv_fmt, [&](auto ct) {
-            return window ? launch(ct, N{}, Y{}, max_len, nullptr, 0) : launch(ct, N{}, N{}, max_len, nullptr, 0);
-        });
-    }
-    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
-    return paged_entry(false, pg, kv_fmt, [&](auto ct, int shift, long len) {
-        return window ? launch(ct, Y{}, Y{}, len, &pg, shift) : launch(ct, Y{}, N{}, len, &pg, shift);
-    });
+    return attn_launch({q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, R, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.pg = {block_table, ld_table, num_pages, page_size, max_pages}, .kv_fmt = kv_fmt, .max_len = max_len, .window = window},
+                       Ragged<false>{seq, row0, S, B});
 }
 
 extern "C" int qpal_attn_rope_prefill_ragged_score(const float *q, const float *k, const float *v, long ld_qkv, void *kcache, void *vcache,
@@ -178,21 +151,8 @@ extern "C" int qpal_attn_rope_prefill_ragged_score(const float *q, const float *
                                                    int page_size, int max_pages, int kv_fmt, int R, int S, int B, int nq, int nkv, int hd,
                                                    long max_len, float scale, long window, float softcap, const float *sinks, void *ws,
                                                    long ws_bytes, void *stream) {
-    if (!q || !k || !v || !kcache || !vcache || !out_f16 || !seq || !row0 || !pos0 || !inv_freq) return QPAL_E_NULL;
-    if (window < 0 || !score_mods_ok(softcap)) return QPAL_E_PARAM;
-    if (softcap == 0.f && !sinks)
-        return qpal_attn_rope_prefill_ragged_window(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, seq, row0, pos0, inv_freq, block_table,
-                                                    ld_table, num_pages, page_size, max_pages, kv_fmt, R, S, B, nq, nkv, hd, max_len, scale,
-                                                    window, ws, ws_bytes, stream);
-    if (kv_fmt != 0 && kv_fmt != 1) return QPAL_E_SHAPE;
-    const ScoreMods mods{softcap, sinks};
-    auto launch = [&](auto ct, auto paged, long len, const PageArgs *pg, int shift) {
-        return attn_rope_ragged<decltype(ct), paged(), true, true>(q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, seq, row0, pos0, inv_freq, R,
-                                                                  S, B, nq, nkv, hd, len, scale, ws, ws_bytes, stream, pg, shift, window,
-                                                                  &mods);
-    };
-    if (!block_table)  // contiguous caches [B][nkv][max_len][hd]
-        return for_kv_fmt(kv_fmt, [&](auto ct) { return launch(ct, std::false_type{}, max_len, nullptr, 0); });
-    const PageArgs pg{block_table, ld_table, num_pages, page_size, max_pages};
-    return paged_entry(false, pg, kv_fmt, [&](auto ct, int shift, long len) { return launch(ct, std::true_type{}, len, &pg, shift); });
+    return attn_launch({q, k, v, ld_qkv, kcache, vcache, out_f16, ld_out, pos0, inv_freq, R, nq, nkv, hd, scale, ws, ws_bytes, stream},
+                       {.pg = {block_table, ld_table, num_pages, page_size, max_pages}, .kv_fmt = kv_fmt, .max_len = max_len, .window = window,
+                        .mods = {softcap, sinks}},
+                       Ragged<false>{seq, row0, S, B});
 }
