@@ -1129,6 +1129,23 @@ int qpal_moe_gemm(float *out, long ldo, int out_rows, const qpal_moe_proj *proj,
  * qpal_tcq_gemv_multi over at most 128 rows each (qpalette_amd.linear.wide_gemm does that).  Never synchronises.              */
 int qpal_tcq_gemm_wide(const qpal_tcq_job *jobs, int njobs, int n, int S, int KV1, int KV2, void *stream);
 
+/* THE SAME FOR THE VQ/SQ (TENSOR-CORE PACKING) LAYERS (csrc/lut_gemm_wide.h): 129 <= n <= 256 batch rows, njobs in
+ * 1 .. 4 jobs that share x, one (bits, vec) for the launch: vec 1 at 2 .. 8 bits, vec 2 at 2 .. 12 bits (qpal_lut_tc_gemv's
+ * eighteen codecs).  For job j, b < n and row < m:
+ *   out[b][row] (+)= (sum_c W[row][c] x[b][c]) * wscale[row] * oscale
+ * with qpal_lut_tc_gemv_multi's meaning of the job fields it honours: out / ldo, qweight, x (fp16 [n][k], ALREADY rotated, the
+ * same pointer in every job), lut (every job its own: a workgroup rebuilds its codebook image where its next item belongs to a
+ * job with another lut), m, k (the same in every job), wscale, oscale, accumulate.  out_zeroed is ignored; the K split, the
+ * clearing kernel in front of a split launch and the fp32 atomics are qpal_tcq_gemm_wide's, and so is what that means for
+ * reproducibility.  Rows >= n of out are never written.  No rotation, RMSNorm or activation: x_had, x_su, x_f32, x_rms_eps,
+ * x_rms_w, act_out, act_su, x_hadk and x_K must be zero (QPAL_E_PARAM).
+ * Codes, decided before any device access and in this order: jobs NULL: QPAL_E_NULL; njobs outside 1 .. 4, n outside 129 .. 256,
+ * k not a multiple of 128, n * k * 2 >= 2^31, m % 32 != 0, jobs of different k, 0 < ldo < m: QPAL_E_SHAPE; a (bits, vec) outside
+ * the eighteen: QPAL_E_PARAM; a NULL out / qweight / x / lut: QPAL_E_NULL; a fusion field: QPAL_E_PARAM; x not 16-byte, wscale not
+ * 2-byte, the others not 4-byte aligned: QPAL_E_ALIGN.  What it refuses runs as passes of qpal_lut_tc_gemv_multi
+ * (qpalette_amd.linear.wide_gemm does that).  Never synchronises (capturable).                                               */
+int qpal_lut_gemm_wide(const qpal_lut_job *jobs, int njobs, int n, int bits, int vec, void *stream);
+
 /* THE SECOND ROUTER AND SHARED EXPERTS (csrc/moe_route.hip; moe.reference_route_ex restates each step in float64).
  * qpal_moe_route_ex is qpal_moe_route's argument list (renorm moves into the struct) plus a qpal_moe_router.  Per row:
  *   1. x̂ and logits are exactly as in qpal_moe_route.  The existing router_bias still adds to the logits.

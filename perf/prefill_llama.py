@@ -44,6 +44,8 @@ def main(argv=None, quiet=False):
     ap.add_argument("--chunk", type=int, default=128)
     ap.add_argument("--wide", type=int, default=None, metavar="R",
                     help="also time Prefill(wide=R), 129 .. 256: chunks of R rows in one weight pass (DESIGN.md §39), same call")
+    ap.add_argument("--wide-lut-sliced", action="store_true",
+                    help="with --wide: also time Prefill(wide=R) with the VQ/SQ layers on multi_gemv slices, the path before DESIGN.md §43")
     ap.add_argument("--wide-attention", action="store_true",
                     help="with --wide: also time Prefill(wide=R, wide_attention=True), one attention call per wide chunk (DESIGN.md §41)")
     ap.add_argument("--slots", type=int, default=1, help="sequences the caches hold (B of a DecodeStep over them)")
@@ -185,6 +187,15 @@ def main(argv=None, quiet=False):
                 ms_w = time_graph(lambda: pfw(tokens, slot=slot, pos0=0), args.iters, dev)
                 note(N, "wide prefill ms", ms_w)
                 res.update({"wide": args.wide, "ms_prefill_wide": ms_w, "prompt_tokens_per_s_prefill_wide": N / ms_w * 1e3})
+            if pfw is not None and args.wide_lut_sliced:  # the same, the VQ/SQ layers on multi_gemv slices as before DESIGN.md §43
+                real = qp.linear._wide_jobs
+                qp.linear._wide_jobs = lambda grp: None if isinstance(grp[0], qp.VQLinearPackTensorCore) else real(grp)
+                try:
+                    ms_ws = time_graph(lambda: pfw(tokens, slot=slot, pos0=0), args.iters, dev)
+                finally:
+                    qp.linear._wide_jobs = real
+                note(N, "wide prefill, LUT layers sliced, ms", ms_ws)
+                res.update({"ms_prefill_wide_lut_sliced": ms_ws, "prompt_tokens_per_s_prefill_wide_lut_sliced": N / ms_ws * 1e3})
             if pfwa is not None:
                 res["next_token_wide_attention"] = int(pfwa(tokens, slot=slot, pos0=0))
                 res["wide_attention_vs_chunk_max_abs_diff_final_norm"] = float((pfwa.hidden().float() - got_h).abs().max())

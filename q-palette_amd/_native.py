@@ -171,6 +171,7 @@ _SIGNATURES = {
     "qpal_moe_gemm": [_P, ctypes.c_long, _I, ctypes.POINTER(MoeProj), _I, _P, ctypes.c_long, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I,
                       _F, _I, _P],
     "qpal_tcq_gemm_wide": [ctypes.POINTER(TcqJob), _I, _I, _I, _I, _I, _P],
+    "qpal_lut_gemm_wide": [ctypes.POINTER(LutJob), _I, _I, _I, _I, _P],
     "qpal_moe_route_ex": [_P, ctypes.c_long, _P, _F, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P,
                           ctypes.POINTER(MoeRouter), _P],
     "qpal_moe_combine_shared": [_P, ctypes.c_long, _P, ctypes.c_long, _P, _P, _P, ctypes.c_long, _P, _I, _I, _I, _I, _I, _P],

@@ -275,14 +275,16 @@ struct TcqCodec {
 //   VEC == 1 : 2*BITS dwords per lane; code q = 2j+e at LE bit r*32B + G*8B + q*B.  For BITS <= 6 the
 //              two codes of a half2 are adjacent, so one gather in a pair table of 2^(2B) half2
 //              entries decodes both (the reference does this for BITS <= 4 only: LOAD_TYPE::DUP).
-template <int BITS, int VEC>
+// CAPLOG2: log2 of the largest image in bytes — 17 (128 KiB) everywhere but in the wide GEMM (lut_gemm_wide.hip: 16, beside two
+// half tiles of 256 rows), where the codebooks of 2^10 .. 2^12 entries keep 16 / 8 / 4 copies instead of 32 / 16 / 8.
+template <int BITS, int VEC, int CAPLOG2 = 17>
 struct LutCodec {
     static_assert(VEC == 1 || VEC == 2, "tensor-core format has vec_sz 1 or 2");
     static constexpr bool PAIR = (VEC == 1 && BITS <= 6);
     static constexpr int NW = (VEC == 2) ? BITS : 2 * BITS;
     static constexpr bool kNeedsNext = false;
     static constexpr int IDXBITS = (VEC == 2) ? BITS : (PAIR ? 2 * BITS : BITS);
-    static constexpr int LOG2C = (15 - IDXBITS) < 5 ? (15 - IDXBITS) : 5;  // <= 128 KiB
+    static constexpr int LOG2C = (CAPLOG2 - 2 - IDXBITS) < 5 ? (CAPLOG2 - 2 - IDXBITS) : 5;  // <= 2^CAPLOG2 bytes (128 KiB)
     static constexpr int C = 1 << LOG2C;
     static constexpr int LDS_DWORDS = (1 << IDXBITS) * C;
     static_assert(LOG2C >= 2, "table build writes 4 copies per 16-byte chunk");

@@ -236,10 +236,29 @@ def multi_gemv(layers, x, outs=None, outs_zeroed=False, prezero=None, wscales=No
 
 
 def _wide_jobs(grp):
-    """(jobs, S, KV1, KV2) of ops.tcq_gemm_wide for layers of one codec key, or None where qpal_tcq_gemm_wide refuses them (its
-    checks, restated: S = 9, KV 2..8, m % 32 == 0, whole 128-column steps in every stream)"""
+    """(entry, jobs, codec arguments) of ops.tcq_gemm_wide / ops.lut_gemm_wide for layers of one codec key, or None where the wide
+    entry points refuse them (their checks, restated: S = 9, KV 2..8 or a (bits, vec) of the tensor-core LUT packing; m % 32 == 0,
+    whole 128-column steps in every stream)"""
+    from .. import ops
+
     first = grp[0]
     kind, k = _codec_key(first)[0], first.in_features
+    if kind == "lut_tc":
+        if any(l.out_features % 32 or not l.qweight.is_cuda for l in grp) or k % 128:
+            return None
+        # Measured (DESIGN.md §43.5, profiles/lut_gemm_wide.json): every class faster in ONE launch (x 1.21 .. 2.35) but §39.6's
+        # few-rows class — ONE layer whose K the launch cuts 16 ways or more (the down projection of Llama-8B) — where the codec's
+        # sliced path is two 128-row passes of one gather per pair: x 1.00 .. 1.03 for sq_dup 4, vq2 6 and vq2 8, inside the spread
+        # of a repeated pair, so those stay on the slices.  With four 64-row passes (x 1.38 .. 1.48) or two gathers per pair
+        # (sq 8: x 1.14) the wide launch wins there too.
+        nblk, T, lsk = sum(-(-l.out_features // 256) for l in grp), k // 128, 0
+        while (nblk << lsk) < 192 and (T >> (lsk + 1)) >= 4 and lsk < 5:
+            lsk += 1
+        two_gathers = first.vec_sz == 1 and first.lut_bits >= 7
+        if len(grp) == 1 and lsk >= 4 and first.max_fused_batch == 128 and not two_gathers:
+            return None
+        # (each job carries its own codebook: the kernel rebuilds its image at a job boundary)
+        return ops.lut_gemm_wide, [(l.qweight, l.lut, l.out_features) for l in grp], (first.lut_bits, first.vec_sz)
     if kind not in ("tcq", "tcombt") or first.tlut_bits != 9 or any(l.out_features % 32 for l in grp):
         return None
     kvs = (first.KV, 0) if kind == "tcq" else tuple(first.KV)
@@ -253,14 +272,15 @@ def _wide_jobs(grp):
     if len(grp) == 1 and lsk >= 4:
         return None
     if kind == "tcq":
-        return [(l.trellis, None, l.tlut, l.out_features) for l in grp], 9, kvs[0], 0
-    return [(l.trellis1, l.trellis2, l.tlut, l.out_features) for l in grp], 9, kvs[0], kvs[1]
+        return ops.tcq_gemm_wide, [(l.trellis, None, l.tlut, l.out_features) for l in grp], (9, kvs[0], 0)
+    return ops.tcq_gemm_wide, [(l.trellis1, l.trellis2, l.tlut, l.out_features) for l in grp], (9, kvs[0], kvs[1])
 
 
 def wide_gemm(layers, x, outs, wscales=None, oscale=1.0, accumulate=False):
     """outs[i] (+)= layers[i](x) * wscales[i] * oscale for 129 .. 256 rows of one ALREADY rotated fp16 input x [n, k]: layers of one
-    codec the wide kernel serves (tcq_* / tcomb_*_0.5 at tlut_bits 9) go out as ONE pass over their weights per group of up to 4
-    (qpal_tcq_gemm_wide); every other layer runs multi_gemv on row slices of at most 128 into the same outs.
+    codec the wide kernels serve (tcq_* / tcomb_*_0.5 at tlut_bits 9: qpal_tcq_gemm_wide; VQLinearPackTensorCore layers
+    of one (bits, vec): qpal_lut_gemm_wide, §43) go out as ONE pass over their weights per group of up to 4; every other layer
+    (VQLinearPackSIMT, comb_*, S >= 10) runs multi_gemv on row slices of at most 128 into the same outs.
     outs: fp32 [n, m_i] tensors (row stride >= m_i).  Returns outs."""
     from .. import ops
 
@@ -276,11 +296,14 @@ def wide_gemm(layers, x, outs, wscales=None, oscale=1.0, accumulate=False):
             ws = [wscales[i] for i in sub] if wscales is not None else None
             wide = _wide_jobs(grp)
             if wide is not None:
-                jobs, S, kv1, kv2 = wide
-                ops.tcq_gemm_wide(jobs, x2, S, kv1, kv2, outs=o, wscales=ws, oscale=oscale, accumulate=accumulate)
+                entry, jobs, codec = wide
+                entry(jobs, x2, *codec, outs=o, wscales=ws, oscale=oscale, accumulate=accumulate)
             else:
-                for r in range(0, n, 128):
-                    multi_gemv(grp, x2[r:r + 128], outs=[t[r:r + 128] for t in o], wscales=ws, oscale=oscale, accumulate=accumulate)
+                # (slices of the group's fused batch: 128 for the tensor-core-order layers that come here, 8 for a SIMT packing,
+                # whose 128-row slice multi_gemv refuses to write into outs)
+                step = min(128, min(l.max_fused_batch for l in grp))
+                for r in range(0, n, step):
+                    multi_gemv(grp, x2[r:r + step], outs=[t[r:r + step] for t in o], wscales=ws, oscale=oscale, accumulate=accumulate)
     return outs
 
 

@@ -455,6 +455,32 @@ def lut_tc_gemv_multi(layers, x, bits, vec, outs=None, outs_zeroed=False, prezer
                        accumulate=accumulate, act_outs=act_outs, act_su=act_su)
 
 
+def lut_gemm_wide(jobs, x, bits, vec, outs=None, wscales=None, oscale=1.0, accumulate=False):
+    """Up to 4 VQ/SQ (tensor-core packing) layers of one (bits, vec) on 129 .. 256 rows of one ALREADY rotated input in ONE pass over
+    the weights (C-ABI qpal_lut_gemm_wide).  jobs: list of (qweight, lut, m) — every layer its own codebook.
+    x: fp16 [n, k].  outs / wscales / oscale / accumulate as in tcq_gemm_wide.  Returns the outputs."""
+    n, k = x.shape
+    _chk(WIDE_MIN_BATCH <= n <= WIDE_MAX_BATCH, f"batch size must be in {WIDE_MIN_BATCH}..{WIDE_MAX_BATCH}")
+    _chk(x.dtype == torch.float16, "x must be fp16 (already rotated)")
+    _chk(outs is not None or not accumulate, "accumulate needs outs")
+    xh = _dev(x, "x")
+    if outs is None:
+        outs = _fresh_outs([j[2] for j in jobs], n, x.device)
+    cjobs = (nat.LutJob * len(jobs))()
+    keep = [xh]
+    for j, (qweight, lut, m) in enumerate(jobs):
+        q, cb = _lut_args(qweight, lut, m, k, bits, vec)
+        out = _out_arg(outs, j, n, m, x.device)
+        cjobs[j] = nat.LutJob(out=out.data_ptr(), qweight=q.data_ptr(), x=xh.data_ptr(), lut=cb.data_ptr(), m=m, k=k,
+                              wscale=_wscale_arg(wscales, j, m), oscale=float(oscale), ldo=_ldo(out, n, m),
+                              accumulate=1 if accumulate else 0)
+        keep += [q, cb]
+    with torch.cuda.device_of(x):
+        rc = nat.lib().qpal_lut_gemm_wide(cjobs, len(jobs), n, bits, vec, _stream(x))
+    nat.check(rc, "qpal_lut_gemm_wide")
+    return list(outs)
+
+
 def tc_to_simt(qweight_tc, m, k, bits, vec):
     """Device re-pack of a tensor-core-format qweight into the SIMT format
     (reference: lib/quantizer/quant_op.py:246-257 convert_tensor_core_to_simt)."""
